@@ -2,7 +2,7 @@
 """Headline benchmark: separated row-frames/s (+ RTF) of the offline separation sandwich
 waveform -> STFT -> BSRNN.forward -> iSTFT -> waveform on synthetic mixtures.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Workload (BASELINE.json metric config): per GPU R = 64 rows x 8 s @ 16 kHz
 (128 000 samples, T = 126 frames), K = 12 bands, fp32, weights and waveforms from the
@@ -16,6 +16,11 @@ One JSON line on rank 0 with the driver's contract fields plus
                 region, on the launch stream): achieved algorithmic rate vs gfx950 peak
   cpu_baseline  the reference's CPU path (stock torch CPU ops, oracle/bsrnn_torch_cpu.py) timed
                 on this box's host cores on a bounded sample, rank 0 at N = 1 only.
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned (the separated waveforms
+[rows, (T-1)*1024], float32) is written as DIR/separated.npy (DIR/separated_rank<r>.npy per rank at N > 1),
+so that two builds can be compared output for output on identical inputs.  At most 64 MB in all: beyond
+that a fixed seeded sample of rows (then of columns) is written.
 """
 import argparse
 import json
@@ -183,6 +188,29 @@ def cpu_baseline(sd, rows, n_samples, budget_s=12.0, max_iters=7):
             "seconds_per_pass": med}
 
 
+DUMP_BYTES = 64 * 10**6         # --dump-outputs: at most this much in all (every rank writes its share)
+
+
+def dump_output(dirname, name, arr, budget):
+    """Write arr [R, n] as dirname/name.npy (float32).  Beyond `budget` bytes: a fixed sample of rows, then of columns
+    (numpy default_rng(0), without replacement, in ascending order), the same for every run with the same arguments."""
+    arr = np.ascontiguousarray(arr, dtype=np.float32)
+    rec = {"file": name + ".npy", "shape": list(arr.shape)}
+    budget -= 1024                                # (the .npy header)
+    if arr.nbytes > budget:
+        R, n = arr.shape
+        keep_r = min(R, max(1, budget // (4 * n)))
+        keep_c = min(n, budget // (4 * keep_r))
+        rng = np.random.default_rng(0)
+        rows = np.sort(rng.choice(R, keep_r, replace=False))
+        cols = np.sort(rng.choice(n, keep_c, replace=False)) if keep_c < n else np.arange(n)
+        arr = np.ascontiguousarray(arr[np.ix_(rows, cols)])
+        rec["sample"] = {"rows": keep_r, "cols": keep_c, "how": "numpy default_rng(0).choice without replacement, sorted: rows, then columns"}
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), arr)
+    return rec
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -296,7 +324,10 @@ def main():
     ap.add_argument("--no-exact-f32", action="store_true", help="skip the exact-fp32 sub-record (a child process)")
     ap.add_argument("--no-train-step", action="store_true", help="skip the training-step sub-record (a child process)")
     ap.add_argument("--no-in-flight", action="store_true", help="skip the two / three batches in flight report item")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` with no launcher: become the launcher (N rank processes), before any GPU call
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -379,6 +410,10 @@ def main():
         model.separate(wave, out=out)
     barrier()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:                         # the last timed step's result, before the report items below reuse `out`
+        name = "separated" if world == 1 else "separated_rank%d" % rank
+        dumped = dump_output(args.dump_outputs, name, out.cpu().numpy(), DUMP_BYTES // world)
     dom_stages = model.stage_times(reset=True)
     n_sampled = (args.steps + SAMPLE - 1) // SAMPLE
     # per-stage table: a few extra steps with every stage bracketed (not part of `value`)
@@ -589,6 +624,8 @@ def main():
             line["exact_f32"] = f32_rec
         if train_rec is not None:
             line["train_step"] = train_rec
+        if dumped is not None:
+            line["dumped_outputs"] = dict(dumped, dir=args.dump_outputs, note="what the last timed step returned (rank 0's file at N > 1)")
         if world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(sd, args.rows, args.samples)
             line["cpu_baseline"] = cb

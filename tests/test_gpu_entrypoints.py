@@ -289,3 +289,29 @@ def test_validate_cli(tmp_path, sd_default):
     assert abs(loss - np.mean([r["loss"] for r in refs])) < 1e-4
     assert abs(sdr - np.mean([r["sdr"] for r in refs])) < 2e-3
     assert abs(sisdr - np.mean([r["sisdr"] for r in refs])) < 2e-3
+
+
+def test_bench_dumps_what_the_last_timed_step_returned(tmp_path, sd_default):
+    """bench.py --dump-outputs: the separated waveforms of the last timed step, against the oracle on the same synthetic batch;
+    a second run with another step count writes the same array bit for bit, and the result line reports the steps it timed."""
+    import json
+    from oracle import bsrnn_numpy as onp
+    from speechseparation_amd import weights
+    rows, n = 4, 32000
+    got = {}
+    for steps in (3, 5):
+        d = tmp_path / ("dump%d" % steps)
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--rows", str(rows),
+               "--samples", str(n), "--no-cpu-baseline", "--no-exact-f32", "--no-train-step", "--no-in-flight", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        assert line["dumped_outputs"]["file"] == "separated.npy" and "sample" not in line["dumped_outputs"]
+        got[steps] = np.load(d / "separated.npy")
+    ref = onp.separate(sd_default, weights.synth_waveform(rows, n, seed=1234))
+    assert got[3].dtype == np.float32 and got[3].shape == ref.shape
+    assert float(np.abs(got[3] - ref).max()) < 1e-4
+    assert np.array_equal(got[3], got[5])
