@@ -138,9 +138,6 @@ struct bsrnn_ctx {
     // Overlapped dual path (run_overlapped below; kernels.h, OvlProducer / OvlConsumer): the second band block runs beside the first
     // time-axis launch and the mask chain beside the second, on the context's first auxiliary stream.
     bool overlap_env = true;        // BSRNN_OVERLAP=0: one launch after the other on the caller's stream (A/B; bit-identical results)
-    int overlap_mode = 3;           // bit 0: the second band block beside the first time-axis launch; bit 1: the mask chain beside the second
-                                    // (BSRNN_OVERLAP=band | mask | 1 = both); bit 2 (BSRNN_OVERLAP=pub, measurement): the publishing / waiting
-                                    // launches one after the other on the caller's stream
     int overlap_sabotage = 0;       // BSRNN_OVERLAP=timeout (test hook): the producers publish nothing, the consumers give up after ~2 ms
     bool overlap_off = false;       // a consumer's wait expired once (range flag value 5): this context runs launch after launch from then on
     int* d_ovl = nullptr;           // [2 time blocks][OVL_HEAD ints: resident counter | progress word per time-axis workgroup]
@@ -155,22 +152,19 @@ struct bsrnn_ctx {
     // How a consumer launch is held back until every workgroup of its producer is resident: a one-wave gate kernel that spins on the
     // resident counter (default).  A resident foreign wave costs a band launch its pairing (its partners sit 8 ids apart and complete inside
     // one round of 512 slots; with 511 the last eight pairs straddle two rounds: +18 us), so the gates are kept off the band launches'
-    // dispatch by events (fork in front of gate 0, a mid event between band 1 and gate 1).  BSRNN_OVL_GATE=cp (measured and rejected,
-    // profiles/r04_gate_kernel_vs_cp.txt): hipStreamWaitValue32 on 8-byte signal words - on this runtime not a command-processor wait but
-    // a blit kernel (__amd_rocclr_streamOpsWait) that spins so hard that the time-axis launch beside it takes 3x as long (1.37 ms per step).
-    int* ovl_sig[2] = {nullptr, nullptr};
+    // dispatch by events (fork in front of gate 0, a mid event between band 1 and gate 1).  (A stream wait on signal memory instead of the
+    // gate kernel was measured and rejected, profiles/r04_gate_kernel_vs_cp.txt: on this runtime hipStreamWaitValue32 is a blit kernel that
+    // spins so hard that the time-axis launch beside it takes 3x as long.)
     hipEvent_t ev_ovl_mid = nullptr;
 
-    // concurrent row blocks of one call (bsrnn_separate)
-    // BSRNN_PARTS / BSRNN_PART_LAG.  0 = automatic: two row blocks on two streams once the batch's time-axis launch no longer fits one round of workgroups
-    // (bsrnn_separate: from 171 rows on at K = 12; until round 4, with four sequences per workgroup only, from 128 rows on), the
-    // second one stage behind the first: one block's matrix work fills the other's latency-bound time-axis LSTM (192 of 256
+    // concurrent row blocks of one call (bsrnn_separate): two row blocks on two streams once the batch's time-axis launch no longer fits one
+    // round of workgroups (bsrnn_separate: from 171 rows on at K = 12; until round 4, with four sequences per workgroup only, from 128 rows on),
+    // the second one stage behind the first: one block's matrix work fills the other's latency-bound time-axis LSTM (192 of 256
     // CUs, serial chain) and the ramps / tails of the fused chain launches (+8-12 % at 128 rows).  At the benchmark's 64 rows
-    // two blocks of 32 gain 3 % (1.157 -> 1.119 ms per step, BSRNN_PARTS=2) but every kernel then runs beside another
+    // two blocks of 32 gain 3 % (1.157 -> 1.119 ms per step) but every kernel then runs beside another
     // block's kernels: the per-kernel durations (and with them the roofline figure of bench.py) stop describing the kernel,
     // so one block there.  Rows are independent; tests/test_gpu_edges.py checks 64- and 130-row calls bit for bit against
     // their row blocks.  (That check first failed: see the note at the top of fft.hip.)
-    int n_parts = 0, part_lag = 1;
     hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
 };
@@ -468,7 +462,6 @@ struct Part {
     size_t state_slab;                                   // floats between the two Time blocks' slabs (uses C_total)
     const float* wave; float* wave_out; int64_t n;       // only for the fused sandwich
     const bsrnn_ctx::OvlTable* ovl;                      // non-null: the overlapped flow (run_overlapped) - producers publish, consumers wait
-    int ovl_mode;                                        // ... which of the two hand-overs (bsrnn_ctx::overlap_mode)
     int ovl_base;                                        // this call's epoch << OVL_EPOCH_SHIFT
     hipEvent_t band_done[2];                             // events the two band launches signal themselves when they complete (or null)
 };
@@ -539,7 +532,7 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
         const float* zi = parts && blk ? p.Z1 : p.Z0;
         if (ctx_pair(c)) {                        // both layers in one launch (A/B: BSRNN_BAND_PAIR=0)
             OvlConsumer oc = {nullptr, 0, 0, nullptr, 0, 2};
-            const bool cons = p.ovl && blk && (p.ovl_mode & 1);
+            const bool cons = p.ovl && blk;
             if (cons)                             // beside the first time-axis launch: tiles in the order their frames leave it
                 oc = OvlConsumer{c->d_ovl + OVL_HEAD, p.T, c->overlap_sabotage ? 200000 : OVL_SPIN_LIMIT, p.ovl->band_order, p.ovl_base, time_lstm_seqs(p.C * K) == 8 ? 3 : 2};
             launch_band_pair(zi, p.HB0, p.HB1, c->bandW16[blk][0], c->bandB[blk][0], c->bandW16[blk][1], c->bandB[blk][1], M, K, c->d_range, s,
@@ -565,8 +558,8 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
         const bool fused = time_lstm_fuses_fc();
         if (ctx_parts(c) && !band_block_is_small(M, K)) {
             OvlProducer op = {nullptr, nullptr, 0};
-            const bool prod = p.ovl && (p.ovl_mode & (blk ? 2 : 1));
-            if (prod) op = OvlProducer{c->ovl_sig[blk] ? c->ovl_sig[blk] : c->d_ovl + blk * c->ovl_stride, c->overlap_sabotage ? nullptr : c->d_ovl + blk * c->ovl_stride + OVL_HEAD, p.ovl_base};
+            const bool prod = p.ovl != nullptr;
+            if (prod) op = OvlProducer{c->d_ovl + blk * c->ovl_stride, c->overlap_sabotage ? nullptr : c->d_ovl + blk * c->ovl_stride + OVL_HEAD, p.ovl_base};
             launch_time_lstm(blk ? p.Z1 : p.Z0, blk ? p.Z0 : p.Z1, c->timeW[blk], c->timeW16[blk], c->timeB[blk],
                              p.state_in ? p.state_in + blk * p.state_slab : nullptr,
                              p.state_out ? p.state_out + blk * p.state_slab : nullptr, p.C, p.T, K, c->d_range, s,
@@ -597,7 +590,7 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
             g.desc = c->d_chain[CHAIN_MASK]; g.tasks = tt.d[CHAIN_MASK]; g.n_tasks = tt.n[CHAIN_MASK];
             g.M = M; g.Xin = p.Z0; g.ldx = KH; g.P = p.P; g.ldp = c->LDP; g.Xmul = p.Xf; g.ldm = c->LDP;
             g.Y = p.Yf; g.ldy = c->LDP; g.tap = p.tap; g.ldt = c->LDP; g.range_flag = c->d_range;
-            if (p.ovl && (p.ovl_mode & 2)) {      // beside the second time-axis launch: the earliest-ready heavy workgroups first
+            if (p.ovl) {                          // beside the second time-axis launch: the earliest-ready heavy workgroups first
                 g.tasks = p.ovl->mask_tasks; g.n_tasks = p.ovl->n_mask;
                 g.ovl_prog = c->d_ovl + c->ovl_stride + OVL_HEAD; g.ovl_T = p.T; g.ovl_K = K;
                 g.ovl_spin = c->overlap_sabotage ? 200000 : OVL_SPIN_LIMIT;
@@ -645,20 +638,6 @@ int ensure_ovl(bsrnn_ctx* c, int C, int T)
     if (!c->ev_ovl_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_ovl_fork, hipEventDisableTiming | hipEventDisableSystemFence));      // (device-side ordering only: no system-scope release on the record)
     if (!c->ev_ovl_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_ovl_join, hipEventDisableTiming | hipEventDisableSystemFence));
     if (!c->ev_ovl_mid) HIP_TRY(hipEventCreateWithFlags(&c->ev_ovl_mid, hipEventDisableTiming | hipEventDisableSystemFence));
-    static const bool want_cp = [] { const char* e = getenv("BSRNN_OVL_GATE"); return e && !strcmp(e, "cp"); }();
-    if (want_cp && !c->ovl_sig[0]) {
-        int can = 0;
-        if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, c->device) != hipSuccess) { can = 0; (void)hipGetLastError(); }
-        for (int b = 0; b < 2 && can; ++b) {
-            ++g_dbg[DBG_ALLOC];
-            if (hipExtMallocWithFlags((void**)&c->ovl_sig[b], 8, hipMallocSignalMemory) != hipSuccess || hipMemset(c->ovl_sig[b], 0, 8) != hipSuccess) {
-                (void)hipGetLastError();
-                for (int k = 0; k <= b; ++k) if (c->ovl_sig[k]) { (void)hipFree(c->ovl_sig[k]); c->ovl_sig[k] = nullptr; }
-                can = 0;                          // (the kernel gates take over)
-            }
-        }
-        if (c->ovl_sig[0]) c->ovl_resident_total[0] = c->ovl_resident_total[1] = 0;
-    }
     const int M = C * T, K = c->K, S = time_lstm_seqs(C * K), nwg = (C * K + S - 1) / S;
     const int stride = OVL_HEAD + ((nwg + 15) & ~15);
     if (stride > c->ovl_stride) {
@@ -667,7 +646,7 @@ int ensure_ovl(bsrnn_ctx* c, int C, int T)
         HIP_TRY(hipMalloc((void**)&c->d_ovl, (size_t)2 * stride * sizeof(int)));
         HIP_TRY(hipMemset(c->d_ovl, 0, (size_t)2 * stride * sizeof(int)));
         c->ovl_stride = stride;
-        if (!c->ovl_sig[0]) c->ovl_resident_total[0] = c->ovl_resident_total[1] = 0;       // (fresh counters; the epochs go on: fresh words are below every base)
+        c->ovl_resident_total[0] = c->ovl_resident_total[1] = 0;       // (fresh counters; the epochs go on: fresh words are below every base)
         ++c->gen;
     }
     const auto key = std::make_pair(C, T);
@@ -729,67 +708,38 @@ void run_overlapped(bsrnn_ctx* c, Part p, const bsrnn_ctx::OvlTable* tb, int fir
 {
     hipStream_t A = p.s, B = c->aux[0];
     p.ovl = tb;
-    p.ovl_mode = c->overlap_mode;
-    const bool band = p.ovl_mode & 1, mask = p.ovl_mode & 2, serial = p.ovl_mode & 4;
     Part pb = p;
-    if (!serial) pb.s = B;
-    const int S = time_lstm_seqs(p.C * c->K), nwg = (p.C * c->K + S - 1) / S, limit = OVL_SPIN_LIMIT;
+    pb.s = B;
+    const int S = time_lstm_seqs(p.C * c->K), nwg = (p.C * c->K + S - 1) / S;
     // this call's epoch (upper bits of every progress word it publishes or waits for) and the gates' targets (running totals)
     if (++c->ovl_epoch >= c->ovl_epoch_period || c->ovl_resident_total[0] > (1 << 30) || c->ovl_resident_total[1] > (1 << 30)) {   // start again: nothing in flight, every word zero
         (void)hipDeviceSynchronize();
         (void)hipMemset(c->d_ovl, 0, (size_t)2 * c->ovl_stride * sizeof(int));
-        for (int b = 0; b < 2; ++b) if (c->ovl_sig[b]) (void)hipMemset(c->ovl_sig[b], 0, 8);
         c->ovl_epoch = 1; c->ovl_resident_total[0] = c->ovl_resident_total[1] = 0;
     }
     p.ovl_base = pb.ovl_base = c->ovl_epoch << OVL_EPOCH_SHIFT;
-    if (band) c->ovl_resident_total[0] += nwg;
-    if (mask) c->ovl_resident_total[1] += nwg;
-    const bool cp = c->ovl_sig[0] != nullptr && !serial;
+    c->ovl_resident_total[0] += nwg;
+    c->ovl_resident_total[1] += nwg;
     // hold stream `s` until every workgroup of time launch `blk` of THIS call is resident
-    auto gate = [&](int blk, hipStream_t s) {
-        if (cp) (void)hipStreamWaitValue32(s, c->ovl_sig[blk], (uint32_t)c->ovl_resident_total[blk], hipStreamWaitValueGte, 0xffffffffu);
-        else launch_ovl_gate(c->d_ovl + blk * c->ovl_stride, c->ovl_resident_total[blk], c->d_range, limit, s);
-    };
-    const bool ev_in_launch = band && !cp && !serial;
-    p.band_done[0] = pb.band_done[0] = ev_in_launch ? c->ev_ovl_fork : nullptr;
-    p.band_done[1] = pb.band_done[1] = ev_in_launch && mask ? c->ev_ovl_mid : nullptr;
+    auto gate = [&](int blk, hipStream_t s) { launch_ovl_gate(c->d_ovl + blk * c->ovl_stride, c->ovl_resident_total[blk], c->d_range, OVL_SPIN_LIMIT, s); };
+    p.band_done[0] = pb.band_done[0] = c->ev_ovl_fork;
+    p.band_done[1] = pb.band_done[1] = c->ev_ovl_mid;
     for (int st = first; st <= MS_BANDSPLIT; ++st) run_stage(c, p, st);
     run_stage(c, p, MS_BAND0);
+    // the fork event keeps gate 0 off band 0's dispatch, and gate 1 waits (event) until band 1 has been dispatched completely
+    (void)hipStreamWaitEvent(B, c->ev_ovl_fork, 0);              // (signalled by band 0's own dispatch: p.band_done)
+    run_stage(c, p, MS_TIME0);
+    gate(0, B);
+    run_stage(c, pb, MS_BAND1);                                  // (... and the mid event by band 1's)
+    run_stage(c, pb, MS_TIME1);
+    (void)hipStreamWaitEvent(A, c->ev_ovl_mid, 0);
+    gate(1, A);
+    run_stage(c, p, MS_MASK);
     // The auxiliary stream is joined on the host where something needs it (finish_call under the default range policy, bsrnn_sync, a stream
     // switch) or by an event for a call that returns LSTM state; a join event in front of the iSTFT cost the caller's stream a 6 us gap.
-    auto join = [&]() {
-        if (serial) return;
-        if (p.state_out) { (void)hipEventRecord(c->ev_ovl_join, B); (void)hipStreamWaitEvent(A, c->ev_ovl_join, 0); }
-        else c->ovl_unjoined = true;
-    };
-    if (band) {
-        // command-processor gates: the auxiliary stream is ordered behind the caller's by the words alone (no fork).  Kernel gates: the
-        // fork event keeps gate 0 off band 0's dispatch, and gate 1 waits (event) until band 1 has been dispatched completely.
-        if (!cp && !serial) (void)hipStreamWaitEvent(B, c->ev_ovl_fork, 0);          // (signalled by band 0's own dispatch: p.band_done)
-        run_stage(c, p, MS_TIME0);
-        gate(0, pb.s);
-        run_stage(c, pb, MS_BAND1);                                                  // (... and the mid event by band 1's)
-        run_stage(c, pb, MS_TIME1);
-        if (mask) {
-            if (!cp && !serial) (void)hipStreamWaitEvent(A, c->ev_ovl_mid, 0);
-            gate(1, A);
-        } else if (!serial) { (void)hipEventRecord(c->ev_ovl_join, B); (void)hipStreamWaitEvent(A, c->ev_ovl_join, 0); }      // (the mask chain does not wait per workgroup)
-        run_stage(c, p, MS_MASK);
-        if (mask) join();
-    } else {                                      // the mask chain alone beside the second time-axis launch
-        run_stage(c, p, MS_TIME0);
-        run_stage(c, p, MS_BAND1);
-        if (!serial) { (void)hipEventRecord(c->ev_ovl_fork, A); (void)hipStreamWaitEvent(B, c->ev_ovl_fork, 0); }           // (time 1 reads what band 1 wrote)
-        run_stage(c, pb, MS_TIME1);
-        gate(1, A);
-        run_stage(c, p, MS_MASK);
-        join();
-    }
+    if (p.state_out) { (void)hipEventRecord(c->ev_ovl_join, B); (void)hipStreamWaitEvent(A, c->ev_ovl_join, 0); }
+    else c->ovl_unjoined = true;
     for (int st = MS_MASK + 1; st <= last; ++st) run_stage(c, p, st);
-    // A command-processor wait has no time-out of its own: if a launch of this call failed, its producer may never arrive - release the waits
-    // from the host (the caller gets the launch error through hipGetLastError at the end of the entry point).
-    if (cp && hipPeekAtLastError() != hipSuccess)
-        for (int b = 0; b < 2; ++b) *(volatile int*)c->ovl_sig[b] = c->ovl_resident_total[b];      // (signal memory is host-visible)
 }
 // host-side join of the auxiliary stream with the last overlapped call (see run_overlapped)
 static int ovl_join_host(bsrnn_ctx* c)
@@ -812,8 +762,7 @@ static const bsrnn_ctx::OvlTable* ovl_table(const bsrnn_ctx* c, int C, int T, hi
 int run_model(bsrnn_ctx* c, const float* Xf, float* Yf, float* tap, int C, int T,
               const float* state_in, float* state_out, hipStream_t s)
 {
-    static const bool gemv_on = [] { const char* e = getenv("BSRNN_GEMV"); return !(e && !strcmp(e, "0")); }();
-    c->small_rows = gemv_on && C * T <= GEMV_MAX_FRAME_ROWS;
+    c->small_rows = C * T <= GEMV_MAX_FRAME_ROWS;
     Part p = make_part(c, 0, C, T, s);
     p.Xf = Xf; p.Yf = Yf; p.tap = tap;
     p.state_in = state_in; p.state_out = state_out;
@@ -980,13 +929,8 @@ int bsrnn_create(int device, const int32_t* widths, int32_t n_bands, bsrnn_ctx**
     }
     if (const char* e = getenv("BSRNN_OVERLAP")) {
         c->overlap_env = strcmp(e, "0") != 0; c->overlap_sabotage = !strcmp(e, "timeout");
-        if (!strcmp(e, "band")) c->overlap_mode = 1;
-        if (!strcmp(e, "mask")) c->overlap_mode = 2;
-        if (!strcmp(e, "pub")) c->overlap_mode = 3 | 4;
     }
     if (const char* e = getenv("BSRNN_OVL_EPOCHS")) c->ovl_epoch_period = std::max(2, std::min(1 << 18, atoi(e)));
-    if (const char* e = getenv("BSRNN_PARTS")) c->n_parts = std::max(0, std::min(MAX_PARTS, atoi(e)));
-    if (const char* e = getenv("BSRNN_PART_LAG")) c->part_lag = std::max(0, std::min((int)MS_COUNT, atoi(e)));
 
     // FFT tables in double precision
     std::vector<float> t(2 * 1024 + 2 * 1025 + 2048 + 1024 + 1024 + 16);
@@ -1044,7 +988,6 @@ static void destroy_now(bsrnn_ctx* c)
     if (c->ev_ovl_join) (void)hipEventDestroy(c->ev_ovl_join);
     free_ovl_tables(c);
     if (c->d_ovl) (void)hipFree(c->d_ovl);
-    for (int b = 0; b < 2; ++b) if (c->ovl_sig[b]) (void)hipFree(c->ovl_sig[b]);
     if (c->ev_ovl_mid) (void)hipEventDestroy(c->ev_ovl_mid);
     if (c->d_ws) (void)hipFree(c->d_ws);
     if (c->d_tap) (void)hipFree(c->d_tap);
@@ -1203,7 +1146,7 @@ int bsrnn_commit_params(bsrnn_ctx* c)
         // per-band costs better (measured 2.75 vs 2.79 ms per step), so it is the default.
         // The split-precision kernels do 2-3x less matrix-pipe work per tile and are bound by the CU's load
         // path instead: there the 128-wide tile (2/3 of the bytes per flop) wins (tools/gemm_planes_bench.hip).
-        const int tn = (maxn > 64 && (gmode != GEMM_F32 || getenv("BSRNN_GEMM_TILE128"))) ? 128 : 64;
+        const int tn = (maxn > 64 && gmode != GEMM_F32) ? 128 : 64;
         c->tile_n[slot] = tn;
         std::vector<int> order;
         for (int ji = j0; ji < (int)jobs.size(); ++ji) order.push_back(ji);
@@ -1316,7 +1259,7 @@ int bsrnn_commit_params(bsrnn_ctx* c)
             // ... and the other bands of the 64-row class (the 514-wide band: 33 feature tiles of 16, ragged) on FOUR row tiles of 16: the same 64
             // rows, but two feature tiles' fragments per k-step and four k-steps in flight per wave (128 KB per CU instead of the 64 KB the
             // two-row-tile 32 x 32 body has registers for, which held its K loops at 48 GB/s per CU against the 70 the fill path gives:
-            // profiles/r03_chain_trace.txt); BSRNN_CHAIN_NO64=1 keeps them on the 32 x 32 geometry
+            // profiles/r03_chain_trace.txt)
             bool try64 = false;
             if (try48 || try80) {
                 int rt16 = try48 ? 3 : 5, ctr = try48 ? 6 : 3;
@@ -1329,7 +1272,7 @@ int bsrnn_commit_params(bsrnn_ctx* c)
                     maxft = imax(maxft, FT); nb48 += 16 * FT;
                     whole = whole && ld[l].N % 16 == 0;
                 }
-                if (try80 && !(whole && maxft % 8 == 0 && maxft <= 8 * ctr && 2 * u48 * (16 * rt16) * 16 <= CHAIN_LDS_EX) && !getenv("BSRNN_CHAIN_NO64")) {
+                if (try80 && !(whole && maxft % 8 == 0 && maxft <= 8 * ctr && 2 * u48 * (16 * rt16) * 16 <= CHAIN_LDS_EX)) {
                     try64 = true; rt16 = 4; ctr = 5;
                 }
                 if (2 * u48 * (16 * rt16) * 16 <= CHAIN_LDS_EX && maxft <= 8 * ctr && nb48 * 4 <= CHAIN_LDS_BIAS && (try48 || try64 || (whole && maxft % 8 == 0))) {
@@ -1994,10 +1937,10 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
     // Rows are independent, so the batch is cut into `parts` contiguous row blocks that run the whole
     // stage sequence concurrently on separate streams: the ramps, tails and latency-bound stages of
     // one block (e.g. the time-axis LSTM occupies 192 of 256 CUs) overlap matrix work of the other.
-    // Part j starts `lag` stages behind part j-1 so that they sit in different stages.
-    // (automatic: one block while the time-axis launch of the whole batch is one round of workgroups - eight sequences each from 1 024 sequences on -,
+    // Part j starts one stage behind part j-1 so that they sit in different stages.
+    // (one block while the time-axis launch of the whole batch is one round of workgroups - eight sequences each from 1 024 sequences on -,
     //  two from there: 128 / 160 rows 1.75 / 2.26 -> 1.73 / 2.18 ms with one block, 192 / 256 rows 2.59 / 3.43 ms with two against 2.72 / 3.47)
-    int parts = c->n_parts > 0 ? c->n_parts : (R >= 128 && ((int64_t)R * c->K + time_lstm_seqs(R * c->K) - 1) / time_lstm_seqs(R * c->K) > device_cus() ? 2 : 1);
+    int parts = R >= 128 && ((int64_t)R * c->K + time_lstm_seqs(R * c->K) - 1) / time_lstm_seqs(R * c->K) > device_cus() ? 2 : 1;
     if (R < 2 * parts || (int64_t)R * T < 2048) parts = 1;
     if (parts > 1 && (rc = ensure_streams(c, parts))) return rc;
     Part pt[MAX_PARTS];
@@ -2022,10 +1965,9 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
         }
         const bsrnn_ctx::OvlTable* tb = parts == 1 ? ovl_table(c, R, T, s) : nullptr;
         if (tb) run_overlapped(c, pt[0], tb, MS_STFT, MS_ISTFT);      // the dual path overlapped on the context's auxiliary stream
-        const int lag = c->part_lag;
-        for (int step = 0; !tb && step < MS_COUNT + lag * (parts - 1); ++step)
+        for (int step = 0; !tb && step < MS_COUNT + parts - 1; ++step)
             for (int j = 0; j < parts; ++j) {
-                const int st = step - lag * j;
+                const int st = step - j;
                 if (st >= 0 && st < MS_COUNT) run_stage(c, pt[j], st);
             }
         if (parts > 1)

@@ -171,8 +171,6 @@ static int resident_slots(const void* kernel)
 }
 static int frames_per_workgroup(int units, int rows, int slots, int extra)
 {
-    static const int forced = [] { const char* e = getenv("BSRNN_FFT_RUN"); return e ? atoi(e) : 0; }();      // measurement / debugging knob
-    if (forced > 0) return forced;
     int best = 4;
     long best_cost = -1;
     for (int L = 16; L >= 4; --L) {
@@ -187,12 +185,8 @@ static int frames_per_workgroup(int units, int rows, int slots, int extra)
 // One workgroup transforms `sch` consecutive frames of one row.  Frames overlap by half: the thread that owns complex
 // samples c + 512, c + 768 of frame t owns c, c + 256 of frame t + 1, so only the new half is loaded per frame
 // (requested before the FFT passes of the current frame) and the raw samples stay in registers.
-#ifndef FFT_OCC_STFT
-#define FFT_OCC_STFT 4            // waves per SIMD (= workgroups per CU) the offline STFT is compiled for (A/B: tools/fft_variants.sh)
-#endif
-#ifndef FFT_OCC_ISTFT
-#define FFT_OCC_ISTFT 4
-#endif
+constexpr int FFT_OCC_STFT = 4;     // waves per SIMD (= workgroups per CU) the offline STFT is compiled for
+constexpr int FFT_OCC_ISTFT = 4;    // ... and the offline iSTFT
 template <bool ZERO_PAD>      // ZERO_PAD: samples outside [0, n) are zeros instead of reflections (the adjoint of the iSTFT, below)
 __global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_kernel(FftTables tb, const float* __restrict__ wave, float* __restrict__ X,
                                                    int64_t n, int T, int sch)

@@ -41,15 +41,14 @@ typedef float v16f __attribute__((ext_vector_type(16)));
 #ifndef GEMM_BK
 #define GEMM_BK 32
 #endif
-constexpr int BM = 128, BK = GEMM_BK, LDS_STRIDE = BK + 4, MCHUNK_MAX = 2;
+constexpr int BM = 128, BK = GEMM_BK, LDS_STRIDE = BK + 4, CHUNK_MTILES_MAX = 2;
 // m-tiles per XCD-pinned chunk: fewer for small batches so that all eight XCDs still get work.  The cap was 8 for the
 // fp32 kernel; with the split-precision kernels (3x less time per tile, same bytes) a chunk of 2 m-tiles keeps its
 // activation rows resident in the XCD's L2 across all column tiles and measures 2.5 % faster (sweep 1/2/3/4/8/16).
 static inline int gemm_mchunk(int m_tiles)
 {
-    static const int cap = [] { const char* e = getenv("BSRNN_GEMM_MCHUNK"); const int v = e ? atoi(e) : MCHUNK_MAX; return v < 1 ? 1 : v; }();   // measurement knob
     const int c = (m_tiles + 7) / 8;
-    return c < 1 ? 1 : (c > cap ? cap : c);
+    return c < 1 ? 1 : (c > CHUNK_MTILES_MAX ? CHUNK_MTILES_MAX : c);
 }
 static_assert(BK == 32 || BK == 64, "BK");
 #ifndef GEMM_OCC64

@@ -8,8 +8,11 @@
 //               that leaves the kernel are fp32;
 //   *_kernel    ("f32")  exact fp32 on v_mfma_f32_16x16x4_f32 / 4x4x1.
 // fc_in (Linear 64->64, no activation) is folded into W_ih of layer 0 on the host
-// (api.hip: W' = W_ih W_in, b' = W_ih b_in + b_ih + b_hh, in double), the trailing fc + residual
-// runs as one grouped-GEMM launch (gemm.hip, EPI_RES).
+// (api.hip: W' = W_ih W_in, b' = W_ih b_in + b_ih + b_hh, in double).  The trailing fc + residual of a
+// block: by default the second band layer of the pair launch writes the two directions' shares of the
+// band block's fc and the time-axis launch adds them and the residual while it stages its input, and the
+// time kernel forms its own block's fc (FUSE); BSRNN_BAND_FC=gemm, the pair launch's fallback, BSRNN_GEMM=f32
+// and the exact-fp32 kernels run it as one grouped-GEMM launch (gemm.hip, EPI_RES).
 #include "kernels.h"
 #include <hip/hip_ext.h>
 
@@ -18,31 +21,12 @@
 #include <cstring>
 #include <type_traits>
 
-#ifndef BAND_NLDS
-#define BAND_NLDS 2                 // second-piece weight blocks of the 128-input layer kept in LDS (3: 226 VGPRs, 2: 242, 1: 254)
-#endif
-#ifndef BAND_NLDS64
-#define BAND_NLDS64 0               // measurement: second-piece weight blocks of the 64-input layer kept in LDS (2: <= 168 VGPRs, three workgroups per CU)
-#endif
-#ifndef BAND_OCC64
-#define BAND_OCC64 2                // measurement: waves per SIMD requested for the 64-input layer
-#endif
-#ifndef PART_DBG
-#define PART_DBG 0                  // measurement only (tools/band_parts_check.hip): 1 no fc MFMAs, 2 no fclds array (fragments = garbage), 4 no tail
-#endif
-#ifndef BAND_NO_PLANES
-#define BAND_NO_PLANES 0            // measurement only: 1 = fp32 instead of fp16 planes between the two band layers (A/B, tools/precision_dual_path.py)
-#endif
-#ifndef OVL_DBG
-#define OVL_DBG 0                   // measurement only (overlapped dual path, tools/overlap_variants.sh): 1 a consumer tile sleeps ~20 us behind its wait, 2 the pair hand-over acquires at agent scope, 4 the time kernel's summed rows are stored write-through
-#endif
-#ifndef BAND_ABL
-#define BAND_ABL 0                // measurement only (tools/lstm_h2_trace.hip): bit 1 no x staging, 2 no global h store, 4 no h publish, 8 no step barrier, 16 no MFMAs, 32 no transcendentals
-#endif
-
 namespace bsrnn {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
+
+constexpr int BAND_NLDS = 2;        // second-piece weight blocks of the 128-input layer kept in LDS (3: 226 VGPRs, 2: 242, 1: 254)
+constexpr int BAND_NLDS64 = 0;      // second-piece weight blocks of the 64-input layer kept in LDS (2: <= 168 VGPRs, three workgroups per CU)
 
 __device__ __forceinline__ float fast_sigmoid(float x)
 {
@@ -55,12 +39,10 @@ __device__ __forceinline__ float fast_tanh(float x)
 }
 __device__ __forceinline__ v4f exp2_4(const v4f x)
 {
-    if (BAND_ABL & 32) return x * 0.5f;
     return (v4f){__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1]), __builtin_amdgcn_exp2f(x[2]), __builtin_amdgcn_exp2f(x[3])};
 }
 __device__ __forceinline__ v4f rcp4(const v4f x)
 {
-    if (BAND_ABL & 32) return x * 0.25f;
     return (v4f){__builtin_amdgcn_rcpf(x[0]), __builtin_amdgcn_rcpf(x[1]), __builtin_amdgcn_rcpf(x[2]), __builtin_amdgcn_rcpf(x[3])};
 }
 
@@ -78,9 +60,7 @@ __device__ __forceinline__ v4f rcp4(const v4f x)
 // c lives in registers; h_t goes to LDS (next step's A operand) and from there, coalesced,
 // to global.  x_{t+1} is prefetched into registers during the MFMAs of step t.
 // =====================================================================================
-#ifndef BAND_OCC
-#define BAND_OCC 2            // waves per SIMD requested for the band kernel (2 workgroups per CU)
-#endif
+constexpr int BAND_OCC = 2;         // waves per SIMD requested for the band kernels (2 workgroups per CU)
 template <int IN>
 __global__ __launch_bounds__(256, BAND_OCC) void band_lstm_kernel(const float* __restrict__ xin, float* __restrict__ hout,
                                                         const float* __restrict__ wpk, const float* __restrict__ bias,
@@ -235,7 +215,7 @@ struct BandLds {
     static constexpr int W2 = HPL + 2 * 2 * HID * 16 * 2;
     static constexpr int BIAS = W2 + (NLDS ? 4 * NLDS * 4 * 64 : 1) * 16;
     static constexpr int FC = BIAS + (4 * HID + HID) * 4;          // gate biases [4][64] + the fc bias of the forward share [64]
-    static constexpr int BYTES = FC + (PART && !(PART_DBG & 2) ? 4 * 2 * 2 * 64 : 1) * 16;
+    static constexpr int BYTES = FC + (PART ? 4 * 2 * 2 * 64 : 1) * 16;
 };
 
 // One layer of one (tile of 16 sequences, direction): the body of band_lstm_h2_kernel and of both phases of band_pair_h2_kernel.
@@ -252,8 +232,8 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
     auto stamp = [&](int k) { if (TRACE) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); tp[k] += now - tq; tq = now; } };
     if (TRACE) tq = __builtin_amdgcn_s_memrealtime();
     constexpr int NBX = IN / 32, NBH = HID / 32, NB = NBX + NBH;
-    constexpr bool PLANES_IN = IN == 2 * HID && !BAND_NO_PLANES;    // layer 1: x arrives as the fp16 planes layer 0 wrote
-    constexpr bool PLANES_OUT = IN == HID && !BAND_NO_PLANES;       // layer 0: h leaves as fp16 planes (read by layer 1 only)
+    constexpr bool PLANES_IN = IN == 2 * HID;    // layer 1: x arrives as the fp16 planes layer 0 wrote
+    constexpr bool PLANES_OUT = IN == HID;       // layer 0: h leaves as fp16 planes (read by layer 1 only)
     // blocks whose second weight piece lives in LDS instead of VGPRs (counted from the last k block): the 128-input
     // layer would need 192 weight + 32 accumulator registers; with the two W_hh blocks in LDS it is 160 + 32 and
     // compiles without scratch at 242 VGPRs (measured with spills: 1.9 us of every 3.5 us step in reloads)
@@ -290,7 +270,7 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
     if (PART) {
         // W_fc as [4 tile][4 k block][2 piece][64 lane][8] (api.hip): tile = this wave's 16 output features, k blocks 2 dir + b
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fclds[(PART_DBG & 2) ? 0 : (wave * 4 + i) * 64 + lane] = wfc[((size_t)(wave * 4 + 2 * dir) * 2 + i) * 64 + lane];
+        for (int i = 0; i < 4; ++i) fclds[(wave * 4 + i) * 64 + lane] = wfc[((size_t)(wave * 4 + 2 * dir) * 2 + i) * 64 + lane];
     }
     // The loads above are still in flight when the step loop starts, and the compiler's wait-count bookkeeping merges
     // that state into the loop (it waited for vmcnt(0), i.e. for the x prefetch of the same step, in front of the last
@@ -362,7 +342,6 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
 #pragma unroll
         for (int gte = 0; gte < 4; ++gte)
             w2[gte] = b >= NB - NLDS ? __builtin_bit_cast(h8v, w2lds[((wave * NLDS + (b - (NB - NLDS))) * 4 + gte) * 64 + lane]) : w[b][gte][1];
-        if (BAND_ABL & 16) { asm volatile("" :: "v"(a0), "v"(a1), "v"(w2[0]), "v"(w2[1]), "v"(w2[2]), "v"(w2[3])); return; }
 #pragma unroll
         for (int gte = 0; gte < 4; ++gte)
             hi[gte] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[b][gte][0], a0, b == 0 ? *reinterpret_cast<const v4f*>(bias_l + gte * HID) : hi[gte], 0, 0, 0);
@@ -393,9 +372,8 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
     const float* const fb_l = bias_lds + 4 * HID + 16 * wave + 4 * q;      // the share's bias from LDS (four registers the kernel does not have)
     if (PART && tid < HID) bias_lds[4 * HID + tid] = dir == 0 ? bfc[tid] : 0.f;
     auto fc_mfma = [&](const int b, const h8v a0, const h8v a1) {
-        if (PART_DBG & 1) { fhi = *reinterpret_cast<const v4f*>(fb_l); flo = zero4; return; }
-        const h8v f1 = __builtin_bit_cast(h8v, (PART_DBG & 2) ? w2lds[(wave * 4 + 2 * b) * 64 + lane] : fclds[(wave * 4 + 2 * b) * 64 + lane]);
-        const h8v f2 = __builtin_bit_cast(h8v, (PART_DBG & 2) ? w2lds[(wave * 4 + 2 * b + 1) * 64 + lane] : fclds[(wave * 4 + 2 * b + 1) * 64 + lane]);
+        const h8v f1 = __builtin_bit_cast(h8v, fclds[(wave * 4 + 2 * b) * 64 + lane]);
+        const h8v f2 = __builtin_bit_cast(h8v, fclds[(wave * 4 + 2 * b + 1) * 64 + lane]);
         fhi = __builtin_amdgcn_mfma_f32_16x16x32_f16(f1, a0, b == 0 ? *reinterpret_cast<const v4f*>(fb_l) : fhi, 0, 0, 0);
         flo = __builtin_amdgcn_mfma_f32_16x16x32_f16(f1, a1, b == 0 ? zero4 : flo, 0, 0, 0);
         flo = __builtin_amdgcn_mfma_f32_16x16x32_f16(f2, a0, flo, 0, 0, 0);
@@ -448,7 +426,7 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
         const bool more2 = step + 2 < L;
 
         h_part((step + 1) & 1, true);            // h_{step-1} lives in slot (step - 1) & 1
-        if (PART && step > 0 && row_ok && !(BAND_ABL & 2))        // ... and its fc share leaves here
+        if (PART && step > 0 && row_ok)        // ... and its fc share leaves here
             *reinterpret_cast<v4f*>(hout + (grow + tmap(step - 1)) * (2 * HID) + dir * HID + 16 * wave + 4 * q) = fhi + flo * (1.f / 2048.f);
         stamp(1);
 
@@ -459,7 +437,7 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
             const v4f gg = 2.0f * rcp4(1.0f + exp2_4(pg * -2.88539008f)) - 1.0f, og = rcp4(1.0f + exp2_4(po * -1.44269504f));
             cv = fg * cv + ig * gg;
             const v4f hv4 = og * (2.0f * rcp4(1.0f + exp2_4(cv * -2.88539008f)) - 1.0f);
-            if (more2 && !(BAND_ABL & 1)) xstore(step & 1, xn);         // slot of x_step, whose readers finished before the last barrier
+            if (more2) xstore(step & 1, xn);         // slot of x_step, whose readers finished before the last barrier
             h4v p0, p1;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -467,11 +445,9 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
                 split_h2(hv4[r], a, b2);
                 p0[r] = a; p1[r] = b2;
             }
-            if (!(BAND_ABL & 4)) {
-                *reinterpret_cast<h4v*>(&hpl[step & 1][0][hoff]) = p0;
-                *reinterpret_cast<h4v*>(&hpl[step & 1][1][hoff]) = p1;
-            }
-            if (row_ok && !(BAND_ABL & 2)) {
+            *reinterpret_cast<h4v*>(&hpl[step & 1][0][hoff]) = p0;
+            *reinterpret_cast<h4v*>(&hpl[step & 1][1][hoff]) = p1;
+            if (row_ok) {
                 if (PLANES_OUT) {
                     _Float16* const hp = reinterpret_cast<_Float16*>(hout) + ((grow + t) * 2) * (2 * HID) + dir * HID + 16 * wave + 4 * q;
                     *reinterpret_cast<h4v*>(hp) = p0;
@@ -485,12 +461,12 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
         stamp(2);
         if (step + 1 < L) x_part((step + 1) & 1);
         stamp(3);
-        if (!(BAND_ABL & 8)) __syncthreads();
+        __syncthreads();
         stamp(4);
     }
-    if (PART && !(PART_DBG & 4)) {               // the last step's h (published before the loop's last barrier)
+    if (PART) {                                  // the last step's h (published before the loop's last barrier)
         h_part((L - 1) & 1, false);
-        if (row_ok && !(BAND_ABL & 2))
+        if (row_ok)
             *reinterpret_cast<v4f*>(hout + (grow + tmap(L - 1)) * (2 * HID) + dir * HID + 16 * wave + 4 * q) = fhi + flo * (1.f / 2048.f);
     }
     if (!(amax <= 65504.f) && range_flag) *range_flag = 1;
@@ -501,17 +477,14 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
     }
 }
 
-// Workgroup -> (tile of 16 sequences, direction).  The two directions of a tile read the same x rows: in the 1-D grid of
-// launch_band_lstm they are 8 workgroup ids apart - the same XCD (id % 8), dispatched together - so the second read of a row
-// is served by that XCD's L2 instead of a second trip to memory (2-D grids, the measurement tools': direction = blockIdx.y).
+// Workgroup -> (tile of 16 sequences, direction) in a 1-D grid of 16 workgroups per eight tiles.  The two directions of a tile read
+// the same x rows: they are 8 workgroup ids apart - the same XCD (id % 8), dispatched together - so the second read of a row is
+// served by that XCD's L2 instead of a second trip to memory.
 __device__ __forceinline__ bool band_tile_of_block(int N, int& dir, int& tile, const int* __restrict__ order = nullptr)
 {
-    dir = blockIdx.y; tile = blockIdx.x;
-    if (gridDim.y == 1) {
-        const int w = blockIdx.x & 15;
-        dir = w >> 3;
-        tile = (blockIdx.x >> 4) * 8 + (w & 7);
-    }
+    const int w = blockIdx.x & 15;
+    dir = w >> 3;
+    tile = (blockIdx.x >> 4) * 8 + (w & 7);
     // overlapped dual path: the dispatch ordinal picks its tile from a table sorted by the time the tile's frames leave the time-axis
     // launch running beside this one (the pair of a tile keeps its place: 8 workgroup ids apart); -1 pads the table to whole groups
     if (order) tile = order[tile];
@@ -519,7 +492,7 @@ __device__ __forceinline__ bool band_tile_of_block(int N, int& dir, int& tile, c
 }
 
 template <int IN, bool TRACE = false, bool PART = false>
-__global__ __launch_bounds__(256, (IN == 64 ? BAND_OCC64 : 2)) void band_lstm_h2_kernel(const float* __restrict__ xin, float* __restrict__ hout,
+__global__ __launch_bounds__(256, BAND_OCC) void band_lstm_h2_kernel(const float* __restrict__ xin, float* __restrict__ hout,
                                                               const uint4* __restrict__ wpk, const float* __restrict__ bias,
                                                               int N, int L, int* __restrict__ range_flag, unsigned long long* __restrict__ dbg,
                                                               const uint4* __restrict__ wfc = nullptr, const float* __restrict__ bfc = nullptr)
@@ -568,8 +541,6 @@ __global__ __launch_bounds__(256, 2) void band_pair_h2_kernel(const float* __res
             return;
         }
         __syncthreads();                          // (partner_ok is written again below)
-        if (OVL_DBG & 1)
-            for (int i = 0; i < 6; ++i) __builtin_amdgcn_s_sleep(127);
     }
     band_layer_body<HID, false, false>(lds, dir, tile, z, hb0, w0, b0, N, L, range_flag, nullptr, nullptr, nullptr);
     // Hand-over through the XCD's L2, which both workgroups share: a store is counted out of vmcnt when L2 has it, so vmcnt(0) is
@@ -595,8 +566,6 @@ __global__ __launch_bounds__(256, 2) void band_pair_h2_kernel(const float* __res
         return;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");      // (orders the plane loads below behind the poll)
-    if (OVL_DBG & 2) { asm volatile("buffer_inv sc1\n\ts_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }
-    else
     asm volatile("buffer_inv sc0" ::: "memory");                 // the partner's planes from L2, not from a line this CU's L1 may hold
     band_layer_body<2 * HID, false, PART>(lds, dir, tile, hb0, hb1, w1, b1, N, L, range_flag, nullptr, wfc, bfc);
 }
@@ -642,16 +611,16 @@ void launch_band_lstm(const float* xin, float* hout, const float* wpk, const voi
                       int N, int L, int IN, int* range_flag, hipStream_t stream)
 {
     if (N <= 0 || L <= 0) return;
-    dim3 grid((N + 15) / 16, 2), block(256);
+    const dim3 block(256);
     if (lstm_mode() == LSTM_FP16X2 && !force_f32()) {
-        static const bool paired = [] { const char* e = getenv("BSRNN_BAND_GRID"); return !(e && !strcmp(e, "2d")); }();   // A/B: 2d = one direction after the other
-        if (paired) grid = dim3((((N + 15) / 16 + 7) / 8) * 16);      // both directions of eight tiles per 16 consecutive workgroups
+        const dim3 grid((((N + 15) / 16 + 7) / 8) * 16);      // both directions of eight tiles per 16 consecutive workgroups
         if (IN == 64)
             hipLaunchKernelGGL(band_lstm_h2_kernel<64>, grid, block, 0, stream, xin, hout, (const uint4*)wpk16, bias, N, L, range_flag, (unsigned long long*)nullptr);
         else
             hipLaunchKernelGGL(band_lstm_h2_kernel<128>, grid, block, 0, stream, xin, hout, (const uint4*)wpk16, bias, N, L, range_flag, (unsigned long long*)nullptr);
         return;
     }
+    const dim3 grid((N + 15) / 16, 2);
     if (IN == 64)
         hipLaunchKernelGGL(band_lstm_kernel<64>, grid, block, 0, stream, xin, hout, wpk, bias, N, L);
     else
@@ -829,8 +798,8 @@ __global__ __launch_bounds__(512) void time_lstm_kernel(const float* __restrict_
 // =====================================================================================
 // Time-axis LSTM, split-precision variant (fp16x2 on v_mfma_f32_16x16x32_f16, as the band kernel above).
 // The fp32 kernel's step is bound by the 4x4x1 MFMA stream (2 waves x 128 MFMAs x 9.5 cycles per SIMD and
-// step).  Same decomposition (4 sequences per workgroup, waves 0-3 layer 0, waves 4-7 layer 1, one barrier per
-// step), but the matrix work is organised around the 16-row tile of the f16 MFMA:
+// step).  Same decomposition (4 sequences per workgroup, one cell per lane), but the matrix work is organised
+// around the 16-row tile of the f16 MFMA:
 //   * recurrent half (h_{t-1} W_hh, the sequential part): A = activations with row 4j = sequence j (the rows in
 //     between repeat it and are ignored), B = weights, tile g = gate g of the wave's 16 units (column n = unit
 //     16w+n), resident in VGPRs.  Accumulator register 0 of lane (n, q = lane >> 4) is gate g of cell
@@ -840,221 +809,13 @@ __global__ __launch_bounds__(512) void time_lstm_kernel(const float* __restrict_
 //     16 rows, and register r of lane (n, q) is then the input pre-activation of this lane's own cell at step
 //     4g + r.  One group of 24 MFMAs per four steps instead of 24 per step; with the two-MFMA recurrent form
 //     below: 22 instead of 48 MFMAs per wave and step (matrix-pipe floor 0.34 instead of 0.73 us per step).  Layer 1 therefore runs four steps behind
-//     layer 0 (its input h0_{4g..4g+3} is complete after layer 0's step 4g+3); h0 lives in a ring of 8 steps.
+//     layer 0 (its input h0_{4g..4g+3} is complete after layer 0's step 4g+3).
 // x_t / h_t live in LDS as two fp16 planes in [k / 8][sequence][8] order per step (fragment reads are
 // conflict-free ds_read_b128; steps are 1088 bytes apart so that the four steps of a batched read hit
 // different banks).
-// =====================================================================================
-constexpr int TSTEP = 2 * 4 * HID + 32;       // halves per step slot in LDS: two pieces of [8][4][8] + 64 bytes of skew
-
-template <bool TRACE = false>
-__global__ __launch_bounds__(512) void time_lstm_h2_kernel(const float* __restrict__ zin, float* __restrict__ hout,
-                                                           const uint4* __restrict__ wpk, const float* __restrict__ bias,
-                                                           const float* __restrict__ state_in, float* __restrict__ state_out,
-                                                           int R, int T, int K, int* __restrict__ range_flag, unsigned long long* __restrict__ dbg)
-{
-    unsigned long long tp[5] = {0, 0, 0, 0, 0}, tq = 0;       // measurement only, as in the band kernel
-    auto stamp = [&](int k) { if (TRACE) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); tp[k] += now - tq; tq = now; } };
-    __shared__ __attribute__((aligned(16))) _Float16 xpl[2 * TCH * TSTEP];     // [chunk slot][step in chunk]
-    __shared__ __attribute__((aligned(16))) _Float16 h0pl[8 * TSTEP];          // ring: h0_t in slot t & 7
-    __shared__ __attribute__((aligned(16))) _Float16 h1pl[2 * TSTEP];          // h1_t in slot t & 1
-
-    const int N = R * K;
-    const int n0 = blockIdx.x * 4;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int layer = wave >> 2, w4 = wave & 3;
-    const int n = lane & 15, q = lane >> 4;
-    const int unit = 16 * w4 + n;
-    const size_t tstride = (size_t)K * HID;
-
-    // this lane's cell: (unit, sequence q)
-    const int nq_raw = n0 + q;
-    const int nq = nq_raw < N ? nq_raw : N - 1;
-    const size_t base_q = ((size_t)(nq / K) * T * K + (nq % K)) * HID;
-
-    h8v w[4][4][2];                               // [k block: 0,1 input half, 2,3 recurrent half][gate][piece]
-    {
-        const uint4* wp = wpk + ((size_t)(layer * 4 + w4) * 4 * 4 * 2) * 64 + lane;
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int gte = 0; gte < 4; ++gte)
-#pragma unroll
-                for (int pc = 0; pc < 2; ++pc) w[b][gte][pc] = __builtin_bit_cast(h8v, wp[((b * 4 + gte) * 2 + pc) * 64]);
-    }
-    float bs[4];
-#pragma unroll
-    for (int gte = 0; gte < 4; ++gte) bs[gte] = bias[layer * 256 + gte * 64 + unit];
-
-    const int hoff = ((unit >> 3) * 4 + q) * 8 + (unit & 7);      // where this lane's h goes inside a piece
-    float c = state_in ? state_in[((size_t)(2 + layer) * N + nq) * HID + unit] : 0.f;
-    {
-        const float hinit = state_in ? state_in[((size_t)layer * N + nq) * HID + unit] : 0.f;
-        _Float16 p0, p1;
-        split_h2(hinit, p0, p1);
-        _Float16* hb = layer ? &h1pl[1 * TSTEP] : &h0pl[7 * TSTEP];   // h_{-1}: slot (-1) & 1 = 1, (-1) & 7 = 7
-        hb[hoff] = p0;
-        hb[4 * HID + hoff] = p1;
-    }
-
-    // x chunk staging: 8 steps x 4 sequences x 16 float4 = 512 float4, one per thread, split on the way into LDS
-    const int xs_t = tid >> 6, xs_i = (tid >> 4) & 3, xs_c4 = tid & 15;
-    size_t xs_base;
-    {
-        int ni = n0 + xs_i; ni = ni < N ? ni : N - 1;
-        xs_base = ((size_t)(ni / K) * T * K + (ni % K)) * HID + 4 * xs_c4;
-    }
-    auto chunk_load = [&](int chunk) -> float4 {
-        int t = chunk * TCH + xs_t;
-        t = t < T ? t : T - 1;
-        return *reinterpret_cast<const float4*>(zin + xs_base + (size_t)t * tstride);
-    };
-    float amax = 0.f;                            // range guard
-    auto chunk_store = [&](int chunk, float4 v) {
-        const float f[4] = {v.x, v.y, v.z, v.w};
-        h4v p0, p1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            amax = __builtin_fmaxf(amax, __builtin_fabsf(f[e]));
-            _Float16 a, b2;
-            split_h2(f[e], a, b2);
-            p0[e] = a; p1[e] = b2;
-        }
-        _Float16* dst = &xpl[((chunk & 1) * TCH + xs_t) * TSTEP + ((xs_c4 >> 1) * 4 + xs_i) * 8 + (xs_c4 & 1) * 4];
-        *reinterpret_cast<h4v*>(dst) = p0;
-        *reinterpret_cast<h4v*>(dst + 4 * HID) = p1;
-    };
-    chunk_store(0, chunk_load(0));
-    float4 xnext = make_float4(0.f, 0.f, 0.f, 0.f);
-    float hsel = 0.f, csel = 0.f;
-    __syncthreads();
-
-    v4f hi[4], lo[4];
-    float pin[4][4];                              // [gate][step in group]: bias + input half of this lane's cell
-    const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
-    // A fragments inside a 32-deep block of a piece: row l & 15 of the recurrent form carries sequence (l & 15) >> 2;
-    // in the batched form it carries (sequence (l & 15) >> 2, step (l & 15) & 3) of the group
-    const int afrag = (q * 4 + (n >> 2)) * 8;
-    const int bstep = n & 3;
-    auto mfma_block = [&](const h8v a0, const h8v a1, const int wb) {
-#pragma unroll
-        for (int gte = 0; gte < 4; ++gte) hi[gte] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, w[wb][gte][0], hi[gte], 0, 0, 0);
-#pragma unroll
-        for (int gte = 0; gte < 4; ++gte) lo[gte] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, w[wb][gte][1], lo[gte], 0, 0, 0);
-#pragma unroll
-        for (int gte = 0; gte < 4; ++gte) lo[gte] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, w[wb][gte][0], lo[gte], 0, 0, 0);
-    };
-    // recurrent half: src = one step slot.  Only rows 4j of the 16-row tile carry a sequence, so row 4j+1 is given
-    // the SECOND piece of the same sequence: one MFMA against w1 (first weight piece) then yields a1 w1 in register
-    // 0 and a2 w1 in register 1 of the owning lane, a second MFMA against w2 yields a1 w2 in register 0 - two
-    // MFMAs per (block, gate) instead of three, and one fragment read per block instead of two.
-    const int rfrag = afrag + ((n & 3) == 1 ? 4 * HID : 0);
-    auto recurrent = [&](const _Float16* src) {
-        h8v a[2];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) a[b] = *reinterpret_cast<const h8v*>(&src[b * 128 + rfrag]);
-#pragma unroll
-        for (int gte = 0; gte < 4; ++gte) { hi[gte] = zero4; lo[gte] = zero4; }
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-#pragma unroll
-            for (int gte = 0; gte < 4; ++gte) hi[gte] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[b], w[2 + b][gte][0], hi[gte], 0, 0, 0);
-#pragma unroll
-            for (int gte = 0; gte < 4; ++gte) lo[gte] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[b], w[2 + b][gte][1], lo[gte], 0, 0, 0);
-        }
-    };
-    // input half of four consecutive steps; `src` = slot of the group's first step, the lane's step is src + bstep slots
-    auto batched_input = [&](const _Float16* src) {
-        const _Float16* mine = src + bstep * TSTEP;
-        h8v a0[2], a1[2];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            a0[b] = *reinterpret_cast<const h8v*>(&mine[b * 128 + afrag]);
-            a1[b] = *reinterpret_cast<const h8v*>(&mine[4 * HID + b * 128 + afrag]);
-        }
-#pragma unroll
-        for (int gte = 0; gte < 4; ++gte) { hi[gte] = zero4; lo[gte] = zero4; }
-#pragma unroll
-        for (int b = 0; b < 2; ++b) mfma_block(a0[b], a1[b], b);
-#pragma unroll
-        for (int gte = 0; gte < 4; ++gte)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) pin[gte][r] = bs[gte] + (hi[gte][r] + lo[gte][r] * (1.f / 2048.f));
-    };
-    auto cell = [&](int t, int r) {
-        // hi[g] = {a1 w1, a2 w1, -, -}, lo[g] = {a1 w2, -, -, -} of this lane's cell (see recurrent())
-        const float ig = fast_sigmoid(pin[0][r] + (hi[0][0] + (hi[0][1] + lo[0][0]) * (1.f / 2048.f)));
-        const float fg = fast_sigmoid(pin[1][r] + (hi[1][0] + (hi[1][1] + lo[1][0]) * (1.f / 2048.f)));
-        const float gg = fast_tanh(pin[2][r] + (hi[2][0] + (hi[2][1] + lo[2][0]) * (1.f / 2048.f)));
-        const float og = fast_sigmoid(pin[3][r] + (hi[3][0] + (hi[3][1] + lo[3][0]) * (1.f / 2048.f)));
-        c = fg * c + ig * gg;
-        hsel = og * fast_tanh(c);
-        csel = c;
-        _Float16 p0, p1;
-        split_h2(hsel, p0, p1);
-        _Float16* hb = layer ? &h1pl[(t & 1) * TSTEP] : &h0pl[(t & 7) * TSTEP];
-        hb[hoff] = p0;
-        hb[4 * HID + hoff] = p1;
-        if (layer && nq_raw < N) hout[base_q + (size_t)t * tstride + unit] = hsel;
-    };
-    auto xslot = [&](int t) { return &xpl[(((t / TCH) & 1) * TCH + (t % TCH)) * TSTEP]; };
-
-    if (layer == 0) batched_input(xslot(0));      // group 0
-    if (TRACE) tq = __builtin_amdgcn_s_memrealtime();
-    // iteration s: layer 0 computes step s, layer 1 computes step s - 4
-    for (int s4 = 0; s4 < T + 4; s4 += 4) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int s = s4 + r;
-            if (s >= T + 4) break;
-            const int chunk = s / TCH, sin = s % TCH;
-            const bool have_next = (chunk + 1) * TCH < T;
-            if (sin == 0 && have_next) xnext = chunk_load(chunk + 1);
-            // x of the next chunk goes to LDS six steps after its load, at the TOP of the step: the wait in front of it then only
-            // covers operations a whole step old (behind this step's h store the compiler has to wait for vmcnt(0), store included).
-            // Its first reader is the batched input at the end of the next step, behind this step's barrier.
-            if (sin == TCH - 2 && have_next) chunk_store(chunk + 1, xnext);
-            stamp(4);
-            if (layer == 0) {
-                if (s < T) {
-                    recurrent(&h0pl[((s + 7) & 7) * TSTEP]);            // h0_{s-1}
-                    stamp(1);
-                    cell(s, r);
-                    stamp(2);
-                }
-                if (r == 3 && s + 1 < T) { batched_input(xslot(s + 1)); stamp(0); }     // next group: x_{s+1 .. s+4}
-            } else {
-                const int t = s - 4;
-                if (r == 0 && t >= 0 && t < T) { batched_input(&h0pl[(t & 7) * TSTEP]); stamp(0); }   // h0_{t .. t+3}
-                if (t >= 0 && t < T) {
-                    recurrent(&h1pl[((t + 1) & 1) * TSTEP]);             // h1_{t-1}
-                    stamp(1);
-                    cell(t, r);
-                    stamp(2);
-                }
-            }
-            __syncthreads();
-            stamp(3);
-        }
-    }
-    if (!(amax <= 65504.f) && range_flag) *range_flag = 1;
-    if (TRACE && lane == 0 && blockIdx.x < 4) {
-        unsigned long long* d = dbg + (blockIdx.x * 8 + wave) * 5;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) d[k] = tp[k];
-    }
-
-    if (state_out && nq_raw < N) {
-        state_out[((size_t)layer * N + nq) * HID + unit] = hsel;           // h_{T-1}
-        state_out[((size_t)(2 + layer) * N + nq) * HID + unit] = csel;     // c_{T-1}
-    }
-}
-
-// =====================================================================================
-// Time-axis LSTM, split precision, SIXTEEN waves per workgroup and NO per-step workgroup barrier (round 3; the kernel
-// the fp16x2 mode launches).  Same decomposition and the same arithmetic as time_lstm_h2_kernel above (4 sequences per
-// workgroup, one cell per lane, recurrent half with the second piece on row 4j + 1, input half of four steps batched into
-// one 16-row tile) - h1 and the carried state are bit-identical to it - but the work is spread over four roles of four
+//
+// SIXTEEN waves per workgroup and NO per-step workgroup barrier (round 3; round 2's kernel ran 8 waves, layer 0 and layer 1
+// four each, with one barrier per step, and computed bit-identical h1 and state): the work is spread over four roles of four
 // waves each, one wave of every role on every SIMD:
 //     M0, M1  "main" waves of layer 0 / layer 1: ONLY the serial chain of a step - h_{t-1} fragments from LDS, 16
 //             recurrent MFMAs against the resident W_hh, the cell, h_t to LDS.  W_hh alone is 64 VGPRs, so a main wave fits
@@ -1077,12 +838,7 @@ __global__ __launch_bounds__(512) void time_lstm_h2_kernel(const float* __restri
 // four steps of a group like the input half (6 MFMAs per group and wave, wave w = output features 16 w .. 16 w + 15): h1
 // never goes to HBM and the separate grouped-GEMM launch (15 us, 75 MB per block) is gone; `hout` is then the block's output.
 // =====================================================================================
-#ifndef TIME_ABL
-#define TIME_ABL 0                // measurement only (tools/time_lstm_v3_bench.hip): 1 main waves do not wait for the input half, 2 helpers issue no MFMAs, 4 main waves do not wait for h(t-1), 8 no helper work at all
-#endif
-#ifndef TIME_OPT
-#define TIME_OPT 3                // 1: main waves at raised priority; 2: h(t-1) fragments requested together with the poll of the step counter
-#endif
+constexpr int TSTEP = 2 * 4 * HID + 32;       // halves per step slot in LDS: two pieces of [8][4][8] + 64 bytes of skew
 constexpr int H0RING = 16, H1RING = 16;        // steps of h0 / h1 kept in LDS
 enum { SY_DONE0 = 0, SY_DONE1, SY_PIN0, SY_PIN1, SY_FC, SY_X, SY_ABORT, SY_COUNT = 8 };
 constexpr int SPIN_LIMIT = 1 << 21;            // polls of one wait before the workgroup gives up (seconds; a step takes ~10 polls)
@@ -1161,7 +917,7 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w_kernel(const float* __rest
     if (tid < SY_COUNT) sync[tid] = 0;
     if (tid >= 64 && tid < 72) outc[tid - 64] = 0;
     // overlapped dual path (kernels.h, OvlProducer): this workgroup is on the chip - the launch that consumes its output is let go when all are
-    if (PART && tid == 0 && ovl_resident) __hip_atomic_fetch_add(ovl_resident, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (may be a signal word the command processor polls)
+    if (PART && tid == 0 && ovl_resident) __hip_atomic_fetch_add(ovl_resident, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (system scope: from when a command-processor wait polled this word)
     if (TRACE) tq = __builtin_amdgcn_s_memrealtime();
 
     // The two role families are laid out as "helpers: ...; return;  main waves: ..." and not as if / else: with a join behind both, the
@@ -1203,7 +959,6 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w_kernel(const float* __rest
         // input half of the four steps of `group` (A rows = (sequence, step), `src` = slot of the group's first step): per gate
         // 6 MFMAs, then bias + result to the LDS buffer the main wave of this cell reads, [step][gate][cell]
         auto input_half = [&](const _Float16* src, int group) {
-            if (TIME_ABL & 8) return;
             const _Float16* mine = src + bstep * TSTEP;
             h8v a0[2], a1[2];
 #pragma unroll
@@ -1220,7 +975,6 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w_kernel(const float* __rest
                 v4f ghi = zero4, glo = zero4;
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
-                    if (TIME_ABL & 2) { ghi[0] += (float)a0[b][0] * (float)w[b][gte][0][0]; glo[1] += (float)a1[b][1] * (float)w[b][gte][1][1]; continue; }
                     ghi = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[b], w[b][gte][0], ghi, 0, 0, 0);
                     glo = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[b], w[b][gte][1], glo, 0, 0, 0);
                     glo = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[b], w[b][gte][0], glo, 0, 0, 0);
@@ -1299,10 +1053,6 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w_kernel(const float* __rest
                     // the store is complete (vmcnt(0) in front of this wave's PIN0 arrival below) long before the chain H0 -> M0 ->
                     // H1 of LDS counters lets H1 ask for it, and nobody has read that line before (no stale copy in the L1).
                     if (n0 + xs_i < N && 4 * g + xs_t < T) {
-                        if (OVL_DBG & 4) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) __hip_atomic_store((float __attribute__((address_space(1)))*)(hout + rows_of(g) + e), f[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        } else
                         *reinterpret_cast<float4*>(hout + rows_of(g)) = make_float4(f[0], f[1], f[2], f[3]);
                     }
                 };
@@ -1482,36 +1232,30 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w_kernel(const float* __rest
         const bool has_reader = layer ? FUSE : true;
         const int rsteps = layer ? H1RING : H0RING;
         __syncthreads();                          // h_{-1}, counters, x chunk 0 (the helpers publish group 0 behind it)
-        if (TIME_OPT & 1) __builtin_amdgcn_s_setprio(2);     // the chain before the helpers wherever both could issue
+        __builtin_amdgcn_s_setprio(2);     // the chain before the helpers wherever both could issue
         for (int t = 0; t < T; ++t) {
             if ((t & 3) == 0) {
-                if (!(TIME_ABL & 1)) lds_wait_ge(sync, my_pin, 4 * ((t >> 2) + 1));              // this group's input half is published
+                lds_wait_ge(sync, my_pin, 4 * ((t >> 2) + 1));              // this group's input half is published
                 if (has_reader && t >= rsteps) lds_wait_ge(sync, reader, 4 * (((t - rsteps) >> 2) + 1));   // the slots this group overwrites have been read
             }
             stamp(3);
             const _Float16* src = &ring[((t - 1) & rmask) * TSTEP];
             h8v a[2];
-            if (TIME_OPT & 2) {
-                // h_{t-1} complete (all four waves)?  The counter and the two fragments are requested together - LDS operations of a
-                // wave execute in order, so fragments that follow a counter value >= 4 t are complete - and requested again if not:
-                // one LDS round trip per step instead of two.
-                const unsigned ca = (unsigned)(size_t)&sync[my_done], fa = (unsigned)(size_t)&src[rfrag];
-                int spins = 0;
-                for (;;) {
-                    int cv;
-                    u4v f0, f1;
-                    asm volatile("ds_read_b32 %0, %3\n\tds_read_b128 %1, %4\n\tds_read_b128 %2, %4 offset:256\n\ts_waitcnt lgkmcnt(0)"
-                                 : "=&v"(cv), "=&v"(f0), "=&v"(f1) : "v"(ca), "v"(fa) : "memory");
-                    a[0] = __builtin_bit_cast(h8v, f0); a[1] = __builtin_bit_cast(h8v, f1);
-                    if ((TIME_ABL & 4) || __builtin_amdgcn_readfirstlane(cv) >= 4 * t) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > SPIN_LIMIT) __hip_atomic_store(&sync[SY_ABORT], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (spins > 64 && lds_peek(&sync[SY_ABORT])) break;
-                }
-            } else {
-                if (!(TIME_ABL & 4)) lds_wait_ge(sync, my_done, 4 * t);                          // h_{t-1} complete (all four waves)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) a[b] = *reinterpret_cast<const h8v*>(&src[b * 128 + rfrag]);
+            // h_{t-1} complete (all four waves)?  The counter and the two fragments are requested together - LDS operations of a
+            // wave execute in order, so fragments that follow a counter value >= 4 t are complete - and requested again if not:
+            // one LDS round trip per step instead of two.
+            const unsigned ca = (unsigned)(size_t)&sync[my_done], fa = (unsigned)(size_t)&src[rfrag];
+            int spins = 0;
+            for (;;) {
+                int cv;
+                u4v f0, f1;
+                asm volatile("ds_read_b32 %0, %3\n\tds_read_b128 %1, %4\n\tds_read_b128 %2, %4 offset:256\n\ts_waitcnt lgkmcnt(0)"
+                             : "=&v"(cv), "=&v"(f0), "=&v"(f1) : "v"(ca), "v"(fa) : "memory");
+                a[0] = __builtin_bit_cast(h8v, f0); a[1] = __builtin_bit_cast(h8v, f1);
+                if (__builtin_amdgcn_readfirstlane(cv) >= 4 * t) break;
+                __builtin_amdgcn_s_sleep(1);
+                if (++spins > SPIN_LIMIT) __hip_atomic_store(&sync[SY_ABORT], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (spins > 64 && lds_peek(&sync[SY_ABORT])) break;
             }
             stamp(2);
             const float* const pin_t = pin_l + (((t >> 2) & 1) * 4 + (t & 3)) * 1024;
@@ -1607,7 +1351,7 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w8_kernel(const float* __res
     if (tid < SY_COUNT) sync[tid] = 0;
     if (tid >= 64 && tid < 72) outc[tid - 64] = 0;
     // overlapped dual path (kernels.h, OvlProducer): this workgroup is on the chip - the launch that consumes its output is let go when all are
-    if (PART && tid == 0 && ovl_resident) __hip_atomic_fetch_add(ovl_resident, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (may be a signal word the command processor polls)
+    if (PART && tid == 0 && ovl_resident) __hip_atomic_fetch_add(ovl_resident, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (system scope: from when a command-processor wait polled this word)
     if (TRACE) tq = __builtin_amdgcn_s_memrealtime();
 
     // The two role families are laid out as "helpers: ...; return;  main waves: ..." and not as if / else: with a join behind both, the
@@ -1649,7 +1393,6 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w8_kernel(const float* __res
         // input half of the four steps of `group` (A rows = (sequence, step), `src` = slot of the group's first step): per gate
         // 6 MFMAs, then bias + result to the LDS buffer the main wave of this cell reads, [step][gate][cell]
         auto input_half = [&](const _Float16* src, int group) {
-            if (TIME_ABL & 8) return;
             const _Float16* mine = src + bstep * TSTEP8;
             h8v a0[2], a1[2];
 #pragma unroll
@@ -1666,7 +1409,6 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w8_kernel(const float* __res
                 v4f ghi = zero4, glo = zero4;
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
-                    if (TIME_ABL & 2) { ghi[0] += (float)a0[b][0] * (float)w[b][gte][0][0]; continue; }
                     ghi = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[b], w[b][gte][0], ghi, 0, 0, 0);
                     glo = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[b], (b == 0 && gte == 0) ? __builtin_bit_cast(h8v, wsp[((role - 2) * 4 + w4) * 64 + lane]) : w[b][gte][1], glo, 0, 0, 0);
                     glo = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[b], w[b][gte][0], glo, 0, 0, 0);
@@ -1746,10 +1488,6 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w8_kernel(const float* __res
                     // the store is complete (vmcnt(0) in front of this wave's PIN0 arrival below) long before the chain H0 -> M0 ->
                     // H1 of LDS counters lets H1 ask for it, and nobody has read that line before (no stale copy in the L1).
                     if (n0 + xs_i < N && 2 * g + xs_t < T) {
-                        if (OVL_DBG & 4) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) __hip_atomic_store((float __attribute__((address_space(1)))*)(hout + rows_of(g) + e), f[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        } else
                         *reinterpret_cast<float4*>(hout + rows_of(g)) = make_float4(f[0], f[1], f[2], f[3]);
                     }
                 };
@@ -1932,36 +1670,30 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w8_kernel(const float* __res
         const bool has_reader = layer ? FUSE : true;
         const int rsteps = RING8;
         __syncthreads();                          // h_{-1}, counters, x chunk 0 (the helpers publish group 0 behind it)
-        if (TIME_OPT & 1) __builtin_amdgcn_s_setprio(2);     // the chain before the helpers wherever both could issue
+        __builtin_amdgcn_s_setprio(2);     // the chain before the helpers wherever both could issue
         for (int t = 0; t < T; ++t) {
             if ((t & 1) == 0) {
-                if (!(TIME_ABL & 1)) lds_wait_ge(sync, my_pin, 4 * ((t >> 1) + 1));              // this group's input half is published
+                lds_wait_ge(sync, my_pin, 4 * ((t >> 1) + 1));              // this group's input half is published
                 if (has_reader && t >= rsteps) lds_wait_ge(sync, reader, 4 * (((t - rsteps) >> 1) + 1));   // the slots this group overwrites have been read
             }
             stamp(3);
             const _Float16* src = &ring[((t - 1) & rmask) * TSTEP8];
             h8v a[2];
-            if (TIME_OPT & 2) {
-                // h_{t-1} complete (all four waves)?  The counter and the two fragments are requested together - LDS operations of a
-                // wave execute in order, so fragments that follow a counter value >= 4 t are complete - and requested again if not:
-                // one LDS round trip per step instead of two.
-                const unsigned ca = (unsigned)(size_t)&sync[my_done], fa = (unsigned)(size_t)&src[rfrag];
-                int spins = 0;
-                for (;;) {
-                    int cv;
-                    u4v f0, f1;
-                    asm volatile("ds_read_b32 %0, %3\n\tds_read_b128 %1, %4\n\tds_read_b128 %2, %4 offset:512\n\ts_waitcnt lgkmcnt(0)"
-                                 : "=&v"(cv), "=&v"(f0), "=&v"(f1) : "v"(ca), "v"(fa) : "memory");
-                    a[0] = __builtin_bit_cast(h8v, f0); a[1] = __builtin_bit_cast(h8v, f1);
-                    if ((TIME_ABL & 4) || __builtin_amdgcn_readfirstlane(cv) >= 4 * t) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > SPIN_LIMIT) __hip_atomic_store(&sync[SY_ABORT], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (spins > 64 && lds_peek(&sync[SY_ABORT])) break;
-                }
-            } else {
-                if (!(TIME_ABL & 4)) lds_wait_ge(sync, my_done, 4 * t);                          // h_{t-1} complete (all four waves)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) a[b] = *reinterpret_cast<const h8v*>(&src[b * 256 + rfrag]);
+            // h_{t-1} complete (all four waves)?  The counter and the two fragments are requested together - LDS operations of a
+            // wave execute in order, so fragments that follow a counter value >= 4 t are complete - and requested again if not:
+            // one LDS round trip per step instead of two.
+            const unsigned ca = (unsigned)(size_t)&sync[my_done], fa = (unsigned)(size_t)&src[rfrag];
+            int spins = 0;
+            for (;;) {
+                int cv;
+                u4v f0, f1;
+                asm volatile("ds_read_b32 %0, %3\n\tds_read_b128 %1, %4\n\tds_read_b128 %2, %4 offset:512\n\ts_waitcnt lgkmcnt(0)"
+                             : "=&v"(cv), "=&v"(f0), "=&v"(f1) : "v"(ca), "v"(fa) : "memory");
+                a[0] = __builtin_bit_cast(h8v, f0); a[1] = __builtin_bit_cast(h8v, f1);
+                if (__builtin_amdgcn_readfirstlane(cv) >= 4 * t) break;
+                __builtin_amdgcn_s_sleep(1);
+                if (++spins > SPIN_LIMIT) __hip_atomic_store(&sync[SY_ABORT], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (spins > 64 && lds_peek(&sync[SY_ABORT])) break;
             }
             stamp(2);
             const float* const pin_t = pin_l + (((t >> 1) & 1) * 2 + (t & 1)) * 2048;
@@ -2180,8 +1912,7 @@ __global__ __launch_bounds__(512) void band_block_small_kernel(const float* __re
 // true when launch_band_block_small() will take the block (fp16x2 modes, few sequences, a band table that fits the LDS images)
 bool band_block_is_small(int N, int L)
 {
-    static const bool on = [] { const char* e = getenv("BSRNN_BAND_SMALL"); return !(e && !strcmp(e, "0")); }();
-    return on && lstm_mode() == LSTM_FP16X2 && !force_f32() && gemm_mode() != GEMM_F32 && N >= 1 && N <= 8 && L >= 1 && L <= BS_MAXL;
+    return lstm_mode() == LSTM_FP16X2 && !force_f32() && gemm_mode() != GEMM_F32 && N >= 1 && N <= 8 && L >= 1 && L <= BS_MAXL;
 }
 void launch_band_block_small(const float* zin, float* zout, const void* w0pk16, const float* bias0, const void* w1pk16, const float* bias1,
                              const void* fc16, const float* fcb, int N, int L, int* range_flag, hipStream_t stream)
@@ -2192,39 +1923,21 @@ void launch_band_block_small(const float* zin, float* zout, const void* w0pk16, 
 
 // The 16-wave kernel computes the block's fc + residual itself when the Linear layers are not asked to be exact fp32
 // (BSRNN_GEMM=f32 keeps every nn.Linear on the fp32 matrix kernels) - api.hip then skips the block's grouped-GEMM launch.
-// BSRNN_TIME_KERNEL = v2 (round-2 kernel, 8 waves) | v3 (16 waves, separate fc launch) | fused (default).
-static int time_kernel_variant()
+// BSRNN_TIME_KERNEL = v3 (the same kernel, the fc as a separate launch) | fused (default).
+static bool time_kernel_fused()
 {
-    static const int v = [] {
+    static const bool fused = [] {
         const char* e = getenv("BSRNN_TIME_KERNEL");
-        if (!e || !*e || !strcmp(e, "fused")) return 2;
-        if (!strcmp(e, "v3")) return 1;
-        if (!strcmp(e, "v2")) return 0;
-        fprintf(stderr, "bsrnn: unknown BSRNN_TIME_KERNEL='%s' (v2 | v3 | fused), using fused\n", e);
-        return 2;
+        if (!e || !*e || !strcmp(e, "fused")) return true;
+        if (!strcmp(e, "v3")) return false;
+        fprintf(stderr, "bsrnn: unknown BSRNN_TIME_KERNEL='%s' (v3 | fused), using fused\n", e);
+        return true;
     }();
-    return v;
+    return fused;
 }
 bool time_lstm_fuses_fc()
 {
-    return lstm_mode() == LSTM_FP16X2 && !force_f32() && gemm_mode() != GEMM_F32 && time_kernel_variant() == 2;
-}
-
-// measurement (BSRNN_BAND_FC=part_add): out = (z + part[.., 0, :]) + part[.., 1, :] as a launch of its own, so that the time kernel
-// runs without PART on the same numbers - separates the two halves of the parts flow when something depends on which one runs
-__global__ void parts_add_kernel(const float* __restrict__ z, const float* __restrict__ part, float* __restrict__ out, size_t n4)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    const size_t row = i / 16, c4 = i % 16;
-    const float4 a = reinterpret_cast<const float4*>(z)[i];
-    const float4 f = reinterpret_cast<const float4*>(part)[row * 32 + c4], b = reinterpret_cast<const float4*>(part)[row * 32 + 16 + c4];
-    reinterpret_cast<float4*>(out)[i] = make_float4((a.x + f.x) + b.x, (a.y + f.y) + b.y, (a.z + f.z) + b.z, (a.w + f.w) + b.w);
-}
-static bool parts_add_mode()
-{
-    static const bool on = [] { const char* e = getenv("BSRNN_BAND_FC"); return e && !strcmp(e, "part_add"); }();
-    return on;
+    return lstm_mode() == LSTM_FP16X2 && !force_f32() && gemm_mode() != GEMM_F32 && time_kernel_fused();
 }
 
 int device_cus()
@@ -2244,11 +1957,6 @@ void launch_time_lstm(const float* zin, float* hout, const float* wpk, const voi
 {
     const int N = R * K;
     if (N <= 0 || T <= 0) return;
-    if (part && parts_add_mode() && time_lstm_fuses_fc() && fc16 && fcb) {
-        const size_t n4 = (size_t)R * T * K * 16;          // in place: zin is the block's input from here on (its old content is dead)
-        hipLaunchKernelGGL(parts_add_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, zin, part, const_cast<float*>(zin), n4);
-        part = nullptr;                                    // zin now holds the block's input; the plain fused kernel follows
-    }
     dim3 grid((N + 3) / 4), block(512), block16(1024);
     if (lstm_mode() == LSTM_FP16X2 && !force_f32()) {
         // Eight sequences per workgroup where four would need more than one round of workgroups (one per CU): the 41-band table, large batches;
@@ -2271,12 +1979,9 @@ void launch_time_lstm(const float* zin, float* hout, const float* wpk, const voi
         else if (time_lstm_fuses_fc() && fc16 && fcb)
             hipLaunchKernelGGL((time_lstm_h2w_kernel<true, false>), grid, block16, 0, stream, zin, hout, (const uint4*)wpk16, bias, (const uint4*)fc16, fcb,
                                state_in, state_out, R, T, K, range_flag, (unsigned long long*)nullptr);
-        else if (time_kernel_variant() >= 1)
+        else
             hipLaunchKernelGGL((time_lstm_h2w_kernel<false, false>), grid, block16, 0, stream, zin, hout, (const uint4*)wpk16, bias, (const uint4*)nullptr,
                                (const float*)nullptr, state_in, state_out, R, T, K, range_flag, (unsigned long long*)nullptr);
-        else
-            hipLaunchKernelGGL(time_lstm_h2_kernel<false>, grid, block, 0, stream, zin, hout, (const uint4*)wpk16, bias, state_in, state_out, R, T, K,
-                               range_flag, (unsigned long long*)nullptr);
         return;
     }
     hipLaunchKernelGGL(time_lstm_kernel, grid, block, 0, stream, zin, hout, wpk, bias, state_in, state_out, R, T, K,

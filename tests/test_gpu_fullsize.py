@@ -127,16 +127,16 @@ def test_dual_path_flows_agree_at_rounding_level(kind):
     """The recurrent blocks have three ways through the library, selected per process: the default (the band block's fc formed as two
     per-direction shares inside the second band layer and added, with the residual, by the time-axis launch's staging wave; the time
     block's fc inside the 16-wave time kernel), BSRNN_BAND_FC=gemm (the band block's fc + residual as a grouped-GEMM launch, rounds
-    1-2) and BSRNN_TIME_KERNEL=v2 on top of it (round 2's 8-wave time kernel + a GEMM launch for its fc).  Same fp16x2 products, sums
-    taken in a different order for the fc: everything the model returns agrees to 1e-5 of its range; the two GEMM-fc flows that
-    differ only in the time kernel (bit-identical h and state by construction) agree to the same bound."""
+    1-2) and BSRNN_TIME_KERNEL=v3 on top of it (the same time kernel without its fused fc + a GEMM launch for the fc).  Same fp16x2
+    products, sums taken in a different order for the fc: everything the model returns agrees to 1e-5 of its range; the two GEMM-fc
+    flows that differ only in where the time block's fc is formed (bit-identical h and state) agree to the same bound."""
     with tempfile.TemporaryDirectory() as d:
         _, part = run_child(kind, {}, d, "part")
-        _, unpaired = run_child(kind, {"BSRNN_BAND_PAIR": "0", "BSRNN_BAND_GRID": "2d"}, d, "unpaired")
+        _, unpaired = run_child(kind, {"BSRNN_BAND_PAIR": "0"}, d, "unpaired")
         _, fallback = run_child(kind, {"BSRNN_BAND_PAIR": "mismatch"}, d, "fallback")
         _, gemm = run_child(kind, {"BSRNN_BAND_FC": "gemm"}, d, "gemm")
-        _, v2 = run_child(kind, {"BSRNN_BAND_FC": "gemm", "BSRNN_TIME_KERNEL": "v2"}, d, "v2")
-    # BSRNN_BAND_PAIR=0 is round 2's flow entirely (one launch per band layer on the 2-D grid, the fc as a GEMM launch): it must be the
+        _, v3 = run_child(kind, {"BSRNN_BAND_FC": "gemm", "BSRNN_TIME_KERNEL": "v3"}, d, "v3")
+    # BSRNN_BAND_PAIR=0 is round 2's flow entirely (one launch per band layer, the fc as a GEMM launch): it must be the
     # GEMM-fc flow bit for bit - with or without the pair launch the band layers do the same arithmetic on the same numbers
     # (the pair launch with the fc shares against separate launches, bit for bit: tools/band_parts_check.hip)
     for k in part:
@@ -145,7 +145,7 @@ def test_dual_path_flows_agree_at_rounding_level(kind):
     # (guard value 4), runs again with one launch per layer and the context stays on that flow - same numbers as BSRNN_BAND_PAIR=0, rc 0
     for k in part:
         assert np.array_equal(fallback[k], unpaired[k]), k
-    for name, a, b in (("parts vs gemm fc", part, gemm), ("16-wave vs 8-wave time kernel", gemm, v2)):
+    for name, a, b in (("parts vs gemm fc", part, gemm), ("fused vs separate time-block fc", gemm, v3)):
         for k in a:
             rel = maxabs(a[k], b[k]) / np.abs(b[k]).max()
             print("%s, %s: %.2e of the range" % (name, k, rel))

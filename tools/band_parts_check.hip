@@ -44,8 +44,8 @@ static int band(int N, int L, int runs)
     CK(hipMemcpy(x, hx.data(), hx.size() * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(w, hw.data(), nw * 2, hipMemcpyHostToDevice));
     CK(hipMemcpy(wfc, hwfc.data(), nfc * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(b, hb.data(), 512 * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(bfc, hbfc.data(), 64 * 4, hipMemcpyHostToDevice));
-    const dim3 grid((N + 15) / 16, 2), block(256);
-    printf("== band layer 1, N=%d sequences x L=%d positions (%d workgroups)\n", N, L, grid.x * 2);
+    const dim3 grid((((N + 15) / 16 + 7) / 8) * 16), block(256);      // the library's 1-D grid: both directions of eight tiles per 16 workgroups
+    printf("== band layer 1, N=%d sequences x L=%d positions (%d workgroups)\n", N, L, grid.x);
     hipLaunchKernelGGL((band_lstm_h2_kernel<128, false, false>), grid, block, 0, 0, (const float*)x, h, (const uint4*)w, b, N, L, (int*)nullptr, (unsigned long long*)nullptr, (const uint4*)nullptr, (const float*)nullptr);
     CK(hipDeviceSynchronize());
     std::vector<float> hh(nrow * 128), first(nrow * 128), cur(nrow * 128);
@@ -150,10 +150,10 @@ static int pair(int N, int L, int runs)
     CK(hipMemcpy(b1, hb.data(), 512 * 4, hipMemcpyHostToDevice));
     for (auto& v : hbfc) v = urand() * 0.5f;
     CK(hipMemcpy(bfc, hbfc.data(), 64 * 4, hipMemcpyHostToDevice));
-    const dim3 g2((N + 15) / 16, 2), g1((((N + 15) / 16 + 7) / 8) * 16), block(256);
+    const dim3 g1((((N + 15) / 16 + 7) / 8) * 16), block(256);
     printf("== band block as one launch, N=%d sequences x L=%d positions (%d workgroups)\n", N, L, g1.x);
-    hipLaunchKernelGGL((band_lstm_h2_kernel<64, false, false>), g2, block, 0, 0, z, hb0, (const uint4*)w0, b0, N, L, (int*)nullptr, (unsigned long long*)nullptr, (const uint4*)nullptr, (const float*)nullptr);
-    hipLaunchKernelGGL((band_lstm_h2_kernel<128, false, true>), g2, block, 0, 0, (const float*)hb0, p_ref, (const uint4*)w1, b1, N, L, (int*)nullptr, (unsigned long long*)nullptr, (const uint4*)wfc, bfc);
+    hipLaunchKernelGGL((band_lstm_h2_kernel<64, false, false>), g1, block, 0, 0, z, hb0, (const uint4*)w0, b0, N, L, (int*)nullptr, (unsigned long long*)nullptr, (const uint4*)nullptr, (const float*)nullptr);
+    hipLaunchKernelGGL((band_lstm_h2_kernel<128, false, true>), g1, block, 0, 0, (const float*)hb0, p_ref, (const uint4*)w1, b1, N, L, (int*)nullptr, (unsigned long long*)nullptr, (const uint4*)wfc, bfc);
     CK(hipDeviceSynchronize());
     std::vector<uint32_t> ref(nrow * 128), cur(nrow * 128);
     CK(hipMemcpy(ref.data(), p_ref, ref.size() * 4, hipMemcpyDeviceToHost));
@@ -164,7 +164,7 @@ static int pair(int N, int L, int runs)
         CK(hipMemset(p_pair, 0xff, nrow * 128 * 4)); CK(hipMemset(hb0b, 0xff, nrow * 128 * 4));
         CK(hipEventRecord(e0, 0));
         hipLaunchKernelGGL((band_pair_h2_kernel<true>), g1, block, 0, 0, (const float*)z, hb0b, p_pair, (const uint4*)w0, b0, (const uint4*)w1, b1, N, L, flag,
-                           (const uint4*)wfc, bfc, flags, 0);
+                           (const uint4*)wfc, bfc, flags, 0, OvlConsumer{nullptr, 0, 0, nullptr, 0, 2}, (int*)nullptr, 0);
         CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1)); best = std::min(best, ms * 1e3f);
         CK(hipMemcpy(cur.data(), p_pair, cur.size() * 4, hipMemcpyDeviceToHost));

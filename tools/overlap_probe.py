@@ -1,6 +1,6 @@
 """Diagnostic of the overlapped dual path under uneven load: contexts with different BSRNN_OVERLAP settings, same inputs, matrix products on
 a second torch stream starting and stopping; every differing call is localised in the spectrogram domain (rows, first frame, bands).
-    python tools/overlap_probe.py [rows] [frames] [calls] [mode ...]        modes: 0 1 band mask pub (default: 0 1)"""
+    python tools/overlap_probe.py [rows] [frames] [calls] [mode ...]        modes: 0 1 (default: 0 1)"""
 import os, sys
 import numpy as np
 import torch

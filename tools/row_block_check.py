@@ -1,5 +1,6 @@
-# Bit-exactness of a 130-row batch against its two row blocks, repeated (used to bisect the BSRNN_PARTS hazard):
-#   PYTHONPATH=. BSRNN_PARTS=2 python tools/row_block_check.py 40
+# Bit-exactness of a 200-row batch (two concurrent row blocks by bsrnn_separate's own rule) against its two halves, repeated
+# (used to bisect the row-block hazard):
+#   PYTHONPATH=. python tools/row_block_check.py 40
 # For every dirty run it also reports whether a second device-to-host copy of the same device tensor differs from the
 # first (stale lines at copy time) and the sizes of the dirty runs of samples (cache-line granularity?).
 import numpy as np, torch, sys
@@ -7,9 +8,9 @@ from speechseparation_amd import weights
 from speechseparation_amd.bsrnn import BSRNN
 sd = weights.synth_state_dict(None, seed=0)
 m = BSRNN().eval(); m.load_state_dict({k: torch.from_numpy(a.copy()) for k, a in sd.items()}); m = m.to('cuda')
-wave = weights.synth_waveform(130, 16 * 1024 + 9, seed=31)
+wave = weights.synth_waveform(200, 16 * 1024 + 9, seed=31)
 w = torch.from_numpy(wave).cuda()
-h0 = m.separate(w[:65].contiguous()).cpu().numpy(); h1 = m.separate(w[65:].contiguous()).cpu().numpy()
+h0 = m.separate(w[:100].contiguous()).cpu().numpy(); h1 = m.separate(w[100:].contiguous()).cpu().numpy()
 halves = np.concatenate([h0, h1], 0)
 bad = 0; reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 for rep in range(reps):

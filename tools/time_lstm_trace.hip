@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <vector>
 using namespace bsrnn;
+namespace bsrnn { bool force_f32() { return false; } int gemm_mode() { return GEMM_FP16X2; } }
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 int main()
 {

@@ -1,6 +1,6 @@
-// Measurement / validation only: the counter-phase time-axis LSTM kernel (time_lstm_h2w_kernel) against the round-2 kernel
-// (time_lstm_h2_kernel): bit-identity of h1 and of the carried state without the fused fc, the fused fc + residual against a
-// double-precision evaluation of fc(h1) + b + x, timing, in-kernel phase stamps.
+// Measurement / validation only: the counter-phase time-axis LSTM kernel (time_lstm_h2w_kernel): the carried state with and
+// without the fused fc bit for bit, the fused fc + residual against a double-precision evaluation of fc(h1) + b + x, the
+// eight-sequence kernel (time_lstm_h2w8_kernel) bit for bit against the four-sequence one, timing, in-kernel phase stamps.
 //   hipcc -O3 --offload-arch=gfx950 -fno-slp-vectorize -o build/time_lstm_v3_bench tools/time_lstm_v3_bench.hip
 #include "../speechseparation_amd/csrc/lstm.hip"
 #include <algorithm>
@@ -23,10 +23,10 @@ static int run(int R, int T, int K, bool with_state, int reps)
     const int N = R * K;
     const size_t nz = (size_t)R * T * K * 64, nst = (size_t)4 * N * 64;
     const size_t nw = (size_t)2 * 4 * 4 * 4 * 2 * 64 * 8, nfc = (size_t)4 * 2 * 2 * 64 * 8;
-    float *z, *h_old, *h_new, *h_fus, *b, *bfc, *st_in, *so_old, *so_new, *so_fus; uint16_t *w, *wfc; unsigned long long* dbg;
-    CK(hipMalloc(&z, nz * 4)); CK(hipMalloc(&h_old, nz * 4)); CK(hipMalloc(&h_new, nz * 4)); CK(hipMalloc(&h_fus, nz * 4));
+    float *z, *h_new, *h_fus, *b, *bfc, *st_in, *so_new, *so_fus; uint16_t *w, *wfc; unsigned long long* dbg;
+    CK(hipMalloc(&z, nz * 4)); CK(hipMalloc(&h_new, nz * 4)); CK(hipMalloc(&h_fus, nz * 4));
     CK(hipMalloc(&w, nw * 2)); CK(hipMalloc(&wfc, nfc * 2)); CK(hipMalloc(&b, 512 * 4)); CK(hipMalloc(&bfc, 64 * 4));
-    CK(hipMalloc(&st_in, nst * 4)); CK(hipMalloc(&so_old, nst * 4)); CK(hipMalloc(&so_new, nst * 4)); CK(hipMalloc(&so_fus, nst * 4));
+    CK(hipMalloc(&st_in, nst * 4)); CK(hipMalloc(&so_new, nst * 4)); CK(hipMalloc(&so_fus, nst * 4));
     CK(hipMalloc(&dbg, 4 * 16 * 4 * 8));
     std::vector<float> hz(nz), hb(512), hbfc(64), hst(nst);
     for (auto& v : hz) v = urand();
@@ -39,37 +39,33 @@ static int run(int R, int T, int K, bool with_state, int reps)
     CK(hipMemcpy(z, hz.data(), nz * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(w, hw.data(), nw * 2, hipMemcpyHostToDevice));
     CK(hipMemcpy(wfc, hwfc.data(), nfc * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(b, hb.data(), 512 * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(bfc, hbfc.data(), 64 * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(st_in, hst.data(), nst * 4, hipMemcpyHostToDevice));
-    CK(hipMemset(h_old, 0xff, nz * 4)); CK(hipMemset(h_new, 0xff, nz * 4)); CK(hipMemset(h_fus, 0xff, nz * 4));
+    CK(hipMemset(h_new, 0xff, nz * 4)); CK(hipMemset(h_fus, 0xff, nz * 4));
     const float* sin_ = with_state ? st_in : nullptr;
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    const dim3 grid((N + 3) / 4), block(512), block16(1024);
+    const dim3 grid((N + 3) / 4), block16(1024);
     printf("== R=%d T=%d K=%d (N=%d sequences, %d workgroups) state_in=%d\n", R, T, K, N, (N + 3) / 4, (int)with_state);
-    float best[3] = {1e9f, 1e9f, 1e9f};
+    float best[2] = {1e9f, 1e9f};
     for (int rep = 0; rep < reps; ++rep)
-        for (int v = 0; v < 3; ++v) {
+        for (int v = 0; v < 2; ++v) {
             CK(hipEventRecord(e0, 0));
-            if (v == 0) hipLaunchKernelGGL(time_lstm_h2_kernel<false>, grid, block, 0, 0, z, h_old, (const uint4*)w, b, sin_, so_old, R, T, K, (int*)nullptr, dbg);
-            if (v == 1) hipLaunchKernelGGL((time_lstm_h2w_kernel<false, false>), grid, block16, 0, 0, z, h_new, (const uint4*)w, b, (const uint4*)nullptr, (const float*)nullptr, sin_, so_new, R, T, K, (int*)nullptr, dbg);
-            if (v == 2) hipLaunchKernelGGL((time_lstm_h2w_kernel<true, false>), grid, block16, 0, 0, z, h_fus, (const uint4*)w, b, (const uint4*)wfc, bfc, sin_, so_fus, R, T, K, (int*)nullptr, dbg);
+            if (v == 0) hipLaunchKernelGGL((time_lstm_h2w_kernel<false, false>), grid, block16, 0, 0, z, h_new, (const uint4*)w, b, (const uint4*)nullptr, (const float*)nullptr, sin_, so_new, R, T, K, (int*)nullptr, dbg);
+            if (v == 1) hipLaunchKernelGGL((time_lstm_h2w_kernel<true, false>), grid, block16, 0, 0, z, h_fus, (const uint4*)w, b, (const uint4*)wfc, bfc, sin_, so_fus, R, T, K, (int*)nullptr, dbg);
             CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
             float ms; CK(hipEventElapsedTime(&ms, e0, e1));
             if (rep) best[v] = std::min(best[v], ms * 1e3f);
         }
     CK(hipGetLastError());
-    printf("   launch time (best of %d): round-2 kernel %.1f us | 16 waves %.1f us | 16 waves + fused fc %.1f us\n", reps - 1, best[0], best[1], best[2]);
-    std::vector<uint32_t> a(nz), c(nz);
+    printf("   launch time (best of %d): 16 waves %.1f us | 16 waves + fused fc %.1f us\n", reps - 1, best[0], best[1]);
+    std::vector<uint32_t> c(nz);
     std::vector<float> f(nz), ho(nz);
-    CK(hipMemcpy(a.data(), h_old, nz * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(c.data(), h_new, nz * 4, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(f.data(), h_fus, nz * 4, hipMemcpyDeviceToHost)); memcpy(ho.data(), a.data(), nz * 4);
-    size_t nd = 0;
-    for (size_t i = 0; i < nz; ++i) nd += a[i] != c[i];
-    std::vector<uint32_t> sa(nst), sb(nst), sc(nst);
-    CK(hipMemcpy(sa.data(), so_old, nst * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(sb.data(), so_new, nst * 4, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(sc.data(), so_fus, nst * 4, hipMemcpyDeviceToHost));
-    size_t nds = 0, ndf = 0;
-    for (size_t i = 0; i < nst; ++i) { nds += sa[i] != sb[i]; ndf += sa[i] != sc[i]; }
-    printf("   h1: %zu of %zu words differ from the round-2 kernel; state_out: %zu (plain) / %zu (fused) of %zu differ\n", nd, nz, nds, ndf, nst);
-    // fused output against fc(h1) + b + x in double (h1 = the round-2 kernel's, which the plain kernel reproduces bit for bit)
+    CK(hipMemcpy(c.data(), h_new, nz * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(f.data(), h_fus, nz * 4, hipMemcpyDeviceToHost)); memcpy(ho.data(), c.data(), nz * 4);
+    std::vector<uint32_t> sb(nst), sc(nst);
+    CK(hipMemcpy(sb.data(), so_new, nst * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(sc.data(), so_fus, nst * 4, hipMemcpyDeviceToHost));
+    size_t ndf = 0;
+    for (size_t i = 0; i < nst; ++i) ndf += sb[i] != sc[i];
+    printf("   state_out: %zu of %zu words differ between the plain and the fused kernel\n", ndf, nst);
+    // fused output against fc(h1) + b + x in double (h1 = the plain kernel's)
     double worst = 0; size_t bad = 0, checked = 0;
     for (int nn = 0; nn < N; nn += (N > 64 ? 5 : 1))
         for (int t = 0; t < T; ++t) {
@@ -153,9 +149,9 @@ static int run(int R, int T, int K, bool with_state, int reps)
             printf("     wave  8 (helper 0): per group of two: staging + waits %.0f ns, input half %.0f ns\n", hd[8 * 4] * 10.0 / G2, hd[8 * 4 + 2] * 10.0 / G2);
             printf("     wave 12 (helper 1): per group of two: waits %.0f ns, input half %.0f ns, fc %.0f ns\n", hd[12 * 4] * 10.0 / G2, hd[12 * 4 + 2] * 10.0 / G2, hd[12 * 4 + 1] * 10.0 / G2);
         }
-    const int fail = (nd != 0) + (nds != 0) + (ndf != 0) + (bad != 0) + (untouched != 0) + (nd8 != 0) + (ndf8 != 0) + (nds8 != 0) + (ndsf8 != 0);
-    hipFree(z); hipFree(h_old); hipFree(h_new); hipFree(h_fus); hipFree(w); hipFree(wfc); hipFree(b); hipFree(bfc);
-    hipFree(st_in); hipFree(so_old); hipFree(so_new); hipFree(so_fus); hipFree(dbg);
+    const int fail = (ndf != 0) + (bad != 0) + (untouched != 0) + (nd8 != 0) + (ndf8 != 0) + (nds8 != 0) + (ndsf8 != 0);
+    hipFree(z); hipFree(h_new); hipFree(h_fus); hipFree(w); hipFree(wfc); hipFree(b); hipFree(bfc);
+    hipFree(st_in); hipFree(so_new); hipFree(so_fus); hipFree(dbg);
     return fail;
 }
 
