@@ -102,8 +102,19 @@ int  bsrnn_get_range_policy(const bsrnn_ctx* ctx);
 /* 1 when the committed context runs the per-band MLP chains (bsrnn.py:404-415, :420-443) as fused launches (one workgroup =
  * one band's five Linear layers, intermediates in LDS; the default), 0 when it runs one grouped launch per layer: the
  * exact-fp32 mode, BSRNN_MLP=layers (A/B), or a band table with a band too wide for the fused kernel's LDS image
- * (more than 768 columns).  Same arithmetic, bit-identical results either way. */
+ * (more than 768 columns).  The same fp16x2 products either way; a band whose chain runs the 32 x 32 x 16 geometry without the ragged
+ * split (bsrnn_chain_geometry) gives results bit-identical to the per-layer flow, the 16 x 16 x 32 geometries and the ragged split sum
+ * in another order and agree with it at fp32 rounding level. */
 int  bsrnn_mlp_fused(const bsrnn_ctx* ctx);
+/* Geometry of the fused MLP chain of one band of the committed context (measurement / test support).  chain: 0 = bandFCs_pre + bandFCs
+ * (bsrnn.py:404-415), 1 = bandFCs_back + bandFCs_back_post (bsrnn.py:420-443); band: 0 .. K-1.  out[6]:
+ *   out[0] frame rows per workgroup; out[1] MFMA shape, 32 (32 x 32 x 16) or 16 (16 x 16 x 32); out[2] RT, row tiles per wave group
+ *   (of 32 rows in the 32 shape, of 16 in the 16 shape); out[3] NW, waves per group (8 / NW groups); out[4] bit l set when the last
+ *   feature tile of layer l is split over the k-steps of all eight waves (the ragged split); out[5] 1 when the 16 shape zeroes the
+ *   k-units of its LDS image that a layer's K loop reads but no layer output covers (a layer width N % 32 != 0; always at 64 rows).
+ * A zero-width band: all six 0 (no matrix work in either chain).  A context that runs the per-layer flow (bsrnn_mlp_fused() == 0):
+ * all six -1 for every band.  BSRNN_EARG for a bad chain or band, BSRNN_ESTATE on a host-only or uncommitted context. */
+int  bsrnn_chain_geometry(const bsrnn_ctx* ctx, int32_t chain, int32_t band, int32_t out[6]);
 /* How this context runs the dual path of large calls (bsrnn.py:352-356, the four recurrent blocks): 1 = overlapped - the second band
  * block is launched beside the first (causal) time-axis launch and the mask MLPs beside the second, on an auxiliary stream of the
  * context, each workgroup waiting for the frames of its own rows (results are bit-identical to 0); 0 = one launch after the other

@@ -19,7 +19,7 @@ SYMBOLS = [
     "bsrnn_stft", "bsrnn_istft", "bsrnn_separate", "bsrnn_stream_create", "bsrnn_stream_destroy", "bsrnn_stream_reset",
     "bsrnn_stream_step", "bsrnn_stream_step_host", "bsrnn_stream_get_state", "bsrnn_set_profiling", "bsrnn_stage_count",
     "bsrnn_stage_name", "bsrnn_stage_times", "bsrnn_dev_alloc", "bsrnn_dev_free", "bsrnn_copy_h2d", "bsrnn_copy_d2h",
-    "bsrnn_sync", "bsrnn_evaluate", "bsrnn_io_count", "bsrnn_io_info", "bsrnn_mlp_fused",
+    "bsrnn_sync", "bsrnn_evaluate", "bsrnn_io_count", "bsrnn_io_info", "bsrnn_mlp_fused", "bsrnn_chain_geometry",
     "bsrnn_lstm_train_forward", "bsrnn_lstm_train_backward", "bsrnn_linear_train_forward", "bsrnn_linear_train_backward",
     "bsrnn_istft_backward", "bsrnn_adamw_step", "bsrnn_adamw_step_multi", "bsrnn_adamw_step_multi_dev",
     "bsrnn_linear_group_train_forward", "bsrnn_linear_group_train_backward",
@@ -56,6 +56,7 @@ def _load():
         "bsrnn_set_range_policy": (C.c_int, [vp, i32]),
         "bsrnn_get_range_policy": (C.c_int, [vp]),
         "bsrnn_mlp_fused": (C.c_int, [vp]),
+        "bsrnn_chain_geometry": (C.c_int, [vp, i32, i32, C.POINTER(i32)]),
         "bsrnn_overlap_state": (C.c_int, [vp]),
         "bsrnn_debug_peek": (C.c_int, [vp, i32, vp, i64]),
         "bsrnn_debug_counter": (C.c_longlong, [i32]),

@@ -176,6 +176,14 @@ class BSRNN(nn.Module):
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         return "fused" if _lib.bsrnn_mlp_fused(self._context(dev)) == 1 else "layers"
 
+    def chain_geometry(self, chain, band, device=None):
+        """(rows per workgroup, MFMA shape, RT, NW, rag layer bits, pad zeroing) of band `band`'s fused chain `chain` (0 split,
+        1 mask); all 0 for a zero-width band, all -1 under the per-layer flow (include/bsrnn_hip.h, bsrnn_chain_geometry)."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        out = (ctypes.c_int32 * 6)()
+        _check(_lib.bsrnn_chain_geometry(self._context(dev), chain, band, out))
+        return tuple(out)
+
     def overlap_state(self, device=None):
         """How this model's context runs the dual path of large calls: 1 overlapped (default), 0 launch after launch (BSRNN_OVERLAP=0),
         2 switched off after a consumer's wait expired (include/bsrnn_hip.h, bsrnn_overlap_state)."""

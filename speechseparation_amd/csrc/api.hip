@@ -1018,6 +1018,23 @@ void bsrnn_destroy(bsrnn_ctx* c)
 
 int bsrnn_n_bands(const bsrnn_ctx* c) { return c ? c->K : -1; }
 int bsrnn_mlp_fused(const bsrnn_ctx* c) { return c ? (c->fused ? 1 : 0) : -1; }
+int bsrnn_chain_geometry(const bsrnn_ctx* c, int32_t chain, int32_t band, int32_t out[6])
+{
+    if (!c || !out || (chain != CHAIN_SPLIT && chain != CHAIN_MASK) || band < 0 || band >= c->K)
+        return fail(BSRNN_EARG, "bsrnn_chain_geometry: bad arguments");
+    if (c->device < 0 || !c->committed) return fail(BSRNN_ESTATE, "bsrnn_chain_geometry: no committed device context");
+    const int v = !c->fused ? -1 : 0;
+    for (int i = 0; i < 6; ++i) out[i] = v;
+    if (!c->fused || c->widths[band] == 0) return 0;
+    for (const ChainDesc& d : c->h_chain[chain]) {
+        if (d.constant || d.z_off != band * HID) continue;
+        out[0] = chain_rows(d); out[1] = d.RT >= 3 ? 16 : 32; out[2] = d.RT; out[3] = d.NW;
+        for (int l = 0; l < CHAIN_LAYERS; ++l) out[4] |= d.L[l].rag ? 1 << l : 0;
+        out[5] = d.zpad;
+        return 0;
+    }
+    return fail(BSRNN_ESTATE, "bsrnn_chain_geometry: band %d has no descriptor in chain %d", band, chain);
+}
 int bsrnn_device(const bsrnn_ctx* c) { return c ? c->device : -1; }
 int bsrnn_debug_peek(bsrnn_ctx* c, int32_t which, float* host_out, int64_t nfloats)
 {
@@ -1265,18 +1282,21 @@ int bsrnn_commit_params(bsrnn_ctx* c)
                 int rt16 = try48 ? 3 : 5, ctr = try48 ? 6 : 3;
                 int u48 = 0, maxft = 0, nb48 = 0;
                 bool whole = true;                                   // every layer's width a multiple of 16 (no ragged tile of 16)
+                bool gap = false;                                    // a layer's output (whole tiles of 16) ends short of the next layer's
+                                                                     // K loop (whole k-steps of 32): N % 32 != 0
                 for (int l = 0; l < CHAIN_LAYERS; ++l) {
                     const int K32 = (ld[l].Kd + 31) / 32, FT = (ld[l].N + 15) / 16;
                     u48 = imax(u48, 4 * K32);
                     if (l + 1 < CHAIN_LAYERS) u48 = imax(u48, 2 * FT);
                     maxft = imax(maxft, FT); nb48 += 16 * FT;
                     whole = whole && ld[l].N % 16 == 0;
+                    gap = gap || (l + 1 < CHAIN_LAYERS && ld[l].N % 32 != 0);
                 }
                 if (try80 && !(whole && maxft % 8 == 0 && maxft <= 8 * ctr && 2 * u48 * (16 * rt16) * 16 <= CHAIN_LDS_EX)) {
                     try64 = true; rt16 = 4; ctr = 5;
                 }
                 if (2 * u48 * (16 * rt16) * 16 <= CHAIN_LDS_EX && maxft <= 8 * ctr && nb48 * 4 <= CHAIN_LDS_BIAS && (try48 || try64 || (whole && maxft % 8 == 0))) {
-                    g48 = true; RT = rt16; GR = 1; units = u48; nbias = 0; cost = 0;
+                    g48 = true; RT = rt16; GR = 1; units = u48; nbias = 0; cost = 0; d.zpad = rt16 == 4 || gap;   // (the 64-row body always zeroes)
                     for (int l = 0; l < CHAIN_LAYERS; ++l) {
                         d.L[l].K16 = (ld[l].Kd + 31) / 32; d.L[l].NTL = (ld[l].N + 15) / 16;
                         d.L[l].bias_off = nbias; nbias += 16 * d.L[l].NTL;

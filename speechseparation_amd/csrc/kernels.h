@@ -96,6 +96,10 @@ struct ChainDesc {
     int a8;              // band width in columns rounded up to 8: what is written to P / Y (pad columns exactly zero)
     int z_off;           // first column of the band inside a Z row
     int constant;        // zero-width band (TrainableConstantModule, bsrnn.py:12-24): Z[:, z_off .. +64) = bias[0 .. 64)
+    int zpad;            // 16 x 16 geometry: the image's k-units that no layer output covers but the next layer's K loop reads are
+                         // zeroed first (chain_body48 ZPAD): set when a layer feeding another has N % 32 != 0 (its output ends
+                         // after an odd number of feature tiles of 16, the next K loop runs whole k-steps of 32); always on the
+                         // 64-row body
 };
 struct ChainLaunch {
     const ChainDesc* desc;   // device array

@@ -503,8 +503,10 @@ __device__ __forceinline__ void chain_body(const ChainLaunch& g, const ChainDesc
 // RT row tiles of 16 (48 rows: the 768-wide band; 80 rows: bands whose image leaves room for five - the 384-wide band, 24 feature
 // tiles = three per wave where the 32 x 32 geometry had twelve tiles for eight waves and 64 rows per weight fragment), CTR = feature
 // tiles per wave the held-tile registers are sized for, PDR = k-steps of weight fragments in flight.
-// ZPAD: the band's widths are not multiples of 16 / 32 (the 514-wide band on four row tiles): the k-units of the image that no layer's
-// output covers but a later layer's K loop reads (against zero weights) are zeroed once - uninitialised LDS may hold NaN patterns.
+// ZPAD: a layer feeding another has a width N % 32 != 0 (the 514-wide band on four row tiles; on three, bands of 289 - 383 bins
+// unless 2 w % 32 == 0, ChainDesc::zpad): its output, whole feature tiles of 16, ends one tile short of the next layer's K loop
+// (whole k-steps of 32).  The k-units of the image that no layer's output covers but a later layer's K loop reads (against zero
+// weights) are zeroed once - uninitialised LDS may hold NaN patterns.
 template <int CHAIN, int TERMS, int RT = 3, int CTR = 6, int PDR = CHAIN_PD48, int TP = 2, bool ZPAD = false>
 __device__ __forceinline__ void chain_body48(const ChainLaunch& g, const ChainDesc* const dp, const int row0, char* const smem)
 {
@@ -800,7 +802,8 @@ __global__ __launch_bounds__(512, 2) void mlp_chain_kernel(ChainLaunch g)
     const int RT = dp->RT, GR = 8 / dp->NW;
     // (every geometry ends in `return`: with an else-if chain and one join the structurizer lays the bodies out one behind the other
     //  and keeps values of the later ones - the thread index, for one - alive through the earlier ones' loops: spills at 256 VGPRs)
-    if (RT == 3) { chain_body48<CHAIN, TERMS>(g, dp, row0, smem); return; }
+    if (RT == 3 && !dp->zpad) { chain_body48<CHAIN, TERMS>(g, dp, row0, smem); return; }        // (the 768-wide band: whole k-steps of 32)
+    if (RT == 3) { chain_body48<CHAIN, TERMS, 3, 6, CHAIN_PD48, 2, true>(g, dp, row0, smem); return; }   // the other widths of the 48-row class
     if (RT == 5) { chain_body48<CHAIN, TERMS, 5, 3, 2, (CHAIN == CHAIN_SPLIT ? 1 : 2)>(g, dp, row0, smem); return; }
     if (RT == 4) { chain_body48<CHAIN, TERMS, 4, 5, CHAIN_PD64, CHAIN_TP64, true>(g, dp, row0, smem); return; }
     if (GR == 8) { chain_body<CHAIN, TERMS, 1, 8>(g, dp, row0, smem); return; }

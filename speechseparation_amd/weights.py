@@ -61,7 +61,8 @@ def synth_state_dict(v=None, seed=0, lstm_gain=1.0, const_gain=1.0):
     """
     out = OrderedDict()
     H = _spec.BAND_FEATURES
-    for key, shape in _spec.param_spec(v).items():
+    ps = _spec.param_spec(v)
+    for key, shape in ps.items():
         n = int(np.prod(shape)) if len(shape) else 1
         if n == 0:
             out[key] = np.zeros(shape, dtype=np.float32)
@@ -74,7 +75,7 @@ def synth_state_dict(v=None, seed=0, lstm_gain=1.0, const_gain=1.0):
         elif key.endswith(".weight"):
             bound = 1.0 / np.sqrt(shape[1])
         else:  # Linear bias: fan_in of the matching weight
-            wshape = _spec.param_spec(v)[key[:-len("bias")] + "weight"]
+            wshape = ps[key[:-len("bias")] + "weight"]
             bound = 1.0 / np.sqrt(wshape[1])
         out[key] = ((2.0 * u - 1.0) * bound).astype(np.float32).reshape(shape)
     return out
