@@ -159,13 +159,19 @@ int  bsrnn_io_info(const bsrnn_ctx* ctx, int32_t index, int32_t C, const char** 
                    int64_t dims[4], int32_t* ndim);
 
 /* ---- model entry points ---------------------------------------------------------------
+ * Aliasing (all model entry points): under BSRNN_RANGE_EXACT a call that left the fp16 range is run again from the same inputs,
+ * after its first run may already have written its outputs.  So an output buffer must not share any byte with an input the re-run
+ * reads (a range overlap, not only an equal pointer): such a call returns BSRNN_EARG, naming the re-run.  Each entry point states
+ * which pairs that concerns; under BSRNN_RANGE_DEFERRED there is no re-run and the buffers may alias as before.
  * bsrnn_forward            = BSRNN.forward            (bsrnn.py:385-443)
- *     x_dev [C, 2050, T] -> y_dev [C, 2050, T]   (y = x * mask; x is not modified)
+ *     x_dev [C, 2050, T] -> y_dev [C, 2050, T]   (y = x * mask; x is not modified unless y or mask
+ *     overlaps it).  y and mask MAY overlap x under either policy (in place): the re-run starts from the library's own copy
+ *     of x, made before anything is written.
  * bsrnn_forward_recurrent  = BSRNN.forward_recurrent  (bsrnn.py:445-510)
  *     x_dev [C, 2050], state_in_dev [4, 2, C*K, 64] -> y_dev [C, 2050], state_out_dev (same
- *     shape; a DIFFERENT buffer under BSRNN_RANGE_EXACT - BSRNN_EARG otherwise: a call that left the
- *     fp16 range is run again from state_in_dev -, may alias it under BSRNN_RANGE_DEFERRED; the same
- *     holds for bsrnn_forward_chunk and bsrnn_dual_path).  State slabs: 0/1 = h/c of lstms.1, 2/3 = h/c of
+ *     shape; under BSRNN_RANGE_EXACT neither state_out_dev nor y_dev may overlap state_in_dev - BSRNN_EARG otherwise: a call
+ *     that left the fp16 range is run again from state_in_dev -; they may alias it under BSRNN_RANGE_DEFERRED; y may overlap x
+ *     as in bsrnn_forward.  The same holds for bsrnn_forward_chunk).  State slabs: 0/1 = h/c of lstms.1, 2/3 = h/c of
  *     lstms.3; dim 1 = LSTM layer; dim 2 = c*K + k.
  * bsrnn_forward_chunk      = L consecutive forward_recurrent steps in one call (BASELINE.json
  *     config 3): x_dev [C, 2050, L], state carried causally; L = 1 equals forward_recurrent.
@@ -178,7 +184,8 @@ int  bsrnn_forward_chunk(bsrnn_ctx* ctx, const float* x_dev, const float* state_
                          float* y_dev, float* state_out_dev, int32_t C, int32_t L, void* stream);
 
 /* `self.lstms(z)` alone (bsrnn.py:352-356, :417): z_dev [C, T, K, 64] -> z_out_dev.  state
- * pointers may be NULL (zero initial state, final state discarded). */
+ * pointers may be NULL (zero initial state, final state discarded).  Under BSRNN_RANGE_EXACT neither z_out_dev nor state_out_dev
+ * may overlap z_dev or state_in_dev (BSRNN_EARG: the re-run reads both again); under BSRNN_RANGE_DEFERRED they may. */
 int  bsrnn_dual_path(bsrnn_ctx* ctx, const float* z_dev, float* z_out_dev,
                      const float* state_in_dev, float* state_out_dev,
                      int32_t C, int32_t T, void* stream);
@@ -252,7 +259,9 @@ int  bsrnn_adamw_step_multi_dev(bsrnn_ctx* ctx, float* const* p_dev, const float
  *                center/reflect, onesided, re/im interleaved.  n must be > 1024.
  * bsrnn_istft  = infer.py:35-37: y_dev [R, 2050, T] -> wave_out_dev [R, (T-1)*1024].
  * bsrnn_separate = the whole sandwich fused on the device (frame-major internally, no
- *                [C,2050,T] round trips): wave_dev [R, n] -> wave_out_dev [R, (T-1)*1024]. */
+ *                [C,2050,T] round trips): wave_dev [R, n] -> wave_out_dev [R, (T-1)*1024].  Under
+ *                BSRNN_RANGE_EXACT wave_out_dev must not overlap wave_dev (BSRNN_EARG: the re-run reads the waveform again);
+ *                under BSRNN_RANGE_DEFERRED it is not checked (row blocks run concurrently: an overlap is still unsafe). */
 int  bsrnn_stft(bsrnn_ctx* ctx, const float* wave_dev, float* x_dev, int32_t R, int64_t n, void* stream);
 int  bsrnn_istft(bsrnn_ctx* ctx, const float* y_dev, float* wave_out_dev, int32_t R, int32_t T, void* stream);
 /* Backward of bsrnn_istft for the training step (the loss of m_dataset.py:211-216 has a waveform term): dwave_dev
@@ -273,7 +282,8 @@ int  bsrnn_separate(bsrnn_ctx* ctx, const float* wave_dev, float* wave_out_dev, 
  *   SISDR         scale-invariant SDR of torchmetrics (zero_mean = False, eps = float32 epsilon), mean over rows;
  *   L1_TIME / L1_RE / L1_IM   the three loss terms;
  *   SEPARATION_DB 10 ln(sum mix^2 / sum (mix - x)^2) over all rows (natural log, as infer.py:47 prints it).
- * est_out_dev (optional) receives the separated signal [R, (T-1)*1024].  Synchronous: returns when the
+ * est_out_dev (optional) receives the separated signal [R, (T-1)*1024]; it must not overlap mix_dev or speech_dev under
+ * either policy (BSRNN_EARG: the metrics, and a re-run, read them after the estimate is written).  Synchronous: returns when the
  * numbers are on the host.  Reductions accumulate in double on the device; rows are independent, so any R
  * works (the reference's un-interleave hard-codes 2 rows, m_dataset.py:192). */
 #define BSRNN_M_LOSS          0
@@ -294,7 +304,8 @@ int  bsrnn_evaluate(bsrnn_ctx* ctx, const float* mix_dev, const float* speech_de
  * bsrnn_stream_create does ALL first-use work (allocations, loading every kernel, and - with BSRNN_STREAM_GRAPH=1 - capturing
  * and instantiating the step's hipGraphs: two throw-away steps on zero input, carry zeroed again afterwards), so that the first
  * bsrnn_stream_step* call costs what every later one costs.
- * bsrnn_stream_step: chunk_dev [C, 1024] -> out_dev [C, 1024] (delayed by one chunk):
+ * bsrnn_stream_step: chunk_dev [C, 1024] -> out_dev [C, 1024] (delayed by one chunk; out_dev may overlap chunk_dev, wholly or
+ *     partly: under BSRNN_RANGE_EXACT such a chunk is copied aside first, so that a re-run still sees it):
  *     rfft(buf*hann) -> forward_recurrent -> irfft -> 2-slot overlap-add / sum(window).
  * bsrnn_stream_step_host: same with host buffers, synchronous (used by the LADSPA plugin);
  *     `mix` applies the plugin's wet/dry control on the spectrum (speech-ladspa-onnx.cpp:

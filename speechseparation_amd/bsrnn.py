@@ -304,14 +304,20 @@ class BSRNN(nn.Module):
         return out if y.is_cuda else out.cpu()
 
     def separate(self, waveform, out=None):
-        """STFT -> forward -> iSTFT fused on the device: [R, n] -> [R, (n//1024)*1024]."""
+        """STFT -> forward -> iSTFT fused on the device: [R, n] -> [R, (n//1024)*1024].  `out`, if given, must be a contiguous
+        float32 tensor of exactly that shape on the call's device (the kernels write it whole) and must not overlap the waveform."""
         dev = self._device_for(waveform)
         w = self._prep(waveform, dev)
         R, n = w.shape
+        shape = (R, (n // _spec.HOP) * _spec.HOP)
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev
+                                or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError("separate: out must be a contiguous float32 tensor %s on %s, got %s" % (
+                shape, dev, "%s %s on %s" % (tuple(out.shape), out.dtype, out.device) if isinstance(out, torch.Tensor) else type(out).__name__))
         with torch.cuda.device(dev):
             ctx = self._context(dev)
             if out is None:
-                out = torch.empty((R, (n // _spec.HOP) * _spec.HOP), device=dev, dtype=torch.float32)
+                out = torch.empty(shape, device=dev, dtype=torch.float32)
             _check(_lib.bsrnn_separate(ctx, _ptr(w), _ptr(out), R, n, _stream_ptr(dev)))
         return out if waveform.is_cuda else out.cpu()
 

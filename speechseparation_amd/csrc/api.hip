@@ -800,6 +800,14 @@ int check_range(bsrnn_ctx* c)
     }
     return 0;
 }
+// True when the byte ranges [a, a + na) and [b, b + nb) share a byte (null pointers share none).  A call whose re-run (finish_call)
+// reads an input that the first run's outputs may have overwritten is refused on this test, not just on pointer equality.
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
 // End of a model entry point under the default range policy (include/bsrnn_hip.h): wait for the call's own kernels, look at the
 // guard word the fp16x2 kernels set when an operand left the fp16 range, and if it is set run the call again on the library's
 // exact-fp32 kernels (fp32 weights are always resident; no range limit) before returning - never wrong numbers with rc 0.
@@ -1585,8 +1593,10 @@ int bsrnn_forward(bsrnn_ctx* c, const float* x, float* y, float* mask, int32_t C
     const size_t M = (size_t)C * T;
     if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M)) || (rc = ensure_ovl(c, C, T))) return rc;
     if (mask && (rc = ensure_tap(c, M))) return rc;
-    auto run = [&]() -> int {
-        { StageScope sc(c, ST_LAYOUT, s); launch_to_frame_major(c->tb, x, c->Xf, C, T, s); }
+    // The re-run (finish_call) starts from the frame-major copy Xf of the first run, which nothing in run_model writes: y and mask
+    // may overlap x (an in-place call) and the re-run still sees the caller's input.
+    auto run = [&](bool layout) -> int {
+        if (layout) { StageScope sc(c, ST_LAYOUT, s); launch_to_frame_major(c->tb, x, c->Xf, C, T, s); }
         if (int rc2 = run_model(c, c->Xf, c->Yf, mask ? c->d_tap : nullptr, C, T, nullptr, nullptr, s)) return rc2;
         {
             StageScope sc(c, ST_LAYOUT, s);
@@ -1596,8 +1606,8 @@ int bsrnn_forward(bsrnn_ctx* c, const float* x, float* y, float* mask, int32_t C
         HIP_TRY(hipGetLastError());
         return 0;
     };
-    if ((rc = run())) return rc;
-    return finish_call(c, s, run);
+    if ((rc = run(true))) return rc;
+    return finish_call(c, s, [&]() -> int { return run(false); });
 }
 
 int bsrnn_forward_chunk(bsrnn_ctx* c, const float* x, const float* state_in, float* y, float* state_out,
@@ -1610,17 +1620,19 @@ int bsrnn_forward_chunk(bsrnn_ctx* c, const float* x, const float* state_in, flo
     ENTER_CALL(c, s);
     const size_t M = (size_t)C * L;
     if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M)) || (rc = ensure_ovl(c, C, L))) return rc;
-    if (state_in == state_out && c->range_policy == BSRNN_RANGE_EXACT)
-        return fail(BSRNN_EARG, "bsrnn_forward_chunk: state_in and state_out must be different buffers (a call that leaves the fp16 range is run again from state_in)");
-    auto run = [&]() -> int {
-        { StageScope sc(c, ST_LAYOUT, s); launch_to_frame_major(c->tb, x, c->Xf, C, L, s); }
+    // The re-run reads state_in again (and x through its frame-major copy Xf, as bsrnn_forward): no output may overlap state_in.
+    const size_t ns = (size_t)4 * 2 * C * c->K * HID * sizeof(float), ny = (size_t)C * F2 * L * sizeof(float);
+    if (c->range_policy == BSRNN_RANGE_EXACT && (ranges_overlap(state_in, ns, state_out, ns) || ranges_overlap(state_in, ns, y, ny)))
+        return fail(BSRNN_EARG, "bsrnn_forward_chunk: state_out and y must not overlap state_in (a call that leaves the fp16 range is run again from state_in)");
+    auto run = [&](bool layout) -> int {
+        if (layout) { StageScope sc(c, ST_LAYOUT, s); launch_to_frame_major(c->tb, x, c->Xf, C, L, s); }
         if (int rc2 = run_model(c, c->Xf, c->Yf, nullptr, C, L, state_in, state_out, s)) return rc2;
         { StageScope sc(c, ST_LAYOUT, s); launch_from_frame_major(c->tb, c->Yf, y, C, L, s); }
         HIP_TRY(hipGetLastError());
         return 0;
     };
-    if ((rc = run())) return rc;
-    return finish_call(c, s, run);
+    if ((rc = run(true))) return rc;
+    return finish_call(c, s, [&]() -> int { return run(false); });
 }
 
 int bsrnn_forward_recurrent(bsrnn_ctx* c, const float* x, const float* state_in, float* y, float* state_out,
@@ -1640,8 +1652,12 @@ int bsrnn_dual_path(bsrnn_ctx* c, const float* z, float* z_out, const float* sta
     const int M = C * T, K = c->K;
     if ((rc = ensure_ws(c, M))) return rc;
     const size_t nz = (size_t)M * K * HID;
-    if (state_in && state_in == state_out && c->range_policy == BSRNN_RANGE_EXACT)
-        return fail(BSRNN_EARG, "bsrnn_dual_path: state_in and state_out must be different buffers");
+    // The re-run copies z in again and reads state_in again: neither may overlap an output of the call.
+    const size_t bz = nz * sizeof(float), bs = (size_t)4 * 2 * C * K * HID * sizeof(float);
+    if (c->range_policy == BSRNN_RANGE_EXACT &&
+        (ranges_overlap(z, bz, z_out, bz) || ranges_overlap(z, bz, state_out, bs) ||
+         ranges_overlap(state_in, bs, z_out, bz) || ranges_overlap(state_in, bs, state_out, bs)))
+        return fail(BSRNN_EARG, "bsrnn_dual_path: z_out and state_out must not overlap z or state_in (a call that leaves the fp16 range is run again from them)");
     auto run = [&]() -> int {
     HIP_TRY(hipMemcpyAsync(c->Z0, z, nz * sizeof(float), hipMemcpyDeviceToDevice, s));
     const size_t slab = (size_t)2 * 2 * C * K * HID;
@@ -1953,6 +1969,10 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
     const int T = 1 + (int)(n / HOPS);
     if ((rc = ensure_ws(c, (size_t)R * T))) return rc;
     const int64_t out_len = (int64_t)(T - 1) * HOPS;
+    // the re-run (finish_call) reads the waveform again; concurrent row blocks write their outputs while others still read
+    if (c->range_policy == BSRNN_RANGE_EXACT &&
+        ranges_overlap(wave, (size_t)R * n * sizeof(float), wave_out, (size_t)R * out_len * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_separate: wave_out must not overlap wave (a call that leaves the fp16 range is run again from wave)");
 
     // Rows are independent, so the batch is cut into `parts` contiguous row blocks that run the whole
     // stage sequence concurrently on separate streams: the ramps, tails and latency-bound stages of
@@ -2023,6 +2043,10 @@ int bsrnn_evaluate(bsrnn_ctx* c, const float* mix, const float* speech, int32_t 
     };
     if ((rc = check_ready(c))) return rc;
     if (!mix || R < 1 || n <= NFFT / 2) return fail(BSRNN_EARG, "bsrnn_evaluate: need n > 1024 samples, got %lld", (long long)n);
+    // the metrics read mix and speech after the estimate is written, and the re-run below reads them again: whatever the policy
+    if (ranges_overlap(est_out, (size_t)R * n_est * sizeof(float), mix, (size_t)R * n * sizeof(float)) ||
+        ranges_overlap(est_out, (size_t)R * n_est * sizeof(float), speech, (size_t)R * n * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_evaluate: est_out must not overlap mix or speech (the metrics and a re-run of the call read them after the estimate is written)");
     hipStream_t s = (hipStream_t)stream;
     ENTER_CALL(c, s);
     if (!est_out && hipMalloc((void**)&est, (size_t)R * n_est * sizeof(float)) != hipSuccess) {
@@ -2258,8 +2282,9 @@ int bsrnn_stream_step(bsrnn_stream* st, const float* chunk, float* out, float mi
     ENTER_CALL(c, s);
     if ((rc = ensure_ws(c, st->C)) || (rc = ensure_tasks(c, st->C))) return rc;
     const float* src = chunk;
-    if (chunk == out && c->range_policy == BSRNN_RANGE_EXACT) {
-        // in place: a re-run (range policy) must still see the input, so it is kept aside first
+    const size_t nb = (size_t)st->C * HOPS * sizeof(float);
+    if (ranges_overlap(chunk, nb, out, nb) && c->range_policy == BSRNN_RANGE_EXACT) {
+        // in place, or partly: a re-run (range policy) must still see the input, so it is kept aside first
         HIP_TRY(hipMemcpyAsync(st->chunk, chunk, (size_t)st->C * HOPS * sizeof(float), hipMemcpyDeviceToDevice, s));
         src = st->chunk;
     }
