@@ -233,15 +233,22 @@ int  bsrnn_linear_group_train_backward(bsrnn_ctx* ctx, int32_t n, const float* c
                                        float* const* dw_dev, float* const* db_dev, const int32_t* K, const int32_t* N,
                                        int32_t M, int32_t leaky, void* stream);
 
+/* Row chunks of the weight-gradient reductions of the calls above (measurement / test support): C [N1][N2] = A^T B over M rows
+ * (dw_ih: N1 = 256, N2 = IN; dw_hh: N1 = 256, N2 = 64; Linear dw and db: N1 = N, N2 = K, M rows per direction or layer) runs as
+ * out[0] chunks of out[1] rows (the last one may be shorter) whose partial products are then added in a fixed order.  A function
+ * of the shape only; no context or device needed.  BSRNN_EARG for M outside [1, 2^30], N1 or N2 outside [1, 65536], or a null out. */
+int  bsrnn_train_reduction_layout(int32_t M, int32_t N1, int32_t N2, int32_t out[2]);
+
 /* torch.optim.AdamW(model.parameters(), lr, weight_decay) of train.py:50, one tensor per call: p, m (exp_avg), v (exp_avg_sq)
- * updated in place from the gradient g; `step` counts from 1 (bias correction).  n floats each, device pointers. */
+ * updated in place from the gradient g; `step` counts from 1 (bias correction).  n floats each, device pointers.  The betas are
+ * double, as torch's: 1 - beta2 and the bias corrections are formed from them in double (from 0.999f, 1 - beta2 is 1.3e-5 off). */
 int  bsrnn_adamw_step(bsrnn_ctx* ctx, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n,
-                      float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, void* stream);
+                      float lr, double beta1, double beta2, float eps, float weight_decay, int32_t step, void* stream);
 
 /* The same update for many parameter tensors at once (80 per launch, pointers passed in the kernel arguments): host arrays
  * [n_tensors] of device pointers and of element counts. */
 int  bsrnn_adamw_step_multi(bsrnn_ctx* ctx, float* const* p_dev, const float* const* g_dev, float* const* m_dev, float* const* v_dev,
-                            const int64_t* sizes, int32_t n_tensors, float lr, float beta1, float beta2, float eps,
+                            const int64_t* sizes, int32_t n_tensors, float lr, double beta1, double beta2, float eps,
                             float weight_decay, int32_t step, void* stream);
 
 /* The same with the step count and the learning rate in DEVICE memory: state_dev = {float lr, float bc1, float bc2s, int32 step}
@@ -250,7 +257,7 @@ int  bsrnn_adamw_step_multi(bsrnn_ctx* ctx, float* const* p_dev, const float* co
  * value, so a whole training iteration (train.py:97-115: forward, backward, this call) can be captured once into a hipGraph and
  * replayed; the learning rate of a schedule is a 4-byte copy into state_dev between replays. */
 int  bsrnn_adamw_step_multi_dev(bsrnn_ctx* ctx, float* const* p_dev, const float* const* g_dev, float* const* m_dev, float* const* v_dev,
-                                const int64_t* sizes, int32_t n_tensors, float* state_dev, float beta1, float beta2, float eps,
+                                const int64_t* sizes, int32_t n_tensors, float* state_dev, double beta1, double beta2, float eps,
                                 float weight_decay, void* stream);
 
 /* ---- the STFT sandwich of the callers --------------------------------------------------

@@ -15,14 +15,16 @@ HID = 64
 
 
 class TorchCpuBSRNN:
-    def __init__(self, sd, v):
-        """sd: key -> array-like (reference state_dict names); v: band widths incl. the 0 band."""
+    def __init__(self, sd, v, dtype=torch.float32):
+        """sd: key -> array-like (reference state_dict names); v: band widths incl. the 0 band; dtype: of the parameters and
+        of the arithmetic (torch.float64: the high-precision reference of the gradient tests)."""
         self.v = list(v)
-        self.p = {k: torch.as_tensor(a, dtype=torch.float32).clone() for k, a in sd.items()}
+        self.dtype = dtype
+        self.p = {k: torch.as_tensor(a).to(dtype).clone() for k, a in sd.items()}
         self.rnn = []
         for j in range(4):
             bidir = (j % 2 == 0)
-            m = torch.nn.LSTM(HID, HID, batch_first=True, num_layers=2, bidirectional=bidir)   # bsrnn.py:70
+            m = torch.nn.LSTM(HID, HID, batch_first=True, num_layers=2, bidirectional=bidir, dtype=dtype)   # bsrnn.py:70
             own = m.state_dict()
             for k in own:
                 own[k] = self.p["lstms.%d.m.rnn.%s" % (j, k)]
@@ -126,8 +128,8 @@ class TorchCpuBSRNN:
 
     @torch.no_grad()
     def separate(self, wave):
-        """infer.py:29-37 on [C, n] float32 -> [C, (T-1)*1024]."""
-        win = torch.hann_window(2048)
+        """infer.py:29-37 on [C, n] (of the model's dtype) -> [C, (T-1)*1024]."""
+        win = torch.hann_window(2048, dtype=self.dtype)
         X = torch.stft(wave, n_fft=2048, hop_length=1024, return_complex=True, window=win)
         x = torch.stack((X.real, X.imag), dim=2)
         x = x.reshape(x.shape[0], x.shape[1] * 2, x.shape[3])

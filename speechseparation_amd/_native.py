@@ -22,7 +22,7 @@ SYMBOLS = [
     "bsrnn_sync", "bsrnn_evaluate", "bsrnn_io_count", "bsrnn_io_info", "bsrnn_mlp_fused", "bsrnn_chain_geometry",
     "bsrnn_lstm_train_forward", "bsrnn_lstm_train_backward", "bsrnn_linear_train_forward", "bsrnn_linear_train_backward",
     "bsrnn_istft_backward", "bsrnn_adamw_step", "bsrnn_adamw_step_multi", "bsrnn_adamw_step_multi_dev",
-    "bsrnn_linear_group_train_forward", "bsrnn_linear_group_train_backward",
+    "bsrnn_linear_group_train_forward", "bsrnn_linear_group_train_backward", "bsrnn_train_reduction_layout",
     "bsrnn_set_range_policy", "bsrnn_get_range_policy", "bsrnn_overlap_state", "bsrnn_debug_peek", "bsrnn_debug_counter",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
@@ -79,9 +79,10 @@ def _load():
         "bsrnn_istft_backward": (C.c_int, [vp, vp, vp, i32, i32, vp]),
         "bsrnn_linear_group_train_forward": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
         "bsrnn_linear_group_train_backward": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
-        "bsrnn_adamw_step_multi": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp]),
-        "bsrnn_adamw_step_multi_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, C.c_float, C.c_float, C.c_float, C.c_float, vp]),
-        "bsrnn_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp]),
+        "bsrnn_train_reduction_layout": (C.c_int, [i32, i32, i32, C.POINTER(i32)]),
+        "bsrnn_adamw_step_multi": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, i32, vp]),
+        "bsrnn_adamw_step_multi_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, C.c_double, C.c_double, C.c_float, C.c_float, vp]),
+        "bsrnn_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, i64, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, i32, vp]),
         "bsrnn_separate": (C.c_int, [vp, vp, vp, i32, i64, vp]),
         "bsrnn_stream_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
         "bsrnn_stream_destroy": (None, [vp]),

@@ -1754,30 +1754,40 @@ int bsrnn_lstm_train_backward(bsrnn_ctx* c, const float* x, const float* h, cons
     return 0;
 }
 
-int bsrnn_adamw_step(bsrnn_ctx* c, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+int bsrnn_train_reduction_layout(int32_t M, int32_t N1, int32_t N2, int32_t out[2])
+{
+    if (!out || M < 1 || M > (1 << 30) || N1 < 1 || N1 > 65536 || N2 < 1 || N2 > 65536)
+        return fail(BSRNN_EARG, "bsrnn_train_reduction_layout: bad arguments (M=%d N1=%d N2=%d)", M, N1, N2);
+    int o[2];
+    train_reduction_layout(M, N1, N2, o);
+    out[0] = o[0]; out[1] = o[1];
+    return 0;
+}
+
+int bsrnn_adamw_step(bsrnn_ctx* c, float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
                      float eps, float weight_decay, int32_t step, void* stream)
 {
     if (!c) return fail(BSRNN_EARG, "null context");
     if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
     HIP_TRY(hipSetDevice(c->device));
-    if (!p || !g || !m || !v || n < 0 || step < 1 || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
+    if (!p || !g || !m || !v || n < 0 || step < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
         return fail(BSRNN_EARG, "bsrnn_adamw_step: bad arguments (n=%lld step=%d)", (long long)n, step);
     hipStream_t s = (hipStream_t)stream;
     ENTER_CALL(c, s);
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
     launch_adamw(p, g, m, v, (size_t)n, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), s);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 static int adamw_multi(bsrnn_ctx* c, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* sizes,
-                       int32_t n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, float* state,
+                       int32_t n_tensors, float lr, double beta1, double beta2, float eps, float weight_decay, int32_t step, float* state,
                        void* stream, const char* who)
 {
     if (!c) return fail(BSRNN_EARG, "null context");
     if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
     HIP_TRY(hipSetDevice(c->device));
-    if (!p || !g || !m || !v || !sizes || n_tensors < 1 || (!state && step < 1) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
+    if (!p || !g || !m || !v || !sizes || n_tensors < 1 || (!state && step < 1) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
         return fail(BSRNN_EARG, "%s: bad arguments (n_tensors=%d step=%d)", who, n_tensors, step);
     for (int i = 0; i < n_tensors; ++i)
         if (!p[i] || !g[i] || !m[i] || !v[i] || sizes[i] < 0) return fail(BSRNN_EARG, "%s: tensor %d: null pointer or negative size", who, i);
@@ -1787,7 +1797,7 @@ static int adamw_multi(bsrnn_ctx* c, float* const* p, const float* const* g, flo
     ENTER_CALL(c, s);
     double bc1 = 1.0, bc2 = 1.0;
     if (state) launch_adamw_tick(state, beta1, beta2, s);
-    else { bc1 = 1.0 - pow((double)beta1, step); bc2 = 1.0 - pow((double)beta2, step); }
+    else { bc1 = 1.0 - pow(beta1, step); bc2 = 1.0 - pow(beta2, step); }
     for (int i0 = 0; i0 < n_tensors; i0 += ADAM_GROUP) {
         AdamGroup a;
         a.count = std::min(ADAM_GROUP, n_tensors - i0);
@@ -1804,13 +1814,13 @@ static int adamw_multi(bsrnn_ctx* c, float* const* p, const float* const* g, flo
 }
 
 int bsrnn_adamw_step_multi(bsrnn_ctx* c, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* sizes,
-                           int32_t n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, void* stream)
+                           int32_t n_tensors, float lr, double beta1, double beta2, float eps, float weight_decay, int32_t step, void* stream)
 {
     return adamw_multi(c, p, g, m, v, sizes, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, stream, "bsrnn_adamw_step_multi");
 }
 
 int bsrnn_adamw_step_multi_dev(bsrnn_ctx* c, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* sizes,
-                               int32_t n_tensors, float* state_dev, float beta1, float beta2, float eps, float weight_decay, void* stream)
+                               int32_t n_tensors, float* state_dev, double beta1, double beta2, float eps, float weight_decay, void* stream)
 {
     if (!state_dev) return fail(BSRNN_EARG, "bsrnn_adamw_step_multi_dev: null optimizer state");
     return adamw_multi(c, p, g, m, v, sizes, n_tensors, 0.f, beta1, beta2, eps, weight_decay, 0, state_dev, stream, "bsrnn_adamw_step_multi_dev");

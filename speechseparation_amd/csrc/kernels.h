@@ -244,6 +244,7 @@ void launch_sgemm_group(TrainGemmGroup& g, int trans_b, int accumulate, int leak
 size_t tn_group_scratch_floats(const TrainGemmGroup& g);
 void launch_sgemm_tn_group(const TrainGemmGroup& g, float* scratch, int L, int shift, hipStream_t stream);   // C_i = A_i^T B_i, bias_i = column sums of A_i
 size_t sgemm_tn_scratch_floats(int M, int N1, int N2);
+void train_reduction_layout(int M, int N1, int N2, int out[2]);           // {chunks, rows per chunk} of A^T B over M rows, C [N1][N2]
 size_t colsum_scratch_floats(int M, int cols);
 void launch_sgemm(const float* A, int lda, const float* B, int ldb, int trans_b, float* C, int ldc, int M, int N, int K,
                   int accumulate, const float* bias, int leaky, hipStream_t stream);
@@ -251,7 +252,7 @@ void launch_sgemm_tn(const float* A, int lda, const float* B, int ldb, float* ou
                      int L, int shift, hipStream_t stream);
 void launch_colsum(const float* A, int lda, float* out, float* scratch, int M, int cols, hipStream_t stream);
 // one AdamW update of n parameters (torch.optim.AdamW semantics; bc1 = 1 - beta1^t, bc2s = sqrt(1 - beta2^t))
-void launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd,
+void launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, double b1, double b2, float eps, float wd,
                   float bc1, float bc2s, hipStream_t stream);
 // the same update for up to ADAM_GROUP tensors in one launch; everything travels by value in the kernel arguments
 constexpr int ADAM_GROUP = 80;
@@ -262,9 +263,9 @@ struct AdamGroup {
     int count;
 };
 // state != nullptr: {lr, bc1, bc2s, step(int32)} in device memory override the by-value arguments (launch_adamw_tick advances it)
-void launch_adamw_group(const AdamGroup& a, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2s, hipStream_t stream,
+void launch_adamw_group(const AdamGroup& a, float lr, double b1, double b2, float eps, float wd, float bc1, float bc2s, hipStream_t stream,
                         const float* state = nullptr);
-void launch_adamw_tick(float* state, float b1, float b2, hipStream_t stream);
+void launch_adamw_tick(float* state, double b1, double b2, hipStream_t stream);
 // nn.Linear (+ LeakyReLU(0.01)) for a group of layers that share the row count M (the same layer of all bands):
 struct LinearJob {
     const float* x; int ldx;        // [M][K], row stride ldx

@@ -253,6 +253,13 @@ int rows_per_chunk(int M, int tiles)
 
 }  // namespace
 
+void train_reduction_layout(int M, int N1, int N2, int out[2])
+{
+    const int rpc = rows_per_chunk(M, ((N1 + 63) / 64) * ((N2 + 63) / 64));
+    out[0] = (M + rpc - 1) / rpc;                         // the chunks launch_sgemm_tn_group runs (can be fewer than chunk_count)
+    out[1] = rpc;
+}
+
 size_t sgemm_tn_scratch_floats(int M, int N1, int N2) { return (size_t)chunk_count(M, ((N1 + 63) / 64) * ((N2 + 63) / 64)) * ((size_t)N1 * N2 + N1); }
 size_t colsum_scratch_floats(int M, int cols) { return (size_t)chunk_count(M, (cols + 255) / 256) * cols; }
 
@@ -340,15 +347,17 @@ void launch_colsum(const float* A, int lda, float* out, float* scratch, int M, i
 // ---------------------------------------------------------------------------------------------- AdamW (train.py:50)
 // torch.optim.AdamW(lr, betas, eps, weight_decay) in torch's own operation order (decoupled decay first, then
 // p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)); bc1 = 1 - b1^t and bc2s = sqrt(1 - b2^t) come from the host.
+// omb1 = 1 - b1 and omb2 = 1 - b2 are formed in double from the double betas, as torch forms its scalars: 1 - 0.999f in float
+// is 1.3e-5 off 0.001, and v with it.
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
-                             float lr, float b1, float b2, float eps, float wd, float bc1, float bc2s)
+                             float lr, float omb1, float b2, float omb2, float eps, float wd, float bc1, float bc2s)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float gi = g[i];
     float pi = p[i] * (1.0f - lr * wd);
-    const float mi = m[i] + (gi - m[i]) * (1.0f - b1);           // lerp, as torch: exp_avg.lerp_(grad, 1 - beta1)
-    const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;
+    const float mi = m[i] + (gi - m[i]) * omb1;                  // lerp, as torch: exp_avg.lerp_(grad, 1 - beta1)
+    const float vi = v[i] * b2 + omb2 * gi * gi;
     const float denom = __builtin_sqrtf(vi) / bc2s + eps;
     pi -= (lr / bc1) * (mi / denom);
     p[i] = pi; m[i] = mi; v[i] = vi;
@@ -357,8 +366,8 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 // update in stream order); block b belongs to the tensor t with first_block[t] <= b < first_block[t + 1], 1024 elements per block
 // state (optional): {lr, bc1, bc2s, step} in device memory, written by adamw_tick_kernel in stream order - a captured launch
 // (hipGraph replay of a whole training iteration) then sees the step count and the learning rate of the replay, not of the capture.
-__global__ __launch_bounds__(256) void adamw_group_kernel(AdamGroup a, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2s,
-                                                          const float* __restrict__ state)
+__global__ __launch_bounds__(256) void adamw_group_kernel(AdamGroup a, float lr, float omb1, float b2, float omb2, float eps, float wd, float bc1,
+                                                          float bc2s, const float* __restrict__ state)
 {
     if (state) { lr = state[0]; bc1 = state[1]; bc2s = state[2]; }
     int ti = 0;
@@ -371,38 +380,40 @@ __global__ __launch_bounds__(256) void adamw_group_kernel(AdamGroup a, float lr,
         if (i >= n) break;
         const float gi = g[i];
         float pi = p[i] * (1.0f - lr * wd);
-        const float mi = m[i] + (gi - m[i]) * (1.0f - b1);
-        const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;
+        const float mi = m[i] + (gi - m[i]) * omb1;
+        const float vi = v[i] * b2 + omb2 * gi * gi;
         pi -= (lr / bc1) * (mi / (__builtin_sqrtf(vi) / bc2s + eps));
         p[i] = pi; m[i] = mi; v[i] = vi;
     }
 }
-void launch_adamw_group(const AdamGroup& a, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2s, hipStream_t s,
+void launch_adamw_group(const AdamGroup& a, float lr, double b1, double b2, float eps, float wd, float bc1, float bc2s, hipStream_t s,
                         const float* state)
 {
     if (a.count <= 0 || a.first_block[a.count] <= 0) return;
-    hipLaunchKernelGGL(adamw_group_kernel, dim3(a.first_block[a.count]), dim3(256), 0, s, a, lr, b1, b2, eps, wd, bc1, bc2s, state);
+    hipLaunchKernelGGL(adamw_group_kernel, dim3(a.first_block[a.count]), dim3(256), 0, s, a, lr, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2),
+                       eps, wd, bc1, bc2s, state);
 }
 // step += 1; bc1 = 1 - b1^step, bc2s = sqrt(1 - b2^step) (double, as the host path computes them)
-__global__ void adamw_tick_kernel(float* state, float b1, float b2)
+__global__ void adamw_tick_kernel(float* state, double b1, double b2)
 {
     if (threadIdx.x || blockIdx.x) return;
     int* step = reinterpret_cast<int*>(state + 3);
     const int t = *step + 1;
     *step = t;
-    state[1] = (float)(1.0 - pow((double)b1, (double)t));
-    state[2] = (float)sqrt(1.0 - pow((double)b2, (double)t));
+    state[1] = (float)(1.0 - pow(b1, (double)t));
+    state[2] = (float)sqrt(1.0 - pow(b2, (double)t));
 }
-void launch_adamw_tick(float* state, float b1, float b2, hipStream_t s)
+void launch_adamw_tick(float* state, double b1, double b2, hipStream_t s)
 {
     hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(64), 0, s, state, b1, b2);
 }
 
-void launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, float wd,
+void launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, double b1, double b2, float eps, float wd,
                   float bc1, float bc2s, hipStream_t s)
 {
     if (!n) return;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s);
+    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, lr, (float)(1.0 - b1), (float)b2,
+                       (float)(1.0 - b2), eps, wd, bc1, bc2s);
 }
 
 // ---------------------------------------------------------------------------------------------- nn.Linear (+ LeakyReLU)

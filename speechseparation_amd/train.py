@@ -75,6 +75,14 @@ def lstm_layer_backward(x, h, gates, cells, dh, w_ih, w_hh, need_dx=True):
     return dx, dw_ih, dw_hh, db
 
 
+def reduction_layout(M, N1, N2):
+    """(chunks, rows per chunk) of the row reduction behind a weight gradient C [N1, N2] = A^T B over M rows: dw_ih (256, IN) and
+    dw_hh (256, 64) of an LSTM layer (M = N L), dw of a Linear layer (N, K) (include/bsrnn_hip.h, bsrnn_train_reduction_layout)."""
+    out = (ctypes.c_int32 * 2)()
+    _native.check(_lib.bsrnn_train_reduction_layout(M, N1, N2, out))
+    return out[0], out[1]
+
+
 class LstmLayerFunction(torch.autograd.Function):
     """One nn.LSTM layer (all directions) with the library's forward and backward.
     apply(x, w_ih, w_hh, b_ih, b_hh) -> h; parameters stacked over directions as in `stack_direction_weights`."""

@@ -276,3 +276,21 @@ def test_train_entry_point_dataset_layout(tmp_path):
     assert mod.dataset(str(tmp_path), "val") == []
     with pytest.raises(SystemExit):
         mod.main([])                                   # neither --datapath nor --synthetic
+
+
+def test_train_reduction_layout_query(built):
+    """bsrnn_train_reduction_layout needs no context or device: the row chunks of the bench's weight-gradient reductions, and
+    its argument refusal."""
+    from speechseparation_amd import _native, train
+    assert train.reduction_layout(96768, 256, 64) == (252, 384)           # band-axis dw_hh: 8 064 sequences x 12 bands
+    assert train.reduction_layout(96768, 256, 128) == (126, 768)          # layer-1 dw_ih
+    assert train.reduction_layout(8064, 768, 768) == (16, 512)            # the 768 x 768 Linear layers
+    assert train.reduction_layout(1, 1, 1) == (1, 16)
+    out = (ctypes.c_int32 * 2)(-7, -7)
+    lib = _native.lib
+    for args in ((0, 256, 64), (96768, 0, 64), (96768, 256, 0), ((1 << 30) + 1, 256, 64), (100, 65537, 1), (-1, 1, 1)):
+        assert lib.bsrnn_train_reduction_layout(*args, out) == 1, args     # BSRNN_EARG
+        assert tuple(out) == (-7, -7)
+    assert lib.bsrnn_train_reduction_layout(100, 1, 1, None) == 1
+    with pytest.raises(_native.NativeError):
+        train.reduction_layout(0, 1, 1)
