@@ -79,7 +79,7 @@ const char* bsrnn_last_error(void);
  *     reported late: the NEXT call on the context, bsrnn_sync or bsrnn_stream_get_state fails with BSRNN_ERANGE, once, and
  *     the results of the call that caused it are invalid (not-a-number or nonsense, never silently plausible saturated
  *     values: nothing is clamped).  The caller repeats the work under the default policy.
- *   bsrnn_stream_step_host always behaves as under BSRNN_RANGE_EXACT (it waits for its kernels anyway).
+ *   bsrnn_stream_step_host and bsrnn_evaluate always behave as under BSRNN_RANGE_EXACT (they wait for their kernels anyway).
  * NaN / Inf inputs are not range errors: they come out as NaN, as they do from the reference. */
 const char* bsrnn_compute_mode(void);
 
@@ -330,7 +330,8 @@ int  bsrnn_stream_get_state(bsrnn_stream* s, float* state_host /* [4,2,C*K,64] *
  * hipEvents on the call's stream (mask < 0 = all stages, 0 = off; each bracket costs ~10 us of
  * stream time, so time-critical runs enable only the stage they report);
  * bsrnn_stage_times() synchronises on the last call and returns per-stage elapsed
- * milliseconds (accumulated since the last reset) and launch counts.  Stage names:
+ * milliseconds (accumulated since the last reset) and launch counts.  Every model entry point records its stages,
+ * bsrnn_dual_path included (band_lstm, band_fc, time_lstm, time_fc).  Stage names:
  * bsrnn_stage_name(i).  Used by bench.py for the live roofline figure. */
 int         bsrnn_set_profiling(bsrnn_ctx* ctx, int32_t on);
 int         bsrnn_stage_count(void);

@@ -93,7 +93,6 @@ struct bsrnn_ctx {
 
     // fused per-band MLP chains (mlp_chain.hip): device descriptor arrays, grouped by class (kernels.h, ChainLaunch)
     bool stage_error = false;       // run_stage() found no task table for its row count (cannot happen: ensure_tasks runs first); reported by the entry point
-    bool small_rows = false;        // the call in flight has <= GEMV_MAX_FRAME_ROWS frame rows: per-layer GEMV launches (gemv.hip)
     bool fused = false;             // false: per-layer launches (BSRNN_MLP=layers, fp32 mode, or a band too wide for the LDS image)
     ChainDesc* d_chain[2] = {nullptr, nullptr};
     std::vector<ChainDesc> h_chain[2];          // host copies (geometry and cost per band: the task tables are made from them)
@@ -431,7 +430,7 @@ int ensure_tasks(bsrnn_ctx* c, const int* Ms, int n)
 }
 int ensure_tasks(bsrnn_ctx* c, int M) { return ensure_tasks(c, &M, 1); }
 
-void gemm_slot(bsrnn_ctx* c, int slot, const float* X, int ldx, float* Y, int ldy, const float* R, int ldr,
+void gemm_slot(bsrnn_ctx* c, bool gemv, int slot, const float* X, int ldx, float* Y, int ldy, const float* R, int ldr,
                const float* Mul, int ldm, float* tap, int M, int epi, hipStream_t s)
 {
     GemmLaunch g;
@@ -445,8 +444,68 @@ void gemm_slot(bsrnn_ctx* c, int slot, const float* X, int ldx, float* Y, int ld
     g.tap = tap; g.ldt = c->LDP; g.M = M; g.epilogue = epi;
     // a call of a few frame rows: its per-band layers (M = C rows) run as exact-fp32 GEMV launches instead of 128-row MFMA
     // tiles; the block fc layers (M K rows against a 64 x 128 matrix) stay on the MFMA kernel (measured: 5.7 vs 28 us)
-    if (c->small_rows && M <= 2 * GEMV_MAX_FRAME_ROWS) launch_gemv(g, s);
+    if (gemv && M <= 2 * GEMV_MAX_FRAME_ROWS) launch_gemv(g, s);
     else launch_gemm(g, s);
+}
+
+// --------------------------------------------------------------------------- the call plan
+// Which kernels one model call runs, decided once per call by plan_call() and read by everything that launches or sizes something for it
+// (run_stage, the overlapped dual path, bsrnn_separate's row blocks): the time-axis launch and the consumers that wait on its progress
+// words agree on its sequences per workgroup because they all read Flow::seqs.
+// Band-axis blocks: a few frame rows (streaming) as one launch of the whole block, fc + residual included (band_block_small_kernel); both
+// layers in one launch writing the shares of the block's fc that the time-axis launch adds (kernels.h); both layers in one launch and the fc
+// + residual as a grouped-GEMM launch; one launch per layer and the same fc launch.
+enum BandForm { BAND_SMALL, BAND_PAIR_PARTS, BAND_PAIR, BAND_LAYERS };
+struct Flow {
+    bool exact;          // force_f32(): the range-guard re-run - every launch on the exact-fp32 kernels
+    bool lstm_f32;       // the recurrent layers on the fp32 kernels (BSRNN_LSTM=f32, or exact)
+    bool gemv;           // a call of <= GEMV_MAX_FRAME_ROWS frame rows: its per-band layers as GEMV launches (gemm_slot, gemv.hip)
+    bool chains;         // the per-band MLPs as fused chains (mlp_chain.hip); else one launch per layer
+    int band;            // BandForm of the band-axis blocks
+    bool time_fc;        // the time-axis launch forms its block's fc + residual itself (no MS_TIMEFC launch)
+    int seqs, nwg;       // the time-axis launch: sequences per workgroup (4, or 8 on time_lstm_h2w8_kernel) and workgroups
+    bool overlap;        // the dual path runs overlapped (run_overlapped), given its tables and no graph capture (ovl_table)
+};
+
+// The plan of a call of C rows x T frames.  gemv / overlap: the entry point may run a few frame rows on the GEMV kernels / the dual path
+// overlapped.  The rest comes from the knobs, force_f32() (the exact re-run plans again) and the context's sticky fall-backs.
+static Flow plan_call(const bsrnn_ctx* c, int C, int T, bool gemv, bool overlap)
+{
+    // The knobs, read once per process: BSRNN_BAND_PAIR=0 one launch per band layer; BSRNN_BAND_FC=gemm the band
+    // block's fc + residual as a grouped-GEMM launch instead of the shares the pair launch writes and the time-axis launch adds (the second
+    // layer alone with the shares sits at the edge of 256 VGPRs - as a kernel of its own it spilled four registers - and is not shipped);
+    // BSRNN_TIME_KERNEL=v3 the time block's fc as a launch of its own; BSRNN_TIME_SEQ8 = 0 / 1: eight sequences per time-axis workgroup never /
+    // always (unset: where four would need more than one round of workgroups).
+    auto is = [](const char* name, const char* value) { const char* e = getenv(name); return e && !strcmp(e, value); };
+    static const bool pair_knob = !is("BSRNN_BAND_PAIR", "0"), parts_knob = !is("BSRNN_BAND_FC", "gemm");
+    static const bool time_fused = [] {
+        const char* e = getenv("BSRNN_TIME_KERNEL");
+        if (e && *e && strcmp(e, "fused") && strcmp(e, "v3")) fprintf(stderr, "bsrnn: unknown BSRNN_TIME_KERNEL='%s' (v3 | fused), using fused\n", e);
+        return !(e && !strcmp(e, "v3"));
+    }();
+    static const int seq8 = [] { const char* e = getenv("BSRNN_TIME_SEQ8"); return e ? atoi(e) : -1; }();
+    Flow f;
+    const int M = C * T, K = c->K, N = C * K, cus = device_cus();
+    f.exact = force_f32();
+    f.lstm_f32 = f.exact || lstm_mode() == LSTM_F32;
+    const bool gemm16 = !f.exact && gemm_mode() != GEMM_F32;
+    f.gemv = gemv && M <= GEMV_MAX_FRAME_ROWS;
+    f.chains = c->fused && !f.exact && !f.gemv;
+    // the fc inside the time-axis kernel unless the Linear layers are asked to be exact fp32 (BSRNN_GEMM=f32)
+    f.time_fc = !f.lstm_f32 && gemm16 && time_fused;
+    // the pair launch is fp16x2 only; a context whose pair launch once reported that its partner workgroups did not meet runs one launch
+    // per layer from then on.  The fc in parts needs the pair launch and the fused time-axis kernel.
+    const bool pair = !f.lstm_f32 && pair_knob && !c->band_pair_off;
+    if (!f.lstm_f32 && gemm16 && M <= 8 && K <= BS_MAXL) f.band = BAND_SMALL;
+    else if (pair && parts_knob && f.time_fc) f.band = BAND_PAIR_PARTS;
+    else f.band = pair ? BAND_PAIR : BAND_LAYERS;
+    f.seqs = f.time_fc && (seq8 == 1 || (seq8 < 0 && (N + 3) / 4 > cus)) ? 8 : 4;
+    f.nwg = (N + f.seqs - 1) / f.seqs;
+    // Overlapped: the parts flow with fused chains (the launches that know how to publish / wait), a time-axis launch that leaves CUs free
+    // (at most 7/8 of them) and enough frames for a head start to exist
+    f.overlap = overlap && c->overlap_env && !c->overlap_off && f.band == BAND_PAIR_PARTS && c->fused && f.nwg >= 32 && f.nwg <= cus - cus / 8 &&
+                T >= 32 && T < (4 << OVL_EPOCH_SHIFT) - 8;
+    return f;
 }
 
 // A contiguous block of rows (utterance-channels) of one call, with its slice of the workspace
@@ -454,6 +513,7 @@ void gemm_slot(bsrnn_ctx* c, int slot, const float* X, int ldx, float* Y, int ld
 // several such parts that run concurrently on separate HIP streams.
 struct Part {
     int C, T;                       // rows and frames of this part
+    Flow f;                         // this part's plan (plan_call; made again for every run of the call)
     hipStream_t s;
     const float* Xf; float* Yf; float* tap;              // [C*T][LDP], band-padded spectrum layout
     float *A1, *A2, *P, *Z0, *Z1, *HB0, *HB1, *H1;
@@ -482,17 +542,13 @@ Part make_part(bsrnn_ctx* c, int row0, int C, int T, hipStream_t s, int j = 0)
     return p;
 }
 
-// the band blocks' fc in parts needs the pair launch (lstm.hip); a context whose pair launch once reported that its partner workgroups
-// did not meet runs the round-2 flow from then on
-static bool ctx_parts(const bsrnn_ctx* c) { return band_fc_in_parts() && !c->band_pair_off; }
-static bool ctx_pair(const bsrnn_ctx* c) { return band_pair_enabled() && !c->band_pair_off; }
-
 enum { MS_STFT, MS_BANDSPLIT, MS_BAND0, MS_BANDFC0, MS_TIME0, MS_TIMEFC0, MS_BAND1, MS_BANDFC1, MS_TIME1, MS_TIMEFC1, MS_MASK, MS_ISTFT, MS_COUNT };
 
 // One stage of the model for one part.  Xf [M][2050] -> Yf [M][2050], M = C*T, row = c*T + t.
 void run_stage(bsrnn_ctx* c, const Part& p, int stage)
 {
     const int M = p.C * p.T, K = c->K, KH = K * HID;
+    const Flow& f = p.f;
     hipStream_t s = p.s;
     switch (stage) {
     case MS_STFT:
@@ -500,7 +556,7 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
         break;
     case MS_BANDSPLIT: {   // bandFCs_pre (2 linears) -> residual P; bandFCs (3 linears) -> Z0   bsrnn.py:404-415
         StageScope sc(c, ST_BANDSPLIT, s);
-        if (c->fused && !force_f32() && !c->small_rows) {      // all five layers of every band in one launch, intermediates in LDS
+        if (f.chains) {                   // all five layers of every band in one launch, intermediates in LDS
             ChainLaunch g;
             memset(&g, 0, sizeof g);
             auto tti = c->chain_tasks.find(M);                           // made by ensure_tasks() before any launch (and outside graph capture)
@@ -511,77 +567,70 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
             launch_mlp_chain(g, CHAIN_SPLIT, s);
             break;
         }
-        gemm_slot(c, PRE0, p.Xf, c->LDP, p.A1, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
-        gemm_slot(c, PRE2, p.A1, c->LDA, p.P, c->LDP, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
-        gemm_slot(c, FC0, p.P, c->LDP, p.A1, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
-        gemm_slot(c, FC2, p.A1, c->LDA, p.A2, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
-        gemm_slot(c, FC4, p.A2, c->LDA, p.Z0, KH, nullptr, 0, nullptr, 0, nullptr, M, EPI_LINEAR, s);
+        gemm_slot(c, f.gemv, PRE0, p.Xf, c->LDP, p.A1, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
+        gemm_slot(c, f.gemv, PRE2, p.A1, c->LDA, p.P, c->LDP, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
+        gemm_slot(c, f.gemv, FC0, p.P, c->LDP, p.A1, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
+        gemm_slot(c, f.gemv, FC2, p.A1, c->LDA, p.A2, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
+        gemm_slot(c, f.gemv, FC4, p.A2, c->LDA, p.Z0, KH, nullptr, 0, nullptr, 0, nullptr, M, EPI_LINEAR, s);
         break;
     }
     case MS_BAND0: case MS_BAND1: {   // BandwiseLSTM: N = M sequences of length K   bsrnn.py:138-153
         const int blk = stage == MS_BAND1;
         StageScope sc(c, ST_BAND_LSTM, s);
-        if (band_block_is_small(M, K)) {          // a few frame rows (streaming): the whole block, fc + residual included, in one launch
+        if (f.band == BAND_SMALL) {               // a few frame rows (streaming): the whole block, fc + residual included, in one launch
             launch_band_block_small(p.Z0, p.Z1, c->bandW16[blk][0], c->bandB[blk][0], c->bandW16[blk][1], c->bandB[blk][1],
                                     c->bandFc16[blk], c->bandFcB[blk], M, K, c->d_range, s);
             break;
         }
-        // parts flow (band_fc_in_parts()): block 0 reads Z0 and its time block writes Z1, block 1 reads Z1 and its time block writes
-        // Z0 - the block's fc + residual are formed inside the two launches around them (kernels.h), MS_BANDFC does not exist
-        const bool parts = ctx_parts(c);
+        // parts flow: block 0 reads Z0 and its time block writes Z1, block 1 reads Z1 and its time block writes Z0 - the block's fc +
+        // residual are formed inside the two launches around them (kernels.h), MS_BANDFC does not exist
+        const bool parts = f.band == BAND_PAIR_PARTS;
         const float* zi = parts && blk ? p.Z1 : p.Z0;
-        if (ctx_pair(c)) {                        // both layers in one launch (A/B: BSRNN_BAND_PAIR=0)
+        if (f.band != BAND_LAYERS) {              // both layers in one launch (A/B: BSRNN_BAND_PAIR=0)
             OvlConsumer oc = {nullptr, 0, 0, nullptr, 0, 2};
             const bool cons = p.ovl && blk;
             if (cons)                             // beside the first time-axis launch: tiles in the order their frames leave it
-                oc = OvlConsumer{c->d_ovl + OVL_HEAD, p.T, c->overlap_sabotage ? 200000 : OVL_SPIN_LIMIT, p.ovl->band_order, p.ovl_base, time_lstm_seqs(p.C * K) == 8 ? 3 : 2};
+                oc = OvlConsumer{c->d_ovl + OVL_HEAD, p.T, c->overlap_sabotage ? 200000 : OVL_SPIN_LIMIT, p.ovl->band_order, p.ovl_base, f.seqs == 8 ? 3 : 2};
             launch_band_pair(zi, p.HB0, p.HB1, c->bandW16[blk][0], c->bandB[blk][0], c->bandW16[blk][1], c->bandB[blk][1], M, K, c->d_range, s,
                              parts ? c->bandFc16[blk] : nullptr, parts ? c->bandFcB[blk] : nullptr, p.band_flags, cons ? &oc : nullptr, nullptr, 0,
                              p.ovl ? p.band_done[blk] : nullptr);
             break;
         }
-        launch_band_lstm(zi, p.HB0, c->bandW[blk][0], c->bandW16[blk][0], c->bandB[blk][0], M, K, 64, c->d_range, s);
-        launch_band_lstm(p.HB0, p.HB1, c->bandW[blk][1], c->bandW16[blk][1], c->bandB[blk][1], M, K, 128, c->d_range, s);
+        launch_band_lstm(zi, p.HB0, c->bandW[blk][0], c->bandW16[blk][0], c->bandB[blk][0], M, K, 64, c->d_range, s, f.lstm_f32);
+        launch_band_lstm(p.HB0, p.HB1, c->bandW[blk][1], c->bandW16[blk][1], c->bandB[blk][1], M, K, 128, c->d_range, s, f.lstm_f32);
         break;
     }
     case MS_BANDFC0: case MS_BANDFC1: {
         const int blk = stage == MS_BANDFC1;
-        if (band_block_is_small(M, K) || ctx_parts(c)) break;     // done inside the band launch / inside the launches around it
+        if (f.band == BAND_SMALL || f.band == BAND_PAIR_PARTS) break;     // done inside the band launch / inside the launches around it
         StageScope sc(c, ST_BAND_FC, s);
-        gemm_slot(c, BLK_FC0 + 2 * blk, p.HB1, 2 * HID, p.Z1, HID, p.Z0, HID, nullptr, 0, nullptr, M * K, EPI_RES, s);
+        gemm_slot(c, f.gemv, BLK_FC0 + 2 * blk, p.HB1, 2 * HID, p.Z1, HID, p.Z0, HID, nullptr, 0, nullptr, M * K, EPI_RES, s);
         break;
     }
     case MS_TIME0: case MS_TIME1: {   // TimewiseLSTM: N = C*K sequences of length T, causal, state carry   bsrnn.py:106-128
         const int blk = stage == MS_TIME1;
         StageScope sc(c, ST_TIME_LSTM, s);
-        // fp16x2 mode: the launch also computes the block's fc + residual (out = fc(h1) + Z1 -> Z0); otherwise it writes h1
-        const bool fused = time_lstm_fuses_fc();
-        if (ctx_parts(c) && !band_block_is_small(M, K)) {
-            OvlProducer op = {nullptr, nullptr, 0};
-            const bool prod = p.ovl != nullptr;
-            if (prod) op = OvlProducer{c->d_ovl + blk * c->ovl_stride, c->overlap_sabotage ? nullptr : c->d_ovl + blk * c->ovl_stride + OVL_HEAD, p.ovl_base};
-            launch_time_lstm(blk ? p.Z1 : p.Z0, blk ? p.Z0 : p.Z1, c->timeW[blk], c->timeW16[blk], c->timeB[blk],
-                             p.state_in ? p.state_in + blk * p.state_slab : nullptr,
-                             p.state_out ? p.state_out + blk * p.state_slab : nullptr, p.C, p.T, K, c->d_range, s,
-                             c->timeFc16[blk], c->timeFcB[blk], p.HB1, prod ? &op : nullptr);
-            break;
-        }
-        launch_time_lstm(p.Z1, fused ? p.Z0 : p.H1, c->timeW[blk], c->timeW16[blk], c->timeB[blk],
-                         p.state_in ? p.state_in + blk * p.state_slab : nullptr,
-                         p.state_out ? p.state_out + blk * p.state_slab : nullptr, p.C, p.T, K, c->d_range, s,
-                         c->timeFc16[blk], c->timeFcB[blk]);
+        // time_fc: the launch also computes the block's fc + residual (out = fc(h1) + Z1 -> Z0); otherwise it writes h1.  Parts flow: it adds
+        // the band block's fc shares (HB1) to its input, block 0 reads Z0 and writes Z1; beside the band / mask launch that waits for it, it publishes
+        const bool first_of_parts = f.band == BAND_PAIR_PARTS && !blk;
+        OvlProducer op = {nullptr, nullptr, 0};
+        if (p.ovl) op = OvlProducer{c->d_ovl + blk * c->ovl_stride, c->overlap_sabotage ? nullptr : c->d_ovl + blk * c->ovl_stride + OVL_HEAD, p.ovl_base};
+        launch_time_lstm(first_of_parts ? p.Z0 : p.Z1, first_of_parts ? p.Z1 : (f.time_fc ? p.Z0 : p.H1), c->timeW[blk], c->timeW16[blk], c->timeB[blk],
+                         p.state_in ? p.state_in + blk * p.state_slab : nullptr, p.state_out ? p.state_out + blk * p.state_slab : nullptr,
+                         p.C, p.T, K, c->d_range, s, f.lstm_f32, f.seqs, f.time_fc ? c->timeFc16[blk] : nullptr, f.time_fc ? c->timeFcB[blk] : nullptr,
+                         f.band == BAND_PAIR_PARTS ? p.HB1 : nullptr, p.ovl ? &op : nullptr);
         break;
     }
     case MS_TIMEFC0: case MS_TIMEFC1: {
         const int blk = stage == MS_TIMEFC1;
-        if (time_lstm_fuses_fc()) break;          // done inside the time-axis launch
+        if (f.time_fc) break;                     // done inside the time-axis launch
         StageScope sc(c, ST_TIME_FC, s);
-        gemm_slot(c, BLK_FC1 + 2 * blk, p.H1, HID, p.Z0, HID, p.Z1, HID, nullptr, 0, nullptr, M * K, EPI_RES, s);
+        gemm_slot(c, f.gemv, BLK_FC1 + 2 * blk, p.H1, HID, p.Z0, HID, p.Z1, HID, nullptr, 0, nullptr, M * K, EPI_RES, s);
         break;
     }
     case MS_MASK: {   // bandFCs_back (3) + bandFCs_back_post (2) + skip + x*mask   bsrnn.py:420-443
         StageScope sc(c, ST_MASK, s);
-        if (c->fused && !force_f32() && !c->small_rows) {
+        if (f.chains) {
             ChainLaunch g;
             memset(&g, 0, sizeof g);
             auto tti = c->chain_tasks.find(M);
@@ -594,16 +643,16 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
                 g.tasks = p.ovl->mask_tasks; g.n_tasks = p.ovl->n_mask;
                 g.ovl_prog = c->d_ovl + c->ovl_stride + OVL_HEAD; g.ovl_T = p.T; g.ovl_K = K;
                 g.ovl_spin = c->overlap_sabotage ? 200000 : OVL_SPIN_LIMIT;
-                g.ovl_base = p.ovl_base; g.ovl_wg_shift = time_lstm_seqs(p.C * K) == 8 ? 3 : 2;
+                g.ovl_base = p.ovl_base; g.ovl_wg_shift = f.seqs == 8 ? 3 : 2;
             }
             launch_mlp_chain(g, CHAIN_MASK, s);
             break;
         }
-        gemm_slot(c, BACK0, p.Z0, KH, p.A1, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
-        gemm_slot(c, BACK2, p.A1, c->LDA, p.A2, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
-        gemm_slot(c, BACK4, p.A2, c->LDA, p.A1, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
-        gemm_slot(c, POST0, p.A1, c->LDA, p.A2, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
-        gemm_slot(c, POST2, p.A2, c->LDA, p.Yf, c->LDP, p.P, c->LDP, p.Xf, c->LDP, p.tap, M, EPI_MASK, s);
+        gemm_slot(c, f.gemv, BACK0, p.Z0, KH, p.A1, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
+        gemm_slot(c, f.gemv, BACK2, p.A1, c->LDA, p.A2, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
+        gemm_slot(c, f.gemv, BACK4, p.A2, c->LDA, p.A1, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
+        gemm_slot(c, f.gemv, POST0, p.A1, c->LDA, p.A2, c->LDA, nullptr, 0, nullptr, 0, nullptr, M, EPI_LEAKY, s);
+        gemm_slot(c, f.gemv, POST2, p.A2, c->LDA, p.Yf, c->LDP, p.P, c->LDP, p.Xf, c->LDP, p.tap, M, EPI_MASK, s);
         break;
     }
     case MS_ISTFT:
@@ -615,30 +664,23 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
     }
 }
 
-// ---- overlapped dual path ------------------------------------------------------------------------------------------------------
-// Whether a call of C rows x T frames runs overlapped: the fp16x2 parts flow with fused chains (the launches that know how to publish /
-// wait), a time-axis launch that leaves CUs free (<= 224 of 256 workgroups) and enough frames for a head start to exist.
-static bool overlap_wanted(const bsrnn_ctx* c, int C, int T)
-{
-    if (!c->overlap_env || c->overlap_off || !ctx_parts(c) || !c->fused || force_f32() || gemm_mode() == GEMM_F32) return false;
-    const int S = time_lstm_seqs(C * c->K), nwg = (C * c->K + S - 1) / S;      // workgroups of the time-axis launch
-    return !band_block_is_small(C * T, c->K) && nwg >= 32 && nwg <= 224 && T >= 32 && T < (4 << OVL_EPOCH_SHIFT) - 8 && C * T > GEMV_MAX_FRAME_ROWS;
-}
+// ---- overlapped dual path (whether a call runs it: plan_call) --------------------------------------------------------------------
 static void free_ovl_tables(bsrnn_ctx* c)
 {
     for (auto& kv : c->ovl_tables) { (void)hipFree(kv.second.mask_tasks); (void)hipFree(kv.second.band_order); }
     c->ovl_tables.clear();
 }
-// Progress words and the consumers' dispatch orders for a call of C rows x T frames (made outside any capture, like the task tables).
-int ensure_ovl(bsrnn_ctx* c, int C, int T)
+// Progress words and the consumers' dispatch orders for a call of C rows x T frames planned as f (made outside any capture, like the task
+// tables, and before the call's first launch).
+int ensure_ovl(bsrnn_ctx* c, const Flow& f, int C, int T)
 {
-    if (!overlap_wanted(c, C, T)) return 0;
+    if (!f.overlap) return 0;
     int rc = ensure_streams(c, 1);
     if (rc) return rc;
     if (!c->ev_ovl_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_ovl_fork, hipEventDisableTiming | hipEventDisableSystemFence));      // (device-side ordering only: no system-scope release on the record)
     if (!c->ev_ovl_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_ovl_join, hipEventDisableTiming | hipEventDisableSystemFence));
     if (!c->ev_ovl_mid) HIP_TRY(hipEventCreateWithFlags(&c->ev_ovl_mid, hipEventDisableTiming | hipEventDisableSystemFence));
-    const int M = C * T, K = c->K, S = time_lstm_seqs(C * K), nwg = (C * K + S - 1) / S;
+    const int M = C * T, nwg = f.nwg;
     const int stride = OVL_HEAD + ((nwg + 15) & ~15);
     if (stride > c->ovl_stride) {
         if (c->d_ovl) { c->retired.push_back(c->d_ovl); c->d_ovl = nullptr; }      // (retired like the workspace, see ensure_ws)
@@ -677,7 +719,7 @@ int ensure_ovl(bsrnn_ctx* c, int C, int T)
     for (int i = 0; i < (int)tasks.size(); ++i)
         if (!ds[tasks[i].x].constant && chain_rows(ds[tasks[i].x]) <= 80 && task_ready(tasks[i]) < T - 1) cand.push_back(i);
     std::stable_sort(cand.begin(), cand.end(), [&](int a, int b) { return task_ready(tasks[a]) < task_ready(tasks[b]); });
-    const int n_early = std::min((int)cand.size(), std::max(0, 256 - nwg));
+    const int n_early = std::min((int)cand.size(), std::max(0, device_cus() - nwg));
     std::vector<char> early(tasks.size(), 0);
     std::vector<int2> mt;
     for (int i = 0; i < n_early; ++i) { mt.push_back(tasks[cand[i]]); early[cand[i]] = 1; }
@@ -710,7 +752,7 @@ void run_overlapped(bsrnn_ctx* c, Part p, const bsrnn_ctx::OvlTable* tb, int fir
     p.ovl = tb;
     Part pb = p;
     pb.s = B;
-    const int S = time_lstm_seqs(p.C * c->K), nwg = (p.C * c->K + S - 1) / S;
+    const int nwg = p.f.nwg;
     // this call's epoch (upper bits of every progress word it publishes or waits for) and the gates' targets (running totals)
     if (++c->ovl_epoch >= c->ovl_epoch_period || c->ovl_resident_total[0] > (1 << 30) || c->ovl_resident_total[1] > (1 << 30)) {   // start again: nothing in flight, every word zero
         (void)hipDeviceSynchronize();
@@ -748,9 +790,9 @@ static int ovl_join_host(bsrnn_ctx* c)
     c->ovl_unjoined = false;
     return 0;
 }
-static const bsrnn_ctx::OvlTable* ovl_table(const bsrnn_ctx* c, int C, int T, hipStream_t s)
+static const bsrnn_ctx::OvlTable* ovl_table(const bsrnn_ctx* c, const Flow& f, int C, int T, hipStream_t s)
 {
-    if (!overlap_wanted(c, C, T) || !c->d_ovl) return nullptr;
+    if (!f.overlap || !c->d_ovl) return nullptr;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (s && hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); return nullptr; }      // (the legacy default stream cannot be captured)
     if (cs != hipStreamCaptureStatusNone) return nullptr;
@@ -762,43 +804,52 @@ static const bsrnn_ctx::OvlTable* ovl_table(const bsrnn_ctx* c, int C, int T, hi
 int run_model(bsrnn_ctx* c, const float* Xf, float* Yf, float* tap, int C, int T,
               const float* state_in, float* state_out, hipStream_t s)
 {
-    c->small_rows = C * T <= GEMV_MAX_FRAME_ROWS;
     Part p = make_part(c, 0, C, T, s);
+    p.f = plan_call(c, C, T, true, true);
+    if (int rc = ensure_ovl(c, p.f, C, T)) return rc;
     p.Xf = Xf; p.Yf = Yf; p.tap = tap;
     p.state_in = state_in; p.state_out = state_out;
     p.state_slab = (size_t)2 * 2 * C * c->K * HID;     // one Time block's (h,c) x 2 layers
-    const bsrnn_ctx::OvlTable* tb = c->small_rows ? nullptr : ovl_table(c, C, T, s);
+    const bsrnn_ctx::OvlTable* tb = ovl_table(c, p.f, C, T, s);
     if (tb) run_overlapped(c, p, tb, MS_BANDSPLIT, MS_MASK);
     else
     for (int st = MS_BANDSPLIT; st <= MS_MASK; ++st) run_stage(c, p, st);
-    c->small_rows = false;
     if (c->stage_error) { c->stage_error = false; return fail(BSRNN_ESTATE, "no task table for %d frame rows (internal error)", C * T); }
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
+// The guard word the fp16x2 kernels set, read and cleared (the host-mapped word: the caller has waited for the kernels it means).
+static int take_guard(bsrnn_ctx* c)
+{
+    if (!c->h_range) return 0;
+    const int v = *(volatile int*)c->h_range;
+    if (v) *(volatile int*)c->h_range = 0;
+    return v;
+}
+// The guard values that are not about the fp16 range (1): 3 = a time-axis launch gave up waiting on its own workgroup-local counters
+// (internal error); 4 = the band-pair launch's partner workgroups did not meet (placement / dispatch order not as assumed); 5 = a consumer
+// of the overlapped dual path gave up waiting for the time-axis launch beside it.  4 and 5 switch the context for good to the flow
+// without that assumption (same arithmetic: one launch per layer / launch after launch; ++gen re-captures streaming graphs, which contain
+// the old flow).  Returns BSRNN_EHIP with the message for 3, 4 and 5 - `who` names the call whose results are invalid -, else 0.
+static int guard_fallback(bsrnn_ctx* c, int v, const char* who)
+{
+    if (v == 3) return fail(BSRNN_EHIP, "%s: a time-axis LSTM launch gave up waiting on its own workgroup-local counters (internal error)", who);
+    if (v != 4 && v != 5) return 0;
+    (v == 4 ? c->band_pair_off : c->overlap_off) = true;
+    ++c->gen;
+    return fail(BSRNN_EHIP, v == 4 ? "%s: a band-axis launch (both layers in one launch) did not find its partner workgroups on the same XCD in time; "
+                                     "its results are invalid - repeat the call (the context now runs one launch per layer)"
+                                   : "%s: a consumer workgroup of the overlapped dual path gave up waiting for the time-axis launch beside it; its "
+                                     "results are invalid - repeat the call (the context now runs launch after launch)", who);
+}
 int check_range(bsrnn_ctx* c)
 {
-    if (c->h_range && *(volatile int*)c->h_range) {
-        const int v = *(volatile int*)c->h_range;
-        *(volatile int*)c->h_range = 0;
-        if (v == 3) return fail(BSRNN_EHIP, "an earlier time-axis LSTM launch gave up waiting on its own workgroup-local counters (internal error)");
-        if (v == 4) {
-            c->band_pair_off = true;
-            ++c->gen;                                 // captured streaming graphs contain the pair launch: re-capture with one launch per layer
-            return fail(BSRNN_EHIP, "an earlier band-axis launch (both layers in one launch, range policy 'deferred') did not find its partner workgroups on the "
-                                    "same XCD in time; its results are invalid - repeat the call (the context now runs one launch per layer)");
-        }
-        if (v == 5) {
-            c->overlap_off = true;
-            ++c->gen;
-            return fail(BSRNN_EHIP, "an earlier call (range policy 'deferred') ran its dual path overlapped and a consumer workgroup gave up waiting for the "
-                                    "time-axis launch beside it; its results are invalid - repeat the call (the context now runs launch after launch)");
-        }
-        return fail(BSRNN_ERANGE, "an earlier call (range policy 'deferred') fed the fp16x2 matrix path an activation beyond +-65504; its "
-                                  "results are invalid - repeat it under the default policy, rescale the input or set BSRNN_GEMM=f32 BSRNN_LSTM=f32");
-    }
-    return 0;
+    const int v = take_guard(c);
+    if (!v) return 0;
+    if (int rc = guard_fallback(c, v, "an earlier call (range policy 'deferred')")) return rc;
+    return fail(BSRNN_ERANGE, "an earlier call (range policy 'deferred') fed the fp16x2 matrix path an activation beyond +-65504; its "
+                              "results are invalid - repeat it under the default policy, rescale the input or set BSRNN_GEMM=f32 BSRNN_LSTM=f32");
 }
 // True when the byte ranges [a, a + na) and [b, b + nb) share a byte (null pointers share none).  A call whose re-run (finish_call)
 // reads an input that the first run's outputs may have overwritten is refused on this test, not just on pointer equality.
@@ -808,35 +859,25 @@ static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return pa < pb + nb && pb < pa + na;
 }
-// End of a model entry point under the default range policy (include/bsrnn_hip.h): wait for the call's own kernels, look at the
-// guard word the fp16x2 kernels set when an operand left the fp16 range, and if it is set run the call again on the library's
-// exact-fp32 kernels (fp32 weights are always resident; no range limit) before returning - never wrong numbers with rc 0.
+// End of a model entry point under the default range policy (include/bsrnn_hip.h; any_policy: whatever the context's policy): wait for
+// the call's own kernels, look at the guard word the fp16x2 kernels set, and if it is set run the call again before returning - never
+// wrong numbers with rc 0.  Structural fall-backs first (guard_fallback: the context switches flow; at most two such re-runs, one per
+// kind), then for an operand that left the fp16 range the library's exact-fp32 kernels (fp32 weights are always resident; no range limit).
 template <class F>
-int finish_call(bsrnn_ctx* c, hipStream_t s, F&& rerun)
+int finish_call(bsrnn_ctx* c, hipStream_t s, F&& rerun, bool any_policy = false)
 {
-    if (c->range_policy != BSRNN_RANGE_EXACT || !c->h_range || force_f32()) return 0;
+    if ((c->range_policy != BSRNN_RANGE_EXACT && !any_policy) || !c->h_range || force_f32()) return 0;
     if (gemm_mode() == GEMM_F32 && lstm_mode() == LSTM_F32) return 0;
-    HIP_TRY(hipStreamSynchronize(s));
-    if (int rcj = ovl_join_host(c)) return rcj;      // (the second time-axis launch of an overlapped call ran on the auxiliary stream: its guard word too)
-    const int v = *(volatile int*)c->h_range;
-    if (!v) return 0;
-    *(volatile int*)c->h_range = 0;
-    if (v == 3) return fail(BSRNN_EHIP, "the time-axis LSTM launch gave up waiting on its own workgroup-local counters (internal error)");
-    // Structural fall-backs first (same arithmetic, fewer assumptions about dispatch): 5 = a consumer of the overlapped dual path gave up
-    // waiting for the time-axis launch beside it -> launch after launch; 4 = the band-pair launch's partners did not meet (placement /
-    // dispatch order not as assumed) -> one launch per layer.  Each sticks to the context; at most one re-run per kind.
-    int vv = v;
-    for (int tries = 0; tries < 2 && (vv == 4 || vv == 5); ++tries) {
-        if (vv == 4) c->band_pair_off = true; else c->overlap_off = true;
-        ++c->gen;                                 // (a streaming graph captured with the old flow is re-captured by the re-run)
-        if (int rc4 = rerun()) return rc4;
+    for (int reruns = 0;; ++reruns) {
         HIP_TRY(hipStreamSynchronize(s));
-        if (int rcj = ovl_join_host(c)) return rcj;
-        vv = *(volatile int*)c->h_range;
-        if (!vv) return 0;
-        *(volatile int*)c->h_range = 0;
+        if (int rcj = ovl_join_host(c)) return rcj;      // (the second time-axis launch of an overlapped call ran on the auxiliary stream: its guard word too)
+        const int v = take_guard(c);
+        if (!v) return 0;
+        if (v != 3 && v != 4 && v != 5) break;
+        const int rc = guard_fallback(c, v, "the call");
+        if (v == 3 || reruns == 2) return rc;
+        if (int rc2 = rerun()) return rc2;
     }
-    if (vv == 3 || vv == 4 || vv == 5) return fail(BSRNN_EHIP, "a recurrent launch gave up waiting on its partners (internal error, guard value %d)", vv);
     set_force_f32(true);
     const int rc = rerun();
     set_force_f32(false);
@@ -1591,7 +1632,7 @@ int bsrnn_forward(bsrnn_ctx* c, const float* x, float* y, float* mask, int32_t C
     hipStream_t s = (hipStream_t)stream;
     ENTER_CALL(c, s);
     const size_t M = (size_t)C * T;
-    if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M)) || (rc = ensure_ovl(c, C, T))) return rc;
+    if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M))) return rc;
     if (mask && (rc = ensure_tap(c, M))) return rc;
     // The re-run (finish_call) starts from the frame-major copy Xf of the first run, which nothing in run_model writes: y and mask
     // may overlap x (an in-place call) and the re-run still sees the caller's input.
@@ -1619,7 +1660,7 @@ int bsrnn_forward_chunk(bsrnn_ctx* c, const float* x, const float* state_in, flo
     hipStream_t s = (hipStream_t)stream;
     ENTER_CALL(c, s);
     const size_t M = (size_t)C * L;
-    if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M)) || (rc = ensure_ovl(c, C, L))) return rc;
+    if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M))) return rc;
     // The re-run reads state_in again (and x through its frame-major copy Xf, as bsrnn_forward): no output may overlap state_in.
     const size_t ns = (size_t)4 * 2 * C * c->K * HID * sizeof(float), ny = (size_t)C * F2 * L * sizeof(float);
     if (c->range_policy == BSRNN_RANGE_EXACT && (ranges_overlap(state_in, ns, state_out, ns) || ranges_overlap(state_in, ns, y, ny)))
@@ -1658,34 +1699,17 @@ int bsrnn_dual_path(bsrnn_ctx* c, const float* z, float* z_out, const float* sta
         (ranges_overlap(z, bz, z_out, bz) || ranges_overlap(z, bz, state_out, bs) ||
          ranges_overlap(state_in, bs, z_out, bz) || ranges_overlap(state_in, bs, state_out, bs)))
         return fail(BSRNN_EARG, "bsrnn_dual_path: z_out and state_out must not overlap z or state_in (a call that leaves the fp16 range is run again from them)");
+    // the recurrent stages of run_stage on one part (never on the GEMV kernels)
     auto run = [&]() -> int {
-    HIP_TRY(hipMemcpyAsync(c->Z0, z, nz * sizeof(float), hipMemcpyDeviceToDevice, s));
-    const size_t slab = (size_t)2 * 2 * C * K * HID;
-    for (int blk = 0; blk < 2; ++blk) {
-        if (band_block_is_small(M, K)) {
-            launch_band_block_small(c->Z0, c->Z1, c->bandW16[blk][0], c->bandB[blk][0], c->bandW16[blk][1], c->bandB[blk][1],
-                                    c->bandFc16[blk], c->bandFcB[blk], M, K, c->d_range, s);
-        } else if (ctx_parts(c)) {                 // the block's fc + residual inside the launches around it (run_stage, kernels.h)
-            float* zi = blk ? c->Z1 : c->Z0;
-            float* zo = blk ? c->Z0 : c->Z1;
-            launch_band_pair(zi, c->HB0, c->HB1, c->bandW16[blk][0], c->bandB[blk][0], c->bandW16[blk][1], c->bandB[blk][1], M, K, c->d_range, s,
-                             c->bandFc16[blk], c->bandFcB[blk], c->band_flags);
-            launch_time_lstm(zi, zo, c->timeW[blk], c->timeW16[blk], c->timeB[blk], state_in ? state_in + blk * slab : nullptr,
-                             state_out ? state_out + blk * slab : nullptr, C, T, K, c->d_range, s, c->timeFc16[blk], c->timeFcB[blk], c->HB1);
-            continue;
-        } else {
-            launch_band_lstm(c->Z0, c->HB0, c->bandW[blk][0], c->bandW16[blk][0], c->bandB[blk][0], M, K, 64, c->d_range, s);
-            launch_band_lstm(c->HB0, c->HB1, c->bandW[blk][1], c->bandW16[blk][1], c->bandB[blk][1], M, K, 128, c->d_range, s);
-            gemm_slot(c, BLK_FC0 + 2 * blk, c->HB1, 2 * HID, c->Z1, HID, c->Z0, HID, nullptr, 0, nullptr, M * K, EPI_RES, s);
-        }
-        const bool fused = time_lstm_fuses_fc();
-        launch_time_lstm(c->Z1, fused ? c->Z0 : c->H1, c->timeW[blk], c->timeW16[blk], c->timeB[blk], state_in ? state_in + blk * slab : nullptr,
-                         state_out ? state_out + blk * slab : nullptr, C, T, K, c->d_range, s, c->timeFc16[blk], c->timeFcB[blk]);
-        if (!fused) gemm_slot(c, BLK_FC1 + 2 * blk, c->H1, HID, c->Z0, HID, c->Z1, HID, nullptr, 0, nullptr, M * K, EPI_RES, s);
-    }
-    HIP_TRY(hipMemcpyAsync(z_out, c->Z0, nz * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipGetLastError());
-    return 0;
+        HIP_TRY(hipMemcpyAsync(c->Z0, z, nz * sizeof(float), hipMemcpyDeviceToDevice, s));
+        Part p = make_part(c, 0, C, T, s);
+        p.f = plan_call(c, C, T, false, false);
+        p.state_in = state_in; p.state_out = state_out;
+        p.state_slab = (size_t)2 * 2 * C * K * HID;
+        for (int st = MS_BAND0; st <= MS_TIMEFC1; ++st) run_stage(c, p, st);
+        HIP_TRY(hipMemcpyAsync(z_out, c->Z0, nz * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipGetLastError());
+        return 0;
     };
     if ((rc = run())) return rc;
     return finish_call(c, s, run);
@@ -1990,7 +2014,8 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
     // Part j starts one stage behind part j-1 so that they sit in different stages.
     // (one block while the time-axis launch of the whole batch is one round of workgroups - eight sequences each from 1 024 sequences on -,
     //  two from there: 128 / 160 rows 1.75 / 2.26 -> 1.73 / 2.18 ms with one block, 192 / 256 rows 2.59 / 3.43 ms with two against 2.72 / 3.47)
-    int parts = R >= 128 && ((int64_t)R * c->K + time_lstm_seqs(R * c->K) - 1) / time_lstm_seqs(R * c->K) > device_cus() ? 2 : 1;
+    const Flow whole = plan_call(c, R, T, false, true);
+    int parts = R >= 128 && whole.nwg > device_cus() ? 2 : 1;
     if (R < 2 * parts || (int64_t)R * T < 2048) parts = 1;
     if (parts > 1 && (rc = ensure_streams(c, parts))) return rc;
     Part pt[MAX_PARTS];
@@ -1998,7 +2023,7 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
         int ms[MAX_PARTS];
         for (int j = 0; j < parts; ++j) ms[j] = ((int)((int64_t)R * (j + 1) / parts) - (int)((int64_t)R * j / parts)) * T;
         if ((rc = ensure_tasks(c, ms, parts))) return rc;
-        if (parts == 1 && (rc = ensure_ovl(c, R, T))) return rc;
+        if (parts == 1 && (rc = ensure_ovl(c, whole, R, T))) return rc;
     }
     for (int j = 0; j < parts; ++j) {
         const int r0 = (int)((int64_t)R * j / parts), r1 = (int)((int64_t)R * (j + 1) / parts);
@@ -2009,11 +2034,12 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
         pt[j].wave_out = wave_out + (size_t)r0 * out_len;
     }
     auto run = [&]() -> int {
+        for (int j = 0; j < parts; ++j) pt[j].f = plan_call(c, pt[j].C, T, false, parts == 1);
         if (parts > 1) {
             HIP_TRY(hipEventRecord(c->ev_fork, s));
             for (int j = 0; j < parts; ++j) HIP_TRY(hipStreamWaitEvent(c->aux[j], c->ev_fork, 0));
         }
-        const bsrnn_ctx::OvlTable* tb = parts == 1 ? ovl_table(c, R, T, s) : nullptr;
+        const bsrnn_ctx::OvlTable* tb = parts == 1 ? ovl_table(c, pt[0].f, R, T, s) : nullptr;
         if (tb) run_overlapped(c, pt[0], tb, MS_STFT, MS_ISTFT);      // the dual path overlapped on the context's auxiliary stream
         for (int step = 0; !tb && step < MS_COUNT + parts - 1; ++step)
             for (int j = 0; j < parts; ++j) {
@@ -2122,17 +2148,10 @@ int bsrnn_evaluate(bsrnn_ctx* c, const float* mix, const float* speech, int32_t 
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : fail(BSRNN_EHIP, "bsrnn_evaluate: %s", hipGetErrorString(e));
     };
-    rc = run();
-    // Synchronous entry point: every kernel of the call has finished, so the range guard of the fp16x2 kernels is final.
-    // If an operand left the fp16 range, the numbers above are saturated: run the call again on the exact-fp32 kernels of
-    // this library (same weights, no range limit) instead of returning them.
-    if (rc == 0 && c->h_range && *(volatile int*)c->h_range && !force_f32()) {
-        *(volatile int*)c->h_range = 0;
-        set_force_f32(true);
-        rc = run();
-        set_force_f32(false);
-    }
-    return cleanup(rc);
+    // A synchronous entry point: whatever the context's range policy, the guard word is handled before the metrics are returned, as under
+    // the default policy (finish_call: a structural fall-back, or the exact-fp32 kernels for an operand that left the fp16 range)
+    if ((rc = run())) return cleanup(rc);
+    return cleanup(finish_call(c, s, run, true));
 }
 
 

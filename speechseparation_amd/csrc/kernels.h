@@ -144,9 +144,6 @@ constexpr int OVL_SPIN_LIMIT = 20000000;       // 100 MHz ticks (s_memrealtime) 
                                                // time-axis launch (0.1 ... a few ms); under a tool that serialises kernels (rocprofv3 --pmc) the
                                                // producer never runs beside the consumer: the call falls back after this long, once per context
 void launch_ovl_gate(const int* resident, int target, int* range_flag, int spin_limit, hipStream_t stream);
-// sequences per workgroup of the time-axis launch over N sequences: 4 (time_lstm_h2w_kernel), or 8 (time_lstm_h2w8_kernel) where four would need more than one
-// round of workgroups or BSRNN_TIME_SEQ8=1 asks for it; the launcher and whoever sizes things by that launch's workgroups (api.hip: overlap) ask here
-int time_lstm_seqs(int N);
 int device_cus();                                  // CUs of the current device (256 on MI355X), read once
 #if defined(__HIPCC__)
 // frame rows m_first .. m_last (m = batch row * T + frame) of bands k_first .. k_last: wait until every time-axis workgroup that owns one
@@ -183,22 +180,22 @@ __device__ __forceinline__ bool ovl_wait_rows(const int* prog, int m_first, int 
 //   wpk  packed [2 dir][4 wave][(IN+64)/4 step][4 gate][64 lane], bias [2][256]
 //   wpk16 (LSTM_FP16X2): the same matrix as two fp16 pieces in the f16 MFMA's B-operand order,
 //         [2 dir][4 wave][(IN+64)/32 blk][4 gate][2 piece][64 lane][8]
+//   f32: the exact-fp32 kernels (BSRNN_LSTM=f32, range-guard re-run), else fp16x2
 void launch_band_lstm(const float* xin, float* hout, const float* wpk, const void* wpk16, const float* bias,
-                      int N, int L, int IN, int* range_flag, hipStream_t stream);
+                      int N, int L, int IN, int* range_flag, hipStream_t stream, bool f32);
 // The block's fc in parts (BSRNN_BAND_FC): with fc16 / fcb the pair launch below writes to hb1, instead of h, the two directions' SHARES
 // of fc(h): hb1[n][t][dir * 64 + f] = sum_k W_fc[f][dir * 64 + k] h_dir[n][t][k] (+ b[f] in the forward half); the time-axis launch
 // adds the halves and the residual (`part` of launch_time_lstm), so the block's fc launch disappears.
-bool band_fc_in_parts();
-// Both layers of a band block in one launch (lstm.hip::band_pair_h2_kernel): flags = 2 ints per tile of 16 sequences, zero before the
-// first launch and otherwise only touched by these launches.
-bool band_pair_enabled();
+// Both layers of a band block in one launch (lstm.hip::band_pair_h2_kernel, fp16x2 only): flags = 2 ints per tile of 16 sequences, zero
+// before the first launch and otherwise only touched by these launches.
 void launch_band_pair(const float* z, float* hb0, float* hb1, const void* w0pk16, const float* bias0, const void* w1pk16, const float* bias1,
                       int N, int L, int* range_flag, hipStream_t stream, const void* fc16, const float* fcb, int* flags,
                       const OvlConsumer* ovl = nullptr, int* zero_words = nullptr, int zero_n = 0, hipEvent_t done = nullptr);   // zero_words: progress words to clear (overlapped dual path)
 // The whole band-axis block (both layers, both directions, fc + residual) of a few sequences in one workgroup: the streaming
 // step's N = C frame rows.  w0pk16 / w1pk16 / bias0 / bias1 are launch_band_lstm's arguments of the two layers; fc16 the block's
 // fc (128 -> 64) as fp16x2 B fragments [4 tile][4 blk][2 piece][64 lane][8], fcb its bias.  zout = fc(h1) + b + zin.
-bool band_block_is_small(int N, int L);
+// fp16x2 only; 1 <= N <= 8 sequences of 1 <= L <= BS_MAXL steps (api.hip decides when a call takes it).
+constexpr int BS_MAXL = 16;                     // positions (bands) the LDS images hold; longer band tables take the general kernels
 void launch_band_block_small(const float* zin, float* zout, const void* w0pk16, const float* bias0, const void* w1pk16, const float* bias1,
                              const void* fc16, const float* fcb, int N, int L, int* range_flag, hipStream_t stream);
 // How the recurrent layers evaluate their gate products (environment BSRNN_LSTM = f32 | fp16x2, read once).
@@ -208,16 +205,17 @@ int lstm_mode();
 //   zin/hout [R][T][K][64]; sequences n = r*K + k;  wpk packed [2 layer][4 wave][128 k][64 lane]
 //   state_in/out [2 (h,c)][2 layer][R*K][64] or null
 //   wpk16 (LSTM_FP16X2): two fp16 pieces in B-operand order, [2 layer][4 wave][4 blk][4 gate][2 piece][64 lane][8]
-//   fc16 / fcb (LSTM_FP16X2, optional): the block's trailing fc (bsrnn.py:84) as two fp16 pieces in B-operand order,
-//         [4 wave][2 blk][2 piece][64 lane][8], and its bias [64].  When time_lstm_fuses_fc() and both are given, the launch
-//         writes the BLOCK's output fc(h1) + b + zin to hout (h1 never leaves the chip); otherwise hout = h1.
+//   f32: the exact-fp32 kernel (time_lstm_kernel; wpk), else the fp16x2 kernels (wpk16)
+//   seqs: sequences per workgroup of the fp16x2 launch: 4 (time_lstm_h2w_kernel), or 8 (time_lstm_h2w8_kernel, with fc16 / fcb only)
+//   fc16 / fcb (fp16x2, optional): the block's trailing fc (bsrnn.py:84) as two fp16 pieces in B-operand order,
+//         [4 wave][2 blk][2 piece][64 lane][8], and its bias [64].  When both are given, the launch writes the BLOCK's output
+//         fc(h1) + b + zin to hout (h1 never leaves the chip); otherwise hout = h1.
 //   part (with fc16 / fcb only, optional) [R][T][K][2][64]: the block's input is zin + part[.., 0, :] + part[.., 1, :] instead of zin
 //         (the shares of the preceding band block's fc, see launch_band_lstm); hout must then be a different buffer than zin.
 void launch_time_lstm(const float* zin, float* hout, const float* wpk, const void* wpk16, const float* bias,
                       const float* state_in, float* state_out, int R, int T, int K, int* range_flag, hipStream_t stream,
-                      const void* fc16 = nullptr, const float* fcb = nullptr, const float* part = nullptr,
+                      bool f32, int seqs, const void* fc16 = nullptr, const float* fcb = nullptr, const float* part = nullptr,
                       const OvlProducer* ovl = nullptr);   // ovl: with fc16 / fcb / part only (the fused launch of the parts flow)
-bool time_lstm_fuses_fc();
 
 // ------------------------------------------------------------------ training step, part 1: recurrent layers (lstm_train.hip)
 // One nn.LSTM layer (bsrnn.py:66-72) with ndir directions over N sequences of L steps, exact fp32; weights in torch layout

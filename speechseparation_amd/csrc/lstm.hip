@@ -570,11 +570,6 @@ __global__ __launch_bounds__(256, 2) void band_pair_h2_kernel(const float* __res
     band_layer_body<2 * HID, false, PART>(lds, dir, tile, hb0, hb1, w1, b1, N, L, range_flag, nullptr, wfc, bfc);
 }
 
-bool band_pair_enabled()
-{
-    static const bool on = [] { const char* e = getenv("BSRNN_BAND_PAIR"); return !(e && !strcmp(e, "0")); }();      // A/B: 0 = one launch per layer
-    return on && lstm_mode() == LSTM_FP16X2 && !force_f32();
-}
 // both layers of a band block as one launch (band_pair_h2_kernel); fc16 / fcb as launch_band_lstm's (shares of the fc) or null
 void launch_band_pair(const float* z, float* hb0, float* hb1, const void* w0pk16, const float* bias0, const void* w1pk16, const float* bias1,
                       int N, int L, int* range_flag, hipStream_t stream, const void* fc16, const float* fcb, int* flags, const OvlConsumer* ovlp,
@@ -597,22 +592,12 @@ void launch_band_pair(const float* z, float* hb0, float* hb1, const void* w0pk16
                               range_flag, (const uint4*)nullptr, (const float*)nullptr, flags, sabotage, ovl, zero_words, zero_n);
 }
 
-// BSRNN_BAND_FC = part (default: the second band layer writes the two directions' shares of the block's fc, the time-axis launch adds
-// them and the residual while it stages its input) | gemm (the block's fc + residual as a grouped-GEMM launch, as in rounds 1-2)
-bool band_fc_in_parts()
-{
-    static const bool on = [] { const char* e = getenv("BSRNN_BAND_FC"); return !(e && !strcmp(e, "gemm")); }();
-    // (the shares are formed by the pair launch only: the second layer alone with the shares sits at the edge of 256 VGPRs - as a
-    //  kernel of its own it compiled with four spilled registers, inside the pair kernel with none - and is not shipped)
-    return on && band_pair_enabled() && time_lstm_fuses_fc();
-}
-
 void launch_band_lstm(const float* xin, float* hout, const float* wpk, const void* wpk16, const float* bias,
-                      int N, int L, int IN, int* range_flag, hipStream_t stream)
+                      int N, int L, int IN, int* range_flag, hipStream_t stream, bool f32)
 {
     if (N <= 0 || L <= 0) return;
     const dim3 block(256);
-    if (lstm_mode() == LSTM_FP16X2 && !force_f32()) {
+    if (!f32) {
         const dim3 grid((((N + 15) / 16 + 7) / 8) * 16);      // both directions of eight tiles per 16 consecutive workgroups
         if (IN == 64)
             hipLaunchKernelGGL(band_lstm_h2_kernel<64>, grid, block, 0, stream, xin, hout, (const uint4*)wpk16, bias, N, L, range_flag, (unsigned long long*)nullptr);
@@ -1763,7 +1748,6 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w8_kernel(const float* __res
 // direction, waves 4-7 the backward one; one barrier per step; all L positions of x, of layer 0's output and of layer 1's
 // output stay in LDS as fp16 pieces ([k / 8][sequence][8] per position), the fc at the end batches four positions per tile.
 // =====================================================================================
-constexpr int BS_MAXL = 16;                     // positions (bands) the LDS images hold; longer band tables take the general kernels
 constexpr int BS_XSTEP = TSTEP;                 // halves per position of the 64-wide x image (2 pieces x [8][4][8] + skew)
 constexpr int BS_HSTEP = 2 * 4 * 2 * HID + 32;  // halves per position of a 128-wide image (forward | backward halves)
 
@@ -1909,11 +1893,6 @@ __global__ __launch_bounds__(512) void band_block_small_kernel(const float* __re
     if (!(amax <= 65504.f) && range_flag) *range_flag = 1;
 }
 
-// true when launch_band_block_small() will take the block (fp16x2 modes, few sequences, a band table that fits the LDS images)
-bool band_block_is_small(int N, int L)
-{
-    return lstm_mode() == LSTM_FP16X2 && !force_f32() && gemm_mode() != GEMM_F32 && N >= 1 && N <= 8 && L >= 1 && L <= BS_MAXL;
-}
 void launch_band_block_small(const float* zin, float* zout, const void* w0pk16, const float* bias0, const void* w1pk16, const float* bias1,
                              const void* fc16, const float* fcb, int N, int L, int* range_flag, hipStream_t stream)
 {
@@ -1921,47 +1900,22 @@ void launch_band_block_small(const float* zin, float* zout, const void* w0pk16, 
                        (const uint4*)w1pk16, bias1, (const uint4*)fc16, fcb, N, L, range_flag);
 }
 
-// The 16-wave kernel computes the block's fc + residual itself when the Linear layers are not asked to be exact fp32
-// (BSRNN_GEMM=f32 keeps every nn.Linear on the fp32 matrix kernels) - api.hip then skips the block's grouped-GEMM launch.
-// BSRNN_TIME_KERNEL = v3 (the same kernel, the fc as a separate launch) | fused (default).
-static bool time_kernel_fused()
-{
-    static const bool fused = [] {
-        const char* e = getenv("BSRNN_TIME_KERNEL");
-        if (!e || !*e || !strcmp(e, "fused")) return true;
-        if (!strcmp(e, "v3")) return false;
-        fprintf(stderr, "bsrnn: unknown BSRNN_TIME_KERNEL='%s' (v3 | fused), using fused\n", e);
-        return true;
-    }();
-    return fused;
-}
-bool time_lstm_fuses_fc()
-{
-    return lstm_mode() == LSTM_FP16X2 && !force_f32() && gemm_mode() != GEMM_F32 && time_kernel_fused();
-}
-
 int device_cus()
 {
     static const int cus = [] { int d = 0, n = 0; return hipGetDevice(&d) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0 ? n : 256; }();
     return cus;
 }
-int time_lstm_seqs(int N)
-{
-    static const int seq8 = [] { const char* e = getenv("BSRNN_TIME_SEQ8"); return e ? atoi(e) : -1; }();
-    if (lstm_mode() != LSTM_FP16X2 || force_f32() || !time_lstm_fuses_fc()) return 4;
-    return seq8 == 1 || (seq8 < 0 && (N + 3) / 4 > device_cus()) ? 8 : 4;
-}
 void launch_time_lstm(const float* zin, float* hout, const float* wpk, const void* wpk16, const float* bias,
                       const float* state_in, float* state_out, int R, int T, int K, int* range_flag, hipStream_t stream,
-                      const void* fc16, const float* fcb, const float* part, const OvlProducer* ovl)
+                      bool f32, int seqs, const void* fc16, const float* fcb, const float* part, const OvlProducer* ovl)
 {
     const int N = R * K;
     if (N <= 0 || T <= 0) return;
     dim3 grid((N + 3) / 4), block(512), block16(1024);
-    if (lstm_mode() == LSTM_FP16X2 && !force_f32()) {
-        // Eight sequences per workgroup where four would need more than one round of workgroups (one per CU): the 41-band table, large batches;
-        // BSRNN_TIME_SEQ8 = 0 never / 1 always (A/B, tests).  Results are bit-identical either way.
-        if (time_lstm_fuses_fc() && fc16 && fcb && time_lstm_seqs(N) == 8) {
+    if (!f32) {
+        // Eight sequences per workgroup (api.hip decides when: where four would need more than one round of workgroups, or BSRNN_TIME_SEQ8=1).
+        // Results are bit-identical either way.
+        if (fc16 && fcb && seqs == 8) {
             const dim3 grid8((N + 7) / 8);
             if (part)
                 hipLaunchKernelGGL((time_lstm_h2w8_kernel<true, false, true>), grid8, block16, 0, stream, zin, hout, (const uint4*)wpk16, bias, (const uint4*)fc16, fcb,
@@ -1972,11 +1926,11 @@ void launch_time_lstm(const float* zin, float* hout, const float* wpk, const voi
                                    state_in, state_out, R, T, K, range_flag, (unsigned long long*)nullptr);
             return;
         }
-        if (time_lstm_fuses_fc() && fc16 && fcb && part)
+        if (fc16 && fcb && part)
             hipLaunchKernelGGL((time_lstm_h2w_kernel<true, false, true>), grid, block16, 0, stream, zin, hout, (const uint4*)wpk16, bias, (const uint4*)fc16, fcb,
                                state_in, state_out, R, T, K, range_flag, (unsigned long long*)nullptr, part, ovl ? ovl->resident : (int*)nullptr,
                                ovl ? ovl->prog : (int*)nullptr, ovl ? ovl->base : 0);
-        else if (time_lstm_fuses_fc() && fc16 && fcb)
+        else if (fc16 && fcb)
             hipLaunchKernelGGL((time_lstm_h2w_kernel<true, false>), grid, block16, 0, stream, zin, hout, (const uint4*)wpk16, bias, (const uint4*)fc16, fcb,
                                state_in, state_out, R, T, K, range_flag, (unsigned long long*)nullptr);
         else

@@ -70,3 +70,34 @@ def test_time_axis_kernel_with_eight_sequences_per_workgroup_is_bit_identical():
         assert r.returncode == 0, r.stdout[-3000:]
         hashes.append([l for l in r.stdout.splitlines() if l.startswith("HASHES ")][-1])
     assert hashes[0] == hashes[1], hashes
+
+
+_DUAL_SCRIPT = r"""
+import hashlib, sys, torch
+sys.path.insert(0, %r)
+from speechseparation_amd import weights
+from speechseparation_amd.bsrnn import BSRNN
+sd = weights.synth_state_dict(None, seed=1, lstm_gain=3.0)
+m = BSRNN().eval(); m.load_state_dict({k: torch.from_numpy(a.copy()) for k, a in sd.items()}, strict=True); m = m.to("cuda")
+out = []
+for C, T, seed in ((5, 33, 1), (100, 20, 2), (2, 3, 3)):
+    z = torch.from_numpy(weights.synth_tensor((C, T, 12, 64), seed=seed, scale=0.4)).cuda()
+    s = torch.from_numpy(weights.synth_tensor((4, 2, C * 12, 64), seed=seed + 10, scale=0.3)).cuda()
+    zo, so = m.dual_path(z, s)
+    out.append(hashlib.sha256(zo.cpu().numpy().tobytes() + so.cpu().numpy().tobytes()).hexdigest())
+print("HASHES " + " ".join(out))
+"""
+
+
+def test_dual_path_with_the_gemm_fc_equals_one_launch_per_layer():
+    """bsrnn_dual_path runs the recurrent stages of the model's own schedule: under BSRNN_BAND_FC=gemm that is the band-pair launch with the
+    block's fc as a grouped-GEMM launch, under BSRNN_BAND_PAIR=0 one launch per band layer with the same fc launch (read once per process).
+    The same arithmetic on the same numbers: the same bits, for a ragged batch, one whose time-axis launch takes eight sequences per workgroup
+    (100 rows x 12 bands) and a few frame rows (the small band block), each with state in and out."""
+    hashes = []
+    for env_extra in ({"BSRNN_BAND_FC": "gemm"}, {"BSRNN_BAND_PAIR": "0"}):
+        env = dict(os.environ, **env_extra)
+        r = subprocess.run([sys.executable, "-c", _DUAL_SCRIPT % REPO], env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:]
+        hashes.append([l for l in r.stdout.splitlines() if l.startswith("HASHES ")][-1])
+    assert hashes[0] == hashes[1], hashes

@@ -3,10 +3,14 @@ first time-axis launch and the mask chain beside the second, on an auxiliary str
 its own rows.  Same kernels and arithmetic as the serial flow, another dispatch order: every result must be EQUAL to BSRNN_OVERLAP=0,
 call after call, also beside other work on the GPU; a consumer whose bounded wait expires is reported and the call falls back."""
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+from conftest import REPO
 
 pytestmark = pytest.mark.gpu
 
@@ -160,7 +164,7 @@ def test_progress_word_epochs_start_again(sd_hot, models):
 
 def test_a_batch_whose_time_axis_launch_takes_eight_sequences_per_workgroup_overlaps_too(models):
     """100 rows x 12 bands = 1 200 sequences: four per workgroup would be 300 workgroups (more than one per CU), so the time-axis launches run
-    eight per workgroup (lstm.hip::time_lstm_seqs) - 150 workgroups, inside the overlap's range: the consumers then map sequences to producer
+    eight per workgroup (api.hip::plan_call, Flow::seqs) - 150 workgroups, inside the overlap's range: the consumers then map sequences to producer
     workgroups eight at a time (OvlConsumer::wg_shift).  Equal to the serial flow."""
     from speechseparation_amd import weights
     ovl, ser = models
@@ -169,3 +173,40 @@ def test_a_batch_whose_time_axis_launch_takes_eight_sequences_per_workgroup_over
     for i in range(3):
         assert np.array_equal(ovl.separate(w).cpu().numpy(), ref), "call %d" % i
     assert ovl.overlap_state() == 1
+
+
+_EVAL_SCRIPT = r"""
+import os, sys, torch
+sys.path.insert(0, %r)
+from speechseparation_amd import weights
+from speechseparation_amd.bsrnn import BSRNN
+sd = weights.synth_state_dict(None, seed=1, lstm_gain=3.0)
+def model(overlap):
+    os.environ["BSRNN_OVERLAP"] = overlap                # (read when the context is created)
+    m = BSRNN().eval(); m.load_state_dict({k: torch.from_numpy(a.copy()) for k, a in sd.items()}, strict=True); m = m.to("cuda")
+    m._context(torch.device("cuda", torch.cuda.current_device()))
+    return m
+ser, bad = model("0"), model("timeout")
+bad.set_range_policy("deferred")
+w = weights.synth_waveform(16, 40 * 1024 + 5, seed=8)
+mix, speech = torch.from_numpy(w).cuda(), torch.from_numpy(0.5 * w + 0.1 * weights.synth_waveform(16, 40 * 1024 + 5, seed=9)).cuda()
+ref = ser.evaluate(mix, speech)
+assert bad.overlap_state() == 1
+for i in range(2):
+    got = bad.evaluate(mix, speech)
+    assert got == ref, (i, got, ref)
+    print("call", i, "overlap_state", bad.overlap_state())
+bad.sync()
+print("EVAL OK overlap_state", bad.overlap_state())
+"""
+
+
+def test_evaluate_falls_back_from_an_expired_wait_under_the_deferred_policy():
+    """evaluate() is synchronous: whatever the range policy, it ends like a call under the default policy.  16 rows x 41 frames (48 time-axis
+    workgroups, one row block: the overlapped path) under BSRNN_OVERLAP=timeout (test hook: every consumer gives up, guard value 5) and the
+    'deferred' policy: rc 0, the metrics of the serial flow exactly, and the context stops overlapping (overlap_state 2).  In a child process
+    of its own (knobs are read once)."""
+    r = subprocess.run([sys.executable, "-c", _EVAL_SCRIPT % REPO], env=dict(os.environ), cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert "call 0 overlap_state 2" in r.stdout and "EVAL OK overlap_state 2" in r.stdout, r.stdout[-3000:]
