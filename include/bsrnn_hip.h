@@ -324,6 +324,17 @@ int  bsrnn_stream_reset(bsrnn_stream* s, void* stream);
 int  bsrnn_stream_step(bsrnn_stream* s, const float* chunk_dev, float* out_dev, float mix, void* stream);
 int  bsrnn_stream_step_host(bsrnn_stream* s, const float* chunk_host, float* out_host, float mix);
 int  bsrnn_stream_get_state(bsrnn_stream* s, float* state_host /* [4,2,C*K,64] */);
+/* L = n_hops consecutive bsrnn_stream_step calls in one: chunk_dev [C, n_hops*1024] -> out_dev [C, n_hops*1024]
+ * (delayed by one hop, like the step).  Carry (analysis buffer, previous synthesis frame, LSTM state) continues from
+ * and for bsrnn_stream_step / _step_host / _process in any mixture.  The model runs once on C * n_hops frame rows, planned
+ * like bsrnn_forward_chunk (so a block of several hops agrees with the same hops stepped one by one to rounding, not bit for
+ * bit; n_hops = 1 IS the step).  Range policy as for the step; the re-run reads chunk_dev again, so under BSRNN_RANGE_EXACT
+ * out_dev must not overlap chunk_dev (BSRNN_EARG); under BSRNN_RANGE_DEFERRED in-place is allowed. */
+int  bsrnn_stream_process(bsrnn_stream* s, const float* chunk_dev, float* out_dev, int32_t n_hops, float mix, void* stream);
+/* Do now everything a later bsrnn_stream_process of up to max_hops hops would otherwise do at first use (workspace and
+ * task tables of C*max_hops frame rows, kernel loading, overlap tables): such calls then allocate, capture and
+ * instantiate nothing (bsrnn_debug_counter 0..2 unchanged).  Synchronous; the carry is left as it is. */
+int  bsrnn_stream_reserve(bsrnn_stream* s, int32_t max_hops);
 
 /* ---- measurement support ---------------------------------------------------------------
  * bsrnn_set_profiling(ctx, mask): bit i of `mask` brackets stage i of every compute call with

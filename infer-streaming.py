@@ -2,7 +2,8 @@
 """Streaming separation entry point -- same command line as the reference's
 infer-streaming.py (--input/--output/--name), with the whole per-chunk loop
 (infer-streaming.py:104-147: slide buffer, rfft, forward_recurrent, irfft, 2-slot overlap-add)
-resident on the MI355X: one `StreamingSeparator.step` per 1024-sample chunk at 44.1 kHz.
+resident on the MI355X: one `StreamingSeparator.step` per 1024-sample chunk at 44.1 kHz, or with
+`--block N` one `StreamingSeparator.process` per N chunks (same output to rounding, far fewer launches).
 
 The reference also dumps the traced model for its LADSPA plugin (hello.onnx, :74); the
 counterpart here is the flat weight file `hello.bsrnnw` that speech_separator_ladspa.so loads
@@ -30,6 +31,9 @@ def main(argv=None):
     ap.add_argument("--synthetic-weights", type=int, default=None, metavar="SEED")
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--export", type=str, default="hello.bsrnnw")
+    ap.add_argument("--block", type=int, default=1, metavar="N",
+                    help="hops per library call: 1 = one step per 1024-sample chunk (the reference's loop), N > 1 = N hops per "
+                         "StreamingSeparator.process call")
     args = ap.parse_args(argv)
 
     torch.set_grad_enabled(False)
@@ -52,8 +56,15 @@ def main(argv=None):
     n_chunks = waveform.shape[1] // CHUNK                 # a short tail chunk ends the stream (:108)
     outs = []
     t = time.time()
-    for i in range(n_chunks):
-        outs.append(sep.step(waveform[:, i * CHUNK:(i + 1) * CHUNK].contiguous()))
+    if args.block < 1:
+        ap.error("--block must be at least 1")
+    if args.block == 1:
+        for i in range(n_chunks):
+            outs.append(sep.step(waveform[:, i * CHUNK:(i + 1) * CHUNK].contiguous()))
+    else:
+        sep.reserve(min(args.block, max(n_chunks, 1)))
+        for i in range(0, n_chunks, args.block):
+            outs.append(sep.process(waveform[:, i * CHUNK:min(i + args.block, n_chunks) * CHUNK]))
     torch.cuda.synchronize()
     elapsed = time.time() - t
     out = torch.cat(outs, 1) if outs else torch.zeros((2, 0))

@@ -24,6 +24,7 @@ SYMBOLS = [
     "bsrnn_istft_backward", "bsrnn_adamw_step", "bsrnn_adamw_step_multi", "bsrnn_adamw_step_multi_dev",
     "bsrnn_linear_group_train_forward", "bsrnn_linear_group_train_backward", "bsrnn_train_reduction_layout",
     "bsrnn_set_range_policy", "bsrnn_get_range_policy", "bsrnn_overlap_state", "bsrnn_debug_peek", "bsrnn_debug_counter",
+    "bsrnn_stream_process", "bsrnn_stream_reserve",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 METRIC_NAMES = ("loss", "sdr", "input_sdr", "sisdr", "l1_time", "l1_re", "l1_im", "separation_db")   # BSRNN_M_* order
@@ -90,6 +91,8 @@ def _load():
         "bsrnn_stream_step": (C.c_int, [vp, vp, vp, C.c_float, vp]),
         "bsrnn_stream_step_host": (C.c_int, [vp, vp, vp, C.c_float]),
         "bsrnn_stream_get_state": (C.c_int, [vp, vp]),
+        "bsrnn_stream_process": (C.c_int, [vp, vp, vp, i32, C.c_float, vp]),
+        "bsrnn_stream_reserve": (C.c_int, [vp, i32]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),
         "bsrnn_stage_name": (C.c_char_p, [i32]),

@@ -382,6 +382,7 @@ class StreamingSeparator:
         _check(_lib.bsrnn_stream_create(ctx, channels, ctypes.byref(h)))
         self._h = h
         self._steps = 0
+        self._pending = None        # process(): the samples (fewer than one hop) that wait for the next call, on the device
 
     def __del__(self):
         try:
@@ -391,6 +392,38 @@ class StreamingSeparator:
 
     def reset(self):
         _check(_lib.bsrnn_stream_reset(self._h, _stream_ptr(self.device)))
+        self._pending = None
+
+    def reserve(self, max_hops):
+        """Do now what a later process() of up to max_hops hops would otherwise do at first use (workspace, task tables,
+        kernel loading): such calls then allocate nothing."""
+        with torch.cuda.device(self.device):
+            _check(_lib.bsrnn_stream_reserve(self._h, int(max_hops)))
+
+    def process(self, wave, mix=1.0):
+        """wave [C, n] float32 (cuda or cpu), any n >= 0 -> [C, L*1024] on the same device: what L consecutive step() calls
+        return, from one library call (bsrnn_stream_process).  L = (pending + n) // 1024; a remainder of fewer than 1024
+        samples stays on the device and is prepended to the next call.  Carries on from and for step() in any mixture."""
+        if wave.dim() != 2 or wave.shape[0] != self.C:
+            raise ValueError("expected wave [%d, n], got %s" % (self.C, tuple(wave.shape)))
+        # the same look at the model's parameters as step() takes (see there), once per call
+        if self._steps % 32 == 0 or self.model._weights_touched(self._steps):
+            self.model._plist = None
+            with torch.cuda.device(self.device):
+                self.model._context(self.device)
+        self._steps += 1
+        w = wave.detach().to(device=self.device, dtype=torch.float32)
+        if self._pending is not None and self._pending.shape[1]:
+            w = torch.cat((self._pending, w), 1)
+        L = w.shape[1] // _spec.HOP
+        self._pending = w[:, L * _spec.HOP:].clone()
+        if L == 0:
+            return torch.empty((self.C, 0), dtype=torch.float32, device=wave.device)
+        x = w[:, :L * _spec.HOP].contiguous()
+        out = torch.empty_like(x)
+        with torch.cuda.device(self.device):
+            _check(_lib.bsrnn_stream_process(self._h, _ptr(x), _ptr(out), L, float(mix), _stream_ptr(self.device)))
+        return out if wave.is_cuda else out.cpu()
 
     def step(self, chunk, mix=1.0):
         """chunk [C, 1024] float32 (cuda or cpu) -> same-shaped output on the same device."""

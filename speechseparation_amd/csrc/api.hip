@@ -99,6 +99,8 @@ struct bsrnn_ctx {
     std::vector<long> chain_cost[2];
     struct TaskTable { int2* d[2]; int n[2]; };
     std::map<int, TaskTable> chain_tasks;       // per row count M: device task tables of the two chains
+    size_t task_cap = 64, ovl_cap = 16;         // bounds of the two table caches (chain_tasks, ovl_tables); bsrnn_stream_reserve raises them to
+                                                // hold one table per block length it was asked for
 
     const float *bandW[2][2], *bandB[2][2], *timeW[2], *timeB[2];
     const void *bandW16[2][2], *timeW16[2];
@@ -401,7 +403,7 @@ int ensure_tasks(bsrnn_ctx* c, const int* Ms, int n)
     int missing = 0;
     for (int i = 0; i < n; ++i) missing += c->chain_tasks.find(Ms[i]) == c->chain_tasks.end();
     if (!missing) return 0;
-    if (c->chain_tasks.size() + missing > 64) {
+    if (c->chain_tasks.size() + missing > c->task_cap) {
         HIP_TRY(hipDeviceSynchronize());
         for (auto& kv : c->chain_tasks)
             for (int ch = 0; ch < 2; ++ch) (void)hipFree(kv.second.d[ch]);
@@ -693,7 +695,7 @@ int ensure_ovl(bsrnn_ctx* c, const Flow& f, int C, int T)
     }
     const auto key = std::make_pair(C, T);
     if (c->ovl_tables.find(key) != c->ovl_tables.end()) return 0;
-    if (c->ovl_tables.size() >= 16) { HIP_TRY(hipDeviceSynchronize()); free_ovl_tables(c); ++c->gen; }
+    if (c->ovl_tables.size() >= c->ovl_cap) { HIP_TRY(hipDeviceSynchronize()); free_ovl_tables(c); ++c->gen; }
     // band block: tiles of 16 frame rows m = row * T + frame, sorted by the last frame the tile needs (a tile that straddles two batch
     // rows needs the first one's last frame); padded with -1 to the launch's whole groups of eight tiles
     const int tiles = (M + 15) / 16, n_ord = ((tiles + 7) / 8) * 8;
@@ -2345,6 +2347,92 @@ int bsrnn_stream_step_host(bsrnn_stream* st, const float* chunk_host, float* out
     HIP_TRY(hipStreamSynchronize(nullptr));
     memcpy(out_host, st->h_out, nb);
     return 0;
+}
+
+// L hops from carry set p = st->cur into set 1 - p: chunk [C][L*1024] -> out [C][L*1024], the spectra in the context's workspace (one call
+// at a time per context).  Does NOT flip st->cur (see stream_step_run).
+static int stream_block_run(bsrnn_stream* st, const float* chunk, float* out, int L, float mix, hipStream_t s)
+{
+    bsrnn_ctx* c = st->ctx;
+    const int p = st->cur, q = p ^ 1;
+    { StageScope sc(c, ST_STREAM_DSP, s); launch_stream_block_analysis(c->tb, st->buf[p], st->buf[q], chunk, c->Xf, st->C, L, s); }
+    if (int rc = run_model(c, c->Xf, c->Yf, nullptr, st->C, L, st->state[p], st->state[q], s)) return rc;
+    { StageScope sc(c, ST_STREAM_DSP, s); launch_stream_block_synthesis(c->tb, c->Yf, c->Xf, mix, st->prev[p], st->prev[q], out, st->C, L, s); }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int bsrnn_stream_process(bsrnn_stream* st, const float* chunk, float* out, int32_t n_hops, float mix, void* stream)
+{
+    if (!st || !chunk || !out) return fail(BSRNN_EARG, "bsrnn_stream_process: null argument");
+    if (n_hops < 1) return fail(BSRNN_EARG, "bsrnn_stream_process: n_hops = %d (at least one hop)", n_hops);
+    bsrnn_ctx* c = st->ctx;
+    int rc = check_ready(c);
+    if (rc) return rc;
+    const size_t nb = (size_t)st->C * n_hops * HOPS * sizeof(float);
+    if (c->range_policy == BSRNN_RANGE_EXACT && ranges_overlap(chunk, nb, out, nb))
+        return fail(BSRNN_EARG, "bsrnn_stream_process: out_dev must not overlap chunk_dev under the exact range policy (the re-run of a call that leaves the fp16 range reads chunk_dev again)");
+    if (n_hops == 1) return bsrnn_stream_step(st, chunk, out, mix, stream);       // the step itself: bit-identical by construction
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const size_t M = (size_t)st->C * n_hops;
+    if (M > (size_t)INT32_MAX / 2) return fail(BSRNN_EARG, "bsrnn_stream_process: %d rows x %d hops is too many frame rows for one call", st->C, n_hops);
+    if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M))) return rc;
+    if ((rc = stream_block_run(st, chunk, out, n_hops, mix, s))) return rc;
+    // range policy as for the step: the re-run repeats analysis, model and synthesis from the untouched carry set
+    if ((rc = finish_call(c, s, [&]() -> int { return stream_block_run(st, chunk, out, n_hops, mix, s); }))) return rc;
+    st->cur ^= 1;
+    return 0;
+}
+
+int bsrnn_stream_reserve(bsrnn_stream* st, int32_t max_hops)
+{
+    if (!st || max_hops < 1) return fail(BSRNN_EARG, "bsrnn_stream_reserve: bad arguments");
+    bsrnn_ctx* c = st->ctx;
+    int rc = check_ready(c);
+    if (rc) return rc;
+    ENTER_CALL(c, (hipStream_t) nullptr);
+    const int C = st->C;
+    if ((size_t)C * max_hops > (size_t)INT32_MAX / 2) return fail(BSRNN_EARG, "bsrnn_stream_reserve: %d rows x %d hops is too many frame rows for one call", C, max_hops);
+    if ((rc = ensure_ws(c, (size_t)C * max_hops))) return rc;
+    // one task table and (where the plan overlaps the dual path) one pair of dispatch orders per block length: they are keyed by the row
+    // count, and a later call of any length up to max_hops must find its own.  The caches' bounds grow so that this set fits beside what
+    // is there already (a few KB per table).
+    std::vector<int> ms;
+    size_t missing = 0, ovl_missing = 0;
+    for (int L = 1; L <= max_hops; ++L) {
+        ms.push_back(C * L);
+        missing += c->fused && c->chain_tasks.find(C * L) == c->chain_tasks.end();
+        ovl_missing += plan_call(c, C, L, true, true).overlap && c->ovl_tables.find(std::make_pair(C, L)) == c->ovl_tables.end();
+    }
+    c->task_cap = std::max(c->task_cap, c->chain_tasks.size() + missing);
+    c->ovl_cap = std::max(c->ovl_cap, c->ovl_tables.size() + ovl_missing + 1);
+    if ((rc = ensure_tasks(c, ms.data(), (int)ms.size()))) return rc;
+    for (int L = 1; L <= max_hops; ++L)
+        if ((rc = ensure_ovl(c, plan_call(c, C, L, true, true), C, L))) return rc;
+    // Load the kernels of every plan a block can take (GEMV rows, few-row band block, chains, overlapped dual path) and fill the launchers'
+    // function-local statics: throw-away blocks of zeros from the current carry set into the OTHER one, which the next real call
+    // overwrites completely (cur is not flipped).
+    const int cand[4] = {2, 8, 31, max_hops};
+    float* tmp = nullptr;
+    const size_t nfl = (size_t)C * max_hops * HOPS;
+    ++g_dbg[DBG_ALLOC];
+    HIP_TRY(hipMalloc((void**)&tmp, 2 * nfl * sizeof(float)));
+    hipError_t e = hipMemset(tmp, 0, 2 * nfl * sizeof(float));
+    int last = 1;
+    for (int i = 0; i < 4 && !rc && e == hipSuccess; ++i) {
+        const int L = std::min(cand[i], (int)max_hops);
+        if (L <= last) continue;
+        last = L;
+        rc = stream_block_run(st, tmp, tmp + nfl, L, 1.0f, nullptr);
+        if (!rc) rc = stream_block_run(st, tmp, tmp + nfl, L, 0.5f, nullptr);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (!rc) rc = ovl_join_host(c);
+    (void)hipFree(tmp);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(BSRNN_EHIP, "bsrnn_stream_reserve: %s", hipGetErrorString(e));
+    return check_range(c);
 }
 
 int bsrnn_stream_get_state(bsrnn_stream* st, float* state_host)

@@ -549,4 +549,152 @@ void launch_stream_synthesis(const FftTables& tb, const float* Y, const float* X
     hipLaunchKernelGGL(stream_synthesis_kernel, dim3(C), dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out);
 }
 
+// ------------------------------------------------------------------------------ streaming DSP, a block of L hops per row
+// The two kernels above for L consecutive hops in one launch (bsrnn_stream_process), built like the offline pair: a workgroup walks
+// `sch` consecutive hops of one row.  Per row the analysis reads S = buf_in[0:2048] ++ chunk[0:L*1024]; frame l is
+// S[(l+1)*1024 : (l+1)*1024 + 2048] (no reflection: the history is the carried buffer), and the new carry is the last frame's raw
+// samples.  Per frame the arithmetic is that of the one-hop kernels, in their order.
+__global__ __launch_bounds__(256, FFT_OCC_STFT) void stream_block_analysis_kernel(FftTables tb, const float* __restrict__ buf_in, float* __restrict__ buf_out,
+                                                                                  const float* __restrict__ chunk, float* __restrict__ X, int L, int sch)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const Twiddles twd = load_twiddles<false>(tb.tw1024, tid);
+    const SplitCtx spl = load_split(tb, tid, false);
+    const int r = blockIdx.y;
+    const int l0 = blockIdx.x * sch;
+    const int l1 = (l0 + sch < L) ? l0 + sch : L;
+    const float* carry = buf_in + (size_t)r * NFFT;
+    const float* fresh = chunk + (size_t)r * L * HOPS;
+    float2 win[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) win[k] = make_float2(tb.hann[2 * (tid + 256 * k)], tb.hann[2 * (tid + 256 * k) + 1]);
+    // complex sample c (0..1023) of frame l = S[(l+1)*1024 + 2c], S[.. + 1]: the carried buffer below index 2048 of S, the chunk above
+    // (both indices on the same side: the boundary is even)
+    auto sample2 = [&](int l, int c) {
+        const int64_t j = (int64_t)(l + 1) * HOPS + 2 * c;
+        return *reinterpret_cast<const float2*>(j < NFFT ? carry + j : fresh + (j - NFFT));
+    };
+    float2 raw[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) raw[k] = sample2(l0, tid + 256 * k);
+    for (int l = l0; l < l1; ++l) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) z0[tid + 256 * k] = make_float2(raw[k].x * win[k].x, raw[k].y * win[k].y);
+        __syncthreads();
+        raw[0] = raw[2]; raw[1] = raw[3];
+        { const int ln = l + 1 < l1 ? l + 1 : l; raw[2] = sample2(ln, tid + 512); raw[3] = sample2(ln, tid + 768); }      // (no branch: after the last frame a dummy reload)
+        const float2* Z = fft1024<false>(z0, z1, twd, tid);
+        rfft_split_store(Z, spl, X + ((size_t)r * L + l) * tb.ld, tid);
+        __syncthreads();                          // Z (= z1) is overwritten by the next frame's first pass
+    }
+    // the workgroup that owns the last hop leaves the new carry: buf_out = S[L*1024 : L*1024 + 2048] = the last frame's samples (its
+    // first half is read again here instead of being kept through the loop; buf_out is another set than buf_in)
+    if (l1 == L) {
+        float* b = buf_out + (size_t)r * NFFT;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 256 * k;
+            *reinterpret_cast<float2*>(b + 2 * c) = sample2(L - 1, c);
+            *reinterpret_cast<float2*>(b + HOPS + 2 * c) = raw[k];      // after the loop raw[0], raw[1] hold the last frame's second half
+        }
+    }
+}
+
+// out hop l = (wf_l[0:1024] + wf_{l-1}[1024:2048]) * inv_wsum with wf_l = irfft(mix(Y_l, X_l)) and wf_{-1} = prev_in; no synthesis
+// window.  A workgroup produces output hops [b0, b1) of one row, keeps the second half of the previous frame in registers and either
+// reads it from prev_in (b0 = 0) or recomputes frame b0 - 1; the spectrum of the next frame is requested before the FFT passes of the
+// current one.  MIX: the wet / dry control of stream_synthesis_kernel (the launcher picks MIX = mix != 1).
+template <bool MIX>
+__global__ __launch_bounds__(256, FFT_OCC_ISTFT) void stream_block_synthesis_kernel(FftTables tb, const float* __restrict__ Y, const float* __restrict__ X,
+                                                                                    const float mix, const float* __restrict__ prev_in,
+                                                                                    float* __restrict__ prev_out, float* __restrict__ out, int L, int ich)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const Twiddles twd = load_twiddles<true>(tb.tw1024, tid);
+    const SplitCtx spl = load_split(tb, tid, true);
+    const int r = blockIdx.y;
+    const int b0 = blockIdx.x * ich;
+    const int b1 = (b0 + ich < L) ? b0 + ich : L;                    // output hops [b0, b1) <- frames b0 - 1 .. b1 - 1
+    const float sc = 1.0f / 1024.0f;
+    const float dry = mix >= 0.f ? 1.f - mix : 1.f;
+    float2 wsum[2], carry[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int c = tid + 256 * k;
+        wsum[k] = make_float2(tb.inv_wsum[2 * c], tb.inv_wsum[2 * c + 1]);
+    }
+    const float* Yr = Y + (size_t)r * L * tb.ld;
+    const float* Xr = X + (size_t)r * L * tb.ld;
+    float* o = out + (size_t)r * L * HOPS;
+    MergeRegs my, mx;
+    auto request = [&](int t) {
+        irfft_load<false>(Yr + (size_t)t * tb.ld, spl, my, tid);
+        if (MIX) irfft_load<false>(Xr + (size_t)t * tb.ld, spl, mx, tid);
+    };
+    // The frame in front of the range only fills the carry; it is peeled so that the loop body has no branch around its loads and stores
+    auto frame = [&](int t, auto first) {
+        if (MIX) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                my.xk[i] = make_float2(mix * my.xk[i].x + dry * mx.xk[i].x, mix * my.xk[i].y + dry * mx.xk[i].y);
+                my.xc[i] = make_float2(mix * my.xc[i].x + dry * mx.xc[i].x, mix * my.xc[i].y + dry * mx.xc[i].y);
+            }
+        }
+        irfft_store(my, spl, z0, tid);
+        __syncthreads();
+        request(t + 1 < b1 ? t + 1 : t);                              // (after the last frame: a dummy reload)
+        const float2* z = fft1024<true>(z0, z1, twd, tid);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 256 * k;
+            const float2 a = z[c], b = z[c + 512];
+            if (!decltype(first)::value) {
+                // same operation order as the one-hop kernel: frame * 1/1024, add, times 1 / window sum
+                const float2 now = make_float2(a.x * sc, a.y * sc);
+                *reinterpret_cast<float2*>(o + (size_t)t * HOPS + 2 * c) =
+                    make_float2((now.x + carry[k].x) * wsum[k].x, (now.y + carry[k].y) * wsum[k].y);
+            }
+            carry[k] = make_float2(b.x * sc, b.y * sc);
+        }
+        __syncthreads();                              // z (= z1) is overwritten by the next frame's first pass
+    };
+    if (b0 == 0) {
+        request(0);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) carry[k] = *reinterpret_cast<const float2*>(prev_in + (size_t)r * NFFT + HOPS + 2 * (tid + 256 * k));
+    } else {
+        request(b0 - 1);
+        frame(b0 - 1, std::true_type());
+    }
+    for (int t = b0; t < b1; ++t) frame(t, std::false_type());
+    // the workgroup that owns the last hop leaves the whole last frame as the new carry, in the one-hop kernel's layout (fft1024 ends
+    // in z1, which nothing has touched since the last frame)
+    if (b1 == L) {
+        float* pv = prev_out + (size_t)r * NFFT;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = tid + 256 * i;
+            *reinterpret_cast<float2*>(pv + 2 * c) = make_float2(z1[c].x * sc, z1[c].y * sc);
+        }
+    }
+}
+
+void launch_stream_block_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L, hipStream_t s)
+{
+    static const int slots = resident_slots((const void*)stream_block_analysis_kernel);
+    const int sch = frames_per_workgroup(L, C, slots, 0);
+    hipLaunchKernelGGL(stream_block_analysis_kernel, dim3((unsigned)((L + sch - 1) / sch), C), dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, L, sch);
+}
+void launch_stream_block_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, const float* prev_in, float* prev_out, float* out,
+                                   int C, int L, hipStream_t s)
+{
+    static const int slots = resident_slots((const void*)stream_block_synthesis_kernel<false>);
+    const int ich = frames_per_workgroup(L, C, slots, 1);
+    const dim3 grid((unsigned)((L + ich - 1) / ich), C);
+    if (mix == 1.f) hipLaunchKernelGGL(stream_block_synthesis_kernel<false>, grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ich);
+    else hipLaunchKernelGGL(stream_block_synthesis_kernel<true>, grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ich);
+}
+
 }  // namespace bsrnn

@@ -320,6 +320,11 @@ void launch_from_frame_major(const FftTables& tb, const float* yf, float* y, int
 void launch_stream_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, hipStream_t s);
 void launch_stream_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, const float* prev_in, float* prev_out, float* out,
                              int C, hipStream_t s);
+// The same for L consecutive hops per row in one launch each (bsrnn_stream_process): chunk / out [C][L*1024], X / Y frame-major
+// [C*L][ld] (row c*L + l).  buf_out = the last 2048 samples of buf_in ++ chunk, prev_out = the last synthesis frame.
+void launch_stream_block_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L, hipStream_t s);
+void launch_stream_block_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, const float* prev_in, float* prev_out, float* out,
+                                   int C, int L, hipStream_t s);
 
 // ------------------------------------------------------------------ validation metrics (metrics.hip)
 // Per-workgroup partial sums in double; the host adds them.  est [R][n_est]; speech, mix [R][n_in] (first n_est used).
