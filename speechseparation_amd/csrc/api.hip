@@ -4,7 +4,7 @@
 // There is no CPU compute path here: every entry point either enqueues HIP kernels or fails.
 #include "../../include/bsrnn_hip.h"
 #include "kernels.h"
-#include "split_host.h"
+#include "commit_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -53,8 +53,6 @@ struct Param {
     int64_t numel() const { return ndim == 2 ? d0 * d1 : d0; }
 };
 
-enum Slot { PRE0, PRE2, FC0, FC2, FC4, BACK0, BACK2, BACK4, POST0, POST2, BLK_FC0, BLK_FC1, BLK_FC2, BLK_FC3, NSLOT };
-
 enum Stage { ST_LAYOUT, ST_STFT, ST_BANDSPLIT, ST_BAND_LSTM, ST_BAND_FC, ST_TIME_LSTM, ST_TIME_FC, ST_MASK, ST_ISTFT, ST_STREAM_DSP, NSTAGE };
 const char* kStageNames[NSTAGE] = {"layout", "stft", "bandsplit_mlp", "band_lstm", "band_fc", "time_lstm", "time_fc",
                                    "mask_mlp", "istft", "stream_dsp"};
@@ -89,26 +87,25 @@ struct bsrnn_ctx {
     float* d_arena = nullptr;
     GemmJob* d_jobs = nullptr;
     int2* d_tiles = nullptr;
-    int job0[NSLOT], njobs[NSLOT], tile0[NSLOT], ntiles[NSLOT], tile_n[NSLOT];
+    SlotTables slots;               // jobs and tiles of every layer slot inside d_jobs / d_tiles (commit_host.h)
 
     // fused per-band MLP chains (mlp_chain.hip): device descriptor arrays, grouped by class (kernels.h, ChainLaunch)
     bool stage_error = false;       // run_stage() found no task table for its row count (cannot happen: ensure_tasks runs first); reported by the entry point
     bool fused = false;             // false: per-layer launches (BSRNN_MLP=layers, fp32 mode, or a band too wide for the LDS image)
     ChainDesc* d_chain[2] = {nullptr, nullptr};
-    std::vector<ChainDesc> h_chain[2];          // host copies (geometry and cost per band: the task tables are made from them)
-    std::vector<long> chain_cost[2];
+    std::vector<ChainDesc> h_chain[2];          // host copies (geometry per band: the task tables are made from them)
     struct TaskTable { int2* d[2]; int n[2]; };
     std::map<int, TaskTable> chain_tasks;       // per row count M: device task tables of the two chains
     size_t task_cap = 64, ovl_cap = 16;         // bounds of the two table caches (chain_tasks, ovl_tables); bsrnn_stream_reserve raises them to
                                                 // hold one table per block length it was asked for
 
-    const float *bandW[2][2], *bandB[2][2], *timeW[2], *timeB[2];
-    const void *bandW16[2][2], *timeW16[2];
-    const void* timeFc16[2] = {nullptr, nullptr};   // the time blocks' fc as fp16x2 B fragments (fused into the time-axis launch, lstm.hip)
+    // recurrent weights per dual-path block, segments of the arena (commit_host.h, BlockSegs; the *16 ones hold fp16x2 pieces in MFMA operand order)
+    const float *bandW[2][2], *bandB[2][2], *bandW16[2][2], *timeW[2], *timeB[2], *timeW16[2];
+    const float* timeFc16[2] = {nullptr, nullptr};  // the time blocks' fc as fp16x2 B fragments (fused into the time-axis launch, lstm.hip)
     const float* timeFcB[2] = {nullptr, nullptr};
-    const void* bandFc16[2] = {nullptr, nullptr};   // the band blocks' fc (128 -> 64) likewise, for the few-sequence kernel (band_block_small_kernel)
+    const float* bandFc16[2] = {nullptr, nullptr};  // the band blocks' fc (128 -> 64) likewise, for the few-sequence kernel (band_block_small_kernel)
     const float* bandFcB[2] = {nullptr, nullptr};
-    int *h_range = nullptr, *d_range = nullptr;    // range guard of the fp16x2 kernels: host-mapped word the kernels set                     // fp16x2 pieces in MFMA operand order (lstm.hip)
+    int *h_range = nullptr, *d_range = nullptr;    // range guard of the fp16x2 kernels: host-mapped word the kernels set
     float* d_tables = nullptr;
     float* d_train_ws = nullptr;       // grow-only scratch of the training entry points (stream-ordered reuse: one call at a time)
     size_t train_ws_floats = 0;
@@ -222,8 +219,6 @@ void add_linear(bsrnn_ctx* c, const std::string& prefix, int n_out, int n_in)
     add_param(c, prefix + ".weight", n_out, n_in, 2);
     add_param(c, prefix + ".bias", n_out, 0, 1);
 }
-int imax(int a, int b) { return a > b ? a : b; }
-int round8(int a) { return (a + 7) & ~7; }
 
 // parameter inventory in the reference's state_dict order (bsrnn.py:329-376)
 void build_inventory(bsrnn_ctx* c)
@@ -275,55 +270,6 @@ void build_inventory(bsrnn_ctx* c)
             snprintf(b, sizeof b, "bandFCs_back_post.%d.2", i); add_linear(c, b, a, a);
         } else { snprintf(b, sizeof b, "bandFCs_back_post.%d.0.trainable_constant", i); add_param(c, b, 0, 0, 1); }
     }
-}
-
-const Param& P_(const bsrnn_ctx* c, const std::string& key) { return c->params[c->index.at(key)]; }
-
-// host-side arena builder (16-byte aligned segments)
-struct Arena {
-    std::vector<float> h;
-    size_t put(const float* p, size_t n)
-    {
-        size_t o = (h.size() + 3) & ~size_t(3);
-        h.resize(o + n);
-        if (n) memcpy(&h[o], p, n * sizeof(float));
-        return o;
-    }
-    size_t put(const std::vector<float>& v) { return put(v.data(), v.size()); }
-};
-
-// [W_ih (fc_in folded for layer 0) | W_hh] and the summed bias of one LSTM layer/direction
-void lstm_cat(const bsrnn_ctx* c, int j, int layer, const char* sfx, int n_in, std::vector<double>& wcat, std::vector<double>& bsum)
-{
-    char b[128];
-    const int H = HID, KT = n_in + H;
-    snprintf(b, sizeof b, "lstms.%d.m.rnn.weight_ih_l%d%s", j, layer, sfx); const Param& wih = P_(c, b);
-    snprintf(b, sizeof b, "lstms.%d.m.rnn.weight_hh_l%d%s", j, layer, sfx); const Param& whh = P_(c, b);
-    snprintf(b, sizeof b, "lstms.%d.m.rnn.bias_ih_l%d%s", j, layer, sfx); const Param& bih = P_(c, b);
-    snprintf(b, sizeof b, "lstms.%d.m.rnn.bias_hh_l%d%s", j, layer, sfx); const Param& bhh = P_(c, b);
-    wcat.assign((size_t)4 * H * KT, 0.0);
-    bsum.assign(4 * H, 0.0);
-    for (int r = 0; r < 4 * H; ++r) bsum[r] = (double)bih.data[r] + (double)bhh.data[r];
-    if (layer == 0) {
-        // fc_in folded: W' = W_ih W_in, b' += W_ih b_in   (bsrnn.py:82-83: rnn(fc_in(x)), no activation between)
-        snprintf(b, sizeof b, "lstms.%d.m.fc_in.weight", j); const Param& win = P_(c, b);
-        snprintf(b, sizeof b, "lstms.%d.m.fc_in.bias", j); const Param& bin = P_(c, b);
-        for (int r = 0; r < 4 * H; ++r) {
-            for (int k = 0; k < H; ++k) {
-                double s = 0;
-                for (int u = 0; u < H; ++u) s += (double)wih.data[(size_t)r * H + u] * (double)win.data[(size_t)u * H + k];
-                wcat[(size_t)r * KT + k] = s;
-            }
-            double sb = 0;
-            for (int u = 0; u < H; ++u) sb += (double)wih.data[(size_t)r * H + u] * (double)bin.data[u];
-            bsum[r] += sb;
-        }
-    } else {
-        for (int r = 0; r < 4 * H; ++r)
-            for (int k = 0; k < n_in; ++k) wcat[(size_t)r * KT + k] = wih.data[(size_t)r * n_in + k];
-    }
-    for (int r = 0; r < 4 * H; ++r)
-        for (int k = 0; k < H; ++k) wcat[(size_t)r * KT + n_in + k] = whh.data[(size_t)r * H + k];
 }
 
 int ensure_ws(bsrnn_ctx* c, size_t rows)
@@ -397,6 +343,12 @@ void build_chain_tasks(const bsrnn_ctx* c, int ch, int M, std::vector<int2>& out
 // Task tables for the row counts of ONE call (several when the call runs as concurrent row blocks).  The cache is bounded; when it
 // is full it is dropped once, before any of this call's tables is made, so a call never evicts a table it is about to use
 // (captured streaming graphs notice through ctx->gen and re-capture).
+void free_chain_tasks(bsrnn_ctx* c)
+{
+    for (auto& kv : c->chain_tasks)
+        for (int ch = 0; ch < 2; ++ch) (void)hipFree(kv.second.d[ch]);
+    c->chain_tasks.clear();
+}
 int ensure_tasks(bsrnn_ctx* c, const int* Ms, int n)
 {
     if (!c->fused) return 0;
@@ -405,9 +357,7 @@ int ensure_tasks(bsrnn_ctx* c, const int* Ms, int n)
     if (!missing) return 0;
     if (c->chain_tasks.size() + missing > c->task_cap) {
         HIP_TRY(hipDeviceSynchronize());
-        for (auto& kv : c->chain_tasks)
-            for (int ch = 0; ch < 2; ++ch) (void)hipFree(kv.second.d[ch]);
-        c->chain_tasks.clear();
+        free_chain_tasks(c);
         ++c->gen;
     }
     for (int i = 0; i < n; ++i) {
@@ -438,10 +388,10 @@ void gemm_slot(bsrnn_ctx* c, bool gemv, int slot, const float* X, int ldx, float
     GemmLaunch g;
     memset(&g, 0, sizeof g);
     g.range_flag = c->d_range;
-    g.jobs = c->d_jobs + c->job0[slot];
-    g.tiles = c->d_tiles + c->tile0[slot];
-    g.n_tiles = c->ntiles[slot];
-    g.tile_n = c->tile_n[slot];
+    g.jobs = c->d_jobs + c->slots.job0[slot];
+    g.tiles = c->d_tiles + c->slots.tile0[slot];
+    g.n_tiles = c->slots.ntiles[slot];
+    g.tile_n = c->slots.tile_n[slot];
     g.X = X; g.ldx = ldx; g.Y = Y; g.ldy = ldy; g.R = R; g.ldr = ldr; g.Mul = Mul; g.ldm = ldm;
     g.tap = tap; g.ldt = c->LDP; g.M = M; g.epilogue = epi;
     // a call of a few frame rows: its per-band layers (M = C rows) run as exact-fp32 GEMV launches instead of 128-row MFMA
@@ -960,15 +910,10 @@ int bsrnn_create(int device, const int32_t* widths, int32_t n_bands, bsrnn_ctx**
     c->device = device;
     c->K = n_bands;
     c->widths.assign(widths, widths + n_bands);
-    int pos = 0, ao = 0, po = 0;
-    for (int i = 0; i < n_bands; ++i) {
-        c->off.push_back(pos); pos += widths[i];
-        // 32-column granularity: the same per-band offsets (x 2, in 16-bit elements) address the slab-format activations,
-        // whose bands are padded to whole 32-deep slabs
-        c->aoff.push_back(ao); ao += (imax(2 * widths[i], 2 * HID) + 31) & ~31;
-        c->poff.push_back(po); po += round8(2 * widths[i]);
-    }
-    c->LDA = ao; c->LDP = imax(po, 8);
+    int pos = 0;
+    for (int i = 0; i < n_bands; ++i) { c->off.push_back(pos); pos += widths[i]; }
+    const BandColumns bc = band_columns(c->widths);
+    c->aoff = bc.aoff; c->poff = bc.poff; c->LDA = bc.LDA; c->LDP = bc.LDP;
     build_inventory(c);
     memset(c->acc_ms, 0, sizeof c->acc_ms);
     memset(c->acc_n, 0, sizeof c->acc_n);
@@ -1047,8 +992,7 @@ static void destroy_now(bsrnn_ctx* c)
     if (c->d_tiles) (void)hipFree(c->d_tiles);
     for (int ch = 0; ch < 2; ++ch)
         if (c->d_chain[ch]) (void)hipFree(c->d_chain[ch]);
-    for (auto& kv : c->chain_tasks)
-        for (int ch = 0; ch < 2; ++ch) (void)hipFree(kv.second.d[ch]);
+    free_chain_tasks(c);
     if (c->d_tables) (void)hipFree(c->d_tables);
     if (c->d_train_ws) (void)hipFree(c->d_train_ws);
     for (float* p : c->train_ws_retired) (void)hipFree(p);
@@ -1079,9 +1023,7 @@ int bsrnn_chain_geometry(const bsrnn_ctx* c, int32_t chain, int32_t band, int32_
     if (!c->fused || c->widths[band] == 0) return 0;
     for (const ChainDesc& d : c->h_chain[chain]) {
         if (d.constant || d.z_off != band * HID) continue;
-        out[0] = chain_rows(d); out[1] = d.RT >= 3 ? 16 : 32; out[2] = d.RT; out[3] = d.NW;
-        for (int l = 0; l < CHAIN_LAYERS; ++l) out[4] |= d.L[l].rag ? 1 << l : 0;
-        out[5] = d.zpad;
+        chain_geometry_answer(d, out);
         return 0;
     }
     return fail(BSRNN_ESTATE, "bsrnn_chain_geometry: band %d has no descriptor in chain %d", band, chain);
@@ -1161,403 +1103,53 @@ int bsrnn_commit_params(bsrnn_ctx* c)
     HIP_TRY(hipDeviceSynchronize());
     ++c->gen;                             // the arena is rebuilt: captured streaming graphs hold pointers into the old one
 
-    Arena ar;
-    std::vector<GemmJob> jobs;
-    std::vector<size_t> jw, jb, jwp;     // arena offsets, patched to pointers after upload
-    // fp16x2 / fp16 modes: the same matrix as two fp16 pieces, slab-interleaved, rows padded to a multiple of 32
-    // (gemm_h2_kernel), packed into arena floats
-    const int gmode = gemm_mode();
-    auto put_planes = [&](const std::vector<float>& wp, int N, int Kp) -> size_t {
-        if (gmode == GEMM_F32 || wp.empty()) return 0;
-        std::vector<uint16_t> pl;
-        const int K32 = (Kp + 31) & ~31, wrow = h2_row_stride(K32);
-        pl.assign((size_t)N * wrow + 1, 0);
-        pack_h2_slabs_host(wp.data(), N, Kp, Kp, K32, wrow, pl.data());
-        std::vector<float> packed(pl.size() / 2 + 1);
-        memcpy(packed.data(), pl.data(), pl.size() * sizeof(uint16_t));
-        return ar.put(packed);
-    };
-    std::vector<int2> tiles;
-    const int H = HID, K = c->K;
-    char b[128];
+    // BSRNN_MLP and the two class knobs are read at every commit, the ragged split and the GEMM mode once per process
+    static const bool rag_on = [] { const char* e = getenv("BSRNN_CHAIN_RAG"); return !(e && !strcmp(e, "0")); }();
+    const char* mlp = getenv("BSRNN_MLP");
+    const CommitKnobs knobs = {gemm_mode(), mlp && !strcmp(mlp, "layers"), getenv("BSRNN_CHAIN_NO48") != nullptr, getenv("BSRNN_CHAIN_NO80") != nullptr, rag_on};
+    const WeightImage im = build_weight_image([c](const std::string& key) -> const std::vector<float>& { return c->params[c->index.at(key)].data; },
+                                              c->widths, c->aoff, c->poff, knobs);
+    c->slots = im.slots;
 
-    auto add_job = [&](const char* prefix, int N, int Kd, int x_off, int y_off, int r_off, int m_off) {
-        GemmJob j;
-        memset(&j, 0, sizeof j);
-        j.N = N; j.K = Kd; j.x_off = x_off; j.y_off = y_off; j.r_off = r_off; j.m_off = m_off;
-        const Param& w = P_(c, std::string(prefix) + ".weight");
-        const Param& bi = P_(c, std::string(prefix) + ".bias");
-        // weight rows padded with zeros to a multiple of 8: every row is 16-byte aligned in fp32 and in the 16-bit
-        // planes, and the kernels' K loops run over whole 16-byte units (the matching input pad columns are zero,
-        // see ensure_ws and the GEMM epilogue)
-        const int Kp = round8(Kd);
-        j.K = Kp;
-        std::vector<float> wp((size_t)N * Kp, 0.f);
-        for (int r = 0; r < N; ++r) memcpy(&wp[(size_t)r * Kp], &w.data[(size_t)r * Kd], Kd * sizeof(float));
-        jw.push_back(ar.put(wp));
-        jb.push_back(ar.put(bi.data));
-        jwp.push_back(put_planes(wp, N, Kp));
-        j.wrow = h2_row_stride((Kp + 31) & ~31);
-        jobs.push_back(j);
-    };
-    auto begin_slot = [&](int slot) { c->job0[slot] = (int)jobs.size(); c->tile0[slot] = (int)tiles.size(); };
-    // column tiles of a slot: 128 wide when any layer of the slot is wider than 64 columns (the
-    // 128 x 128 kernel does twice the MFMA work per barrier), else 64; heaviest K first so the
-    // tail of a launch is made of cheap tiles.  tiles[].x is relative to the slot's first job.
-    auto end_slot = [&](int slot) {
-        const int j0 = c->job0[slot];
-        c->njobs[slot] = (int)jobs.size() - j0;
-        int maxn = 0;
-        for (int ji = j0; ji < (int)jobs.size(); ++ji) maxn = imax(maxn, jobs[ji].N);
-        // 128-wide tiles pay off only when the launch has many more workgroups than CU slots (uniform
-        // large GEMMs: 114 vs 99 TFLOP/s); at M = C*T ~ 8k rows the 64-wide tiling balances the ragged
-        // per-band costs better (measured 2.75 vs 2.79 ms per step), so it is the default.
-        // The split-precision kernels do 2-3x less matrix-pipe work per tile and are bound by the CU's load
-        // path instead: there the 128-wide tile (2/3 of the bytes per flop) wins (tools/gemm_planes_bench.hip).
-        const int tn = (maxn > 64 && gmode != GEMM_F32) ? 128 : 64;
-        c->tile_n[slot] = tn;
-        std::vector<int> order;
-        for (int ji = j0; ji < (int)jobs.size(); ++ji) order.push_back(ji);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return jobs[a].K > jobs[b].K; });
-        for (int ji : order)
-            for (int t = 0; t < (jobs[ji].N + tn - 1) / tn; ++t) tiles.push_back(make_int2(ji - j0, t));
-        c->ntiles[slot] = (int)tiles.size() - c->tile0[slot];
-    };
-
-    // per-band MLP chains; tiles[].x is relative to the slot's first job
-    struct Def { int slot; const char* fmt; };
-    for (int slot = PRE0; slot <= POST2; ++slot) {
-        begin_slot(slot);
-        for (int i = 0; i < K; ++i) {
-            const int a = 2 * c->widths[i];
-            const int xin = c->poff[i];            // column of the band in the band-padded spectrum layout (16-byte aligned)
-            const int m = imax(a, H), pz = imax(a, 2 * H);
-            if (a == 0) {
-                if (slot == FC4) {                 // TrainableConstantModule -> Z[:, :, i, :] = constant
-                    GemmJob j;
-                    memset(&j, 0, sizeof j);
-                    j.N = H; j.K = 0; j.y_off = i * H;
-                    snprintf(b, sizeof b, "bandFCs.%d.0.trainable_constant", i);
-                    const Param& cst = P_(c, b);
-                    jw.push_back(ar.put(cst.data)); jb.push_back(ar.put(cst.data)); jwp.push_back(0);
-                    jobs.push_back(j);
-                }
-                continue;
-            }
-            switch (slot) {
-            case PRE0:  snprintf(b, sizeof b, "bandFCs_pre.%d.0", i); add_job(b, a, a, xin, c->aoff[i], 0, 0); break;
-            case PRE2:  snprintf(b, sizeof b, "bandFCs_pre.%d.2", i); add_job(b, a, a, c->aoff[i], c->poff[i], 0, 0); break;
-            case FC0:   snprintf(b, sizeof b, "bandFCs.%d.0", i); add_job(b, m, a, c->poff[i], c->aoff[i], 0, 0); break;
-            case FC2:   snprintf(b, sizeof b, "bandFCs.%d.2", i); add_job(b, H, m, c->aoff[i], c->aoff[i], 0, 0); break;
-            case FC4:   snprintf(b, sizeof b, "bandFCs.%d.4", i); add_job(b, H, H, c->aoff[i], i * H, 0, 0); break;
-            case BACK0: snprintf(b, sizeof b, "bandFCs_back.%d.0", i); add_job(b, 2 * H, H, i * H, c->aoff[i], 0, 0); break;
-            case BACK2: snprintf(b, sizeof b, "bandFCs_back.%d.2", i); add_job(b, pz, 2 * H, c->aoff[i], c->aoff[i], 0, 0); break;
-            case BACK4: snprintf(b, sizeof b, "bandFCs_back.%d.4", i); add_job(b, a, pz, c->aoff[i], c->aoff[i], 0, 0); break;
-            case POST0: snprintf(b, sizeof b, "bandFCs_back_post.%d.0", i); add_job(b, a, a, c->aoff[i], c->aoff[i], 0, 0); break;
-            case POST2: snprintf(b, sizeof b, "bandFCs_back_post.%d.2", i); add_job(b, a, a, c->aoff[i], xin, c->poff[i], xin); break;
-            }
-        }
-        end_slot(slot);
-    }
-    // fc of the four NormRNNResidual blocks (bsrnn.py:84), one job each over M*K rows
-    for (int j = 0; j < 4; ++j) {
-        const int slot = BLK_FC0 + j;
-        begin_slot(slot);
-        snprintf(b, sizeof b, "lstms.%d.m.fc", j);
-        add_job(b, H, (j % 2 == 0) ? 2 * H : H, 0, 0, 0, 0);
-        end_slot(slot);
-    }
-
-    // fused chains (mlp_chain.hip): per band and chain the five layers' fragment streams, the concatenated biases and a
-    // descriptor; classes by rows per workgroup (the activation image of a row tile must fit 96 KB / RT of LDS)
-    std::vector<ChainDesc> chains[2];
-    std::vector<size_t> ch_w[2], ch_b[2];           // arena offsets, patched to pointers after upload
-    bool fused = gmode != GEMM_F32;
-    if (const char* e = getenv("BSRNN_MLP")) fused = fused && strcmp(e, "layers") != 0;
-    for (int ch = 0; ch < 2 && fused; ++ch) {
-        struct Built { ChainDesc d; size_t w, b; long cost; };
-        std::vector<Built> built;
-        for (int i = 0; i < K && fused; ++i) {
-            const int a = 2 * c->widths[i], m = imax(a, H), pz = imax(a, 2 * H);
-            Built bu;
-            memset(&bu.d, 0, sizeof bu.d);
-            ChainDesc& d = bu.d;
-            d.p_off = c->poff[i]; d.a8 = round8(a); d.z_off = i * H;
-            if (a == 0) {
-                if (ch != CHAIN_SPLIT) continue;
-                snprintf(b, sizeof b, "bandFCs.%d.0.trainable_constant", i);
-                d.constant = 1; d.NW = 1; d.RT = 1; d.nbias = H;     // (a 256-row class member, like the GR = 8 geometry)
-                bu.w = 0; bu.b = ar.put(P_(c, b).data); bu.cost = -1;
-                built.push_back(bu);
-                continue;
-            }
-            struct LD { const char* fmt; int N, Kd, leaky; };
-            const LD split_l[5] = {{"bandFCs_pre.%d.0", a, a, 1}, {"bandFCs_pre.%d.2", a, a, 1}, {"bandFCs.%d.0", m, a, 1},
-                                   {"bandFCs.%d.2", H, m, 1}, {"bandFCs.%d.4", H, H, 0}};
-            const LD mask_l[5] = {{"bandFCs_back.%d.0", 2 * H, H, 1}, {"bandFCs_back.%d.2", pz, 2 * H, 1}, {"bandFCs_back.%d.4", a, pz, 1},
-                                  {"bandFCs_back_post.%d.0", a, a, 1}, {"bandFCs_back_post.%d.2", a, a, 0}};
-            const LD* ld = ch == CHAIN_SPLIT ? split_l : mask_l;
-            int units = 0, maxntl = 0, nbias = 0;
-            long cost = 0;
-            for (int l = 0; l < CHAIN_LAYERS; ++l) {
-                d.L[l].K16 = (ld[l].Kd + 15) / 16; d.L[l].NTL = (ld[l].N + 31) / 32; d.L[l].leaky = ld[l].leaky;
-                d.L[l].bias_off = nbias; nbias += 32 * d.L[l].NTL;
-                units = imax(units, 2 * d.L[l].K16);
-                if (l + 1 < CHAIN_LAYERS) units = imax(units, 4 * d.L[l].NTL);
-                maxntl = imax(maxntl, d.L[l].NTL);
-                cost += (long)d.L[l].K16 * d.L[l].NTL;
-            }
-            const int img = 2 * units * 512;                                  // bytes of one row tile's image (both pieces)
-            // geometry (mlp_chain.hip): RT row tiles per wave group (each weight fragment is used for all of them), GR groups
-            int RT = 0, GR = 1;
-            if (8 * img <= CHAIN_LDS_EX && maxntl <= 4) { RT = 1; GR = 8; }          // narrowest: every wave a chain of its own
-            else if (4 * img <= CHAIN_LDS_EX && maxntl <= 6) { RT = 1; GR = 4; }     // narrow: four groups of two waves
-            else if (4 * img <= CHAIN_LDS_EX && maxntl <= 12) { RT = 2; GR = 2; }    // two groups of four waves, two row tiles each
-            else if (2 * img <= CHAIN_LDS_EX) { RT = 2; GR = 1; }
-            else if (img <= CHAIN_LDS_EX) { RT = 1; GR = 1; }
-            // the widest bands (32 rows would be all the LDS holds): 48 rows on 16 x 16 x 32 MFMAs instead (chain_body48); there the
-            // layer fields count k-steps of 32 and feature tiles of 16
-            // ... and bands of the 64-row class whose image leaves room for FIVE row tiles of 16 and whose feature tiles of 16 are at most
-            // three per wave (the 384-wide band: 24 tiles = 3 x 8 where the 32 x 32 geometry has twelve tiles for eight waves): 80 rows
-            // per weight fragment instead of 64, every wave busy (BSRNN_CHAIN_NO80=1 keeps them on the 32 x 32 geometry)
-            bool g48 = false;
-            const bool no48 = getenv("BSRNN_CHAIN_NO48") != nullptr;
-            const bool try48 = RT == 1 && GR == 1 && !no48;
-            const bool try80 = RT == 2 && GR == 1 && !no48 && !getenv("BSRNN_CHAIN_NO80");
-            // ... and the other bands of the 64-row class (the 514-wide band: 33 feature tiles of 16, ragged) on FOUR row tiles of 16: the same 64
-            // rows, but two feature tiles' fragments per k-step and four k-steps in flight per wave (128 KB per CU instead of the 64 KB the
-            // two-row-tile 32 x 32 body has registers for, which held its K loops at 48 GB/s per CU against the 70 the fill path gives:
-            // profiles/r03_chain_trace.txt)
-            bool try64 = false;
-            if (try48 || try80) {
-                int rt16 = try48 ? 3 : 5, ctr = try48 ? 6 : 3;
-                int u48 = 0, maxft = 0, nb48 = 0;
-                bool whole = true;                                   // every layer's width a multiple of 16 (no ragged tile of 16)
-                bool gap = false;                                    // a layer's output (whole tiles of 16) ends short of the next layer's
-                                                                     // K loop (whole k-steps of 32): N % 32 != 0
-                for (int l = 0; l < CHAIN_LAYERS; ++l) {
-                    const int K32 = (ld[l].Kd + 31) / 32, FT = (ld[l].N + 15) / 16;
-                    u48 = imax(u48, 4 * K32);
-                    if (l + 1 < CHAIN_LAYERS) u48 = imax(u48, 2 * FT);
-                    maxft = imax(maxft, FT); nb48 += 16 * FT;
-                    whole = whole && ld[l].N % 16 == 0;
-                    gap = gap || (l + 1 < CHAIN_LAYERS && ld[l].N % 32 != 0);
-                }
-                if (try80 && !(whole && maxft % 8 == 0 && maxft <= 8 * ctr && 2 * u48 * (16 * rt16) * 16 <= CHAIN_LDS_EX)) {
-                    try64 = true; rt16 = 4; ctr = 5;
-                }
-                if (2 * u48 * (16 * rt16) * 16 <= CHAIN_LDS_EX && maxft <= 8 * ctr && nb48 * 4 <= CHAIN_LDS_BIAS && (try48 || try64 || (whole && maxft % 8 == 0))) {
-                    g48 = true; RT = rt16; GR = 1; units = u48; nbias = 0; cost = 0; d.zpad = rt16 == 4 || gap;   // (the 64-row body always zeroes)
-                    for (int l = 0; l < CHAIN_LAYERS; ++l) {
-                        d.L[l].K16 = (ld[l].Kd + 31) / 32; d.L[l].NTL = (ld[l].N + 15) / 16;
-                        d.L[l].bias_off = nbias; nbias += 16 * d.L[l].NTL;
-                        cost += (long)d.L[l].K16 * d.L[l].NTL;          // (half the MACs of a 32 x 32 x 16 unit each: same scale per row)
-                    }
-                }
-            }
-            const int ct_max = GR == 8 ? 4 : CHAIN_CT;                                // feature tiles per wave the geometry's body holds
-            if (!g48 && (RT < 1 || (8 / GR) * ct_max < maxntl || nbias * 4 > CHAIN_LDS_BIAS)) { fused = false; break; }   // a band too wide for the fused kernel: per-layer flow
-            d.RT = RT; d.NW = 8 / GR; d.plane_units = units; d.nbias = nbias;
-            d.in_off = ch == CHAIN_SPLIT ? c->poff[i] : i * H;
-            d.K0 = ch == CHAIN_SPLIT ? round8(a) : H;
-            // a last feature tile with at most 4 real features (514 columns = 16 tiles + 2) is split over the k-steps of all eight
-            // waves instead of costing one wave a whole tile (mlp_chain.hip, split_host.h): the geometry that implements it is
-            // RT 2 / GR 1, and the partial sums need 8 KB of LDS behind the two activation images
-            static const bool rag_on = [] { const char* e = getenv("BSRNN_CHAIN_RAG"); return !(e && !strcmp(e, "0")); }();
-            if (rag_on && !g48 && RT == 2 && GR == 1 && 2 * img + CHAIN_RAG_LDS <= CHAIN_LDS_EX)
-                for (int l = 0; l < CHAIN_LAYERS; ++l) {
-                    const int tail = ld[l].N % 32;
-                    if (tail >= 1 && tail <= 4 && d.L[l].NTL >= 2) {
-                        d.L[l].rag = 1;
-                        cost -= (long)d.L[l].K16 - d.L[l].K16 / 8;
-                    }
-                }
-            std::vector<uint16_t> stream;
-            std::vector<float> biases(nbias, 0.f);
-            for (int l = 0; l < CHAIN_LAYERS; ++l) {
-                snprintf(b, sizeof b, ld[l].fmt, i);
-                const Param& w = P_(c, std::string(b) + ".weight");
-                const Param& bi = P_(c, std::string(b) + ".bias");
-                d.L[l].w_off = (unsigned)(stream.size() * sizeof(uint16_t));
-                const int npl = (gmode == GEMM_FP16 || gmode == GEMM_BF16) ? 1 : 2;
-                if (g48) pack_chain_layer16_host(w.data.data(), ld[l].N, ld[l].Kd, ld[l].Kd, 8, npl, stream, gmode == GEMM_BF16);
-                else pack_chain_layer_host(w.data.data(), ld[l].N, ld[l].Kd, ld[l].Kd, d.NW, npl, stream, d.L[l].rag, gmode == GEMM_BF16);
-                memcpy(&biases[d.L[l].bias_off], bi.data.data(), ld[l].N * sizeof(float));
-            }
-            stream.resize((stream.size() + 7) & ~size_t(7), 0);
-            bu.w = ar.put(reinterpret_cast<const float*>(stream.data()), stream.size() / 2);
-            bu.b = ar.put(biases);
-            bu.cost = cost;
-            built.push_back(bu);
-        }
-        if (!fused) break;
-        // class = rows per workgroup (RT = 1, 2, 4, constant bands), heaviest band first inside a class
-        std::stable_sort(built.begin(), built.end(), [](const Built& x, const Built& y) {
-            auto cls = [](const ChainDesc& d) { const int rows = chain_rows(d); return d.constant ? 4 : (rows <= 48 ? 0 : (rows <= 80 ? 1 : (rows == 128 ? 2 : 3))); };
-            const int cx = cls(x.d), cy = cls(y.d);
-            return cx != cy ? cx < cy : x.cost > y.cost;
-        });
-        c->chain_cost[ch].clear();
-        for (const Built& bu : built) {
-            chains[ch].push_back(bu.d); ch_w[ch].push_back(bu.w); ch_b[ch].push_back(bu.b);
-            c->chain_cost[ch].push_back(bu.cost);
-        }
-    }
-
-    // LSTM weights, folded and packed in the kernels' register order (lstm.hip)
-    size_t o_bandW[2][2], o_bandW16[2][2], o_bandB[2][2], o_timeW[2], o_timeW16[2], o_timeB[2], o_timeFc16[2], o_timeFcB[2], o_bandFc16[2], o_bandFcB[2];
-    std::vector<double> wcat, bsum;
-    for (int blk = 0; blk < 2; ++blk) {
-        const int jb_ = 2 * blk;                               // lstms.0 / lstms.2: bidirectional over bands
-        for (int layer = 0; layer < 2; ++layer) {
-            const int IN = layer == 0 ? H : 2 * H, KT = IN + H, NS = KT / 4;
-            std::vector<float> pk((size_t)2 * 4 * NS * 4 * 64), pb(2 * 256);
-            const int NB = KT / 32;
-            std::vector<uint16_t> pk16((size_t)2 * 4 * NB * 4 * 2 * 64 * 8);
-            for (int d = 0; d < 2; ++d) {
-                lstm_cat(c, jb_, layer, d ? "_reverse" : "", IN, wcat, bsum);
-                for (int wv = 0; wv < 4; ++wv)
-                    for (int bk = 0; bk < NB; ++bk)
-                        for (int g = 0; g < 4; ++g)
-                            for (int ln = 0; ln < 64; ++ln)
-                                for (int e = 0; e < 8; ++e) {
-                                    const int row = g * 64 + 16 * wv + (ln & 15);
-                                    const int k = 32 * bk + 8 * (ln >> 4) + e;
-                                    const float v = (float)wcat[(size_t)row * KT + k];
-                                    uint16_t pc[2];
-                                    split_planes_host(&v, 1, 2, pc);
-                                    const size_t base = ((((size_t)d * 4 + wv) * NB + bk) * 4 + g) * 2;
-                                    pk16[((base + 0) * 64 + ln) * 8 + e] = pc[0];
-                                    pk16[((base + 1) * 64 + ln) * 8 + e] = pc[1];
-                                }
-                for (int wv = 0; wv < 4; ++wv)
-                    for (int s = 0; s < NS; ++s)
-                        for (int g = 0; g < 4; ++g)
-                            for (int ln = 0; ln < 64; ++ln) {
-                                const int row = g * 64 + 16 * wv + (ln & 15);
-                                const int k = 16 * (s / 4) + 4 * (ln >> 4) + (s % 4);
-                                pk[((((size_t)d * 4 + wv) * NS + s) * 4 + g) * 64 + ln] = (float)wcat[(size_t)row * KT + k];
-                            }
-                for (int r = 0; r < 256; ++r) pb[d * 256 + r] = (float)bsum[r];
-            }
-            o_bandW[blk][layer] = ar.put(pk);
-            o_bandB[blk][layer] = ar.put(pb);
-            o_bandW16[blk][layer] = ar.put(reinterpret_cast<const float*>(pk16.data()), pk16.size() / 2);
-        }
-        {   // the block's fc (128 -> 64, bsrnn.py:84) as fp16x2 B fragments for band_block_small_kernel: [4 tile][4 blk][2 piece][64 lane][8],
-            // lane (n = l & 15, kb = l >> 4) holds W_fc[16 tile + n][32 blk + 8 kb .. + 7]
-            snprintf(b, sizeof b, "lstms.%d.m.fc.weight", jb_); const Param& wfc = P_(c, b);
-            snprintf(b, sizeof b, "lstms.%d.m.fc.bias", jb_); const Param& bfc = P_(c, b);
-            std::vector<uint16_t> f16((size_t)4 * 4 * 2 * 64 * 8);
-            for (int tl = 0; tl < 4; ++tl)
-                for (int bk = 0; bk < 4; ++bk)
-                    for (int ln = 0; ln < 64; ++ln)
-                        for (int e = 0; e < 8; ++e) {
-                            const float v = wfc.data[(size_t)(16 * tl + (ln & 15)) * 2 * H + 32 * bk + 8 * (ln >> 4) + e];
-                            uint16_t pc[2];
-                            split_planes_host(&v, 1, 2, pc);
-                            const size_t base = ((size_t)tl * 4 + bk) * 2;
-                            f16[((base + 0) * 64 + ln) * 8 + e] = pc[0];
-                            f16[((base + 1) * 64 + ln) * 8 + e] = pc[1];
-                        }
-            o_bandFc16[blk] = ar.put(reinterpret_cast<const float*>(f16.data()), f16.size() / 2);
-            o_bandFcB[blk] = ar.put(bfc.data);
-        }
-        const int jt = 2 * blk + 1;                            // lstms.1 / lstms.3: causal over time
-        std::vector<float> pk((size_t)2 * 4 * 128 * 64), pb(2 * 256);
-        std::vector<uint16_t> pk16((size_t)2 * 4 * 4 * 4 * 2 * 64 * 8);
-        for (int layer = 0; layer < 2; ++layer) {
-            lstm_cat(c, jt, layer, "", H, wcat, bsum);
-            for (int wv = 0; wv < 4; ++wv)
-                for (int bk = 0; bk < 4; ++bk)
-                    for (int g = 0; g < 4; ++g)
-                        for (int ln = 0; ln < 64; ++ln)
-                            for (int e = 0; e < 8; ++e) {
-                                const int row = g * 64 + 16 * wv + (ln & 15);
-                                const int k = 32 * bk + 8 * (ln >> 4) + e;
-                                const float v = (float)wcat[(size_t)row * 128 + k];
-                                uint16_t pc[2];
-                                split_planes_host(&v, 1, 2, pc);
-                                const size_t base = ((((size_t)layer * 4 + wv) * 4 + bk) * 4 + g) * 2;
-                                pk16[((base + 0) * 64 + ln) * 8 + e] = pc[0];
-                                pk16[((base + 1) * 64 + ln) * 8 + e] = pc[1];
-                            }
-            for (int wv = 0; wv < 4; ++wv)
-                for (int k = 0; k < 128; ++k)
-                    for (int ln = 0; ln < 64; ++ln) {
-                        const int row = (ln & 3) * 64 + 16 * wv + (ln >> 2);
-                        pk[(((size_t)layer * 4 + wv) * 128 + k) * 64 + ln] = (float)wcat[(size_t)row * 128 + k];
-                    }
-            for (int r = 0; r < 256; ++r) pb[layer * 256 + r] = (float)bsum[r];
-        }
-        o_timeW[blk] = ar.put(pk);
-        o_timeW16[blk] = ar.put(reinterpret_cast<const float*>(pk16.data()), pk16.size() / 2);
-        o_timeB[blk] = ar.put(pb);
-        {   // the block's fc (64 -> 64, bsrnn.py:84) in the f16 MFMA's B-operand order: [4 wave][2 blk][2 piece][64 lane][8],
-            // lane (n = l & 15, kb = l >> 4) holds W_fc[16 wave + n][32 blk + 8 kb .. + 7]
-            snprintf(b, sizeof b, "lstms.%d.m.fc.weight", jt); const Param& wfc = P_(c, b);
-            snprintf(b, sizeof b, "lstms.%d.m.fc.bias", jt); const Param& bfc = P_(c, b);
-            std::vector<uint16_t> f16((size_t)4 * 2 * 2 * 64 * 8);
-            for (int wv = 0; wv < 4; ++wv)
-                for (int bk = 0; bk < 2; ++bk)
-                    for (int ln = 0; ln < 64; ++ln)
-                        for (int e = 0; e < 8; ++e) {
-                            const float v = wfc.data[(size_t)(16 * wv + (ln & 15)) * H + 32 * bk + 8 * (ln >> 4) + e];
-                            uint16_t pc[2];
-                            split_planes_host(&v, 1, 2, pc);
-                            const size_t base = ((size_t)wv * 2 + bk) * 2;
-                            f16[((base + 0) * 64 + ln) * 8 + e] = pc[0];
-                            f16[((base + 1) * 64 + ln) * 8 + e] = pc[1];
-                        }
-            o_timeFc16[blk] = ar.put(reinterpret_cast<const float*>(f16.data()), f16.size() / 2);
-            o_timeFcB[blk] = ar.put(bfc.data);
-        }
-    }
-
-    // upload
+    // upload: the arena first, then the descriptors with the arena's device address added to their offsets
     if (c->d_arena) { HIP_TRY(hipFree(c->d_arena)); c->d_arena = nullptr; }
     if (c->d_jobs) { HIP_TRY(hipFree(c->d_jobs)); c->d_jobs = nullptr; }
     if (c->d_tiles) { HIP_TRY(hipFree(c->d_tiles)); c->d_tiles = nullptr; }
-    HIP_TRY(hipMalloc((void**)&c->d_arena, (ar.h.size() + 4) * sizeof(float)));
-    HIP_TRY(hipMemcpy(c->d_arena, ar.h.data(), ar.h.size() * sizeof(float), hipMemcpyHostToDevice));
-    for (size_t i = 0; i < jobs.size(); ++i) {
-        jobs[i].W = c->d_arena + jw[i]; jobs[i].bias = c->d_arena + jb[i];
-        jobs[i].Wp = c->d_arena + jwp[i];
+    HIP_TRY(hipMalloc((void**)&c->d_arena, (im.arena.size() + 4) * sizeof(float)));
+    HIP_TRY(hipMemcpy(c->d_arena, im.arena.data(), im.arena.size() * sizeof(float), hipMemcpyHostToDevice));
+    std::vector<GemmJob> jobs;
+    for (const JobRec& r : im.jobs) {
+        jobs.push_back(r.j);
+        jobs.back().W = c->d_arena + r.w; jobs.back().bias = c->d_arena + r.b; jobs.back().Wp = c->d_arena + r.wp;
     }
     HIP_TRY(hipMalloc((void**)&c->d_jobs, jobs.size() * sizeof(GemmJob)));
     HIP_TRY(hipMemcpy(c->d_jobs, jobs.data(), jobs.size() * sizeof(GemmJob), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void**)&c->d_tiles, tiles.size() * sizeof(int2)));
-    HIP_TRY(hipMemcpy(c->d_tiles, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice));
+    static_assert(sizeof(GemmTile) == sizeof(int2) && alignof(GemmTile) <= alignof(int2), "the kernels read a GemmTile as an int2");
+    HIP_TRY(hipMalloc((void**)&c->d_tiles, im.tiles.size() * sizeof(int2)));
+    HIP_TRY(hipMemcpy(c->d_tiles, im.tiles.data(), im.tiles.size() * sizeof(int2), hipMemcpyHostToDevice));
     c->fused = false;
-    for (auto& kv : c->chain_tasks)
-        for (int ch = 0; ch < 2; ++ch) (void)hipFree(kv.second.d[ch]);
-    c->chain_tasks.clear();
+    free_chain_tasks(c);
     for (int ch = 0; ch < 2; ++ch) {
         c->h_chain[ch].clear();
         if (c->d_chain[ch]) { HIP_TRY(hipFree(c->d_chain[ch])); c->d_chain[ch] = nullptr; }
-        if (!fused) continue;
-        for (size_t i = 0; i < chains[ch].size(); ++i) {
-            chains[ch][i].wstream = c->d_arena + ch_w[ch][i];
-            chains[ch][i].bias = c->d_arena + ch_b[ch][i];
+        if (!im.fused) continue;
+        std::vector<ChainDesc> descs;
+        for (const ChainRec& r : im.chains[ch]) {
+            descs.push_back(r.d);
+            descs.back().wstream = c->d_arena + r.w; descs.back().bias = c->d_arena + r.b;
         }
-        HIP_TRY(hipMalloc((void**)&c->d_chain[ch], chains[ch].size() * sizeof(ChainDesc)));
-        HIP_TRY(hipMemcpy(c->d_chain[ch], chains[ch].data(), chains[ch].size() * sizeof(ChainDesc), hipMemcpyHostToDevice));
-        c->h_chain[ch] = chains[ch];
+        HIP_TRY(hipMalloc((void**)&c->d_chain[ch], descs.size() * sizeof(ChainDesc)));
+        HIP_TRY(hipMemcpy(c->d_chain[ch], descs.data(), descs.size() * sizeof(ChainDesc), hipMemcpyHostToDevice));
+        c->h_chain[ch] = descs;
     }
-    c->fused = fused;
+    c->fused = im.fused;
     for (int blk = 0; blk < 2; ++blk) {
-        for (int layer = 0; layer < 2; ++layer) {
-            c->bandW[blk][layer] = c->d_arena + o_bandW[blk][layer];
-            c->bandB[blk][layer] = c->d_arena + o_bandB[blk][layer];
-            c->bandW16[blk][layer] = c->d_arena + o_bandW16[blk][layer];
-        }
-        c->timeW[blk] = c->d_arena + o_timeW[blk];
-        c->timeW16[blk] = c->d_arena + o_timeW16[blk];
-        c->timeB[blk] = c->d_arena + o_timeB[blk];
-        c->bandFc16[blk] = c->d_arena + o_bandFc16[blk];
-        c->bandFcB[blk] = c->d_arena + o_bandFcB[blk];
-        c->timeFc16[blk] = c->d_arena + o_timeFc16[blk];
-        c->timeFcB[blk] = c->d_arena + o_timeFcB[blk];
+        const BlockSegs& s = im.blk[blk];
+        const struct { const float** member; size_t off; } segs[] = {
+            {&c->bandW[blk][0], s.bandW[0]}, {&c->bandW[blk][1], s.bandW[1]}, {&c->bandB[blk][0], s.bandB[0]}, {&c->bandB[blk][1], s.bandB[1]},
+            {&c->bandW16[blk][0], s.bandW16[0]}, {&c->bandW16[blk][1], s.bandW16[1]}, {&c->bandFc16[blk], s.bandFc16}, {&c->bandFcB[blk], s.bandFcB},
+            {&c->timeW[blk], s.timeW}, {&c->timeB[blk], s.timeB}, {&c->timeW16[blk], s.timeW16}, {&c->timeFc16[blk], s.timeFc16}, {&c->timeFcB[blk], s.timeFcB}};
+        for (const auto& sg : segs) *sg.member = c->d_arena + sg.off;
     }
     c->committed = true;
     return 0;

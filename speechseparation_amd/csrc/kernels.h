@@ -3,29 +3,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "descriptors.h"   // GemmJob, ChainDesc and the constants the host packs against (HIP-free)
+
 namespace bsrnn {
 
-constexpr int HID = 64;       // band_features (bsrnn.py:60)
 constexpr int NFFT = 2048;    // infer.py:31
 constexpr int HOPS = 1024;
 constexpr int NBINS = 1025;
 constexpr int F2 = 2050;      // interleaved re/im columns
 
-// ------------------------------------------------------------------ grouped linear layers
-// One job = one nn.Linear of one band.  A launch runs every job of one "layer slot" of the
-// per-band MLP chains over all M = C*T frame rows.
-struct GemmJob {
-    const float* W;      // [N][K] row-major (torch Linear layout), device, K padded to a multiple of 8 floats
-    const void* Wp;      // the same matrix as two fp16 pieces, slab-interleaved [N][K32 / 32][2][32] (split_host.h)
-    const float* bias;   // [N]
-    int N, K;            // K may be 0: y = bias (TrainableConstantModule, bsrnn.py:12-24)
-    int x_off;           // column offset of the job's input inside an X row
-    int y_off;           // column offset of the output inside a Y row
-    int r_off;           // column offset inside the residual row (EPI_RES, EPI_MASK)
-    int m_off;           // column offset inside the multiplier / mask-tap row (EPI_MASK)
-    int wrow;            // 16-bit elements between consecutive weight rows of Wp
-};
-
+// ------------------------------------------------------------------ grouped linear layers (GemmJob: descriptors.h)
 enum GemmEpilogue {
     EPI_LINEAR = 0,      // y = acc + b
     EPI_LEAKY = 1,       // y = leaky_relu(acc + b, 0.01)
@@ -53,58 +40,17 @@ void launch_gemm(const GemmLaunch& g, hipStream_t stream);
 // streaming step: C rows).  api.hip uses it for every per-layer launch of a call with C * L <= GEMV_MAX_FRAME_ROWS.
 constexpr int GEMV_MAX_FRAME_ROWS = 4;
 void launch_gemv(const GemmLaunch& g, hipStream_t stream);
-// How the Linear layers are evaluated (environment BSRNN_GEMM = f32 | fp16x2 | fp16, read once per process).
-// fp16 = plain 16-bit operands, one MFMA term, fp32 accumulate (the reduced-precision configuration, not the default).
-// The fp32 weights are always resident beside the fp16 pieces: a call whose operands left the fp16x2 range is re-run on
-// the exact-fp32 kernels (set_force_f32, per host thread) by the synchronous entry points of api.hip.
-// bf16 = plain bf16 operands, one MFMA term, in the fused MLP chains (BASELINE config 2 as it is named; no range limit, 8 significant
-// bits); the few launches outside the chains (a band too wide for the LDS image, the block fc of the BSRNN_BAND_FC=gemm flow) then run fp16x2.
-enum GemmMode { GEMM_F32 = 0, GEMM_FP16 = 1, GEMM_FP16X2 = 2, GEMM_BF16 = 3 };
+// How the Linear layers are evaluated: GemmMode (descriptors.h), from the environment BSRNN_GEMM, read once per process.
 int gemm_mode();
 void set_force_f32(bool on);
 bool force_f32();
 constexpr int GEMM_BM = 128;
 
-// ------------------------------------------------------------------ fused per-band MLP chains (mlp_chain.hip)
-// One workgroup = one band x one block of frame rows, all five Linear layers of BandSplit (bsrnn.py:404-415) or of
-// MaskEstimation (bsrnn.py:420-443); intermediates stay in LDS as fp16x2 pieces.
-constexpr int CHAIN_LAYERS = 5;
-constexpr int CHAIN_CT = 3;                   // feature tiles (32 wide) per wave and layer, at most
-constexpr int CHAIN_LDS_EX = 144 * 1024;      // activation images of the workgroup's row tiles
-constexpr int CHAIN_LDS_BIAS = 13 * 1024;     // the chain's biases (both together: 157 of the CU's 160 KB)
-enum { CHAIN_SPLIT = 0, CHAIN_MASK = 1 };
-struct ChainLayer {
-    int K16;             // k-steps of 16 (input width rounded up)
-    int NTL;             // feature tiles of 32 (output width rounded up); weights and biases beyond N are zero
-    int bias_off;        // first bias of the layer inside the chain's bias block (floats)
-    int leaky;           // LeakyReLU(0.01) after the layer
-    unsigned w_off;      // byte offset of the layer's fragment streams inside ChainDesc::wstream
-    int rag;             // 1: the last of the NTL feature tiles (<= 4 real features) is split over the k-steps of all waves (split_host.h)
-};
-constexpr int CHAIN_RAG_LDS = 8 * 1024;       // LDS behind the activation images that the partial sums of such a tile need
-struct ChainDesc {
-    ChainLayer L[CHAIN_LAYERS];
-    const void* wstream; // per layer, per wave wn: for tile t = wn + NW c, for ks, for piece: 64 lanes x 8 fp16 (split_host.h)
-    const float* bias;   // the five bias vectors, each padded with zeros to NTL * 32 (constant band: the constant itself)
-    int nbias;
-    int NW, RT;          // groups of NW waves share the feature tiles of their RT row tiles (of 32 rows): mlp_chain.hip.
-                         // RT = 3: the 48-row geometry on 16 x 16 x 32 MFMAs (K16 then counts k-steps of 32, NTL tiles of 16)
-    int plane_units;     // 512-byte units of one piece of one row tile's activation image: max(2 K16, 4 NTL) over the layers
-    int in_off;          // first column of the band inside an input row (SPLIT: spectrum row, MASK: b * 64 of a Z row)
-    int K0;              // valid input columns, a multiple of 8 (beyond: zeros)
-    int p_off;           // first column of the band in the band-padded rows (P, spectrum, output)
-    int a8;              // band width in columns rounded up to 8: what is written to P / Y (pad columns exactly zero)
-    int z_off;           // first column of the band inside a Z row
-    int constant;        // zero-width band (TrainableConstantModule, bsrnn.py:12-24): Z[:, z_off .. +64) = bias[0 .. 64)
-    int zpad;            // 16 x 16 geometry: the image's k-units that no layer output covers but the next layer's K loop reads are
-                         // zeroed first (chain_body48 ZPAD): set when a layer feeding another has N % 32 != 0 (its output ends
-                         // after an odd number of feature tiles of 16, the next K loop runs whole k-steps of 32); always on the
-                         // 64-row body
-};
+// ------------------------------------------------------------------ fused per-band MLP chains (mlp_chain.hip; ChainDesc: descriptors.h)
 struct ChainLaunch {
     const ChainDesc* desc;   // device array
     const int2* tasks;       // device array [n_tasks]: (descriptor index, first frame row) of every workgroup, in dispatch order
-    int n_tasks;             //   (built per M by chain_tasks(): the fill-bound wide bands interleaved with the others)
+    int n_tasks;             //   (built per M by build_chain_tasks(), api.hip: descriptor after descriptor, all row blocks of a band together)
     int M;
     const float* Xin; int ldx;       // SPLIT: spectrum rows; MASK: Z rows
     float* P; int ldp;               // SPLIT: written (bandFCs_pre output = the mask's residual); MASK: read
@@ -118,8 +64,6 @@ struct ChainLaunch {
     // waits until the frames of its rows have left that launch (OvlConsumer below); null = the input is complete at launch
     const int* ovl_prog; int ovl_T, ovl_K, ovl_spin, ovl_base, ovl_wg_shift;
 };
-// rows per workgroup of a descriptor (32 RT GR; 256 for a constant band)
-__host__ __device__ inline int chain_rows(const ChainDesc& d) { return d.constant ? 256 : (d.RT >= 3 ? 16 * d.RT : 32 * d.RT * (8 / d.NW)); }   // RT >= 3: row tiles of 16 (16 x 16 x 32 geometry: 48 or 80 rows)
 void launch_mlp_chain(const ChainLaunch& g, int chain, hipStream_t stream);
 
 // ------------------------------------------------------------------ overlapped dual path (api.hip: run_overlapped)
@@ -195,7 +139,6 @@ void launch_band_pair(const float* z, float* hb0, float* hb1, const void* w0pk16
 // step's N = C frame rows.  w0pk16 / w1pk16 / bias0 / bias1 are launch_band_lstm's arguments of the two layers; fc16 the block's
 // fc (128 -> 64) as fp16x2 B fragments [4 tile][4 blk][2 piece][64 lane][8], fcb its bias.  zout = fc(h1) + b + zin.
 // fp16x2 only; 1 <= N <= 8 sequences of 1 <= L <= BS_MAXL steps (api.hip decides when a call takes it).
-constexpr int BS_MAXL = 16;                     // positions (bands) the LDS images hold; longer band tables take the general kernels
 void launch_band_block_small(const float* zin, float* zout, const void* w0pk16, const float* bias0, const void* w1pk16, const float* bias1,
                              const void* fc16, const float* fcb, int N, int L, int* range_flag, hipStream_t stream);
 // How the recurrent layers evaluate their gate products (environment BSRNN_LSTM = f32 | fp16x2, read once).

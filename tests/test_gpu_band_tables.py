@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 N_BINS = 1025
 EXTRA_WIDTHS = (449, 512, 513, 640, 767, 768, 769, 833, 1000, 1024, 1025)
 CLASS_EDGES = (64, 96, 144, 192, 288, 384)       # the width ranges of the chain geometries end here (include/bsrnn_hip.h)
-RAG_PAIRS = tuple(w for w in range(145, 259) if 1 <= (2 * w) % 32 <= 4)   # the ragged split under BSRNN_CHAIN_NO48 (api.hip)
+RAG_PAIRS = tuple(w for w in range(145, 259) if 1 <= (2 * w) % 32 <= 4)   # the ragged split under BSRNN_CHAIN_NO48 (csrc/commit_host.h)
 # the 48-row class (289 - 383 bins) at whole tiles of 16: 2 w % 32 == 16 leaves one tile of 16 between a layer's output and the next
 # layer's K loop (pad zeroing on), 2 w % 32 == 0 leaves none (off)
 WIDTHS_48 = tuple(range(296, 384, 8))
