@@ -278,6 +278,37 @@ int  bsrnn_istft(bsrnn_ctx* ctx, const float* y_dev, float* wave_out_dev, int32_
 int  bsrnn_istft_backward(bsrnn_ctx* ctx, const float* dwave_dev, float* dy_dev, int32_t R, int32_t T, void* stream);
 int  bsrnn_separate(bsrnn_ctx* ctx, const float* wave_dev, float* wave_out_dev, int32_t R, int64_t n, void* stream);
 
+/* ---- long-form separation: bsrnn_separate in segments, bounded memory ---------------------
+ * bsrnn_separate's result for a clip of any length from a workspace of one segment.  Shapes as bsrnn_separate: wave [R, n] ->
+ * wave_out [R, (T-1)*1024], T = 1 + n/1024, n > 1024.  The T frames are cut into consecutive segments of seg_frames frames (the last
+ * one shorter, down to one frame); each segment runs STFT of its frames (reflect padding at the CLIP's ends, never at a segment
+ * edge) -> the model on R * L frame rows, planned like bsrnn_forward_chunk, the time-axis LSTM state carried from segment to segment
+ * (the first starts from zeros; the model is causal along time) -> iSTFT of the hops the segment completes, the windowed second half
+ * of its last frame carried to the next segment.  Same DSP as bsrnn_separate (Hann synthesis window, sum of squared windows, no delay):
+ * given the same spectra the samples are bit-identical; the chunked model agrees with the one-shot model to rounding, as
+ * bsrnn_forward_chunk does with bsrnn_forward.  seg_frames >= T: the call IS bsrnn_separate (it delegates: bit-identical);
+ * seg_frames < 1: BSRNN_EARG.
+ * Memory: workspace of R * min(seg_frames, T) frame rows, task tables of at most two row counts (the full segment and the tail), two
+ * sets of LSTM state and of synthesis carry; nothing grows with T.  One fixed seg_frames therefore serves clips of every length from
+ * one workspace and one or two tables.
+ * Range policy per segment, as bsrnn_stream_process: under BSRNN_RANGE_EXACT the call waits after each segment and runs a segment
+ * that left the fp16 range again on the exact-fp32 kernels from that segment's untouched state and carry set; under
+ * BSRNN_RANGE_DEFERRED no segment waits.  wave_out must not overlap wave under EITHER policy (BSRNN_EARG): the reflected tail of the
+ * clip, and every later segment, is read after early hops have been written.  The two concurrent row blocks of bsrnn_separate for
+ * R >= 128 are not used here.
+ * bsrnn_separate_long_host: the same with both buffers in ordinary host memory, synchronous.  The library stages through two pinned
+ * input windows and two pinned output blocks with device mirrors of the same sizes and copies on a stream of its own, so the upload
+ * of segment i+1 and the download of segment i-1 run beside the kernels of segment i.  Device memory of the call is O(R * seg_frames),
+ * waveform included; the staging is made at first use and reused while R and seg_frames do not grow (a later call of any n allocates
+ * nothing: bsrnn_debug_counter(0)).  Same kernels, same order, same cut: bit-identical to bsrnn_separate_long. */
+int  bsrnn_separate_long(bsrnn_ctx* ctx, const float* wave_dev, float* wave_out_dev, int32_t R, int64_t n, int32_t seg_frames,
+                         void* stream);
+int  bsrnn_separate_long_host(bsrnn_ctx* ctx, const float* wave_host, float* wave_out_host, int32_t R, int64_t n,
+                              int32_t seg_frames);
+/* Frame rows the context's current workspace holds (measurement / test support); 0 before first use, on a host-only context and for
+ * a null context.  The workspace is grow-only: this is the largest R * T (or R * seg_frames) any call has needed, rounded up by growth. */
+int64_t bsrnn_workspace_rows(const bsrnn_ctx* ctx);
+
 /* ---- validation metrics (m_dataset.py:182-226 `infer` + `train_infer`, infer.py:44-47) ------
  * bsrnn_evaluate: mix_dev [R, n] (the mixture, sample[0]) and speech_dev [R, n] (the clean target,
  * sample[1]) -> separates the mixture (bsrnn_separate) and returns, in metrics_host[BSRNN_N_METRICS]:

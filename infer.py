@@ -7,7 +7,9 @@ Reference flow (infer.py:17-79): load model-always.pth -> load audio, mono dupli
 rows (:26-27) -> STFT (:29-33) -> BSRNN.forward (:34) -> iSTFT (:35-37) -> save -> report.
 Here STFT -> forward -> iSTFT is one fused device call (`BSRNN.separate`), numerically the same
 sandwich.  Extra flags: --weights (checkpoint or flat file), --synthetic-weights SEED (no
-trained weights ship with the reference), --device, --outdir for the re-mix files.
+trained weights ship with the reference), --device, --outdir for the re-mix files, --segment-frames N
+(long files: the waveform stays on the host and is separated N frames at a time in bounded device
+memory, `BSRNN.separate_long`; everything after the separation is unchanged).
 """
 import argparse
 import os
@@ -30,6 +32,8 @@ def main(argv=None):
     ap.add_argument("--synthetic-weights", type=int, default=None, metavar="SEED")
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--outdir", type=str, default=".")
+    ap.add_argument("--segment-frames", type=int, default=None, metavar="N",
+                    help="separate N STFT frames at a time (bounded device memory, for long files); default: the whole file in one call")
     args = ap.parse_args(argv)
 
     torch.set_grad_enabled(False)
@@ -42,7 +46,11 @@ def main(argv=None):
         waveform = torch.cat((waveform, waveform), 0)
     orig_peak = waveform.max().item()
 
-    dialog = model.separate(waveform.to(args.device)).cpu()
+    if args.segment_frames is None:
+        dialog = model.separate(waveform.to(args.device)).cpu()
+    else:
+        with torch.cuda.device(args.device):
+            dialog = model.separate_long(waveform, args.segment_frames)
     waveform = waveform[:, :dialog.shape[1]]
     audio.save_wav(args.output, dialog, sr)
 

@@ -321,6 +321,47 @@ class BSRNN(nn.Module):
             _check(_lib.bsrnn_separate(ctx, _ptr(w), _ptr(out), R, n, _stream_ptr(dev)))
         return out if waveform.is_cuda else out.cpu()
 
+    def separate_long(self, waveform, segment_frames=256, out=None):
+        """`separate` for a clip of any length in bounded memory: [R, n] -> [R, (n//1024)*1024], the frames cut into segments of
+        `segment_frames` (LSTM state and overlap-add tail carried from segment to segment; include/bsrnn_hip.h, bsrnn_separate_long).
+        The library's workspace is that of one segment.  A CUDA tensor is separated on its device; a CPU tensor stays on the host -
+        the library streams it through pinned windows, so the device holds O(R * segment_frames) of it, never the clip - and the
+        result is a CPU tensor.  `out` as in `separate`: contiguous float32 of exactly the result's shape on the waveform's device,
+        not overlapping it.  segment_frames >= the clip's frames is `separate` itself (bit-identical).  The default of 256 frames is
+        the chunk length of the chunked benchmark configuration, not a measured optimum."""
+        if not isinstance(waveform, torch.Tensor) or waveform.dim() != 2:
+            raise ValueError("separate_long: expected waveform [R, n], got %s" % (
+                tuple(waveform.shape) if isinstance(waveform, torch.Tensor) else type(waveform).__name__,))
+        dev = self._device_for(waveform)
+        on_host = not waveform.is_cuda
+        w = waveform.detach().to(dtype=torch.float32).contiguous() if on_host else self._prep(waveform, dev)
+        R, n = w.shape
+        shape = (R, (n // _spec.HOP) * _spec.HOP)
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != w.device
+                                or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError("separate_long: out must be a contiguous float32 tensor %s on %s, got %s" % (
+                shape, w.device, "%s %s on %s" % (tuple(out.shape), out.dtype, out.device) if isinstance(out, torch.Tensor) else type(out).__name__))
+        with torch.cuda.device(dev):
+            ctx = self._context(dev)
+            if out is None:
+                out = torch.empty(shape, device=w.device, dtype=torch.float32)
+            if on_host:
+                _check(_lib.bsrnn_separate_long_host(ctx, _ptr(w), _ptr(out), R, n, int(segment_frames)))
+            else:
+                _check(_lib.bsrnn_separate_long(ctx, _ptr(w), _ptr(out), R, n, int(segment_frames), _stream_ptr(dev)))
+        return out
+
+    def workspace_rows(self, device=None):
+        """Frame rows the native context's workspace holds right now (grow-only; 0 before the first call): what `separate` raises to
+        R * T and `separate_long` keeps at R * segment_frames (bsrnn_workspace_rows).  `device`: only the context on that device counts."""
+        if self._ctx is None:
+            return 0
+        if device is not None:
+            d = torch.device(device)
+            if (d.index if d.index is not None else torch.cuda.current_device()) != self._ctx_device:
+                return 0
+        return int(_lib.bsrnn_workspace_rows(self._ctx))
+
     def evaluate(self, mix, speech, return_estimate=False):
         """The reference's validation arithmetic on the device (m_dataset.py:182-226 `infer` + `train_infer` without
         the discriminator, and the "Separation dB" of infer.py:44-47): mix, speech [R, n] -> dict of

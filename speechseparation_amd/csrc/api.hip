@@ -165,6 +165,22 @@ struct bsrnn_ctx {
     // their row blocks.  (That check first failed: see the note at the top of fft.hip.)
     hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
+
+    // Long-form separation (bsrnn_separate_long / _long_host): what one segment of a clip hands to the next - the time-axis LSTM state and
+    // the synthesis carry (the windowed second half of the segment's last frame) - exists twice, like a bsrnn_stream's carry: segment i
+    // reads set i & 1 and writes the other one, so a segment that leaves the fp16 range is run again from its untouched starting point.
+    // The host-buffer entry point stages through two pinned input windows and two pinned output blocks with device mirrors of the same
+    // sizes, copied on a stream of their own.  All of it is sized by (rows, frames per segment), never by the clip.
+    struct LongForm {
+        int rows = 0;                                         // rows the carry sets were made for (grow-only)
+        float *state[2] = {nullptr, nullptr}, *carry[2] = {nullptr, nullptr};      // one allocation, state[0] its base
+        size_t in_floats = 0, out_floats = 0;                 // floats per input window / output block of the staging (grow-only)
+        float *h_base = nullptr, *d_base = nullptr;           // the pinned and the device allocation: [in 0 | in 1 | out 0 | out 1]
+        float *h_in[2], *h_out[2], *d_in[2], *d_out[2];
+        hipStream_t copy = nullptr;
+        // per block: its H2D has completed / the segment that read d_in and wrote d_out is final / its D2H has completed
+        hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_d2h[2] = {nullptr, nullptr};
+    } lf;
 };
 
 constexpr int MAX_PARTS = 4;
@@ -980,6 +996,13 @@ static void destroy_now(bsrnn_ctx* c)
         if (c->ev_join[j]) (void)hipEventDestroy(c->ev_join[j]);
     }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+    if (c->lf.copy) (void)hipStreamDestroy(c->lf.copy);
+    for (int k = 0; k < 2; ++k)
+        for (hipEvent_t e : {c->lf.ev_h2d[k], c->lf.ev_comp[k], c->lf.ev_d2h[k]})
+            if (e) (void)hipEventDestroy(e);
+    if (c->lf.state[0]) (void)hipFree(c->lf.state[0]);
+    if (c->lf.d_base) (void)hipFree(c->lf.d_base);
+    if (c->lf.h_base) (void)hipHostFree(c->lf.h_base);
     if (c->ev_ovl_fork) (void)hipEventDestroy(c->ev_ovl_fork);
     if (c->ev_ovl_join) (void)hipEventDestroy(c->ev_ovl_join);
     free_ovl_tables(c);
@@ -1652,6 +1675,218 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
     if ((rc = run())) return rc;
     return finish_call(c, s, run);
 }
+
+// --------------------------------------------------------------------------- long-form separation: the sandwich in segments
+// A clip of T frames as consecutive segments of `seg` frames (the last one shorter): segment STFT -> run_model on R * L frame rows with
+// the time-axis LSTM state carried (the model is causal along time; the band-axis blocks see one frame at a time) -> segment iSTFT with
+// the overlap-add tail carried.  Workspace, task tables and carry are those of one segment.
+
+// Clip samples [*lo, *hi] that the STFT of frames [ta, te) reads, reflections included: frame t covers t*1024 - 1024 .. t*1024 + 1023,
+// an index below 0 reflects to at most 1024 (< n), one above n - 1 to 2 (n - 1) - index - for the clip's last frame down to one sample
+// in front of the frame's own first when n is a multiple of 1024 (never below 1: n > 1024).
+static void segment_window(int64_t n, int ta, int te, int64_t* lo, int64_t* hi)
+{
+    const int64_t a = (int64_t)ta * HOPS - HOPS, b = (int64_t)(te - 1) * HOPS + HOPS - 1;
+    int64_t l = std::max<int64_t>(a, 0), h = std::min<int64_t>(b, n - 1);
+    if (a < 0) h = std::max<int64_t>(h, std::min<int64_t>(-a, n - 1));
+    if (b >= n) l = std::min<int64_t>(l, 2 * (n - 1) - b);
+    *lo = l; *hi = h;
+}
+
+static int ensure_long_carry(bsrnn_ctx* c, int R)
+{
+    bsrnn_ctx::LongForm& lf = c->lf;
+    if (R <= lf.rows) return 0;
+    const size_t nstate = (size_t)4 * 2 * R * c->K * HID, ncarry = (size_t)R * HOPS;
+    float* p = nullptr;
+    ++g_dbg[DBG_ALLOC];
+    HIP_TRY(hipMalloc((void**)&p, 2 * (nstate + ncarry) * sizeof(float)));
+    if (lf.state[0]) c->retired.push_back(lf.state[0]);           // (work of an earlier call may still read it: retired like the workspace)
+    for (int k = 0; k < 2; ++k) { lf.state[k] = p; p += nstate; }
+    for (int k = 0; k < 2; ++k) { lf.carry[k] = p; p += ncarry; }
+    lf.rows = R;
+    return 0;
+}
+
+// Staging of the host-buffer entry point for R rows and segments of `seg` frames.  A window holds at most (seg + 1) * 1024 + 1 samples per
+// row (segment_window), a block at most seg hops; the caller has nothing of its own in flight on them (the entry point is synchronous).
+static int ensure_long_staging(bsrnn_ctx* c, int R, int seg)
+{
+    bsrnn_ctx::LongForm& lf = c->lf;
+    if (!lf.copy) { ++g_dbg[DBG_ALLOC]; HIP_TRY(hipStreamCreateWithFlags(&lf.copy, hipStreamNonBlocking)); }
+    for (int k = 0; k < 2; ++k)
+        for (hipEvent_t* e : {&lf.ev_h2d[k], &lf.ev_comp[k], &lf.ev_d2h[k]})
+            if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    const size_t in = (size_t)R * (seg + 2) * HOPS, out = (size_t)R * seg * HOPS;
+    if (in <= lf.in_floats && out <= lf.out_floats) return 0;
+    const size_t in_new = std::max(in, lf.in_floats), out_new = std::max(out, lf.out_floats);
+    HIP_TRY(hipStreamSynchronize(lf.copy));
+    if (lf.d_base) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(lf.d_base); (void)hipHostFree(lf.h_base); lf.d_base = lf.h_base = nullptr; lf.in_floats = lf.out_floats = 0; }
+    const size_t bytes = 2 * (in_new + out_new) * sizeof(float);
+    g_dbg[DBG_ALLOC] += 2;
+    HIP_TRY(hipHostMalloc((void**)&lf.h_base, bytes, hipHostMallocDefault));
+    hipError_t e = hipMalloc((void**)&lf.d_base, bytes);
+    if (e != hipSuccess) { (void)hipHostFree(lf.h_base); lf.h_base = lf.d_base = nullptr; return fail(BSRNN_EHIP, "hipMalloc: %s", hipGetErrorString(e)); }
+    for (int k = 0; k < 2; ++k) {
+        lf.h_in[k] = lf.h_base + k * in_new; lf.d_in[k] = lf.d_base + k * in_new;
+        lf.h_out[k] = lf.h_base + 2 * in_new + k * out_new; lf.d_out[k] = lf.d_base + 2 * in_new + k * out_new;
+    }
+    lf.in_floats = in_new; lf.out_floats = out_new;
+    return 0;
+}
+
+// One segment from carry set p into set 1 - p (does not decide which set the next one reads: the caller does, once the segment is final).
+// src / stride / base as launch_stft_segment's, out / out_stride as launch_istft_segment's.
+static int long_segment_run(bsrnn_ctx* c, const float* src, int64_t stride, int64_t base, float* out, int64_t out_stride, int R, int64_t n, int ta,
+                            int te, int p, hipStream_t s)
+{
+    bsrnn_ctx::LongForm& lf = c->lf;
+    { StageScope sc(c, ST_STFT, s); launch_stft_segment(c->tb, src, stride, base, c->Xf, R, n, ta, te, s); }
+    if (int rc = run_model(c, c->Xf, c->Yf, nullptr, R, te - ta, lf.state[p], lf.state[p ^ 1], s)) return rc;
+    { StageScope sc(c, ST_ISTFT, s); launch_istft_segment(c->tb, c->Yf, out, out_stride, ta ? lf.carry[p] : nullptr, lf.carry[p ^ 1], R, te - ta, s); }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// All segments of a clip on stream s.  host = false: wave / wave_out are the whole clip and the whole result on the device.  host = true:
+// they are host memory; segment i goes through staging block i & 1 (ensure_long_staging), its window copied in and its hops copied out on the
+// copy stream beside the kernels of its neighbours:
+//   host:  stage window i+1 (when H2D i-1 has left the pinned window), take block i-1 (when D2H i-1 is there)  - while segment i computes
+//   copy:  H2D i+1 (after segment i-1, which read that mirror, is final) | D2H i (after segment i is final)
+//   s:     segment i after H2D i, and after D2H i-2 (which read the mirror segment i writes)
+// Same kernels, same order, same cut either way.
+static int long_segments(bsrnn_ctx* c, const float* wave, float* wave_out, int R, int64_t n, int T, int seg, hipStream_t s, bool host)
+{
+    bsrnn_ctx::LongForm& lf = c->lf;
+    const int nseg = (T + seg - 1) / seg;
+    const int64_t out_len = (int64_t)(T - 1) * HOPS;
+    struct Cut { int ta, te, hop0, nh; int64_t lo, wl; };
+    auto cut = [&](int i) {
+        Cut q;
+        q.ta = i * seg; q.te = std::min(T, q.ta + seg);
+        q.hop0 = std::max(q.ta - 1, 0); q.nh = q.te - 1 - q.hop0;
+        int64_t hi;
+        segment_window(n, q.ta, q.te, &q.lo, &hi);
+        q.wl = hi - q.lo + 1;
+        return q;
+    };
+    auto stage_in = [&](int i) -> int {
+        const Cut q = cut(i);
+        const int b = i & 1;
+        if ((size_t)R * q.wl > lf.in_floats) return fail(BSRNN_ESTATE, "segment window larger than its staging block (internal error)");
+        if (i >= 2) { HIP_TRY(hipEventSynchronize(lf.ev_h2d[b])); HIP_TRY(hipStreamWaitEvent(lf.copy, lf.ev_comp[b], 0)); }
+        for (int r = 0; r < R; ++r) memcpy(lf.h_in[b] + (size_t)r * q.wl, wave + (size_t)r * n + q.lo, (size_t)q.wl * sizeof(float));
+        HIP_TRY(hipMemcpyAsync(lf.d_in[b], lf.h_in[b], (size_t)R * q.wl * sizeof(float), hipMemcpyHostToDevice, lf.copy));
+        HIP_TRY(hipEventRecord(lf.ev_h2d[b], lf.copy));
+        return 0;
+    };
+    auto take_out = [&](int i) -> int {
+        const Cut q = cut(i);
+        if (!q.nh) return 0;
+        HIP_TRY(hipEventSynchronize(lf.ev_d2h[i & 1]));
+        const size_t len = (size_t)q.nh * HOPS;
+        for (int r = 0; r < R; ++r) memcpy(wave_out + (size_t)r * out_len + (size_t)q.hop0 * HOPS, lf.h_out[i & 1] + r * len, len * sizeof(float));
+        return 0;
+    };
+    int rc;
+    HIP_TRY(hipMemsetAsync(lf.state[0], 0, (size_t)4 * 2 * R * c->K * HID * sizeof(float), s));      // the clip starts from zero state (and needs no carry)
+    if (host && (rc = stage_in(0))) return rc;
+    for (int i = 0; i < nseg; ++i) {
+        const Cut q = cut(i);
+        const int b = i & 1;
+        const float* src = wave;
+        float* out = wave_out + (size_t)q.hop0 * HOPS;
+        int64_t stride = n, base = 0, out_stride = out_len;
+        if (host) {
+            src = lf.d_in[b]; stride = q.wl; base = q.lo; out = lf.d_out[b]; out_stride = (int64_t)q.nh * HOPS;
+            HIP_TRY(hipStreamWaitEvent(s, lf.ev_h2d[b], 0));
+            if (i >= 2) HIP_TRY(hipStreamWaitEvent(s, lf.ev_d2h[b], 0));
+        }
+        auto run = [&]() -> int { return long_segment_run(c, src, stride, base, out, out_stride, R, n, q.ta, q.te, b, s); };
+        if ((rc = run())) return rc;
+        if (host) {
+            if (i + 1 < nseg && (rc = stage_in(i + 1))) return rc;
+            if (i >= 1 && (rc = take_out(i - 1))) return rc;
+        }
+        // range policy per segment, as for a block of stream hops: the re-run starts from this segment's untouched state and carry set
+        if ((rc = finish_call(c, s, run))) return rc;
+        if (host) {
+            HIP_TRY(hipEventRecord(lf.ev_comp[b], s));
+            HIP_TRY(hipStreamWaitEvent(lf.copy, lf.ev_comp[b], 0));
+            if (q.nh) HIP_TRY(hipMemcpyAsync(lf.h_out[b], lf.d_out[b], (size_t)R * q.nh * HOPS * sizeof(float), hipMemcpyDeviceToHost, lf.copy));
+            HIP_TRY(hipEventRecord(lf.ev_d2h[b], lf.copy));
+        }
+    }
+    if (host) {
+        if ((rc = take_out(nseg - 1))) return rc;
+        HIP_TRY(hipStreamSynchronize(lf.copy));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+// What both entry points need before their first launch: workspace and task tables of the (at most two) segment lengths, the carry sets.
+static int long_prepare(bsrnn_ctx* c, int R, int T, int seg, const char* who)
+{
+    if ((int64_t)R * seg > INT32_MAX / 2) return fail(BSRNN_EARG, "%s: %d rows x %d frames is too many frame rows for one segment", who, R, seg);
+    int rc;
+    if ((rc = ensure_ws(c, (size_t)R * seg))) return rc;
+    int ms[2] = {R * seg, R * (T % seg)};
+    if ((rc = ensure_tasks(c, ms, ms[1] ? 2 : 1))) return rc;
+    return ensure_long_carry(c, R);
+}
+
+int bsrnn_separate_long(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, int64_t n, int32_t seg_frames, void* stream)
+{
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!wave || !wave_out || R < 1 || n <= NFFT / 2)
+        return fail(BSRNN_EARG, "bsrnn_separate_long: need two buffers, R >= 1 and n > 1024 samples, got R = %d, n = %lld", R, (long long)n);
+    if (seg_frames < 1) return fail(BSRNN_EARG, "bsrnn_separate_long: seg_frames = %d (at least one frame per segment)", seg_frames);
+    int rc = check_ready(c);
+    if (rc) return rc;
+    const int T = 1 + (int)(n / HOPS);
+    // whatever the range policy: the clip's reflected tail (and every later segment) is read after early hops have been written
+    if (ranges_overlap(wave, (size_t)R * n * sizeof(float), wave_out, (size_t)R * (T - 1) * HOPS * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_separate_long: wave_out must not overlap wave (later segments read the waveform after earlier hops are written)");
+    if (seg_frames >= T) return bsrnn_separate(c, wave, wave_out, R, n, stream);       // one segment IS the one-shot call: bit-identical by construction
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    if ((rc = long_prepare(c, R, T, seg_frames, "bsrnn_separate_long"))) return rc;
+    return long_segments(c, wave, wave_out, R, n, T, seg_frames, s, false);
+}
+
+int bsrnn_separate_long_host(bsrnn_ctx* c, const float* wave_host, float* wave_out_host, int32_t R, int64_t n, int32_t seg_frames)
+{
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!wave_host || !wave_out_host || R < 1 || n <= NFFT / 2)
+        return fail(BSRNN_EARG, "bsrnn_separate_long_host: need two buffers, R >= 1 and n > 1024 samples, got R = %d, n = %lld", R, (long long)n);
+    if (seg_frames < 1) return fail(BSRNN_EARG, "bsrnn_separate_long_host: seg_frames = %d (at least one frame per segment)", seg_frames);
+    int rc = check_ready(c);
+    if (rc) return rc;
+    const int T = 1 + (int)(n / HOPS);
+    const size_t out_floats = (size_t)R * (T - 1) * HOPS;
+    if (ranges_overlap(wave_host, (size_t)R * n * sizeof(float), wave_out_host, out_floats * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_separate_long_host: wave_out must not overlap wave (later segments read the waveform after earlier hops are written)");
+    hipStream_t s = nullptr;
+    ENTER_CALL(c, s);
+    const int seg = std::min<int>(seg_frames, T);
+    if ((int64_t)R * seg > INT32_MAX / 2) return fail(BSRNN_EARG, "bsrnn_separate_long_host: %d rows x %d frames is too many frame rows for one segment", R, seg);
+    if ((rc = ensure_long_staging(c, R, seg))) return rc;
+    bsrnn_ctx::LongForm& lf = c->lf;
+    if (seg_frames >= T) {       // one segment: the one-shot call on the staged clip (R * n <= R * (T + 1) * 1024 floats: it fits a window)
+        memcpy(lf.h_in[0], wave_host, (size_t)R * n * sizeof(float));
+        HIP_TRY(hipMemcpyAsync(lf.d_in[0], lf.h_in[0], (size_t)R * n * sizeof(float), hipMemcpyHostToDevice, s));
+        if ((rc = bsrnn_separate(c, lf.d_in[0], lf.d_out[0], R, n, s))) return rc;
+        HIP_TRY(hipMemcpyAsync(lf.h_out[0], lf.d_out[0], out_floats * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        memcpy(wave_out_host, lf.h_out[0], out_floats * sizeof(float));
+        return 0;
+    }
+    if ((rc = long_prepare(c, R, T, seg, "bsrnn_separate_long_host"))) return rc;
+    return long_segments(c, wave_host, wave_out_host, R, n, T, seg, s, true);
+}
+
+int64_t bsrnn_workspace_rows(const bsrnn_ctx* c) { return c ? (int64_t)c->cap_rows : 0; }
 
 // --------------------------------------------------------------------------- validation metrics
 // m_dataset.py:182-226 (`infer` + `train_infer` without the discriminator) and infer.py:44-47.

@@ -697,4 +697,134 @@ void launch_stream_block_synthesis(const FftTables& tb, const float* Y, const fl
     else hipLaunchKernelGGL(stream_block_synthesis_kernel<true>, grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ich);
 }
 
+// ------------------------------------------------------------------------------ offline DSP, one segment of a clip
+// The offline pair for frames [ta, te) of a clip of T = 1 + n / 1024 frames (bsrnn_separate_long): the clip is transformed segment after
+// segment, so nothing here grows with the clip.  Per frame the arithmetic is that of stft_kernel<false> / istft_fused_kernel, in their
+// order: given the same samples / spectra, a segment's rows and hops are bit-identical to the same frames of the one-shot kernels.
+//
+// Analysis: padded sample i of frame t is sample t*1024 + i - 1024 of the WHOLE clip, reflected at 0 and at n - 1 (never at a segment
+// edge).  `src` is either the whole clip (base = 0, stride = n) or a staged window of it that starts at clip sample `base` (rows `stride`
+// floats apart); `base` is subtracted after the reflection, and the caller makes the window hold every index the segment touches
+// (api.hip: segment_window).  Rows of X are segment-local: X[(r * (te - ta) + (t - ta)) * ld].
+__global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_segment_kernel(FftTables tb, const float* __restrict__ wave, float* __restrict__ X,
+                                                                         int64_t n, int64_t base, int64_t stride, int ta, int te, int sch)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const Twiddles twd = load_twiddles<false>(tb.tw1024, tid);
+    const SplitCtx spl = load_split(tb, tid, false);
+    const int r = blockIdx.y;
+    const int t0 = ta + blockIdx.x * sch;
+    const int t1 = (t0 + sch < te) ? t0 + sch : te;
+    const float* src = wave + (size_t)r * stride;
+    float2 win[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) win[k] = make_float2(tb.hann[2 * (tid + 256 * k)], tb.hann[2 * (tid + 256 * k) + 1]);
+    auto sample2 = [&](int t, int c) {
+        float v[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            int64_t idx = (int64_t)t * HOPS + 2 * c + e - NFFT / 2;
+            if (idx < 0) idx = -idx;
+            if (idx >= n) idx = 2 * (n - 1) - idx;
+            v[e] = src[idx - base];
+        }
+        return make_float2(v[0], v[1]);
+    };
+    float2 raw[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) raw[k] = sample2(t0, tid + 256 * k);
+    for (int t = t0; t < t1; ++t) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) z0[tid + 256 * k] = make_float2(raw[k].x * win[k].x, raw[k].y * win[k].y);
+        __syncthreads();
+        raw[0] = raw[2]; raw[1] = raw[3];
+        { const int tn = t + 1 < t1 ? t + 1 : t; raw[2] = sample2(tn, tid + 512); raw[3] = sample2(tn, tid + 768); }      // (no branch: after the last frame a dummy reload)
+        const float2* Z = fft1024<false>(z0, z1, twd, tid);
+        rfft_split_store(Z, spl, X + ((size_t)r * (te - ta) + (t - ta)) * tb.ld, tid);
+        __syncthreads();                          // Z (= z1) is overwritten by the next frame's first pass
+    }
+}
+
+// Synthesis: Y = the spectra of the segment's L = te - ta frames (segment-local rows).  Output hop b of the clip is the first half of
+// frame b + 1 plus the second half of frame b, so the segment completes hops [max(ta - 1, 0), te - 1): every frame but the clip's first
+// completes one.  A workgroup walks the frames [a0, a1) that complete its hops with the windowed second half of the frame in front in
+// registers: recomputed from that frame like istft_fused_kernel does - or, for the segment's first frame when the clip has frames in
+// front of it (carry_in != null), read from carry_in [R][1024], where the previous segment's launch left exactly those registers
+// (sample j of the windowed and scaled second half at [r][j]).  The workgroup that walks frame L - 1 leaves carry_out likewise (another
+// set than carry_in).  `out` points at the segment's first hop of row 0, rows out_stride floats apart.
+__global__ __launch_bounds__(256, FFT_OCC_ISTFT) void istft_segment_kernel(FftTables tb, const float* __restrict__ Y, float* __restrict__ out, int64_t out_stride,
+                                                                           const float* __restrict__ carry_in, float* __restrict__ carry_out, int L, int ich)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const Twiddles twd = load_twiddles<true>(tb.tw1024, tid);
+    const SplitCtx spl = load_split(tb, tid, true);
+    const int r = blockIdx.y;
+    const int f0 = carry_in ? 0 : 1;                                  // the first frame that completes a hop (local hop = frame - f0)
+    const int a0 = f0 + blockIdx.x * ich;
+    const int a1 = (a0 + ich < L) ? a0 + ich : L;                     // (a one-frame first segment: a0 = a1 = 1, the carry only)
+    const float sc = 1.0f / 1024.0f;
+    float2 wlo[2], whi[2], env[2], carry[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int c = tid + 256 * k;
+        wlo[k] = make_float2(tb.hann[2 * c] * sc, tb.hann[2 * c + 1] * sc);
+        whi[k] = make_float2(tb.hann[2 * c + HOPS] * sc, tb.hann[2 * c + 1 + HOPS] * sc);
+        env[k] = make_float2(tb.inv_env[2 * c], tb.inv_env[2 * c + 1]);
+        carry[k] = make_float2(0.f, 0.f);
+    }
+    const float* Yr = Y + (size_t)r * L * tb.ld;
+    float* o = out + (size_t)r * out_stride;
+    MergeRegs mr;
+    // The frame in front of the range only fills the carry; it is peeled so that the loop body has no branch around its loads and stores
+    auto frame = [&](int t, auto first) {
+        irfft_store(mr, spl, z0, tid);
+        __syncthreads();
+        irfft_load<false>(Yr + (size_t)(t + 1 < a1 ? t + 1 : t) * tb.ld, spl, mr, tid);      // (after the last frame: a dummy reload)
+        const float2* z = fft1024<true>(z0, z1, twd, tid);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 256 * k;
+            const float2 a = z[c], b = z[c + 512];
+            if (!decltype(first)::value) {
+                // same operation order as istft_fused_kernel: (frame * 1/1024 * window) summed, then / envelope
+                const float2 v = make_float2((a.x * wlo[k].x + carry[k].x) * env[k].x, (a.y * wlo[k].y + carry[k].y) * env[k].y);
+                *reinterpret_cast<float2*>(o + (size_t)(t - f0) * HOPS + 2 * c) = v;
+            }
+            carry[k] = make_float2(b.x * whi[k].x, b.y * whi[k].y);
+        }
+        __syncthreads();                          // z (= z1) is overwritten by the next frame's first pass
+    };
+    if (a0 == 0) {
+        irfft_load<false>(Yr, spl, mr, tid);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) carry[k] = *reinterpret_cast<const float2*>(carry_in + (size_t)r * HOPS + 2 * (tid + 256 * k));
+    } else {
+        irfft_load<false>(Yr + (size_t)(a0 - 1) * tb.ld, spl, mr, tid);
+        frame(a0 - 1, std::true_type());
+    }
+    for (int t = a0; t < a1; ++t) frame(t, std::false_type());
+    if (a1 == L) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) *reinterpret_cast<float2*>(carry_out + (size_t)r * HOPS + 2 * (tid + 256 * k)) = carry[k];
+    }
+}
+
+void launch_stft_segment(const FftTables& tb, const float* src, int64_t stride, int64_t base, float* X, int R, int64_t n, int ta, int te, hipStream_t s)
+{
+    static const int slots = resident_slots((const void*)stft_segment_kernel);
+    const int sch = frames_per_workgroup(te - ta, R, slots, 0);
+    hipLaunchKernelGGL(stft_segment_kernel, dim3((unsigned)((te - ta + sch - 1) / sch), R), dim3(256), 0, s, tb, src, X, n, base, stride, ta, te, sch);
+}
+void launch_istft_segment(const FftTables& tb, const float* Y, float* out, int64_t out_stride, const float* carry_in, float* carry_out, int R, int L,
+                          hipStream_t s)
+{
+    static const int slots = resident_slots((const void*)istft_segment_kernel);
+    const int hops = L - (carry_in ? 0 : 1);                           // 0: a one-frame first segment (one workgroup per row leaves the carry)
+    const int ich = frames_per_workgroup(hops > 0 ? hops : 1, R, slots, 1);
+    const dim3 grid((unsigned)(hops > 0 ? (hops + ich - 1) / ich : 1), R);
+    hipLaunchKernelGGL(istft_segment_kernel, grid, dim3(256), 0, s, tb, Y, out, out_stride, carry_in, carry_out, L, ich);
+}
+
 }  // namespace bsrnn

@@ -250,6 +250,15 @@ struct FftTables {           // device tables, built once per context (double pr
 void launch_stft(const FftTables& tb, const float* wave, float* X, int R, int64_t n, int T, hipStream_t s);
 // Y frame-major [R*T][ld] -> wave_out [R][(T-1)*1024]: inverse real FFT, synthesis window, overlap-add / envelope, fused
 void launch_istft(const FftTables& tb, const float* Y, float* out, int R, int T, hipStream_t s);
+// The same pair for frames [ta, te) of the clip alone (bsrnn_separate_long; fft.hip), segment-local rows X / Y [R*(te-ta)][ld]:
+//   analysis: src = the clip (stride = n, base = 0) or a staged window of it that starts at clip sample `base`, rows `stride` floats apart;
+//             reflection is at the clip's ends
+//   synthesis: writes the hops the segment completes, [max(ta-1, 0), te-1), to out (its first hop of row 0; rows out_stride floats apart);
+//             carry_in [R][1024] = the windowed second half of frame ta-1 as the previous segment's launch left it (null: ta = 0),
+//             carry_out [R][1024] = that of frame te-1 (another buffer than carry_in)
+void launch_stft_segment(const FftTables& tb, const float* src, int64_t stride, int64_t base, float* X, int R, int64_t n, int ta, int te, hipStream_t s);
+void launch_istft_segment(const FftTables& tb, const float* Y, float* out, int64_t out_stride, const float* carry_in, float* carry_out, int R, int L,
+                          hipStream_t s);
 // gradient of launch_istft's output w.r.t. its input (training step): dwave [R][(T-1)*1024] -> dY frame-major [R*T][ld];
 // scratch [R][(T-1)*1024]
 void launch_istft_backward(const FftTables& tb, const float* dwave, float* scratch, float* dY, int R, int T, hipStream_t s);
