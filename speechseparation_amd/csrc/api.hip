@@ -5,6 +5,7 @@
 #include "../../include/bsrnn_hip.h"
 #include "kernels.h"
 #include "commit_host.h"
+#include "plan_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -183,9 +184,6 @@ struct bsrnn_ctx {
     } lf;
 };
 
-constexpr int MAX_PARTS = 4;
-constexpr int OVL_HEAD = 16;          // ints in front of a block's progress words (the resident counter on a line of its own)
-
 struct bsrnn_stream {
     bsrnn_ctx* ctx;
     int C;
@@ -296,12 +294,8 @@ int ensure_ws(bsrnn_ctx* c, size_t rows)
     // call may still be running in it.  It stays valid scratch for whoever knows it; everything new uses the new one (streaming graphs of
     // this library re-capture: generation counter).  At most ~3x the final size in all, released with the context.
     if (c->cap_rows) rows = std::max(rows, c->cap_rows + c->cap_rows / 2);
-    const size_t KH = (size_t)c->K * HID;
-    auto seg = [](size_t n) { return (n + 63) & ~size_t(63); };
-    const size_t sizes[11] = {seg(rows * c->LDP), seg(rows * c->LDP), seg(rows * c->LDA), seg(rows * c->LDA), seg(rows * c->LDP),
-                              seg(rows * KH), seg(rows * KH), seg(rows * KH * 2), seg(rows * KH * 2), seg(rows * KH),
-                              seg(rows / 8 + 2 * MAX_PARTS + 64)};
-    size_t total = 0;
+    size_t sizes[WS_SEGS], total = 0;
+    workspace_segments(rows, c->LDP, c->LDA, c->K, sizes);
     for (size_t s : sizes) total += s;
     float* fresh = nullptr;
     ++g_dbg[DBG_ALLOC];
@@ -343,20 +337,18 @@ int ensure_streams(bsrnn_ctx* c, int parts)
     return 0;
 }
 
-// Task table of a fused chain launch for M frame rows: one entry (descriptor, first row) per workgroup, in dispatch order:
-// longest workgroups first (the descriptors are sorted by class and cost at commit), all row blocks of a band together
-// (they share its weight stream through L2).  Measured and dropped: interleaving the fill-bound 768-wide band with the
-// others (its workgroups take 97 us on half the CUs against 129 us on all of them, tools/chain_bench.hip) - the late starts
-// of the long workgroups cost more than the contention saves (310 vs 250 us per chain).
-void build_chain_tasks(const bsrnn_ctx* c, int ch, int M, std::vector<int2>& out)
+// A small table on the device: `bytes` of h behind a fresh allocation of bytes + slack.  On failure nothing is left allocated and *d is null.
+static_assert(sizeof(ChainTask) == sizeof(int2) && alignof(ChainTask) <= alignof(int2), "the kernels read a ChainTask as an int2");
+template <class T>
+hipError_t upload_table(T** d, const void* h, size_t bytes, size_t slack = 0)
 {
-    out.clear();
-    const auto& ds = c->h_chain[ch];
-    for (size_t di = 0; di < ds.size(); ++di)
-        for (int r0 = 0; r0 < M; r0 += chain_rows(ds[di])) out.push_back(make_int2((int)di, r0));
+    *d = nullptr;
+    hipError_t e = hipMalloc((void**)d, bytes + slack);
+    if (e == hipSuccess && (e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice)) != hipSuccess) { (void)hipFree(*d); *d = nullptr; }
+    return e;
 }
 
-// Task tables for the row counts of ONE call (several when the call runs as concurrent row blocks).  The cache is bounded; when it
+// Task tables (build_chain_tasks, plan_host.h) for the row counts of ONE call (several when the call runs as concurrent row blocks).  The cache is bounded; when it
 // is full it is dropped once, before any of this call's tables is made, so a call never evicts a table it is about to use
 // (captured streaming graphs notice through ctx->gen and re-capture).
 void free_chain_tasks(bsrnn_ctx* c)
@@ -380,15 +372,14 @@ int ensure_tasks(bsrnn_ctx* c, const int* Ms, int n)
         if (c->chain_tasks.find(Ms[i]) != c->chain_tasks.end()) continue;
         bsrnn_ctx::TaskTable t;
         t.d[0] = t.d[1] = nullptr;
-        std::vector<int2> h;
+        std::vector<ChainTask> h;
         for (int ch = 0; ch < 2; ++ch) {
-            build_chain_tasks(c, ch, Ms[i], h);
+            build_chain_tasks(c->h_chain[ch], Ms[i], h);
             t.n[ch] = (int)h.size();
             ++g_dbg[DBG_ALLOC];
-            hipError_t e = hipMalloc((void**)&t.d[ch], (h.size() + 1) * sizeof(int2));
-            if (e == hipSuccess) e = hipMemcpy(t.d[ch], h.data(), h.size() * sizeof(int2), hipMemcpyHostToDevice);
+            const hipError_t e = upload_table(&t.d[ch], h.data(), h.size() * sizeof(int2), sizeof(int2));
             if (e != hipSuccess) {
-                for (int k = 0; k <= ch; ++k) if (t.d[k]) (void)hipFree(t.d[k]);
+                (void)hipFree(t.d[0]);
                 return fail(BSRNN_EHIP, "task table: %s", hipGetErrorString(e));
             }
         }
@@ -416,64 +407,22 @@ void gemm_slot(bsrnn_ctx* c, bool gemv, int slot, const float* X, int ldx, float
     else launch_gemm(g, s);
 }
 
-// --------------------------------------------------------------------------- the call plan
-// Which kernels one model call runs, decided once per call by plan_call() and read by everything that launches or sizes something for it
-// (run_stage, the overlapped dual path, bsrnn_separate's row blocks): the time-axis launch and the consumers that wait on its progress
-// words agree on its sequences per workgroup because they all read Flow::seqs.
-// Band-axis blocks: a few frame rows (streaming) as one launch of the whole block, fc + residual included (band_block_small_kernel); both
-// layers in one launch writing the shares of the block's fc that the time-axis launch adds (kernels.h); both layers in one launch and the fc
-// + residual as a grouped-GEMM launch; one launch per layer and the same fc launch.
-enum BandForm { BAND_SMALL, BAND_PAIR_PARTS, BAND_PAIR, BAND_LAYERS };
-struct Flow {
-    bool exact;          // force_f32(): the range-guard re-run - every launch on the exact-fp32 kernels
-    bool lstm_f32;       // the recurrent layers on the fp32 kernels (BSRNN_LSTM=f32, or exact)
-    bool gemv;           // a call of <= GEMV_MAX_FRAME_ROWS frame rows: its per-band layers as GEMV launches (gemm_slot, gemv.hip)
-    bool chains;         // the per-band MLPs as fused chains (mlp_chain.hip); else one launch per layer
-    int band;            // BandForm of the band-axis blocks
-    bool time_fc;        // the time-axis launch forms its block's fc + residual itself (no MS_TIMEFC launch)
-    int seqs, nwg;       // the time-axis launch: sequences per workgroup (4, or 8 on time_lstm_h2w8_kernel) and workgroups
-    bool overlap;        // the dual path runs overlapped (run_overlapped), given its tables and no graph capture (ovl_table)
-};
-
-// The plan of a call of C rows x T frames.  gemv / overlap: the entry point may run a few frame rows on the GEMV kernels / the dual path
-// overlapped.  The rest comes from the knobs, force_f32() (the exact re-run plans again) and the context's sticky fall-backs.
+// --------------------------------------------------------------------------- the call plan (plan_host.h)
+// The knobs of the plan, read from the environment once per process, at the first call that plans
+static const PlanKnobs& plan_knobs()
+{
+    static const PlanKnobs knobs = [] {
+        auto is = [](const char* name, const char* value) { const char* e = getenv(name); return e && !strcmp(e, value); };
+        const char *tk = getenv("BSRNN_TIME_KERNEL"), *s8 = getenv("BSRNN_TIME_SEQ8");
+        if (tk && *tk && strcmp(tk, "fused") && strcmp(tk, "v3")) fprintf(stderr, "bsrnn: unknown BSRNN_TIME_KERNEL='%s' (v3 | fused), using fused\n", tk);
+        return PlanKnobs{!is("BSRNN_BAND_PAIR", "0"), !is("BSRNN_BAND_FC", "gemm"), !is("BSRNN_TIME_KERNEL", "v3"), s8 ? atoi(s8) : -1,
+                         gemm_mode(), lstm_mode(), device_cus()};
+    }();
+    return knobs;
+}
 static Flow plan_call(const bsrnn_ctx* c, int C, int T, bool gemv, bool overlap)
 {
-    // The knobs, read once per process: BSRNN_BAND_PAIR=0 one launch per band layer; BSRNN_BAND_FC=gemm the band
-    // block's fc + residual as a grouped-GEMM launch instead of the shares the pair launch writes and the time-axis launch adds (the second
-    // layer alone with the shares sits at the edge of 256 VGPRs - as a kernel of its own it spilled four registers - and is not shipped);
-    // BSRNN_TIME_KERNEL=v3 the time block's fc as a launch of its own; BSRNN_TIME_SEQ8 = 0 / 1: eight sequences per time-axis workgroup never /
-    // always (unset: where four would need more than one round of workgroups).
-    auto is = [](const char* name, const char* value) { const char* e = getenv(name); return e && !strcmp(e, value); };
-    static const bool pair_knob = !is("BSRNN_BAND_PAIR", "0"), parts_knob = !is("BSRNN_BAND_FC", "gemm");
-    static const bool time_fused = [] {
-        const char* e = getenv("BSRNN_TIME_KERNEL");
-        if (e && *e && strcmp(e, "fused") && strcmp(e, "v3")) fprintf(stderr, "bsrnn: unknown BSRNN_TIME_KERNEL='%s' (v3 | fused), using fused\n", e);
-        return !(e && !strcmp(e, "v3"));
-    }();
-    static const int seq8 = [] { const char* e = getenv("BSRNN_TIME_SEQ8"); return e ? atoi(e) : -1; }();
-    Flow f;
-    const int M = C * T, K = c->K, N = C * K, cus = device_cus();
-    f.exact = force_f32();
-    f.lstm_f32 = f.exact || lstm_mode() == LSTM_F32;
-    const bool gemm16 = !f.exact && gemm_mode() != GEMM_F32;
-    f.gemv = gemv && M <= GEMV_MAX_FRAME_ROWS;
-    f.chains = c->fused && !f.exact && !f.gemv;
-    // the fc inside the time-axis kernel unless the Linear layers are asked to be exact fp32 (BSRNN_GEMM=f32)
-    f.time_fc = !f.lstm_f32 && gemm16 && time_fused;
-    // the pair launch is fp16x2 only; a context whose pair launch once reported that its partner workgroups did not meet runs one launch
-    // per layer from then on.  The fc in parts needs the pair launch and the fused time-axis kernel.
-    const bool pair = !f.lstm_f32 && pair_knob && !c->band_pair_off;
-    if (!f.lstm_f32 && gemm16 && M <= 8 && K <= BS_MAXL) f.band = BAND_SMALL;
-    else if (pair && parts_knob && f.time_fc) f.band = BAND_PAIR_PARTS;
-    else f.band = pair ? BAND_PAIR : BAND_LAYERS;
-    f.seqs = f.time_fc && (seq8 == 1 || (seq8 < 0 && (N + 3) / 4 > cus)) ? 8 : 4;
-    f.nwg = (N + f.seqs - 1) / f.seqs;
-    // Overlapped: the parts flow with fused chains (the launches that know how to publish / wait), a time-axis launch that leaves CUs free
-    // (at most 7/8 of them) and enough frames for a head start to exist
-    f.overlap = overlap && c->overlap_env && !c->overlap_off && f.band == BAND_PAIR_PARTS && c->fused && f.nwg >= 32 && f.nwg <= cus - cus / 8 &&
-                T >= 32 && T < (4 << OVL_EPOCH_SHIFT) - 8;
-    return f;
+    return plan_call(c->K, C, T, gemv, overlap, plan_knobs(), PlanState{force_f32(), c->fused, c->band_pair_off, c->overlap_env, c->overlap_off});
 }
 
 // A contiguous block of rows (utterance-channels) of one call, with its slice of the workspace
@@ -504,13 +453,23 @@ Part make_part(bsrnn_ctx* c, int row0, int C, int T, hipStream_t s, int j = 0)
     p.A1 = c->A1 + m0 * c->LDA; p.A2 = c->A2 + m0 * c->LDA; p.P = c->P + m0 * c->LDP;
     p.Z0 = c->Z0 + m0 * KH; p.Z1 = c->Z1 + m0 * KH; p.H1 = c->H1 + m0 * KH;
     p.HB0 = c->HB0 + m0 * KH * 2; p.HB1 = c->HB1 + m0 * KH * 2;
-    // Row block j starts j pairs behind its first tile's natural place: block j - 1 ends at most at floor(m0 / 16) + 1 + (j - 1), so the
-    // pair ranges of concurrent blocks are disjoint for any row split (odd R, 3 or 4 blocks included; checked in bsrnn_separate)
-    p.band_flags = c->band_flags + 2 * (m0 / 16 + j);
+    p.band_flags = c->band_flags + flag_offset(m0, j);
     return p;
 }
 
 enum { MS_STFT, MS_BANDSPLIT, MS_BAND0, MS_BANDFC0, MS_TIME0, MS_TIMEFC0, MS_BAND1, MS_BANDFC1, MS_TIME1, MS_TIMEFC1, MS_MASK, MS_ISTFT, MS_COUNT };
+
+// What the launches of both fused chains share for a part: the task table of its M frame rows (made by ensure_tasks() before any launch,
+// and outside graph capture) and the common operands.  False: no such table (stage_error is set).
+bool chain_launch(bsrnn_ctx* c, const Part& p, int chain, ChainLaunch& g)
+{
+    memset(&g, 0, sizeof g);
+    auto tti = c->chain_tasks.find(p.C * p.T);
+    if (tti == c->chain_tasks.end()) { c->stage_error = true; return false; }
+    g.desc = c->d_chain[chain]; g.tasks = tti->second.d[chain]; g.n_tasks = tti->second.n[chain];
+    g.M = p.C * p.T; g.P = p.P; g.ldp = c->LDP; g.range_flag = c->d_range;
+    return true;
+}
 
 // One stage of the model for one part.  Xf [M][2050] -> Yf [M][2050], M = C*T, row = c*T + t.
 void run_stage(bsrnn_ctx* c, const Part& p, int stage)
@@ -526,12 +485,8 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
         StageScope sc(c, ST_BANDSPLIT, s);
         if (f.chains) {                   // all five layers of every band in one launch, intermediates in LDS
             ChainLaunch g;
-            memset(&g, 0, sizeof g);
-            auto tti = c->chain_tasks.find(M);                           // made by ensure_tasks() before any launch (and outside graph capture)
-            if (tti == c->chain_tasks.end()) { c->stage_error = true; break; }
-            const bsrnn_ctx::TaskTable& tt = tti->second;
-            g.desc = c->d_chain[CHAIN_SPLIT]; g.tasks = tt.d[CHAIN_SPLIT]; g.n_tasks = tt.n[CHAIN_SPLIT];
-            g.M = M; g.Xin = p.Xf; g.ldx = c->LDP; g.P = p.P; g.ldp = c->LDP; g.Z = p.Z0; g.ldz = KH; g.range_flag = c->d_range;
+            if (!chain_launch(c, p, CHAIN_SPLIT, g)) break;
+            g.Xin = p.Xf; g.ldx = c->LDP; g.Z = p.Z0; g.ldz = KH;
             launch_mlp_chain(g, CHAIN_SPLIT, s);
             break;
         }
@@ -600,13 +555,9 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
         StageScope sc(c, ST_MASK, s);
         if (f.chains) {
             ChainLaunch g;
-            memset(&g, 0, sizeof g);
-            auto tti = c->chain_tasks.find(M);
-            if (tti == c->chain_tasks.end()) { c->stage_error = true; break; }
-            const bsrnn_ctx::TaskTable& tt = tti->second;
-            g.desc = c->d_chain[CHAIN_MASK]; g.tasks = tt.d[CHAIN_MASK]; g.n_tasks = tt.n[CHAIN_MASK];
-            g.M = M; g.Xin = p.Z0; g.ldx = KH; g.P = p.P; g.ldp = c->LDP; g.Xmul = p.Xf; g.ldm = c->LDP;
-            g.Y = p.Yf; g.ldy = c->LDP; g.tap = p.tap; g.ldt = c->LDP; g.range_flag = c->d_range;
+            if (!chain_launch(c, p, CHAIN_MASK, g)) break;
+            g.Xin = p.Z0; g.ldx = KH; g.Xmul = p.Xf; g.ldm = c->LDP;
+            g.Y = p.Yf; g.ldy = c->LDP; g.tap = p.tap; g.ldt = c->LDP;
             if (p.ovl) {                          // beside the second time-axis launch: the earliest-ready heavy workgroups first
                 g.tasks = p.ovl->mask_tasks; g.n_tasks = p.ovl->n_mask;
                 g.ovl_prog = c->d_ovl + c->ovl_stride + OVL_HEAD; g.ovl_T = p.T; g.ovl_K = K;
@@ -648,8 +599,7 @@ int ensure_ovl(bsrnn_ctx* c, const Flow& f, int C, int T)
     if (!c->ev_ovl_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_ovl_fork, hipEventDisableTiming | hipEventDisableSystemFence));      // (device-side ordering only: no system-scope release on the record)
     if (!c->ev_ovl_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_ovl_join, hipEventDisableTiming | hipEventDisableSystemFence));
     if (!c->ev_ovl_mid) HIP_TRY(hipEventCreateWithFlags(&c->ev_ovl_mid, hipEventDisableTiming | hipEventDisableSystemFence));
-    const int M = C * T, nwg = f.nwg;
-    const int stride = OVL_HEAD + ((nwg + 15) & ~15);
+    const int stride = ovl_stride(f.nwg);
     if (stride > c->ovl_stride) {
         if (c->d_ovl) { c->retired.push_back(c->d_ovl); c->d_ovl = nullptr; }      // (retired like the workspace, see ensure_ws)
         ++g_dbg[DBG_ALLOC];
@@ -662,48 +612,12 @@ int ensure_ovl(bsrnn_ctx* c, const Flow& f, int C, int T)
     const auto key = std::make_pair(C, T);
     if (c->ovl_tables.find(key) != c->ovl_tables.end()) return 0;
     if (c->ovl_tables.size() >= c->ovl_cap) { HIP_TRY(hipDeviceSynchronize()); free_ovl_tables(c); ++c->gen; }
-    // band block: tiles of 16 frame rows m = row * T + frame, sorted by the last frame the tile needs (a tile that straddles two batch
-    // rows needs the first one's last frame); padded with -1 to the launch's whole groups of eight tiles
-    const int tiles = (M + 15) / 16, n_ord = ((tiles + 7) / 8) * 8;
-    std::vector<int> order(tiles), ready(tiles);
-    for (int t = 0; t < tiles; ++t) {
-        const int m0 = 16 * t, m1 = std::min(M - 1, m0 + 15);
-        order[t] = t;
-        ready[t] = m0 / T != m1 / T ? T - 1 : m1 % T;
-    }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ready[a] < ready[b]; });
-    order.resize(n_ord, -1);
-    // mask chain: its task table (longest workgroups first) with the workgroups that can START while the time-axis launch still runs
-    // in front: as many as that launch leaves CUs free (each runs longer than the rest of it), the earliest-ready of the heavy classes
-    // (<= 80 rows per workgroup: the widest bands, which also end the launch when they start late)
-    std::vector<int2> tasks;
-    build_chain_tasks(c, CHAIN_MASK, M, tasks);
-    const auto& ds = c->h_chain[CHAIN_MASK];
-    std::vector<int> cand;
-    auto task_ready = [&](const int2& t) {
-        const int m1 = std::min(M - 1, t.y + chain_rows(ds[t.x]) - 1);
-        return t.y / T != m1 / T ? T - 1 : m1 % T;
-    };
-    for (int i = 0; i < (int)tasks.size(); ++i)
-        if (!ds[tasks[i].x].constant && chain_rows(ds[tasks[i].x]) <= 80 && task_ready(tasks[i]) < T - 1) cand.push_back(i);
-    std::stable_sort(cand.begin(), cand.end(), [&](int a, int b) { return task_ready(tasks[a]) < task_ready(tasks[b]); });
-    const int n_early = std::min((int)cand.size(), std::max(0, device_cus() - nwg));
-    std::vector<char> early(tasks.size(), 0);
-    std::vector<int2> mt;
-    for (int i = 0; i < n_early; ++i) { mt.push_back(tasks[cand[i]]); early[cand[i]] = 1; }
-    for (int i = 0; i < (int)tasks.size(); ++i)
-        if (!early[i]) mt.push_back(tasks[i]);
+    const OvlOrders o = ovl_orders(C * T, T, f.nwg, device_cus(), c->h_chain[CHAIN_MASK]);
     bsrnn_ctx::OvlTable tb;
-    tb.mask_tasks = nullptr; tb.band_order = nullptr; tb.n_mask = (int)mt.size(); tb.n_ord = n_ord;
-    hipError_t e = hipMalloc((void**)&tb.mask_tasks, (mt.size() + 1) * sizeof(int2));
-    if (e == hipSuccess) e = hipMemcpy(tb.mask_tasks, mt.data(), mt.size() * sizeof(int2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&tb.band_order, (size_t)n_ord * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(tb.band_order, order.data(), (size_t)n_ord * sizeof(int), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (tb.mask_tasks) (void)hipFree(tb.mask_tasks);
-        if (tb.band_order) (void)hipFree(tb.band_order);
-        return fail(BSRNN_EHIP, "overlap tables: %s", hipGetErrorString(e));
-    }
+    tb.n_mask = (int)o.mask_tasks.size(); tb.n_ord = (int)o.band_order.size();
+    hipError_t e = upload_table(&tb.mask_tasks, o.mask_tasks.data(), o.mask_tasks.size() * sizeof(int2), sizeof(int2));
+    if (e == hipSuccess && (e = upload_table(&tb.band_order, o.band_order.data(), o.band_order.size() * sizeof(int))) != hipSuccess) (void)hipFree(tb.mask_tasks);
+    if (e != hipSuccess) return fail(BSRNN_EHIP, "overlap tables: %s", hipGetErrorString(e));
     c->ovl_tables.emplace(key, tb);
     return 0;
 }
@@ -777,7 +691,7 @@ int run_model(bsrnn_ctx* c, const float* Xf, float* Yf, float* tap, int C, int T
     if (int rc = ensure_ovl(c, p.f, C, T)) return rc;
     p.Xf = Xf; p.Yf = Yf; p.tap = tap;
     p.state_in = state_in; p.state_out = state_out;
-    p.state_slab = (size_t)2 * 2 * C * c->K * HID;     // one Time block's (h,c) x 2 layers
+    p.state_slab = state_slab_floats(C, c->K);
     const bsrnn_ctx::OvlTable* tb = ovl_table(c, p.f, C, T, s);
     if (tb) run_overlapped(c, p, tb, MS_BANDSPLIT, MS_MASK);
     else
@@ -853,15 +767,19 @@ int finish_call(bsrnn_ctx* c, hipStream_t s, F&& rerun, bool any_policy = false)
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
-int check_ready(bsrnn_ctx* c)
+// The opening of every compute entry point: a context that can compute, on its device.  model: the entry points that run the committed
+// model say which of the two it is, need the weights, and report a range violation that an earlier call left behind.
+int check_device(bsrnn_ctx* c, bool model = false)
 {
     if (!c) return fail(BSRNN_EARG, "null context");
-    if (c->device < 0) return fail(BSRNN_ESTATE, "host-only context (device -1): no compute entry points");
-    if (c->zombie) return fail(BSRNN_ESTATE, "context was destroyed");
-    if (!c->committed) return fail(BSRNN_ESTATE, "bsrnn_commit_params() has not been called");
+    if (c->device < 0 || c->zombie)
+        return fail(BSRNN_ESTATE, !model ? "context cannot compute (host-only or destroyed)"
+                                         : (c->device < 0 ? "host-only context (device -1): no compute entry points" : "context was destroyed"));
+    if (model && !c->committed) return fail(BSRNN_ESTATE, "bsrnn_commit_params() has not been called");
     HIP_TRY(hipSetDevice(c->device));
-    return check_range(c);
+    return model ? check_range(c) : 0;
 }
+int check_ready(bsrnn_ctx* c) { return check_device(c, true); }
 
 // One call at a time per context: an overlapping call from another host thread is refused instead of racing on the
 // workspace.  (Re-entrant on the same thread: bsrnn_evaluate -> bsrnn_separate, stream_step_host -> stream_step.)
@@ -1279,7 +1197,7 @@ int bsrnn_forward_chunk(bsrnn_ctx* c, const float* x, const float* state_in, flo
     const size_t M = (size_t)C * L;
     if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M))) return rc;
     // The re-run reads state_in again (and x through its frame-major copy Xf, as bsrnn_forward): no output may overlap state_in.
-    const size_t ns = (size_t)4 * 2 * C * c->K * HID * sizeof(float), ny = (size_t)C * F2 * L * sizeof(float);
+    const size_t ns = state_floats(C, c->K) * sizeof(float), ny = (size_t)C * F2 * L * sizeof(float);
     if (c->range_policy == BSRNN_RANGE_EXACT && (ranges_overlap(state_in, ns, state_out, ns) || ranges_overlap(state_in, ns, y, ny)))
         return fail(BSRNN_EARG, "bsrnn_forward_chunk: state_out and y must not overlap state_in (a call that leaves the fp16 range is run again from state_in)");
     auto run = [&](bool layout) -> int {
@@ -1311,7 +1229,7 @@ int bsrnn_dual_path(bsrnn_ctx* c, const float* z, float* z_out, const float* sta
     if ((rc = ensure_ws(c, M))) return rc;
     const size_t nz = (size_t)M * K * HID;
     // The re-run copies z in again and reads state_in again: neither may overlap an output of the call.
-    const size_t bz = nz * sizeof(float), bs = (size_t)4 * 2 * C * K * HID * sizeof(float);
+    const size_t bz = nz * sizeof(float), bs = state_floats(C, K) * sizeof(float);
     if (c->range_policy == BSRNN_RANGE_EXACT &&
         (ranges_overlap(z, bz, z_out, bz) || ranges_overlap(z, bz, state_out, bs) ||
          ranges_overlap(state_in, bs, z_out, bz) || ranges_overlap(state_in, bs, state_out, bs)))
@@ -1322,7 +1240,7 @@ int bsrnn_dual_path(bsrnn_ctx* c, const float* z, float* z_out, const float* sta
         Part p = make_part(c, 0, C, T, s);
         p.f = plan_call(c, C, T, false, false);
         p.state_in = state_in; p.state_out = state_out;
-        p.state_slab = (size_t)2 * 2 * C * K * HID;
+        p.state_slab = state_slab_floats(C, K);
         for (int st = MS_BAND0; st <= MS_TIMEFC1; ++st) run_stage(c, p, st);
         HIP_TRY(hipMemcpyAsync(z_out, c->Z0, nz * sizeof(float), hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipGetLastError());
@@ -1355,9 +1273,7 @@ static float* train_scratch(bsrnn_ctx* c, size_t floats)
 
 static int train_args_ok(bsrnn_ctx* c, int32_t N, int32_t L, int32_t IN, int32_t ndir, const char* who)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = check_device(c)) return rc0;
     if (N < 1 || L < 1 || (IN != HID && IN != 2 * HID) || ndir < 1 || ndir > 2 || (int64_t)N * L > (int64_t)1 << 30)
         return fail(BSRNN_EARG, "%s: need N, L >= 1, IN = 64 | 128, ndir = 1 | 2 (got N=%d L=%d IN=%d ndir=%d)", who, N, L, IN, ndir);
     return 0;
@@ -1408,9 +1324,7 @@ int bsrnn_train_reduction_layout(int32_t M, int32_t N1, int32_t N2, int32_t out[
 int bsrnn_adamw_step(bsrnn_ctx* c, float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
                      float eps, float weight_decay, int32_t step, void* stream)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = check_device(c)) return rc0;
     if (!p || !g || !m || !v || n < 0 || step < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
         return fail(BSRNN_EARG, "bsrnn_adamw_step: bad arguments (n=%lld step=%d)", (long long)n, step);
     hipStream_t s = (hipStream_t)stream;
@@ -1425,9 +1339,7 @@ static int adamw_multi(bsrnn_ctx* c, float* const* p, const float* const* g, flo
                        int32_t n_tensors, float lr, double beta1, double beta2, float eps, float weight_decay, int32_t step, float* state,
                        void* stream, const char* who)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = check_device(c)) return rc0;
     if (!p || !g || !m || !v || !sizes || n_tensors < 1 || (!state && step < 1) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
         return fail(BSRNN_EARG, "%s: bad arguments (n_tensors=%d step=%d)", who, n_tensors, step);
     for (int i = 0; i < n_tensors; ++i)
@@ -1470,9 +1382,7 @@ int bsrnn_adamw_step_multi_dev(bsrnn_ctx* c, float* const* p, const float* const
 int bsrnn_linear_train_forward(bsrnn_ctx* c, const float* x, int32_t ldx, const float* w, const float* b, float* y, int32_t ldy,
                                int32_t M, int32_t K, int32_t N, int32_t leaky, void* stream)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = check_device(c)) return rc0;
     if (!x || !w || !b || !y || M < 1 || K < 1 || N < 1 || ldx < K || ldy < N)
         return fail(BSRNN_EARG, "bsrnn_linear_train_forward: bad arguments (M=%d K=%d N=%d ldx=%d ldy=%d)", M, K, N, ldx, ldy);
     hipStream_t s = (hipStream_t)stream;
@@ -1486,9 +1396,7 @@ int bsrnn_linear_train_backward(bsrnn_ctx* c, const float* x, int32_t ldx, const
                                 const float* dy, int32_t lddy, float* dx, int32_t lddx, float* dw, float* db,
                                 int32_t M, int32_t K, int32_t N, int32_t leaky, void* stream)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = check_device(c)) return rc0;
     if (!x || !w || !dy || !dw || !db || (leaky && !y) || M < 1 || K < 1 || N < 1 || ldx < K || lddy < N || (leaky && ldy < N) || (dx && lddx < K))
         return fail(BSRNN_EARG, "bsrnn_linear_train_backward: bad arguments (M=%d K=%d N=%d)", M, K, N);
     hipStream_t s = (hipStream_t)stream;
@@ -1506,9 +1414,7 @@ int bsrnn_linear_group_train_forward(bsrnn_ctx* c, int32_t n, const float* const
                                      const float* const* b, float* const* y, const int32_t* ldy, const int32_t* K, const int32_t* N,
                                      int32_t M, int32_t leaky, void* stream)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = check_device(c)) return rc0;
     if (n < 1 || n > 4096 || !x || !ldx || !w || !b || !y || !ldy || !K || !N || M < 1) return fail(BSRNN_EARG, "bsrnn_linear_group_train_forward: bad arguments");
     std::vector<LinearJob> jobs((size_t)n);
     for (int i = 0; i < n; ++i) {
@@ -1530,9 +1436,7 @@ int bsrnn_linear_group_train_backward(bsrnn_ctx* c, int32_t n, const float* cons
                                       float* const* dx, const int32_t* lddx, float* const* dw, float* const* db,
                                       const int32_t* K, const int32_t* N, int32_t M, int32_t leaky, void* stream)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = check_device(c)) return rc0;
     if (n < 1 || n > 4096 || !x || !ldx || !w || !dy || !lddy || !dx || !lddx || !dw || !db || !K || !N || M < 1 || (leaky && (!y || !ldy)))
         return fail(BSRNN_EARG, "bsrnn_linear_group_train_backward: bad arguments");
     std::vector<LinearJob> jobs((size_t)n);
@@ -1558,9 +1462,7 @@ int bsrnn_linear_group_train_backward(bsrnn_ctx* c, int32_t n, const float* cons
 // --------------------------------------------------------------------------- STFT sandwich
 int bsrnn_stft(bsrnn_ctx* c, const float* wave, float* x, int32_t R, int64_t n, void* stream)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = check_device(c)) return rc0;
     if (!wave || !x || R < 1 || n <= NFFT / 2) return fail(BSRNN_EARG, "bsrnn_stft: need n > 1024 samples (reflect padding), got %lld", (long long)n);
     hipStream_t s = (hipStream_t)stream;
     ENTER_CALL(c, s);
@@ -1575,9 +1477,7 @@ int bsrnn_stft(bsrnn_ctx* c, const float* wave, float* x, int32_t R, int64_t n, 
 
 int bsrnn_istft(bsrnn_ctx* c, const float* y, float* wave_out, int32_t R, int32_t T, void* stream)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = check_device(c)) return rc0;
     if (!y || !wave_out || R < 1 || T < 2) return fail(BSRNN_EARG, "bsrnn_istft: need T >= 2 frames");
     hipStream_t s = (hipStream_t)stream;
     ENTER_CALL(c, s);
@@ -1594,9 +1494,7 @@ int bsrnn_istft(bsrnn_ctx* c, const float* y, float* wave_out, int32_t R, int32_
 
 int bsrnn_istft_backward(bsrnn_ctx* c, const float* dwave, float* dy, int32_t R, int32_t T, void* stream)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (c->device < 0 || c->zombie) return fail(BSRNN_ESTATE, "context cannot compute (host-only or destroyed)");
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = check_device(c)) return rc0;
     if (!dwave || !dy || R < 1 || T < 2) return fail(BSRNN_EARG, "bsrnn_istft_backward: need T >= 2 frames");
     hipStream_t s = (hipStream_t)stream;
     ENTER_CALL(c, s);
@@ -1625,27 +1523,20 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
         ranges_overlap(wave, (size_t)R * n * sizeof(float), wave_out, (size_t)R * out_len * sizeof(float)))
         return fail(BSRNN_EARG, "bsrnn_separate: wave_out must not overlap wave (a call that leaves the fp16 range is run again from wave)");
 
-    // Rows are independent, so the batch is cut into `parts` contiguous row blocks that run the whole
-    // stage sequence concurrently on separate streams: the ramps, tails and latency-bound stages of
-    // one block (e.g. the time-axis LSTM occupies 192 of 256 CUs) overlap matrix work of the other.
+    // The batch as concurrent row blocks on separate streams (how many, and which rows: row_block_count, plan_host.h).
     // Part j starts one stage behind part j-1 so that they sit in different stages.
-    // (one block while the time-axis launch of the whole batch is one round of workgroups - eight sequences each from 1 024 sequences on -,
-    //  two from there: 128 / 160 rows 1.75 / 2.26 -> 1.73 / 2.18 ms with one block, 192 / 256 rows 2.59 / 3.43 ms with two against 2.72 / 3.47)
     const Flow whole = plan_call(c, R, T, false, true);
-    int parts = R >= 128 && whole.nwg > device_cus() ? 2 : 1;
-    if (R < 2 * parts || (int64_t)R * T < 2048) parts = 1;
+    const int parts = row_block_count(R, T, whole.nwg, device_cus());
+    const RowBlocks rb = row_blocks(R, T, parts);
     if (parts > 1 && (rc = ensure_streams(c, parts))) return rc;
     Part pt[MAX_PARTS];
-    {   // task tables of every row block of this call, made before any launch: one call never evicts a table it needs itself
-        int ms[MAX_PARTS];
-        for (int j = 0; j < parts; ++j) ms[j] = ((int)((int64_t)R * (j + 1) / parts) - (int)((int64_t)R * j / parts)) * T;
-        if ((rc = ensure_tasks(c, ms, parts))) return rc;
-        if (parts == 1 && (rc = ensure_ovl(c, whole, R, T))) return rc;
-    }
+    // task tables of every row block of this call, made before any launch: one call never evicts a table it needs itself
+    if ((rc = ensure_tasks(c, rb.ms, parts))) return rc;
+    if (parts == 1 && (rc = ensure_ovl(c, whole, R, T))) return rc;
     for (int j = 0; j < parts; ++j) {
-        const int r0 = (int)((int64_t)R * j / parts), r1 = (int)((int64_t)R * (j + 1) / parts);
-        pt[j] = make_part(c, r0, r1 - r0, T, parts > 1 ? c->aux[j] : s, j);
-        if (j && pt[j].band_flags < pt[j - 1].band_flags + 2 * (((size_t)pt[j - 1].C * T + 15) / 16))
+        const int r0 = rb.r0[j];
+        pt[j] = make_part(c, r0, rb.r0[j + 1] - r0, T, parts > 1 ? c->aux[j] : s, j);
+        if (j && row_blocks_share_flags(rb, T, j))
             return fail(BSRNN_ESTATE, "row blocks %d and %d would share a hand-over flag pair (internal error)", j - 1, j);
         pt[j].wave = wave + (size_t)r0 * n; pt[j].n = n;
         pt[j].wave_out = wave_out + (size_t)r0 * out_len;
@@ -1681,23 +1572,11 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
 // the time-axis LSTM state carried (the model is causal along time; the band-axis blocks see one frame at a time) -> segment iSTFT with
 // the overlap-add tail carried.  Workspace, task tables and carry are those of one segment.
 
-// Clip samples [*lo, *hi] that the STFT of frames [ta, te) reads, reflections included: frame t covers t*1024 - 1024 .. t*1024 + 1023,
-// an index below 0 reflects to at most 1024 (< n), one above n - 1 to 2 (n - 1) - index - for the clip's last frame down to one sample
-// in front of the frame's own first when n is a multiple of 1024 (never below 1: n > 1024).
-static void segment_window(int64_t n, int ta, int te, int64_t* lo, int64_t* hi)
-{
-    const int64_t a = (int64_t)ta * HOPS - HOPS, b = (int64_t)(te - 1) * HOPS + HOPS - 1;
-    int64_t l = std::max<int64_t>(a, 0), h = std::min<int64_t>(b, n - 1);
-    if (a < 0) h = std::max<int64_t>(h, std::min<int64_t>(-a, n - 1));
-    if (b >= n) l = std::min<int64_t>(l, 2 * (n - 1) - b);
-    *lo = l; *hi = h;
-}
-
 static int ensure_long_carry(bsrnn_ctx* c, int R)
 {
     bsrnn_ctx::LongForm& lf = c->lf;
     if (R <= lf.rows) return 0;
-    const size_t nstate = (size_t)4 * 2 * R * c->K * HID, ncarry = (size_t)R * HOPS;
+    const size_t nstate = state_floats(R, c->K), ncarry = (size_t)R * HOPS;
     float* p = nullptr;
     ++g_dbg[DBG_ALLOC];
     HIP_TRY(hipMalloc((void**)&p, 2 * (nstate + ncarry) * sizeof(float)));
@@ -1708,8 +1587,8 @@ static int ensure_long_carry(bsrnn_ctx* c, int R)
     return 0;
 }
 
-// Staging of the host-buffer entry point for R rows and segments of `seg` frames.  A window holds at most (seg + 1) * 1024 + 1 samples per
-// row (segment_window), a block at most seg hops; the caller has nothing of its own in flight on them (the entry point is synchronous).
+// Staging of the host-buffer entry point for R rows and segments of `seg` frames (window and block sizes: plan_host.h); the caller has
+// nothing of its own in flight on them (the entry point is synchronous).
 static int ensure_long_staging(bsrnn_ctx* c, int R, int seg)
 {
     bsrnn_ctx::LongForm& lf = c->lf;
@@ -1717,7 +1596,7 @@ static int ensure_long_staging(bsrnn_ctx* c, int R, int seg)
     for (int k = 0; k < 2; ++k)
         for (hipEvent_t* e : {&lf.ev_h2d[k], &lf.ev_comp[k], &lf.ev_d2h[k]})
             if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    const size_t in = (size_t)R * (seg + 2) * HOPS, out = (size_t)R * seg * HOPS;
+    const size_t in = (size_t)R * staging_window_floats(seg), out = (size_t)R * staging_block_floats(seg);
     if (in <= lf.in_floats && out <= lf.out_floats) return 0;
     const size_t in_new = std::max(in, lf.in_floats), out_new = std::max(out, lf.out_floats);
     HIP_TRY(hipStreamSynchronize(lf.copy));
@@ -1760,18 +1639,8 @@ static int long_segments(bsrnn_ctx* c, const float* wave, float* wave_out, int R
     bsrnn_ctx::LongForm& lf = c->lf;
     const int nseg = (T + seg - 1) / seg;
     const int64_t out_len = (int64_t)(T - 1) * HOPS;
-    struct Cut { int ta, te, hop0, nh; int64_t lo, wl; };
-    auto cut = [&](int i) {
-        Cut q;
-        q.ta = i * seg; q.te = std::min(T, q.ta + seg);
-        q.hop0 = std::max(q.ta - 1, 0); q.nh = q.te - 1 - q.hop0;
-        int64_t hi;
-        segment_window(n, q.ta, q.te, &q.lo, &hi);
-        q.wl = hi - q.lo + 1;
-        return q;
-    };
     auto stage_in = [&](int i) -> int {
-        const Cut q = cut(i);
+        const SegmentCut q = segment_cut(n, T, seg, i);
         const int b = i & 1;
         if ((size_t)R * q.wl > lf.in_floats) return fail(BSRNN_ESTATE, "segment window larger than its staging block (internal error)");
         if (i >= 2) { HIP_TRY(hipEventSynchronize(lf.ev_h2d[b])); HIP_TRY(hipStreamWaitEvent(lf.copy, lf.ev_comp[b], 0)); }
@@ -1781,7 +1650,7 @@ static int long_segments(bsrnn_ctx* c, const float* wave, float* wave_out, int R
         return 0;
     };
     auto take_out = [&](int i) -> int {
-        const Cut q = cut(i);
+        const SegmentCut q = segment_cut(n, T, seg, i);
         if (!q.nh) return 0;
         HIP_TRY(hipEventSynchronize(lf.ev_d2h[i & 1]));
         const size_t len = (size_t)q.nh * HOPS;
@@ -1789,10 +1658,10 @@ static int long_segments(bsrnn_ctx* c, const float* wave, float* wave_out, int R
         return 0;
     };
     int rc;
-    HIP_TRY(hipMemsetAsync(lf.state[0], 0, (size_t)4 * 2 * R * c->K * HID * sizeof(float), s));      // the clip starts from zero state (and needs no carry)
+    HIP_TRY(hipMemsetAsync(lf.state[0], 0, state_floats(R, c->K) * sizeof(float), s));      // the clip starts from zero state (and needs no carry)
     if (host && (rc = stage_in(0))) return rc;
     for (int i = 0; i < nseg; ++i) {
-        const Cut q = cut(i);
+        const SegmentCut q = segment_cut(n, T, seg, i);
         const int b = i & 1;
         const float* src = wave;
         float* out = wave_out + (size_t)q.hop0 * HOPS;
@@ -1829,25 +1698,31 @@ static int long_segments(bsrnn_ctx* c, const float* wave, float* wave_out, int R
 static int long_prepare(bsrnn_ctx* c, int R, int T, int seg, const char* who)
 {
     if ((int64_t)R * seg > INT32_MAX / 2) return fail(BSRNN_EARG, "%s: %d rows x %d frames is too many frame rows for one segment", who, R, seg);
-    int rc;
+    int rc, ms[2];
     if ((rc = ensure_ws(c, (size_t)R * seg))) return rc;
-    int ms[2] = {R * seg, R * (T % seg)};
-    if ((rc = ensure_tasks(c, ms, ms[1] ? 2 : 1))) return rc;
+    if ((rc = ensure_tasks(c, ms, long_frame_rows(R, T, seg, ms)))) return rc;
     return ensure_long_carry(c, R);
+}
+// What both entry points check before anything else (who: the entry point's name).  The overlap is refused whatever the range policy:
+// the clip's reflected tail (and every later segment) is read after early hops have been written.
+static int long_check(bsrnn_ctx* c, const float* wave, float* wave_out, int R, int64_t n, int seg_frames, const char* who)
+{
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!wave || !wave_out || R < 1 || n <= NFFT / 2)
+        return fail(BSRNN_EARG, "%s: need two buffers, R >= 1 and n > 1024 samples, got R = %d, n = %lld", who, R, (long long)n);
+    if (seg_frames < 1) return fail(BSRNN_EARG, "%s: seg_frames = %d (at least one frame per segment)", who, seg_frames);
+    if (int rc = check_ready(c)) return rc;
+    const int T = 1 + (int)(n / HOPS);
+    if (ranges_overlap(wave, (size_t)R * n * sizeof(float), wave_out, (size_t)R * (T - 1) * HOPS * sizeof(float)))
+        return fail(BSRNN_EARG, "%s: wave_out must not overlap wave (later segments read the waveform after earlier hops are written)", who);
+    return 0;
 }
 
 int bsrnn_separate_long(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, int64_t n, int32_t seg_frames, void* stream)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (!wave || !wave_out || R < 1 || n <= NFFT / 2)
-        return fail(BSRNN_EARG, "bsrnn_separate_long: need two buffers, R >= 1 and n > 1024 samples, got R = %d, n = %lld", R, (long long)n);
-    if (seg_frames < 1) return fail(BSRNN_EARG, "bsrnn_separate_long: seg_frames = %d (at least one frame per segment)", seg_frames);
-    int rc = check_ready(c);
+    int rc = long_check(c, wave, wave_out, R, n, seg_frames, "bsrnn_separate_long");
     if (rc) return rc;
     const int T = 1 + (int)(n / HOPS);
-    // whatever the range policy: the clip's reflected tail (and every later segment) is read after early hops have been written
-    if (ranges_overlap(wave, (size_t)R * n * sizeof(float), wave_out, (size_t)R * (T - 1) * HOPS * sizeof(float)))
-        return fail(BSRNN_EARG, "bsrnn_separate_long: wave_out must not overlap wave (later segments read the waveform after earlier hops are written)");
     if (seg_frames >= T) return bsrnn_separate(c, wave, wave_out, R, n, stream);       // one segment IS the one-shot call: bit-identical by construction
     hipStream_t s = (hipStream_t)stream;
     ENTER_CALL(c, s);
@@ -1857,16 +1732,10 @@ int bsrnn_separate_long(bsrnn_ctx* c, const float* wave, float* wave_out, int32_
 
 int bsrnn_separate_long_host(bsrnn_ctx* c, const float* wave_host, float* wave_out_host, int32_t R, int64_t n, int32_t seg_frames)
 {
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (!wave_host || !wave_out_host || R < 1 || n <= NFFT / 2)
-        return fail(BSRNN_EARG, "bsrnn_separate_long_host: need two buffers, R >= 1 and n > 1024 samples, got R = %d, n = %lld", R, (long long)n);
-    if (seg_frames < 1) return fail(BSRNN_EARG, "bsrnn_separate_long_host: seg_frames = %d (at least one frame per segment)", seg_frames);
-    int rc = check_ready(c);
+    int rc = long_check(c, wave_host, wave_out_host, R, n, seg_frames, "bsrnn_separate_long_host");
     if (rc) return rc;
     const int T = 1 + (int)(n / HOPS);
     const size_t out_floats = (size_t)R * (T - 1) * HOPS;
-    if (ranges_overlap(wave_host, (size_t)R * n * sizeof(float), wave_out_host, out_floats * sizeof(float)))
-        return fail(BSRNN_EARG, "bsrnn_separate_long_host: wave_out must not overlap wave (later segments read the waveform after earlier hops are written)");
     hipStream_t s = nullptr;
     ENTER_CALL(c, s);
     const int seg = std::min<int>(seg_frames, T);
@@ -1986,7 +1855,7 @@ int bsrnn_evaluate(bsrnn_ctx* c, const float* mix, const float* speech, int32_t 
 
 // --------------------------------------------------------------------------- streaming
 // Device layout of a stream object: two carry sets [buf | prev | state] (see bsrnn_stream), then the per-step scratch [X | Y | chunk | out].
-static size_t stream_carry_floats(const bsrnn_ctx* c, int C) { return (size_t)C * NFFT * 2 + (size_t)4 * 2 * C * c->K * HID; }
+static size_t stream_carry_floats(const bsrnn_ctx* c, int C) { return (size_t)C * NFFT * 2 + state_floats(C, c->K); }
 static size_t stream_total_floats(const bsrnn_ctx* c, int C)
 {
     return 2 * stream_carry_floats(c, C) + (size_t)C * ((size_t)c->LDP * 2 + HOPS * 2) + 4;
@@ -2001,7 +1870,7 @@ int bsrnn_stream_create(bsrnn_ctx* c, int32_t C, bsrnn_stream** out)
     if (!guard_.ok) return guard_.refuse();
     bsrnn_stream* st = new bsrnn_stream();
     st->ctx = c; st->C = C;
-    const size_t nstate = (size_t)4 * 2 * C * c->K * HID;
+    const size_t nstate = state_floats(C, c->K);
     const size_t total = stream_total_floats(c, C);
     float* p = nullptr;
     ++g_dbg[DBG_ALLOC];
@@ -2267,7 +2136,7 @@ int bsrnn_stream_get_state(bsrnn_stream* st, float* state_host)
     if (!st || !state_host) return fail(BSRNN_EARG, "null argument");
     HIP_TRY(hipSetDevice(st->ctx->device));
     HIP_TRY(hipDeviceSynchronize());
-    const size_t nstate = (size_t)4 * 2 * st->C * st->ctx->K * HID;
+    const size_t nstate = state_floats(st->C, st->ctx->K);
     HIP_TRY(hipMemcpy(state_host, st->state[st->cur], nstate * sizeof(float), hipMemcpyDeviceToHost));
     return check_range(st->ctx);          // steps made under the 'deferred' policy report a range violation here (or at the next call / bsrnn_sync)
 }

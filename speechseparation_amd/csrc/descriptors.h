@@ -1,4 +1,5 @@
-// Plain-data descriptors that the host fills at commit time (commit_host.h) and the kernels read (kernels.h includes this file).
+// Plain-data descriptors that the host fills at commit time (commit_host.h) and the kernels read (kernels.h includes this file),
+// and the constants that the host-side call plan (plan_host.h) shares with the kernels.
 // No HIP here: a host compiler takes it as it is.
 #pragma once
 
@@ -11,6 +12,10 @@
 namespace bsrnn {
 
 constexpr int HID = 64;       // band_features (bsrnn.py:60)
+constexpr int NFFT = 2048;    // infer.py:31
+constexpr int HOPS = 1024;
+constexpr int NBINS = 1025;
+constexpr int F2 = 2050;      // interleaved re/im columns
 
 // ------------------------------------------------------------------ grouped linear layers
 // One job = one nn.Linear of one band.  A launch runs every job of one "layer slot" of the
@@ -36,6 +41,10 @@ struct GemmTile { int job, tile; };
 // bf16 = plain bf16 operands, one MFMA term, in the fused MLP chains (BASELINE config 2 as it is named; no range limit, 8 significant
 // bits); the few launches outside the chains (a band too wide for the LDS image, the block fc of the BSRNN_BAND_FC=gemm flow) then run fp16x2.
 enum GemmMode { GEMM_F32 = 0, GEMM_FP16 = 1, GEMM_FP16X2 = 2, GEMM_BF16 = 3 };
+// How the recurrent layers evaluate their gate products (environment BSRNN_LSTM = f32 | fp16x2, read once).
+enum LstmMode { LSTM_F32 = 0, LSTM_FP16X2 = 2 };
+// A call of at most this many frame rows runs its per-band layers on the GEMV kernels (gemv.hip; plan_call, plan_host.h)
+constexpr int GEMV_MAX_FRAME_ROWS = 4;
 
 // ------------------------------------------------------------------ fused per-band MLP chains (mlp_chain.hip)
 // One workgroup = one band x one block of frame rows, all five Linear layers of BandSplit (bsrnn.py:404-415) or of
@@ -75,6 +84,9 @@ struct ChainDesc {
 };
 // rows per workgroup of a descriptor (32 RT GR; 256 for a constant band)
 BSRNN_HD inline int chain_rows(const ChainDesc& d) { return d.constant ? 256 : (d.RT >= 3 ? 16 * d.RT : 32 * d.RT * (8 / d.NW)); }   // RT >= 3: row tiles of 16 (16 x 16 x 32 geometry: 48 or 80 rows)
+
+// Overlapped dual path (kernels.h): a progress word is epoch << OVL_EPOCH_SHIFT | groups of four steps done
+constexpr int OVL_EPOCH_SHIFT = 12;            // groups of four steps per launch < 4096 (frames < 16 384: plan_call checks, plan_host.h)
 
 // positions (bands) the LDS images of the band-block kernel for a few sequences hold (launch_band_block_small, kernels.h); longer
 // band tables take the general kernels

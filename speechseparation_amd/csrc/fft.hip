@@ -705,7 +705,7 @@ void launch_stream_block_synthesis(const FftTables& tb, const float* Y, const fl
 // Analysis: padded sample i of frame t is sample t*1024 + i - 1024 of the WHOLE clip, reflected at 0 and at n - 1 (never at a segment
 // edge).  `src` is either the whole clip (base = 0, stride = n) or a staged window of it that starts at clip sample `base` (rows `stride`
 // floats apart); `base` is subtracted after the reflection, and the caller makes the window hold every index the segment touches
-// (api.hip: segment_window).  Rows of X are segment-local: X[(r * (te - ta) + (t - ta)) * ld].
+// (plan_host.h: segment_window).  Rows of X are segment-local: X[(r * (te - ta) + (t - ta)) * ld].
 __global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_segment_kernel(FftTables tb, const float* __restrict__ wave, float* __restrict__ X,
                                                                          int64_t n, int64_t base, int64_t stride, int ta, int te, int sch)
 {

@@ -7,11 +7,6 @@
 
 namespace bsrnn {
 
-constexpr int NFFT = 2048;    // infer.py:31
-constexpr int HOPS = 1024;
-constexpr int NBINS = 1025;
-constexpr int F2 = 2050;      // interleaved re/im columns
-
 // ------------------------------------------------------------------ grouped linear layers (GemmJob: descriptors.h)
 enum GemmEpilogue {
     EPI_LINEAR = 0,      // y = acc + b
@@ -37,8 +32,7 @@ struct GemmLaunch {
 };
 void launch_gemm(const GemmLaunch& g, hipStream_t stream);
 // Small-M path (gemv.hip): the same launch on the vector ALU in exact fp32, for calls of a few frame rows (the one-frame
-// streaming step: C rows).  api.hip uses it for every per-layer launch of a call with C * L <= GEMV_MAX_FRAME_ROWS.
-constexpr int GEMV_MAX_FRAME_ROWS = 4;
+// streaming step: C rows).  api.hip uses it for every per-layer launch of a call with C * L <= GEMV_MAX_FRAME_ROWS (descriptors.h).
 void launch_gemv(const GemmLaunch& g, hipStream_t stream);
 // How the Linear layers are evaluated: GemmMode (descriptors.h), from the environment BSRNN_GEMM, read once per process.
 int gemm_mode();
@@ -50,7 +44,7 @@ constexpr int GEMM_BM = 128;
 struct ChainLaunch {
     const ChainDesc* desc;   // device array
     const int2* tasks;       // device array [n_tasks]: (descriptor index, first frame row) of every workgroup, in dispatch order
-    int n_tasks;             //   (built per M by build_chain_tasks(), api.hip: descriptor after descriptor, all row blocks of a band together)
+    int n_tasks;             //   (built per M by build_chain_tasks(), plan_host.h: descriptor after descriptor, all row blocks of a band together)
     int M;
     const float* Xin; int ldx;       // SPLIT: spectrum rows; MASK: Z rows
     float* P; int ldp;               // SPLIT: written (bandFCs_pre output = the mask's residual); MASK: read
@@ -83,7 +77,7 @@ void launch_mlp_chain(const ChainLaunch& g, int chain, hipStream_t stream);
 // a graph - api.hip - so by-value epochs cannot go stale; every 2^18 calls the host drains the device and starts the epochs again).
 struct OvlProducer { int* resident; int* prog; int base; };                          // base = epoch << OVL_EPOCH_SHIFT
 struct OvlConsumer { const int* prog; int T; int spin_limit; const int* order; int base; int wg_shift; };   // spin_limit: 100 MHz ticks a wait may last; wg_shift: log2 of the producer's sequences per workgroup
-constexpr int OVL_EPOCH_SHIFT = 12;            // groups of four steps per launch < 4096 (frames < 16 384: api.hip checks)   // order (band launch): dispatch ordinal -> tile of 16 sequences, by the time its frames are ready
+// OVL_EPOCH_SHIFT: descriptors.h.  order (band launch): dispatch ordinal -> tile of 16 sequences, by the time its frames are ready
 constexpr int OVL_SPIN_LIMIT = 20000000;       // 100 MHz ticks (s_memrealtime) before a wait gives up: 200 ms - a healthy wait lasts as long as a
                                                // time-axis launch (0.1 ... a few ms); under a tool that serialises kernels (rocprofv3 --pmc) the
                                                // producer never runs beside the consumer: the call falls back after this long, once per context
@@ -141,8 +135,7 @@ void launch_band_pair(const float* z, float* hb0, float* hb1, const void* w0pk16
 // fp16x2 only; 1 <= N <= 8 sequences of 1 <= L <= BS_MAXL steps (api.hip decides when a call takes it).
 void launch_band_block_small(const float* zin, float* zout, const void* w0pk16, const float* bias0, const void* w1pk16, const float* bias1,
                              const void* fc16, const float* fcb, int N, int L, int* range_flag, hipStream_t stream);
-// How the recurrent layers evaluate their gate products (environment BSRNN_LSTM = f32 | fp16x2, read once).
-enum LstmMode { LSTM_F32 = 0, LSTM_FP16X2 = 2 };
+// How the recurrent layers evaluate their gate products: LstmMode (descriptors.h), from the environment BSRNN_LSTM, read once.
 int lstm_mode();
 // Time-axis LSTM, both layers pipelined in one launch, causal with state carry.
 //   zin/hout [R][T][K][64]; sequences n = r*K + k;  wpk packed [2 layer][4 wave][128 k][64 lane]

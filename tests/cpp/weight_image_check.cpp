@@ -6,41 +6,16 @@
 //   | per chain: u64 n, n x {ChainLayer[5], i32 nbias .. zpad (11), u64 wstream, bias, i64 cost} | per block: u64[13] BlockSegs
 // and prints one JSON line: arena size, fused, build time, the segment offsets and, per chain and band, bsrnn_chain_geometry's answer.
 #include "commit_host.h"
+#include "weight_file.h"
 #include <chrono>
-#include <cstdlib>
-#include <map>
 using namespace bsrnn;
-
-static void die(const char* why) { fprintf(stderr, "weight_image_check: %s\n", why); exit(2); }
 
 int main(int argc, char** argv)
 {
     if (argc != 8) die("usage");
-    FILE* f = fopen(argv[1], "rb");
-    if (!f) die("cannot open the weight file");
-    auto rd = [&](void* p, size_t n) { if (fread(p, 1, n, f) != n) die("truncated weight file"); };
-    char magic[8];
-    uint32_t nb, nt;
-    rd(magic, 8);
-    if (memcmp(magic, "BSRNNW01", 8)) die("bad magic");
-    rd(&nb, 4);
-    std::vector<int> widths(nb);
-    for (uint32_t i = 0; i < nb; ++i) { uint32_t w; rd(&w, 4); widths[i] = (int)w; }
-    rd(&nt, 4);
-    std::map<std::string, std::vector<float>> params;
-    for (uint32_t t = 0; t < nt; ++t) {
-        uint32_t kl, nd;
-        rd(&kl, 4);
-        std::string key(kl, ' ');
-        rd(&key[0], kl);
-        rd(&nd, 4);
-        uint64_t n = 1, d;
-        for (uint32_t i = 0; i < nd; ++i) { rd(&d, 8); n *= d; }
-        std::vector<float>& v = params[key];
-        v.resize(n);
-        rd(v.data(), 4 * n);
-    }
-    fclose(f);
+    const WeightFile wf = read_weight_file(argv[1]);
+    const std::vector<int>& widths = wf.widths;
+    const auto& params = wf.params;
     const CommitKnobs kn = {atoi(argv[2]), atoi(argv[3]) != 0, atoi(argv[4]) != 0, atoi(argv[5]) != 0, atoi(argv[6]) != 0};
     const BandColumns bc = band_columns(widths);
     const auto t0 = std::chrono::steady_clock::now();
@@ -48,7 +23,7 @@ int main(int argc, char** argv)
                                               widths, bc.aoff, bc.poff, kn);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 
-    f = fopen(argv[7], "wb");
+    FILE* f = fopen(argv[7], "wb");
     if (!f) die("cannot open the dump file");
     auto w64 = [&](uint64_t v) { fwrite(&v, 8, 1, f); };
     auto w32 = [&](int32_t v) { fwrite(&v, 4, 1, f); };

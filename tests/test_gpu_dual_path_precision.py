@@ -1,7 +1,7 @@
 """Every dual-path kernel variant at the fp32 rounding bound, with carried state in and out.
 
 BSRNN.dual_path(z, state) (bsrnn_dual_path: the four recurrent blocks of the model's own schedule) runs in a child process per
-knob set (the knobs of plan_call, csrc/api.hip, are read once per process) at the smallest shapes that cross each decision and tile
+knob set (the knobs of plan_call, csrc/plan_host.h, are read once per process by csrc/api.hip) at the smallest shapes that cross each decision and tile
 edge of the band-axis and time-axis kernels of csrc/lstm.hip.  Both outputs, z_out and state_out, are held on all rows to the
 criterion of test_gpu_parity.py::test_precision_is_at_fp32_rounding_level,
     e_hip <= 3 * e_f32 + 1e-7,

@@ -164,7 +164,7 @@ def test_progress_word_epochs_start_again(sd_hot, models):
 
 def test_a_batch_whose_time_axis_launch_takes_eight_sequences_per_workgroup_overlaps_too(models):
     """100 rows x 12 bands = 1 200 sequences: four per workgroup would be 300 workgroups (more than one per CU), so the time-axis launches run
-    eight per workgroup (api.hip::plan_call, Flow::seqs) - 150 workgroups, inside the overlap's range: the consumers then map sequences to producer
+    eight per workgroup (plan_host.h::plan_call, Flow::seqs) - 150 workgroups, inside the overlap's range: the consumers then map sequences to producer
     workgroups eight at a time (OvlConsumer::wg_shift).  Equal to the serial flow."""
     from speechseparation_amd import weights
     ovl, ser = models
