@@ -175,6 +175,7 @@ def test_istft_backward_is_the_transpose_of_torch_istft():
     assert _rel(wg, w) < 2e-6
     # torch gives the imaginary parts of bins 0 and 1024 no gradient either (irfft ignores them)
     assert float(y.grad[:, 1, :].abs().max()) == 0.0 and float(yg.grad[:, 1, :].abs().max()) == 0.0
+    assert float(y.grad[:, 2049, :].abs().max()) == 0.0 and float(yg.grad[:, 2049, :].abs().max()) == 0.0
     print("iSTFT backward: relative error %.1e" % _rel(yg.grad, y.grad))
     assert _rel(yg.grad, y.grad) < 1e-5
 
