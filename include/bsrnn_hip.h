@@ -277,6 +277,29 @@ int  bsrnn_istft(bsrnn_ctx* ctx, const float* y_dev, float* wave_out_dev, int32_
  * for the imaginary parts of bins 0 and 1024). */
 int  bsrnn_istft_backward(bsrnn_ctx* ctx, const float* dwave_dev, float* dy_dev, int32_t R, int32_t T, void* stream);
 int  bsrnn_separate(bsrnn_ctx* ctx, const float* wave_dev, float* wave_out_dev, int32_t R, int64_t n, void* stream);
+/* bsrnn_separate_ragged = bsrnn_separate for R clips of DIFFERENT lengths in one call (a validation set, a request queue): wave_dev holds R
+ * rows wave_stride floats apart, row r holds lens_host[r] samples, 1024 < lens_host[r] <= wave_stride (what lies behind them in the row is
+ * never read).  With T_r = 1 + lens[r] / 1024 and Tmax = the largest T_r, wave_out_dev is [R, (Tmax-1)*1024]: row r holds the
+ * (lens[r] / 1024) * 1024 samples bsrnn_separate gives for that clip alone (reflect padding at the clip's own end, not at the stride or at
+ * Tmax), then zeros to the end of the row.  The model is causal along time, its band-axis blocks see one frame at a time and rows are
+ * independent, so only the STFT and the iSTFT know the lengths: frames t >= T_r of a row enter the model as zero spectra and leave it as
+ * zeros, whatever an earlier call left in the workspace.
+ *   - Equal lengths: with all lengths n and wave_stride = n the samples are bit-identical to bsrnn_separate(R, n) wherever that call runs
+ *     as one row block (the same plan, the same arithmetic per frame).  The call always runs as ONE row block: the two concurrent row
+ *     blocks of bsrnn_separate for R >= 128 are not reproduced (as in bsrnn_separate_long).
+ *   - Unequal lengths: a row agrees with bsrnn_separate of that clip alone to rounding (the kernels are chosen for R x Tmax, not 1 x T_r).
+ *   - Cost: the model runs on all R * Tmax frame rows - padding is paid for, so batch clips of similar length (the Python layer's
+ *     separate_many does: spec.ragged_buckets).  Memory: a workspace of R * Tmax frame rows.
+ *   - lens_host is ordinary host memory and may be reused as soon as the call returns, under either range policy; the lengths (and the
+ *     call's task tables) travel in one grow-only block of the context, made at first use and when R or R * Tmax outgrows it
+ *     (bsrnn_debug_counter(0)); a call that fits allocates nothing.
+ *   - Range policy as bsrnn_separate: under BSRNN_RANGE_EXACT a call that left the fp16 range is run again in exact fp32 from the same
+ *     waveform and the same lengths, so wave_out_dev must not overlap the R * wave_stride floats of wave_dev (BSRNN_EARG); under
+ *     BSRNN_RANGE_DEFERRED it is not checked.
+ * BSRNN_EARG, before any device work (also on a host-only context, in front of its BSRNN_ESTATE): a null ctx, wave_dev, lens_host or
+ * wave_out_dev; R < 1; a length <= 1024 or > wave_stride (the text names the row and the value). */
+int  bsrnn_separate_ragged(bsrnn_ctx* ctx, const float* wave_dev, int64_t wave_stride, const int64_t* lens_host,
+                           float* wave_out_dev, int32_t R, void* stream);
 
 /* ---- long-form separation: bsrnn_separate in segments, bounded memory ---------------------
  * bsrnn_separate's result for a clip of any length from a workspace of one segment.  Shapes as bsrnn_separate: wave [R, n] ->

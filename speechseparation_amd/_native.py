@@ -25,6 +25,7 @@ SYMBOLS = [
     "bsrnn_linear_group_train_forward", "bsrnn_linear_group_train_backward", "bsrnn_train_reduction_layout",
     "bsrnn_set_range_policy", "bsrnn_get_range_policy", "bsrnn_overlap_state", "bsrnn_debug_peek", "bsrnn_debug_counter",
     "bsrnn_stream_process", "bsrnn_stream_reserve", "bsrnn_separate_long", "bsrnn_separate_long_host", "bsrnn_workspace_rows",
+    "bsrnn_separate_ragged",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 METRIC_NAMES = ("loss", "sdr", "input_sdr", "sisdr", "l1_time", "l1_re", "l1_im", "separation_db")   # BSRNN_M_* order
@@ -85,6 +86,7 @@ def _load():
         "bsrnn_adamw_step_multi_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, C.c_double, C.c_double, C.c_float, C.c_float, vp]),
         "bsrnn_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, i64, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, i32, vp]),
         "bsrnn_separate": (C.c_int, [vp, vp, vp, i32, i64, vp]),
+        "bsrnn_separate_ragged": (C.c_int, [vp, vp, i64, vp, vp, i32, vp]),
         "bsrnn_separate_long": (C.c_int, [vp, vp, vp, i32, i64, i32, vp]),
         "bsrnn_separate_long_host": (C.c_int, [vp, vp, vp, i32, i64, i32]),
         "bsrnn_workspace_rows": (i64, [vp]),

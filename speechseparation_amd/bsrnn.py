@@ -351,6 +351,75 @@ class BSRNN(nn.Module):
                 _check(_lib.bsrnn_separate_long(ctx, _ptr(w), _ptr(out), R, n, int(segment_frames), _stream_ptr(dev)))
         return out
 
+    def separate_ragged(self, waveform, lengths, out=None):
+        """`separate` for clips of different lengths in one call: waveform [R, n_max], row r holding lengths[r] samples (1024 < lengths[r]
+        <= n_max; what lies behind them in the row is never read) -> [R, (Tmax - 1) * 1024], Tmax = 1 + max(lengths) // 1024.  Row r holds
+        the (lengths[r] // 1024) * 1024 samples `separate` gives for that clip alone (to rounding; bit-identical when all lengths are n_max),
+        then zeros.  The model runs on all R * Tmax frame rows: padding is paid for (include/bsrnn_hip.h, bsrnn_separate_ragged;
+        `separate_many` batches clips of similar length).  `out` as in `separate`: contiguous float32 of exactly the result's shape on the
+        call's device, not overlapping the waveform."""
+        if not isinstance(waveform, torch.Tensor) or waveform.dim() != 2:
+            raise ValueError("separate_ragged: expected waveform [R, n_max], got %s" % (
+                tuple(waveform.shape) if isinstance(waveform, torch.Tensor) else type(waveform).__name__,))
+        R, n_max = waveform.shape
+        try:
+            lens = [int(x) for x in lengths]
+        except TypeError:
+            raise ValueError("separate_ragged: lengths must be a sequence of %d ints, got %s" % (R, type(lengths).__name__)) from None
+        if len(lens) != R or R < 1:
+            raise ValueError("separate_ragged: %d lengths for %d rows" % (len(lens), R))
+        for r, n in enumerate(lens):
+            if not _spec.HOP < n <= n_max:
+                raise ValueError("separate_ragged: row %d has %d samples, need 1024 < length <= %d" % (r, n, n_max))
+        shape = (R, (max(lens) // _spec.HOP) * _spec.HOP)
+        if out is not None and not isinstance(out, torch.Tensor):
+            raise ValueError("separate_ragged: out must be a tensor, got %s" % type(out).__name__)
+        dev = self._device_for(waveform)
+        if out is not None and (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError("separate_ragged: out must be a contiguous float32 tensor %s on %s, got %s %s on %s" % (
+                shape, dev, tuple(out.shape), out.dtype, out.device))
+        w = self._prep(waveform, dev)
+        with torch.cuda.device(dev):
+            ctx = self._context(dev)
+            if out is None:
+                out = torch.empty(shape, device=dev, dtype=torch.float32)
+            _check(_lib.bsrnn_separate_ragged(ctx, _ptr(w), n_max, (ctypes.c_int64 * R)(*lens), _ptr(out), R, _stream_ptr(dev)))
+        return out if waveform.is_cuda else out.cpu()
+
+    def separate_many(self, clips, max_rows=64, max_padding=0.25):
+        """`separate` for a list of clips of different lengths, batched: clips are 1-D [n] or 2-D [ch, n] tensors (n > 1024) on the GPU
+        or the CPU.  `spec.ragged_buckets` groups them (longest first; at most `max_rows` rows and a padding share of at most `max_padding`
+        per bucket), each bucket is packed into one [rows, n_max] buffer and runs as ONE `separate_ragged` call.  Returns the results in
+        input order, each [ch, (n // 1024) * 1024] - 1-D for a 1-D clip - on its clip's own device, equal to `separate` of that clip alone
+        to rounding.  max_rows = 64 is the benchmark's batch; max_padding = 0.25 is a default, not a measured optimum."""
+        clips = list(clips)
+        for i, c in enumerate(clips):
+            if not isinstance(c, torch.Tensor) or c.dim() not in (1, 2) or c.shape[-1] <= _spec.HOP or c.shape[0] < 1:
+                raise ValueError("separate_many: clip %d must be a tensor [n] or [ch, n] with n > 1024, got %s" % (
+                    i, tuple(c.shape) if isinstance(c, torch.Tensor) else type(c).__name__))
+        buckets = _spec.ragged_buckets([_spec.n_frames(c.shape[-1]) for c in clips], [1 if c.dim() == 1 else c.shape[0] for c in clips],
+                                       max_rows, max_padding)
+        if not clips:
+            return []
+        dev = next((c.device for c in clips if c.is_cuda), None) or self._device_for(clips[0])
+        results = [None] * len(clips)
+        for bucket in buckets:
+            rows = [1 if clips[i].dim() == 1 else clips[i].shape[0] for i in bucket]
+            lens = [clips[i].shape[-1] for i in bucket]
+            buf = torch.empty((sum(rows), max(lens)), device=dev, dtype=torch.float32)      # (behind a row's end nothing is read)
+            r0 = 0
+            for i, ch, n in zip(bucket, rows, lens):
+                buf[r0:r0 + ch, :n] = clips[i].detach().reshape(ch, n).to(device=dev, dtype=torch.float32)
+                r0 += ch
+            out = self.separate_ragged(buf, [n for ch, n in zip(rows, lens) for _ in range(ch)])
+            r0 = 0
+            for i, ch, n in zip(bucket, rows, lens):
+                y = out[r0:r0 + ch, :(n // _spec.HOP) * _spec.HOP]
+                y = (y[0] if clips[i].dim() == 1 else y).to(clips[i].device, copy=True)
+                results[i] = y.contiguous()
+                r0 += ch
+        return results
+
     def workspace_rows(self, device=None):
         """Frame rows the native context's workspace holds right now (grow-only; 0 before the first call): what `separate` raises to
         R * T and `separate_long` keeps at R * segment_frames (bsrnn_workspace_rows).  `device`: only the context on that device counts."""

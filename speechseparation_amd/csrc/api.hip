@@ -182,6 +182,20 @@ struct bsrnn_ctx {
         // per block: its H2D has completed / the segment that read d_in and wrote d_out is final / its D2H has completed
         hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_d2h[2] = {nullptr, nullptr};
     } lf;
+
+    // Ragged batches (bsrnn_separate_ragged): what the kernels of one call read besides the waveform - the rows' lengths and, for the fused
+    // chains, the task tables of its R * Tmax frame rows - travels as ONE block [R int64 lengths | split tasks | mask tasks], copied on the
+    // caller's stream into `d` in front of the call's kernels.  (Not the table cache above: a ragged caller meets another Tmax with nearly
+    // every call, and a cached table per frame-row count would make first-use work the rule and flush the bounded cache.)  The copy reads a
+    // pinned mirror; there are RG_SLOTS of them, used in turn, and mirror k is written again only when the copy that read it has completed
+    // (ev[k]), so the caller's array is free when the call returns and calls still queue up behind each other.  Grow-only.
+    static constexpr int RG_SLOTS = 4;
+    struct Ragged {
+        size_t cap = 0;                               // bytes of the device block and of each mirror
+        char *d = nullptr, *h = nullptr;              // h: RG_SLOTS mirrors of cap bytes
+        unsigned calls = 0;
+        hipEvent_t ev[RG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+    } rg;
 };
 
 struct bsrnn_stream {
@@ -438,6 +452,9 @@ struct Part {
     const float* state_in; float* state_out;             // [4][2][C_total*K][64] slabs already offset to this part's first row
     size_t state_slab;                                   // floats between the two Time blocks' slabs (uses C_total)
     const float* wave; float* wave_out; int64_t n;       // only for the fused sandwich
+    const int64_t* lens;                                 // non-null: rows of different lengths (bsrnn_separate_ragged) - device array [C]; n unused,
+    int64_t wave_stride, out_stride;                     //   rows of wave / wave_out this many floats apart
+    const int2* tasks[2]; int n_tasks[2];                // non-null: this call's own task tables of the two chains (else the cache, chain_launch)
     const bsrnn_ctx::OvlTable* ovl;                      // non-null: the overlapped flow (run_overlapped) - producers publish, consumers wait
     int ovl_base;                                        // this call's epoch << OVL_EPOCH_SHIFT
     hipEvent_t band_done[2];                             // events the two band launches signal themselves when they complete (or null)
@@ -464,9 +481,13 @@ enum { MS_STFT, MS_BANDSPLIT, MS_BAND0, MS_BANDFC0, MS_TIME0, MS_TIMEFC0, MS_BAN
 bool chain_launch(bsrnn_ctx* c, const Part& p, int chain, ChainLaunch& g)
 {
     memset(&g, 0, sizeof g);
-    auto tti = c->chain_tasks.find(p.C * p.T);
-    if (tti == c->chain_tasks.end()) { c->stage_error = true; return false; }
-    g.desc = c->d_chain[chain]; g.tasks = tti->second.d[chain]; g.n_tasks = tti->second.n[chain];
+    g.desc = c->d_chain[chain];
+    if (p.tasks[chain]) { g.tasks = p.tasks[chain]; g.n_tasks = p.n_tasks[chain]; }
+    else {
+        auto tti = c->chain_tasks.find(p.C * p.T);
+        if (tti == c->chain_tasks.end()) { c->stage_error = true; return false; }
+        g.tasks = tti->second.d[chain]; g.n_tasks = tti->second.n[chain];
+    }
     g.M = p.C * p.T; g.P = p.P; g.ldp = c->LDP; g.range_flag = c->d_range;
     return true;
 }
@@ -479,7 +500,11 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
     hipStream_t s = p.s;
     switch (stage) {
     case MS_STFT:
-        if (p.wave) { StageScope sc(c, ST_STFT, s); launch_stft(c->tb, p.wave, const_cast<float*>(p.Xf), p.C, p.n, p.T, s); }
+        if (p.wave) {
+            StageScope sc(c, ST_STFT, s);
+            if (p.lens) launch_stft_ragged(c->tb, p.wave, p.wave_stride, p.lens, const_cast<float*>(p.Xf), p.C, p.T, s);
+            else launch_stft(c->tb, p.wave, const_cast<float*>(p.Xf), p.C, p.n, p.T, s);
+        }
         break;
     case MS_BANDSPLIT: {   // bandFCs_pre (2 linears) -> residual P; bandFCs (3 linears) -> Z0   bsrnn.py:404-415
         StageScope sc(c, ST_BANDSPLIT, s);
@@ -577,7 +602,8 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
     case MS_ISTFT:
         if (p.wave_out) {
             StageScope sc(c, ST_ISTFT, s);
-            launch_istft(c->tb, p.Yf, p.wave_out, p.C, p.T, s);
+            if (p.lens) launch_istft_ragged(c->tb, p.Yf, p.wave_out, p.out_stride, p.lens, p.C, p.T, s);
+            else launch_istft(c->tb, p.Yf, p.wave_out, p.C, p.T, s);
         }
         break;
     }
@@ -921,6 +947,10 @@ static void destroy_now(bsrnn_ctx* c)
     if (c->lf.state[0]) (void)hipFree(c->lf.state[0]);
     if (c->lf.d_base) (void)hipFree(c->lf.d_base);
     if (c->lf.h_base) (void)hipHostFree(c->lf.h_base);
+    if (c->rg.d) (void)hipFree(c->rg.d);
+    if (c->rg.h) (void)hipHostFree(c->rg.h);
+    for (hipEvent_t e : c->rg.ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->ev_ovl_fork) (void)hipEventDestroy(c->ev_ovl_fork);
     if (c->ev_ovl_join) (void)hipEventDestroy(c->ev_ovl_join);
     free_ovl_tables(c);
@@ -1560,6 +1590,98 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
                 HIP_TRY(hipStreamWaitEvent(s, c->ev_join[j], 0));
             }
         if (c->stage_error) { c->stage_error = false; return fail(BSRNN_ESTATE, "no task table for a row block of this call (internal error)"); }
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    if ((rc = run())) return rc;
+    return finish_call(c, s, run);
+}
+
+// --------------------------------------------------------------------------- ragged batches: rows of different lengths in one call
+// The model is causal along time, its band-axis blocks see one frame at a time and rows are independent: frames t < T_r of row r do not
+// depend on what frames t >= T_r of that row, or any other row, hold.  So the call is bsrnn_separate on the rectangle R x Tmax with the two
+// DSP ends told the rows' lengths (fft.hip: the padded frames go in as zero rows, the padded hops come out as zeros); every stage between
+// them runs as for a rectangular call, the overlapped dual path included.
+
+// This call's block (bsrnn_ctx::Ragged) for R rows of M = R * Tmax frame rows, copied in on stream s; where its parts are on the device.
+static int ragged_upload(bsrnn_ctx* c, const int64_t* lens, int R, int M, hipStream_t s, Part& p)
+{
+    bsrnn_ctx::Ragged& rg = c->rg;
+    std::vector<ChainTask> tk[2];
+    const size_t b_lens = (size_t)R * sizeof(int64_t);
+    size_t off[2], bytes = b_lens;
+    for (int ch = 0; ch < 2; ++ch) {
+        if (c->fused) build_chain_tasks(c->h_chain[ch], M, tk[ch]);
+        off[ch] = bytes;
+        bytes += (tk[ch].size() + 1) * sizeof(int2);                  // (one entry of slack, as upload_table's)
+    }
+    if (bytes > rg.cap) {
+        HIP_TRY(hipDeviceSynchronize());                              // queued copies read the old mirrors, queued kernels the old block
+        if (rg.d) { (void)hipFree(rg.d); (void)hipHostFree(rg.h); rg.d = rg.h = nullptr; rg.cap = 0; }
+        const size_t cap = (bytes + bytes / 2 + 255) & ~size_t(255);
+        g_dbg[DBG_ALLOC] += 2;
+        HIP_TRY(hipHostMalloc((void**)&rg.h, bsrnn_ctx::RG_SLOTS * cap, hipHostMallocDefault));
+        const hipError_t e = hipMalloc((void**)&rg.d, cap);
+        if (e != hipSuccess) { (void)hipHostFree(rg.h); rg.h = rg.d = nullptr; return fail(BSRNN_EHIP, "hipMalloc: %s", hipGetErrorString(e)); }
+        for (hipEvent_t& ev : rg.ev)
+            if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        rg.cap = cap;
+    }
+    const int k = (int)(rg.calls++ % bsrnn_ctx::RG_SLOTS);
+    HIP_TRY(hipEventSynchronize(rg.ev[k]));                           // (the copy of RG_SLOTS calls ago; an event never recorded counts as complete)
+    char* h = rg.h + (size_t)k * rg.cap;
+    memcpy(h, lens, b_lens);
+    for (int ch = 0; ch < 2; ++ch) {
+        memcpy(h + off[ch], tk[ch].data(), tk[ch].size() * sizeof(int2));
+        memset(h + off[ch] + tk[ch].size() * sizeof(int2), 0, sizeof(int2));
+    }
+    HIP_TRY(hipMemcpyAsync(rg.d, h, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(rg.ev[k], s));
+    p.lens = reinterpret_cast<const int64_t*>(rg.d);
+    for (int ch = 0; ch < 2; ++ch) {
+        p.tasks[ch] = c->fused ? reinterpret_cast<const int2*>(rg.d + off[ch]) : nullptr;
+        p.n_tasks[ch] = (int)tk[ch].size();
+    }
+    return 0;
+}
+
+int bsrnn_separate_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_stride, const int64_t* lens_host, float* wave_out, int32_t R, void* stream)
+{
+    // arguments first, device or not (a host-only context answers them before BSRNN_ESTATE)
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!wave || !lens_host || !wave_out || R < 1)
+        return fail(BSRNN_EARG, "bsrnn_separate_ragged: need a waveform, R lengths, an output buffer and R >= 1, got R = %d", R);
+    const RaggedShape q = ragged_shape(lens_host, R, wave_stride);
+    if (q.why == RAGGED_SHORT)
+        return fail(BSRNN_EARG, "bsrnn_separate_ragged: row %d has %lld samples, need more than 1024 (reflect padding)", q.bad_row, (long long)q.bad_len);
+    if (q.why == RAGGED_LONG)
+        return fail(BSRNN_EARG, "bsrnn_separate_ragged: row %d has %lld samples, more than the row stride of %lld", q.bad_row, (long long)q.bad_len,
+                    (long long)wave_stride);
+    if (q.Tmax * R > INT32_MAX / 2) return fail(BSRNN_EARG, "bsrnn_separate_ragged: %d rows x %lld frames is too many frame rows for one call", R, (long long)q.Tmax);
+    // the re-run (finish_call) reads the waveform again
+    if (c->range_policy == BSRNN_RANGE_EXACT &&
+        ranges_overlap(wave, (size_t)R * wave_stride * sizeof(float), wave_out, (size_t)R * q.out_stride * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_separate_ragged: wave_out must not overlap wave (a call that leaves the fp16 range is run again from wave)");
+    int rc = check_ready(c);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const int T = (int)q.Tmax;
+    if ((rc = ensure_ws(c, (size_t)R * T))) return rc;
+    if ((rc = ensure_ovl(c, plan_call(c, R, T, false, true), R, T))) return rc;
+    // one row block (the two concurrent row blocks of bsrnn_separate for R >= 128 are not reproduced, as in bsrnn_separate_long)
+    Part p = make_part(c, 0, R, T, s);
+    p.wave = wave; p.wave_stride = wave_stride;
+    p.wave_out = wave_out; p.out_stride = q.out_stride;
+    if ((rc = ragged_upload(c, lens_host, R, R * T, s, p))) return rc;
+    // a re-run sees the same lengths: the block on the device is not touched before the next call
+    auto run = [&]() -> int {
+        p.f = plan_call(c, R, T, false, true);
+        const bsrnn_ctx::OvlTable* tb = ovl_table(c, p.f, R, T, s);
+        if (tb) run_overlapped(c, p, tb, MS_STFT, MS_ISTFT);
+        else
+            for (int st = 0; st < MS_COUNT; ++st) run_stage(c, p, st);
+        if (c->stage_error) { c->stage_error = false; return fail(BSRNN_ESTATE, "no task table for this call (internal error)"); }
         HIP_TRY(hipGetLastError());
         return 0;
     };

@@ -827,4 +827,138 @@ void launch_istft_segment(const FftTables& tb, const float* Y, float* out, int64
     hipLaunchKernelGGL(istft_segment_kernel, grid, dim3(256), 0, s, tb, Y, out, out_stride, carry_in, carry_out, L, ich);
 }
 
+// ------------------------------------------------------------------------------ offline DSP, rows of different lengths
+// The offline pair for a batch whose row r holds lens[r] samples (bsrnn_separate_ragged): T_r = 1 + lens[r] / 1024 frames of its own inside a
+// rectangle of Tmax = max T_r frames per row.  Per frame / hop the arithmetic is that of stft_kernel<false> / istft_fused_kernel, in their
+// order: a frame or a hop that both compute has the same bits.  Row and chunk belong to the workgroup, so every condition below is
+// workgroup-uniform, and each walk is one loop over the real frames / hops (no branch inside it) and one over the padded ones.
+//
+// Analysis: frames t < T_r of row r come from wave + r * stride, reflected at 0 and at lens[r] - 1 (never at the stride: samples
+// [lens[r], stride) are not read).  Frames T_r <= t < Tmax are written as zeros in ALL ld columns of their row of X: the workspace is reused
+// from call to call, and what an earlier call left there must reach neither the range guard nor, through 0 * mask, the rows of Y.
+__global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_ragged_kernel(FftTables tb, const float* __restrict__ wave, float* __restrict__ X,
+                                                                        int64_t stride, const int64_t* __restrict__ lens, int Tmax, int sch)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const int r = blockIdx.y;
+    const int64_t n = lens[r];
+    const int Tr = 1 + (int)(n / HOPS);
+    const int t0 = blockIdx.x * sch;
+    const int te = (t0 + sch < Tmax) ? t0 + sch : Tmax;               // the chunk: frames [t0, te) of the rectangle
+    const int t1 = te < Tr ? te : Tr;                                 // its real frames: [t0, t1), none when t1 <= t0
+    float* Xr = X + (size_t)r * Tmax * tb.ld;
+    if (t0 < t1) {
+        const Twiddles twd = load_twiddles<false>(tb.tw1024, tid);
+        const SplitCtx spl = load_split(tb, tid, false);
+        const float* src = wave + (size_t)r * stride;
+        float2 win[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) win[k] = make_float2(tb.hann[2 * (tid + 256 * k)], tb.hann[2 * (tid + 256 * k) + 1]);
+        auto sample2 = [&](int t, int c) {
+            float v[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                int64_t idx = (int64_t)t * HOPS + 2 * c + e - NFFT / 2;
+                if (idx < 0) idx = -idx;
+                if (idx >= n) idx = 2 * (n - 1) - idx;
+                v[e] = src[idx];
+            }
+            return make_float2(v[0], v[1]);
+        };
+        float2 raw[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) raw[k] = sample2(t0, tid + 256 * k);
+        for (int t = t0; t < t1; ++t) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) z0[tid + 256 * k] = make_float2(raw[k].x * win[k].x, raw[k].y * win[k].y);
+            __syncthreads();
+            raw[0] = raw[2]; raw[1] = raw[3];
+            { const int tn = t + 1 < t1 ? t + 1 : t; raw[2] = sample2(tn, tid + 512); raw[3] = sample2(tn, tid + 768); }      // (no branch: after the last frame a dummy reload)
+            const float2* Z = fft1024<false>(z0, z1, twd, tid);
+            rfft_split_store(Z, spl, Xr + (size_t)t * tb.ld, tid);
+            __syncthreads();                          // Z (= z1) is overwritten by the next frame's first pass
+        }
+    }
+    // the padded frames of the chunk (rows of X start 16-byte aligned and ld is a multiple of 4: commit_host.h, band_columns)
+    for (int t = t0 > t1 ? t0 : t1; t < te; ++t) {
+        float4* row = reinterpret_cast<float4*>(Xr + (size_t)t * tb.ld);
+        for (int i = tid; i < tb.ld / 4; i += 256) row[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// Synthesis: Y = the spectra of the rectangle, [R * Tmax][ld]; row r of `out` starts at out + r * out_stride and holds Tmax - 1 hops.  Hops
+// b < T_r - 1 are computed from frames b and b + 1 like istft_fused_kernel's; hops T_r - 1 <= b < Tmax - 1 are STORED as zeros, not
+// computed (hop T_r - 1 would add the row's last real second half to a padded frame).  A workgroup whose chunk lies past the row's end does
+// no FFT.
+__global__ __launch_bounds__(256, FFT_OCC_ISTFT) void istft_ragged_kernel(FftTables tb, const float* __restrict__ Y, float* __restrict__ out, int64_t out_stride,
+                                                                          const int64_t* __restrict__ lens, int Tmax, int ich)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const int r = blockIdx.y;
+    const int Tr = 1 + (int)(lens[r] / HOPS);
+    const int b0 = blockIdx.x * ich;
+    const int be = (b0 + ich < Tmax - 1) ? b0 + ich : Tmax - 1;      // the chunk: hops [b0, be) of the rectangle
+    const int b1 = be < Tr - 1 ? be : Tr - 1;                         // its real hops: [b0, b1) <- frames b0 .. b1, none when b1 <= b0
+    float* o = out + (size_t)r * out_stride;
+    if (b0 < b1) {
+        const Twiddles twd = load_twiddles<true>(tb.tw1024, tid);
+        const SplitCtx spl = load_split(tb, tid, true);
+        const float sc = 1.0f / 1024.0f;
+        float2 wlo[2], whi[2], env[2], carry[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 256 * k;
+            wlo[k] = make_float2(tb.hann[2 * c] * sc, tb.hann[2 * c + 1] * sc);
+            whi[k] = make_float2(tb.hann[2 * c + HOPS] * sc, tb.hann[2 * c + 1 + HOPS] * sc);
+            env[k] = make_float2(tb.inv_env[2 * c], tb.inv_env[2 * c + 1]);
+            carry[k] = make_float2(0.f, 0.f);
+        }
+        const float* Yr = Y + (size_t)r * Tmax * tb.ld;
+        MergeRegs mr;
+        irfft_load<false>(Yr + (size_t)b0 * tb.ld, spl, mr, tid);
+        // The first frame of the chunk only fills the carry; it is peeled so that the loop body has no branch around its loads and stores
+        auto frame = [&](int t, auto first) {
+            irfft_store(mr, spl, z0, tid);
+            __syncthreads();
+            irfft_load<false>(Yr + (size_t)(t < b1 ? t + 1 : t) * tb.ld, spl, mr, tid);      // (after the last frame: a dummy reload)
+            const float2* z = fft1024<true>(z0, z1, twd, tid);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int c = tid + 256 * k;
+                const float2 a = z[c], b = z[c + 512];
+                if (!decltype(first)::value) {
+                    // same operation order as istft_fused_kernel: (frame * 1/1024 * window) summed, then / envelope
+                    const float2 v = make_float2((a.x * wlo[k].x + carry[k].x) * env[k].x, (a.y * wlo[k].y + carry[k].y) * env[k].y);
+                    *reinterpret_cast<float2*>(o + (size_t)(t - 1) * HOPS + 2 * c) = v;
+                }
+                carry[k] = make_float2(b.x * whi[k].x, b.y * whi[k].y);
+            }
+            __syncthreads();                          // z (= z1) is overwritten by the next frame's first pass
+        };
+        frame(b0, std::true_type());
+        for (int t = b0 + 1; t <= b1; ++t) frame(t, std::false_type());
+    }
+    // the padded hops of the chunk, at the addresses and with the 8-byte stores of the real ones
+    for (int b = b0 > b1 ? b0 : b1; b < be; ++b) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) *reinterpret_cast<float2*>(o + (size_t)b * HOPS + 2 * (tid + 256 * k)) = make_float2(0.f, 0.f);
+    }
+}
+
+void launch_stft_ragged(const FftTables& tb, const float* wave, int64_t stride, const int64_t* lens, float* X, int R, int Tmax, hipStream_t s)
+{
+    static const int slots = resident_slots((const void*)stft_ragged_kernel);
+    const int sch = frames_per_workgroup(Tmax, R, slots, 0);
+    hipLaunchKernelGGL(stft_ragged_kernel, dim3((unsigned)((Tmax + sch - 1) / sch), R), dim3(256), 0, s, tb, wave, X, stride, lens, Tmax, sch);
+}
+void launch_istft_ragged(const FftTables& tb, const float* Y, float* out, int64_t out_stride, const int64_t* lens, int R, int Tmax, hipStream_t s)
+{
+    if (Tmax < 2) return;
+    static const int slots = resident_slots((const void*)istft_ragged_kernel);
+    const int ich = frames_per_workgroup(Tmax - 1, R, slots, 1);
+    hipLaunchKernelGGL(istft_ragged_kernel, dim3((unsigned)((Tmax - 1 + ich - 1) / ich), R), dim3(256), 0, s, tb, Y, out, out_stride, lens, Tmax, ich);
+}
+
 }  // namespace bsrnn

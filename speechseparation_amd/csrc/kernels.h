@@ -252,6 +252,11 @@ void launch_istft(const FftTables& tb, const float* Y, float* out, int R, int T,
 void launch_stft_segment(const FftTables& tb, const float* src, int64_t stride, int64_t base, float* X, int R, int64_t n, int ta, int te, hipStream_t s);
 void launch_istft_segment(const FftTables& tb, const float* Y, float* out, int64_t out_stride, const float* carry_in, float* carry_out, int R, int L,
                           hipStream_t s);
+// The same pair for rows of different lengths (bsrnn_separate_ragged; fft.hip): row r holds lens[r] samples (device int64) at wave + r * stride
+// and T_r = 1 + lens[r] / 1024 frames of the rectangle X / Y [R*Tmax][ld]; its frames t >= T_r are written as zero rows of X, its hops
+// b >= T_r - 1 as zeros of out (rows out_stride floats apart, Tmax - 1 hops each)
+void launch_stft_ragged(const FftTables& tb, const float* wave, int64_t stride, const int64_t* lens, float* X, int R, int Tmax, hipStream_t s);
+void launch_istft_ragged(const FftTables& tb, const float* Y, float* out, int64_t out_stride, const int64_t* lens, int R, int Tmax, hipStream_t s);
 // gradient of launch_istft's output w.r.t. its input (training step): dwave [R][(T-1)*1024] -> dY frame-major [R*T][ld];
 // scratch [R][(T-1)*1024]
 void launch_istft_backward(const FftTables& tb, const float* dwave, float* scratch, float* dY, int R, int T, hipStream_t s);

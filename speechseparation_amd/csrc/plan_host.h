@@ -220,4 +220,24 @@ inline int long_frame_rows(int R, int T, int seg, int ms[2])
     return ms[1] ? 2 : 1;
 }
 
+// --------------------------------------------------------------------------- ragged batches: rows of different lengths (bsrnn_separate_ragged)
+// Row r holds lens[r] samples, 1024 < lens[r] <= stride (reflect padding needs more than half a frame; rows are `stride` floats apart), and
+// has T_r = 1 + lens[r] / 1024 frames of its own.  The call runs on the rectangle R x Tmax, Tmax = the largest T_r, and writes rows of
+// (Tmax - 1) * 1024 samples.  The first row that breaks a bound is refused: bad_row >= 0, bad_len its length, why = RAGGED_SHORT / RAGGED_LONG.
+inline int64_t ragged_frames(int64_t n) { return 1 + n / HOPS; }
+enum RaggedWhy { RAGGED_OK, RAGGED_SHORT, RAGGED_LONG };
+struct RaggedShape { int64_t Tmax, out_stride; int bad_row; int64_t bad_len; int why; };
+inline RaggedShape ragged_shape(const int64_t* lens, int R, int64_t stride)
+{
+    RaggedShape q = {0, 0, -1, 0, RAGGED_OK};
+    for (int r = 0; r < R; ++r) {
+        if (lens[r] <= NFFT / 2 || lens[r] > stride) {
+            return RaggedShape{0, 0, r, lens[r], lens[r] > stride ? RAGGED_LONG : RAGGED_SHORT};
+        }
+        q.Tmax = std::max(q.Tmax, ragged_frames(lens[r]));
+    }
+    q.out_stride = (q.Tmax - 1) * HOPS;
+    return q;
+}
+
 }  // namespace bsrnn

@@ -135,3 +135,34 @@ def param_spec(v=None):
 def n_frames(n_samples, hop=HOP):
     """torch.stft(center=True) frame count: 1 + n // hop (infer.py:31)."""
     return 1 + n_samples // hop
+
+
+def ragged_buckets(frames, rows, max_rows, max_padding):
+    """Group clips of different lengths into batches for `BSRNN.separate_ragged` (which pays for the rectangle rows x longest clip).
+
+    frames[i] / rows[i]: frame count and channel count of clip i.  Returns a list of buckets, each a list of clip indices; every clip is in
+    exactly one bucket and all its channels with it.  A bucket has at most `max_rows` rows - except a single clip that alone has more, which
+    gets a bucket of its own - and its padding share 1 - sum(rows_i * frames_i) / (sum(rows_i) * max(frames_i)) is at most `max_padding`.
+    Greedy: clips sorted by frame count, longest first (ties by index), each joins the open bucket if both caps allow it and opens a new one
+    otherwise.  Deterministic; not an optimal packing."""
+    frames, rows = [int(f) for f in frames], [int(r) for r in rows]
+    if len(frames) != len(rows):
+        raise ValueError("ragged_buckets: %d frame counts for %d row counts" % (len(frames), len(rows)))
+    if any(f < 1 for f in frames) or any(r < 1 for r in rows):
+        raise ValueError("ragged_buckets: frame and row counts must be at least 1")
+    if max_rows < 1 or not 0 <= max_padding < 1:
+        raise ValueError("ragged_buckets: need max_rows >= 1 and 0 <= max_padding < 1, got %r and %r" % (max_rows, max_padding))
+    buckets = []
+    cur, n_rows, work, longest = [], 0, 0, 0
+    for i in sorted(range(len(frames)), key=lambda j: (-frames[j], j)):
+        if cur and n_rows + rows[i] <= max_rows and 1 - (work + rows[i] * frames[i]) / ((n_rows + rows[i]) * longest) <= max_padding:
+            cur.append(i)
+            n_rows += rows[i]
+            work += rows[i] * frames[i]
+            continue
+        if cur:
+            buckets.append(cur)
+        cur, n_rows, work, longest = [i], rows[i], rows[i] * frames[i], frames[i]
+    if cur:
+        buckets.append(cur)
+    return buckets
