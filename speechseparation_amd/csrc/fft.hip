@@ -127,6 +127,9 @@ __device__ __forceinline__ void irfft_load(const float* __restrict__ Y, const Sp
         r.xc[i] = *reinterpret_cast<const float2*>(Y + (LIN ? 2 * (1024 - k) : sc.colr[i]));
     }
 }
+// PINNED spells out the fused multiply-adds of o = dd * conj(tw) (istft_walk).  Left to the compiler's contraction, which of the two products
+// of each component is rounded first depends on the code around the call.
+template <bool PINNED = false>
 __device__ __forceinline__ void irfft_store(const MergeRegs& r, const SplitCtx& sc, float2* z, int tid)
 {
 #pragma unroll
@@ -137,7 +140,8 @@ __device__ __forceinline__ void irfft_store(const MergeRegs& r, const SplitCtx& 
         b = cconj(b);
         const float2 e = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y + b.y));
         const float2 dd = make_float2(0.5f * (a.x - b.x), 0.5f * (a.y - b.y));
-        const float2 o = cmul(dd, cconj(sc.tw[i]));
+        const float2 t = sc.tw[i];
+        const float2 o = PINNED ? make_float2(fmaf(dd.x, t.x, dd.y * t.y), fmaf(dd.y, t.x, -(dd.x * t.y))) : cmul(dd, cconj(t));
         z[k] = make_float2(e.x - o.y, e.y + o.x);                     // e + i*o
     }
 }
@@ -180,49 +184,36 @@ static int frames_per_workgroup(int units, int rows, int slots, int extra)
     }
     return best;
 }
-
-// ------------------------------------------------------------------------------ offline STFT
-// One workgroup transforms `sch` consecutive frames of one row.  Frames overlap by half: the thread that owns complex
-// samples c + 512, c + 768 of frame t owns c, c + 256 of frame t + 1, so only the new half is loaded per frame
-// (requested before the FFT passes of the current frame) and the raw samples stay in registers.
-constexpr int FFT_OCC_STFT = 4;     // waves per SIMD (= workgroups per CU) the offline STFT is compiled for
-constexpr int FFT_OCC_ISTFT = 4;    // ... and the offline iSTFT
-template <bool ZERO_PAD>      // ZERO_PAD: samples outside [0, n) are zeros instead of reflections (the adjoint of the iSTFT, below)
-__global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_kernel(FftTables tb, const float* __restrict__ wave, float* __restrict__ X,
-                                                   int64_t n, int T, int sch)
+// Chunk length and grid of a chunked launch: ceil(units / chunk) workgroups per row.  One resident-slots value per kernel.
+struct Chunks { int len; dim3 grid; };
+template <auto KERNEL>
+static Chunks chunks_for(int units, int rows, int extra)
 {
-    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
-#ifdef FFT_EXCLUSIVE_LDS
-    // measurement only (tools/coresident_variants.sh): the workgroup claims the CU's whole LDS, so no other kernel's waves share its CU
-    __shared__ float lds_pad[(160 * 1024 - 2 * 1024 * 8) / 4 - 64];
-    { volatile float* vp = lds_pad; float t_ = vp[threadIdx.x]; asm volatile("" :: "v"(t_)); }
-#endif
-    const int tid = threadIdx.x;
+    static const int slots = resident_slots((const void*)KERNEL);
+    const int len = frames_per_workgroup(units, rows, slots, extra);
+    return {len, dim3((unsigned)((units + len - 1) / len), rows)};
+}
+
+// ------------------------------------------------------------------------------ the two frame walks
+// Every chunked STFT kernel (offline, segment, ragged, block streaming) is this walk over frames [t0, t1) of one row plus its own
+// sample source, row destination and epilogue, and every windowed iSTFT kernel (offline, segment, ragged) is istft_walk below: a frame
+// or a hop that two of them compute has the same bits because it is the same code.
+//
+// Analysis.  Frames overlap by half: the thread that owns complex samples c + 512, c + 768 of frame t owns c, c + 256 of frame t + 1, so
+// only the new half is loaded per frame (requested before the FFT passes of the current frame) and the raw samples stay in registers.
+// sample2(t, c) = complex sample c (0..1023) of frame t, row(t) = where the spectrum of frame t goes.  The walk fetches the twiddle and split
+// tables itself (passed in from the kernel, the counted vmcnt(28) wait in front of the loop became a vmcnt(0) in front of the sample loads).  Returns the raw second half of
+// the last frame (complex samples 512 + tid, 768 + tid).
+struct RawHalf { float2 v[2]; };
+template <class SAMPLE2, class ROW>
+__device__ __forceinline__ RawHalf stft_walk(const FftTables& tb, float2* z0, float2* z1, int tid, int t0, int t1,
+                                             SAMPLE2 sample2, ROW row)
+{
     const Twiddles twd = load_twiddles<false>(tb.tw1024, tid);
     const SplitCtx spl = load_split(tb, tid, false);
-    const int r = blockIdx.y;
-    const int t0 = blockIdx.x * sch;
-    const int t1 = (t0 + sch < T) ? t0 + sch : T;
-    const float* src = wave + (size_t)r * n;
     float2 win[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) win[k] = make_float2(tb.hann[2 * (tid + 256 * k)], tb.hann[2 * (tid + 256 * k) + 1]);
-    // padded frame sample i (0..2047) of frame t is original index t*1024 + i - 1024, reflected at both ends
-    auto sample2 = [&](int t, int c) {
-        float v[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            int64_t idx = (int64_t)t * HOPS + 2 * c + e - NFFT / 2;
-            if (ZERO_PAD) {
-                v[e] = (idx >= 0 && idx < n) ? src[idx] : 0.f;
-                continue;
-            }
-            if (idx < 0) idx = -idx;
-            if (idx >= n) idx = 2 * (n - 1) - idx;
-            v[e] = src[idx];
-        }
-        return make_float2(v[0], v[1]);
-    };
     float2 raw[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) raw[k] = sample2(t0, tid + 256 * k);
@@ -233,17 +224,107 @@ __global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_kernel(FftTables tb, c
         raw[0] = raw[2]; raw[1] = raw[3];
         { const int tn = t + 1 < t1 ? t + 1 : t; raw[2] = sample2(tn, tid + 512); raw[3] = sample2(tn, tid + 768); }      // (no branch: after the last frame a dummy reload)
         const float2* Z = fft1024<false>(z0, z1, twd, tid);
-        rfft_split_store(Z, spl, X + ((size_t)r * T + t) * tb.ld, tid);
+        rfft_split_store(Z, spl, row(t), tid);
         __syncthreads();                          // Z (= z1) is overwritten by the next frame's first pass
     }
+    return {{raw[0], raw[1]}};
+}
+
+// Synthesis.  Output hop = first half of a synthesis frame + second half of the frame in front of it, divided by the window envelope
+// (torch.istft).  The walk takes frames [a0, a1) of one row, each of which completes one hop, with the windowed second half of the frame
+// in front in `carry` (the thread that owns complex samples c, c + 256 of a frame's first half also owns c + 512, c + 768 of the second
+// half): recomputed from frame a0 - 1 (`peel`), or as the caller loaded it.  No [M][2048] frame buffer in HBM and no separate overlap-add
+// launch (was 132 MB + 15 us).  The spectrum of frame t + 1 is requested before the FFT passes of frame t.  spectrum(t) = the row of
+// frame t, hop(t) = where the hop that frame t completes goes.  On return `carry` holds the windowed second half of frame a1 - 1.
+template <class SPECTRUM, class HOP>
+__device__ __forceinline__ void istft_walk(const FftTables& tb, float2* z0, float2* z1, int tid, int a0, int a1, SPECTRUM spectrum, HOP hop,
+                                           bool peel, float2 (&carry)[2])
+{
+    const Twiddles twd = load_twiddles<true>(tb.tw1024, tid);
+    const SplitCtx spl = load_split(tb, tid, true);
+    const float sc = 1.0f / 1024.0f;
+    float2 wlo[2], whi[2], env[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int c = tid + 256 * k;
+        wlo[k] = make_float2(tb.hann[2 * c] * sc, tb.hann[2 * c + 1] * sc);
+        whi[k] = make_float2(tb.hann[2 * c + HOPS] * sc, tb.hann[2 * c + 1 + HOPS] * sc);
+        env[k] = make_float2(tb.inv_env[2 * c], tb.inv_env[2 * c + 1]);
+    }
+    MergeRegs mr;
+    // The frame in front of the range only fills the carry; it is peeled so that the loop body has no branch around its loads and
+    // stores (the compiler then counts them and waits for the next spectrum with vmcnt(2) instead of vmcnt(0), stores included).
+    auto frame = [&](int t, auto first) {
+        irfft_store<true>(mr, spl, z0, tid);
+        __syncthreads();
+        irfft_load<false>(spectrum(t + 1 < a1 ? t + 1 : t), spl, mr, tid);      // (after the last frame: a dummy reload)
+        const float2* z = fft1024<true>(z0, z1, twd, tid);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 256 * k;
+            const float2 a = z[c], b = z[c + 512];
+            if (!decltype(first)::value) {
+                // (frame * 1/1024 * window) summed, then / envelope.  The fused multiply-add is spelled out: left to the compiler's
+                // contraction, it is free to round the other product (a * wlo instead of the carry), and has done so
+                const float2 v = make_float2(fmaf(a.x, wlo[k].x, carry[k].x) * env[k].x, fmaf(a.y, wlo[k].y, carry[k].y) * env[k].y);
+                *reinterpret_cast<float2*>(hop(t) + 2 * c) = v;
+            }
+            carry[k] = make_float2(b.x * whi[k].x, b.y * whi[k].y);
+        }
+        __syncthreads();                          // z (= z1) is overwritten by the next frame's first pass
+    };
+    irfft_load<false>(spectrum(peel ? a0 - 1 : a0), spl, mr, tid);
+    if (peel) frame(a0 - 1, std::true_type());
+    for (int t = a0; t < a1; ++t) frame(t, std::false_type());
+}
+
+// Complex sample c (0..1023) of frame t of a clip of n samples: padded frame sample i (0..2047) is clip sample t*1024 + i - 1024, reflected
+// at both ends.  `src` points at clip sample `base` (subtracted after the reflection).
+__device__ __forceinline__ float2 reflected_sample2(const float* __restrict__ src, int64_t n, int64_t base, int t, int c)
+{
+    float v[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        int64_t idx = (int64_t)t * HOPS + 2 * c + e - NFFT / 2;
+        if (idx < 0) idx = -idx;
+        if (idx >= n) idx = 2 * (n - 1) - idx;
+        v[e] = src[idx - base];
+    }
+    return make_float2(v[0], v[1]);
+}
+
+// ------------------------------------------------------------------------------ offline STFT
+// One workgroup transforms `sch` consecutive frames of one row (stft_walk).
+constexpr int FFT_OCC_STFT = 4;     // waves per SIMD (= workgroups per CU) the offline STFT is compiled for
+constexpr int FFT_OCC_ISTFT = 4;    // ... and the offline iSTFT
+template <bool ZERO_PAD>      // ZERO_PAD: samples outside [0, n) are zeros instead of reflections (the adjoint of the iSTFT, below)
+__global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_kernel(FftTables tb, const float* __restrict__ wave, float* __restrict__ X,
+                                                   int64_t n, int T, int sch)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const int r = blockIdx.y;
+    const int t0 = blockIdx.x * sch;
+    const int t1 = (t0 + sch < T) ? t0 + sch : T;
+    const float* src = wave + (size_t)r * n;
+    auto sample2 = [&](int t, int c) {
+        if (!ZERO_PAD) return reflected_sample2(src, n, 0, t, c);
+        float v[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int64_t idx = (int64_t)t * HOPS + 2 * c + e - NFFT / 2;
+            v[e] = (idx >= 0 && idx < n) ? src[idx] : 0.f;
+        }
+        return make_float2(v[0], v[1]);
+    };
+    auto row = [&](int t) { return X + ((size_t)r * T + t) * tb.ld; };
+    stft_walk(tb, z0, z1, tid, t0, t1, sample2, row);
 }
 
 void launch_stft(const FftTables& tb, const float* wave, float* X, int R, int64_t n, int T, hipStream_t s)
 {
-    static const int slots = resident_slots((const void*)stft_kernel<false>);
-    const int sch = frames_per_workgroup(T, R, slots, 0);
-    dim3 grid((unsigned)((T + sch - 1) / sch), R);
-    hipLaunchKernelGGL(stft_kernel<false>, grid, dim3(256), 0, s, tb, wave, X, n, T, sch);
+    const Chunks ch = chunks_for<stft_kernel<false>>(T, R, 0);
+    hipLaunchKernelGGL(stft_kernel<false>, ch.grid, dim3(256), 0, s, tb, wave, X, n, T, ch.len);
 }
 
 // ------------------------------------------------------------------------------ backward of the offline iSTFT (training step)
@@ -278,79 +359,35 @@ void launch_istft_backward(const FftTables& tb, const float* dwave, float* scrat
     const int64_t n = (int64_t)(T - 1) * HOPS;
     const size_t total = (size_t)R * n;
     hipLaunchKernelGGL(istft_bwd_prescale_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, tb, dwave, scratch, total);
-    static const int slots = resident_slots((const void*)stft_kernel<true>);
-    const int sch = frames_per_workgroup(T, R, slots, 0);
-    hipLaunchKernelGGL(stft_kernel<true>, dim3((unsigned)((T + sch - 1) / sch), R), dim3(256), 0, s, tb, scratch, dY, n, T, sch);
+    const Chunks ch = chunks_for<stft_kernel<true>>(T, R, 0);
+    hipLaunchKernelGGL(stft_kernel<true>, ch.grid, dim3(256), 0, s, tb, scratch, dY, n, T, ch.len);
     const size_t rows = (size_t)R * T;
     hipLaunchKernelGGL(istft_bwd_postscale_kernel, dim3((unsigned)((rows * NBINS + 255) / 256)), dim3(256), 0, s, tb, dY, rows);
 }
 
 // ------------------------------------------------------------------------------ offline iSTFT
-// One workgroup produces `ich` consecutive output hops of one row: output hop b = first half of synthesis frame
-// b + 1 + second half of frame b, divided by the window envelope (torch.istft).  The workgroup walks frames
-// b0 .. b0 + ich, keeps the windowed second half of the previous frame in registers (the thread that owns complex
-// samples c, c + 256 of a frame's first half also owns c + 512, c + 768 of the second half) and recomputes one
-// frame per chunk - no [M][2048] frame buffer in HBM and no separate overlap-add launch (was 132 MB + 15 us).
-// The spectrum of frame t + 1 is requested before the FFT passes of frame t.
+// One workgroup produces `ich` consecutive output hops of one row: output hop b = first half of synthesis frame b + 1 + second half of
+// frame b.  The workgroup walks frames b0 .. b0 + ich (istft_walk) and recomputes one frame per chunk.
 __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void istft_fused_kernel(FftTables tb, const float* __restrict__ Y, float* __restrict__ out, int T, int ich)
 {
     __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
-#ifdef FFT_EXCLUSIVE_LDS
-    // measurement only (tools/coresident_variants.sh): the workgroup claims the CU's whole LDS, so no other kernel's waves share its CU
-    __shared__ float lds_pad[(160 * 1024 - 2 * 1024 * 8) / 4 - 64];
-    { volatile float* vp = lds_pad; float t_ = vp[threadIdx.x]; asm volatile("" :: "v"(t_)); }
-#endif
     const int tid = threadIdx.x;
-    const Twiddles twd = load_twiddles<true>(tb.tw1024, tid);
-    const SplitCtx spl = load_split(tb, tid, true);
     const int r = blockIdx.y;
     const int b0 = blockIdx.x * ich;
     const int b1 = (b0 + ich < T - 1) ? b0 + ich : T - 1;          // output hops [b0, b1) <- frames b0 .. b1
-    const size_t len = (size_t)(T - 1) * HOPS;
-    const float sc = 1.0f / 1024.0f;
-    float2 wlo[2], whi[2], env[2], carry[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int c = tid + 256 * k;
-        wlo[k] = make_float2(tb.hann[2 * c] * sc, tb.hann[2 * c + 1] * sc);
-        whi[k] = make_float2(tb.hann[2 * c + HOPS] * sc, tb.hann[2 * c + 1 + HOPS] * sc);
-        env[k] = make_float2(tb.inv_env[2 * c], tb.inv_env[2 * c + 1]);
-        carry[k] = make_float2(0.f, 0.f);
-    }
     const float* Yr = Y + (size_t)r * T * tb.ld;
-    MergeRegs mr;
-    irfft_load<false>(Yr + (size_t)b0 * tb.ld, spl, mr, tid);
-    // The first frame of the chunk only fills the carry; it is peeled so that the loop body has no branch around its loads and
-    // stores (the compiler then counts them and waits for the next spectrum with vmcnt(2) instead of vmcnt(0), stores included).
-    auto frame = [&](int t, auto first) {
-        irfft_store(mr, spl, z0, tid);
-        __syncthreads();
-        irfft_load<false>(Yr + (size_t)(t < b1 ? t + 1 : t) * tb.ld, spl, mr, tid);      // (after the last frame: a dummy reload)
-        const float2* z = fft1024<true>(z0, z1, twd, tid);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int c = tid + 256 * k;
-            const float2 a = z[c], b = z[c + 512];
-            if (!decltype(first)::value) {
-                // same operation order as the two-pass version: (frame * 1/1024 * window) summed, then / envelope
-                const float2 v = make_float2((a.x * wlo[k].x + carry[k].x) * env[k].x, (a.y * wlo[k].y + carry[k].y) * env[k].y);
-                *reinterpret_cast<float2*>(out + (size_t)r * len + (size_t)(t - 1) * HOPS + 2 * c) = v;
-            }
-            carry[k] = make_float2(b.x * whi[k].x, b.y * whi[k].y);
-        }
-        __syncthreads();                          // z (= z1) is overwritten by the next frame's first pass
-    };
-    frame(b0, std::true_type());
-    for (int t = b0 + 1; t <= b1; ++t) frame(t, std::false_type());
+    float* o = out + (size_t)r * (T - 1) * HOPS;
+    auto spectrum = [&](int t) { return Yr + (size_t)t * tb.ld; };
+    auto hop = [&](int t) { return o + (size_t)(t - 1) * HOPS; };
+    float2 carry[2];
+    istft_walk(tb, z0, z1, tid, b0 + 1, b1 + 1, spectrum, hop, true, carry);
 }
 
 void launch_istft(const FftTables& tb, const float* Y, float* out, int R, int T, hipStream_t s)
 {
     if (T < 2) return;
-    static const int slots = resident_slots((const void*)istft_fused_kernel);
-    const int ich = frames_per_workgroup(T - 1, R, slots, 1);
-    dim3 grid((unsigned)((T - 1 + ich - 1) / ich), R);
-    hipLaunchKernelGGL(istft_fused_kernel, grid, dim3(256), 0, s, tb, Y, out, T, ich);
+    const Chunks ch = chunks_for<istft_fused_kernel>(T - 1, R, 1);
+    hipLaunchKernelGGL(istft_fused_kernel, ch.grid, dim3(256), 0, s, tb, Y, out, T, ch.len);
 }
 
 // ------------------------------------------------------------------------------ [C][2050][T] <-> [C*T][ld]
@@ -551,7 +588,7 @@ void launch_stream_synthesis(const FftTables& tb, const float* Y, const float* X
 
 // ------------------------------------------------------------------------------ streaming DSP, a block of L hops per row
 // The two kernels above for L consecutive hops in one launch (bsrnn_stream_process), built like the offline pair: a workgroup walks
-// `sch` consecutive hops of one row.  Per row the analysis reads S = buf_in[0:2048] ++ chunk[0:L*1024]; frame l is
+// `sch` consecutive hops of one row (the analysis with stft_walk).  Per row the analysis reads S = buf_in[0:2048] ++ chunk[0:L*1024]; frame l is
 // S[(l+1)*1024 : (l+1)*1024 + 2048] (no reflection: the history is the carried buffer), and the new carry is the last frame's raw
 // samples.  Per frame the arithmetic is that of the one-hop kernels, in their order.
 __global__ __launch_bounds__(256, FFT_OCC_STFT) void stream_block_analysis_kernel(FftTables tb, const float* __restrict__ buf_in, float* __restrict__ buf_out,
@@ -559,35 +596,19 @@ __global__ __launch_bounds__(256, FFT_OCC_STFT) void stream_block_analysis_kerne
 {
     __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
     const int tid = threadIdx.x;
-    const Twiddles twd = load_twiddles<false>(tb.tw1024, tid);
-    const SplitCtx spl = load_split(tb, tid, false);
     const int r = blockIdx.y;
     const int l0 = blockIdx.x * sch;
     const int l1 = (l0 + sch < L) ? l0 + sch : L;
     const float* carry = buf_in + (size_t)r * NFFT;
     const float* fresh = chunk + (size_t)r * L * HOPS;
-    float2 win[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) win[k] = make_float2(tb.hann[2 * (tid + 256 * k)], tb.hann[2 * (tid + 256 * k) + 1]);
     // complex sample c (0..1023) of frame l = S[(l+1)*1024 + 2c], S[.. + 1]: the carried buffer below index 2048 of S, the chunk above
     // (both indices on the same side: the boundary is even)
     auto sample2 = [&](int l, int c) {
         const int64_t j = (int64_t)(l + 1) * HOPS + 2 * c;
         return *reinterpret_cast<const float2*>(j < NFFT ? carry + j : fresh + (j - NFFT));
     };
-    float2 raw[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) raw[k] = sample2(l0, tid + 256 * k);
-    for (int l = l0; l < l1; ++l) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) z0[tid + 256 * k] = make_float2(raw[k].x * win[k].x, raw[k].y * win[k].y);
-        __syncthreads();
-        raw[0] = raw[2]; raw[1] = raw[3];
-        { const int ln = l + 1 < l1 ? l + 1 : l; raw[2] = sample2(ln, tid + 512); raw[3] = sample2(ln, tid + 768); }      // (no branch: after the last frame a dummy reload)
-        const float2* Z = fft1024<false>(z0, z1, twd, tid);
-        rfft_split_store(Z, spl, X + ((size_t)r * L + l) * tb.ld, tid);
-        __syncthreads();                          // Z (= z1) is overwritten by the next frame's first pass
-    }
+    auto row = [&](int l) { return X + ((size_t)r * L + l) * tb.ld; };
+    const RawHalf last = stft_walk(tb, z0, z1, tid, l0, l1, sample2, row);
     // the workgroup that owns the last hop leaves the new carry: buf_out = S[L*1024 : L*1024 + 2048] = the last frame's samples (its
     // first half is read again here instead of being kept through the loop; buf_out is another set than buf_in)
     if (l1 == L) {
@@ -596,7 +617,7 @@ __global__ __launch_bounds__(256, FFT_OCC_STFT) void stream_block_analysis_kerne
         for (int k = 0; k < 2; ++k) {
             const int c = tid + 256 * k;
             *reinterpret_cast<float2*>(b + 2 * c) = sample2(L - 1, c);
-            *reinterpret_cast<float2*>(b + HOPS + 2 * c) = raw[k];      // after the loop raw[0], raw[1] hold the last frame's second half
+            *reinterpret_cast<float2*>(b + HOPS + 2 * c) = last.v[k];   // the last frame's second half, as the walk left it
         }
     }
 }
@@ -683,24 +704,21 @@ __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void stream_block_synthesis_ker
 
 void launch_stream_block_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L, hipStream_t s)
 {
-    static const int slots = resident_slots((const void*)stream_block_analysis_kernel);
-    const int sch = frames_per_workgroup(L, C, slots, 0);
-    hipLaunchKernelGGL(stream_block_analysis_kernel, dim3((unsigned)((L + sch - 1) / sch), C), dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, L, sch);
+    const Chunks ch = chunks_for<stream_block_analysis_kernel>(L, C, 0);
+    hipLaunchKernelGGL(stream_block_analysis_kernel, ch.grid, dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, L, ch.len);
 }
 void launch_stream_block_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, const float* prev_in, float* prev_out, float* out,
                                    int C, int L, hipStream_t s)
 {
-    static const int slots = resident_slots((const void*)stream_block_synthesis_kernel<false>);
-    const int ich = frames_per_workgroup(L, C, slots, 1);
-    const dim3 grid((unsigned)((L + ich - 1) / ich), C);
-    if (mix == 1.f) hipLaunchKernelGGL(stream_block_synthesis_kernel<false>, grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ich);
-    else hipLaunchKernelGGL(stream_block_synthesis_kernel<true>, grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ich);
+    const Chunks ch = chunks_for<stream_block_synthesis_kernel<false>>(L, C, 1);
+    if (mix == 1.f) hipLaunchKernelGGL(stream_block_synthesis_kernel<false>, ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len);
+    else hipLaunchKernelGGL(stream_block_synthesis_kernel<true>, ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len);
 }
 
 // ------------------------------------------------------------------------------ offline DSP, one segment of a clip
 // The offline pair for frames [ta, te) of a clip of T = 1 + n / 1024 frames (bsrnn_separate_long): the clip is transformed segment after
-// segment, so nothing here grows with the clip.  Per frame the arithmetic is that of stft_kernel<false> / istft_fused_kernel, in their
-// order: given the same samples / spectra, a segment's rows and hops are bit-identical to the same frames of the one-shot kernels.
+// segment, so nothing here grows with the clip.  Both kernels run the shared walks (stft_walk / istft_walk), like stft_kernel<false> /
+// istft_fused_kernel: given the same samples / spectra, a segment's rows and hops are bit-identical to the same frames of the one-shot kernels.
 //
 // Analysis: padded sample i of frame t is sample t*1024 + i - 1024 of the WHOLE clip, reflected at 0 and at n - 1 (never at a segment
 // edge).  `src` is either the whole clip (base = 0, stride = n) or a staged window of it that starts at clip sample `base` (rows `stride`
@@ -711,45 +729,19 @@ __global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_segment_kernel(FftTabl
 {
     __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
     const int tid = threadIdx.x;
-    const Twiddles twd = load_twiddles<false>(tb.tw1024, tid);
-    const SplitCtx spl = load_split(tb, tid, false);
     const int r = blockIdx.y;
     const int t0 = ta + blockIdx.x * sch;
     const int t1 = (t0 + sch < te) ? t0 + sch : te;
     const float* src = wave + (size_t)r * stride;
-    float2 win[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) win[k] = make_float2(tb.hann[2 * (tid + 256 * k)], tb.hann[2 * (tid + 256 * k) + 1]);
-    auto sample2 = [&](int t, int c) {
-        float v[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            int64_t idx = (int64_t)t * HOPS + 2 * c + e - NFFT / 2;
-            if (idx < 0) idx = -idx;
-            if (idx >= n) idx = 2 * (n - 1) - idx;
-            v[e] = src[idx - base];
-        }
-        return make_float2(v[0], v[1]);
-    };
-    float2 raw[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) raw[k] = sample2(t0, tid + 256 * k);
-    for (int t = t0; t < t1; ++t) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) z0[tid + 256 * k] = make_float2(raw[k].x * win[k].x, raw[k].y * win[k].y);
-        __syncthreads();
-        raw[0] = raw[2]; raw[1] = raw[3];
-        { const int tn = t + 1 < t1 ? t + 1 : t; raw[2] = sample2(tn, tid + 512); raw[3] = sample2(tn, tid + 768); }      // (no branch: after the last frame a dummy reload)
-        const float2* Z = fft1024<false>(z0, z1, twd, tid);
-        rfft_split_store(Z, spl, X + ((size_t)r * (te - ta) + (t - ta)) * tb.ld, tid);
-        __syncthreads();                          // Z (= z1) is overwritten by the next frame's first pass
-    }
+    auto sample2 = [&](int t, int c) { return reflected_sample2(src, n, base, t, c); };
+    auto row = [&](int t) { return X + ((size_t)r * (te - ta) + (t - ta)) * tb.ld; };
+    stft_walk(tb, z0, z1, tid, t0, t1, sample2, row);
 }
 
 // Synthesis: Y = the spectra of the segment's L = te - ta frames (segment-local rows).  Output hop b of the clip is the first half of
 // frame b + 1 plus the second half of frame b, so the segment completes hops [max(ta - 1, 0), te - 1): every frame but the clip's first
 // completes one.  A workgroup walks the frames [a0, a1) that complete its hops with the windowed second half of the frame in front in
-// registers: recomputed from that frame like istft_fused_kernel does - or, for the segment's first frame when the clip has frames in
+// registers: recomputed from that frame (istft_walk's peeled frame, as in istft_fused_kernel) - or, for the segment's first frame when the clip has frames in
 // front of it (carry_in != null), read from carry_in [R][1024], where the previous segment's launch left exactly those registers
 // (sample j of the windowed and scaled second half at [r][j]).  The workgroup that walks frame L - 1 leaves carry_out likewise (another
 // set than carry_in).  `out` points at the segment's first hop of row 0, rows out_stride floats apart.
@@ -758,53 +750,20 @@ __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void istft_segment_kernel(FftTa
 {
     __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
     const int tid = threadIdx.x;
-    const Twiddles twd = load_twiddles<true>(tb.tw1024, tid);
-    const SplitCtx spl = load_split(tb, tid, true);
     const int r = blockIdx.y;
     const int f0 = carry_in ? 0 : 1;                                  // the first frame that completes a hop (local hop = frame - f0)
     const int a0 = f0 + blockIdx.x * ich;
     const int a1 = (a0 + ich < L) ? a0 + ich : L;                     // (a one-frame first segment: a0 = a1 = 1, the carry only)
-    const float sc = 1.0f / 1024.0f;
-    float2 wlo[2], whi[2], env[2], carry[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int c = tid + 256 * k;
-        wlo[k] = make_float2(tb.hann[2 * c] * sc, tb.hann[2 * c + 1] * sc);
-        whi[k] = make_float2(tb.hann[2 * c + HOPS] * sc, tb.hann[2 * c + 1 + HOPS] * sc);
-        env[k] = make_float2(tb.inv_env[2 * c], tb.inv_env[2 * c + 1]);
-        carry[k] = make_float2(0.f, 0.f);
-    }
     const float* Yr = Y + (size_t)r * L * tb.ld;
     float* o = out + (size_t)r * out_stride;
-    MergeRegs mr;
-    // The frame in front of the range only fills the carry; it is peeled so that the loop body has no branch around its loads and stores
-    auto frame = [&](int t, auto first) {
-        irfft_store(mr, spl, z0, tid);
-        __syncthreads();
-        irfft_load<false>(Yr + (size_t)(t + 1 < a1 ? t + 1 : t) * tb.ld, spl, mr, tid);      // (after the last frame: a dummy reload)
-        const float2* z = fft1024<true>(z0, z1, twd, tid);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int c = tid + 256 * k;
-            const float2 a = z[c], b = z[c + 512];
-            if (!decltype(first)::value) {
-                // same operation order as istft_fused_kernel: (frame * 1/1024 * window) summed, then / envelope
-                const float2 v = make_float2((a.x * wlo[k].x + carry[k].x) * env[k].x, (a.y * wlo[k].y + carry[k].y) * env[k].y);
-                *reinterpret_cast<float2*>(o + (size_t)(t - f0) * HOPS + 2 * c) = v;
-            }
-            carry[k] = make_float2(b.x * whi[k].x, b.y * whi[k].y);
-        }
-        __syncthreads();                          // z (= z1) is overwritten by the next frame's first pass
-    };
+    auto spectrum = [&](int t) { return Yr + (size_t)t * tb.ld; };
+    auto hop = [&](int t) { return o + (size_t)(t - f0) * HOPS; };
+    float2 carry[2];
     if (a0 == 0) {
-        irfft_load<false>(Yr, spl, mr, tid);
 #pragma unroll
         for (int k = 0; k < 2; ++k) carry[k] = *reinterpret_cast<const float2*>(carry_in + (size_t)r * HOPS + 2 * (tid + 256 * k));
-    } else {
-        irfft_load<false>(Yr + (size_t)(a0 - 1) * tb.ld, spl, mr, tid);
-        frame(a0 - 1, std::true_type());
     }
-    for (int t = a0; t < a1; ++t) frame(t, std::false_type());
+    istft_walk(tb, z0, z1, tid, a0, a1, spectrum, hop, a0 > 0, carry);
     if (a1 == L) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) *reinterpret_cast<float2*>(carry_out + (size_t)r * HOPS + 2 * (tid + 256 * k)) = carry[k];
@@ -813,24 +772,21 @@ __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void istft_segment_kernel(FftTa
 
 void launch_stft_segment(const FftTables& tb, const float* src, int64_t stride, int64_t base, float* X, int R, int64_t n, int ta, int te, hipStream_t s)
 {
-    static const int slots = resident_slots((const void*)stft_segment_kernel);
-    const int sch = frames_per_workgroup(te - ta, R, slots, 0);
-    hipLaunchKernelGGL(stft_segment_kernel, dim3((unsigned)((te - ta + sch - 1) / sch), R), dim3(256), 0, s, tb, src, X, n, base, stride, ta, te, sch);
+    const Chunks ch = chunks_for<stft_segment_kernel>(te - ta, R, 0);
+    hipLaunchKernelGGL(stft_segment_kernel, ch.grid, dim3(256), 0, s, tb, src, X, n, base, stride, ta, te, ch.len);
 }
 void launch_istft_segment(const FftTables& tb, const float* Y, float* out, int64_t out_stride, const float* carry_in, float* carry_out, int R, int L,
                           hipStream_t s)
 {
-    static const int slots = resident_slots((const void*)istft_segment_kernel);
     const int hops = L - (carry_in ? 0 : 1);                           // 0: a one-frame first segment (one workgroup per row leaves the carry)
-    const int ich = frames_per_workgroup(hops > 0 ? hops : 1, R, slots, 1);
-    const dim3 grid((unsigned)(hops > 0 ? (hops + ich - 1) / ich : 1), R);
-    hipLaunchKernelGGL(istft_segment_kernel, grid, dim3(256), 0, s, tb, Y, out, out_stride, carry_in, carry_out, L, ich);
+    const Chunks ch = chunks_for<istft_segment_kernel>(hops > 0 ? hops : 1, R, 1);
+    hipLaunchKernelGGL(istft_segment_kernel, ch.grid, dim3(256), 0, s, tb, Y, out, out_stride, carry_in, carry_out, L, ch.len);
 }
 
 // ------------------------------------------------------------------------------ offline DSP, rows of different lengths
 // The offline pair for a batch whose row r holds lens[r] samples (bsrnn_separate_ragged): T_r = 1 + lens[r] / 1024 frames of its own inside a
-// rectangle of Tmax = max T_r frames per row.  Per frame / hop the arithmetic is that of stft_kernel<false> / istft_fused_kernel, in their
-// order: a frame or a hop that both compute has the same bits.  Row and chunk belong to the workgroup, so every condition below is
+// rectangle of Tmax = max T_r frames per row.  Both kernels run the shared walks (stft_walk / istft_walk), like stft_kernel<false> /
+// istft_fused_kernel: a frame or a hop that both compute has the same bits.  Row and chunk belong to the workgroup, so every condition below is
 // workgroup-uniform, and each walk is one loop over the real frames / hops (no branch inside it) and one over the padded ones.
 //
 // Analysis: frames t < T_r of row r come from wave + r * stride, reflected at 0 and at lens[r] - 1 (never at the stride: samples
@@ -849,36 +805,10 @@ __global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_ragged_kernel(FftTable
     const int t1 = te < Tr ? te : Tr;                                 // its real frames: [t0, t1), none when t1 <= t0
     float* Xr = X + (size_t)r * Tmax * tb.ld;
     if (t0 < t1) {
-        const Twiddles twd = load_twiddles<false>(tb.tw1024, tid);
-        const SplitCtx spl = load_split(tb, tid, false);
         const float* src = wave + (size_t)r * stride;
-        float2 win[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) win[k] = make_float2(tb.hann[2 * (tid + 256 * k)], tb.hann[2 * (tid + 256 * k) + 1]);
-        auto sample2 = [&](int t, int c) {
-            float v[2];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                int64_t idx = (int64_t)t * HOPS + 2 * c + e - NFFT / 2;
-                if (idx < 0) idx = -idx;
-                if (idx >= n) idx = 2 * (n - 1) - idx;
-                v[e] = src[idx];
-            }
-            return make_float2(v[0], v[1]);
-        };
-        float2 raw[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) raw[k] = sample2(t0, tid + 256 * k);
-        for (int t = t0; t < t1; ++t) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) z0[tid + 256 * k] = make_float2(raw[k].x * win[k].x, raw[k].y * win[k].y);
-            __syncthreads();
-            raw[0] = raw[2]; raw[1] = raw[3];
-            { const int tn = t + 1 < t1 ? t + 1 : t; raw[2] = sample2(tn, tid + 512); raw[3] = sample2(tn, tid + 768); }      // (no branch: after the last frame a dummy reload)
-            const float2* Z = fft1024<false>(z0, z1, twd, tid);
-            rfft_split_store(Z, spl, Xr + (size_t)t * tb.ld, tid);
-            __syncthreads();                          // Z (= z1) is overwritten by the next frame's first pass
-        }
+        auto sample2 = [&](int t, int c) { return reflected_sample2(src, n, 0, t, c); };
+        auto row = [&](int t) { return Xr + (size_t)t * tb.ld; };
+        stft_walk(tb, z0, z1, tid, t0, t1, sample2, row);
     }
     // the padded frames of the chunk (rows of X start 16-byte aligned and ld is a multiple of 4: commit_host.h, band_columns)
     for (int t = t0 > t1 ? t0 : t1; t < te; ++t) {
@@ -888,7 +818,7 @@ __global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_ragged_kernel(FftTable
 }
 
 // Synthesis: Y = the spectra of the rectangle, [R * Tmax][ld]; row r of `out` starts at out + r * out_stride and holds Tmax - 1 hops.  Hops
-// b < T_r - 1 are computed from frames b and b + 1 like istft_fused_kernel's; hops T_r - 1 <= b < Tmax - 1 are STORED as zeros, not
+// b < T_r - 1 are computed from frames b and b + 1 by istft_walk, as istft_fused_kernel's are; hops T_r - 1 <= b < Tmax - 1 are STORED as zeros, not
 // computed (hop T_r - 1 would add the row's last real second half to a padded frame).  A workgroup whose chunk lies past the row's end does
 // no FFT.
 __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void istft_ragged_kernel(FftTables tb, const float* __restrict__ Y, float* __restrict__ out, int64_t out_stride,
@@ -903,42 +833,11 @@ __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void istft_ragged_kernel(FftTab
     const int b1 = be < Tr - 1 ? be : Tr - 1;                         // its real hops: [b0, b1) <- frames b0 .. b1, none when b1 <= b0
     float* o = out + (size_t)r * out_stride;
     if (b0 < b1) {
-        const Twiddles twd = load_twiddles<true>(tb.tw1024, tid);
-        const SplitCtx spl = load_split(tb, tid, true);
-        const float sc = 1.0f / 1024.0f;
-        float2 wlo[2], whi[2], env[2], carry[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int c = tid + 256 * k;
-            wlo[k] = make_float2(tb.hann[2 * c] * sc, tb.hann[2 * c + 1] * sc);
-            whi[k] = make_float2(tb.hann[2 * c + HOPS] * sc, tb.hann[2 * c + 1 + HOPS] * sc);
-            env[k] = make_float2(tb.inv_env[2 * c], tb.inv_env[2 * c + 1]);
-            carry[k] = make_float2(0.f, 0.f);
-        }
         const float* Yr = Y + (size_t)r * Tmax * tb.ld;
-        MergeRegs mr;
-        irfft_load<false>(Yr + (size_t)b0 * tb.ld, spl, mr, tid);
-        // The first frame of the chunk only fills the carry; it is peeled so that the loop body has no branch around its loads and stores
-        auto frame = [&](int t, auto first) {
-            irfft_store(mr, spl, z0, tid);
-            __syncthreads();
-            irfft_load<false>(Yr + (size_t)(t < b1 ? t + 1 : t) * tb.ld, spl, mr, tid);      // (after the last frame: a dummy reload)
-            const float2* z = fft1024<true>(z0, z1, twd, tid);
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int c = tid + 256 * k;
-                const float2 a = z[c], b = z[c + 512];
-                if (!decltype(first)::value) {
-                    // same operation order as istft_fused_kernel: (frame * 1/1024 * window) summed, then / envelope
-                    const float2 v = make_float2((a.x * wlo[k].x + carry[k].x) * env[k].x, (a.y * wlo[k].y + carry[k].y) * env[k].y);
-                    *reinterpret_cast<float2*>(o + (size_t)(t - 1) * HOPS + 2 * c) = v;
-                }
-                carry[k] = make_float2(b.x * whi[k].x, b.y * whi[k].y);
-            }
-            __syncthreads();                          // z (= z1) is overwritten by the next frame's first pass
-        };
-        frame(b0, std::true_type());
-        for (int t = b0 + 1; t <= b1; ++t) frame(t, std::false_type());
+        auto spectrum = [&](int t) { return Yr + (size_t)t * tb.ld; };
+        auto hop = [&](int t) { return o + (size_t)(t - 1) * HOPS; };
+        float2 carry[2];
+        istft_walk(tb, z0, z1, tid, b0 + 1, b1 + 1, spectrum, hop, true, carry);
     }
     // the padded hops of the chunk, at the addresses and with the 8-byte stores of the real ones
     for (int b = b0 > b1 ? b0 : b1; b < be; ++b) {
@@ -949,16 +848,14 @@ __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void istft_ragged_kernel(FftTab
 
 void launch_stft_ragged(const FftTables& tb, const float* wave, int64_t stride, const int64_t* lens, float* X, int R, int Tmax, hipStream_t s)
 {
-    static const int slots = resident_slots((const void*)stft_ragged_kernel);
-    const int sch = frames_per_workgroup(Tmax, R, slots, 0);
-    hipLaunchKernelGGL(stft_ragged_kernel, dim3((unsigned)((Tmax + sch - 1) / sch), R), dim3(256), 0, s, tb, wave, X, stride, lens, Tmax, sch);
+    const Chunks ch = chunks_for<stft_ragged_kernel>(Tmax, R, 0);
+    hipLaunchKernelGGL(stft_ragged_kernel, ch.grid, dim3(256), 0, s, tb, wave, X, stride, lens, Tmax, ch.len);
 }
 void launch_istft_ragged(const FftTables& tb, const float* Y, float* out, int64_t out_stride, const int64_t* lens, int R, int Tmax, hipStream_t s)
 {
     if (Tmax < 2) return;
-    static const int slots = resident_slots((const void*)istft_ragged_kernel);
-    const int ich = frames_per_workgroup(Tmax - 1, R, slots, 1);
-    hipLaunchKernelGGL(istft_ragged_kernel, dim3((unsigned)((Tmax - 1 + ich - 1) / ich), R), dim3(256), 0, s, tb, Y, out, out_stride, lens, Tmax, ich);
+    const Chunks ch = chunks_for<istft_ragged_kernel>(Tmax - 1, R, 1);
+    hipLaunchKernelGGL(istft_ragged_kernel, ch.grid, dim3(256), 0, s, tb, Y, out, out_stride, lens, Tmax, ch.len);
 }
 
 }  // namespace bsrnn
