@@ -358,6 +358,30 @@ int64_t bsrnn_workspace_rows(const bsrnn_ctx* ctx);
 #define BSRNN_N_METRICS       8
 int  bsrnn_evaluate(bsrnn_ctx* ctx, const float* mix_dev, const float* speech_dev, int32_t R, int64_t n,
                     float* est_out_dev, double* metrics_host, void* stream);
+/* bsrnn_evaluate_ragged = bsrnn_evaluate for n_clips clips of DIFFERENT lengths in one call (a validation set).  The unit of the metrics is
+ * a CLIP - one sample of the reference: all rows of one file, all of one length; its validation loop averages per-clip numbers
+ * (train.py:132-150) - so the call returns one set of the eight metrics per clip, metrics_host [n_clips][BSRNN_N_METRICS], each what
+ * bsrnn_evaluate gives for that clip alone (to rounding: the kernels are chosen for the whole batch).  Nothing is summed across clips:
+ * INPUT_SDR sums over the rows of its own clip at each of the clip's sample positions.
+ *   - Clip c owns clip_rows_host[c] >= 1 consecutive rows (NULL: one row per clip) of clip_lens_host[c] samples each, 1024 < length <=
+ *     wave_stride; R = the sum of the row counts.  mix_dev and speech_dev hold R rows, wave_stride floats apart; what lies behind a row's
+ *     samples is never read, in either buffer.
+ *   - With n = the clip's length, T = 1 + n / 1024 and n_est = (T - 1) * 1024: the L1 means divide by rows * n_est and rows * 1025 * T,
+ *     INPUT_SDR averages over the clip's n positions, SDR and SISDR are means over the clip's rows, SEPARATION_DB runs over the clip's rows.
+ *   - est_out_dev (optional) is [R, (Tmax-1)*1024] as bsrnn_separate_ragged writes it (Tmax = the largest T): every row's estimate, then
+ *     zeros to the end of the row.  It must not overlap the R * wave_stride floats of mix_dev or speech_dev under either policy (BSRNN_EARG).
+ *   - Synchronous; the call waits once, for the partial sums (under BSRNN_RANGE_EXACT bsrnn_separate_ragged inside it waits for the guard as
+ *     well).  Range policy as bsrnn_evaluate: the guard is always handled before the numbers return; a re-run repeats the whole flow in
+ *     exact fp32 from the same inputs and lengths.
+ *   - The two host arrays are the caller's again at return.  The clip table, the partial sums and (without est_out_dev) the estimate live in
+ *     grow-only blocks of the context: a second call that fits allocates nothing (bsrnn_debug_counter(0)).  Cost and memory as
+ *     bsrnn_separate_ragged: padding is paid for in the model, so batch clips of similar length (the Python layer's evaluate_many does).
+ * BSRNN_EARG, before any device work (also on a host-only context, in front of its BSRNN_ESTATE): a null ctx, mix_dev, speech_dev,
+ * clip_lens_host or metrics_host; n_clips < 1; a row count < 1; a length <= 1024 or > wave_stride (the text names the clip and the value);
+ * R * Tmax beyond bsrnn_separate_ragged's limit. */
+int  bsrnn_evaluate_ragged(bsrnn_ctx* ctx, const float* mix_dev, const float* speech_dev, int64_t wave_stride,
+                           const int64_t* clip_lens_host, const int32_t* clip_rows_host, int32_t n_clips,
+                           float* est_out_dev, double* metrics_host, void* stream);
 
 /* ---- streaming (infer-streaming.py:84-147; speech-ladspa-onnx.cpp:171-267) -------------
  * A bsrnn_stream owns, on the device, the sliding 2048-sample analysis buffer, the LSTM

@@ -25,7 +25,7 @@ SYMBOLS = [
     "bsrnn_linear_group_train_forward", "bsrnn_linear_group_train_backward", "bsrnn_train_reduction_layout",
     "bsrnn_set_range_policy", "bsrnn_get_range_policy", "bsrnn_overlap_state", "bsrnn_debug_peek", "bsrnn_debug_counter",
     "bsrnn_stream_process", "bsrnn_stream_reserve", "bsrnn_separate_long", "bsrnn_separate_long_host", "bsrnn_workspace_rows",
-    "bsrnn_separate_ragged",
+    "bsrnn_separate_ragged", "bsrnn_evaluate_ragged",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 METRIC_NAMES = ("loss", "sdr", "input_sdr", "sisdr", "l1_time", "l1_re", "l1_im", "separation_db")   # BSRNN_M_* order
@@ -108,6 +108,7 @@ def _load():
         "bsrnn_copy_d2h": (C.c_int, [vp, vp, vp, i64]),
         "bsrnn_sync": (C.c_int, [vp, vp]),
         "bsrnn_evaluate": (C.c_int, [vp, vp, vp, i32, i64, vp, C.POINTER(C.c_double), vp]),
+        "bsrnn_evaluate_ragged": (C.c_int, [vp, vp, vp, i64, vp, vp, i32, vp, C.POINTER(C.c_double), vp]),
         "bsrnn_io_count": (C.c_int, []),
         "bsrnn_io_info": (C.c_int, [vp, i32, i32, C.POINTER(C.c_char_p), C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]),
     }

@@ -450,6 +450,83 @@ class BSRNN(nn.Module):
             out["x_time"] = est if mix.is_cuda else est.cpu()
         return out
 
+    def evaluate_ragged(self, mix, speech, lengths, clip_rows=None, return_estimate=False):
+        """`evaluate` for clips of different lengths in one call: mix, speech [R, n_max]; clip c owns clip_rows[c] consecutive rows (None:
+        one row per clip) of lengths[c] samples each, 1024 < lengths[c] <= n_max; what lies behind a row's samples is never read.  Returns
+        a list of dicts, one per clip, each what `evaluate` gives for that clip alone (to rounding): a clip is the unit of the reference's
+        metrics, nothing is summed across clips (include/bsrnn_hip.h, bsrnn_evaluate_ragged).  With return_estimate each dict also has
+        "x_time": the clip's rows cut to its own (n // 1024) * 1024 samples."""
+        if (not isinstance(mix, torch.Tensor) or not isinstance(speech, torch.Tensor) or mix.dim() != 2
+                or tuple(mix.shape) != tuple(speech.shape)):
+            raise ValueError("evaluate_ragged: expected mix and speech [R, n_max] of the same shape, got %s and %s" % (
+                tuple(mix.shape) if isinstance(mix, torch.Tensor) else type(mix).__name__,
+                tuple(speech.shape) if isinstance(speech, torch.Tensor) else type(speech).__name__))
+        R, n_max = mix.shape
+        try:
+            lens = [int(x) for x in lengths]
+            rows = [1] * len(lens) if clip_rows is None else [int(x) for x in clip_rows]
+        except TypeError:
+            raise ValueError("evaluate_ragged: lengths and clip_rows must be sequences of ints") from None
+        if not lens or len(rows) != len(lens):
+            raise ValueError("evaluate_ragged: %d lengths and %d row counts, need one of each per clip and at least one clip" % (len(lens), len(rows)))
+        for c, (n, ch) in enumerate(zip(lens, rows)):
+            if ch < 1:
+                raise ValueError("evaluate_ragged: clip %d has %d rows, need at least 1" % (c, ch))
+            if not _spec.HOP < n <= n_max:
+                raise ValueError("evaluate_ragged: clip %d has %d samples, need 1024 < length <= %d" % (c, n, n_max))
+        if sum(rows) != R:
+            raise ValueError("evaluate_ragged: the clips own %d rows, mix has %d" % (sum(rows), R))
+        dev = self._device_for(mix)
+        m, s = self._prep(mix, dev), self._prep(speech, dev)
+        n_clips = len(lens)
+        vals = (ctypes.c_double * (n_clips * len(_native.METRIC_NAMES)))()
+        with torch.cuda.device(dev):
+            ctx = self._context(dev)
+            est = torch.empty((R, (max(lens) // _spec.HOP) * _spec.HOP), device=dev, dtype=torch.float32) if return_estimate else None
+            _check(_lib.bsrnn_evaluate_ragged(ctx, _ptr(m), _ptr(s), n_max, (ctypes.c_int64 * n_clips)(*lens), (ctypes.c_int32 * n_clips)(*rows),
+                                              n_clips, _ptr(est) if return_estimate else None, vals, _stream_ptr(dev)))
+        out, r0, nm = [], 0, len(_native.METRIC_NAMES)
+        for c, (n, ch) in enumerate(zip(lens, rows)):
+            d = {k: vals[c * nm + i] for i, k in enumerate(_native.METRIC_NAMES)}
+            if return_estimate:
+                x = est[r0:r0 + ch, :(n // _spec.HOP) * _spec.HOP].contiguous()
+                d["x_time"] = x if mix.is_cuda else x.cpu()
+            out.append(d)
+            r0 += ch
+        return out
+
+    def evaluate_many(self, pairs, max_rows=64, max_padding=0.25):
+        """`evaluate` for a list of (mix, speech) pairs of different lengths, batched: each tensor [n] or [ch, n] (n > 1024), both of a pair
+        of the same rank and channel count and cut to their common length.  `spec.ragged_buckets` groups the pairs exactly as
+        `separate_many` groups clips; each bucket is packed into two [rows, n_max] buffers and runs as ONE `evaluate_ragged` call.
+        Returns the per-pair metric dicts in input order."""
+        pairs = list(pairs)
+        shapes = []
+        for i, p in enumerate(pairs):
+            ok = isinstance(p, (tuple, list)) and len(p) == 2 and all(isinstance(t, torch.Tensor) and t.dim() in (1, 2) for t in p)
+            ok = ok and p[0].dim() == p[1].dim() and (p[0].dim() == 1 or (p[0].shape[0] == p[1].shape[0] and p[0].shape[0] >= 1))
+            n = min(p[0].shape[-1], p[1].shape[-1]) if ok else 0
+            if not ok or n <= _spec.HOP:
+                raise ValueError("evaluate_many: pair %d must be (mix, speech) tensors, both [n] or both [ch, n], with n > 1024" % i)
+            shapes.append((1 if p[0].dim() == 1 else p[0].shape[0], n))
+        buckets = _spec.ragged_buckets([_spec.n_frames(n) for _, n in shapes], [ch for ch, _ in shapes], max_rows, max_padding)
+        if not pairs:
+            return []
+        dev = next((t.device for p in pairs for t in p if t.is_cuda), None) or self._device_for(pairs[0][0])
+        results = [None] * len(pairs)
+        for bucket in buckets:
+            rows = [shapes[i][0] for i in bucket]
+            lens = [shapes[i][1] for i in bucket]
+            bufs = torch.empty((2, sum(rows), max(lens)), device=dev, dtype=torch.float32)    # (behind a row's end nothing is read)
+            r0 = 0
+            for i, ch, n in zip(bucket, rows, lens):
+                for k in range(2):
+                    bufs[k, r0:r0 + ch, :n] = pairs[i][k].detach().reshape(ch, -1)[:, :n].to(device=dev, dtype=torch.float32)
+                r0 += ch
+            for i, d in zip(bucket, self.evaluate_ragged(bufs[0], bufs[1], lens, rows)):
+                results[i] = d
+        return results
+
     # ------------------------------------------------------------------ measurement
     def set_profiling(self, on, device=None):
         """on: False/True (all stages) or an iterable of stage names to bracket with events."""

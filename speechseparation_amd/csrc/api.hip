@@ -6,6 +6,7 @@
 #include "kernels.h"
 #include "commit_host.h"
 #include "plan_host.h"
+#include "metrics_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -196,6 +197,20 @@ struct bsrnn_ctx {
         unsigned calls = 0;
         hipEvent_t ev[RG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
     } rg;
+
+    // Ragged evaluate (bsrnn_evaluate_ragged): the metric kernels' table [R int64 row lengths | n_clips MetricClip] travels like the block
+    // above - pinned mirrors used in turn, a mirror rewritten only after the copy that read it has completed - and their scratch is one
+    // device block [partial sums, doubles | the estimate when the caller wants none] with a pinned mirror of the partials for the one
+    // download of a call.  All grow-only: a call that fits allocates nothing.
+    struct EvalRagged {
+        size_t cap = 0;                               // bytes of the table on the device and of each mirror
+        char *d = nullptr, *h = nullptr;
+        unsigned calls = 0;
+        hipEvent_t ev[RG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+        size_t part_cap = 0, est_cap = 0;             // doubles / floats the scratch holds
+        double *d_part = nullptr, *h_part = nullptr;
+        float* d_est = nullptr;
+    } er;
 };
 
 struct bsrnn_stream {
@@ -951,6 +966,13 @@ static void destroy_now(bsrnn_ctx* c)
     if (c->rg.h) (void)hipHostFree(c->rg.h);
     for (hipEvent_t e : c->rg.ev)
         if (e) (void)hipEventDestroy(e);
+    if (c->er.d) (void)hipFree(c->er.d);
+    if (c->er.h) (void)hipHostFree(c->er.h);
+    if (c->er.d_part) (void)hipFree(c->er.d_part);
+    if (c->er.h_part) (void)hipHostFree(c->er.h_part);
+    if (c->er.d_est) (void)hipFree(c->er.d_est);
+    for (hipEvent_t e : c->er.ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->ev_ovl_fork) (void)hipEventDestroy(c->ev_ovl_fork);
     if (c->ev_ovl_join) (void)hipEventDestroy(c->ev_ovl_join);
     free_ovl_tables(c);
@@ -1657,7 +1679,7 @@ int bsrnn_separate_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_stride, 
     if (q.why == RAGGED_LONG)
         return fail(BSRNN_EARG, "bsrnn_separate_ragged: row %d has %lld samples, more than the row stride of %lld", q.bad_row, (long long)q.bad_len,
                     (long long)wave_stride);
-    if (q.Tmax * R > INT32_MAX / 2) return fail(BSRNN_EARG, "bsrnn_separate_ragged: %d rows x %lld frames is too many frame rows for one call", R, (long long)q.Tmax);
+    if (ragged_too_many(R, q.Tmax)) return fail(BSRNN_EARG, "bsrnn_separate_ragged: %d rows x %lld frames is too many frame rows for one call", R, (long long)q.Tmax);
     // the re-run (finish_call) reads the waveform again
     if (c->range_policy == BSRNN_RANGE_EXACT &&
         ranges_overlap(wave, (size_t)R * wave_stride * sizeof(float), wave_out, (size_t)R * q.out_stride * sizeof(float)))
@@ -1972,6 +1994,143 @@ int bsrnn_evaluate(bsrnn_ctx* c, const float* mix, const float* speech, int32_t 
     // the default policy (finish_call: a structural fall-back, or the exact-fp32 kernels for an operand that left the fp16 range)
     if ((rc = run())) return cleanup(rc);
     return cleanup(finish_call(c, s, run, true));
+}
+
+
+// --------------------------------------------------------------------------- ragged evaluate: the metrics per clip of a ragged batch
+// A clip is the unit of the reference's metrics (one `sample`: all rows of one file, one length; validate.py and train.py:132-150 average
+// per-clip numbers), so a ragged evaluate returns the eight numbers PER CLIP, each what bsrnn_evaluate gives for that clip alone: the
+// reference's `sdr2` sums over the rows of its own clip, which all have one length, and nothing is summed across clips.
+// Flow: bsrnn_separate_ragged(mix) with the per-clip lengths expanded to rows (Yf keeps the estimate's spectrum, padded frames zero) ->
+// the clean signal through the ragged analysis into Xf -> the four ragged metric kernels (alpha of the SI-SDR pass formed on the device)
+// -> one download of the partial sums -> metrics_host.h per clip, in a fixed order.
+static_assert(CM_LOSS == BSRNN_M_LOSS && CM_SDR == BSRNN_M_SDR && CM_INPUT_SDR == BSRNN_M_INPUT_SDR && CM_SISDR == BSRNN_M_SISDR &&
+              CM_L1_TIME == BSRNN_M_L1_TIME && CM_L1_RE == BSRNN_M_L1_RE && CM_L1_IM == BSRNN_M_L1_IM &&
+              CM_SEPARATION_DB == BSRNN_M_SEPARATION_DB && CM_COUNT == BSRNN_N_METRICS && CLIP_ROW_Q == METRIC_TIME_Q + 2, "metrics_host.h");
+
+// The context's table block and scratch (bsrnn_ctx::EvalRagged) for a call of these sizes; grow-only
+static int eval_ragged_reserve(bsrnn_ctx* c, size_t table_bytes, size_t n_part, size_t n_est)
+{
+    bsrnn_ctx::EvalRagged& er = c->er;
+    if (table_bytes <= er.cap && n_part <= er.part_cap && n_est <= er.est_cap) return 0;
+    HIP_TRY(hipDeviceSynchronize());                                  // queued copies read the old mirrors, queued kernels the old blocks
+    auto grown = [](size_t n) { return (n + n / 2 + 255) & ~size_t(255); };
+    if (table_bytes > er.cap) {
+        if (er.d) { (void)hipFree(er.d); (void)hipHostFree(er.h); er.d = er.h = nullptr; er.cap = 0; }
+        const size_t cap = grown(table_bytes);
+        g_dbg[DBG_ALLOC] += 2;
+        HIP_TRY(hipHostMalloc((void**)&er.h, bsrnn_ctx::RG_SLOTS * cap, hipHostMallocDefault));
+        const hipError_t e = hipMalloc((void**)&er.d, cap);
+        if (e != hipSuccess) { (void)hipHostFree(er.h); er.h = er.d = nullptr; return fail(BSRNN_EHIP, "hipMalloc: %s", hipGetErrorString(e)); }
+        for (hipEvent_t& ev : er.ev)
+            if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        er.cap = cap;
+    }
+    if (n_part > er.part_cap) {
+        if (er.d_part) { (void)hipFree(er.d_part); (void)hipHostFree(er.h_part); er.d_part = er.h_part = nullptr; er.part_cap = 0; }
+        const size_t cap = grown(n_part);
+        g_dbg[DBG_ALLOC] += 2;
+        HIP_TRY(hipHostMalloc((void**)&er.h_part, cap * sizeof(double), hipHostMallocDefault));
+        const hipError_t e = hipMalloc((void**)&er.d_part, cap * sizeof(double));
+        if (e != hipSuccess) { (void)hipHostFree(er.h_part); er.h_part = er.d_part = nullptr; return fail(BSRNN_EHIP, "hipMalloc: %s", hipGetErrorString(e)); }
+        er.part_cap = cap;
+    }
+    if (n_est > er.est_cap) {
+        if (er.d_est) { (void)hipFree(er.d_est); er.d_est = nullptr; er.est_cap = 0; }
+        const size_t cap = grown(n_est);
+        ++g_dbg[DBG_ALLOC];
+        const hipError_t e = hipMalloc((void**)&er.d_est, cap * sizeof(float));
+        if (e != hipSuccess) { er.d_est = nullptr; return fail(BSRNN_EHIP, "hipMalloc: %s", hipGetErrorString(e)); }
+        er.est_cap = cap;
+    }
+    return 0;
+}
+
+int bsrnn_evaluate_ragged(bsrnn_ctx* c, const float* mix, const float* speech, int64_t wave_stride, const int64_t* clip_lens_host,
+                          const int32_t* clip_rows_host, int32_t n_clips, float* est_out, double* metrics, void* stream)
+{
+    // arguments first, device or not (a host-only context answers them before BSRNN_ESTATE)
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!mix || !speech || !clip_lens_host || !metrics || n_clips < 1)
+        return fail(BSRNN_EARG, "bsrnn_evaluate_ragged: need a mixture, a clean signal, the clips' lengths, room for the metrics and n_clips >= 1, got n_clips = %d", n_clips);
+    std::vector<int64_t> row_lens;
+    std::vector<int> first_row;
+    const ClipShape q = clip_shape(clip_lens_host, clip_rows_host, n_clips, wave_stride, row_lens, first_row);
+    if (q.why == CLIPS_ROWS) return fail(BSRNN_EARG, "bsrnn_evaluate_ragged: clip %d has %lld rows, need at least 1", q.bad_clip, (long long)q.bad_value);
+    if (q.why == CLIPS_SHORT)
+        return fail(BSRNN_EARG, "bsrnn_evaluate_ragged: clip %d has %lld samples, need more than 1024 (reflect padding)", q.bad_clip, (long long)q.bad_value);
+    if (q.why == CLIPS_LONG)
+        return fail(BSRNN_EARG, "bsrnn_evaluate_ragged: clip %d has %lld samples, more than the row stride of %lld", q.bad_clip, (long long)q.bad_value,
+                    (long long)wave_stride);
+    if (q.why == CLIPS_MANY)
+        return fail(BSRNN_EARG, "bsrnn_evaluate_ragged: %lld rows x %lld frames is too many frame rows for one call", (long long)q.R, (long long)q.Tmax);
+    const int R = (int)q.R, T = (int)q.Tmax;
+    // the metrics read mix and speech after the estimate is written, and a re-run reads them again: whatever the policy
+    if (ranges_overlap(est_out, (size_t)R * q.out_stride * sizeof(float), mix, (size_t)R * wave_stride * sizeof(float)) ||
+        ranges_overlap(est_out, (size_t)R * q.out_stride * sizeof(float), speech, (size_t)R * wave_stride * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_evaluate_ragged: est_out must not overlap mix or speech (the metrics and a re-run of the call read them after the estimate is written)");
+    int rc = check_ready(c);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+
+    const int chunks = metric_time_chunks(q.out_stride), FB = std::min(T, 16), IB = 64;
+    const size_t n_time = (size_t)R * chunks * METRIC_TIME_Q, n_si = (size_t)R * chunks * 2, n_freq = (size_t)R * FB * 2, n_in = (size_t)n_clips * IB;
+    const size_t n_part = n_time + n_si + n_freq + n_in;
+    const size_t b_lens = (size_t)R * sizeof(int64_t), b_table = b_lens + (size_t)n_clips * sizeof(MetricClip);
+    if ((rc = eval_ragged_reserve(c, b_table, n_part, est_out ? 0 : (size_t)R * q.out_stride))) return rc;
+    bsrnn_ctx::EvalRagged& er = c->er;
+    float* est = est_out ? est_out : er.d_est;
+    {   // the table: mirror k is written again only when the copy of RG_SLOTS calls ago has completed (an event never recorded counts as complete)
+        const int k = (int)(er.calls++ % bsrnn_ctx::RG_SLOTS);
+        HIP_TRY(hipEventSynchronize(er.ev[k]));
+        char* h = er.h + (size_t)k * er.cap;
+        memcpy(h, row_lens.data(), b_lens);
+        MetricClip* mc = reinterpret_cast<MetricClip*>(h + b_lens);
+        for (int i = 0; i < n_clips; ++i) mc[i] = MetricClip{first_row[i], clip_rows_host ? clip_rows_host[i] : 1, clip_lens_host[i]};
+        HIP_TRY(hipMemcpyAsync(er.d, h, b_table, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(er.ev[k], s));
+    }
+    const int64_t* d_lens = reinterpret_cast<const int64_t*>(er.d);
+    const MetricClip* d_clips = reinterpret_cast<const MetricClip*>(er.d + b_lens);
+    double *p_time = er.d_part, *p_si = p_time + n_time, *p_freq = p_si + n_si, *p_in = p_freq + n_freq;
+
+    // a re-run sees the same table: the block on the device is not touched before the next call
+    auto run = [&]() -> int {
+        // x_time of every row and the estimate's spectrum (left in Yf, frame-major, padded frames zero)      m_dataset.py:186-195
+        if (int rc2 = bsrnn_separate_ragged(c, mix, wave_stride, row_lens.data(), est, R, stream)) return rc2;
+        // waveform_speech_freq: the clean signal through the same analysis (Xf is free once the mask launch ran)   :196
+        launch_stft_ragged(c->tb, speech, wave_stride, d_lens, c->Xf, R, T, s);
+        launch_metric_time_ragged(est, speech, mix, d_lens, R, T, q.out_stride, wave_stride, p_time, s);
+        launch_metric_sisdr_ragged(est, speech, d_lens, R, T, q.out_stride, wave_stride, p_time, p_si, s);
+        launch_metric_freq_ragged(c->tb, c->Yf, c->Xf, d_lens, R, T, p_freq, FB, s);
+        launch_metric_input_sdr_ragged(speech, mix, d_clips, n_clips, wave_stride, p_in, IB, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(er.h_part, er.d_part, n_part * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const double *h_time = er.h_part, *h_si = h_time + n_time, *h_freq = h_si + n_si, *h_in = h_freq + n_freq;
+        std::vector<double> rows;
+        for (int i = 0; i < n_clips; ++i) {
+            const int r0 = first_row[i], nr = clip_rows_host ? clip_rows_host[i] : 1;
+            rows.assign((size_t)nr * CLIP_ROW_Q, 0.0);
+            double re = 0, im = 0;
+            for (int r = 0; r < nr; ++r) {
+                const size_t row = (size_t)(r0 + r);
+                for (int j = 0; j < METRIC_TIME_Q; ++j) rows[(size_t)r * CLIP_ROW_Q + j] = add_in_order(h_time + row * chunks * METRIC_TIME_Q + j, chunks, METRIC_TIME_Q);
+                for (int j = 0; j < 2; ++j) rows[(size_t)r * CLIP_ROW_Q + METRIC_TIME_Q + j] = add_in_order(h_si + row * chunks * 2 + j, chunks, 2);
+                re += add_in_order(h_freq + row * FB * 2, FB, 2);
+                im += add_in_order(h_freq + row * FB * 2 + 1, FB, 2);
+            }
+            const int64_t n = clip_lens_host[i], Tc = ragged_frames(n);
+            finish_clip_metrics(rows.data(), nr, re, im, add_in_order(h_in + (size_t)i * IB, IB, 1), n, Tc, (Tc - 1) * HOPS,
+                                metrics + (size_t)i * BSRNN_N_METRICS);
+        }
+        return 0;
+    };
+    // A synchronous entry point: whatever the context's range policy, the guard word is handled before the metrics are returned, as in
+    // bsrnn_evaluate (finish_call: a structural fall-back, or the whole flow again on the exact-fp32 kernels from the same inputs and lengths)
+    if ((rc = run())) return rc;
+    return finish_call(c, s, run, true);
 }
 
 

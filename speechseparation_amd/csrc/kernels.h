@@ -286,5 +286,18 @@ void launch_metric_sisdr(const float* est, const float* speech, const float* alp
                          double* part /* [R][chunks][2] */, hipStream_t s);
 void launch_metric_input_sdr(const float* speech, const float* mix, int R, int64_t n, double* part /* [blocks] */, int blocks, hipStream_t s);
 void launch_metric_freq(const FftTables& tb, const float* Yf, const float* Sf, int M, double* part /* [blocks][2] */, int blocks, hipStream_t s);
+// The same for rows and clips of different lengths (bsrnn_evaluate_ragged): lens [R] the rows' lengths on the device (T_r = 1 + lens[r] / 1024
+// frames inside the rectangle R x Tmax, n_est_r = (T_r - 1) * 1024 samples), est rows out_stride floats apart, speech and mix rows wave_stride
+// floats apart.  Every slot of every partial array is written.  chunks = metric_time_chunks((Tmax - 1) * 1024).
+struct MetricClip { int first, rows; int64_t len; };                    // a clip: its first row, its rows, their common length
+void launch_metric_time_ragged(const float* est, const float* speech, const float* mix, const int64_t* lens, int R, int Tmax,
+                               int64_t out_stride, int64_t wave_stride, double* part /* [R][chunks][7] */, hipStream_t s);
+void launch_metric_sisdr_ragged(const float* est, const float* speech, const int64_t* lens, int R, int Tmax, int64_t out_stride,
+                                int64_t wave_stride, const double* time_part /* launch_metric_time_ragged's */, double* part /* [R][chunks][2] */,
+                                hipStream_t s);
+void launch_metric_input_sdr_ragged(const float* speech, const float* mix, const MetricClip* clips, int n_clips, int64_t wave_stride,
+                                    double* part /* [n_clips][blocks] */, int blocks, hipStream_t s);
+void launch_metric_freq_ragged(const FftTables& tb, const float* Yf, const float* Sf, const int64_t* lens, int R, int Tmax,
+                               double* part /* [R][blocks][2] */, int blocks, hipStream_t s);
 
 }  // namespace bsrnn

@@ -1,0 +1,53 @@
+// The host end of the validation metrics of one CLIP (bsrnn_evaluate_ragged): from the sums the metric kernels leave - per row, per clip - to
+// the eight numbers of include/bsrnn_hip.h (BSRNN_M_*), by the arithmetic bsrnn_evaluate documents: m_dataset.py:202-226, infer.py:44-47.
+// Host arithmetic only, in a fixed order, so tests run it without a GPU (tests/cpp/metrics_finish_check.cpp).
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+namespace bsrnn {
+
+// the order of BSRNN_M_* (api.hip asserts that the two agree)
+enum ClipMetric { CM_LOSS, CM_SDR, CM_INPUT_SDR, CM_SISDR, CM_L1_TIME, CM_L1_RE, CM_L1_IM, CM_SEPARATION_DB, CM_COUNT };
+
+// Sums of one row over its n_est samples (x the estimate, s the clean signal, m the mixture): the seven of the time kernel -
+// s^2, (x-s)^2, x*s, x^2, |x-s|, m^2, (m-x)^2 - then the SI-SDR pass's (alpha s)^2 and (alpha s - x)^2
+constexpr int CLIP_ROW_Q = 9;
+constexpr double SISDR_EPS = 1.1920928955078125e-07;          // float32 machine epsilon (torchmetrics)
+
+// Partial sums p[0], p[stride], ... added in index order
+inline double add_in_order(const double* p, size_t count, size_t stride)
+{
+    double a = 0.0;
+    for (size_t i = 0; i < count; ++i) a += p[i * stride];
+    return a;
+}
+
+// One clip of `rows` rows, n samples each, T = 1 + n / 1024 frames, n_est = (T - 1) * 1024 estimated samples per row.
+// row_sums [rows][CLIP_ROW_Q]; re_sum, im_sum: sum |Re Y - Re S|, sum |Im Y - Im S| over the clip's rows * T frames * 1025 bins;
+// in_sdr_sum: sum over the clip's n sample positions of 10 log10 of the reference's `sdr2` ratio (its sums run over the clip's rows).
+inline void finish_clip_metrics(const double* row_sums, int rows, double re_sum, double im_sum, double in_sdr_sum, int64_t n, int64_t T,
+                                int64_t n_est, double out[CM_COUNT])
+{
+    double sdr = 0, sisdr = 0, l1_time = 0, m2 = 0, md2 = 0;
+    for (int r = 0; r < rows; ++r) {
+        const double* q = row_sums + (size_t)r * CLIP_ROW_Q;
+        sdr += 10.0 * std::log10((q[0] + 1e-9) / (q[1] + 1e-9));                               // m_dataset.py:214-217
+        sisdr += 10.0 * std::log10((q[7] + SISDR_EPS) / (q[8] + SISDR_EPS));
+        l1_time += q[4]; m2 += q[5]; md2 += q[6];
+    }
+    l1_time /= (double)rows * (double)n_est;                                                   // L1Loss(reduction='mean'), train.py:54
+    const double l1_re = re_sum / ((double)rows * 1025.0 * (double)T);
+    const double l1_im = im_sum / ((double)rows * 1025.0 * (double)T);
+    out[CM_LOSS] = l1_time + l1_re + l1_im;                                                    // m_dataset.py:211-213
+    out[CM_SDR] = sdr / rows;
+    out[CM_INPUT_SDR] = in_sdr_sum / (double)n;
+    out[CM_SISDR] = sisdr / rows;
+    out[CM_L1_TIME] = l1_time;
+    out[CM_L1_RE] = l1_re;
+    out[CM_L1_IM] = l1_im;
+    out[CM_SEPARATION_DB] = 10.0 * std::log(m2 / md2);                                         // natural log, infer.py:47
+}
+
+}  // namespace bsrnn

@@ -239,5 +239,36 @@ inline RaggedShape ragged_shape(const int64_t* lens, int R, int64_t stride)
     q.out_stride = (q.Tmax - 1) * HOPS;
     return q;
 }
+// Frame rows R * Tmax one ragged call may run on (the frame-row index and twice it stay ints)
+inline bool ragged_too_many(int64_t R, int64_t Tmax) { return R > INT32_MAX / 2 || (R > 0 && Tmax > (INT32_MAX / 2) / R); }
+
+// --------------------------------------------------------------------------- ragged evaluate: clips of different lengths (bsrnn_evaluate_ragged)
+// The unit of the validation metrics is a CLIP: clip c owns rows[c] >= 1 consecutive rows (rows == nullptr: one each) of lens[c] samples each,
+// 1024 < lens[c] <= stride.  The call runs bsrnn_separate_ragged on the R = sum rows[c] rows, whose per-row lengths are the per-clip ones
+// expanded.  The first clip that breaks a bound is refused: bad_clip >= 0, bad_value its row count (CLIPS_ROWS) or its length (CLIPS_SHORT /
+// CLIPS_LONG); CLIPS_MANY: R * Tmax is beyond what one ragged call takes (bad_clip -1).  row_lens / first_row are filled only for CLIPS_OK.
+enum ClipsWhy { CLIPS_OK, CLIPS_ROWS, CLIPS_SHORT, CLIPS_LONG, CLIPS_MANY };
+struct ClipShape { int64_t R, Tmax, out_stride; int bad_clip; int64_t bad_value; int why; };
+inline ClipShape clip_shape(const int64_t* lens, const int32_t* rows, int n_clips, int64_t stride, std::vector<int64_t>& row_lens,
+                            std::vector<int>& first_row)
+{
+    ClipShape q = {0, 0, 0, -1, 0, CLIPS_OK};
+    row_lens.clear(); first_row.clear();
+    for (int c = 0; c < n_clips; ++c) {
+        const int64_t nr = rows ? rows[c] : 1;
+        if (nr < 1) return ClipShape{0, 0, 0, c, nr, CLIPS_ROWS};
+        if (lens[c] <= NFFT / 2 || lens[c] > stride) return ClipShape{0, 0, 0, c, lens[c], lens[c] > stride ? CLIPS_LONG : CLIPS_SHORT};
+        q.R += nr;
+        q.Tmax = std::max(q.Tmax, ragged_frames(lens[c]));
+    }
+    if (ragged_too_many(q.R, q.Tmax)) return ClipShape{q.R, q.Tmax, 0, -1, 0, CLIPS_MANY};
+    q.out_stride = (q.Tmax - 1) * HOPS;
+    row_lens.reserve((size_t)q.R); first_row.reserve((size_t)n_clips);
+    for (int c = 0; c < n_clips; ++c) {
+        first_row.push_back((int)row_lens.size());
+        row_lens.insert(row_lens.end(), (size_t)(rows ? rows[c] : 1), lens[c]);
+    }
+    return q;
+}
 
 }  // namespace bsrnn

@@ -16,6 +16,12 @@ def evaluate(model, mix, speech, return_estimate=False):
     return model.evaluate(mix, speech, return_estimate=return_estimate)
 
 
+def evaluate_many(model, pairs, max_rows=64, max_padding=0.25):
+    """pairs: a list of (mix, speech), each [n] or [ch, n], of different lengths -> the per-pair metric dicts in input order, from a few
+    batched calls (BSRNN.evaluate_many -> bsrnn_evaluate_ragged): each pair is a clip, evaluated as `evaluate` evaluates it alone."""
+    return model.evaluate_many(pairs, max_rows=max_rows, max_padding=max_padding)
+
+
 def train_infer(model, discriminator, sample, lossfn=None, verbose=False):
     """m_dataset.py:202-226.  sample = (waveform, waveform_speech), each [1, R, n].  lossfn must be the reference's
     L1Loss(reduction='mean') (train.py:54) or None.  Returns 0-dim tensors like the reference (its validation loop calls

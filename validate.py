@@ -2,9 +2,10 @@
 """Validation pass over (mixture, clean speech) file pairs -- the `with torch.no_grad()` block of the reference's
 train.py:132-150 without the training around it: `train_infer(model, None, sample, l1loss)` per pair, then the averages
 the reference prints ("Validation Loss", "Validation SDR") plus the SI-SDR it logs.  Separation, both STFTs and every
-reduction run on the MI355X (one bsrnn_evaluate call per pair).
+reduction run on the MI355X: one bsrnn_evaluate call per pair, or with --batch-rows N the pairs batched by length into a few
+bsrnn_evaluate_ragged calls of at most N rows (the same per-pair numbers to rounding, then the same averages).
 
-    validate.py --pairs mix1.wav speech1.wav [mix2.wav speech2.wav ...] [--weights model-always.pth]
+    validate.py --pairs mix1.wav speech1.wav [mix2.wav speech2.wav ...] [--weights model-always.pth] [--batch-rows 64]
 """
 import argparse
 
@@ -20,6 +21,8 @@ def main(argv=None):
     ap.add_argument("--weights", type=str, default="model-always.pth")
     ap.add_argument("--synthetic-weights", type=int, default=None, metavar="SEED")
     ap.add_argument("--device", type=str, default="cuda:0")
+    ap.add_argument("--batch-rows", type=int, default=0, metavar="N",
+                    help="0: one call per pair; N > 0: pairs of similar length batched into calls of at most N rows")
     args = ap.parse_args(argv)
     if len(args.pairs) % 2:
         ap.error("--pairs needs an even number of files")
@@ -32,15 +35,23 @@ def main(argv=None):
 
     val_loss = val_sdr = val_sdr2 = val_sisdr = 0.0
     n_pairs = len(args.pairs) // 2
+    loaded = []
     for mix_path, speech_path in zip(args.pairs[0::2], args.pairs[1::2]):
         mix, _ = audio.load_wav(mix_path)
         speech, _ = audio.load_wav(speech_path)
         if mix.shape[0] == 1:                                       # mono -> two identical rows, as infer.py:26-27
             mix, speech = torch.cat((mix, mix), 0), torch.cat((speech, speech), 0)
         n = min(mix.shape[1], speech.shape[1])
+        if args.batch_rows > 0:
+            loaded.append((mix[:, :n], speech[:, :n]))
+            continue
         sample = (mix[None, :, :n].to(args.device), speech[None, :, :n].to(args.device))
         loss, sdr, sdr2, sisdr = metrics.train_infer(model, None, sample, l1loss)
         val_loss += loss.item(); val_sdr += sdr.item(); val_sdr2 += sdr2.item(); val_sisdr += sisdr.item()
+    if args.batch_rows > 0:
+        with torch.cuda.device(args.device):
+            for m in metrics.evaluate_many(model, loaded, max_rows=args.batch_rows):
+                val_loss += m["loss"]; val_sdr += m["sdr"]; val_sdr2 += m["input_sdr"]; val_sisdr += m["sisdr"]
     print("Validation Loss", val_loss / n_pairs, "Validation SDR", val_sdr / n_pairs)
     print("Validation input SDR", val_sdr2 / n_pairs, "Validation SI-SDR", val_sisdr / n_pairs)
 
