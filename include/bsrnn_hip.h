@@ -414,6 +414,35 @@ int  bsrnn_stream_process(bsrnn_stream* s, const float* chunk_dev, float* out_de
  * instantiate nothing (bsrnn_debug_counter 0..2 unchanged).  Synchronous; the carry is left as it is. */
 int  bsrnn_stream_reserve(bsrnn_stream* s, int32_t max_hops);
 
+/* ---- streaming session slots: hold, reset and move single rows of a bsrnn_stream --------
+ * A step is launch-bound (its cost hardly depends on C), so many live sessions are served as a few rows each of ONE wide stream.
+ * These calls let the rows of a stream live apart: they join, pause, leave and move one by one.  They take streams of at most
+ * BSRNN_STREAM_ROWS_MAX rows (BSRNN_EARG above that; the other stream calls keep their own limits): the set of rows a call means
+ * travels by value in the kernel arguments, so no call allocates, stages a copy or keeps anything alive after it returns.
+ * bsrnn_stream_process_rows: bsrnn_stream_process for the rows with active_host[r] != 0 (active_host [C] in ordinary host memory, the
+ *     caller's again at return under either range policy; NULL = every row).  A held row (active_host[r] == 0) keeps its analysis
+ *     buffer, previous synthesis frame and LSTM state bit for bit, its out_dev row is zeros and its chunk_dev row is never read (it may
+ *     hold NaN; the row enters the model as a zero spectrum, so stale memory cannot trip the range guard).  An active row gets exactly
+ *     the bits the same call with every row active would give it.  mix_rows_dev [C], if not NULL, is a device array of the caller's
+ *     with one wet/dry value per row (the formula of bsrnn_stream_step_host; a row at 1 gets the bits of mix = 1) and replaces `mix`; it
+ *     must overlap neither chunk_dev nor out_dev.  Every row active and mix_rows_dev == NULL IS bsrnn_stream_process; no row active
+ *     zeroes out_dev and does nothing else.  n_hops = 1 takes the step's kernels (and its captured graph, if that is on), more hops the
+ *     block path.  Range policy as for bsrnn_stream_process, held rows staying held through a re-run; under BSRNN_RANGE_EXACT out_dev
+ *     must not overlap chunk_dev for any n_hops (BSRNN_EARG).  Costs no launch more than the plain call.
+ * bsrnn_stream_reset_rows: zeroes the carry of the n_rows rows listed in rows_host (each in [0, C); BSRNN_EARG names a bad one), in
+ *     stream order and one launch: the next hops of such a row are those of the same row of a freshly created stream of the same C.
+ * bsrnn_stream_row_floats: floats of one row's carry, 2*2048 + 8*K*64 (-1 for a null stream).
+ * bsrnn_stream_get_row / _set_row: synchronous; copy one row's carry to / from blob_host [buf 2048 | prev 2048 | state 4,2,K,64].  A
+ *     blob set into any row of a stream of the same C and band table continues bit for bit as it would have in place.  get_row reports
+ *     a range violation left by calls under BSRNN_RANGE_DEFERRED, like bsrnn_stream_get_state. */
+#define BSRNN_STREAM_ROWS_MAX 2048
+int     bsrnn_stream_process_rows(bsrnn_stream* s, const float* chunk_dev, float* out_dev, int32_t n_hops,
+                                  const uint8_t* active_host, const float* mix_rows_dev, float mix, void* stream);
+int     bsrnn_stream_reset_rows(bsrnn_stream* s, const int32_t* rows_host, int32_t n_rows, void* stream);
+int64_t bsrnn_stream_row_floats(const bsrnn_stream* s);
+int     bsrnn_stream_get_row(bsrnn_stream* s, int32_t row, float* blob_host);
+int     bsrnn_stream_set_row(bsrnn_stream* s, int32_t row, const float* blob_host);
+
 /* ---- measurement support ---------------------------------------------------------------
  * bsrnn_set_profiling(ctx, mask): bit i of `mask` brackets stage i of every compute call with
  * hipEvents on the call's stream (mask < 0 = all stages, 0 = off; each bracket costs ~10 us of

@@ -26,8 +26,10 @@ SYMBOLS = [
     "bsrnn_set_range_policy", "bsrnn_get_range_policy", "bsrnn_overlap_state", "bsrnn_debug_peek", "bsrnn_debug_counter",
     "bsrnn_stream_process", "bsrnn_stream_reserve", "bsrnn_separate_long", "bsrnn_separate_long_host", "bsrnn_workspace_rows",
     "bsrnn_separate_ragged", "bsrnn_evaluate_ragged",
+    "bsrnn_stream_process_rows", "bsrnn_stream_reset_rows", "bsrnn_stream_row_floats", "bsrnn_stream_get_row", "bsrnn_stream_set_row",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
+STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
 METRIC_NAMES = ("loss", "sdr", "input_sdr", "sisdr", "l1_time", "l1_re", "l1_im", "separation_db")   # BSRNN_M_* order
 
 
@@ -98,6 +100,11 @@ def _load():
         "bsrnn_stream_get_state": (C.c_int, [vp, vp]),
         "bsrnn_stream_process": (C.c_int, [vp, vp, vp, i32, C.c_float, vp]),
         "bsrnn_stream_reserve": (C.c_int, [vp, i32]),
+        "bsrnn_stream_process_rows": (C.c_int, [vp, vp, vp, i32, vp, vp, C.c_float, vp]),
+        "bsrnn_stream_reset_rows": (C.c_int, [vp, vp, i32, vp]),
+        "bsrnn_stream_row_floats": (i64, [vp]),
+        "bsrnn_stream_get_row": (C.c_int, [vp, i32, vp]),
+        "bsrnn_stream_set_row": (C.c_int, [vp, i32, vp]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),
         "bsrnn_stage_name": (C.c_char_p, [i32]),

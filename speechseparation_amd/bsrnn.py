@@ -642,3 +642,205 @@ class StreamingSeparator:
         s = np.empty((4, 2, self.C * K, band_features), np.float32)
         _check(_lib.bsrnn_stream_get_state(self._h, s.ctypes.data_as(ctypes.c_void_p)))
         return torch.from_numpy(s)
+
+    # ------------------------------------------------------------------ rows that live apart (session slots)
+    def _look_at_weights(self):
+        # the same look at the model's parameters as step() takes (see there), once per call
+        if self._steps % 32 == 0 or self.model._weights_touched(self._steps):
+            self.model._plist = None
+            with torch.cuda.device(self.device):
+                self.model._context(self.device)
+        self._steps += 1
+
+    def _check_row(self, row, what):
+        if isinstance(row, bool) or not isinstance(row, (int, np.integer)):
+            raise ValueError("%s: row must be an int, got %s" % (what, type(row).__name__))
+        if not 0 <= row < self.C:
+            raise ValueError("%s: row %d is outside [0, %d)" % (what, row, self.C))
+        return int(row)
+
+    def row_floats(self):
+        """Floats of one row's carry as get_row / set_row move it: buf[2048], prev[2048], state[4][2][K][64]."""
+        return 2 * _spec.N_FFT + 8 * len(self.model.band_widths) * band_features
+
+    def process_rows(self, wave, active=None, mix=1.0):
+        """wave [C, L*1024] float32 (cuda or cpu), whole hops -> [C, L*1024] on the same device (bsrnn_stream_process_rows): rows with a
+        true entry in `active` (a sequence or tensor of C flags; None: every row) take the L hops exactly as process() would give them,
+        the others are HELD - their carry stays bit for bit, their output rows are zeros and their input rows are never read.  `mix` is
+        one wet / dry value or a [C] tensor of one per row.  Takes no part in process()'s carrying of partial hops."""
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != self.C:
+            raise ValueError("process_rows: expected wave [%d, L*1024], got %s" % (
+                self.C, tuple(wave.shape) if isinstance(wave, torch.Tensor) else type(wave).__name__))
+        if wave.shape[1] % _spec.HOP:
+            raise ValueError("process_rows: wave must hold whole hops of 1024 samples, got %d samples per row" % wave.shape[1])
+        flags = None
+        if active is not None:
+            try:
+                flags = [bool(a) for a in (active.tolist() if isinstance(active, (torch.Tensor, np.ndarray)) else active)]
+            except TypeError:
+                raise ValueError("process_rows: active must be a sequence of %d flags, got %s" % (self.C, type(active).__name__)) from None
+            if len(flags) != self.C:
+                raise ValueError("process_rows: %d flags for %d rows" % (len(flags), self.C))
+        mix_rows = None
+        if isinstance(mix, torch.Tensor):
+            if tuple(mix.shape) != (self.C,):
+                raise ValueError("process_rows: mix must be a float or a tensor [%d], got %s" % (self.C, tuple(mix.shape)))
+            mix_rows, mix = mix, 1.0
+        elif isinstance(mix, bool) or not isinstance(mix, (int, float, np.floating, np.integer)):
+            raise ValueError("process_rows: mix must be a float or a tensor [%d], got %s" % (self.C, type(mix).__name__))
+        L = wave.shape[1] // _spec.HOP
+        if L == 0:
+            return torch.empty((self.C, 0), dtype=torch.float32, device=wave.device)
+        self._look_at_weights()
+        x = wave.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        out = torch.empty_like(x)
+        if mix_rows is not None:
+            mix_rows = mix_rows.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        act = (ctypes.c_uint8 * self.C)(*flags) if flags is not None else None
+        with torch.cuda.device(self.device):
+            _check(_lib.bsrnn_stream_process_rows(self._h, _ptr(x), _ptr(out), L, act, _ptr(mix_rows) if mix_rows is not None else None,
+                                                  float(mix), _stream_ptr(self.device)))
+        return out if wave.is_cuda else out.cpu()
+
+    def reset_rows(self, rows):
+        """Zero the carry of the listed rows (bsrnn_stream_reset_rows): each then continues as the same row of a fresh stream would."""
+        try:
+            rows = [self._check_row(r, "reset_rows") for r in rows]
+        except TypeError:
+            raise ValueError("reset_rows: rows must be a sequence of ints, got %s" % type(rows).__name__) from None
+        if not rows:
+            raise ValueError("reset_rows: no rows")
+        with torch.cuda.device(self.device):
+            _check(_lib.bsrnn_stream_reset_rows(self._h, (ctypes.c_int32 * len(rows))(*rows), len(rows), _stream_ptr(self.device)))
+
+    def get_row(self, row):
+        """One row's carry as a CPU tensor [row_floats()] (bsrnn_stream_get_row; synchronous)."""
+        row = self._check_row(row, "get_row")
+        blob = np.empty(self.row_floats(), np.float32)
+        _check(_lib.bsrnn_stream_get_row(self._h, row, blob.ctypes.data_as(ctypes.c_void_p)))
+        return torch.from_numpy(blob)
+
+    def set_row(self, row, blob):
+        """Put a carry taken with get_row - from this stream or another one of the same C and band table - into `row`: the row continues
+        bit for bit as it would have where it came from (bsrnn_stream_set_row; synchronous)."""
+        row = self._check_row(row, "set_row")
+        if not isinstance(blob, torch.Tensor) or blob.numel() != self.row_floats() or blob.dim() != 1:
+            raise ValueError("set_row: blob must be a tensor [%d], got %s" % (
+                self.row_floats(), tuple(blob.shape) if isinstance(blob, torch.Tensor) else type(blob).__name__))
+        b = np.ascontiguousarray(blob.detach().to("cpu", torch.float32).numpy())
+        _check(_lib.bsrnn_stream_set_row(self._h, row, b.ctypes.data_as(ctypes.c_void_p)))
+
+
+class StreamPool:
+    """Many live sessions on one wide stream: `slots` sessions of `rows_per_session` rows each share one StreamingSeparator of
+    slots * rows_per_session rows, and one step() serves whichever of them have audio this tick at the price of one streaming call
+    (a step is launch-bound: its cost hardly grows with the rows).  Sessions join (open), leave (close), pause (not named in a step:
+    their rows are held) and move between pools (export / adopt) one by one.  The stream is created at the first call that needs the
+    device; shape and type errors are raised before that."""
+
+    def __init__(self, model, slots, rows_per_session=1, device=None):
+        for name, v in (("slots", slots), ("rows_per_session", rows_per_session)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError("StreamPool: %s must be a positive int, got %r" % (name, v))
+        if slots * rows_per_session > _native.STREAM_ROWS_MAX:
+            raise ValueError("StreamPool: %d slots x %d rows is more than the %d rows a rows call takes" % (slots, rows_per_session, _native.STREAM_ROWS_MAX))
+        self.model, self.slots, self.rows, self._device = model, int(slots), int(rows_per_session), device
+        self._st = None
+        self._slot = {}                     # session id -> slot
+        self._free = list(range(self.slots))
+        self._next = 0
+
+    def _stream(self):
+        if self._st is None:
+            self._st = StreamingSeparator(self.model, channels=self.slots * self.rows, device=self._device)
+        return self._st
+
+    def _rows_of(self, sid):
+        slot = self._slot[sid]              # KeyError: no such session
+        return range(slot * self.rows, (slot + 1) * self.rows)
+
+    def sessions(self):
+        return list(self._slot)
+
+    def open(self):
+        """-> a new session's id; its rows start from silence.  ValueError when every slot is taken."""
+        if not self._free:
+            raise ValueError("StreamPool: all %d slots are in use" % self.slots)
+        slot = self._free.pop(0)
+        sid, self._next = self._next, self._next + 1
+        self._slot[sid] = slot
+        if self._st is not None:            # (a stream that does not exist yet starts zeroed)
+            self._st.reset_rows(list(self._rows_of(sid)))
+        return sid
+
+    def close(self, sid):
+        self._free.append(self._slot.pop(sid))
+        self._free.sort()
+
+    def step(self, chunks, mix=None):
+        """chunks {sid: tensor [rows_per_session, L*1024]}, one L for all -> {sid: tensor of the same shape, on its chunk's device}, delayed
+        by one hop like StreamingSeparator.step.  Sessions not named are held.  mix: None (1.0), one float, or {sid: float} (sessions not
+        in it: 1.0).  An empty dict makes no library call."""
+        if not isinstance(chunks, dict):
+            raise ValueError("StreamPool.step: chunks must be a dict {session id: tensor}, got %s" % type(chunks).__name__)
+        n = None
+        for sid, t in chunks.items():
+            self._rows_of(sid)
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != self.rows:
+                raise ValueError("StreamPool.step: session %r needs a tensor [%d, L*1024], got %s" % (
+                    sid, self.rows, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+            if t.shape[1] % _spec.HOP or t.shape[1] == 0:
+                raise ValueError("StreamPool.step: session %r holds %d samples per row, need whole hops of 1024" % (sid, t.shape[1]))
+            if n is not None and t.shape[1] != n:
+                raise ValueError("StreamPool.step: session %r holds %d samples per row, the others %d (one L per step)" % (sid, t.shape[1], n))
+            n = t.shape[1]
+        per_row = isinstance(mix, dict)
+        if per_row:
+            for sid, v in mix.items():
+                self._rows_of(sid)
+                if isinstance(v, bool) or not isinstance(v, (int, float)):
+                    raise ValueError("StreamPool.step: mix of session %r must be a float, got %s" % (sid, type(v).__name__))
+        elif mix is not None and (isinstance(mix, bool) or not isinstance(mix, (int, float))):
+            raise ValueError("StreamPool.step: mix must be None, a float or a dict {session id: float}, got %s" % type(mix).__name__)
+        if not chunks:
+            return {}
+        st = self._stream()
+        C = self.slots * self.rows
+        wave = torch.zeros((C, n), dtype=torch.float32, device=st.device)
+        active = [False] * C
+        mix_rows = [1.0] * C
+        for sid, t in chunks.items():
+            rows = self._rows_of(sid)
+            wave[rows.start:rows.stop] = t.detach().to(device=st.device, dtype=torch.float32)
+            for r in rows:
+                active[r] = True
+                if per_row:
+                    mix_rows[r] = float(mix.get(sid, 1.0))
+        m = torch.tensor(mix_rows, dtype=torch.float32) if per_row else (1.0 if mix is None else float(mix))
+        out = st.process_rows(wave, active, m)
+        res = {}
+        for sid, t in chunks.items():
+            rows = self._rows_of(sid)
+            o = out[rows.start:rows.stop]
+            res[sid] = o.clone() if t.is_cuda else o.cpu()
+        return res
+
+    def export(self, sid):
+        """-> the session's carry, one blob (CPU tensor) per row, for adopt() of this or another pool of the same model."""
+        rows = self._rows_of(sid)
+        st = self._stream()
+        return [st.get_row(r) for r in rows]
+
+    def adopt(self, blobs):
+        """A session exported elsewhere continues here, bit for bit -> its new id."""
+        blobs = list(blobs)
+        nf = 2 * _spec.N_FFT + 8 * len(self.model.band_widths) * band_features
+        if len(blobs) != self.rows or not all(isinstance(b, torch.Tensor) and b.dim() == 1 and b.numel() == nf for b in blobs):
+            raise ValueError("StreamPool.adopt: need %d blobs of %d floats each" % (self.rows, nf))
+        if not self._free:
+            raise ValueError("StreamPool: all %d slots are in use" % self.slots)
+        st = self._stream()
+        sid = self.open()
+        for r, b in zip(self._rows_of(sid), blobs):
+            st.set_row(r, b)
+        return sid

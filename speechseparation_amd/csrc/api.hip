@@ -2233,12 +2233,20 @@ int bsrnn_stream_reset(bsrnn_stream* st, void* stream)
 
 // One step from carry set p = st->cur into set 1 - p: chunk -> out (device pointers of the caller or the object's own buffers).
 // The model part is a graph replay when possible.  Does NOT flip st->cur: the caller does, once the step is known to be good.
-static int stream_step_run(bsrnn_stream* st, const float* chunk, float* out, float mix, hipStream_t s)
+// rows (bsrnn_stream_process_rows): only the rows of rows->active take the step; the others are held by the two DSP launches (the model part
+// is the same, captured graph included: a held row enters it as a zero spectrum, and the synthesis launch - behind every launch of the
+// model in stream order - puts its LSTM state back).
+struct RowArgs { RowSet active; const float* mix_rows; };
+static int stream_step_run(bsrnn_stream* st, const float* chunk, float* out, float mix, hipStream_t s, const RowArgs* rows = nullptr)
 {
     bsrnn_ctx* c = st->ctx;
     const int p = st->cur, q = p ^ 1;
     int rc;
-    { StageScope sc(c, ST_STREAM_DSP, s); launch_stream_analysis(c->tb, st->buf[p], st->buf[q], chunk, st->X, st->C, s); }
+    {
+        StageScope sc(c, ST_STREAM_DSP, s);
+        if (rows) launch_stream_analysis_rows(c->tb, st->buf[p], st->buf[q], chunk, st->X, st->C, rows->active, s);
+        else launch_stream_analysis(c->tb, st->buf[p], st->buf[q], chunk, st->X, st->C, s);
+    }
     if (st->use_graph && c->prof == 0 && !force_f32()) {
         // The captured launches hold the context's workspace and weight-arena pointers.  A larger call on the context (workspace
         // regrown) or a re-commit of the parameters (arena rebuilt) since the capture changes ctx->gen: capture again
@@ -2275,7 +2283,12 @@ static int stream_step_run(bsrnn_stream* st, const float* chunk, float* out, flo
     } else if ((rc = run_model(c, st->X, st->Y, nullptr, st->C, 1, st->state[p], st->state[q], s))) {
         return rc;
     }
-    { StageScope sc(c, ST_STREAM_DSP, s); launch_stream_synthesis(c->tb, st->Y, st->X, mix, st->prev[p], st->prev[q], out, st->C, s); }
+    {
+        StageScope sc(c, ST_STREAM_DSP, s);
+        if (rows) launch_stream_synthesis_rows(c->tb, st->Y, st->X, mix, rows->mix_rows, st->prev[p], st->prev[q], out, st->state[p], st->state[q], st->C, c->K,
+                                               rows->active, s);
+        else launch_stream_synthesis(c->tb, st->Y, st->X, mix, st->prev[p], st->prev[q], out, st->C, s);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2328,13 +2341,25 @@ int bsrnn_stream_step_host(bsrnn_stream* st, const float* chunk_host, float* out
 
 // L hops from carry set p = st->cur into set 1 - p: chunk [C][L*1024] -> out [C][L*1024], the spectra in the context's workspace (one call
 // at a time per context).  Does NOT flip st->cur (see stream_step_run).
-static int stream_block_run(bsrnn_stream* st, const float* chunk, float* out, int L, float mix, hipStream_t s)
+// rows: as for stream_step_run.  On the overlapped plan the second time-axis launch writes its half of state[q] on the auxiliary stream;
+// run_overlapped joins that stream into `s` by an event for every call that returns LSTM state - this one does - so the synthesis launch,
+// which copies the held rows' state over what the model wrote, follows both.
+static int stream_block_run(bsrnn_stream* st, const float* chunk, float* out, int L, float mix, hipStream_t s, const RowArgs* rows = nullptr)
 {
     bsrnn_ctx* c = st->ctx;
     const int p = st->cur, q = p ^ 1;
-    { StageScope sc(c, ST_STREAM_DSP, s); launch_stream_block_analysis(c->tb, st->buf[p], st->buf[q], chunk, c->Xf, st->C, L, s); }
+    {
+        StageScope sc(c, ST_STREAM_DSP, s);
+        if (rows) launch_stream_block_analysis_rows(c->tb, st->buf[p], st->buf[q], chunk, c->Xf, st->C, L, rows->active, s);
+        else launch_stream_block_analysis(c->tb, st->buf[p], st->buf[q], chunk, c->Xf, st->C, L, s);
+    }
     if (int rc = run_model(c, c->Xf, c->Yf, nullptr, st->C, L, st->state[p], st->state[q], s)) return rc;
-    { StageScope sc(c, ST_STREAM_DSP, s); launch_stream_block_synthesis(c->tb, c->Yf, c->Xf, mix, st->prev[p], st->prev[q], out, st->C, L, s); }
+    {
+        StageScope sc(c, ST_STREAM_DSP, s);
+        if (rows) launch_stream_block_synthesis_rows(c->tb, c->Yf, c->Xf, mix, rows->mix_rows, st->prev[p], st->prev[q], out, st->state[p], st->state[q], st->C,
+                                                     c->K, L, rows->active, s);
+        else launch_stream_block_synthesis(c->tb, c->Yf, c->Xf, mix, st->prev[p], st->prev[q], out, st->C, L, s);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2420,6 +2445,102 @@ int bsrnn_stream_get_state(bsrnn_stream* st, float* state_host)
     const size_t nstate = state_floats(st->C, st->ctx->K);
     HIP_TRY(hipMemcpy(state_host, st->state[st->cur], nstate * sizeof(float), hipMemcpyDeviceToHost));
     return check_range(st->ctx);          // steps made under the 'deferred' policy report a range violation here (or at the next call / bsrnn_sync)
+}
+
+// --------------------------------------------------------------------------- streaming, row by row (session slots)
+static_assert(BSRNN_STREAM_ROWS_MAX == STREAM_ROWS_MAX, "include/bsrnn_hip.h and stream_rows_host.h disagree");
+
+int bsrnn_stream_process_rows(bsrnn_stream* st, const float* chunk, float* out, int32_t n_hops, const uint8_t* active_host, const float* mix_rows,
+                              float mix, void* stream)
+{
+    if (!st || !chunk || !out) return fail(BSRNN_EARG, "bsrnn_stream_process_rows: null argument");
+    if (n_hops < 1) return fail(BSRNN_EARG, "bsrnn_stream_process_rows: n_hops = %d (at least one hop)", n_hops);
+    RowArgs ra;
+    ra.mix_rows = mix_rows;
+    const int n_active = pack_row_set(active_host, st->C, ra.active);      // (the caller's array is not looked at again)
+    if (n_active < 0)
+        return fail(BSRNN_EARG, "bsrnn_stream_process_rows: the stream has %d rows, the rows calls take at most BSRNN_STREAM_ROWS_MAX = %d", st->C, STREAM_ROWS_MAX);
+    bsrnn_ctx* c = st->ctx;
+    const size_t nb = (size_t)st->C * n_hops * HOPS * sizeof(float);
+    if (c->range_policy == BSRNN_RANGE_EXACT && ranges_overlap(chunk, nb, out, nb))
+        return fail(BSRNN_EARG, "bsrnn_stream_process_rows: out_dev must not overlap chunk_dev under the exact range policy (the re-run of a call that leaves the fp16 range reads chunk_dev again)");
+    if (ranges_overlap(mix_rows, (size_t)st->C * sizeof(float), chunk, nb) || ranges_overlap(mix_rows, (size_t)st->C * sizeof(float), out, nb))
+        return fail(BSRNN_EARG, "bsrnn_stream_process_rows: mix_rows_dev must overlap neither chunk_dev nor out_dev");
+    // every row, one wet / dry value: the plain call itself
+    if (n_active == st->C && !mix_rows) return bsrnn_stream_process(st, chunk, out, n_hops, mix, stream);
+    int rc = check_ready(c);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    // no row: nothing advances, the carry sets stay as they are
+    if (n_active == 0) { HIP_TRY(hipMemsetAsync(out, 0, nb, s)); return 0; }
+    const size_t M = (size_t)st->C * n_hops;
+    if (M > (size_t)INT32_MAX / 2) return fail(BSRNN_EARG, "bsrnn_stream_process_rows: %d rows x %d hops is too many frame rows for one call", st->C, n_hops);
+    if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M))) return rc;
+    // one hop: the step's kernels and its captured graph; more: the block path.  Both read carry set cur and write the other one, for
+    // held rows too, so the re-run of the range policy starts from the untouched set with the same rows held.
+    auto run = [&]() -> int { return n_hops == 1 ? stream_step_run(st, chunk, out, mix, s, &ra) : stream_block_run(st, chunk, out, n_hops, mix, s, &ra); };
+    if ((rc = run())) return rc;
+    if ((rc = finish_call(c, s, run))) return rc;
+    st->cur ^= 1;
+    return 0;
+}
+
+int bsrnn_stream_reset_rows(bsrnn_stream* st, const int32_t* rows_host, int32_t n_rows, void* stream)
+{
+    if (!st) return fail(BSRNN_EARG, "bsrnn_stream_reset_rows: null stream");
+    if (!rows_host || n_rows < 1) return fail(BSRNN_EARG, "bsrnn_stream_reset_rows: no rows (null list or n_rows = %d)", n_rows);
+    if (st->C > STREAM_ROWS_MAX)
+        return fail(BSRNN_EARG, "bsrnn_stream_reset_rows: the stream has %d rows, the rows calls take at most BSRNN_STREAM_ROWS_MAX = %d", st->C, STREAM_ROWS_MAX);
+    RowSet rs;
+    const int bad = pack_row_list(rows_host, n_rows, st->C, rs);
+    if (bad >= 0) return fail(BSRNN_EARG, "bsrnn_stream_reset_rows: row %d (entry %d of the list) is outside [0, %d)", rows_host[bad], bad, st->C);
+    HIP_TRY(hipSetDevice(st->ctx->device));
+    launch_stream_reset_rows(st->buf[st->cur], st->prev[st->cur], st->state[st->cur], st->C, st->ctx->K, rs, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int64_t bsrnn_stream_row_floats(const bsrnn_stream* st) { return st ? stream_row_floats(st->ctx->K) : -1; }
+
+// One row's carry <-> blob [buf 2048 | prev 2048 | state 4*2 slabs of K*64]: two plain copies and one strided one (the row's slab is
+// K*64 contiguous floats at dim 2 = row*K of each of the eight [C*K][64] slabs).
+static int stream_move_row(bsrnn_stream* st, int row, float* blob, bool get)
+{
+    bsrnn_ctx* c = st->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const int p = st->cur;
+    const size_t slab = (size_t)c->K * HID * sizeof(float), pitch = slab * st->C;
+    float* buf = st->buf[p] + (size_t)row * NFFT;
+    float* prev = st->prev[p] + (size_t)row * NFFT;
+    float* state = st->state[p] + (size_t)row * c->K * HID;
+    if (get) {
+        HIP_TRY(hipMemcpy(blob, buf, NFFT * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(blob + NFFT, prev, NFFT * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy2D(blob + 2 * NFFT, slab, state, pitch, slab, 8, hipMemcpyDeviceToHost));
+    } else {
+        HIP_TRY(hipMemcpy(buf, blob, NFFT * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(prev, blob + NFFT, NFFT * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy2D(state, pitch, blob + 2 * NFFT, slab, slab, 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    return 0;
+}
+
+int bsrnn_stream_get_row(bsrnn_stream* st, int32_t row, float* blob_host)
+{
+    if (!st || !blob_host) return fail(BSRNN_EARG, "bsrnn_stream_get_row: null argument");
+    if (row < 0 || row >= st->C) return fail(BSRNN_EARG, "bsrnn_stream_get_row: row %d is outside [0, %d)", row, st->C);
+    if (int rc = stream_move_row(st, row, blob_host, true)) return rc;
+    return check_range(st->ctx);          // as bsrnn_stream_get_state: calls made under the 'deferred' policy report a range violation here
+}
+
+int bsrnn_stream_set_row(bsrnn_stream* st, int32_t row, const float* blob_host)
+{
+    if (!st || !blob_host) return fail(BSRNN_EARG, "bsrnn_stream_set_row: null argument");
+    if (row < 0 || row >= st->C) return fail(BSRNN_EARG, "bsrnn_stream_set_row: row %d is outside [0, %d)", row, st->C);
+    return stream_move_row(st, row, const_cast<float*>(blob_host), false);
 }
 
 // --------------------------------------------------------------------------- measurement

@@ -505,11 +505,60 @@ void launch_from_frame_major(const FftTables& tb, const float* yf, float* y, int
 }
 
 // ------------------------------------------------------------------------------ streaming DSP
+// The four kernels below are templates over ROWS: AllRows is the plain call (an empty argument: the code of a kernel without it), HeldRows
+// the row-masked form of bsrnn_stream_process_rows - the set of ACTIVE rows by value (stream_rows_host.h), an optional wet / dry value per
+// row, and where the LSTM state of a held row lives and goes.  What a HELD row costs: its workgroups move what their kernel owns from the
+// read carry set to the written one - the analysis the buffer, the synthesis the previous frame and the row's LSTM state - and write zeros
+// where an active row's spectra and samples go.  A workgroup belongs to one row, so all of that is uniform over the workgroup, and it
+// returns before any barrier.  An active row runs the very code of the plain call.
+struct AllRows { static constexpr bool masked = false; };
+struct HeldRows {
+    static constexpr bool masked = true;
+    RowSet active;
+    const float* mix_rows;             // [C] on the device, or null: the call's `mix` for every row
+    // state [4][2][C*K][64]: row c owns the K*64 floats at (slab * C + c) * K * 64 of each of the eight slabs (multiples of 64 floats:
+    // 16-byte aligned).  Copied by the synthesis launch, which follows every launch that wrote state_out for the call.
+    const float* state_in; float* state_out; int C, K;
+};
+__device__ __forceinline__ void copy_floats4(const float* __restrict__ src, float* __restrict__ dst, int n4, int tid)
+{
+    for (int i = tid; i < n4; i += 256) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i];
+}
+__device__ __forceinline__ void zero_floats4(float* __restrict__ dst, int n4, int tid)
+{
+    for (int i = tid; i < n4; i += 256) reinterpret_cast<float4*>(dst)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// one hop of the caller's output, with the 8-byte stores of the computed ones (the caller's buffer need not be 16-byte aligned)
+__device__ __forceinline__ void zero_hop(float* __restrict__ o, int tid)
+{
+#pragma unroll
+    for (int k = 0; k < 2; ++k) *reinterpret_cast<float2*>(o + 2 * (tid + 256 * k)) = make_float2(0.f, 0.f);
+}
+__device__ __forceinline__ void hold_state_row(const HeldRows& h, int c, int tid)
+{
+    const int n4 = h.K * 16;                              // float4 per slab
+    for (int i = tid; i < 8 * n4; i += 256) {
+        const int slab = i / n4, j = i - slab * n4;
+        const size_t at = ((size_t)slab * h.C + c) * n4 + j;
+        reinterpret_cast<float4*>(h.state_out)[at] = reinterpret_cast<const float4*>(h.state_in)[at];
+    }
+}
+
+template <class ROWS>
 __global__ __launch_bounds__(256) void stream_analysis_kernel(FftTables tb, const float* __restrict__ buf_in, float* __restrict__ buf,
-                                                              const float* __restrict__ chunk, float* __restrict__ X)
+                                                              const float* __restrict__ chunk, float* __restrict__ X, ROWS rows)
 {
     __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
     const int tid = threadIdx.x;
+    if constexpr (ROWS::masked) {
+        // held: the buffer as it is, a zero spectrum (all ld columns: rows start 16-byte aligned and ld is a multiple of 4), chunk unread
+        const int c = blockIdx.x;
+        if (!row_set_has(rows.active, c)) {
+            copy_floats4(buf_in + (size_t)c * NFFT, buf + (size_t)c * NFFT, NFFT / 4, tid);
+            zero_floats4(X + (size_t)c * tb.ld, tb.ld / 4, tid);
+            return;
+        }
+    }
     const Twiddles twd = load_twiddles<false>(tb.tw1024, tid);
     const SplitCtx spl = load_split(tb, tid, false);
     const int c = blockIdx.x;
@@ -537,13 +586,25 @@ __global__ __launch_bounds__(256) void stream_analysis_kernel(FftTables tb, cons
     rfft_split_store(Z, spl, X + (size_t)c * tb.ld, tid);
 }
 
+template <class ROWS>
 __global__ __launch_bounds__(256) void stream_synthesis_kernel(FftTables tb, const float* __restrict__ Y, const float* __restrict__ X,
-                                                               const float mix, const float* __restrict__ prev_in, float* __restrict__ prev,
-                                                               float* __restrict__ out)
+                                                               const float mix_all, const float* __restrict__ prev_in, float* __restrict__ prev,
+                                                               float* __restrict__ out, ROWS rows)
 {
     __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
     __shared__ __attribute__((aligned(16))) float spec[F2 + 2];
     const int tid = threadIdx.x;
+    float mix = mix_all;
+    if constexpr (ROWS::masked) {
+        const int c = blockIdx.x;
+        if (!row_set_has(rows.active, c)) {
+            copy_floats4(prev_in + (size_t)c * NFFT, prev + (size_t)c * NFFT, NFFT / 4, tid);
+            zero_hop(out + (size_t)c * HOPS, tid);
+            hold_state_row(rows, c, tid);
+            return;
+        }
+        if (rows.mix_rows) mix = rows.mix_rows[c];          // one load per workgroup; mix == 1 below is decided per row
+    }
     const Twiddles twd = load_twiddles<true>(tb.tw1024, tid);
     const SplitCtx spl = load_split(tb, tid, false);
     const int c = blockIdx.x;
@@ -576,14 +637,42 @@ __global__ __launch_bounds__(256) void stream_synthesis_kernel(FftTables tb, con
         *reinterpret_cast<float2*>(pv + 2 * cc) = make_float2(z[cc].x * sc, z[cc].y * sc);
 }
 
+// Zeroes the carry of the rows in `rows` in one carry set (bsrnn_stream_reset_rows): one workgroup per row of the stream.
+__global__ __launch_bounds__(256) void stream_reset_rows_kernel(RowSet rows, float* __restrict__ buf, float* __restrict__ prev, float* __restrict__ state,
+                                                                int C, int K)
+{
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x;
+    if (!row_set_has(rows, c)) return;
+    zero_floats4(buf + (size_t)c * NFFT, NFFT / 4, tid);
+    zero_floats4(prev + (size_t)c * NFFT, NFFT / 4, tid);
+    const int n4 = K * 16;
+    for (int slab = 0; slab < 8; ++slab) zero_floats4(state + ((size_t)slab * C + c) * n4 * 4, n4, tid);
+}
+
 void launch_stream_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, hipStream_t s)
 {
-    hipLaunchKernelGGL(stream_analysis_kernel, dim3(C), dim3(256), 0, s, tb, buf_in, buf_out, chunk, X);
+    hipLaunchKernelGGL(stream_analysis_kernel<AllRows>, dim3(C), dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, AllRows{});
 }
 void launch_stream_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, const float* prev_in, float* prev_out, float* out,
                              int C, hipStream_t s)
 {
-    hipLaunchKernelGGL(stream_synthesis_kernel, dim3(C), dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out);
+    hipLaunchKernelGGL(stream_synthesis_kernel<AllRows>, dim3(C), dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, AllRows{});
+}
+void launch_stream_analysis_rows(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, const RowSet& active,
+                                 hipStream_t s)
+{
+    hipLaunchKernelGGL(stream_analysis_kernel<HeldRows>, dim3(C), dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, HeldRows{active, nullptr, nullptr, nullptr, C, 0});
+}
+void launch_stream_synthesis_rows(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
+                                  float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, const RowSet& active, hipStream_t s)
+{
+    hipLaunchKernelGGL(stream_synthesis_kernel<HeldRows>, dim3(C), dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out,
+                       HeldRows{active, mix_rows, state_in, state_out, C, K});
+}
+void launch_stream_reset_rows(float* buf, float* prev, float* state, int C, int K, const RowSet& rows, hipStream_t s)
+{
+    hipLaunchKernelGGL(stream_reset_rows_kernel, dim3(C), dim3(256), 0, s, rows, buf, prev, state, C, K);
 }
 
 // ------------------------------------------------------------------------------ streaming DSP, a block of L hops per row
@@ -591,14 +680,24 @@ void launch_stream_synthesis(const FftTables& tb, const float* Y, const float* X
 // `sch` consecutive hops of one row (the analysis with stft_walk).  Per row the analysis reads S = buf_in[0:2048] ++ chunk[0:L*1024]; frame l is
 // S[(l+1)*1024 : (l+1)*1024 + 2048] (no reflection: the history is the carried buffer), and the new carry is the last frame's raw
 // samples.  Per frame the arithmetic is that of the one-hop kernels, in their order.
+// ROWS = HeldRows: a held row's workgroups write zero spectra for their frames, and the one that owns the last hop copies the buffer.
+template <class ROWS>
 __global__ __launch_bounds__(256, FFT_OCC_STFT) void stream_block_analysis_kernel(FftTables tb, const float* __restrict__ buf_in, float* __restrict__ buf_out,
-                                                                                  const float* __restrict__ chunk, float* __restrict__ X, int L, int sch)
+                                                                                  const float* __restrict__ chunk, float* __restrict__ X, int L, int sch,
+                                                                                  ROWS rows)
 {
     __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
     const int tid = threadIdx.x;
     const int r = blockIdx.y;
     const int l0 = blockIdx.x * sch;
     const int l1 = (l0 + sch < L) ? l0 + sch : L;
+    if constexpr (ROWS::masked) {
+        if (!row_set_has(rows.active, r)) {
+            for (int l = l0; l < l1; ++l) zero_floats4(X + ((size_t)r * L + l) * tb.ld, tb.ld / 4, tid);
+            if (l1 == L) copy_floats4(buf_in + (size_t)r * NFFT, buf_out + (size_t)r * NFFT, NFFT / 4, tid);
+            return;
+        }
+    }
     const float* carry = buf_in + (size_t)r * NFFT;
     const float* fresh = chunk + (size_t)r * L * HOPS;
     // complex sample c (0..1023) of frame l = S[(l+1)*1024 + 2c], S[.. + 1]: the carried buffer below index 2048 of S, the chunk above
@@ -626,13 +725,33 @@ __global__ __launch_bounds__(256, FFT_OCC_STFT) void stream_block_analysis_kerne
 // window.  A workgroup produces output hops [b0, b1) of one row, keeps the second half of the previous frame in registers and either
 // reads it from prev_in (b0 = 0) or recomputes frame b0 - 1; the spectrum of the next frame is requested before the FFT passes of the
 // current one.  MIX: the wet / dry control of stream_synthesis_kernel (the launcher picks MIX = mix != 1).
-template <bool MIX>
+// ROWS = HeldRows: a held row's workgroups write zeros to their hops, and the first of them copies the previous frame and the row's LSTM
+// state.  With a wet / dry value per row the launcher picks MIX = true, and a row at 1 skips the blend (a branch around register
+// arithmetic only, uniform over the workgroup): its spectra reach the transform untouched, as under MIX = false.
+template <bool MIX, class ROWS>
 __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void stream_block_synthesis_kernel(FftTables tb, const float* __restrict__ Y, const float* __restrict__ X,
-                                                                                    const float mix, const float* __restrict__ prev_in,
-                                                                                    float* __restrict__ prev_out, float* __restrict__ out, int L, int ich)
+                                                                                    const float mix_all, const float* __restrict__ prev_in,
+                                                                                    float* __restrict__ prev_out, float* __restrict__ out, int L, int ich,
+                                                                                    ROWS rows)
 {
     __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
     const int tid = threadIdx.x;
+    float mix = mix_all;
+    if constexpr (ROWS::masked) {
+        const int r = blockIdx.y;
+        if (!row_set_has(rows.active, r)) {
+            const int b0 = blockIdx.x * ich;
+            const int b1 = (b0 + ich < L) ? b0 + ich : L;
+            for (int b = b0; b < b1; ++b) zero_hop(out + ((size_t)r * L + b) * HOPS, tid);
+            if (blockIdx.x == 0) {
+                copy_floats4(prev_in + (size_t)r * NFFT, prev_out + (size_t)r * NFFT, NFFT / 4, tid);
+                hold_state_row(rows, r, tid);
+            }
+            return;
+        }
+        if (MIX && rows.mix_rows) mix = rows.mix_rows[r];
+    }
+    const bool blend = !ROWS::masked || mix != 1.f;       // (AllRows: the launcher chose MIX by it)
     const Twiddles twd = load_twiddles<true>(tb.tw1024, tid);
     const SplitCtx spl = load_split(tb, tid, true);
     const int r = blockIdx.y;
@@ -656,14 +775,17 @@ __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void stream_block_synthesis_ker
     };
     // The frame in front of the range only fills the carry; it is peeled so that the loop body has no branch around its loads and stores
     auto frame = [&](int t, auto first) {
-        if (MIX) {
+        if (MIX && blend) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                my.xk[i] = make_float2(mix * my.xk[i].x + dry * mx.xk[i].x, mix * my.xk[i].y + dry * mx.xk[i].y);
-                my.xc[i] = make_float2(mix * my.xc[i].x + dry * mx.xc[i].x, mix * my.xc[i].y + dry * mx.xc[i].y);
+                my.xk[i] = make_float2(fmaf(mix, my.xk[i].x, dry * mx.xk[i].x), fmaf(mix, my.xk[i].y, dry * mx.xk[i].y));
+                my.xc[i] = make_float2(fmaf(mix, my.xc[i].x, dry * mx.xc[i].x), fmaf(mix, my.xc[i].y, dry * mx.xc[i].y));
             }
         }
-        irfft_store(my, spl, z0, tid);
+        // The fused multiply-adds of the blend above and of the merge are spelled out (irfft_store<true>), as in istft_walk: left to the
+        // compiler's contraction, which product is rounded first differed between the instantiations of this kernel, and a row of a rows
+        // call has to get the bits of the plain call whichever of them computes it.
+        irfft_store<true>(my, spl, z0, tid);
         __syncthreads();
         request(t + 1 < b1 ? t + 1 : t);                              // (after the last frame: a dummy reload)
         const float2* z = fft1024<true>(z0, z1, twd, tid);
@@ -704,15 +826,32 @@ __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void stream_block_synthesis_ker
 
 void launch_stream_block_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L, hipStream_t s)
 {
-    const Chunks ch = chunks_for<stream_block_analysis_kernel>(L, C, 0);
-    hipLaunchKernelGGL(stream_block_analysis_kernel, ch.grid, dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, L, ch.len);
+    const Chunks ch = chunks_for<stream_block_analysis_kernel<AllRows>>(L, C, 0);
+    hipLaunchKernelGGL(stream_block_analysis_kernel<AllRows>, ch.grid, dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, L, ch.len, AllRows{});
 }
 void launch_stream_block_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, const float* prev_in, float* prev_out, float* out,
                                    int C, int L, hipStream_t s)
 {
-    const Chunks ch = chunks_for<stream_block_synthesis_kernel<false>>(L, C, 1);
-    if (mix == 1.f) hipLaunchKernelGGL(stream_block_synthesis_kernel<false>, ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len);
-    else hipLaunchKernelGGL(stream_block_synthesis_kernel<true>, ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len);
+    const Chunks ch = chunks_for<stream_block_synthesis_kernel<false, AllRows>>(L, C, 1);
+    if (mix == 1.f) hipLaunchKernelGGL((stream_block_synthesis_kernel<false, AllRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, AllRows{});
+    else hipLaunchKernelGGL((stream_block_synthesis_kernel<true, AllRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, AllRows{});
+}
+// (the chunk lengths may differ from the plain launches': a hop has the same bits whichever workgroup computes it, see above)
+void launch_stream_block_analysis_rows(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L,
+                                       const RowSet& active, hipStream_t s)
+{
+    const Chunks ch = chunks_for<stream_block_analysis_kernel<HeldRows>>(L, C, 0);
+    hipLaunchKernelGGL(stream_block_analysis_kernel<HeldRows>, ch.grid, dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, L, ch.len,
+                       HeldRows{active, nullptr, nullptr, nullptr, C, 0});
+}
+void launch_stream_block_synthesis_rows(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
+                                        float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, int L,
+                                        const RowSet& active, hipStream_t s)
+{
+    const HeldRows rows{active, mix_rows, state_in, state_out, C, K};
+    const Chunks ch = chunks_for<stream_block_synthesis_kernel<false, HeldRows>>(L, C, 1);
+    if (!mix_rows && mix == 1.f) hipLaunchKernelGGL((stream_block_synthesis_kernel<false, HeldRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
+    else hipLaunchKernelGGL((stream_block_synthesis_kernel<true, HeldRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
 }
 
 // ------------------------------------------------------------------------------ offline DSP, one segment of a clip

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "descriptors.h"   // GemmJob, ChainDesc and the constants the host packs against (HIP-free)
+#include "stream_rows_host.h"   // RowSet: the rows a streaming rows call means, by value (HIP-free)
 
 namespace bsrnn {
 
@@ -275,6 +276,21 @@ void launch_stream_synthesis(const FftTables& tb, const float* Y, const float* X
 void launch_stream_block_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L, hipStream_t s);
 void launch_stream_block_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, const float* prev_in, float* prev_out, float* out,
                                    int C, int L, hipStream_t s);
+// The four launches above for a call that advances only the rows in `active` (bsrnn_stream_process_rows; the set travels by value,
+// stream_rows_host.h).  A held row: buf_out / prev_out = buf_in / prev_in, zero rows in X, zeros in out, chunk unread - and, in the
+// synthesis, its LSTM state copied from state_in to state_out [4][2][C*K][64], so that launch follows the model's.  mix_rows, if not
+// null, holds one wet / dry value per row [C] on the device and replaces `mix`.  Active rows: the bits of the plain launches.
+void launch_stream_analysis_rows(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, const RowSet& active,
+                                 hipStream_t s);
+void launch_stream_synthesis_rows(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
+                                  float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, const RowSet& active, hipStream_t s);
+void launch_stream_block_analysis_rows(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L,
+                                       const RowSet& active, hipStream_t s);
+void launch_stream_block_synthesis_rows(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
+                                        float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, int L,
+                                        const RowSet& active, hipStream_t s);
+// zeroes buf, prev and state of the rows in `rows` of one carry set, in one launch (bsrnn_stream_reset_rows)
+void launch_stream_reset_rows(float* buf, float* prev, float* state, int C, int K, const RowSet& rows, hipStream_t s);
 
 // ------------------------------------------------------------------ validation metrics (metrics.hip)
 // Per-workgroup partial sums in double; the host adds them.  est [R][n_est]; speech, mix [R][n_in] (first n_est used).

@@ -1,0 +1,235 @@
+#!/usr/bin/env python3
+"""Session slots against their alternatives, on one GPU, inputs resident, deferred range policy, one hop per step.
+
+Part 1, for S = 1, 8 and 32 live sessions of 2 rows each (REPORTED, no ratio is asked of it):
+  (a) one bsrnn_stream_process_rows on ONE stream of 64 rows (32 slots): the S sessions' rows active with a wet / dry value per row,
+      the other rows held - the row-masked kernels
+  (b) S separate two-row streams, bsrnn_stream_step on each in turn (a context takes one call at a time)
+  (p) StreamPool.step for the same S sessions: (a) plus the Python side's packing and unpacking of the sessions' tensors
+
+Part 2, at C = 64 (a CHECK: the rows entry point with nothing held must cost what the plain call costs):
+  (r) bsrnn_stream_process_rows, active = ones, mix_rows_dev = NULL      (f) the same with mix_rows_dev = ones: the row-masked kernels
+  (q) bsrnn_stream_process
+Every run of part 2 is a process of its own, and runs alternate between this build and, with --baseline-lib, another build of the
+library (the parent commit's, which has no rows call: q only), twice each: the difference between the two runs of the SAME library
+is the file's own run-to-run spread, and q of this build against q of the baseline is to be read against it.
+
+Each figure is the median over REPEATS windows of a host clock around enough jobs to fill ~0.2 s, ending in a device synchronise; the
+variants alternate inside every repeat, and min .. max of the windows is printed beside the median.
+
+    python tools/stream_pool_bench.py [--baseline-lib PATH] [--out profiles/stream_rows_ab.txt]
+"""
+import argparse
+import ctypes
+import os
+import subprocess
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+SESSIONS = (1, 8, 32)
+ROWS = 2
+SLOTS = 32
+REPEATS = 7
+WINDOW_S = 0.2
+HOP = 1024
+PLAIN_SHAPES = ((64, 1), (64, 8))
+
+
+def measure(jobs, sync):
+    """{name: job} -> {name: (median, min, max)} in us per job; the jobs alternate inside every repeat."""
+    import numpy as np
+    n = {}
+    for k, f in jobs.items():                     # warm-up, and how many jobs fill a window
+        for _ in range(3):
+            f()
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(3):
+            f()
+        sync()
+        n[k] = max(3, int(WINDOW_S / max((time.perf_counter() - t0) / 3, 1e-6)))
+    t = {k: [] for k in jobs}
+    for _ in range(REPEATS):
+        for k, f in jobs.items():
+            sync()
+            t0 = time.perf_counter()
+            for _ in range(n[k]):
+                f()
+            sync()
+            t[k].append((time.perf_counter() - t0) / n[k] * 1e6)
+    return {k: (float(np.median(v)), min(v), max(v)) for k, v in t.items()}
+
+
+def cell(v):
+    return "%9.1f [%8.1f .. %8.1f]" % v
+
+
+def setup():
+    import torch
+    from speechseparation_amd import weights
+    from speechseparation_amd.bsrnn import BSRNN
+    assert torch.cuda.is_available(), "needs a GPU"
+    sd = weights.synth_state_dict(None, seed=0)
+    model = BSRNN().eval()
+    model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()})
+    model = model.to("cuda:0")
+    model.set_range_policy("deferred")
+    return model
+
+
+def plain_only():
+    """Part 2 in this process, on the library BSRNN_HIP_LIB names (default: the in-tree build), through the C ABI alone - the same
+    harness for a build with and without the rows calls: one line per shape."""
+    import numpy as np
+    from speechseparation_amd import spec, weights
+    path = os.environ.get("BSRNN_HIP_LIB") or os.path.join(REPO, "speechseparation_amd", "lib", "libbsrnn_hip.so")
+    lib = ctypes.CDLL(path)
+    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+    sig = {"bsrnn_create": [ctypes.c_int, ctypes.POINTER(i32), i32, ctypes.POINTER(vp)], "bsrnn_set_param": [vp, ctypes.c_char_p, vp, i64],
+           "bsrnn_commit_params": [vp], "bsrnn_set_range_policy": [vp, i32], "bsrnn_stream_create": [vp, i32, ctypes.POINTER(vp)],
+           "bsrnn_stream_reserve": [vp, i32], "bsrnn_stream_process": [vp, vp, vp, i32, ctypes.c_float, vp], "bsrnn_dev_alloc": [vp, i64, ctypes.POINTER(vp)],
+           "bsrnn_copy_h2d": [vp, vp, vp, i64], "bsrnn_sync": [vp, vp], "bsrnn_stream_destroy": [vp], "bsrnn_dev_free": [vp, vp]}
+    has_rows = hasattr(lib, "bsrnn_stream_process_rows")
+    if has_rows:
+        sig["bsrnn_stream_process_rows"] = [vp, vp, vp, i32, vp, vp, ctypes.c_float, vp]
+    for name, args in sig.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = None if name == "bsrnn_stream_destroy" else ctypes.c_int
+    lib.bsrnn_last_error.restype = ctypes.c_char_p
+
+    def check(rc):
+        if rc != 0:
+            raise SystemExit("libbsrnn_hip: error %d: %s" % (rc, lib.bsrnn_last_error().decode()))
+    v = spec.generate_bandsplits()[0]
+    ctx = vp()
+    check(lib.bsrnn_create(0, (i32 * len(v))(*v), len(v), ctypes.byref(ctx)))
+    for key, val in weights.synth_state_dict(None, seed=0).items():
+        a = np.ascontiguousarray(val, np.float32)
+        check(lib.bsrnn_set_param(ctx, key.encode(), a.ctypes.data_as(vp), a.size))
+    check(lib.bsrnn_commit_params(ctx))
+    check(lib.bsrnn_set_range_policy(ctx, 0))                # deferred
+
+    def on_device(a):
+        p = vp()
+        check(lib.bsrnn_dev_alloc(ctx, a.nbytes, ctypes.byref(p)))
+        check(lib.bsrnn_copy_h2d(ctx, p, a.ctypes.data_as(vp), a.nbytes))
+        return p
+    one = ctypes.c_float(1.0)
+    for C, L in PLAIN_SHAPES:
+        st = vp()
+        check(lib.bsrnn_stream_create(ctx, C, ctypes.byref(st)))
+        check(lib.bsrnn_stream_reserve(st, L))
+        wave = on_device(np.ascontiguousarray(weights.synth_waveform(C, L * HOP, seed=5), np.float32))
+        out = on_device(np.zeros((C, L * HOP), np.float32))
+        jobs = {"q": lambda: check(lib.bsrnn_stream_process(st, wave, out, L, one, None))}
+        if has_rows:
+            ones = (ctypes.c_uint8 * C)(*([1] * C))
+            mix_rows = on_device(np.ones(C, np.float32))
+            jobs["r"] = lambda: check(lib.bsrnn_stream_process_rows(st, wave, out, L, ones, None, one, None))
+            jobs["f"] = lambda: check(lib.bsrnn_stream_process_rows(st, wave, out, L, ones, mix_rows, one, None))
+        res = measure(jobs, lambda: check(lib.bsrnn_sync(ctx, None)))
+        print("PLAIN %d %d %s" % (C, L, " ".join("%s %.2f %.2f %.2f" % ((k,) + v) for k, v in res.items())), flush=True)
+        lib.bsrnn_stream_destroy(st)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--baseline-lib", default=None, help="another build of libbsrnn_hip.so (the parent commit's) for part 2")
+    ap.add_argument("--plain-only", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.plain_only:
+        return plain_only()
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    # ---- part 2 first: child processes, before this one opens the GPU
+    runs = [("this build", None), ("this build", None)]
+    if args.baseline_lib:
+        base = os.path.abspath(args.baseline_lib)
+        assert os.path.exists(base), base
+        runs = [("baseline", base), ("this build", None), ("baseline", base), ("this build", None)]
+    part2 = []
+    for name, path in runs:
+        env = dict(os.environ)
+        env.pop("BSRNN_HIP_LIB", None)
+        if path:
+            env["BSRNN_HIP_LIB"] = path
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--plain-only"], env=env, capture_output=True, text=True, timeout=600)
+        if out.returncode != 0:
+            sys.stderr.write(out.stdout + out.stderr)
+            raise SystemExit("part 2 run on %s failed with status %d" % (name, out.returncode))
+        for ln in out.stdout.splitlines():
+            if ln.startswith("PLAIN "):
+                f = ln.split()
+                vals = {f[i]: tuple(float(x) for x in f[i + 1:i + 4]) for i in range(3, len(f), 4)}
+                part2.append((name, int(f[1]), int(f[2]), vals))
+
+    import torch
+    from speechseparation_amd import _native, weights
+    from speechseparation_amd.bsrnn import StreamingSeparator, StreamPool
+    lib, check = _native.lib, _native.check
+    model = setup()
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    one = ctypes.c_float(1.0)
+    say("# %s, %s, compute mode %s" % (torch.cuda.get_device_name(0), torch.version.hip, _native.compute_mode()))
+    say("# us per step of one hop: median [min .. max] of %d windows of ~%.1f s" % (REPEATS, WINDOW_S))
+    say("# part 1: S sessions of %d rows.  a = one process_rows on a %d-row stream (S sessions active, per-row mix, the rest held), "
+        "b = S two-row streams stepped in turn, p = StreamPool.step" % (ROWS, SLOTS * ROWS))
+    say("%4s %28s %28s %28s %8s %8s" % ("S", "a us", "b us", "p us", "b/a", "b/p"))
+    C = SLOTS * ROWS
+    wide = StreamingSeparator(model, channels=C, device="cuda:0")
+    pool = StreamPool(model, SLOTS, rows_per_session=ROWS, device="cuda:0")
+    sids = [pool.open() for _ in range(SLOTS)]
+    singles = [StreamingSeparator(model, channels=ROWS, device="cuda:0") for _ in range(max(SESSIONS))]
+    wave = torch.from_numpy(weights.synth_waveform(C, HOP, seed=5)).cuda()
+    out = torch.empty_like(wave)
+    mix_rows = torch.ones(C, device="cuda")
+    pairs = [wave[ROWS * i:ROWS * (i + 1)].contiguous() for i in range(SLOTS)]
+    pair_out = torch.empty((ROWS, HOP), device="cuda")
+    for S in SESSIONS:
+        active = (ctypes.c_uint8 * C)(*([1] * (ROWS * S) + [0] * (C - ROWS * S)))
+        chunks = {sids[i]: pairs[i] for i in range(S)}
+        mixes = {sids[i]: 1.0 for i in range(S)}
+
+        def job_a():
+            check(lib.bsrnn_stream_process_rows(wide._h, ptr(wave), ptr(out), 1, active, ptr(mix_rows), one, None))
+
+        def job_b():
+            for i in range(S):
+                check(lib.bsrnn_stream_step(singles[i]._h, ptr(pairs[i]), ptr(pair_out), one, None))
+
+        def job_p():
+            pool.step(chunks, mixes)
+
+        r = measure({"a": job_a, "b": job_b, "p": job_p}, torch.cuda.synchronize)
+        model.sync()
+        say("%4d %28s %28s %28s %8.2f %8.2f" % (S, cell(r["a"]), cell(r["b"]), cell(r["p"]), r["b"][0] / r["a"][0], r["b"][0] / r["p"][0]))
+    say("")
+    say("# part 2: C = 64, nothing held, each line a process of its own.  q = stream_process, r = stream_process_rows(active = ones, "
+        "mix_rows = NULL), f = the same with mix_rows = ones (row-masked kernels)")
+    say("%-11s %4s %4s %28s %28s %28s" % ("library", "C", "L", "q us", "r us", "f us"))
+    for name, Cc, L, vals in part2:
+        say("%-11s %4d %4d %28s %28s %28s" % (name, Cc, L, cell(vals["q"]), cell(vals["r"]) if "r" in vals else "-", cell(vals["f"]) if "f" in vals else "-"))
+    for Cc, L in PLAIN_SHAPES:
+        q = {n: [v["q"][0] for (nm, c2, l2, v) in part2 if nm == n and (c2, l2) == (Cc, L)] for n in ("baseline", "this build")}
+        spread = max(abs(v[0] - v[1]) for v in q.values() if len(v) == 2)
+        line = "C %d L %d: run-to-run spread of q (same library, two processes) %.1f us" % (Cc, L, spread)
+        if q["baseline"]:
+            line += "; q this build - q baseline (means of the two runs) %+.1f us" % (sum(q["this build"]) / 2 - sum(q["baseline"]) / 2)
+        rr = [v["r"][0] - v["q"][0] for (nm, c2, l2, v) in part2 if nm == "this build" and (c2, l2) == (Cc, L)]
+        line += "; r - q inside a run %s us" % ", ".join("%+.1f" % x for x in rr)
+        say(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
