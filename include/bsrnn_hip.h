@@ -129,7 +129,9 @@ int  bsrnn_debug_peek(bsrnn_ctx* ctx, int32_t which, float* host_out, int64_t nf
 /* Process-wide counts of what the library has done that does not belong on a real-time thread: which = 0 device / pinned / stream
  * allocations, 1 stream captures begun, 2 graph instantiations, 3 graph launches.  A bsrnn_stream does all of the first three in
  * bsrnn_stream_create (as the reference's plugin does in its constructor, speech-ladspa-onnx.cpp:55-120); its step calls leave them
- * unchanged (tests/test_gpu_entrypoints.py drives the LADSPA plugin's run() and checks). */
+ * unchanged (tests/test_gpu_entrypoints.py drives the LADSPA plugin's run() and checks).  which = 4 counts work instead: the frame rows
+ * (rows x frames, summed over the segments) bsrnn_separate_long_ragged has handed to the model - below R * Tmax when rows retire.
+ * Any other value: -1. */
 long long bsrnn_debug_counter(int32_t which);
 
 /* ---- parameters ---------------------------------------------------------------------
@@ -328,6 +330,29 @@ int  bsrnn_separate_long(bsrnn_ctx* ctx, const float* wave_dev, float* wave_out_
                          void* stream);
 int  bsrnn_separate_long_host(bsrnn_ctx* ctx, const float* wave_host, float* wave_out_host, int32_t R, int64_t n,
                               int32_t seg_frames);
+/* bsrnn_separate_long_ragged = bsrnn_separate_ragged in segments: R clips of DIFFERENT lengths, each of any length, from a workspace of
+ * R * min(seg_frames, Tmax) frame rows.  Arguments and result as bsrnn_separate_ragged: rows wave_stride floats apart, lens_host[r]
+ * samples in row r (1024 < lens_host[r] <= wave_stride, nothing behind them is read), wave_out_dev [R, (Tmax-1)*1024] with row r holding
+ * the (lens[r] / 1024) * 1024 samples of that clip, then zeros; all of it is written.  The Tmax frames are cut as bsrnn_separate_long cuts
+ * them.  Segment i, frames [ta, te), runs on the ALIVE PREFIX of the rows, R_i = 1 + the last row r with T_r > ta: STFT of those rows
+ * (reflect padding at each clip's own ends; a row's frames at and behind T_r are zero spectra) -> the model on R_i * (te - ta) frame rows
+ * with the time-axis state carried -> iSTFT of the segment's hops over all R rows (zeros where a row has ended).  Rows are never
+ * reordered: a row inside the prefix that has already ended is carried as zero frames, so any order gives each clip's result, and
+ * LONGEST FIRST is the cheap one - then the model runs on about the real frames, rounded up to a segment per row
+ * (bsrnn_debug_counter(4) counts them).  When the prefix shrinks the surviving rows' state and overlap-add tail are packed by one small
+ * launch on the caller's stream; nothing is allocated or waited for.
+ *   - seg_frames >= Tmax: the call IS bsrnn_separate_ragged (it delegates: bit-identical).  Equal lengths: bit-identical to
+ *     bsrnn_separate_long(R, n, seg_frames).  Unequal lengths: a row agrees with bsrnn_separate of that clip alone to rounding.
+ *   - Before the first launch: the workspace, the task tables of every distinct R_i * (te - ta) of the call, the two carry sets of
+ *     bsrnn_separate_long for R rows; the lengths go up once per call through the pinned mirrors of bsrnn_separate_ragged's block, so
+ *     lens_host is the caller's again at return.  A second call that fits allocates nothing (bsrnn_debug_counter(0)).
+ *   - Range policy per segment, as bsrnn_separate_long; wave_out_dev must not overlap the R * wave_stride floats of wave_dev under
+ *     EITHER policy.
+ * BSRNN_EARG, before any device work (also on a host-only context, in front of its BSRNN_ESTATE): a null ctx, wave_dev, lens_host or
+ * wave_out_dev; R < 1; seg_frames < 1; a length <= 1024 or > wave_stride (the text names the row and the value); R * min(seg_frames, Tmax)
+ * beyond 2^30 frame rows; the overlap. */
+int  bsrnn_separate_long_ragged(bsrnn_ctx* ctx, const float* wave_dev, int64_t wave_stride, const int64_t* lens_host,
+                                float* wave_out_dev, int32_t R, int32_t seg_frames, void* stream);
 /* Frame rows the context's current workspace holds (measurement / test support); 0 before first use, on a host-only context and for
  * a null context.  The workspace is grow-only: this is the largest R * T (or R * seg_frames) any call has needed, rounded up by growth. */
 int64_t bsrnn_workspace_rows(const bsrnn_ctx* ctx);

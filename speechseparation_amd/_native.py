@@ -25,7 +25,7 @@ SYMBOLS = [
     "bsrnn_linear_group_train_forward", "bsrnn_linear_group_train_backward", "bsrnn_train_reduction_layout",
     "bsrnn_set_range_policy", "bsrnn_get_range_policy", "bsrnn_overlap_state", "bsrnn_debug_peek", "bsrnn_debug_counter",
     "bsrnn_stream_process", "bsrnn_stream_reserve", "bsrnn_separate_long", "bsrnn_separate_long_host", "bsrnn_workspace_rows",
-    "bsrnn_separate_ragged", "bsrnn_evaluate_ragged",
+    "bsrnn_separate_ragged", "bsrnn_evaluate_ragged", "bsrnn_separate_long_ragged",
     "bsrnn_stream_process_rows", "bsrnn_stream_reset_rows", "bsrnn_stream_row_floats", "bsrnn_stream_get_row", "bsrnn_stream_set_row",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
@@ -91,6 +91,7 @@ def _load():
         "bsrnn_separate_ragged": (C.c_int, [vp, vp, i64, vp, vp, i32, vp]),
         "bsrnn_separate_long": (C.c_int, [vp, vp, vp, i32, i64, i32, vp]),
         "bsrnn_separate_long_host": (C.c_int, [vp, vp, vp, i32, i64, i32]),
+        "bsrnn_separate_long_ragged": (C.c_int, [vp, vp, i64, vp, vp, i32, i32, vp]),
         "bsrnn_workspace_rows": (i64, [vp]),
         "bsrnn_stream_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
         "bsrnn_stream_destroy": (None, [vp]),

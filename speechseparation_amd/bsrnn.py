@@ -420,6 +420,88 @@ class BSRNN(nn.Module):
                 r0 += ch
         return results
 
+    def separate_long_ragged(self, waveform, lengths, segment_frames=256, out=None):
+        """`separate_ragged` in segments, for clips that are long AND unequal: waveform [R, n_max], row r holding lengths[r] samples ->
+        [R, (Tmax - 1) * 1024] exactly as `separate_ragged` lays it out (each row its clip's samples, then zeros), from a workspace of
+        R * segment_frames frame rows.  A row that has ended is absent from later segments, so put the rows LONGEST FIRST: then the model
+        runs on about the real frames, rounded up to a segment per row (`spec.long_plan` gives the count); any order gives the same
+        result to rounding, a row that ends in front of a longer one is carried as zero frames.  Checks and `out` as `separate_ragged`;
+        segment_frames >= Tmax is `separate_ragged` itself, equal lengths are `separate_long` (both bit-identical).  A CPU waveform is
+        moved to the device whole (there is no host-buffer variant), the result comes back as a CPU tensor.  The default of 256 frames
+        is inherited from `separate_long`, not a measured optimum (include/bsrnn_hip.h, bsrnn_separate_long_ragged)."""
+        if not isinstance(waveform, torch.Tensor) or waveform.dim() != 2:
+            raise ValueError("separate_long_ragged: expected waveform [R, n_max], got %s" % (
+                tuple(waveform.shape) if isinstance(waveform, torch.Tensor) else type(waveform).__name__,))
+        R, n_max = waveform.shape
+        try:
+            lens = [int(x) for x in lengths]
+        except TypeError:
+            raise ValueError("separate_long_ragged: lengths must be a sequence of %d ints, got %s" % (R, type(lengths).__name__)) from None
+        if len(lens) != R or R < 1:
+            raise ValueError("separate_long_ragged: %d lengths for %d rows" % (len(lens), R))
+        for r, n in enumerate(lens):
+            if not _spec.HOP < n <= n_max:
+                raise ValueError("separate_long_ragged: row %d has %d samples, need 1024 < length <= %d" % (r, n, n_max))
+        try:
+            seg = int(segment_frames)
+        except (TypeError, ValueError):
+            raise ValueError("separate_long_ragged: segment_frames must be an int, got %r" % (segment_frames,)) from None
+        if seg < 1:
+            raise ValueError("separate_long_ragged: segment_frames = %d (at least one frame per segment)" % seg)
+        shape = (R, (max(lens) // _spec.HOP) * _spec.HOP)
+        if out is not None and not isinstance(out, torch.Tensor):
+            raise ValueError("separate_long_ragged: out must be a tensor, got %s" % type(out).__name__)
+        dev = self._device_for(waveform)
+        if out is not None and (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError("separate_long_ragged: out must be a contiguous float32 tensor %s on %s, got %s %s on %s" % (
+                shape, dev, tuple(out.shape), out.dtype, out.device))
+        w = self._prep(waveform, dev)
+        with torch.cuda.device(dev):
+            ctx = self._context(dev)
+            if out is None:
+                out = torch.empty(shape, device=dev, dtype=torch.float32)
+            _check(_lib.bsrnn_separate_long_ragged(ctx, _ptr(w), n_max, (ctypes.c_int64 * R)(*lens), _ptr(out), R, seg, _stream_ptr(dev)))
+        return out if waveform.is_cuda else out.cpu()
+
+    def separate_many_long(self, clips, segment_frames=256, max_rows=64):
+        """`separate_many` for clips that are long and of very different lengths: clips are 1-D [n] or 2-D [ch, n] tensors (n > 1024) on
+        the GPU or the CPU.  `spec.long_buckets` sorts them longest first and fills buckets of at most `max_rows` rows - no padding cap,
+        the segments bound the padding -, each bucket is packed into one [rows, n_max] buffer, rows longest first, and runs as ONE
+        `separate_long_ragged` call.  Returns the results in input order, each [ch, (n // 1024) * 1024] - 1-D for a 1-D clip - on its
+        clip's own device, equal to `separate` of that clip alone to rounding."""
+        clips = list(clips)
+        for i, c in enumerate(clips):
+            if not isinstance(c, torch.Tensor) or c.dim() not in (1, 2) or c.shape[-1] <= _spec.HOP or c.shape[0] < 1:
+                raise ValueError("separate_many_long: clip %d must be a tensor [n] or [ch, n] with n > 1024, got %s" % (
+                    i, tuple(c.shape) if isinstance(c, torch.Tensor) else type(c).__name__))
+        try:
+            seg = int(segment_frames)
+        except (TypeError, ValueError):
+            raise ValueError("separate_many_long: segment_frames must be an int, got %r" % (segment_frames,)) from None
+        if seg < 1:
+            raise ValueError("separate_many_long: segment_frames = %d (at least one frame per segment)" % seg)
+        buckets = _spec.long_buckets([_spec.n_frames(c.shape[-1]) for c in clips], [1 if c.dim() == 1 else c.shape[0] for c in clips], max_rows)
+        if not clips:
+            return []
+        dev = next((c.device for c in clips if c.is_cuda), None) or self._device_for(clips[0])
+        results = [None] * len(clips)
+        for bucket in buckets:
+            rows = [1 if clips[i].dim() == 1 else clips[i].shape[0] for i in bucket]
+            lens = [clips[i].shape[-1] for i in bucket]
+            buf = torch.empty((sum(rows), max(lens)), device=dev, dtype=torch.float32)      # (behind a row's end nothing is read)
+            r0 = 0
+            for i, ch, n in zip(bucket, rows, lens):
+                buf[r0:r0 + ch, :n] = clips[i].detach().reshape(ch, n).to(device=dev, dtype=torch.float32)
+                r0 += ch
+            out = self.separate_long_ragged(buf, [n for ch, n in zip(rows, lens) for _ in range(ch)], seg)
+            r0 = 0
+            for i, ch, n in zip(bucket, rows, lens):
+                y = out[r0:r0 + ch, :(n // _spec.HOP) * _spec.HOP]
+                y = (y[0] if clips[i].dim() == 1 else y).to(clips[i].device, copy=True)
+                results[i] = y.contiguous()
+                r0 += ch
+        return results
+
     def workspace_rows(self, device=None):
         """Frame rows the native context's workspace holds right now (grow-only; 0 before the first call): what `separate` raises to
         R * T and `separate_long` keeps at R * segment_frames (bsrnn_workspace_rows).  `device`: only the context on that device counts."""

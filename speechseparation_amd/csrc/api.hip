@@ -23,9 +23,10 @@ using namespace bsrnn;
 
 // --------------------------------------------------------------------------- first-use accounting (bsrnn_debug_counter)
 // What the library has done that does not belong on a real-time thread: device / pinned allocations, stream captures, graph
-// instantiations.  Process-wide; tests read them around the LADSPA plugin's run() (tests/test_gpu_entrypoints.py).
-static std::atomic<long long> g_dbg[4];
-enum { DBG_ALLOC = 0, DBG_CAPTURE = 1, DBG_INSTANTIATE = 2, DBG_GRAPH_LAUNCH = 3 };
+// instantiations.  Process-wide; tests read them around the LADSPA plugin's run() (tests/test_gpu_entrypoints.py).  The fifth counts work, not
+// first use: the frame rows (rows x frames) bsrnn_separate_long_ragged has handed to the model, which is what shows that rows retire.
+static std::atomic<long long> g_dbg[5];
+enum { DBG_ALLOC = 0, DBG_CAPTURE = 1, DBG_INSTANTIATE = 2, DBG_GRAPH_LAUNCH = 3, DBG_LONG_RAGGED_ROWS = 4 };
 
 // --------------------------------------------------------------------------- error plumbing
 static thread_local char g_err[512] = "";
@@ -1035,7 +1036,7 @@ int bsrnn_debug_peek(bsrnn_ctx* c, int32_t which, float* host_out, int64_t nfloa
     HIP_TRY(hipMemcpy(host_out, src[which], (size_t)nfloats * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
-long long bsrnn_debug_counter(int32_t which) { return which >= 0 && which < 4 ? g_dbg[which].load() : -1; }
+long long bsrnn_debug_counter(int32_t which) { return which >= 0 && which < 5 ? g_dbg[which].load() : -1; }
 int bsrnn_overlap_state(const bsrnn_ctx* c) { return !c ? -1 : (c->overlap_off ? 2 : (c->overlap_env ? 1 : 0)); }
 int bsrnn_set_range_policy(bsrnn_ctx* c, int32_t policy)
 {
@@ -1897,6 +1898,99 @@ int bsrnn_separate_long_host(bsrnn_ctx* c, const float* wave_host, float* wave_o
     }
     if ((rc = long_prepare(c, R, T, seg, "bsrnn_separate_long_host"))) return rc;
     return long_segments(c, wave_host, wave_out_host, R, n, T, seg, s, true);
+}
+
+// --------------------------------------------------------------------------- ragged long-form: rows of different lengths in segments
+// bsrnn_separate_ragged's batch cut like bsrnn_separate_long's clip, and both arguments hold together: the model is causal along time, the
+// band-axis blocks and the per-band MLPs see one frame at a time, rows are independent.  Segment i runs the model on the alive prefix of
+// the rows (plan_host.h: ragged_long_plan) - a row that has ended is absent from later segments, one inside the prefix is carried as zero
+// frames - so the model sees about the real frames, rounded up to a segment per row, from a workspace of R x seg frame rows.  Carry sets as
+// long_segments': segment i reads set p and writes set p ^ 1, and p flips when the segment is final.  When the prefix shrinks, the next
+// segment's state has another slab pitch: the surviving rows' state and overlap-add tail are packed from the written set into the one the
+// finished segment read (launch_long_compact, on the caller's stream), and p does NOT flip - so a segment always reads a set that nothing
+// of its own writes, and its range re-run (finish_call) starts from untouched state and carry.
+int bsrnn_separate_long_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_stride, const int64_t* lens_host, float* wave_out, int32_t R,
+                               int32_t seg_frames, void* stream)
+{
+    // arguments first, device or not (a host-only context answers them before BSRNN_ESTATE)
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!wave || !lens_host || !wave_out || R < 1)
+        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: need a waveform, R lengths, an output buffer and R >= 1, got R = %d", R);
+    if (seg_frames < 1) return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: seg_frames = %d (at least one frame per segment)", seg_frames);
+    const RaggedLongPlan q = ragged_long_plan(lens_host, R, wave_stride, seg_frames);
+    if (q.shape.why == RAGGED_SHORT)
+        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: row %d has %lld samples, need more than 1024 (reflect padding)", q.shape.bad_row,
+                    (long long)q.shape.bad_len);
+    if (q.shape.why == RAGGED_LONG)
+        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: row %d has %lld samples, more than the row stride of %lld", q.shape.bad_row,
+                    (long long)q.shape.bad_len, (long long)wave_stride);
+    if (q.too_many)
+        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: %d rows x %lld frames is too many frame rows for one segment", R,
+                    (long long)std::min<int64_t>(seg_frames, q.shape.Tmax));
+    // whatever the range policy: later segments read the waveform after earlier hops are written
+    const int64_t out_stride = q.shape.out_stride;
+    if (ranges_overlap(wave, (size_t)R * wave_stride * sizeof(float), wave_out, (size_t)R * out_stride * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: wave_out must not overlap wave (later segments read the waveform after earlier hops are written)");
+    if (seg_frames >= q.shape.Tmax) {                                 // one segment IS the ragged call: bit-identical by construction
+        const int rc1 = bsrnn_separate_ragged(c, wave, wave_stride, lens_host, wave_out, R, stream);
+        if (!rc1) g_dbg[DBG_LONG_RAGGED_ROWS] += q.frame_rows;
+        return rc1;
+    }
+    int rc = check_ready(c);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const int T = (int)q.shape.Tmax, seg = seg_frames, K = c->K;
+    // everything the segments need, before the first launch: the workspace of one segment, the task tables and (where a segment's plan
+    // overlaps the dual path) the dispatch orders of every distinct shape rows[i] x frames, the carry sets.  The caches' bounds grow so
+    // that this call's set fits beside what is there (as bsrnn_stream_reserve's).
+    if ((rc = ensure_ws(c, (size_t)R * seg))) return rc;
+    std::vector<std::pair<int, int>> shapes;
+    for (int i = 0; i < q.nseg; ++i) {
+        const std::pair<int, int> sh(q.rows[i], std::min(T, (i + 1) * seg) - i * seg);
+        if (std::find(shapes.begin(), shapes.end(), sh) == shapes.end()) shapes.push_back(sh);
+    }
+    size_t missing = 0, ovl_missing = 0;
+    for (int m : q.ms) missing += c->fused && c->chain_tasks.find(m) == c->chain_tasks.end();
+    for (const auto& sh : shapes)
+        ovl_missing += plan_call(c, sh.first, sh.second, true, true).overlap && c->ovl_tables.find(sh) == c->ovl_tables.end();
+    c->task_cap = std::max(c->task_cap, c->chain_tasks.size() + missing);
+    c->ovl_cap = std::max(c->ovl_cap, c->ovl_tables.size() + ovl_missing + 1);
+    if ((rc = ensure_tasks(c, q.ms.data(), (int)q.ms.size()))) return rc;
+    for (const auto& sh : shapes)
+        if ((rc = ensure_ovl(c, plan_call(c, sh.first, sh.second, true, true), sh.first, sh.second))) return rc;
+    if ((rc = ensure_long_carry(c, R))) return rc;
+    // the lengths go up once, in front of the first segment (the block's task tables stay empty: the segments find theirs in the cache)
+    Part lp = make_part(c, 0, R, 1, s);
+    if ((rc = ragged_upload(c, lens_host, R, 0, s, lp))) return rc;
+    const int64_t* d_lens = lp.lens;
+
+    bsrnn_ctx::LongForm& lf = c->lf;
+    HIP_TRY(hipMemsetAsync(lf.state[0], 0, state_floats(R, K) * sizeof(float), s));       // every clip starts from zero state (and needs no carry)
+    int p = 0;
+    for (int i = 0; i < q.nseg; ++i) {
+        const int ta = i * seg, te = std::min(T, ta + seg), Ri = q.rows[i];
+        float* out = wave_out + (size_t)std::max(ta - 1, 0) * HOPS;
+        auto run = [&]() -> int {
+            { StageScope sc(c, ST_STFT, s); launch_stft_ragged_segment(c->tb, wave, wave_stride, d_lens, c->Xf, Ri, ta, te, s); }
+            if (int rc2 = run_model(c, c->Xf, c->Yf, nullptr, Ri, te - ta, lf.state[p], lf.state[p ^ 1], s)) return rc2;
+            {
+                StageScope sc(c, ST_ISTFT, s);
+                launch_istft_ragged_segment(c->tb, c->Yf, out, out_stride, d_lens, ta ? lf.carry[p] : nullptr, lf.carry[p ^ 1], R, Ri, ta, te, s);
+            }
+            HIP_TRY(hipGetLastError());
+            return 0;
+        };
+        if ((rc = run())) return rc;
+        g_dbg[DBG_LONG_RAGGED_ROWS] += (long long)Ri * (te - ta);
+        // range policy per segment, as in long_segments: the re-run starts from this segment's untouched state and carry set
+        if ((rc = finish_call(c, s, run))) return rc;
+        if (i + 1 < q.nseg && q.rows[i + 1] < Ri) {
+            launch_long_compact(lf.state[p ^ 1], lf.state[p], lf.carry[p ^ 1], lf.carry[p], Ri, q.rows[i + 1], K, s);
+            HIP_TRY(hipGetLastError());
+        } else p ^= 1;
+    }
+    return 0;
 }
 
 int64_t bsrnn_workspace_rows(const bsrnn_ctx* c) { return c ? (int64_t)c->cap_rows : 0; }

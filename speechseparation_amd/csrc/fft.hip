@@ -9,6 +9,7 @@
 #include "kernels.h"
 #include <type_traits>
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace bsrnn {
@@ -995,6 +996,115 @@ void launch_istft_ragged(const FftTables& tb, const float* Y, float* out, int64_
     if (Tmax < 2) return;
     const Chunks ch = chunks_for<istft_ragged_kernel>(Tmax - 1, R, 1);
     hipLaunchKernelGGL(istft_ragged_kernel, ch.grid, dim3(256), 0, s, tb, Y, out, out_stride, lens, Tmax, ch.len);
+}
+
+// ------------------------------------------------------------------------------ offline DSP, one segment of rows of different lengths
+// The two pairs above put together for frames [ta, te) of a ragged batch (bsrnn_separate_long_ragged): a segment's bounds AND a row's own.
+// Both kernels run the shared walks, so a frame or a hop that one of the other pairs computes too has the same bits; row and chunk belong
+// to the workgroup, so every condition below is workgroup-uniform, and each walk is one loop over the real frames / hops (no branch inside
+// it) and one over the padded ones.
+//
+// Analysis, on the Ri rows of the segment's alive prefix: frames t in [ta, min(te, T_r)) of row r come from wave + r * stride, reflected at
+// 0 and at lens[r] - 1 (never at a segment edge or at the stride: nothing at or behind lens[r] is read); frames [T_r, te) are written as
+// zeros in ALL ld columns.  Rows of X are segment-local: X[(r * (te - ta) + (t - ta)) * ld].
+__global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_ragged_segment_kernel(FftTables tb, const float* __restrict__ wave, float* __restrict__ X,
+                                                                                int64_t stride, const int64_t* __restrict__ lens, int ta, int te, int sch)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const int r = blockIdx.y;
+    const int64_t n = lens[r];
+    const int Tr = 1 + (int)(n / HOPS);
+    const int t0 = ta + blockIdx.x * sch;
+    const int tc = (t0 + sch < te) ? t0 + sch : te;                   // the chunk: frames [t0, tc) of the segment
+    const int t1 = tc < Tr ? tc : Tr;                                 // its real frames: [t0, t1), none when t1 <= t0
+    float* Xr = X + (size_t)r * (te - ta) * tb.ld;
+    if (t0 < t1) {
+        const float* src = wave + (size_t)r * stride;
+        auto sample2 = [&](int t, int c) { return reflected_sample2(src, n, 0, t, c); };
+        auto row = [&](int t) { return Xr + (size_t)(t - ta) * tb.ld; };
+        stft_walk(tb, z0, z1, tid, t0, t1, sample2, row);
+    }
+    // the padded frames of the chunk (rows of X start 16-byte aligned and ld is a multiple of 4: commit_host.h, band_columns)
+    for (int t = t0 > t1 ? t0 : t1; t < tc; ++t) zero_floats4(Xr + (size_t)(t - ta) * tb.ld, tb.ld / 4, tid);
+}
+
+// Synthesis, on ALL R rows of the call (every output sample of the segment's hops is written): Y = the spectra of the segment's L = te - ta
+// frames of the Ri rows of the prefix, `out` points at the segment's first hop of row 0, carry_in / carry_out as istft_segment_kernel's
+// (carry_in == null: the clip's first segment).  Local frame a = t - ta completes clip hop t - 1, which is real when t < T_r: those are
+// computed as istft_segment_kernel computes them (the segment's first from carry_in[r]), every other hop of the segment is STORED as zeros.
+// A workgroup with no real hop - a row at or beyond Ri, a chunk past the row's end - does no FFT and reads no row of Y.  The workgroup
+// whose chunk ends the segment leaves carry_out[r]: the windowed second half of frame te - 1 when the row has a frame te to add it to,
+// else zeros (nothing reads them; the buffer never holds stale values).
+__global__ __launch_bounds__(256, FFT_OCC_ISTFT) void istft_ragged_segment_kernel(FftTables tb, const float* __restrict__ Y, float* __restrict__ out,
+                                                                                  int64_t out_stride, const int64_t* __restrict__ lens,
+                                                                                  const float* __restrict__ carry_in, float* __restrict__ carry_out,
+                                                                                  int ta, int te, int Ri, int ich)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const int r = blockIdx.y;
+    const int L = te - ta;
+    const int Tr = 1 + (int)(lens[r] / HOPS);
+    const int f0 = carry_in ? 0 : 1;                                  // the first frame that completes a hop (local hop = frame - f0)
+    const int a0 = f0 + blockIdx.x * ich;
+    const int ac = (a0 + ich < L) ? a0 + ich : L;                     // the chunk: local frames [a0, ac) (a one-frame first segment: a0 = ac = 1)
+    const int Lr = r < Ri ? (Tr - ta < L ? Tr - ta : L) : 0;          // the row's real frames of the segment: local [0, Lr), none when Lr <= 0
+    const int a1 = ac < Lr ? ac : Lr;                                 // the chunk's real frames: [a0, a1), none when a1 <= a0
+    const bool last = ac == L;                                        // this workgroup leaves the carry ...
+    const bool onward = last && Tr > te;                              // ... and the row goes on behind the segment (then Lr = L and a1 = ac)
+    float* o = out + (size_t)r * out_stride;
+    float2 carry[2] = {make_float2(0.f, 0.f), make_float2(0.f, 0.f)};
+    if (a0 < a1 || onward) {
+        const float* Yr = Y + (size_t)r * L * tb.ld;
+        auto spectrum = [&](int t) { return Yr + (size_t)t * tb.ld; };
+        auto hop = [&](int t) { return o + (size_t)(t - f0) * HOPS; };
+        if (a0 == 0) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) carry[k] = *reinterpret_cast<const float2*>(carry_in + (size_t)r * HOPS + 2 * (tid + 256 * k));
+        }
+        istft_walk(tb, z0, z1, tid, a0, a1, spectrum, hop, a0 > 0, carry);
+    }
+    // the padded hops of the chunk, at the addresses and with the 8-byte stores of the real ones
+    for (int a = a0 > a1 ? a0 : a1; a < ac; ++a) zero_hop(o + (size_t)(a - f0) * HOPS, tid);
+    if (last) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            *reinterpret_cast<float2*>(carry_out + (size_t)r * HOPS + 2 * (tid + 256 * k)) = onward ? carry[k] : make_float2(0.f, 0.f);
+    }
+}
+
+// When the alive prefix shrinks from Ro to Rn rows between two segments: the surviving rows' time-axis state - eight slabs, each a prefix of
+// n4 = Rn * K * 16 float4 at the old pitch of Ro * K * 16 - and their overlap-add tail (one prefix of c4 = Rn * 256 float4) move from the
+// carry set the finished segment wrote into the one it read, packed at the new pitch.
+__global__ __launch_bounds__(256) void long_compact_kernel(const float4* __restrict__ state_src, float4* __restrict__ state_dst, size_t pitch_src, size_t n4,
+                                                           const float4* __restrict__ carry_src, float4* __restrict__ carry_dst, size_t c4)
+{
+    const size_t step = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < 8 * n4 + c4; i += step) {
+        if (i < 8 * n4) { const size_t slab = i / n4; state_dst[i] = state_src[slab * pitch_src + (i - slab * n4)]; }
+        else carry_dst[i - 8 * n4] = carry_src[i - 8 * n4];
+    }
+}
+
+void launch_stft_ragged_segment(const FftTables& tb, const float* wave, int64_t stride, const int64_t* lens, float* X, int Ri, int ta, int te, hipStream_t s)
+{
+    const Chunks ch = chunks_for<stft_ragged_segment_kernel>(te - ta, Ri, 0);
+    hipLaunchKernelGGL(stft_ragged_segment_kernel, ch.grid, dim3(256), 0, s, tb, wave, X, stride, lens, ta, te, ch.len);
+}
+void launch_istft_ragged_segment(const FftTables& tb, const float* Y, float* out, int64_t out_stride, const int64_t* lens, const float* carry_in,
+                                 float* carry_out, int R, int Ri, int ta, int te, hipStream_t s)
+{
+    const int hops = te - ta - (carry_in ? 0 : 1);                     // 0: a one-frame first segment (one workgroup per row leaves the carry)
+    const Chunks ch = chunks_for<istft_ragged_segment_kernel>(hops > 0 ? hops : 1, R, 1);
+    hipLaunchKernelGGL(istft_ragged_segment_kernel, ch.grid, dim3(256), 0, s, tb, Y, out, out_stride, lens, carry_in, carry_out, ta, te, Ri, ch.len);
+}
+void launch_long_compact(const float* state_src, float* state_dst, const float* carry_src, float* carry_dst, int R_old, int R_new, int K, hipStream_t s)
+{
+    const size_t n4 = (size_t)R_new * K * (HID / 4), c4 = (size_t)R_new * (HOPS / 4), total = 8 * n4 + c4;
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 1024);
+    hipLaunchKernelGGL(long_compact_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<const float4*>(state_src), reinterpret_cast<float4*>(state_dst),
+                       (size_t)R_old * K * (HID / 4), n4, reinterpret_cast<const float4*>(carry_src), reinterpret_cast<float4*>(carry_dst), c4);
 }
 
 }  // namespace bsrnn

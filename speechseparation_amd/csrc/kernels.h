@@ -258,6 +258,15 @@ void launch_istft_segment(const FftTables& tb, const float* Y, float* out, int64
 // b >= T_r - 1 as zeros of out (rows out_stride floats apart, Tmax - 1 hops each)
 void launch_stft_ragged(const FftTables& tb, const float* wave, int64_t stride, const int64_t* lens, float* X, int R, int Tmax, hipStream_t s);
 void launch_istft_ragged(const FftTables& tb, const float* Y, float* out, int64_t out_stride, const int64_t* lens, int R, int Tmax, hipStream_t s);
+// Both at once (bsrnn_separate_long_ragged; fft.hip): frames [ta, te) of a ragged batch, segment-local rows X / Y [Ri*(te-ta)][ld] for the Ri
+// rows of the segment's alive prefix (plan_host.h, ragged_long_plan).  The analysis runs on those Ri rows (frames t >= T_r as zero rows); the
+// synthesis on all R rows of the call - out, carry_in, carry_out as launch_istft_segment's, hops that are not a row's own stored as zeros,
+// carry_out[r] zeros for a row without a frame te.  launch_long_compact: the state ([4][2][R_old*K][64] -> [4][2][R_new*K][64]) and the carry
+// of the first R_new rows from one carry set into the other when the prefix shrinks.
+void launch_stft_ragged_segment(const FftTables& tb, const float* wave, int64_t stride, const int64_t* lens, float* X, int Ri, int ta, int te, hipStream_t s);
+void launch_istft_ragged_segment(const FftTables& tb, const float* Y, float* out, int64_t out_stride, const int64_t* lens, const float* carry_in,
+                                 float* carry_out, int R, int Ri, int ta, int te, hipStream_t s);
+void launch_long_compact(const float* state_src, float* state_dst, const float* carry_src, float* carry_dst, int R_old, int R_new, int K, hipStream_t s);
 // gradient of launch_istft's output w.r.t. its input (training step): dwave [R][(T-1)*1024] -> dY frame-major [R*T][ld];
 // scratch [R][(T-1)*1024]
 void launch_istft_backward(const FftTables& tb, const float* dwave, float* scratch, float* dY, int R, int T, hipStream_t s);

@@ -242,6 +242,39 @@ inline RaggedShape ragged_shape(const int64_t* lens, int R, int64_t stride)
 // Frame rows R * Tmax one ragged call may run on (the frame-row index and twice it stay ints)
 inline bool ragged_too_many(int64_t R, int64_t Tmax) { return R > INT32_MAX / 2 || (R > 0 && Tmax > (INT32_MAX / 2) / R); }
 
+// --------------------------------------------------------------------------- ragged long-form: rows of different lengths in segments (bsrnn_separate_long_ragged)
+// The rectangle R x Tmax of a ragged batch cut into segments of `seg` frames: segment i covers frames [ta, te) = [i * seg, min(Tmax, (i + 1) * seg))
+// and runs on the ALIVE PREFIX of the rows, rows[i] = 1 + max{ r : T_r > ta } - rows are never reordered, so a row inside the prefix that
+// has already ended is carried as zero frames (any order is correct, longest first is the cheap one).  rows[i] never increases with i, and
+// rows[0] = R (every row has two frames).  ms: the distinct frame-row counts rows[i] * (te - ta), in order of first use (what the task tables
+// are keyed by); frame_rows: their sum over the segments, the model work of the call.  shape: ragged_shape's answer, refusals included
+// (nothing else is filled then); too_many: R * min(seg, Tmax) is beyond what one segment takes (long_prepare's limit).
+struct RaggedLongPlan { RaggedShape shape; bool too_many; int nseg; std::vector<int> rows, ms; int64_t frame_rows; };
+inline RaggedLongPlan ragged_long_plan(const int64_t* lens, int R, int64_t stride, int seg)
+{
+    RaggedLongPlan q;
+    q.shape = ragged_shape(lens, R, stride);
+    q.too_many = false; q.nseg = 0; q.frame_rows = 0;
+    if (q.shape.why != RAGGED_OK || R < 1 || seg < 1) return q;
+    const int64_t Tmax = q.shape.Tmax;
+    if ((int64_t)R * std::min<int64_t>(seg, Tmax) > INT32_MAX / 2) { q.too_many = true; return q; }
+    // most[r] = the largest T of rows r .. R - 1: row r is inside the prefix of a segment that starts at ta exactly when most[r] > ta
+    std::vector<int64_t> most((size_t)R);
+    for (int r = R - 1; r >= 0; --r) most[r] = std::max(ragged_frames(lens[r]), r + 1 < R ? most[r + 1] : 0);
+    q.nseg = (int)((Tmax + seg - 1) / seg);
+    q.rows.reserve((size_t)q.nseg);
+    int alive = R;
+    for (int i = 0; i < q.nseg; ++i) {
+        const int64_t ta = (int64_t)i * seg, te = std::min<int64_t>(Tmax, ta + seg);
+        while (alive > 1 && most[alive - 1] <= ta) --alive;
+        const int m = alive * (int)(te - ta);
+        q.rows.push_back(alive);
+        q.frame_rows += m;
+        if (std::find(q.ms.begin(), q.ms.end(), m) == q.ms.end()) q.ms.push_back(m);
+    }
+    return q;
+}
+
 // --------------------------------------------------------------------------- ragged evaluate: clips of different lengths (bsrnn_evaluate_ragged)
 // The unit of the validation metrics is a CLIP: clip c owns rows[c] >= 1 consecutive rows (rows == nullptr: one each) of lens[c] samples each,
 // 1024 < lens[c] <= stride.  The call runs bsrnn_separate_ragged on the R = sum rows[c] rows, whose per-row lengths are the per-clip ones

@@ -166,3 +166,49 @@ def ragged_buckets(frames, rows, max_rows, max_padding):
     if cur:
         buckets.append(cur)
     return buckets
+
+
+def long_plan(frames, seg):
+    """The segments of `BSRNN.separate_long_ragged` for rows of frames[r] frames each, in the given order, cut into segments of `seg`
+    frames (a mirror of csrc/plan_host.h, ragged_long_plan).  Segment i covers frames [i * seg, min(Tmax, (i + 1) * seg)) and runs the
+    model on the alive prefix of the rows, 1 + the last row r with frames[r] > i * seg: rows are never reordered, so a row inside the
+    prefix that has already ended is carried as zero frames.  Returns (rows, frame_rows): the prefix of every segment (it never
+    increases) and the sum of prefix x frames over the segments, the model work of the call - against len(frames) * Tmax for the
+    rectangle.  Longest first makes it smallest."""
+    frames, seg = [int(f) for f in frames], int(seg)
+    if not frames or any(f < 1 for f in frames) or seg < 1:
+        raise ValueError("long_plan: need at least one row, frame counts >= 1 and seg >= 1, got %r and %r" % (frames, seg))
+    t_max = max(frames)
+    rows, frame_rows = [], 0
+    for ta in range(0, t_max, seg):
+        alive = 1 + max(r for r, f in enumerate(frames) if f > ta)
+        rows.append(alive)
+        frame_rows += alive * (min(t_max, ta + seg) - ta)
+    return rows, frame_rows
+
+
+def long_buckets(frames, rows, max_rows):
+    """Group clips of different lengths into batches for `BSRNN.separate_long_ragged`, whose segments bound the padding: there is no
+    padding cap, only the row cap.  frames[i] / rows[i]: frame count and channel count of clip i.  Clips are sorted by frame count,
+    longest first (ties by index), and fill the buckets in that order to at most `max_rows` rows; a clip that alone has more rows gets a
+    bucket of its own.  Returns a list of buckets, each a list of clip indices, longest first inside and across buckets.  Deterministic."""
+    frames, rows = [int(f) for f in frames], [int(r) for r in rows]
+    if len(frames) != len(rows):
+        raise ValueError("long_buckets: %d frame counts for %d row counts" % (len(frames), len(rows)))
+    if any(f < 1 for f in frames) or any(r < 1 for r in rows):
+        raise ValueError("long_buckets: frame and row counts must be at least 1")
+    if max_rows < 1:
+        raise ValueError("long_buckets: need max_rows >= 1, got %r" % (max_rows,))
+    buckets = []
+    cur, n_rows = [], 0
+    for i in sorted(range(len(frames)), key=lambda j: (-frames[j], j)):
+        if cur and n_rows + rows[i] <= max_rows:
+            cur.append(i)
+            n_rows += rows[i]
+            continue
+        if cur:
+            buckets.append(cur)
+        cur, n_rows = [i], rows[i]
+    if cur:
+        buckets.append(cur)
+    return buckets
