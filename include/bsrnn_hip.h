@@ -468,6 +468,50 @@ int64_t bsrnn_stream_row_floats(const bsrnn_stream* s);
 int     bsrnn_stream_get_row(bsrnn_stream* s, int32_t row, float* blob_host);
 int     bsrnn_stream_set_row(bsrnn_stream* s, int32_t row, const float* blob_host);
 
+/* ---- sample-rate conversion on the device ------------------------------------------------
+ * The model is trained on 44.1 kHz audio; these calls bring audio of another rate to it and back without leaving the device.  They replace
+ * the host-side resampling in front of the reference's loops: `torchaudio.functional.resample` at infer-streaming.py:77-78 / the
+ * `sample_rate=44100` its StreamReader asks ffmpeg for, and what a caller of infer.py has to do to a 48 kHz file beforehand.
+ * DEFINITION: exactly scipy.signal.resample_poly(x, up, down) with its defaults (zero phase, zeros outside the clip), the project's own
+ * host behaviour until now (speechseparation_amd/audio.py:resample).  g = gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g,
+ * M = max(up, down), half = 10 * M, taps h = firwin(2 * half + 1, 1 / M, window = ('kaiser', 5.0)) * up designed in double and rounded to
+ * fp32 once, n_out = ceil(n_in * up / down), y[j] = sum_i x[i] * h[j * down - i * up + half] over the i inside the clip and the filter;
+ * fp32 accumulation.  Parity with ffmpeg's (or torchaudio's) resampler is NOT pinned: their filters differ from scipy's.
+ * Limits (BSRNN_EARG, the text names the value; answered before anything touches a device, also on a host-only context in front of its
+ * BSRNN_ESTATE): a rate < 1; a reduced max(up, down) > 1024 (44.1 kHz to and from 8 / 11.025 / 12 / 16 / 22.05 / 24 / 32 / 48 / 88.2 / 96 /
+ * 176.4 / 192 kHz all fit: 441 or 640 at most); n_in < 1.
+ * bsrnn_resample_len: n_out for n_in samples, or -1 for arguments bsrnn_resample would refuse.  Needs no context.
+ * bsrnn_resample: in_dev holds R rows in_stride floats apart with n_in samples each (nothing behind them in a row is read) -> out_dev, R rows
+ *     out_stride floats apart, n_out samples each (nothing behind them in a row is written): the strides fit the padded buffers of the
+ *     ragged calls.  Enqueues and returns.  Equal rates make the call a copy.  out_dev (its (R - 1) * out_stride + n_out floats) must not
+ *     overlap the (R - 1) * in_stride + n_in floats that the rows of in_dev span - first sample of the first row to last sample of the last,
+ *     the padding between rows included, the padding behind the last row not: it may belong to another allocation - and a stride must hold
+ *     its row (BSRNN_EARG).  The polyphase table of a rate pair is built and uploaded when the context first meets the
+ *     pair (bsrnn_debug_counter(0)); it needs no committed weights.  Counts as a call on the context (concurrency contract above).
+ * A bsrnn_resampler converts a stream block by block.  It holds, on the device and per row, the input samples that later outputs still
+ *     need (at most 2 * half / up + down / up + 2 floats); its two sample counters live on the host.
+ *   bsrnn_resampler_create does all first-use work (table, carry, kernel loading); _process, _flush and _reset allocate nothing
+ *     (bsrnn_debug_counter(0) unchanged).  Lifetime against bsrnn_destroy as a bsrnn_stream's: the context is released with the last object.
+ *   bsrnn_resampler_process: in_dev [C rows, in_stride apart, n_in samples], any n_in >= 0 -> writes to out_dev [C rows, out_stride apart]
+ *     exactly the outputs that have become determined - those whose last input has arrived - and reports their count per row in
+ *     *n_out_host without synchronising (the count is host arithmetic: bsrnn_resampler_ready(r, n_in) gives it beforehand, -1 for a
+ *     null object or n_in < 0).  out_dev must not overlap in_dev and out_stride must hold the count (BSRNN_EARG).
+ *   bsrnn_resampler_flush: writes the rest, up to ceil(N * up / down) for the N samples taken, the future counting as zeros, and leaves the
+ *     object reset.  bsrnn_resampler_reset: forget the stream so far (host only; nothing is enqueued).
+ *   The concatenated outputs of any sequence of _process calls and one _flush EQUAL bsrnn_resample of the concatenated input, value for
+ *     value: one kernel forms an output sample from the same taps in the same order wherever its inputs lie. */
+typedef struct bsrnn_resampler bsrnn_resampler;
+int64_t bsrnn_resample_len(int64_t n_in, int32_t rate_in, int32_t rate_out);
+int     bsrnn_resample(bsrnn_ctx* ctx, const float* in_dev, int64_t in_stride, float* out_dev, int64_t out_stride,
+                       int32_t R, int64_t n_in, int32_t rate_in, int32_t rate_out, void* stream);
+int     bsrnn_resampler_create(bsrnn_ctx* ctx, int32_t C, int32_t rate_in, int32_t rate_out, bsrnn_resampler** out);
+void    bsrnn_resampler_destroy(bsrnn_resampler* r);
+int     bsrnn_resampler_reset(bsrnn_resampler* r, void* stream);
+int64_t bsrnn_resampler_ready(const bsrnn_resampler* r, int64_t n_in);
+int     bsrnn_resampler_process(bsrnn_resampler* r, const float* in_dev, int64_t in_stride, int64_t n_in,
+                                float* out_dev, int64_t out_stride, int64_t* n_out_host, void* stream);
+int     bsrnn_resampler_flush(bsrnn_resampler* r, float* out_dev, int64_t out_stride, int64_t* n_out_host, void* stream);
+
 /* ---- measurement support ---------------------------------------------------------------
  * bsrnn_set_profiling(ctx, mask): bit i of `mask` brackets stage i of every compute call with
  * hipEvents on the call's stream (mask < 0 = all stages, 0 = off; each bracket costs ~10 us of

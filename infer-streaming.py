@@ -3,7 +3,8 @@
 infer-streaming.py (--input/--output/--name), with the whole per-chunk loop
 (infer-streaming.py:104-147: slide buffer, rfft, forward_recurrent, irfft, 2-slot overlap-add)
 resident on the MI355X: one `StreamingSeparator.step` per 1024-sample chunk at 44.1 kHz, or with
-`--block N` one `StreamingSeparator.process` per N chunks (same output to rounding, far fewer launches).
+`--block N` one `StreamingSeparator.process` per N chunks (same output to rounding, far fewer launches).  A file at another rate is brought to
+44.1 kHz on the host (`audio.resample`, the default) or, with `--device-resample`, on the device through a `Resampler`.
 
 The reference also dumps the traced model for its LADSPA plugin (hello.onnx, :74); the
 counterpart here is the flat weight file `hello.bsrnnw` that speech_separator_ladspa.so loads
@@ -16,7 +17,7 @@ import time
 import torch
 
 from speechseparation_amd import audio
-from speechseparation_amd.bsrnn import BSRNN, StreamingSeparator
+from speechseparation_amd.bsrnn import BSRNN, Resampler, StreamingSeparator
 
 STREAM_RATE = 44100      # infer-streaming.py:78
 CHUNK = 1024
@@ -34,6 +35,8 @@ def main(argv=None):
     ap.add_argument("--block", type=int, default=1, metavar="N",
                     help="hops per library call: 1 = one step per 1024-sample chunk (the reference's loop), N > 1 = N hops per "
                          "StreamingSeparator.process call")
+    ap.add_argument("--device-resample", action="store_true",
+                    help="convert a file at another rate to 44.1 kHz on the device (Resampler) instead of on the host (audio.resample)")
     args = ap.parse_args(argv)
 
     torch.set_grad_enabled(False)
@@ -47,10 +50,16 @@ def main(argv=None):
         print("Flat weight file dumped")
 
     waveform, sr = audio.load_wav(args.input)
-    waveform = audio.resample(waveform, sr, STREAM_RATE)
+    if not args.device_resample:
+        waveform = audio.resample(waveform, sr, STREAM_RATE)
     if waveform.shape[0] == 1:
         waveform = torch.cat((waveform, waveform), 0)
     waveform = waveform[:2].to(args.device)
+    if args.device_resample and sr != STREAM_RATE:
+        # the file as one block through the streaming resampler, then what the block's end still owes
+        with torch.cuda.device(args.device):
+            rs = Resampler(model, 2, sr, STREAM_RATE)
+            waveform = torch.cat((rs.process(waveform.contiguous()), rs.flush()), 1)
 
     sep = StreamingSeparator(model, channels=2, device=args.device)
     n_chunks = waveform.shape[1] // CHUNK                 # a short tail chunk ends the stream (:108)

@@ -9,7 +9,9 @@ Here STFT -> forward -> iSTFT is one fused device call (`BSRNN.separate`), numer
 sandwich.  Extra flags: --weights (checkpoint or flat file), --synthetic-weights SEED (no
 trained weights ship with the reference), --device, --outdir for the re-mix files, --segment-frames N
 (long files: the waveform stays on the host and is separated N frames at a time in bounded device
-memory, `BSRNN.separate_long`; everything after the separation is unchanged).
+memory, `BSRNN.separate_long`; everything after the separation is unchanged), --model-rate HZ (a file at another rate is
+converted to HZ on the device, separated and converted back, `BSRNN.separate_at_rate`; off by default: the reference runs
+the model at whatever rate the file has).
 """
 import argparse
 import os
@@ -34,6 +36,9 @@ def main(argv=None):
     ap.add_argument("--outdir", type=str, default=".")
     ap.add_argument("--segment-frames", type=int, default=None, metavar="N",
                     help="separate N STFT frames at a time (bounded device memory, for long files); default: the whole file in one call")
+    ap.add_argument("--model-rate", type=int, default=0, metavar="HZ",
+                    help="the rate the model was trained at (44100): a file at another rate is resampled to it on the device, separated "
+                         "and resampled back; default 0: run the model at the file's rate, as the reference does")
     args = ap.parse_args(argv)
 
     torch.set_grad_enabled(False)
@@ -46,7 +51,9 @@ def main(argv=None):
         waveform = torch.cat((waveform, waveform), 0)
     orig_peak = waveform.max().item()
 
-    if args.segment_frames is None:
+    if args.model_rate and args.model_rate != sr:
+        dialog = model.separate_at_rate(waveform.to(args.device), sr, args.model_rate, args.segment_frames).cpu()
+    elif args.segment_frames is None:
         dialog = model.separate(waveform.to(args.device)).cpu()
     else:
         with torch.cuda.device(args.device):

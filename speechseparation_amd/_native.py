@@ -27,6 +27,8 @@ SYMBOLS = [
     "bsrnn_stream_process", "bsrnn_stream_reserve", "bsrnn_separate_long", "bsrnn_separate_long_host", "bsrnn_workspace_rows",
     "bsrnn_separate_ragged", "bsrnn_evaluate_ragged", "bsrnn_separate_long_ragged",
     "bsrnn_stream_process_rows", "bsrnn_stream_reset_rows", "bsrnn_stream_row_floats", "bsrnn_stream_get_row", "bsrnn_stream_set_row",
+    "bsrnn_resample_len", "bsrnn_resample", "bsrnn_resampler_create", "bsrnn_resampler_destroy", "bsrnn_resampler_reset",
+    "bsrnn_resampler_ready", "bsrnn_resampler_process", "bsrnn_resampler_flush",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
@@ -106,6 +108,14 @@ def _load():
         "bsrnn_stream_row_floats": (i64, [vp]),
         "bsrnn_stream_get_row": (C.c_int, [vp, i32, vp]),
         "bsrnn_stream_set_row": (C.c_int, [vp, i32, vp]),
+        "bsrnn_resample_len": (i64, [i64, i32, i32]),
+        "bsrnn_resample": (C.c_int, [vp, vp, i64, vp, i64, i32, i64, i32, i32, vp]),
+        "bsrnn_resampler_create": (C.c_int, [vp, i32, i32, i32, C.POINTER(vp)]),
+        "bsrnn_resampler_destroy": (None, [vp]),
+        "bsrnn_resampler_reset": (C.c_int, [vp, vp]),
+        "bsrnn_resampler_ready": (i64, [vp, i64]),
+        "bsrnn_resampler_process": (C.c_int, [vp, vp, i64, i64, vp, i64, C.POINTER(i64), vp]),
+        "bsrnn_resampler_flush": (C.c_int, [vp, vp, i64, C.POINTER(i64), vp]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),
         "bsrnn_stage_name": (C.c_char_p, [i32]),

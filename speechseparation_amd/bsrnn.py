@@ -502,6 +502,70 @@ class BSRNN(nn.Module):
                 r0 += ch
         return results
 
+    # ------------------------------------------------------------------ sample-rate conversion on the device
+    @staticmethod
+    def _rows_view(t):
+        """(tensor, row stride) of a 2-D float32 cuda tensor for a call that takes rows `stride` floats apart.  The tensor's own stride(0)
+        is passed on only where it describes such rows: samples contiguous and rows at least a row's length apart (buf[:, a:b], buf[::2]).
+        Every other view is copied: strided samples, and rows that overlap or coincide (mono.expand(2, -1) has stride(0) = 0; unfold and
+        as_strided give 0 < stride(0) < n) - the library refuses a stride below the row length."""
+        R, n = t.shape
+        if (n > 1 and t.stride(1) != 1) or (R > 1 and t.stride(0) < n):
+            t = t.contiguous()
+        return t, (t.stride(0) if R > 1 else n)
+
+    def resample(self, wave, rate_in, rate_out, out=None):
+        """wave [R, n] float32 on a HIP device -> [R, n_out] at rate_out, n_out = ceil(n * up / down): exactly
+        scipy.signal.resample_poly(wave, up, down, axis=1) evaluated in fp32 on the device (include/bsrnn_hip.h, bsrnn_resample).  Rows may
+        be a view into a wider buffer (wave = buf[:, a:b]): the row stride is passed on and nothing behind a row's n samples is read.  Any
+        other view (strided samples, expanded or overlapping rows such as mono.expand(2, -1)) is copied first.  `out`, if given, is a
+        float32 tensor [R, n_out] on the same device with contiguous rows at least n_out apart (it may be a view into a wider buffer too);
+        it must not overlap the span of the input, first sample of the first row to last sample of the last."""
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[1] < 1 or wave.shape[0] < 1:
+            raise ValueError("resample: expected wave [R, n] with n >= 1, got %s" % (
+                tuple(wave.shape) if isinstance(wave, torch.Tensor) else type(wave).__name__,))
+        if wave.dtype != torch.float32:
+            raise ValueError("resample: expected a float32 tensor, got %s" % wave.dtype)
+        R, n = wave.shape
+        n_out = resample_len(n, rate_in, rate_out)
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != wave.device
+                                or tuple(out.shape) != (R, n_out) or (out.stride(1) != 1 and n_out > 1)
+                                or (R > 1 and out.stride(0) < n_out)):
+            raise ValueError("resample: out must be a float32 tensor %s with contiguous rows that do not overlap on %s, got %s" % (
+                (R, n_out), wave.device, "%s %s with strides %s on %s" % (tuple(out.shape), out.dtype, tuple(out.stride()), out.device)
+                if isinstance(out, torch.Tensor) else type(out).__name__))
+        if not wave.is_cuda:
+            raise _native.NativeError("resample: the waveform must be on a HIP device (audio.resample is the host utility)")
+        dev = wave.device
+        w, w_stride = self._rows_view(wave.detach())
+        with torch.cuda.device(dev):
+            ctx = self._context(dev)
+            if out is None:
+                out = torch.empty((R, n_out), device=dev, dtype=torch.float32)
+            o_stride = out.stride(0) if R > 1 else n_out
+            _check(_lib.bsrnn_resample(ctx, _ptr(w), w_stride, _ptr(out), o_stride, R, n, int(rate_in), int(rate_out), _stream_ptr(dev)))
+        return out
+
+    def separate_at_rate(self, wave, sample_rate, model_rate=44100, segment_frames=None):
+        """`separate` for audio at another rate than the model's: wave [R, n] float32 on a HIP device at sample_rate -> resample to
+        model_rate, `separate` (`separate_long` with segment_frames, if given), resample back - the three public calls chained, all on
+        the device - cut to at most n samples (the model returns whole hops, so the result is usually a little shorter than the
+        input).  sample_rate == model_rate IS `separate`."""
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2:
+            raise ValueError("separate_at_rate: expected wave [R, n], got %s" % (
+                tuple(wave.shape) if isinstance(wave, torch.Tensor) else type(wave).__name__,))
+        if int(sample_rate) < 1 or int(model_rate) < 1:
+            raise ValueError("separate_at_rate: rates must be at least 1, got %s and %s" % (sample_rate, model_rate))
+        if segment_frames is not None and int(segment_frames) < 1:
+            raise ValueError("separate_at_rate: segment_frames must be at least 1, got %s" % (segment_frames,))
+
+        def run(w):
+            return self.separate(w) if segment_frames is None else self.separate_long(w, int(segment_frames))
+        if int(sample_rate) == int(model_rate):
+            return run(wave)
+        y = self.resample(run(self.resample(wave, sample_rate, model_rate)), model_rate, sample_rate)
+        return y[:, :min(wave.shape[1], y.shape[1])]
+
     def workspace_rows(self, device=None):
         """Frame rows the native context's workspace holds right now (grow-only; 0 before the first call): what `separate` raises to
         R * T and `separate_long` keeps at R * segment_frames (bsrnn_workspace_rows).  `device`: only the context on that device counts."""
@@ -811,6 +875,78 @@ class StreamingSeparator:
                 self.row_floats(), tuple(blob.shape) if isinstance(blob, torch.Tensor) else type(blob).__name__))
         b = np.ascontiguousarray(blob.detach().to("cpu", torch.float32).numpy())
         _check(_lib.bsrnn_stream_set_row(self._h, row, b.ctypes.data_as(ctypes.c_void_p)))
+
+
+def resample_len(n_in, rate_in, rate_out):
+    """Samples bsrnn_resample gives for n_in: ceil(n_in * up / down).  ValueError for what the library refuses (a rate < 1, a reduced
+    max(up, down) beyond 1024, n_in < 1)."""
+    n = _lib.bsrnn_resample_len(int(n_in), int(rate_in), int(rate_out))
+    if n < 0:
+        raise ValueError("resample: cannot convert %s samples from %s to %s Hz (rates >= 1, reduced max(up, down) <= 1024, n >= 1)" % (
+            n_in, rate_in, rate_out))
+    return n
+
+
+class Resampler:
+    """Streaming sample-rate conversion on the device (bsrnn_resampler_*): feed blocks of any length, get the output samples that have
+    become determined; flush() gives the rest.  The concatenation equals model.resample() of the concatenated input, value for value.
+    Replaces the host-side audio.resample in front of a streaming loop (infer-streaming.py --device-resample)."""
+
+    def __init__(self, model, channels, rate_in, rate_out):
+        resample_len(1, rate_in, rate_out)          # (the limits, as a ValueError)
+        self.model = model
+        self.C = int(channels)
+        self.rate_in, self.rate_out = int(rate_in), int(rate_out)
+        self.device = torch.device("cuda", model._ctx_device if model._ctx_device is not None else torch.cuda.current_device())
+        with torch.cuda.device(self.device):
+            ctx = model._context(self.device)
+            h = ctypes.c_void_p()
+            _check(_lib.bsrnn_resampler_create(ctx, self.C, self.rate_in, self.rate_out, ctypes.byref(h)))
+        self._h = h
+        self._taken = self._given = 0       # the library's two counters, mirrored to size flush()'s result before the call
+
+    def __del__(self):
+        try:
+            _lib.bsrnn_resampler_destroy(self._h)
+        except Exception:
+            pass
+
+    def ready(self, n_in):
+        """Samples per row the next process() of n_in samples would return."""
+        return int(_lib.bsrnn_resampler_ready(self._h, int(n_in)))
+
+    def process(self, wave):
+        """wave [C, n] float32 on the resampler's device, any n >= 0 -> [C, ready(n)]."""
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != self.C:
+            raise ValueError("Resampler.process: expected wave [C = %d, n], got %s" % (
+                self.C, tuple(wave.shape) if isinstance(wave, torch.Tensor) else type(wave).__name__))
+        if wave.dtype != torch.float32 or wave.device != self.device:
+            raise ValueError("Resampler.process: expected a float32 tensor on %s, got %s on %s" % (self.device, wave.dtype, wave.device))
+        n = ctypes.c_int64(-1)
+        w, w_stride = BSRNN._rows_view(wave.detach())
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.C, self.ready(w.shape[1])), device=self.device, dtype=torch.float32)
+            _check(_lib.bsrnn_resampler_process(self._h, _ptr(w), w_stride, w.shape[1], _ptr(out), out.shape[1], ctypes.byref(n),
+                                                _stream_ptr(self.device)))
+        assert n.value == out.shape[1], (n.value, tuple(out.shape))
+        self._taken += w.shape[1]
+        self._given += out.shape[1]
+        return out
+
+    def flush(self):
+        """The samples still owed for the input so far (the future counting as zeros); the resampler starts afresh."""
+        owed = (resample_len(self._taken, self.rate_in, self.rate_out) if self._taken else 0) - self._given
+        n = ctypes.c_int64(-1)
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.C, owed), device=self.device, dtype=torch.float32)
+            _check(_lib.bsrnn_resampler_flush(self._h, _ptr(out), owed, ctypes.byref(n), _stream_ptr(self.device)))
+        assert n.value == owed, (n.value, owed)
+        self._taken = self._given = 0
+        return out
+
+    def reset(self):
+        _check(_lib.bsrnn_resampler_reset(self._h, _stream_ptr(self.device)))
+        self._taken = self._given = 0
 
 
 class StreamPool:

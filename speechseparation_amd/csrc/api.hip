@@ -7,6 +7,7 @@
 #include "commit_host.h"
 #include "plan_host.h"
 #include "metrics_host.h"
+#include "resample_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -212,6 +213,11 @@ struct bsrnn_ctx {
         double *d_part = nullptr, *h_part = nullptr;
         float* d_est = nullptr;
     } er;
+
+    // Sample-rate conversion (bsrnn_resample, bsrnn_resampler_*): the polyphase table of each reduced (up, down) this context has met, designed
+    // on the host and uploaded at first use (bsrnn_debug_counter(0)); grow-only, a handful of entries of at most 100 KB, freed with the context.
+    struct ResampleTable { ResampleRatio q; ResampleTiling g; float* d; };
+    std::vector<ResampleTable> rs_tables;
 };
 
 struct bsrnn_stream {
@@ -972,6 +978,7 @@ static void destroy_now(bsrnn_ctx* c)
     if (c->er.d_part) (void)hipFree(c->er.d_part);
     if (c->er.h_part) (void)hipHostFree(c->er.h_part);
     if (c->er.d_est) (void)hipFree(c->er.d_est);
+    for (auto& t : c->rs_tables) (void)hipFree(t.d);
     for (hipEvent_t e : c->er.ev)
         if (e) (void)hipEventDestroy(e);
     if (c->ev_ovl_fork) (void)hipEventDestroy(c->ev_ovl_fork);
@@ -2635,6 +2642,230 @@ int bsrnn_stream_set_row(bsrnn_stream* st, int32_t row, const float* blob_host)
     if (!st || !blob_host) return fail(BSRNN_EARG, "bsrnn_stream_set_row: null argument");
     if (row < 0 || row >= st->C) return fail(BSRNN_EARG, "bsrnn_stream_set_row: row %d is outside [0, %d)", row, st->C);
     return stream_move_row(st, row, const_cast<float*>(blob_host), false);
+}
+
+// --------------------------------------------------------------------------- sample-rate conversion
+// The definition and all index arithmetic: resample_host.h; the kernel: resample.hip.  One launch per call, for the one-shot form and
+// for the streaming object alike.
+struct bsrnn_resampler {
+    bsrnn_ctx* ctx;
+    int C;
+    ResampleRatio q;
+    ResampleTiling g;
+    const float* tab;              // the context's table of (up, down)
+    // The inputs that outputs not yet determined still need, per row: two buffers of cap floats per row, a call reads set `cur` and
+    // writes the other (the launch that reads the carry also writes the next one).  N inputs taken and J outputs given so far; the
+    // carry holds inputs [max(0, resample_base(J)), N).
+    float* carry[2];
+    int64_t cap;
+    int cur;
+    int64_t N, J;
+};
+
+static int resample_check_rates(int32_t rate_in, int32_t rate_out, const char* who, ResampleRatio& q)
+{
+    q = resample_ratio(rate_in, rate_out);
+    if (q.why == RESAMPLE_BAD_RATE)
+        return fail(BSRNN_EARG, "%s: rates must be at least 1, got rate_in = %d, rate_out = %d", who, rate_in, rate_out);
+    if (q.why == RESAMPLE_TOO_FINE)
+        return fail(BSRNN_EARG, "%s: %d -> %d reduces to %lld / %lld, beyond the limit of %d for max(up, down)", who, rate_in, rate_out,
+                    (long long)q.up, (long long)q.down, RESAMPLE_MAX_FACTOR);
+    return 0;
+}
+
+// The context's table of q's (up, down): designed in double, rounded to fp32 and uploaded when the pair is met first (synchronous).
+static int resample_table_of(bsrnn_ctx* c, const ResampleRatio& q, const bsrnn_ctx::ResampleTable** out)
+{
+    for (const auto& t : c->rs_tables)
+        if (t.q.up == q.up && t.q.down == q.down) { *out = &t; return 0; }
+    bsrnn_ctx::ResampleTable t{q, resample_tiling(q), nullptr};
+    const std::vector<float> tab = resample_table_by_output(q, resample_design(q), t.g.ld);
+    ++g_dbg[DBG_ALLOC];
+    HIP_TRY(hipMalloc((void**)&t.d, tab.size() * sizeof(float)));
+    if (hipError_t e = hipMemcpy(t.d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice)) {
+        (void)hipFree(t.d);
+        return fail(BSRNN_EHIP, "resampling table upload: %s", hipGetErrorString(e));
+    }
+    c->rs_tables.push_back(t);
+    *out = &c->rs_tables.back();
+    return 0;
+}
+
+static ResampleArgs resample_args(const ResampleRatio& q, const ResampleTiling& g, const float* tab)
+{
+    ResampleArgs a{};
+    a.tab = tab; a.up = (int)q.up; a.down = (int)q.down; a.Kh = q.Kh; a.ld = g.ld; a.chunk = g.chunk; a.tile = g.tile;
+    return a;
+}
+
+int64_t bsrnn_resample_len(int64_t n_in, int32_t rate_in, int32_t rate_out)
+{
+    const ResampleRatio q = resample_ratio(rate_in, rate_out);
+    if (q.why != RESAMPLE_OK || n_in < 1 || n_in > (INT64_MAX >> 12)) return -1;
+    return resample_n_out(n_in, q.up, q.down);
+}
+
+int bsrnn_resample(bsrnn_ctx* c, const float* in, int64_t in_stride, float* out, int64_t out_stride, int32_t R, int64_t n_in,
+                   int32_t rate_in, int32_t rate_out, void* stream)
+{
+    // arguments first, device or not (a host-only context answers them before BSRNN_ESTATE)
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!in || !out || R < 1) return fail(BSRNN_EARG, "bsrnn_resample: need an input, an output and R >= 1, got R = %d", R);
+    ResampleRatio q;
+    if (int rc = resample_check_rates(rate_in, rate_out, "bsrnn_resample", q)) return rc;
+    if (n_in < 1 || n_in > (INT64_MAX >> 12)) return fail(BSRNN_EARG, "bsrnn_resample: need n_in >= 1 samples, got %lld", (long long)n_in);
+    const int64_t n_out = resample_n_out(n_in, q.up, q.down);
+    if (in_stride < n_in) return fail(BSRNN_EARG, "bsrnn_resample: in_stride %lld is less than n_in = %lld", (long long)in_stride, (long long)n_in);
+    if (out_stride < n_out)
+        return fail(BSRNN_EARG, "bsrnn_resample: out_stride %lld is less than the %lld samples of a row's result", (long long)out_stride, (long long)n_out);
+    // the extent of what the rows span, not R * in_stride: behind the last row of a column view (buf[:, a:b]) lies somebody else's memory
+    if (ranges_overlap(in, ((size_t)(R - 1) * in_stride + n_in) * sizeof(float), out, ((size_t)(R - 1) * out_stride + n_out) * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_resample: out_dev must not overlap the (R - 1) * in_stride + n_in floats the rows of in_dev span "
+                                "(rows are read while others are written)");
+    if (int rc = check_device(c)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    if (q.up == q.down) {           // equal rates: a copy
+        HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride * sizeof(float), in, (size_t)in_stride * sizeof(float), (size_t)n_in * sizeof(float), R,
+                                 hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+    const bsrnn_ctx::ResampleTable* t = nullptr;
+    if (int rc = resample_table_of(c, q, &t)) return rc;
+    ResampleArgs a = resample_args(t->q, t->g, t->d);
+    a.b = in; a.b_stride = in_stride; a.n_total = n_in;
+    a.out = out; a.out_stride = out_stride; a.n_j = n_out;
+    a.n_tiles = (int)((n_out + t->g.tile - 1) / t->g.tile);
+    launch_resample(a, R, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int64_t resampler_keep_from(const bsrnn_resampler* rs, int64_t J)
+{
+    const int64_t b = resample_base(J, rs->q.up, rs->q.down, rs->q.Kh);
+    return b > 0 ? b : 0;
+}
+
+int bsrnn_resampler_create(bsrnn_ctx* c, int32_t C, int32_t rate_in, int32_t rate_out, bsrnn_resampler** out)
+{
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!out || C < 1) return fail(BSRNN_EARG, "bsrnn_resampler_create: need C >= 1 rows and a place for the object, got C = %d", C);
+    ResampleRatio q;
+    if (int rc = resample_check_rates(rate_in, rate_out, "bsrnn_resampler_create", q)) return rc;
+    if (int rc = check_device(c)) return rc;
+    CallGuard guard_(c);
+    if (!guard_.ok) return guard_.refuse();
+    const bsrnn_ctx::ResampleTable* t = nullptr;
+    if (int rc = resample_table_of(c, q, &t)) return rc;
+    bsrnn_resampler* rs = new bsrnn_resampler();
+    rs->ctx = c; rs->C = C; rs->q = t->q; rs->g = t->g; rs->tab = t->d;
+    rs->cap = resample_carry_floats(q);
+    rs->cur = 0; rs->N = rs->J = 0;
+    float* p = nullptr;
+    ++g_dbg[DBG_ALLOC];
+    const size_t bytes = 2 * (size_t)C * rs->cap * sizeof(float);
+    hipError_t e = hipMalloc((void**)&p, bytes);
+    if (e == hipSuccess && (e = hipMemset(p, 0, bytes)) != hipSuccess) (void)hipFree(p);
+    if (e != hipSuccess) { delete rs; return fail(BSRNN_EHIP, "bsrnn_resampler_create: %s", hipGetErrorString(e)); }
+    rs->carry[0] = p; rs->carry[1] = p + (size_t)C * rs->cap;
+    // the kernel's first launch (code object loading) happens here, not in the first bsrnn_resampler_process: an empty carry hand-over
+    ResampleArgs a = resample_args(rs->q, rs->g, rs->tab);
+    a.a = rs->carry[0]; a.a_stride = rs->cap; a.carry = rs->carry[1]; a.carry_stride = rs->cap;
+    launch_resample(a, C, nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) { (void)hipFree(p); delete rs; return fail(BSRNN_EHIP, "bsrnn_resampler_create: %s", hipGetErrorString(e)); }
+    ++c->live_streams;
+    *out = rs;
+    return 0;
+}
+
+void bsrnn_resampler_destroy(bsrnn_resampler* rs)
+{
+    if (!rs) return;
+    bsrnn_ctx* c = rs->ctx;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(rs->carry[0]);
+    delete rs;
+    if (--c->live_streams == 0 && c->zombie) destroy_now(c);     // as bsrnn_stream_destroy: the context goes with the last object that points at it
+}
+
+int bsrnn_resampler_reset(bsrnn_resampler* rs, void* stream)
+{
+    if (!rs) return fail(BSRNN_EARG, "null resampler");
+    (void)stream;          // nothing to enqueue: with no input taken the carry holds no sample a call would read
+    rs->N = rs->J = 0;
+    return 0;
+}
+
+int64_t bsrnn_resampler_ready(const bsrnn_resampler* rs, int64_t n_in)
+{
+    if (!rs || n_in < 0 || n_in > (INT64_MAX >> 12) - rs->N) return -1;
+    return resample_ready(rs->N + n_in, rs->q.up, rs->q.down, rs->q.half) - rs->J;
+}
+
+// process (flush == false): the block joins the carry and the outputs it determines are written; flush: what is left up to the final
+// length, the future taken as zeros.
+static int resampler_run(bsrnn_resampler* rs, const float* in, int64_t in_stride, int64_t n_in, float* out, int64_t out_stride,
+                         int64_t* n_out_host, bool flush, hipStream_t s)
+{
+    const char* who = flush ? "bsrnn_resampler_flush" : "bsrnn_resampler_process";
+    if (!rs) return fail(BSRNN_EARG, "null resampler");
+    if (!n_out_host) return fail(BSRNN_EARG, "%s: nowhere to report the sample count", who);
+    if (n_in < 0 || n_in > (INT64_MAX >> 12) - rs->N) return fail(BSRNN_EARG, "%s: need n_in >= 0 samples, got %lld", who, (long long)n_in);
+    if (n_in > 0 && (!in || in_stride < n_in))
+        return fail(BSRNN_EARG, "%s: need an input block with in_stride >= n_in, got in_stride = %lld, n_in = %lld", who, (long long)in_stride, (long long)n_in);
+    const ResampleRatio& q = rs->q;
+    const int64_t N1 = rs->N + n_in;
+    const int64_t J1 = flush ? resample_n_out(N1, q.up, q.down) : resample_ready(N1, q.up, q.down, q.half);
+    const int64_t count = J1 - rs->J;
+    if (count > 0 && (!out || out_stride < count))
+        return fail(BSRNN_EARG, "%s: need an output block with out_stride >= the %lld samples this call writes per row, got out_stride = %lld", who,
+                    (long long)count, (long long)out_stride);
+    if (n_in > 0 && count > 0 &&
+        ranges_overlap(in, ((size_t)(rs->C - 1) * in_stride + n_in) * sizeof(float), out, ((size_t)(rs->C - 1) * out_stride + count) * sizeof(float)))
+        return fail(BSRNN_EARG, "%s: out_dev must not overlap in_dev (rows are read while others are written)", who);
+    bsrnn_ctx* c = rs->ctx;
+    if (int rc = check_device(c)) return rc;
+    ENTER_CALL(c, s);
+    *n_out_host = count;
+    if (flush) {
+        if (count > 0) {
+            ResampleArgs a = resample_args(q, rs->g, rs->tab);
+            a.a = rs->carry[rs->cur]; a.a_stride = rs->cap; a.a0 = resampler_keep_from(rs, rs->J); a.a1 = rs->N; a.n_total = rs->N;
+            a.out = out; a.out_stride = out_stride; a.j0 = rs->J; a.n_j = count;
+            a.n_tiles = (int)((count + rs->g.tile - 1) / rs->g.tile);
+            launch_resample(a, rs->C, s);
+            HIP_TRY(hipGetLastError());
+        }
+        rs->N = rs->J = 0;
+        return 0;
+    }
+    if (n_in == 0) return 0;
+    ResampleArgs a = resample_args(q, rs->g, rs->tab);
+    a.a = rs->carry[rs->cur]; a.a_stride = rs->cap; a.a0 = resampler_keep_from(rs, rs->J); a.a1 = rs->N;
+    a.b = in; a.b_stride = in_stride; a.n_total = N1;
+    a.out = out; a.out_stride = out_stride; a.j0 = rs->J; a.n_j = count;
+    a.n_tiles = (int)((count + rs->g.tile - 1) / rs->g.tile);
+    a.carry = rs->carry[rs->cur ^ 1]; a.carry_stride = rs->cap; a.c0 = resampler_keep_from(rs, J1);
+    if (N1 - a.c0 > rs->cap) return fail(BSRNN_ESTATE, "%s: the carry would hold %lld samples of %lld (internal error)", who, (long long)(N1 - a.c0), (long long)rs->cap);
+    launch_resample(a, rs->C, s);
+    HIP_TRY(hipGetLastError());
+    rs->N = N1; rs->J = J1; rs->cur ^= 1;
+    return 0;
+}
+
+int bsrnn_resampler_process(bsrnn_resampler* rs, const float* in, int64_t in_stride, int64_t n_in, float* out, int64_t out_stride,
+                            int64_t* n_out_host, void* stream)
+{
+    return resampler_run(rs, in, in_stride, n_in, out, out_stride, n_out_host, false, (hipStream_t)stream);
+}
+
+int bsrnn_resampler_flush(bsrnn_resampler* rs, float* out, int64_t out_stride, int64_t* n_out_host, void* stream)
+{
+    return resampler_run(rs, nullptr, 0, 0, out, out_stride, n_out_host, true, (hipStream_t)stream);
 }
 
 // --------------------------------------------------------------------------- measurement

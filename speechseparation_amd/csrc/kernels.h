@@ -325,4 +325,20 @@ void launch_metric_input_sdr_ragged(const float* speech, const float* mix, const
 void launch_metric_freq_ragged(const FftTables& tb, const float* Yf, const float* Sf, const int64_t* lens, int R, int Tmax,
                                double* part /* [R][blocks][2] */, int blocks, hipStream_t s);
 
+// ------------------------------------------------------------------ sample-rate conversion (resample.hip; the definition: resample_host.h)
+// One launch serves bsrnn_resample and the streaming resampler.  The input of row r is the concatenation of two segments - a [a0, a1),
+// the resampler's carry (rows a_stride apart; absent offline: a0 = a1 = 0), and b [a1, n_total), the caller's block (rows b_stride
+// apart; null in a flush) - with zeros in front of 0 and from n_total on.  Outputs j0 .. j0 + n_j - 1 of every row go to out[r][j - j0].
+// carry (optional): the launch also writes inputs [c0, n_total) of every row to carry[r][0 ..], the next call's segment a; it must not
+// be the buffer a points at.  tab [ld][up] on the device, laid out by output (resample_table_by_output); ld, chunk and tile from resample_tiling().
+struct ResampleArgs {
+    const float* a; int64_t a_stride, a0;
+    const float* b; int64_t b_stride, a1, n_total;
+    float* out; int64_t out_stride, j0, n_j;
+    const float* tab;
+    int up, down, Kh, ld, chunk, tile, n_tiles;
+    float* carry; int64_t carry_stride, c0;
+};
+void launch_resample(ResampleArgs g, int R, hipStream_t s);
+
 }  // namespace bsrnn

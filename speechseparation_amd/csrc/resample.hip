@@ -1,0 +1,130 @@
+// Sample-rate conversion on the device: scipy.signal.resample_poly's polyphase FIR (resample_host.h holds the definition and every
+// index rule).  One kernel for bsrnn_resample and for the streaming resampler: they differ only in where an input sample lives (the
+// caller's buffer, or the resampler's carry in front of it), never in how an output sample is formed - resample_mac below, the same
+// taps in the same order - which is what makes the concatenated streaming output equal the one-shot call bit for bit.
+//
+// A workgroup owns `tile` consecutive outputs of one row.  Their inputs are one contiguous span (tile * down / up + L samples), staged
+// in LDS once and read L times.  The taps come through L1 / L2 from the table laid out BY OUTPUT, [ld][up] with column j mod up
+// (resample_table_by_output): for each t the lanes of a wave read consecutive floats.  With the table as [up][ld] - a row per phase,
+// 16-byte loads - every lane of a load read another row, 64 cache lines per instruction, and the kernel ran at the vector memory
+// pipeline's one line per clock, 7 to 15 times a copy of the same bytes; the whole table is 13 KB at 48 k -> 44.1 k, 52 KB at the largest audio pair,
+// and every workgroup of the launch reads the same one (measurements: DESIGN.md section 4n).  fp32 accumulation in four partial sums
+// (t mod 4), added pairwise at the end.
+#include "kernels.h"
+#include "resample_host.h"
+
+namespace bsrnn {
+
+namespace {
+
+struct RsAcc { float a, b, c, d; };
+
+// One output sample's share of n taps (n % 4 == 0): x[0 .. n) from LDS against taps[0], taps[up], .. (its column of the table)
+__device__ __forceinline__ void resample_mac(const float* __restrict__ x, const float* __restrict__ taps, unsigned up, int n, RsAcc& s)
+{
+    for (int t = 0; t < n; t += 4) {
+        const float h0 = taps[0], h1 = taps[up], h2 = taps[2 * up], h3 = taps[3 * up];
+        taps += 4 * up;
+        s.a = __builtin_fmaf(x[t], h0, s.a);
+        s.b = __builtin_fmaf(x[t + 1], h1, s.b);
+        s.c = __builtin_fmaf(x[t + 2], h2, s.c);
+        s.d = __builtin_fmaf(x[t + 3], h3, s.d);
+    }
+}
+
+// Input sample i of the row whose segments start at ra / rb: zero outside [a0, n_total)
+__device__ __forceinline__ float resample_input(const ResampleArgs& g, const float* ra, const float* rb, int64_t i)
+{
+    if (i < g.a0 || i >= g.n_total) return 0.0f;
+    return i < g.a1 ? ra[i - g.a0] : rb[i - g.a1];
+}
+
+}  // namespace
+
+// grid (n_tiles [+ 1 when a carry is written], R)
+__global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs g, const int vec)
+{
+    __shared__ float xs[RESAMPLE_SPAN];
+    const int tid = threadIdx.x;
+    const int64_t r = blockIdx.y;
+    const float* ra = g.a + r * g.a_stride;
+    const float* rb = g.b + r * g.b_stride;
+    if ((int)blockIdx.x == g.n_tiles) {            // the extra workgroup of a streaming call: what the next call still needs
+        float* dst = g.carry + r * g.carry_stride;
+        const int n = (int)(g.n_total - g.c0);
+        for (int k = tid; k < n; k += 256) dst[k] = resample_input(g, ra, rb, g.c0 + k);
+        return;
+    }
+    const int64_t jt = g.j0 + (int64_t)blockIdx.x * g.tile;
+    const int64_t left = g.j0 + g.n_j - jt;
+    const int nj = left < g.tile ? (int)left : g.tile;
+    // j * down = q0 * up + r0 for the tile's first output; from there on 32 bits do (tile, down, up <= 1024)
+    const int64_t c = jt * g.down;
+    const int64_t q0 = c / g.up;
+    const unsigned r0 = (unsigned)(c - q0 * g.up), up = (unsigned)g.up, down = (unsigned)g.down;
+    const unsigned jm0 = (unsigned)(jt % g.up);
+    unsigned off[4], col[4];            // per output: where its inputs start in the span, its column of the table (j mod up)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        off[k] = (r0 + (unsigned)(tid + 256 * k) * down) / up;
+        col[k] = (jm0 + (unsigned)(tid + 256 * k)) % up;
+    }
+    const int reach = (int)((r0 + (unsigned)(nj - 1) * down) / up);      // off of the tile's last output
+    RsAcc acc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] = RsAcc{0.0f, 0.0f, 0.0f, 0.0f};
+
+    for (int t0 = 0; t0 < g.ld; t0 += g.chunk) {
+        const int nt = g.ld - t0 < g.chunk ? g.ld - t0 : g.chunk;
+        const int len = reach + nt;                                      // <= RESAMPLE_SPAN (resample_tiling)
+        const int64_t s0 = q0 - g.Kh + t0;                               // the input index of xs[0]
+        if (vec) {
+            // 16-byte loads of the aligned groups of four of segment b that lie wholly inside it and inside the span; the groups at
+            // the edges, the carry and the zeros sample by sample.  (vec: every row of b starts 16-byte aligned.)
+            const int64_t eb = s0 - g.a1, nb = g.n_total - g.a1;         // xs[0] is b[eb]
+            const int64_t e_first = eb - (((eb % 4) + 4) % 4);
+            const int groups = (int)((eb + len - e_first + 3) / 4);
+            for (int u = tid; u < groups; u += 256) {
+                const int64_t e4 = e_first + 4 * (int64_t)u;
+                const int k = (int)(e4 - eb);
+                if (e4 >= 0 && e4 + 3 < nb && k >= 0 && k + 3 < len) {
+                    const float4 v = *reinterpret_cast<const float4*>(rb + e4);
+                    xs[k] = v.x; xs[k + 1] = v.y; xs[k + 2] = v.z; xs[k + 3] = v.w;
+                } else {
+#pragma unroll
+                    for (int m = 0; m < 4; ++m)
+                        if (k + m >= 0 && k + m < len) xs[k + m] = resample_input(g, ra, rb, s0 + k + m);
+                }
+            }
+        } else {
+            for (int k = tid; k < len; k += 256) xs[k] = resample_input(g, ra, rb, s0 + k);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (tid + 256 * k < nj) resample_mac(xs + off[k], g.tab + (size_t)t0 * up + col[k], up, nt, acc[k]);
+        __syncthreads();
+    }
+    float* dst = g.out + r * g.out_stride + (jt - g.j0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (tid + 256 * k < nj) dst[tid + 256 * k] = (acc[k].a + acc[k].b) + (acc[k].c + acc[k].d);
+}
+
+void launch_resample(ResampleArgs g, int R, hipStream_t s)
+{
+    const int blocks = g.n_tiles + (g.carry ? 1 : 0);
+    if (blocks < 1 || R < 1) return;
+    // 16-byte loads where every row of the caller's block starts aligned, as metric_time_kernel decides: the base and the stride
+    const int vec = g.b && ((uintptr_t)g.b & 15) == 0 && g.b_stride % 4 == 0;
+    for (int r = 0; r < R; r += 65535) {             // (rows are the grid's y: 65535 per launch)
+        const int rows = R - r < 65535 ? R - r : 65535;
+        hipLaunchKernelGGL(resample_kernel, dim3(blocks, rows), dim3(256), 0, s, g, vec);
+        if (g.a) g.a += rows * g.a_stride;
+        if (g.b) g.b += rows * g.b_stride;
+        if (g.carry) g.carry += rows * g.carry_stride;
+        if (g.out) g.out += rows * g.out_stride;
+    }
+}
+
+}  // namespace bsrnn
