@@ -459,10 +459,31 @@ int  bsrnn_stream_reserve(bsrnn_stream* s, int32_t max_hops);
  * bsrnn_stream_row_floats: floats of one row's carry, 2*2048 + 8*K*64 (-1 for a null stream).
  * bsrnn_stream_get_row / _set_row: synchronous; copy one row's carry to / from blob_host [buf 2048 | prev 2048 | state 4,2,K,64].  A
  *     blob set into any row of a stream of the same C and band table continues bit for bit as it would have in place.  get_row reports
- *     a range violation left by calls under BSRNN_RANGE_DEFERRED, like bsrnn_stream_get_state. */
+ *     a range violation left by calls under BSRNN_RANGE_DEFERRED, like bsrnn_stream_get_state.
+ * bsrnn_stream_process_hops: one call in which every row advances by its OWN number of hops - what a server needs whose sessions do
+ *     not deliver audio in lock step.  Buffers as for bsrnn_stream_process_rows: chunk_dev and out_dev are [C, n_hops*1024]; hops_host
+ *     [C] (ordinary host memory, each in [0, n_hops], the caller's again at return under either range policy) says how far each row
+ *     goes.  Row r with h = hops_host[r]: its first h*1024 samples of chunk_dev are read and nothing behind them (it may hold NaN); its
+ *     first h*1024 samples of out_dev are what h consecutive bsrnn_stream_step calls would give that row, the rest of its out_dev row is
+ *     zeros; its carry (analysis buffer, previous synthesis frame, LSTM state) is the carry after exactly h hops.  h = 0 holds the row
+ *     as bsrnn_stream_process_rows does: carry bit for bit as it was.  The counts travel by value in the kernel arguments (8 bits per
+ *     row: at most BSRNN_STREAM_HOPS_MAX hops per call), so the call allocates nothing, stages no copy and keeps nothing alive.
+ *     When every count is 0 or n_hops the call IS bsrnn_stream_process_rows with active = hops != 0 (bit-identical by construction,
+ *     one-hop path included; no row with a hop: out_dev zeroed, nothing else).  Mixed counts always take the block path: the model runs
+ *     on all C * n_hops frame rows (a row's frames past its count enter it as zero spectra), planned exactly as the plain call, and its
+ *     time-axis launches hand back each row's LSTM state after that row's last frame.  The frames of a row below its count are
+ *     those of a call in which the row has all n_hops hops of the same leading audio: the time axis is causal, all else is per frame.
+ *     mix_rows_dev, mix, range policy (a re-run keeps the counts), the overlap rules and the concurrency contract: as
+ *     bsrnn_stream_process_rows.  After bsrnn_stream_reserve(max_hops) - or after the first hops call of a shape - hops calls of up to
+ *     max_hops hops allocate, capture and instantiate nothing, whatever the counts.
+ *     BSRNN_EARG, the text naming the problem: a null s, chunk_dev, out_dev or hops_host; n_hops outside [1, BSRNN_STREAM_HOPS_MAX];
+ *     a count outside [0, n_hops] (the row is named); more than BSRNN_STREAM_ROWS_MAX rows; the overlaps above. */
 #define BSRNN_STREAM_ROWS_MAX 2048
+#define BSRNN_STREAM_HOPS_MAX 255
 int     bsrnn_stream_process_rows(bsrnn_stream* s, const float* chunk_dev, float* out_dev, int32_t n_hops,
                                   const uint8_t* active_host, const float* mix_rows_dev, float mix, void* stream);
+int     bsrnn_stream_process_hops(bsrnn_stream* s, const float* chunk_dev, float* out_dev, int32_t n_hops,
+                                  const int32_t* hops_host, const float* mix_rows_dev, float mix, void* stream);
 int     bsrnn_stream_reset_rows(bsrnn_stream* s, const int32_t* rows_host, int32_t n_rows, void* stream);
 int64_t bsrnn_stream_row_floats(const bsrnn_stream* s);
 int     bsrnn_stream_get_row(bsrnn_stream* s, int32_t row, float* blob_host);

@@ -26,12 +26,13 @@ SYMBOLS = [
     "bsrnn_set_range_policy", "bsrnn_get_range_policy", "bsrnn_overlap_state", "bsrnn_debug_peek", "bsrnn_debug_counter",
     "bsrnn_stream_process", "bsrnn_stream_reserve", "bsrnn_separate_long", "bsrnn_separate_long_host", "bsrnn_workspace_rows",
     "bsrnn_separate_ragged", "bsrnn_evaluate_ragged", "bsrnn_separate_long_ragged",
-    "bsrnn_stream_process_rows", "bsrnn_stream_reset_rows", "bsrnn_stream_row_floats", "bsrnn_stream_get_row", "bsrnn_stream_set_row",
+    "bsrnn_stream_process_rows", "bsrnn_stream_process_hops", "bsrnn_stream_reset_rows", "bsrnn_stream_row_floats", "bsrnn_stream_get_row", "bsrnn_stream_set_row",
     "bsrnn_resample_len", "bsrnn_resample", "bsrnn_resampler_create", "bsrnn_resampler_destroy", "bsrnn_resampler_reset",
     "bsrnn_resampler_ready", "bsrnn_resampler_process", "bsrnn_resampler_flush",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
+STREAM_HOPS_MAX = 255                       # BSRNN_STREAM_HOPS_MAX
 METRIC_NAMES = ("loss", "sdr", "input_sdr", "sisdr", "l1_time", "l1_re", "l1_im", "separation_db")   # BSRNN_M_* order
 
 
@@ -104,6 +105,7 @@ def _load():
         "bsrnn_stream_process": (C.c_int, [vp, vp, vp, i32, C.c_float, vp]),
         "bsrnn_stream_reserve": (C.c_int, [vp, i32]),
         "bsrnn_stream_process_rows": (C.c_int, [vp, vp, vp, i32, vp, vp, C.c_float, vp]),
+        "bsrnn_stream_process_hops": (C.c_int, [vp, vp, vp, i32, vp, vp, C.c_float, vp]),
         "bsrnn_stream_reset_rows": (C.c_int, [vp, vp, i32, vp]),
         "bsrnn_stream_row_floats": (i64, [vp]),
         "bsrnn_stream_get_row": (C.c_int, [vp, i32, vp]),

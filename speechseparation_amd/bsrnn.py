@@ -848,6 +848,51 @@ class StreamingSeparator:
                                                   float(mix), _stream_ptr(self.device)))
         return out if wave.is_cuda else out.cpu()
 
+    def process_hops(self, wave, hops, mix=1.0):
+        """wave [C, L*1024] float32 (cuda or cpu), whole hops, and hops, a sequence or tensor of C ints in [0, L] -> [C, L*1024] on the same
+        device, from one library call (bsrnn_stream_process_hops): row r takes its first hops[r] hops exactly as that many step() calls
+        would give them, its output row is zeros behind them, its input row is never read behind them, and its carry is the one after
+        hops[r] hops; a row at 0 is held as by process_rows.  At most 255 hops per call.  `mix` is one wet / dry value or a [C] tensor
+        of one per row.  Takes no part in process()'s carrying of partial hops."""
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != self.C:
+            raise ValueError("process_hops: expected wave [%d, L*1024], got %s" % (
+                self.C, tuple(wave.shape) if isinstance(wave, torch.Tensor) else type(wave).__name__))
+        if wave.shape[1] % _spec.HOP:
+            raise ValueError("process_hops: wave must hold whole hops of 1024 samples, got %d samples per row" % wave.shape[1])
+        L = wave.shape[1] // _spec.HOP
+        if L > _native.STREAM_HOPS_MAX:
+            raise ValueError("process_hops: %d hops, a call takes at most %d" % (L, _native.STREAM_HOPS_MAX))
+        try:
+            counts = list(hops.tolist() if isinstance(hops, (torch.Tensor, np.ndarray)) else hops)
+        except TypeError:
+            raise ValueError("process_hops: hops must be a sequence of %d ints, got %s" % (self.C, type(hops).__name__)) from None
+        if len(counts) != self.C:
+            raise ValueError("process_hops: %d counts for %d rows" % (len(counts), self.C))
+        for r, h in enumerate(counts):
+            if isinstance(h, bool) or not isinstance(h, (int, np.integer)):
+                raise ValueError("process_hops: the count of row %d must be an int, got %s" % (r, type(h).__name__))
+            if not 0 <= h <= L:
+                raise ValueError("process_hops: row %d has %d hops, outside [0, %d]" % (r, h, L))
+        mix_rows = None
+        if isinstance(mix, torch.Tensor):
+            if tuple(mix.shape) != (self.C,):
+                raise ValueError("process_hops: mix must be a float or a tensor [%d], got %s" % (self.C, tuple(mix.shape)))
+            mix_rows, mix = mix, 1.0
+        elif isinstance(mix, bool) or not isinstance(mix, (int, float, np.floating, np.integer)):
+            raise ValueError("process_hops: mix must be a float or a tensor [%d], got %s" % (self.C, type(mix).__name__))
+        if L == 0:
+            return torch.empty((self.C, 0), dtype=torch.float32, device=wave.device)
+        self._look_at_weights()
+        x = wave.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        out = torch.empty_like(x)
+        if mix_rows is not None:
+            mix_rows = mix_rows.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        cnt = (ctypes.c_int32 * self.C)(*[int(h) for h in counts])
+        with torch.cuda.device(self.device):
+            _check(_lib.bsrnn_stream_process_hops(self._h, _ptr(x), _ptr(out), L, cnt, _ptr(mix_rows) if mix_rows is not None else None,
+                                                  float(mix), _stream_ptr(self.device)))
+        return out if wave.is_cuda else out.cpu()
+
     def reset_rows(self, rows):
         """Zero the carry of the listed rows (bsrnn_stream_reset_rows): each then continues as the same row of a fresh stream would."""
         try:
@@ -952,8 +997,9 @@ class Resampler:
 class StreamPool:
     """Many live sessions on one wide stream: `slots` sessions of `rows_per_session` rows each share one StreamingSeparator of
     slots * rows_per_session rows, and one step() serves whichever of them have audio this tick at the price of one streaming call
-    (a step is launch-bound: its cost hardly grows with the rows).  Sessions join (open), leave (close), pause (not named in a step:
-    their rows are held) and move between pools (export / adopt) one by one.  The stream is created at the first call that needs the
+    (a step is launch-bound: its cost hardly grows with the rows).  feed() does the same for sessions that do NOT deliver audio in lock
+    step: each gives whatever it has, and one call advances every session by its own number of hops.  Sessions join (open), leave
+    (close), pause (not named in a step or feed: their rows are held) and move between pools (export / adopt) one by one.  The stream is created at the first call that needs the
     device; shape and type errors are raised before that."""
 
     def __init__(self, model, slots, rows_per_session=1, device=None):
@@ -967,6 +1013,7 @@ class StreamPool:
         self._slot = {}                     # session id -> slot
         self._free = list(range(self.slots))
         self._next = 0
+        self._pend = {}                     # feed(): session id -> the samples (fewer than one hop) that wait for its next feed
 
     def _stream(self):
         if self._st is None:
@@ -992,8 +1039,81 @@ class StreamPool:
         return sid
 
     def close(self, sid):
+        """The session leaves; samples of it that feed() kept waiting are dropped."""
         self._free.append(self._slot.pop(sid))
         self._free.sort()
+        self._pend.pop(sid, None)
+
+    def pending(self, sid):
+        """Samples per row of the session that wait for its next feed() (fewer than one hop)."""
+        self._rows_of(sid)
+        p = self._pend.get(sid)
+        return 0 if p is None else int(p.shape[1])
+
+    def feed(self, chunks, mix=None):
+        """chunks {sid: tensor [rows_per_session, n]}, ANY n >= 0 and another one per session -> {sid: tensor [rows_per_session, h*1024] on
+        its chunk's device}: every session advances by the h = (pending + n) // 1024 hops it has in hand, in ONE library call
+        (bsrnn_stream_process_hops; several of at most 255 hops where a session brings more than that).  The remainder of fewer than one
+        hop waits per session, on the device, and is prepended at the session's next feed, as StreamingSeparator.process does for a whole
+        stream.  A session without a whole hop gets an empty tensor and its rows are held; so are sessions not named.  If nobody has a
+        hop, no library call is made.  mix as in step().  The pending samples are NOT part of the carry that export() hands out: feed
+        whole hops before moving a session, or move pending(sid) samples of its audio yourself."""
+        if not isinstance(chunks, dict):
+            raise ValueError("StreamPool.feed: chunks must be a dict {session id: tensor}, got %s" % type(chunks).__name__)
+        for sid, t in chunks.items():
+            self._rows_of(sid)
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != self.rows:
+                raise ValueError("StreamPool.feed: session %r needs a tensor [%d, n], got %s" % (
+                    sid, self.rows, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+        per_row = isinstance(mix, dict)
+        if per_row:
+            for sid, v in mix.items():
+                self._rows_of(sid)
+                if isinstance(v, bool) or not isinstance(v, (int, float)):
+                    raise ValueError("StreamPool.feed: mix of session %r must be a float, got %s" % (sid, type(v).__name__))
+        elif mix is not None and (isinstance(mix, bool) or not isinstance(mix, (int, float))):
+            raise ValueError("StreamPool.feed: mix must be None, a float or a dict {session id: float}, got %s" % type(mix).__name__)
+        hop = _spec.HOP
+        have = {sid: self.pending(sid) + t.shape[1] for sid, t in chunks.items()}
+        anyone = any(n >= hop for n in have.values())
+        # (the stream is made by the first feed that has a hop for it; until then what waits stays where the caller's tensors are)
+        dev = self._stream().device if anyone else (self._st.device if self._st is not None else None)
+        audio = {}
+        for sid, t in chunks.items():
+            w = t.detach().to(dtype=torch.float32) if dev is None else t.detach().to(device=dev, dtype=torch.float32)
+            p = self._pend.get(sid)
+            if p is not None and p.shape[1]:
+                w = torch.cat((p.to(w.device), w), 1)
+            audio[sid] = w
+            self._pend[sid] = w[:, (have[sid] // hop) * hop:].clone()
+        res = {sid: [] for sid in chunks}
+        done = {sid: 0 for sid in chunks}
+        C = self.slots * self.rows
+        while any(have[sid] // hop > done[sid] for sid in chunks):
+            st = self._st
+            take = {sid: min(have[sid] // hop - done[sid], _native.STREAM_HOPS_MAX) for sid in chunks}
+            L = max(take.values())
+            wave = torch.zeros((C, L * hop), dtype=torch.float32, device=st.device)
+            counts = [0] * C
+            mix_rows = [1.0] * C
+            for sid, h in take.items():
+                rows = self._rows_of(sid)
+                wave[rows.start:rows.stop, :h * hop] = audio[sid][:, done[sid] * hop:(done[sid] + h) * hop]
+                for r in rows:
+                    counts[r] = h
+                    if per_row:
+                        mix_rows[r] = float(mix.get(sid, 1.0))
+            m = torch.tensor(mix_rows, dtype=torch.float32) if per_row else (1.0 if mix is None else float(mix))
+            out = st.process_hops(wave, counts, m)
+            for sid, h in take.items():
+                rows = self._rows_of(sid)
+                res[sid].append(out[rows.start:rows.stop, :h * hop])
+                done[sid] += h
+        ret = {}
+        for sid, t in chunks.items():
+            o = torch.cat(res[sid], 1) if res[sid] else torch.empty((self.rows, 0), dtype=torch.float32, device=t.device)
+            ret[sid] = (o.clone() if len(res[sid]) == 1 else o) if t.is_cuda else o.cpu()
+        return ret
 
     def step(self, chunks, mix=None):
         """chunks {sid: tensor [rows_per_session, L*1024]}, one L for all -> {sid: tensor of the same shape, on its chunk's device}, delayed

@@ -230,6 +230,7 @@ struct bsrnn_stream {
     float *buf[2], *prev[2], *state[2];
     int cur = 0;                       // the set the NEXT step reads
     float *X, *Y, *chunk, *out;
+    int* row_frames = nullptr;         // [C]: the hops of every row of a bsrnn_stream_process_hops call (its analysis launch writes them, its time-axis launches read them)
     float *h_in = nullptr, *h_out = nullptr;   // pinned staging for the host-buffer entry point
     // One step = analysis, ~18 launches of the model, synthesis.  The model part works on fixed buffers (X -> Y, state set p -> set
     // 1 - p), so it is captured once per parity into a hipGraph and replayed (launch-bound inner loop); the two DSP kernels are
@@ -480,6 +481,7 @@ struct Part {
     const bsrnn_ctx::OvlTable* ovl;                      // non-null: the overlapped flow (run_overlapped) - producers publish, consumers wait
     int ovl_base;                                        // this call's epoch << OVL_EPOCH_SHIFT
     hipEvent_t band_done[2];                             // events the two band launches signal themselves when they complete (or null)
+    const int* row_frames;                               // non-null: frames per row [C] on the device - the time-axis launches return the state after them (bsrnn_stream_process_hops)
 };
 
 Part make_part(bsrnn_ctx* c, int row0, int C, int T, hipStream_t s, int j = 0)
@@ -588,7 +590,7 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
         launch_time_lstm(first_of_parts ? p.Z0 : p.Z1, first_of_parts ? p.Z1 : (f.time_fc ? p.Z0 : p.H1), c->timeW[blk], c->timeW16[blk], c->timeB[blk],
                          p.state_in ? p.state_in + blk * p.state_slab : nullptr, p.state_out ? p.state_out + blk * p.state_slab : nullptr,
                          p.C, p.T, K, c->d_range, s, f.lstm_f32, f.seqs, f.time_fc ? c->timeFc16[blk] : nullptr, f.time_fc ? c->timeFcB[blk] : nullptr,
-                         f.band == BAND_PAIR_PARTS ? p.HB1 : nullptr, p.ovl ? &op : nullptr);
+                         f.band == BAND_PAIR_PARTS ? p.HB1 : nullptr, p.ovl ? &op : nullptr, p.row_frames);
         break;
     }
     case MS_TIMEFC0: case MS_TIMEFC1: {
@@ -732,9 +734,10 @@ static const bsrnn_ctx::OvlTable* ovl_table(const bsrnn_ctx* c, const Flow& f, i
 
 // The model proper for a single part on one stream.
 int run_model(bsrnn_ctx* c, const float* Xf, float* Yf, float* tap, int C, int T,
-              const float* state_in, float* state_out, hipStream_t s)
+              const float* state_in, float* state_out, hipStream_t s, const int* row_frames = nullptr)
 {
     Part p = make_part(c, 0, C, T, s);
+    p.row_frames = row_frames;
     p.f = plan_call(c, C, T, true, true);
     if (int rc = ensure_ovl(c, p.f, C, T)) return rc;
     p.Xf = Xf; p.Yf = Yf; p.tap = tap;
@@ -2236,11 +2239,12 @@ int bsrnn_evaluate_ragged(bsrnn_ctx* c, const float* mix, const float* speech, i
 
 
 // --------------------------------------------------------------------------- streaming
-// Device layout of a stream object: two carry sets [buf | prev | state] (see bsrnn_stream), then the per-step scratch [X | Y | chunk | out].
+// Device layout of a stream object: two carry sets [buf | prev | state] (see bsrnn_stream), then the per-step scratch [X | Y | chunk | out]
+// and the hop counts of a hops call [row_frames].
 static size_t stream_carry_floats(const bsrnn_ctx* c, int C) { return (size_t)C * NFFT * 2 + state_floats(C, c->K); }
 static size_t stream_total_floats(const bsrnn_ctx* c, int C)
 {
-    return 2 * stream_carry_floats(c, C) + (size_t)C * ((size_t)c->LDP * 2 + HOPS * 2) + 4;
+    return 2 * stream_carry_floats(c, C) + (size_t)C * ((size_t)c->LDP * 2 + HOPS * 2 + 1) + 4;      // (+ 1: row_frames, one word per row)
 }
 
 int bsrnn_stream_create(bsrnn_ctx* c, int32_t C, bsrnn_stream** out)
@@ -2268,6 +2272,7 @@ int bsrnn_stream_create(bsrnn_ctx* c, int32_t C, bsrnn_stream** out)
     st->Y = p; p += (size_t)C * c->LDP;
     st->chunk = p; p += (size_t)C * HOPS;
     st->out = p; p += (size_t)C * HOPS;
+    st->row_frames = reinterpret_cast<int*>(p); p += C;
     // The model part of a step as plain launches (default) or as one hipGraph per carry parity (BSRNN_STREAM_GRAPH=1).  Measured from C
     // (tools/stream_cloop.cpp, profiles/r04_stream_kernels.txt): the graph launch of the 14 dependent kernel nodes costs the host MORE than
     // 14 plain launches (78 vs 68 us inside the call) and the chunk 143.2 vs 139.5 us - the gaps between dependent kernels are the same
@@ -2445,19 +2450,26 @@ int bsrnn_stream_step_host(bsrnn_stream* st, const float* chunk_host, float* out
 // rows: as for stream_step_run.  On the overlapped plan the second time-axis launch writes its half of state[q] on the auxiliary stream;
 // run_overlapped joins that stream into `s` by an event for every call that returns LSTM state - this one does - so the synthesis launch,
 // which copies the held rows' state over what the model wrote, follows both.
-static int stream_block_run(bsrnn_stream* st, const float* chunk, float* out, int L, float mix, hipStream_t s, const RowArgs* rows = nullptr)
+// hops (bsrnn_stream_process_hops): row r advances by its own count.  The analysis launch leaves the counts in st->row_frames, the two
+// time-axis launches return every row's state after ITS last frame, and the synthesis - which follows both, as above - holds the rows at 0.
+struct HopArgs { RowHops hops; const float* mix_rows; };
+static int stream_block_run(bsrnn_stream* st, const float* chunk, float* out, int L, float mix, hipStream_t s, const RowArgs* rows = nullptr,
+                            const HopArgs* hops = nullptr)
 {
     bsrnn_ctx* c = st->ctx;
     const int p = st->cur, q = p ^ 1;
     {
         StageScope sc(c, ST_STREAM_DSP, s);
-        if (rows) launch_stream_block_analysis_rows(c->tb, st->buf[p], st->buf[q], chunk, c->Xf, st->C, L, rows->active, s);
+        if (hops) launch_stream_block_analysis_hops(c->tb, st->buf[p], st->buf[q], chunk, c->Xf, st->C, L, hops->hops, st->row_frames, s);
+        else if (rows) launch_stream_block_analysis_rows(c->tb, st->buf[p], st->buf[q], chunk, c->Xf, st->C, L, rows->active, s);
         else launch_stream_block_analysis(c->tb, st->buf[p], st->buf[q], chunk, c->Xf, st->C, L, s);
     }
-    if (int rc = run_model(c, c->Xf, c->Yf, nullptr, st->C, L, st->state[p], st->state[q], s)) return rc;
+    if (int rc = run_model(c, c->Xf, c->Yf, nullptr, st->C, L, st->state[p], st->state[q], s, hops ? st->row_frames : nullptr)) return rc;
     {
         StageScope sc(c, ST_STREAM_DSP, s);
-        if (rows) launch_stream_block_synthesis_rows(c->tb, c->Yf, c->Xf, mix, rows->mix_rows, st->prev[p], st->prev[q], out, st->state[p], st->state[q], st->C,
+        if (hops) launch_stream_block_synthesis_hops(c->tb, c->Yf, c->Xf, mix, hops->mix_rows, st->prev[p], st->prev[q], out, st->state[p], st->state[q], st->C,
+                                                     c->K, L, hops->hops, s);
+        else if (rows) launch_stream_block_synthesis_rows(c->tb, c->Yf, c->Xf, mix, rows->mix_rows, st->prev[p], st->prev[q], out, st->state[p], st->state[q], st->C,
                                                      c->K, L, rows->active, s);
         else launch_stream_block_synthesis(c->tb, c->Yf, c->Xf, mix, st->prev[p], st->prev[q], out, st->C, L, s);
     }
@@ -2529,6 +2541,17 @@ int bsrnn_stream_reserve(bsrnn_stream* st, int32_t max_hops)
         last = L;
         rc = stream_block_run(st, tmp, tmp + nfl, L, 1.0f, nullptr);
         if (!rc) rc = stream_block_run(st, tmp, tmp + nfl, L, 0.5f, nullptr);
+        if (C <= STREAM_ROWS_MAX && L <= STREAM_HOPS_MAX) {      // ... and of the same plans as bsrnn_stream_process_hops runs them (the ragged time-axis kernels, the HopRows DSP pair)
+            HopArgs ha;
+            RowHopsInfo info;
+            std::vector<int32_t> cnt((size_t)C);
+            for (int r = 0; r < C; ++r) cnt[r] = L - (r & 1);
+            ha.mix_rows = nullptr;
+            if (pack_row_hops(cnt.data(), C, L, ha.hops, info) < 0) {
+                if (!rc) rc = stream_block_run(st, tmp, tmp + nfl, L, 1.0f, nullptr, nullptr, &ha);
+                if (!rc) rc = stream_block_run(st, tmp, tmp + nfl, L, 0.5f, nullptr, nullptr, &ha);
+            }
+        }
     }
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (!rc) rc = ovl_join_host(c);
@@ -2581,6 +2604,48 @@ int bsrnn_stream_process_rows(bsrnn_stream* st, const float* chunk, float* out, 
     // one hop: the step's kernels and its captured graph; more: the block path.  Both read carry set cur and write the other one, for
     // held rows too, so the re-run of the range policy starts from the untouched set with the same rows held.
     auto run = [&]() -> int { return n_hops == 1 ? stream_step_run(st, chunk, out, mix, s, &ra) : stream_block_run(st, chunk, out, n_hops, mix, s, &ra); };
+    if ((rc = run())) return rc;
+    if ((rc = finish_call(c, s, run))) return rc;
+    st->cur ^= 1;
+    return 0;
+}
+
+static_assert(BSRNN_STREAM_HOPS_MAX == STREAM_HOPS_MAX, "include/bsrnn_hip.h and stream_rows_host.h disagree");
+
+int bsrnn_stream_process_hops(bsrnn_stream* st, const float* chunk, float* out, int32_t n_hops, const int32_t* hops_host, const float* mix_rows,
+                              float mix, void* stream)
+{
+    if (n_hops < 1 || n_hops > STREAM_HOPS_MAX)
+        return fail(BSRNN_EARG, "bsrnn_stream_process_hops: n_hops = %d (1 to BSRNN_STREAM_HOPS_MAX = %d hops per call)", n_hops, STREAM_HOPS_MAX);
+    if (!st || !chunk || !out || !hops_host) return fail(BSRNN_EARG, "bsrnn_stream_process_hops: null argument");
+    if (st->C > STREAM_ROWS_MAX)
+        return fail(BSRNN_EARG, "bsrnn_stream_process_hops: the stream has %d rows, the rows calls take at most BSRNN_STREAM_ROWS_MAX = %d", st->C, STREAM_ROWS_MAX);
+    HopArgs ha;
+    RowHopsInfo info;
+    ha.mix_rows = mix_rows;
+    const int bad = pack_row_hops(hops_host, st->C, n_hops, ha.hops, info);      // (the caller's array is not looked at again, but for the delegation below)
+    if (bad >= 0) return fail(BSRNN_EARG, "bsrnn_stream_process_hops: row %d has %d hops, outside [0, n_hops = %d]", bad, hops_host[bad], n_hops);
+    bsrnn_ctx* c = st->ctx;
+    const size_t nb = (size_t)st->C * n_hops * HOPS * sizeof(float);
+    if (c->range_policy == BSRNN_RANGE_EXACT && ranges_overlap(chunk, nb, out, nb))
+        return fail(BSRNN_EARG, "bsrnn_stream_process_hops: out_dev must not overlap chunk_dev under the exact range policy (the re-run of a call that leaves the fp16 range reads chunk_dev again)");
+    if (ranges_overlap(mix_rows, (size_t)st->C * sizeof(float), chunk, nb) || ranges_overlap(mix_rows, (size_t)st->C * sizeof(float), out, nb))
+        return fail(BSRNN_EARG, "bsrnn_stream_process_hops: mix_rows_dev must overlap neither chunk_dev nor out_dev");
+    // every count 0 or n_hops (none at all included): the rows call itself, bit-identical by construction, one-hop graph path and all
+    if (info.all_or_none) {
+        std::vector<uint8_t> active((size_t)st->C);
+        for (int r = 0; r < st->C; ++r) active[r] = hops_host[r] != 0;
+        return bsrnn_stream_process_rows(st, chunk, out, n_hops, active.data(), mix_rows, mix, stream);
+    }
+    int rc = check_ready(c);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const size_t M = (size_t)st->C * n_hops;
+    if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M))) return rc;
+    // mixed counts always take the block path (n_hops >= 2 here); the re-run of the range policy repeats the masked analysis, the model and
+    // the masked synthesis from the untouched carry set with the same counts
+    auto run = [&]() -> int { return stream_block_run(st, chunk, out, n_hops, mix, s, nullptr, &ha); };
     if ((rc = run())) return rc;
     if ((rc = finish_call(c, s, run))) return rc;
     st->cur ^= 1;

@@ -512,9 +512,20 @@ void launch_from_frame_major(const FftTables& tb, const float* yf, float* y, int
 // read carry set to the written one - the analysis the buffer, the synthesis the previous frame and the row's LSTM state - and write zeros
 // where an active row's spectra and samples go.  A workgroup belongs to one row, so all of that is uniform over the workgroup, and it
 // returns before any barrier.  An active row runs the very code of the plain call.
-struct AllRows { static constexpr bool masked = false; };
+// HopRows (the two block kernels only) is the form of bsrnn_stream_process_hops: a hop count per row by value (stream_rows_host.h) in
+// place of the set.  Row r with n = hops[r] of the call's L hops: its frames / hops below n are the plain call's, those from n on are
+// zero spectra / zero samples, its carry is the one after n hops (the workgroup whose range holds frame n - 1 writes it), and n = 0 is a
+// held row.  The analysis also leaves n in row_frames[r] for the time-axis launches of the call (lstm.hip, the ragged instantiations).
+struct AllRows { static constexpr bool masked = false, ragged = false; };
+struct HopRows {
+    static constexpr bool masked = true, ragged = true;
+    RowHops hops;
+    const float* mix_rows;             // as HeldRows'
+    const float* state_in; float* state_out; int C, K;
+    int* row_frames;                   // [C] on the device (analysis only)
+};
 struct HeldRows {
-    static constexpr bool masked = true;
+    static constexpr bool masked = true, ragged = false;
     RowSet active;
     const float* mix_rows;             // [C] on the device, or null: the call's `mix` for every row
     // state [4][2][C*K][64]: row c owns the K*64 floats at (slab * C + c) * K * 64 of each of the eight slabs (multiples of 64 floats:
@@ -535,7 +546,8 @@ __device__ __forceinline__ void zero_hop(float* __restrict__ o, int tid)
 #pragma unroll
     for (int k = 0; k < 2; ++k) *reinterpret_cast<float2*>(o + 2 * (tid + 256 * k)) = make_float2(0.f, 0.f);
 }
-__device__ __forceinline__ void hold_state_row(const HeldRows& h, int c, int tid)
+template <class ROWS>
+__device__ __forceinline__ void hold_state_row(const ROWS& h, int c, int tid)
 {
     const int n4 = h.K * 16;                              // float4 per slab
     for (int i = tid; i < 8 * n4; i += 256) {
@@ -691,8 +703,16 @@ __global__ __launch_bounds__(256, FFT_OCC_STFT) void stream_block_analysis_kerne
     const int tid = threadIdx.x;
     const int r = blockIdx.y;
     const int l0 = blockIdx.x * sch;
-    const int l1 = (l0 + sch < L) ? l0 + sch : L;
-    if constexpr (ROWS::masked) {
+    int l1 = (l0 + sch < L) ? l0 + sch : L;
+    int n = L;                                                       // the frames the row advances by
+    if constexpr (ROWS::ragged) {
+        n = row_hops_of(rows.hops, r);
+        if (l0 == 0 && tid == 0) rows.row_frames[r] = n;
+        for (int l = l0 > n ? l0 : n; l < l1; ++l) zero_floats4(X + ((size_t)r * L + l) * tb.ld, tb.ld / 4, tid);
+        if (n == 0 && l0 == 0) copy_floats4(buf_in + (size_t)r * NFFT, buf_out + (size_t)r * NFFT, NFFT / 4, tid);
+        if (l0 >= n) return;                                         // (uniform over the workgroup, before any barrier)
+        if (l1 > n) l1 = n;
+    } else if constexpr (ROWS::masked) {
         if (!row_set_has(rows.active, r)) {
             for (int l = l0; l < l1; ++l) zero_floats4(X + ((size_t)r * L + l) * tb.ld, tb.ld / 4, tid);
             if (l1 == L) copy_floats4(buf_in + (size_t)r * NFFT, buf_out + (size_t)r * NFFT, NFFT / 4, tid);
@@ -710,13 +730,13 @@ __global__ __launch_bounds__(256, FFT_OCC_STFT) void stream_block_analysis_kerne
     auto row = [&](int l) { return X + ((size_t)r * L + l) * tb.ld; };
     const RawHalf last = stft_walk(tb, z0, z1, tid, l0, l1, sample2, row);
     // the workgroup that owns the last hop leaves the new carry: buf_out = S[L*1024 : L*1024 + 2048] = the last frame's samples (its
-    // first half is read again here instead of being kept through the loop; buf_out is another set than buf_in)
-    if (l1 == L) {
+    // first half is read again here instead of being kept through the loop; buf_out is another set than buf_in).  HopRows: n for L
+    if (l1 == n) {
         float* b = buf_out + (size_t)r * NFFT;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int c = tid + 256 * k;
-            *reinterpret_cast<float2*>(b + 2 * c) = sample2(L - 1, c);
+            *reinterpret_cast<float2*>(b + 2 * c) = sample2(n - 1, c);
             *reinterpret_cast<float2*>(b + HOPS + 2 * c) = last.v[k];   // the last frame's second half, as the walk left it
         }
     }
@@ -738,7 +758,20 @@ __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void stream_block_synthesis_ker
     __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
     const int tid = threadIdx.x;
     float mix = mix_all;
-    if constexpr (ROWS::masked) {
+    int n = L;                                                       // the hops the row advances by
+    if constexpr (ROWS::ragged) {
+        const int r = blockIdx.y;
+        n = row_hops_of(rows.hops, r);
+        const int b0 = blockIdx.x * ich;
+        const int b1 = (b0 + ich < L) ? b0 + ich : L;
+        for (int b = b0 > n ? b0 : n; b < b1; ++b) zero_hop(out + ((size_t)r * L + b) * HOPS, tid);
+        if (n == 0 && blockIdx.x == 0) {
+            copy_floats4(prev_in + (size_t)r * NFFT, prev_out + (size_t)r * NFFT, NFFT / 4, tid);
+            hold_state_row(rows, r, tid);
+        }
+        if (b0 >= n) return;                                         // (uniform over the workgroup, before any barrier)
+        if (MIX && rows.mix_rows) mix = rows.mix_rows[r];
+    } else if constexpr (ROWS::masked) {
         const int r = blockIdx.y;
         if (!row_set_has(rows.active, r)) {
             const int b0 = blockIdx.x * ich;
@@ -757,7 +790,7 @@ __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void stream_block_synthesis_ker
     const SplitCtx spl = load_split(tb, tid, true);
     const int r = blockIdx.y;
     const int b0 = blockIdx.x * ich;
-    const int b1 = (b0 + ich < L) ? b0 + ich : L;                    // output hops [b0, b1) <- frames b0 - 1 .. b1 - 1
+    const int b1 = (b0 + ich < n) ? b0 + ich : n;                    // output hops [b0, b1) <- frames b0 - 1 .. b1 - 1 (n = L but for HopRows)
     const float sc = 1.0f / 1024.0f;
     const float dry = mix >= 0.f ? 1.f - mix : 1.f;
     float2 wsum[2], carry[2];
@@ -815,7 +848,7 @@ __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void stream_block_synthesis_ker
     for (int t = b0; t < b1; ++t) frame(t, std::false_type());
     // the workgroup that owns the last hop leaves the whole last frame as the new carry, in the one-hop kernel's layout (fft1024 ends
     // in z1, which nothing has touched since the last frame)
-    if (b1 == L) {
+    if (b1 == n) {
         float* pv = prev_out + (size_t)r * NFFT;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -853,6 +886,24 @@ void launch_stream_block_synthesis_rows(const FftTables& tb, const float* Y, con
     const Chunks ch = chunks_for<stream_block_synthesis_kernel<false, HeldRows>>(L, C, 1);
     if (!mix_rows && mix == 1.f) hipLaunchKernelGGL((stream_block_synthesis_kernel<false, HeldRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
     else hipLaunchKernelGGL((stream_block_synthesis_kernel<true, HeldRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
+}
+
+// bsrnn_stream_process_hops: row r advances by row_hops_of(hops, r) of the L hops; the analysis leaves the counts in row_frames [C]
+void launch_stream_block_analysis_hops(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L,
+                                       const RowHops& hops, int* row_frames, hipStream_t s)
+{
+    const Chunks ch = chunks_for<stream_block_analysis_kernel<HopRows>>(L, C, 0);
+    hipLaunchKernelGGL(stream_block_analysis_kernel<HopRows>, ch.grid, dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, L, ch.len,
+                       HopRows{hops, nullptr, nullptr, nullptr, C, 0, row_frames});
+}
+void launch_stream_block_synthesis_hops(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
+                                        float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, int L,
+                                        const RowHops& hops, hipStream_t s)
+{
+    const HopRows rows{hops, mix_rows, state_in, state_out, C, K, nullptr};
+    const Chunks ch = chunks_for<stream_block_synthesis_kernel<false, HopRows>>(L, C, 1);
+    if (!mix_rows && mix == 1.f) hipLaunchKernelGGL((stream_block_synthesis_kernel<false, HopRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
+    else hipLaunchKernelGGL((stream_block_synthesis_kernel<true, HopRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
 }
 
 // ------------------------------------------------------------------------------ offline DSP, one segment of a clip

@@ -152,7 +152,11 @@ int lstm_mode();
 void launch_time_lstm(const float* zin, float* hout, const float* wpk, const void* wpk16, const float* bias,
                       const float* state_in, float* state_out, int R, int T, int K, int* range_flag, hipStream_t stream,
                       bool f32, int seqs, const void* fc16 = nullptr, const float* fcb = nullptr, const float* part = nullptr,
-                      const OvlProducer* ovl = nullptr);   // ovl: with fc16 / fcb / part only (the fused launch of the parts flow)
+                      const OvlProducer* ovl = nullptr,    // ovl: with fc16 / fcb / part only (the fused launch of the parts flow)
+                      const int* row_frames = nullptr);
+//   row_frames (optional) [R] on the device: the ragged instantiations (bsrnn_stream_process_hops) - state_out holds the state of row
+//         r's sequences after step row_frames[r] - 1 instead of after step T - 1 (anything for a row at 0); all T steps are still run
+//         and published, and hout is unspecified but finite from a row's count on
 
 // ------------------------------------------------------------------ training step, part 1: recurrent layers (lstm_train.hip)
 // One nn.LSTM layer (bsrnn.py:66-72) with ndir directions over N sequences of L steps, exact fp32; weights in torch layout
@@ -298,6 +302,15 @@ void launch_stream_block_analysis_rows(const FftTables& tb, const float* buf_in,
 void launch_stream_block_synthesis_rows(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
                                         float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, int L,
                                         const RowSet& active, hipStream_t s);
+// The two block launches for a call in which every row advances by its own number of hops (bsrnn_stream_process_hops; the counts travel
+// by value, stream_rows_host.h): row r with n = row_hops_of(hops, r) - frames / hops below n as the plain launches give them, zero rows
+// of X / zeros of out from n on, chunk unread from n * 1024 on, buf_out / prev_out the carry after n hops; n = 0 is a held row.  The
+// analysis writes row_frames[r] = n ([C] on the device) for the call's time-axis launches (launch_time_lstm).
+void launch_stream_block_analysis_hops(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L,
+                                       const RowHops& hops, int* row_frames, hipStream_t s);
+void launch_stream_block_synthesis_hops(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
+                                        float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, int L,
+                                        const RowHops& hops, hipStream_t s);
 // zeroes buf, prev and state of the rows in `rows` of one carry set, in one launch (bsrnn_stream_reset_rows)
 void launch_stream_reset_rows(float* buf, float* prev, float* state, int C, int K, const RowSet& rows, hipStream_t s);
 

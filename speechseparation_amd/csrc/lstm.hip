@@ -645,10 +645,19 @@ int lstm_mode()
 constexpr int TCH = 8;        // x steps staged per chunk
 constexpr int TS = HID + 4;   // LDS row stride (68 floats: 4 rows hit 4 distinct b128 slots)
 
+// RAGGED (here and in the two fp16x2 kernels below; bsrnn_stream_process_hops): row_frames [R] holds a step count per row, and
+// state_out receives the state of a sequence after step row_frames[n / K] - 1 instead of after step T - 1.  All T steps still run (the
+// steps from a row's count on belong to frames of zero spectra whose output nobody reads), so the launch's shape, its progress words
+// and every other instantiation are what they were.  Sequences of one workgroup can belong to different rows (K = 42 with four, K = 12
+// with eight of them): the count is per sequence.  Here the kept state is a SNAPSHOT - hsel / csel take the cell's values only while t
+// is below the count, off the dependency chain.  The four-sequence kernel has no register for a second (h, c): it STORES the state at
+// the step that is the sequence's last counted one, and nothing at the end.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(512) void time_lstm_kernel(const float* __restrict__ zin, float* __restrict__ hout,
                                                         const float* __restrict__ wpk, const float* __restrict__ bias,
                                                         const float* __restrict__ state_in, float* __restrict__ state_out,
-                                                        int R, int T, int K, unsigned long long* __restrict__ dbg)
+                                                        int R, int T, int K, unsigned long long* __restrict__ dbg,
+                                                        const int* __restrict__ row_frames = nullptr)
 {
     __shared__ __attribute__((aligned(16))) float xbuf[2][TCH][4 * TS];
     __shared__ __attribute__((aligned(16))) float h0buf[2][4 * TS];
@@ -704,6 +713,8 @@ __global__ __launch_bounds__(512) void time_lstm_kernel(const float* __restrict_
     chunk_store(0, chunk_load(0));
     float4 xnext = make_float4(0.f, 0.f, 0.f, 0.f);
     float hsel = 0.f, csel = 0.f;
+    int len = T;
+    if constexpr (RAGGED) len = row_frames[nj / K];
     __syncthreads();
 
     // Gate accumulators (4 independent MFMA chains).  Both layer-groups run the same phase order in
@@ -740,11 +751,11 @@ __global__ __launch_bounds__(512) void time_lstm_kernel(const float* __restrict_
         const float gg = fast_tanh(gsum[2]);
         const float og = fast_sigmoid(gsum[3]);
         c = fg * c + ig * gg;
-        hsel = og * fast_tanh(c);
-        csel = c;
+        const float hnew = og * fast_tanh(c);
+        if (!RAGGED || t < len) { hsel = hnew; csel = c; }
         float* hb = layer ? h1buf[t & 1] : h0buf[t & 1];
-        hb[j * TS + unit] = hsel;
-        if (layer && nj_raw < N) hout[base_j + (size_t)t * tstride + unit] = hsel;
+        hb[j * TS + unit] = hnew;
+        if (layer && nj_raw < N) hout[base_j + (size_t)t * tstride + unit] = hnew;
     };
     // measurement only (dbg != nullptr): 100 MHz stamps per phase, accumulated per wave
     unsigned long long tp[4] = {0, 0, 0, 0}, tq = 0;
@@ -861,13 +872,14 @@ __device__ __forceinline__ void lds_arrive(int* cnt, int lane)
 // PART: the block's input is not zin alone but zin + part[.., 0:64] + part[.., 64:128] - the residual and the two directions' shares
 // of the preceding band block's fc (band_lstm_h2_kernel<128, ., true> wrote them, [sequence-position][2][64]); the staging wave adds
 // them on the way into LDS and the fc wave adds the same three rows as ITS residual, so that block's fc launch does not exist.
-template <bool FUSE, bool TRACE = false, bool PART = false>
+template <bool FUSE, bool TRACE = false, bool PART = false, bool RAGGED = false>
 __global__ __launch_bounds__(1024) void time_lstm_h2w_kernel(const float* __restrict__ zin, float* __restrict__ hout,
                                                              const uint4* __restrict__ wpk, const float* __restrict__ bias,
                                                              const uint4* __restrict__ wfc, const float* __restrict__ bfc,
                                                              const float* __restrict__ state_in, float* __restrict__ state_out,
                                                              int R, int T, int K, int* __restrict__ range_flag, unsigned long long* __restrict__ dbg,
-                                                             const float* __restrict__ part = nullptr, int* ovl_resident = nullptr, int* ovl_prog = nullptr, int ovl_base = 0)
+                                                             const float* __restrict__ part = nullptr, int* ovl_resident = nullptr, int* ovl_prog = nullptr, int ovl_base = 0,
+                                                             const int* __restrict__ row_frames = nullptr)
 {
     unsigned long long tp[4] = {0, 0, 0, 0}, tq = 0;          // measurement only
     auto stamp = [&](int k) { if (TRACE) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); tp[k] += now - tq; tq = now; } };
@@ -876,7 +888,7 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w_kernel(const float* __rest
     __shared__ __attribute__((aligned(16))) _Float16 h1pl[H1RING * TSTEP];     // h1_t in slot t & 15
     __shared__ __attribute__((aligned(16))) float pinb[2 * 2 * 4 * 4 * 256];   // [layer][group parity][step in group][gate][cell]: bias + input half
     __shared__ __attribute__((aligned(16))) uint4 wflds[FUSE ? 4 * 4 * 64 : 1];
-    __shared__ int sync[SY_COUNT];            // the counters (and the abort word) of lds_wait_ge / lds_arrive
+    __shared__ int sync[SY_COUNT + (RAGGED ? 4 : 0)];   // the counters (and the abort word) of lds_wait_ge / lds_arrive; RAGGED: the four sequences' step counts
     __shared__ float hb_lds[PART ? 512 : 1];  // PART: the helpers' biases [layer][gate][unit]
     __shared__ int outc[8];                   // overlapped dual path: storing waves that have drained group f, in slot f & 7 (monotonic: 4 per use)
 
@@ -901,6 +913,9 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w_kernel(const float* __rest
     const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
     if (tid < SY_COUNT) sync[tid] = 0;
     if (tid >= 64 && tid < 72) outc[tid - 64] = 0;
+    if constexpr (RAGGED) {
+        if (tid >= 72 && tid < 76) { const int v = n0 + tid - 72; sync[SY_COUNT + tid - 72] = row_frames[(v < N ? v : N - 1) / K]; }
+    }
     // overlapped dual path (kernels.h, OvlProducer): this workgroup is on the chip - the launch that consumes its output is let go when all are
     if (PART && tid == 0 && ovl_resident) __hip_atomic_fetch_add(ovl_resident, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (system scope: from when a command-processor wait polled this word)
     if (TRACE) tq = __builtin_amdgcn_s_memrealtime();
@@ -1261,18 +1276,30 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w_kernel(const float* __rest
             const float gg = fast_tanh(pin_g + (hi[2][0] + (hi[2][1] + lo[2][0]) * (1.f / 2048.f)));
             const float og = fast_sigmoid(pin_o + (hi[3][0] + (hi[3][1] + lo[3][0]) * (1.f / 2048.f)));
             c = fg * c + ig * gg;
-            hsel = og * fast_tanh(c);
+            const float hnew = og * fast_tanh(c);
+            hsel = hnew;
             csel = c;
+            if constexpr (RAGGED) {
+                // the state leaves at the sequence's last counted step (the lane's coordinates again, from the lane counter: this kernel
+                // has no register to keep anything more across the step loop - neither a second copy of (h, c) nor the count)
+                const int le = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                const int ne = n0 + (le >> 4);
+                if (t + 1 == sync[SY_COUNT + (le >> 4)] && state_out && ne < N) {
+                    const int ue = 16 * w4 + (le & 15);
+                    state_out[((size_t)layer * N + ne) * HID + ue] = hnew;
+                    state_out[((size_t)(2 + layer) * N + ne) * HID + ue] = c;
+                }
+            }
             _Float16 p0, p1;
-            split_h2(hsel, p0, p1);
+            split_h2(hnew, p0, p1);
             _Float16* hb = &ring[(t & rmask) * TSTEP];
             hb[hoff] = p0;
             hb[4 * HID + hoff] = p1;
             lds_arrive(&sync[my_done], lane);
-            if (!FUSE && layer && nq_raw < N) hout[base_q + (size_t)t * tstride + unit] = hsel;
+            if (!FUSE && layer && nq_raw < N) hout[base_q + (size_t)t * tstride + unit] = hnew;
             stamp(0);
         }
-        if (state_out && nq_raw < N) {
+        if (!RAGGED && state_out && nq_raw < N) {
             state_out[((size_t)layer * N + nq) * HID + unit] = hsel;           // h_{T-1}
             state_out[((size_t)(2 + layer) * N + nq) * HID + unit] = csel;     // c_{T-1}
         }
@@ -1292,13 +1319,17 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w_kernel(const float* __rest
 // =====================================================================================
 constexpr int TCH8 = 4, RING8 = 8;
 constexpr int TSTEP8 = 2 * 8 * HID + 32;      // halves per step slot: two pieces of [8][8][8] + 64 bytes of skew
-template <bool FUSE, bool TRACE = false, bool PART = false>
+// RAGGED (time_lstm_kernel's comment): here the kept state is FROZEN - from a sequence's count on, c and the kept h take no new value -
+// which needs no register beyond the two cells' own; the eight counts live in LDS behind the counters (sync[SY_COUNT ..]) and are read
+// per step, since nothing of the prologue's index math stays live across the step loop.
+template <bool FUSE, bool TRACE = false, bool PART = false, bool RAGGED = false>
 __global__ __launch_bounds__(1024) void time_lstm_h2w8_kernel(const float* __restrict__ zin, float* __restrict__ hout,
                                                              const uint4* __restrict__ wpk, const float* __restrict__ bias,
                                                              const uint4* __restrict__ wfc, const float* __restrict__ bfc,
                                                              const float* __restrict__ state_in, float* __restrict__ state_out,
                                                              int R, int T, int K, int* __restrict__ range_flag, unsigned long long* __restrict__ dbg,
-                                                             const float* __restrict__ part = nullptr, int* ovl_resident = nullptr, int* ovl_prog = nullptr, int ovl_base = 0)
+                                                             const float* __restrict__ part = nullptr, int* ovl_resident = nullptr, int* ovl_prog = nullptr, int ovl_base = 0,
+                                                             const int* __restrict__ row_frames = nullptr)
 {
     unsigned long long tp[4] = {0, 0, 0, 0}, tq = 0;          // measurement only
     auto stamp = [&](int k) { if (TRACE) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); tp[k] += now - tq; tq = now; } };
@@ -1307,7 +1338,7 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w8_kernel(const float* __res
     __shared__ __attribute__((aligned(16))) _Float16 h1pl[RING8 * TSTEP8];     // h1_t in slot t & 7
     __shared__ __attribute__((aligned(16))) float pinb[2 * 2 * 2 * 4 * 512];   // [layer][group parity][step in group][gate][cell]: bias + input half
     __shared__ __attribute__((aligned(16))) uint4 wflds[FUSE ? 4 * 4 * 64 : 1];
-    __shared__ int sync[SY_COUNT];            // the counters (and the abort word) of lds_wait_ge / lds_arrive
+    __shared__ int sync[SY_COUNT + (RAGGED ? 8 : 0)];   // the counters (and the abort word) of lds_wait_ge / lds_arrive; RAGGED: the eight sequences' step counts
     __shared__ float hb_lds[512];            // PART: the helpers' biases [layer][gate][unit]
     __shared__ __attribute__((aligned(16))) uint4 wsp[8 * 64];      // one W_ih fragment of every helper wave (the two cells' index math took its registers)
     __shared__ int outc[8];                   // overlapped dual path: storing waves that have drained group f, in slot f & 7 (monotonic: 4 per use)
@@ -1335,6 +1366,9 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w8_kernel(const float* __res
     const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
     if (tid < SY_COUNT) sync[tid] = 0;
     if (tid >= 64 && tid < 72) outc[tid - 64] = 0;
+    if constexpr (RAGGED) {
+        if (tid >= 72 && tid < 80) { const int v = n0 + tid - 72; sync[SY_COUNT + tid - 72] = row_frames[(v < N ? v : N - 1) / K]; }
+    }
     // overlapped dual path (kernels.h, OvlProducer): this workgroup is on the chip - the launch that consumes its output is let go when all are
     if (PART && tid == 0 && ovl_resident) __hip_atomic_fetch_add(ovl_resident, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (system scope: from when a command-processor wait polled this word)
     if (TRACE) tq = __builtin_amdgcn_s_memrealtime();
@@ -1697,16 +1731,26 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w8_kernel(const float* __res
             }
             // hi[g] = {a1 w1, a2 w1 | the same of the second cell}, lo[g] = {a1 w2, - | a1 w2, -} of this lane's two cells
             _Float16* hb = &ring[(t & rmask) * TSTEP8];
+            float hnow[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const float ig = fast_sigmoid(pin_i[j] + (hi[0][2 * j] + (hi[0][2 * j + 1] + lo[0][2 * j]) * (1.f / 2048.f)));
                 const float fg = fast_sigmoid(pin_f[j] + (hi[1][2 * j] + (hi[1][2 * j + 1] + lo[1][2 * j]) * (1.f / 2048.f)));
                 const float gg = fast_tanh(pin_g[j] + (hi[2][2 * j] + (hi[2][2 * j + 1] + lo[2][2 * j]) * (1.f / 2048.f)));
                 const float og = fast_sigmoid(pin_o[j] + (hi[3][2 * j] + (hi[3][2 * j + 1] + lo[3][2 * j]) * (1.f / 2048.f)));
-                c[j] = fg * c[j] + ig * gg;
-                hsel[j] = og * fast_tanh(c[j]);
+                const float cnew = fg * c[j] + ig * gg;
+                const float hnew = og * fast_tanh(cnew);
+                if constexpr (RAGGED) {
+                    const bool counts = t < sync[SY_COUNT + 2 * q + j];
+                    c[j] = counts ? cnew : c[j];
+                    hsel[j] = counts ? hnew : hsel[j];
+                } else {
+                    c[j] = cnew;
+                    hsel[j] = hnew;
+                }
+                hnow[j] = hnew;
                 _Float16 p0, p1;
-                split_h2(hsel[j], p0, p1);
+                split_h2(hnew, p0, p1);
                 hb[hoff + 8 * j] = p0;
                 hb[8 * HID + hoff + 8 * j] = p1;
             }
@@ -1714,7 +1758,7 @@ __global__ __launch_bounds__(1024) void time_lstm_h2w8_kernel(const float* __res
             if (!FUSE && layer) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
-                    if (nq_raw_of(j) < N) hout[base_of(j) + (size_t)t * tstride + unit] = hsel[j];
+                    if (nq_raw_of(j) < N) hout[base_of(j) + (size_t)t * tstride + unit] = hnow[j];
             }
             stamp(0);
         }
@@ -1907,11 +1951,40 @@ int device_cus()
 }
 void launch_time_lstm(const float* zin, float* hout, const float* wpk, const void* wpk16, const float* bias,
                       const float* state_in, float* state_out, int R, int T, int K, int* range_flag, hipStream_t stream,
-                      bool f32, int seqs, const void* fc16, const float* fcb, const float* part, const OvlProducer* ovl)
+                      bool f32, int seqs, const void* fc16, const float* fcb, const float* part, const OvlProducer* ovl, const int* row_frames)
 {
     const int N = R * K;
     if (N <= 0 || T <= 0) return;
     dim3 grid((N + 3) / 4), block(512), block16(1024);
+    if (row_frames) {
+        // The ragged instantiations (bsrnn_stream_process_hops): the same choice of kernel, grid and arguments as below, plus the counts
+        int* const res = ovl ? ovl->resident : (int*)nullptr;
+        int* const prog = ovl ? ovl->prog : (int*)nullptr;
+        const int base = ovl ? ovl->base : 0;
+        unsigned long long* const nodbg = nullptr;
+        const uint4* const w16 = (const uint4*)wpk16;
+        const uint4* const f16 = (const uint4*)fc16;
+        if (f32)
+            hipLaunchKernelGGL(time_lstm_kernel<true>, grid, block, 0, stream, zin, hout, wpk, bias, state_in, state_out, R, T, K, nodbg, row_frames);
+        else if (fc16 && fcb && seqs == 8) {
+            const dim3 grid8((N + 7) / 8);
+            if (part)
+                hipLaunchKernelGGL((time_lstm_h2w8_kernel<true, false, true, true>), grid8, block16, 0, stream, zin, hout, w16, bias, f16, fcb, state_in, state_out, R, T,
+                                   K, range_flag, nodbg, part, res, prog, base, row_frames);
+            else
+                hipLaunchKernelGGL((time_lstm_h2w8_kernel<true, false, false, true>), grid8, block16, 0, stream, zin, hout, w16, bias, f16, fcb, state_in, state_out, R, T,
+                                   K, range_flag, nodbg, (const float*)nullptr, (int*)nullptr, (int*)nullptr, 0, row_frames);
+        } else if (fc16 && fcb && part)
+            hipLaunchKernelGGL((time_lstm_h2w_kernel<true, false, true, true>), grid, block16, 0, stream, zin, hout, w16, bias, f16, fcb, state_in, state_out, R, T, K,
+                               range_flag, nodbg, part, res, prog, base, row_frames);
+        else if (fc16 && fcb)
+            hipLaunchKernelGGL((time_lstm_h2w_kernel<true, false, false, true>), grid, block16, 0, stream, zin, hout, w16, bias, f16, fcb, state_in, state_out, R, T, K,
+                               range_flag, nodbg, (const float*)nullptr, (int*)nullptr, (int*)nullptr, 0, row_frames);
+        else
+            hipLaunchKernelGGL((time_lstm_h2w_kernel<false, false, false, true>), grid, block16, 0, stream, zin, hout, w16, bias, (const uint4*)nullptr, (const float*)nullptr,
+                               state_in, state_out, R, T, K, range_flag, nodbg, (const float*)nullptr, (int*)nullptr, (int*)nullptr, 0, row_frames);
+        return;
+    }
     if (!f32) {
         // Eight sequences per workgroup (api.hip decides when: where four would need more than one round of workgroups, or BSRNN_TIME_SEQ8=1).
         // Results are bit-identical either way.
@@ -1938,8 +2011,8 @@ void launch_time_lstm(const float* zin, float* hout, const float* wpk, const voi
                                (const float*)nullptr, state_in, state_out, R, T, K, range_flag, (unsigned long long*)nullptr);
         return;
     }
-    hipLaunchKernelGGL(time_lstm_kernel, grid, block, 0, stream, zin, hout, wpk, bias, state_in, state_out, R, T, K,
-                       (unsigned long long*)nullptr);
+    hipLaunchKernelGGL(time_lstm_kernel<false>, grid, block, 0, stream, zin, hout, wpk, bias, state_in, state_out, R, T, K,
+                       (unsigned long long*)nullptr, (const int*)nullptr);
 }
 
 // Gate of the overlapped dual path (kernels.h): ONE wave that leaves when every workgroup of the time-axis launch on the other stream is

@@ -18,6 +18,16 @@ Each figure is the median over REPEATS windows of a host clock around enough job
 variants alternate inside every repeat, and min .. max of the windows is printed beside the median.
 
     python tools/stream_pool_bench.py [--baseline-lib PATH] [--out profiles/stream_rows_ab.txt]
+
+--hops times the hop count per row (bsrnn_stream_process_hops) instead of part 1, the same way (several hops per call here):
+  H1, the use case: the 64-row stream, 32 sessions of 2 rows whose counts are drawn from {1, 2, 3} (fixed seed).  (h) ONE process_hops
+      call per tick against (g) what a build without it needs for the same audio: one process_rows per distinct count, the sessions of
+      that count active.
+  H2, the cost of the ragged form: (h) process_hops with every row at 7 of 8 hops - mixed counts, so nothing delegates - against
+      (q) bsrnn_stream_process at 8 hops, C = 64, same process, alternating.
+  H3, the plain calls: part 2 above, this build against --baseline-lib.
+
+    python tools/stream_pool_bench.py --hops [--baseline-lib PATH] [--out profiles/stream_hops_ab.txt]
 """
 import argparse
 import ctypes
@@ -135,24 +145,11 @@ def plain_only():
         lib.bsrnn_stream_destroy(st)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--baseline-lib", default=None, help="another build of libbsrnn_hip.so (the parent commit's) for part 2")
-    ap.add_argument("--plain-only", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
-    if args.plain_only:
-        return plain_only()
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    # ---- part 2 first: child processes, before this one opens the GPU
+def plain_runs(baseline_lib):
+    """Part 2: child processes, before this one opens the GPU -> [(library, C, L, {variant: (median, min, max)})]."""
     runs = [("this build", None), ("this build", None)]
-    if args.baseline_lib:
-        base = os.path.abspath(args.baseline_lib)
+    if baseline_lib:
+        base = os.path.abspath(baseline_lib)
         assert os.path.exists(base), base
         runs = [("baseline", base), ("this build", None), ("baseline", base), ("this build", None)]
     part2 = []
@@ -170,6 +167,106 @@ def main():
                 f = ln.split()
                 vals = {f[i]: tuple(float(x) for x in f[i + 1:i + 4]) for i in range(3, len(f), 4)}
                 part2.append((name, int(f[1]), int(f[2]), vals))
+    return part2
+
+
+def report_plain(say, part2):
+    say("# part 2: C = 64, nothing held, each line a process of its own.  q = stream_process, r = stream_process_rows(active = ones, "
+        "mix_rows = NULL), f = the same with mix_rows = ones (row-masked kernels)")
+    say("%-11s %4s %4s %28s %28s %28s" % ("library", "C", "L", "q us", "r us", "f us"))
+    for name, Cc, L, vals in part2:
+        say("%-11s %4d %4d %28s %28s %28s" % (name, Cc, L, cell(vals["q"]), cell(vals["r"]) if "r" in vals else "-", cell(vals["f"]) if "f" in vals else "-"))
+    for Cc, L in PLAIN_SHAPES:
+        q = {n: [v["q"][0] for (nm, c2, l2, v) in part2 if nm == n and (c2, l2) == (Cc, L)] for n in ("baseline", "this build")}
+        spread = max(abs(v[0] - v[1]) for v in q.values() if len(v) == 2)
+        line = "C %d L %d: run-to-run spread of q (same library, two processes) %.1f us" % (Cc, L, spread)
+        if q["baseline"]:
+            line += "; q this build - q baseline (means of the two runs) %+.1f us" % (sum(q["this build"]) / 2 - sum(q["baseline"]) / 2)
+        rr = [v["r"][0] - v["q"][0] for (nm, c2, l2, v) in part2 if nm == "this build" and (c2, l2) == (Cc, L)]
+        line += "; r - q inside a run %s us" % ", ".join("%+.1f" % x for x in rr)
+        say(line)
+
+
+def hops_parts(say):
+    """H1 and H2 of --hops, in this process."""
+    import random
+    import torch
+    from speechseparation_amd import _native, weights
+    from speechseparation_amd.bsrnn import StreamingSeparator
+    lib, check = _native.lib, _native.check
+    model = setup()
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    one = ctypes.c_float(1.0)
+    C = SLOTS * ROWS
+    say("# %s, %s, compute mode %s" % (torch.cuda.get_device_name(0), torch.version.hip, _native.compute_mode()))
+    say("# us per call (or per tick): median [min .. max] of %d windows of ~%.1f s; inputs resident, deferred range policy" % (REPEATS, WINDOW_S))
+    wide = StreamingSeparator(model, channels=C, device="cuda:0")
+    wide.reserve(8)
+    rnd = random.Random(7)
+    per_session = [rnd.choice((1, 2, 3)) for _ in range(SLOTS)]
+    counts = [per_session[r // ROWS] for r in range(C)]
+    L = max(counts)
+    waves = {k: torch.from_numpy(weights.synth_waveform(C, k * HOP, seed=5)).cuda() for k in (1, 2, 3, 8)}
+    outs = {k: torch.empty_like(w) for k, w in waves.items()}
+    cnt = (ctypes.c_int32 * C)(*counts)
+    flags = {k: (ctypes.c_uint8 * C)(*[int(c == k) for c in counts]) for k in sorted(set(counts))}
+
+    def job_h():
+        check(lib.bsrnn_stream_process_hops(wide._h, ptr(waves[L]), ptr(outs[L]), L, cnt, None, one, None))
+
+    def job_g():
+        for k, fl in flags.items():
+            check(lib.bsrnn_stream_process_rows(wide._h, ptr(waves[k]), ptr(outs[k]), k, fl, None, one, None))
+
+    r = measure({"h": job_h, "g": job_g}, torch.cuda.synchronize)
+    model.sync()
+    say("# H1: %d-row stream, %d sessions of %d rows, counts from {1, 2, 3} (seed 7: %s sessions at 1 / 2 / 3 hops); per tick" % (
+        C, SLOTS, ROWS, " / ".join(str(per_session.count(k)) for k in (1, 2, 3))))
+    say("%-44s %28s" % ("h  one process_hops (L = %d)" % L, cell(r["h"])))
+    say("%-44s %28s" % ("g  one process_rows per distinct count (%d)" % len(flags), cell(r["g"])))
+    say("g / h = %.2f" % (r["g"][0] / r["h"][0]))
+    say("")
+    seven = (ctypes.c_int32 * C)(*([7] * C))
+
+    def job_h8():
+        check(lib.bsrnn_stream_process_hops(wide._h, ptr(waves[8]), ptr(outs[8]), 8, seven, None, one, None))
+
+    def job_q8():
+        check(lib.bsrnn_stream_process(wide._h, ptr(waves[8]), ptr(outs[8]), 8, one, None))
+
+    r = measure({"h": job_h8, "q": job_q8}, torch.cuda.synchronize)
+    model.sync()
+    say("# H2: C = %d, L = 8.  h = process_hops with every row at 7 hops (the ragged kernels), q = stream_process at 8 hops" % C)
+    say("%-44s %28s" % ("h  process_hops, all rows 7 of 8", cell(r["h"])))
+    say("%-44s %28s" % ("q  stream_process, 8 hops", cell(r["q"])))
+    say("h - q = %+.1f us (%.1f %%)" % (r["h"][0] - r["q"][0], 100.0 * (r["h"][0] / r["q"][0] - 1.0)))
+    say("")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--baseline-lib", default=None, help="another build of libbsrnn_hip.so (the parent commit's) for part 2")
+    ap.add_argument("--hops", action="store_true", help="time bsrnn_stream_process_hops (H1 - H3 above) instead of part 1")
+    ap.add_argument("--plain-only", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.plain_only:
+        return plain_only()
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    part2 = plain_runs(args.baseline_lib)
+    if args.hops:
+        hops_parts(say)
+        say("# H3 = part 2:")
+        report_plain(say, part2)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
 
     import torch
     from speechseparation_amd import _native, weights
@@ -212,20 +309,7 @@ def main():
         model.sync()
         say("%4d %28s %28s %28s %8.2f %8.2f" % (S, cell(r["a"]), cell(r["b"]), cell(r["p"]), r["b"][0] / r["a"][0], r["b"][0] / r["p"][0]))
     say("")
-    say("# part 2: C = 64, nothing held, each line a process of its own.  q = stream_process, r = stream_process_rows(active = ones, "
-        "mix_rows = NULL), f = the same with mix_rows = ones (row-masked kernels)")
-    say("%-11s %4s %4s %28s %28s %28s" % ("library", "C", "L", "q us", "r us", "f us"))
-    for name, Cc, L, vals in part2:
-        say("%-11s %4d %4d %28s %28s %28s" % (name, Cc, L, cell(vals["q"]), cell(vals["r"]) if "r" in vals else "-", cell(vals["f"]) if "f" in vals else "-"))
-    for Cc, L in PLAIN_SHAPES:
-        q = {n: [v["q"][0] for (nm, c2, l2, v) in part2 if nm == n and (c2, l2) == (Cc, L)] for n in ("baseline", "this build")}
-        spread = max(abs(v[0] - v[1]) for v in q.values() if len(v) == 2)
-        line = "C %d L %d: run-to-run spread of q (same library, two processes) %.1f us" % (Cc, L, spread)
-        if q["baseline"]:
-            line += "; q this build - q baseline (means of the two runs) %+.1f us" % (sum(q["this build"]) / 2 - sum(q["baseline"]) / 2)
-        rr = [v["r"][0] - v["q"][0] for (nm, c2, l2, v) in part2 if nm == "this build" and (c2, l2) == (Cc, L)]
-        line += "; r - q inside a run %s us" % ", ".join("%+.1f" % x for x in rr)
-        say(line)
+    report_plain(say, part2)
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")

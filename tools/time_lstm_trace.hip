@@ -20,7 +20,7 @@ int main()
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (int rep = 0; rep < 3; ++rep) {
         CK(hipEventRecord(e0, 0));
-        hipLaunchKernelGGL(time_lstm_kernel, dim3(R * K / 4), dim3(512), 0, 0, z, h, w, b, (const float*)nullptr, (float*)nullptr, R, T, K, rep == 2 ? dbg : nullptr);
+        hipLaunchKernelGGL(time_lstm_kernel<false>, dim3(R * K / 4), dim3(512), 0, 0, z, h, w, b, (const float*)nullptr, (float*)nullptr, R, T, K, rep == 2 ? dbg : nullptr, (const int*)nullptr);
         CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         printf("time_lstm launch %d: %.1f us\n", rep, ms * 1e3);
