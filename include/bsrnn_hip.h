@@ -533,6 +533,49 @@ int     bsrnn_resampler_process(bsrnn_resampler* r, const float* in_dev, int64_t
                                 float* out_dev, int64_t out_stride, int64_t* n_out_host, void* stream);
 int     bsrnn_resampler_flush(bsrnn_resampler* r, float* out_dev, int64_t out_stride, int64_t* n_out_host, void* stream);
 
+/* ---- a bank of streaming resamplers: a rate pair, a block length and a stream position PER ROW ----
+ * A bsrnn_resampler has one rate pair and moves all its rows in lock step.  A bsrnn_resampler_bank holds C rows that each sit on one of up
+ * to BSRNN_BANK_PAIRS_MAX declared rate pairs, at their own place in their own stream, and converts all of them in ONE launch-bound call:
+ * what a pool of live sessions at 8, 16, 32, 48 and 96 kHz needs in front of and behind one bsrnn_stream_process_hops (one bank into the
+ * model's 44.1 kHz, one out of it), instead of two bsrnn_resampler calls per session.
+ * DEFINITION: row r of a bank IS a one-row bsrnn_resampler of r's pair.  Counts and samples are equal value for value - the same kernel
+ * code forms an output sample from the same taps in the same order - so the concatenated outputs of a row, flush included, equal
+ * bsrnn_resample of the row's concatenated input.
+ * Limits (BSRNN_EARG, the text names the value; answered before anything touches a device): a null object; a row outside [0, C) or listed
+ * twice; a pair outside [0, n_pairs); n_pairs outside [1, BSRNN_BANK_PAIRS_MAX]; a rate pair bsrnn_resample would refuse; a count < 0, or
+ * more than 2^30 samples into or out of one row in one call; in_stride below the largest count given; out_stride below the largest count
+ * written; out_dev overlapping the span of in_dev.
+ *   bsrnn_resampler_bank_create does all first-use work - the tables of all declared pairs (shared with the context's other resampling
+ *     calls), the carry (two sets of C x cap floats, cap the largest carry of the declared pairs), the pair table on the device, kernel
+ *     loading; every other call allocates nothing (bsrnn_debug_counter(0) unchanged).  All rows start on pair 0 at the beginning of a
+ *     stream.  Lifetime against bsrnn_destroy as a bsrnn_resampler's.
+ *   bsrnn_resampler_bank_assign: the listed rows move to declared pair `pair` and start a new stream there.  _reset_rows: the listed rows
+ *     start a new stream on the pair they have.  Both are host-only (nothing is enqueued: with no input taken a row's carry holds no sample
+ *     a call would read).  _pair_of: a row's pair, -1 for a null object or a row outside [0, C).
+ *   bsrnn_resampler_bank_ready: the count the next _process would report for `row` if it gave the row n_in samples; -1 for a null object, a
+ *     row outside [0, C) or n_in < 0.
+ *   bsrnn_resampler_bank_process: row r reads its first n_in_host[r] samples of in_dev [C rows, in_stride apart] and nothing behind them;
+ *     a count of 0 HOLDS the row - nothing of it is read or written, its carry stays.  Each row gets exactly the outputs that have
+ *     become determined, out_dev[r][0 .. n_out_host[r]), and nothing behind them is written; the counts are host arithmetic, reported
+ *     without synchronising.  Enqueues and returns: the per-row descriptors travel by value in the kernel arguments, so n_in_host and
+ *     n_out_host are the caller's own again at return.  One launch per 179 rows.
+ *   bsrnn_resampler_bank_flush_rows: the listed rows get what they are still owed - up to ceil(N * up / down) for the N samples a row
+ *     took, the future counting as zeros - and are left at the beginning of a stream; the other rows are untouched and report 0.
+ *   A bank call counts as a call on the context (concurrency contract above). */
+#define BSRNN_BANK_PAIRS_MAX 16
+typedef struct bsrnn_resampler_bank bsrnn_resampler_bank;
+int     bsrnn_resampler_bank_create(bsrnn_ctx* ctx, int32_t C, const int32_t* rates_in_host, const int32_t* rates_out_host,
+                                    int32_t n_pairs, bsrnn_resampler_bank** out);
+void    bsrnn_resampler_bank_destroy(bsrnn_resampler_bank* b);
+int     bsrnn_resampler_bank_assign(bsrnn_resampler_bank* b, const int32_t* rows_host, int32_t n_rows, int32_t pair);
+int     bsrnn_resampler_bank_pair_of(const bsrnn_resampler_bank* b, int32_t row);
+int64_t bsrnn_resampler_bank_ready(const bsrnn_resampler_bank* b, int32_t row, int64_t n_in);
+int     bsrnn_resampler_bank_process(bsrnn_resampler_bank* b, const float* in_dev, int64_t in_stride, const int64_t* n_in_host,
+                                     float* out_dev, int64_t out_stride, int64_t* n_out_host, void* stream);
+int     bsrnn_resampler_bank_flush_rows(bsrnn_resampler_bank* b, const int32_t* rows_host, int32_t n_rows,
+                                        float* out_dev, int64_t out_stride, int64_t* n_out_host, void* stream);
+int     bsrnn_resampler_bank_reset_rows(bsrnn_resampler_bank* b, const int32_t* rows_host, int32_t n_rows);
+
 /* ---- measurement support ---------------------------------------------------------------
  * bsrnn_set_profiling(ctx, mask): bit i of `mask` brackets stage i of every compute call with
  * hipEvents on the call's stream (mask < 0 = all stages, 0 = off; each bracket costs ~10 us of

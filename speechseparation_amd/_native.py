@@ -29,10 +29,13 @@ SYMBOLS = [
     "bsrnn_stream_process_rows", "bsrnn_stream_process_hops", "bsrnn_stream_reset_rows", "bsrnn_stream_row_floats", "bsrnn_stream_get_row", "bsrnn_stream_set_row",
     "bsrnn_resample_len", "bsrnn_resample", "bsrnn_resampler_create", "bsrnn_resampler_destroy", "bsrnn_resampler_reset",
     "bsrnn_resampler_ready", "bsrnn_resampler_process", "bsrnn_resampler_flush",
+    "bsrnn_resampler_bank_create", "bsrnn_resampler_bank_destroy", "bsrnn_resampler_bank_assign", "bsrnn_resampler_bank_pair_of",
+    "bsrnn_resampler_bank_ready", "bsrnn_resampler_bank_process", "bsrnn_resampler_bank_flush_rows", "bsrnn_resampler_bank_reset_rows",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
 STREAM_HOPS_MAX = 255                       # BSRNN_STREAM_HOPS_MAX
+BANK_PAIRS_MAX = 16                         # BSRNN_BANK_PAIRS_MAX
 METRIC_NAMES = ("loss", "sdr", "input_sdr", "sisdr", "l1_time", "l1_re", "l1_im", "separation_db")   # BSRNN_M_* order
 
 
@@ -118,6 +121,14 @@ def _load():
         "bsrnn_resampler_ready": (i64, [vp, i64]),
         "bsrnn_resampler_process": (C.c_int, [vp, vp, i64, i64, vp, i64, C.POINTER(i64), vp]),
         "bsrnn_resampler_flush": (C.c_int, [vp, vp, i64, C.POINTER(i64), vp]),
+        "bsrnn_resampler_bank_create": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(vp)]),
+        "bsrnn_resampler_bank_destroy": (None, [vp]),
+        "bsrnn_resampler_bank_assign": (C.c_int, [vp, C.POINTER(i32), i32, i32]),
+        "bsrnn_resampler_bank_pair_of": (C.c_int, [vp, i32]),
+        "bsrnn_resampler_bank_ready": (i64, [vp, i32, i64]),
+        "bsrnn_resampler_bank_process": (C.c_int, [vp, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), vp]),
+        "bsrnn_resampler_bank_flush_rows": (C.c_int, [vp, C.POINTER(i32), i32, vp, i64, C.POINTER(i64), vp]),
+        "bsrnn_resampler_bank_reset_rows": (C.c_int, [vp, C.POINTER(i32), i32]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),
         "bsrnn_stage_name": (C.c_char_p, [i32]),

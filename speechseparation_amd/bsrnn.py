@@ -14,6 +14,7 @@ called -- all arithmetic happens in hand-written HIP kernels behind the C ABI, a
 the built library this module cannot be imported (no CPU fallback).
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -994,13 +995,196 @@ class Resampler:
         self._taken = self._given = 0
 
 
-class StreamPool:
+def _check_pairs(pairs, who):
+    """[(rate_in, rate_out), ...] as ints, or ValueError for what bsrnn_resampler_bank_create refuses (no device needed)."""
+    try:
+        pairs = [(int(a), int(b)) for a, b in pairs]
+    except (TypeError, ValueError):
+        raise ValueError("%s: pairs must be a sequence of (rate_in, rate_out), got %r" % (who, pairs)) from None
+    if not 1 <= len(pairs) <= _native.BANK_PAIRS_MAX:
+        raise ValueError("%s: %d rate pairs, a bank takes 1 to %d" % (who, len(pairs), _native.BANK_PAIRS_MAX))
+    for a, b in pairs:
+        resample_len(1, a, b)
+    return pairs
+
+
+class ResamplerBank:
+    """Streaming sample-rate conversion for rows that do NOT share a rate or a clock (bsrnn_resampler_bank_*): every row sits on one of
+    the declared `pairs` [(rate_in, rate_out), ...] (at most 16), at its own place in its own stream, and one process() converts whatever
+    each row brings - in one launch-bound library call.  Row r equals a one-row Resampler of r's pair value for value.  All rows start
+    on pairs[0]."""
+
+    def __init__(self, model, channels, pairs):
+        self.pairs = _check_pairs(pairs, "ResamplerBank")
+        if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or channels < 1:
+            raise ValueError("ResamplerBank: channels must be a positive int, got %r" % (channels,))
+        self.model = model
+        self.C = int(channels)
+        self.device = torch.device("cuda", model._ctx_device if model._ctx_device is not None else torch.cuda.current_device())
+        n = len(self.pairs)
+        with torch.cuda.device(self.device):
+            ctx = model._context(self.device)
+            h = ctypes.c_void_p()
+            _check(_lib.bsrnn_resampler_bank_create(ctx, self.C, (ctypes.c_int32 * n)(*[p[0] for p in self.pairs]),
+                                                    (ctypes.c_int32 * n)(*[p[1] for p in self.pairs]), n, ctypes.byref(h)))
+        self._h = h
+        # the library's per-row counters and pairs, mirrored to size the results before the calls
+        self._taken, self._given, self._pair = [0] * self.C, [0] * self.C, [0] * self.C
+        self._ratio = []                    # per pair: up, down, half (csrc/resample_host.h, resample_ratio)
+        for a, b in self.pairs:
+            g = math.gcd(a, b)
+            self._ratio.append((b // g, a // g, 10 * max(a // g, b // g)))
+
+    def __del__(self):
+        try:
+            _lib.bsrnn_resampler_bank_destroy(self._h)
+        except Exception:
+            pass
+
+    def _rows(self, rows, who):
+        try:
+            rows = list(rows)
+        except TypeError:
+            raise ValueError("ResamplerBank.%s: rows must be a sequence of ints, got %s" % (who, type(rows).__name__)) from None
+        for r in rows:
+            if isinstance(r, bool) or not isinstance(r, (int, np.integer)):
+                raise ValueError("ResamplerBank.%s: a row must be an int, got %s" % (who, type(r).__name__))
+            if not 0 <= r < self.C:
+                raise ValueError("ResamplerBank.%s: row %d is outside [0, %d)" % (who, r, self.C))
+        if len(set(rows)) != len(rows):
+            raise ValueError("ResamplerBank.%s: a row is listed twice in %s" % (who, rows))
+        return [int(r) for r in rows], (ctypes.c_int32 * len(rows))(*rows)
+
+    def pair_of(self, row):
+        return self._pair[self._rows([row], "pair_of")[0][0]]
+
+    def assign(self, rows, pair):
+        """The listed rows move to pairs[pair] and start a new stream there (host only)."""
+        if isinstance(pair, bool) or not isinstance(pair, (int, np.integer)) or not 0 <= pair < len(self.pairs):
+            raise ValueError("ResamplerBank.assign: pair %r is outside [0, %d)" % (pair, len(self.pairs)))
+        rows, arr = self._rows(rows, "assign")
+        _check(_lib.bsrnn_resampler_bank_assign(self._h, arr, len(rows), int(pair)))
+        for r in rows:
+            self._taken[r] = self._given[r] = 0
+            self._pair[r] = int(pair)
+
+    def reset_rows(self, rows):
+        """The listed rows forget their stream so far and start a new one on the pair they have (host only)."""
+        rows, arr = self._rows(rows, "reset_rows")
+        _check(_lib.bsrnn_resampler_bank_reset_rows(self._h, arr, len(rows)))
+        for r in rows:
+            self._taken[r] = self._given[r] = 0
+
+    def ready(self, row, n):
+        """Samples the next process() would return for `row` if it gave the row n samples."""
+        row = self._rows([row], "ready")[0][0]
+        return int(_lib.bsrnn_resampler_bank_ready(self._h, row, int(n)))
+
+    def _ready(self, r, n):
+        # ready() from the mirrored counters, without a library call per row: the outputs whose last input, floor((j * down + half) / up),
+        # has arrived (csrc/resample_host.h, resample_ready).  process() holds the library's own counts against it.
+        up, down, half = self._ratio[self._pair[r]]
+        N = self._taken[r] + n
+        a = N * up - half - 1
+        return (0 if N < 1 or a < 0 else min(a // down + 1, -(-N * up // down))) - self._given[r]
+
+    def process(self, wave, counts):
+        """wave [C, n] float32 on the bank's device and counts, C ints in [0, n] -> (tensor [C, max count out], the counts out as a list):
+        row r reads its first counts[r] samples and nothing behind them, and gets the outputs that have become determined in
+        out[r, :counts_out[r]]; what lies behind them in the tensor is unspecified.  A count of 0 holds the row."""
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != self.C:
+            raise ValueError("ResamplerBank.process: expected wave [C = %d, n], got %s" % (
+                self.C, tuple(wave.shape) if isinstance(wave, torch.Tensor) else type(wave).__name__))
+        if wave.dtype != torch.float32 or wave.device != self.device:
+            raise ValueError("ResamplerBank.process: expected a float32 tensor on %s, got %s on %s" % (self.device, wave.dtype, wave.device))
+        try:
+            counts = list(counts.tolist() if isinstance(counts, (torch.Tensor, np.ndarray)) else counts)
+        except TypeError:
+            raise ValueError("ResamplerBank.process: counts must be a sequence of %d ints, got %s" % (self.C, type(counts).__name__)) from None
+        if len(counts) != self.C:
+            raise ValueError("ResamplerBank.process: %d counts for %d rows" % (len(counts), self.C))
+        for r, n in enumerate(counts):
+            if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+                raise ValueError("ResamplerBank.process: the count of row %d must be an int, got %s" % (r, type(n).__name__))
+            if not 0 <= n <= wave.shape[1]:
+                raise ValueError("ResamplerBank.process: row %d has %d samples, outside [0, %d]" % (r, n, wave.shape[1]))
+        w, w_stride = BSRNN._rows_view(wave.detach())
+        want = [self._ready(r, n) if n else 0 for r, n in enumerate(counts)]
+        n_in = (ctypes.c_int64 * self.C)(*[int(n) for n in counts])
+        n_out = (ctypes.c_int64 * self.C)(*([-1] * self.C))
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.C, max(want)), device=self.device, dtype=torch.float32)
+            _check(_lib.bsrnn_resampler_bank_process(self._h, _ptr(w), w_stride, n_in, _ptr(out), out.shape[1], n_out, _stream_ptr(self.device)))
+        got = list(n_out)
+        assert got == want, (got, want)
+        for r in range(self.C):
+            self._taken[r] += int(counts[r])
+            self._given[r] += got[r]
+        return out, got
+
+    def flush_rows(self, rows):
+        """The listed rows get the samples they are still owed for their input so far (the future counting as zeros) and start afresh;
+        the others are untouched.  -> (tensor [C, max count], the counts as a list: 0 for rows not listed)."""
+        rows, arr = self._rows(rows, "flush_rows")
+        want = [0] * self.C
+        for r in rows:
+            want[r] = (resample_len(self._taken[r], *self.pairs[self._pair[r]]) if self._taken[r] else 0) - self._given[r]
+        n_out = (ctypes.c_int64 * self.C)(*([-1] * self.C))
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.C, max(want)), device=self.device, dtype=torch.float32)
+            _check(_lib.bsrnn_resampler_bank_flush_rows(self._h, arr, len(rows), _ptr(out), out.shape[1], n_out, _stream_ptr(self.device)))
+        got = list(n_out)
+        assert got == want, (got, want)
+        for r in rows:
+            self._taken[r] = self._given[r] = 0
+        return out, got
+
+
+class _StreamPoolType(type):
+    """StreamPool(model, slots, rows_per_session=1, device=None, rates=None): the keyword `rates` is taken HERE, by the call of the
+    class, and checked before anything else happens; StreamPool.__init__ keeps the four parameters it has always had, which callers
+    and tests/test_stream_rows_host.py hold it to (inspect.signature(StreamPool) shows the whole call)."""
+
+    def __call__(cls, model, slots, rows_per_session=1, device=None, rates=None):
+        rates = cls._checked_rates(rates)
+        pool = super().__call__(model, slots, rows_per_session, device)
+        pool.rates = rates
+        return pool
+
+
+class StreamPool(metaclass=_StreamPoolType):
     """Many live sessions on one wide stream: `slots` sessions of `rows_per_session` rows each share one StreamingSeparator of
     slots * rows_per_session rows, and one step() serves whichever of them have audio this tick at the price of one streaming call
     (a step is launch-bound: its cost hardly grows with the rows).  feed() does the same for sessions that do NOT deliver audio in lock
     step: each gives whatever it has, and one call advances every session by its own number of hops.  Sessions join (open), leave
     (close), pause (not named in a step or feed: their rows are held) and move between pools (export / adopt) one by one.  The stream is created at the first call that needs the
-    device; shape and type errors are raised before that."""
+    device; shape and type errors are raised before that.
+
+    Sessions at their own sample rates: with `rates`, a tuple of at most 16 rates, open(sample_rate=r) makes a session that gives and
+    gets audio at r, one of them.  feed() then converts what all such sessions bring to the model's 44.1 kHz in ONE call of a
+    ResamplerBank (a rate pair, a count and a stream position per row), runs everybody's hops as before, and converts the separated
+    audio back in one more; the stream's one-hop delay is taken out of such a session's audio (its first hop is dropped), so what it
+    gets lines up with what it gave, and drain() ends its audio.  The two banks are made with the stream, and only when `rates` is
+    given: without it the pool makes exactly the library calls it made before."""
+
+    MODEL_RATE = 44100
+
+    @classmethod
+    def _checked_rates(cls, rates):
+        """`rates` as a tuple of ints (None stays None), or ValueError for what the conversions to and from the model's rate refuse."""
+        if rates is None:
+            return None
+        try:
+            rates = tuple(rates)
+        except TypeError:
+            raise ValueError("StreamPool: rates must be a tuple of sample rates, got %s" % type(rates).__name__) from None
+        if not 1 <= len(rates) <= _native.BANK_PAIRS_MAX:
+            raise ValueError("StreamPool: %d rates, a pool takes 1 to %d" % (len(rates), _native.BANK_PAIRS_MAX))
+        for r in rates:
+            if isinstance(r, bool) or not isinstance(r, (int, np.integer)):
+                raise ValueError("StreamPool: a rate must be an int, got %r" % (r,))
+            resample_len(1, r, cls.MODEL_RATE)          # (the limits of the conversion, as a ValueError)
+        return tuple(int(r) for r in rates)
 
     def __init__(self, model, slots, rows_per_session=1, device=None):
         for name, v in (("slots", slots), ("rows_per_session", rows_per_session)):
@@ -1014,10 +1198,21 @@ class StreamPool:
         self._free = list(range(self.slots))
         self._next = 0
         self._pend = {}                     # feed(): session id -> the samples (fewer than one hop) that wait for its next feed
+        self.rates = None                   # the pool's session rates; the call of the class sets them (_StreamPoolType)
+        self._rate = {}                     # session id -> index into rates, for the sessions that have one
+        self._skip = {}                     # such a session -> samples of the stream's delay still to be dropped from its output
+        self._bank_in = self._bank_out = None
 
     def _stream(self):
         if self._st is None:
             self._st = StreamingSeparator(self.model, channels=self.slots * self.rows, device=self._device)
+            if self.rates is not None:
+                C = self.slots * self.rows
+                self._bank_in = ResamplerBank(self.model, C, [(r, self.MODEL_RATE) for r in self.rates])
+                self._bank_out = ResamplerBank(self.model, C, [(self.MODEL_RATE, r) for r in self.rates])
+                for sid, k in self._rate.items():
+                    self._bank_in.assign(list(self._rows_of(sid)), k)
+                    self._bank_out.assign(list(self._rows_of(sid)), k)
         return self._st
 
     def _rows_of(self, sid):
@@ -1027,8 +1222,14 @@ class StreamPool:
     def sessions(self):
         return list(self._slot)
 
-    def open(self):
-        """-> a new session's id; its rows start from silence.  ValueError when every slot is taken."""
+    def open(self, sample_rate=None):
+        """-> a new session's id; its rows start from silence.  sample_rate: None or the model's 44100 for a session that gives and gets
+        audio at the model's rate, else one of the pool's `rates`.  ValueError when every slot is taken or the rate is not one of them."""
+        k = None
+        if sample_rate is not None and sample_rate != self.MODEL_RATE:
+            if self.rates is None or sample_rate not in self.rates:
+                raise ValueError("StreamPool.open: sample_rate %r is not one of the pool's rates %r" % (sample_rate, self.rates))
+            k = self.rates.index(sample_rate)
         if not self._free:
             raise ValueError("StreamPool: all %d slots are in use" % self.slots)
         slot = self._free.pop(0)
@@ -1036,16 +1237,32 @@ class StreamPool:
         self._slot[sid] = slot
         if self._st is not None:            # (a stream that does not exist yet starts zeroed)
             self._st.reset_rows(list(self._rows_of(sid)))
+        if k is not None:
+            self._rate[sid], self._skip[sid] = k, _spec.HOP
+            if self._bank_in is not None:   # (banks that do not exist yet are told at their creation)
+                self._bank_in.assign(list(self._rows_of(sid)), k)
+                self._bank_out.assign(list(self._rows_of(sid)), k)
         return sid
 
     def close(self, sid):
-        """The session leaves; samples of it that feed() kept waiting are dropped."""
+        """The session leaves; samples of it that feed() kept waiting are dropped, and its rows of the resampler banks start afresh."""
+        rows = list(self._rows_of(sid))
+        if self._rate.pop(sid, None) is not None and self._bank_in is not None:
+            self._bank_in.reset_rows(rows)
+            self._bank_out.reset_rows(rows)
+        self._skip.pop(sid, None)
         self._free.append(self._slot.pop(sid))
         self._free.sort()
         self._pend.pop(sid, None)
 
+    def rate_of(self, sid):
+        """The session's sample rate (44100 for one opened without)."""
+        self._rows_of(sid)
+        return self.rates[self._rate[sid]] if sid in self._rate else self.MODEL_RATE
+
     def pending(self, sid):
-        """Samples per row of the session that wait for its next feed() (fewer than one hop)."""
+        """Samples per row of the session that wait for its next feed() (fewer than one hop) - at the MODEL's rate, 44.1 kHz, also for a
+        session with a rate of its own: they are what the conversion has given and no whole hop has taken yet."""
         self._rows_of(sid)
         p = self._pend.get(sid)
         return 0 if p is None else int(p.shape[1])
@@ -1057,7 +1274,11 @@ class StreamPool:
         hop waits per session, on the device, and is prepended at the session's next feed, as StreamingSeparator.process does for a whole
         stream.  A session without a whole hop gets an empty tensor and its rows are held; so are sessions not named.  If nobody has a
         hop, no library call is made.  mix as in step().  The pending samples are NOT part of the carry that export() hands out: feed
-        whole hops before moving a session, or move pending(sid) samples of its audio yourself."""
+        whole hops before moving a session, or move pending(sid) samples of its audio yourself.
+        A session opened with a sample rate gives its chunk AT THAT RATE and gets back, at that rate, the output samples that have
+        become determined - a length that varies from tick to tick, and lags what it gave by the two conversions' filters and the hop
+        that is still filling; the stream's own one-hop delay is taken out.  All such sessions of a tick share one inbound and one
+        outbound ResamplerBank call around the one bsrnn_stream_process_hops; drain() gives a session the rest."""
         if not isinstance(chunks, dict):
             raise ValueError("StreamPool.feed: chunks must be a dict {session id: tensor}, got %s" % type(chunks).__name__)
         for sid, t in chunks.items():
@@ -1073,6 +1294,52 @@ class StreamPool:
                     raise ValueError("StreamPool.feed: mix of session %r must be a float, got %s" % (sid, type(v).__name__))
         elif mix is not None and (isinstance(mix, bool) or not isinstance(mix, (int, float))):
             raise ValueError("StreamPool.feed: mix must be None, a float or a dict {session id: float}, got %s" % type(mix).__name__)
+        rated = [sid for sid in chunks if sid in self._rate]
+        if not rated:
+            return self._feed_hops(chunks, mix)
+        # Sessions with a rate: what they bring goes to 44.1 kHz in one bank call, then everybody's audio takes the path it always took,
+        # then what came out for them goes back to their rates in one more
+        self._stream()
+        conv = self._bank_call(self._bank_in, {sid: chunks[sid] for sid in rated})
+        res = self._feed_hops({sid: conv.get(sid, t) for sid, t in chunks.items()}, mix)
+        back = self._bank_call(self._bank_out, {sid: self._undelayed(sid, res[sid]) for sid in rated})
+        for sid in rated:
+            res[sid] = back[sid] if chunks[sid].is_cuda else back[sid].cpu()
+        return res
+
+    def _undelayed(self, sid, out):
+        """The stream's output for a session with a rate, without the samples of the one-hop delay that are still to be dropped."""
+        k = min(self._skip[sid], out.shape[1])
+        self._skip[sid] -= k
+        return out[:, k:]
+
+    def _bank_call(self, bank, blocks):
+        """blocks {sid: tensor [rows_per_session, n]} of sessions with a rate -> {sid: tensor [rows_per_session, count] on the pool's
+        device}, the samples that have become determined: ONE process() of the bank, every other row held.  The results are views of
+        the call's one output tensor, which nobody else holds."""
+        C = self.slots * self.rows
+        dev = self._st.device
+        n_max = max(t.shape[1] for t in blocks.values())
+        if n_max == 0:
+            return {sid: torch.empty((self.rows, 0), dtype=torch.float32, device=dev) for sid in blocks}
+        wave = torch.empty((C, n_max), dtype=torch.float32, device=dev)
+        counts = [0] * C
+        for sid, t in blocks.items():
+            rows = self._rows_of(sid)
+            if t.shape[1]:
+                wave[rows.start:rows.stop, :t.shape[1]] = t.detach().to(device=dev, dtype=torch.float32)
+            for r in rows:
+                counts[r] = t.shape[1]
+        out, got = bank.process(wave, counts)
+        res = {}
+        for sid in blocks:
+            rows = self._rows_of(sid)
+            res[sid] = out[rows.start:rows.stop, :got[rows.start]]
+        return res
+
+    def _feed_hops(self, chunks, mix):
+        """feed() behind its argument checks, for chunks at the model's rate."""
+        per_row = isinstance(mix, dict)
         hop = _spec.HOP
         have = {sid: self.pending(sid) + t.shape[1] for sid, t in chunks.items()}
         anyone = any(n >= hop for n in have.values())
@@ -1132,6 +1399,9 @@ class StreamPool:
             if n is not None and t.shape[1] != n:
                 raise ValueError("StreamPool.step: session %r holds %d samples per row, the others %d (one L per step)" % (sid, t.shape[1], n))
             n = t.shape[1]
+            if sid in self._rate:
+                raise ValueError("StreamPool.step: session %r has a sample rate of its own (%d Hz): its audio does not come in whole hops, "
+                                 "use feed()" % (sid, self.rates[self._rate[sid]]))
         per_row = isinstance(mix, dict)
         if per_row:
             for sid, v in mix.items():
@@ -1166,11 +1436,48 @@ class StreamPool:
     def export(self, sid):
         """-> the session's carry, one blob (CPU tensor) per row, for adopt() of this or another pool of the same model."""
         rows = self._rows_of(sid)
+        if sid in self._rate:
+            raise ValueError("StreamPool.export: session %r has a sample rate of its own (%d Hz); the resamplers' carries do not move "
+                             "with a session" % (sid, self.rates[self._rate[sid]]))
         st = self._stream()
         return [st.get_row(r) for r in rows]
 
+    def drain(self, sid, mix=None):
+        """The session's audio ends: -> the tail it is still owed, [rows_per_session, n] on the pool's device, at the session's rate.  In
+        order: the inbound resampler's rows are flushed (the future counting as zeros); what waits is padded with zeros to a whole hop;
+        one more hop of zeros follows for the stream's one-hop delay; those hops run with every other session held; the outbound
+        resampler converts them and is flushed.  Afterwards the session's rows of the stream and of both banks are reset: it stays open
+        and its next feed() begins a new piece of audio.  A session without a rate skips the resampler steps: it gets the padded hops
+        and the extra one as the stream gives them.
+        LENGTH: a session that fed n samples at its rate r since it was opened (or drained) has received, feed() results and this tail
+        together, resample_len(m, 44100, r) samples with m = resample_len(n, r, 44100) rounded up to whole hops of 1024.
+        mix: None or one float, as in feed()."""
+        rows = self._rows_of(sid)
+        if mix is not None and (isinstance(mix, bool) or not isinstance(mix, (int, float))):
+            raise ValueError("StreamPool.drain: mix must be None or a float, got %s" % type(mix).__name__)
+        st = self._stream()
+        rated = sid in self._rate
+        lst = list(rows)
+        if rated:
+            out, got = self._bank_in.flush_rows(lst)
+            x = out[rows.start:rows.stop, :got[rows.start]]
+        else:
+            x = torch.empty((self.rows, 0), dtype=torch.float32, device=st.device)
+        hop = _spec.HOP
+        pad = -(self.pending(sid) + x.shape[1]) % hop
+        x = torch.cat((x, torch.zeros((self.rows, pad + hop), dtype=torch.float32, device=st.device)), 1)
+        tail = self._feed_hops({sid: x}, mix)[sid]
+        if rated:
+            a = self._bank_call(self._bank_out, {sid: self._undelayed(sid, tail)})[sid]
+            out, got = self._bank_out.flush_rows(lst)
+            tail = torch.cat((a, out[rows.start:rows.stop, :got[rows.start]]), 1)
+            self._skip[sid] = hop
+        st.reset_rows(lst)
+        self._pend.pop(sid, None)
+        return tail
+
     def adopt(self, blobs):
-        """A session exported elsewhere continues here, bit for bit -> its new id."""
+        """A session exported elsewhere continues here, bit for bit -> its new id (a session without a sample rate of its own)."""
         blobs = list(blobs)
         nf = 2 * _spec.N_FFT + 8 * len(self.model.band_widths) * band_features
         if len(blobs) != self.rows or not all(isinstance(b, torch.Tensor) and b.dim() == 1 and b.numel() == nf for b in blobs):

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -2931,6 +2932,184 @@ int bsrnn_resampler_process(bsrnn_resampler* rs, const float* in, int64_t in_str
 int bsrnn_resampler_flush(bsrnn_resampler* rs, float* out, int64_t out_stride, int64_t* n_out_host, void* stream)
 {
     return resampler_run(rs, nullptr, 0, 0, out, out_stride, n_out_host, true, (hipStream_t)stream);
+}
+
+// A bank of streaming resamplers: every row on one of the declared pairs and at its own place in its own stream, one launch per call
+// (per BANK_GROUP_ROWS rows).  The per-row arithmetic: resample_bank_host.h; the kernel: resample_bank_kernel of resample.hip.
+struct bsrnn_resampler_bank {
+    bsrnn_ctx* ctx;
+    int C, n_pairs;
+    ResampleRatio q[BANK_PAIRS_MAX];
+    int tile[BANK_PAIRS_MAX];
+    BankPair* pairs;                 // [n_pairs] on the device, written by _create and constant afterwards
+    float* carry;                    // two sets of C * cap floats; row r's current set is pos[r].cur
+    int64_t cap;                     // the largest resample_carry_floats of the declared pairs
+    std::vector<BankPos> pos, next;  // [C]: where every row stands; next is a call's scratch (nothing is allocated after _create)
+    std::vector<BankRow> desc;       // [C], a call's descriptors
+    std::vector<uint8_t> seen;       // [C], for "a row listed twice"
+};
+
+// rows_host [n_rows] -> seen[] marks them; refuses a null list, a row outside [0, C) and a row listed twice
+static int bank_mark_rows(bsrnn_resampler_bank* bk, const int32_t* rows, int32_t n_rows, const char* who)
+{
+    if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(BSRNN_EARG, "%s: need a list of n_rows >= 0 rows, got n_rows = %d", who, n_rows);
+    std::fill(bk->seen.begin(), bk->seen.end(), (uint8_t)0);
+    for (int i = 0; i < n_rows; ++i) {
+        const int32_t r = rows[i];
+        if (r < 0 || r >= bk->C) return fail(BSRNN_EARG, "%s: row %d (entry %d of the list) is outside [0, %d)", who, r, i, bk->C);
+        if (bk->seen[r]) return fail(BSRNN_EARG, "%s: row %d is listed twice", who, r);
+        bk->seen[r] = 1;
+    }
+    return 0;
+}
+
+int bsrnn_resampler_bank_create(bsrnn_ctx* c, int32_t C, const int32_t* rates_in, const int32_t* rates_out, int32_t n_pairs,
+                                bsrnn_resampler_bank** out)
+{
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!out || C < 1) return fail(BSRNN_EARG, "bsrnn_resampler_bank_create: need C >= 1 rows and a place for the object, got C = %d", C);
+    if (n_pairs < 1 || n_pairs > BANK_PAIRS_MAX)
+        return fail(BSRNN_EARG, "bsrnn_resampler_bank_create: n_pairs = %d is outside [1, %d]", n_pairs, BANK_PAIRS_MAX);
+    if (!rates_in || !rates_out) return fail(BSRNN_EARG, "bsrnn_resampler_bank_create: need the %d rate pairs", n_pairs);
+    ResampleRatio q[BANK_PAIRS_MAX];
+    for (int k = 0; k < n_pairs; ++k)
+        if (int rc = resample_check_rates(rates_in[k], rates_out[k], "bsrnn_resampler_bank_create", q[k])) return rc;
+    if (int rc = check_device(c)) return rc;
+    CallGuard guard_(c);
+    if (!guard_.ok) return guard_.refuse();
+    std::unique_ptr<bsrnn_resampler_bank> bk(new bsrnn_resampler_bank());
+    bk->ctx = c; bk->C = C; bk->n_pairs = n_pairs; bk->cap = 0;
+    BankPair host[BANK_PAIRS_MAX];
+    for (int k = 0; k < n_pairs; ++k) {
+        const bsrnn_ctx::ResampleTable* t = nullptr;
+        if (int rc = resample_table_of(c, q[k], &t)) return rc;
+        bk->q[k] = t->q; bk->tile[k] = t->g.tile;
+        host[k] = BankPair{t->d, (int)t->q.up, (int)t->q.down, t->q.Kh, t->g.ld, t->g.chunk, t->g.tile};
+        bk->cap = std::max(bk->cap, resample_carry_floats(t->q));
+    }
+    bk->pos.assign(C, BankPos());
+    bk->next.assign(C, BankPos());
+    bk->desc.assign(C, BankRow{0, 0, 0, 0, 0});
+    bk->seen.assign(C, 0);
+    // one allocation: the pair table (512 bytes), then the two carry sets
+    char* p = nullptr;
+    ++g_dbg[DBG_ALLOC];
+    const size_t head = BANK_PAIRS_MAX * sizeof(BankPair), bytes = head + 2 * (size_t)C * bk->cap * sizeof(float);
+    hipError_t e = hipMalloc((void**)&p, bytes);
+    if (e == hipSuccess && (e = hipMemset(p, 0, bytes)) == hipSuccess) e = hipMemcpy(p, host, n_pairs * sizeof(BankPair), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        bk->pairs = (BankPair*)p; bk->carry = (float*)(p + head);
+        // the kernel's first launch (code object loading) happens here: every row hands an empty carry over (a block of nothing)
+        for (int r = 0; r < C; ++r) bk->desc[r] = BankRow{0, 0, 0, 0, BANK_ROW_RUNS | BANK_ROW_CARRIES};
+        BankLaunch L{bk->pairs, nullptr, 0, nullptr, 0, bk->carry, bk->cap, (int64_t)C * bk->cap, 0};
+        launch_resample_bank(L, bk->tile, bk->desc.data(), C, nullptr);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    }
+    if (e != hipSuccess) { (void)hipFree(p); return fail(BSRNN_EHIP, "bsrnn_resampler_bank_create: %s", hipGetErrorString(e)); }
+    ++c->live_streams;
+    *out = bk.release();
+    return 0;
+}
+
+void bsrnn_resampler_bank_destroy(bsrnn_resampler_bank* bk)
+{
+    if (!bk) return;
+    bsrnn_ctx* c = bk->ctx;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(bk->pairs);
+    delete bk;
+    if (--c->live_streams == 0 && c->zombie) destroy_now(c);     // as bsrnn_resampler_destroy
+}
+
+int bsrnn_resampler_bank_assign(bsrnn_resampler_bank* bk, const int32_t* rows, int32_t n_rows, int32_t pair)
+{
+    if (!bk) return fail(BSRNN_EARG, "null resampler bank");
+    if (pair < 0 || pair >= bk->n_pairs) return fail(BSRNN_EARG, "bsrnn_resampler_bank_assign: pair %d is outside [0, %d)", pair, bk->n_pairs);
+    if (int rc = bank_mark_rows(bk, rows, n_rows, "bsrnn_resampler_bank_assign")) return rc;
+    // nothing to enqueue, as bsrnn_resampler_reset: with no input taken the carry holds no sample a call would read
+    for (int i = 0; i < n_rows; ++i) bank_row_assign(bk->pos[rows[i]], pair);
+    return 0;
+}
+
+int bsrnn_resampler_bank_reset_rows(bsrnn_resampler_bank* bk, const int32_t* rows, int32_t n_rows)
+{
+    if (!bk) return fail(BSRNN_EARG, "null resampler bank");
+    if (int rc = bank_mark_rows(bk, rows, n_rows, "bsrnn_resampler_bank_reset_rows")) return rc;
+    for (int i = 0; i < n_rows; ++i) bank_row_reset(bk->pos[rows[i]]);
+    return 0;
+}
+
+int bsrnn_resampler_bank_pair_of(const bsrnn_resampler_bank* bk, int32_t row)
+{
+    return bk && row >= 0 && row < bk->C ? bk->pos[row].pair : -1;
+}
+
+int64_t bsrnn_resampler_bank_ready(const bsrnn_resampler_bank* bk, int32_t row, int64_t n_in)
+{
+    if (!bk || row < 0 || row >= bk->C) return -1;
+    const BankPos& p = bk->pos[row];
+    if (n_in < 0 || n_in > (INT64_MAX >> 12) - p.N) return -1;
+    return bank_row_ready(bk->q[p.pair], p, n_in);
+}
+
+// process (rows == null: every row takes n_in[r]) or flush (the rows marked in seen[]): descriptors and next positions first, then
+// every refusal, then the launches
+static int bank_run(bsrnn_resampler_bank* bk, const float* in, int64_t in_stride, const int64_t* n_in, float* out, int64_t out_stride,
+                    int64_t* n_out_host, bool flush, hipStream_t s)
+{
+    const char* who = flush ? "bsrnn_resampler_bank_flush_rows" : "bsrnn_resampler_bank_process";
+    if (!n_out_host) return fail(BSRNN_EARG, "%s: nowhere to report the sample counts", who);
+    if (!flush && !n_in) return fail(BSRNN_EARG, "%s: need the rows' sample counts", who);
+    int64_t max_in = 0, max_out = 0;
+    for (int r = 0; r < bk->C; ++r) {
+        const BankPos& p = bk->pos[r];
+        const ResampleRatio& q = bk->q[p.pair];
+        const int64_t n = flush ? 0 : n_in[r];
+        const int why = flush ? (bk->seen[r] ? bank_row_flush(q, p, bk->desc[r], bk->next[r]) : bank_row_process(q, p, 0, bk->desc[r], bk->next[r]))
+                              : bank_row_process(q, p, n, bk->desc[r], bk->next[r]);
+        if (why == BANK_BAD_COUNT) return fail(BSRNN_EARG, "%s: need n_in >= 0 samples for every row, got %lld for row %d", who, (long long)n, r);
+        if (why == BANK_BLOCK_TOO_LONG)
+            return fail(BSRNN_EARG, "%s: row %d would take %lld samples or give more than %lld; one call moves at most %lld per row", who, r,
+                        (long long)n, (long long)BANK_BLOCK_MAX, (long long)BANK_BLOCK_MAX);
+        if (why != BANK_OK) return fail(BSRNN_ESTATE, "%s: the carry of row %d would overflow (internal error)", who, r);
+        max_in = std::max(max_in, n);
+        max_out = std::max(max_out, (int64_t)bk->desc[r].n_j);
+    }
+    if (max_in > 0 && (!in || in_stride < max_in))
+        return fail(BSRNN_EARG, "%s: need an input block with in_stride >= the largest count, got in_stride = %lld, largest n_in = %lld", who,
+                    (long long)in_stride, (long long)max_in);
+    if (max_out > 0 && (!out || out_stride < max_out))
+        return fail(BSRNN_EARG, "%s: need an output block with out_stride >= the %lld samples this call writes to a row, got out_stride = %lld", who,
+                    (long long)max_out, (long long)out_stride);
+    if (max_in > 0 && max_out > 0 &&
+        ranges_overlap(in, ((size_t)(bk->C - 1) * in_stride + max_in) * sizeof(float), out, ((size_t)(bk->C - 1) * out_stride + max_out) * sizeof(float)))
+        return fail(BSRNN_EARG, "%s: out_dev must not overlap the span of in_dev (rows are read while others are written)", who);
+    bsrnn_ctx* c = bk->ctx;
+    if (int rc = check_device(c)) return rc;
+    ENTER_CALL(c, s);
+    for (int r = 0; r < bk->C; ++r) n_out_host[r] = bk->desc[r].n_j;
+    BankLaunch L{bk->pairs, max_in > 0 ? in : nullptr, in_stride, out, out_stride, bk->carry, bk->cap, (int64_t)bk->C * bk->cap, 0};
+    launch_resample_bank(L, bk->tile, bk->desc.data(), bk->C, s);
+    HIP_TRY(hipGetLastError());
+    bk->pos.swap(bk->next);
+    return 0;
+}
+
+int bsrnn_resampler_bank_process(bsrnn_resampler_bank* bk, const float* in, int64_t in_stride, const int64_t* n_in_host, float* out,
+                                 int64_t out_stride, int64_t* n_out_host, void* stream)
+{
+    if (!bk) return fail(BSRNN_EARG, "null resampler bank");
+    return bank_run(bk, in, in_stride, n_in_host, out, out_stride, n_out_host, false, (hipStream_t)stream);
+}
+
+int bsrnn_resampler_bank_flush_rows(bsrnn_resampler_bank* bk, const int32_t* rows, int32_t n_rows, float* out, int64_t out_stride,
+                                    int64_t* n_out_host, void* stream)
+{
+    if (!bk) return fail(BSRNN_EARG, "null resampler bank");
+    if (int rc = bank_mark_rows(bk, rows, n_rows, "bsrnn_resampler_bank_flush_rows")) return rc;
+    return bank_run(bk, nullptr, 0, nullptr, out, out_stride, n_out_host, true, (hipStream_t)stream);
 }
 
 // --------------------------------------------------------------------------- measurement

@@ -5,6 +5,7 @@
 
 #include "descriptors.h"   // GemmJob, ChainDesc and the constants the host packs against (HIP-free)
 #include "stream_rows_host.h"   // RowSet: the rows a streaming rows call means, by value (HIP-free)
+#include "resample_bank_host.h" // BankRow: what a resampler bank's kernel knows of a row, by value (HIP-free)
 
 namespace bsrnn {
 
@@ -353,5 +354,21 @@ struct ResampleArgs {
     float* carry; int64_t carry_stride, c0;
 };
 void launch_resample(ResampleArgs g, int R, hipStream_t s);
+
+// A bank call (bsrnn_resampler_bank_*; the arithmetic: resample_bank_host.h): C rows, each on its own pair, block length and stream
+// position, one launch per BANK_GROUP_ROWS rows.  pairs [n_pairs] on the device, written once; carry: two sets of carry_set = C * cap
+// floats, rows cap apart, a row reads the set its descriptor names and writes the other; in (null in a flush) / out: rows in_stride /
+// out_stride apart, row r reads in[r][0 .. n_in_r) and writes out[r][0 .. n_j_r).  vec is the launcher's.  tiles [n_pairs] on the host:
+// the pairs' tile sizes, for the grid.
+struct BankPair { const float* tab; int up, down, Kh, ld, chunk, tile; };
+struct BankLaunch {
+    const BankPair* pairs;
+    const float* in; int64_t in_stride;
+    float* out; int64_t out_stride;
+    float* carry; int64_t cap, carry_set;
+    int vec;
+};
+static_assert(sizeof(BankLaunch) <= BANK_ARG_OTHER, "resample_bank_host.h sizes a group of descriptors beside these");
+void launch_resample_bank(BankLaunch L, const int* tiles, const BankRow* rows, int C, hipStream_t s);
 
 }  // namespace bsrnn

@@ -28,6 +28,13 @@ variants alternate inside every repeat, and min .. max of the windows is printed
   H3, the plain calls: part 2 above, this build against --baseline-lib.
 
     python tools/stream_pool_bench.py --hops [--baseline-lib PATH] [--out profiles/stream_hops_ab.txt]
+
+--rates times sessions at their own sample rates: the 64-row stream, 32 sessions of 2 rows whose rates are drawn from {16 000, 32 000,
+48 000, 96 000} (fixed seed), each giving one hop's worth of audio at its rate per tick.  (a) StreamPool.feed of a pool with rates:
+one inbound and one outbound resampler-bank call around the one process_hops; (b) the same tick from a pool without rates and one
+Resampler per session and direction around one feed; (c) the two bank calls alone, through the C ABI.
+
+    python tools/stream_pool_bench.py --rates [--out profiles/stream_rates_ab.txt]
 """
 import argparse
 import ctypes
@@ -46,6 +53,8 @@ REPEATS = 7
 WINDOW_S = 0.2
 HOP = 1024
 PLAIN_SHAPES = ((64, 1), (64, 8))
+RATES = (16000, 32000, 48000, 96000)
+MODEL_RATE = 44100
 
 
 def measure(jobs, sync):
@@ -243,9 +252,78 @@ def hops_parts(say):
     say("")
 
 
+def rates_part(say):
+    """--rates, in this process."""
+    import random
+    import torch
+    from speechseparation_amd import _native, weights
+    from speechseparation_amd.bsrnn import Resampler, ResamplerBank, StreamPool
+    lib, check = _native.lib, _native.check
+    model = setup()
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    C = SLOTS * ROWS
+    say("# %s, %s, compute mode %s" % (torch.cuda.get_device_name(0), torch.version.hip, _native.compute_mode()))
+    say("# us per tick: median [min .. max] of %d windows of ~%.1f s; inputs resident, deferred range policy" % (REPEATS, WINDOW_S))
+    rnd = random.Random(7)
+    per_session = [rnd.choice(RATES) for _ in range(SLOTS)]
+    n_of = {r: (HOP * r + MODEL_RATE // 2) // MODEL_RATE for r in RATES}           # one hop's worth of audio at rate r
+    audio = torch.from_numpy(weights.synth_waveform(C, max(n_of.values()), seed=5)).cuda()
+    blocks = [audio[ROWS * i:ROWS * (i + 1), :n_of[r]].contiguous() for i, r in enumerate(per_session)]
+    # (a) the pool with its banks
+    pool = StreamPool(model, SLOTS, rows_per_session=ROWS, device="cuda:0", rates=RATES)
+    sids = [pool.open(sample_rate=r) for r in per_session]
+    chunks = {sids[i]: blocks[i] for i in range(SLOTS)}
+    # (b) a pool without rates and one Resampler per session and direction
+    plain = StreamPool(model, SLOTS, rows_per_session=ROWS, device="cuda:0")
+    psids = [plain.open() for _ in range(SLOTS)]
+    rin = [Resampler(model, ROWS, r, MODEL_RATE) for r in per_session]
+    rout = [Resampler(model, ROWS, MODEL_RATE, r) for r in per_session]
+    # (c) the two bank calls alone, through the C ABI: the tick's counts inbound, one hop per row outbound
+    bank_in = ResamplerBank(model, C, [(r, MODEL_RATE) for r in RATES])
+    bank_out = ResamplerBank(model, C, [(MODEL_RATE, r) for r in RATES])
+    for i, r in enumerate(per_session):
+        bank_in.assign(list(range(ROWS * i, ROWS * (i + 1))), RATES.index(r))
+        bank_out.assign(list(range(ROWS * i, ROWS * (i + 1))), RATES.index(r))
+    wave_in = torch.zeros((C, max(n_of.values())), device="cuda")
+    for i, b in enumerate(blocks):
+        wave_in[ROWS * i:ROWS * (i + 1), :b.shape[1]] = b
+    i64 = ctypes.c_int64
+    counts_in = (i64 * C)(*[n_of[per_session[r // ROWS]] for r in range(C)])
+    counts_hop = (i64 * C)(*([HOP] * C))
+    n_out = (i64 * C)()
+    conv = torch.empty((C, HOP + 64), device="cuda")
+    wave_hop = torch.from_numpy(weights.synth_waveform(C, HOP, seed=6)).cuda()
+    back = torch.empty((C, 4 * HOP), device="cuda")
+
+    def job_a():
+        pool.feed(chunks)
+
+    def job_b():
+        res = plain.feed({psids[i]: rin[i].process(blocks[i]) for i in range(SLOTS)})
+        for i in range(SLOTS):
+            o = res[psids[i]]
+            if o.shape[1]:
+                rout[i].process(o)
+
+    def job_c():
+        check(lib.bsrnn_resampler_bank_process(bank_in._h, ptr(wave_in), wave_in.stride(0), counts_in, ptr(conv), conv.stride(0), n_out, None))
+        check(lib.bsrnn_resampler_bank_process(bank_out._h, ptr(wave_hop), HOP, counts_hop, ptr(back), back.stride(0), n_out, None))
+
+    r = measure({"a": job_a, "b": job_b, "c": job_c}, torch.cuda.synchronize)
+    model.sync()
+    say("# %d-row stream, %d sessions of %d rows, rates from {%s} (seed 7: %s sessions), one hop's worth of audio per session per tick" % (
+        C, SLOTS, ROWS, ", ".join(str(x) for x in RATES), " / ".join(str(per_session.count(x)) for x in RATES)))
+    say("%-64s %28s" % ("a  StreamPool.feed with the two resampler banks", cell(r["a"])))
+    say("%-64s %28s" % ("b  one Resampler per session and direction around one feed", cell(r["b"])))
+    say("%-64s %28s" % ("c  the two bank calls alone (C ABI)", cell(r["c"])))
+    say("b / a = %.2f; a - c = %.1f us" % (r["b"][0] / r["a"][0], r["a"][0] - r["c"][0]))
+    say("")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--rates", action="store_true", help="time StreamPool.feed with sessions at their own sample rates instead")
     ap.add_argument("--baseline-lib", default=None, help="another build of libbsrnn_hip.so (the parent commit's) for part 2")
     ap.add_argument("--hops", action="store_true", help="time bsrnn_stream_process_hops (H1 - H3 above) instead of part 1")
     ap.add_argument("--plain-only", action="store_true", help=argparse.SUPPRESS)
@@ -258,6 +336,12 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
+    if args.rates:
+        rates_part(say)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     part2 = plain_runs(args.baseline_lib)
     if args.hops:
         hops_parts(say)
