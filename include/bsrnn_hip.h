@@ -408,6 +408,58 @@ int  bsrnn_evaluate_ragged(bsrnn_ctx* ctx, const float* mix_dev, const float* sp
                            const int64_t* clip_lens_host, const int32_t* clip_rows_host, int32_t n_clips,
                            float* est_out_dev, double* metrics_host, void* stream);
 
+/* ---- ragged training: the clips of one optimizer step in one backward pass -----------------
+ * The reference accumulates gradients clip by clip (train.py:97-115).  The same step as ONE rectangle R x Tmax: the model is causal along
+ * time, its band-axis blocks see one frame at a time and rows are independent, so a zero-padded rectangle gives every real frame its own
+ * result; y = x * mask with x = 0 in the padded frames, so those frames carry neither value nor gradient.  Only the two DSP ends and the
+ * loss know the lengths - the five calls below, at the [R, 2050, Tmax] boundary autograd works on (re/im interleaved, T innermost).
+ * Conventions as bsrnn_separate_ragged / bsrnn_evaluate_ragged: rows wave_stride floats apart, lens_host[r] samples in row r,
+ * 1024 < length <= wave_stride, T_r = 1 + length / 1024, Tmax = the largest T_r, n_est_r = (T_r - 1) * 1024.  The host arrays are the
+ * caller's again at return (the lengths travel through the pinned mirrors of bsrnn_separate_ragged's block, in stream order); no call
+ * waits for the device and every result stays in device memory, so the calls of one step queue up on ONE stream.  A second step that fits
+ * allocates nothing (bsrnn_debug_counter(0)).  No committed weights are needed.
+ * BSRNN_EARG, before any device work (also on a host-only context, in front of its BSRNN_ESTATE): a null ctx, buffer or length array;
+ * R or n_clips < 1; a row count < 1; a length <= 1024 or > wave_stride (the text names the row or the clip and the value); R * Tmax beyond
+ * bsrnn_separate_ragged's limit.
+ *
+ * bsrnn_stft_ragged: wave_dev -> x_dev [R, 2050, Tmax].  Row r, frames t < T_r: bit-identical to bsrnn_stft of that clip alone (reflect
+ *     padding at the clip's own end); frames t >= T_r are written as zeros.
+ * bsrnn_istft_ragged: y_dev [R, 2050, Tmax] -> wave_out_dev [R, (Tmax-1)*1024].  Row r gets the n_est_r samples bsrnn_istft gives for
+ *     y[r, :, :T_r] (bit-identical), then zeros; what y holds in frames t >= T_r is not used.
+ * bsrnn_istft_ragged_backward: the transpose of bsrnn_istft_ragged, row by row.  dwave_dev [R, (Tmax-1)*1024] -> dy_dev [R, 2050, Tmax]:
+ *     dy[r, :, t < T_r] is what bsrnn_istft_backward gives for dwave[r, :n_est_r] with T_r frames (the same three passes: bit-identical),
+ *     dy[r, :, t >= T_r] = 0, the imaginary parts of bins 0 and 1024 are 0; dwave[r, i >= n_est_r] is never read. */
+int  bsrnn_stft_ragged(bsrnn_ctx* ctx, const float* wave_dev, int64_t wave_stride, const int64_t* lens_host, float* x_dev, int32_t R,
+                       void* stream);
+int  bsrnn_istft_ragged(bsrnn_ctx* ctx, const float* y_dev, const int64_t* lens_host, float* wave_out_dev, int32_t R, void* stream);
+int  bsrnn_istft_ragged_backward(bsrnn_ctx* ctx, const float* dwave_dev, const int64_t* lens_host, float* dy_dev, int32_t R, void* stream);
+/* bsrnn_train_loss_ragged: the L1 tri-loss and the SDR of `train_infer` (m_dataset.py:202-217) PER CLIP.  Clips as bsrnn_evaluate_ragged's:
+ *     clip c owns clip_rows_host[c] >= 1 consecutive rows of clip_lens_host[c] samples (NULL: one row per clip).  y_dev (the model's
+ *     output) and s_dev (the clean signal's spectrum) are [R, 2050, Tmax], xtime_dev is [R, (Tmax-1)*1024], speech_dev rows are wave_stride
+ *     floats apart.  values_dev, double [n_clips][BSRNN_N_TRAIN_VALUES], receives LOSS, L1_TIME, L1_RE, L1_IM and SDR exactly as
+ *     bsrnn_evaluate_ragged defines them for that clip alone (the means divide by rows * n_est and rows * 1025 * T; SDR is the mean over the
+ *     clip's rows); row_sums_dev, double [R][2], receives sum s^2 and sum (x - s)^2 of each row for the backward call.  What the tensors
+ *     hold behind a row's frames or samples never reaches a result.  Differences in fp32, sums in double in a fixed order: a second run is
+ *     bit-identical.
+ * bsrnn_train_loss_ragged_backward: the same tensors and tables, row_sums_dev as the forward call left it, and gclip_dev, float
+ *     [n_clips][2]: the upstream gradient of each clip's LOSS and of its SDR.  Writes ALL of dy_dev [R, 2050, Tmax] and dxtime_dev
+ *     [R, (Tmax-1)*1024]:
+ *       dy[r, c, t]  = gL sgn(y - s) / (rows * 1025 * T)                                      for t < T_r, else 0   (sgn(0) = 0)
+ *       dxtime[r, i] = gL sgn(x - s) / (rows * n_est) - gS (10 / ln 10) 2 (x - s) / (rows * (sum (x - s)^2_r + 1e-9))   for i < n_est_r, else 0 */
+#define BSRNN_TV_LOSS          0
+#define BSRNN_TV_L1_TIME       1
+#define BSRNN_TV_L1_RE         2
+#define BSRNN_TV_L1_IM         3
+#define BSRNN_TV_SDR           4
+#define BSRNN_N_TRAIN_VALUES   5
+int  bsrnn_train_loss_ragged(bsrnn_ctx* ctx, const float* y_dev, const float* s_dev, const float* xtime_dev, const float* speech_dev,
+                             int64_t wave_stride, const int64_t* clip_lens_host, const int32_t* clip_rows_host, int32_t n_clips,
+                             double* values_dev, double* row_sums_dev, void* stream);
+int  bsrnn_train_loss_ragged_backward(bsrnn_ctx* ctx, const float* y_dev, const float* s_dev, const float* xtime_dev,
+                                      const float* speech_dev, int64_t wave_stride, const int64_t* clip_lens_host,
+                                      const int32_t* clip_rows_host, int32_t n_clips, const double* row_sums_dev, const float* gclip_dev,
+                                      float* dy_dev, float* dxtime_dev, void* stream);
+
 /* ---- streaming (infer-streaming.py:84-147; speech-ladspa-onnx.cpp:171-267) -------------
  * A bsrnn_stream owns, on the device, the sliding 2048-sample analysis buffer, the LSTM
  * state [4,2,C*K,64] and the previous synthesis frame for C rows.

@@ -26,6 +26,7 @@ SYMBOLS = [
     "bsrnn_set_range_policy", "bsrnn_get_range_policy", "bsrnn_overlap_state", "bsrnn_debug_peek", "bsrnn_debug_counter",
     "bsrnn_stream_process", "bsrnn_stream_reserve", "bsrnn_separate_long", "bsrnn_separate_long_host", "bsrnn_workspace_rows",
     "bsrnn_separate_ragged", "bsrnn_evaluate_ragged", "bsrnn_separate_long_ragged",
+    "bsrnn_stft_ragged", "bsrnn_istft_ragged", "bsrnn_istft_ragged_backward", "bsrnn_train_loss_ragged", "bsrnn_train_loss_ragged_backward",
     "bsrnn_stream_process_rows", "bsrnn_stream_process_hops", "bsrnn_stream_reset_rows", "bsrnn_stream_row_floats", "bsrnn_stream_get_row", "bsrnn_stream_set_row",
     "bsrnn_resample_len", "bsrnn_resample", "bsrnn_resampler_create", "bsrnn_resampler_destroy", "bsrnn_resampler_reset",
     "bsrnn_resampler_ready", "bsrnn_resampler_process", "bsrnn_resampler_flush",
@@ -36,6 +37,7 @@ RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
 STREAM_HOPS_MAX = 255                       # BSRNN_STREAM_HOPS_MAX
 BANK_PAIRS_MAX = 16                         # BSRNN_BANK_PAIRS_MAX
+TRAIN_VALUE_NAMES = ("loss", "l1_time", "l1_re", "l1_im", "sdr")     # BSRNN_TV_* order
 METRIC_NAMES = ("loss", "sdr", "input_sdr", "sisdr", "l1_time", "l1_re", "l1_im", "separation_db")   # BSRNN_M_* order
 
 
@@ -140,6 +142,11 @@ def _load():
         "bsrnn_sync": (C.c_int, [vp, vp]),
         "bsrnn_evaluate": (C.c_int, [vp, vp, vp, i32, i64, vp, C.POINTER(C.c_double), vp]),
         "bsrnn_evaluate_ragged": (C.c_int, [vp, vp, vp, i64, vp, vp, i32, vp, C.POINTER(C.c_double), vp]),
+        "bsrnn_stft_ragged": (C.c_int, [vp, vp, i64, vp, vp, i32, vp]),
+        "bsrnn_istft_ragged": (C.c_int, [vp, vp, vp, vp, i32, vp]),
+        "bsrnn_istft_ragged_backward": (C.c_int, [vp, vp, vp, vp, i32, vp]),
+        "bsrnn_train_loss_ragged": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, vp]),
+        "bsrnn_train_loss_ragged_backward": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp]),
         "bsrnn_io_count": (C.c_int, []),
         "bsrnn_io_info": (C.c_int, [vp, i32, i32, C.POINTER(C.c_char_p), C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]),
     }

@@ -193,12 +193,14 @@ struct bsrnn_ctx {
     // every call, and a cached table per frame-row count would make first-use work the rule and flush the bounded cache.)  The copy reads a
     // pinned mirror; there are RG_SLOTS of them, used in turn, and mirror k is written again only when the copy that read it has completed
     // (ev[k]), so the caller's array is free when the call returns and calls still queue up behind each other.  Grow-only.
-    static constexpr int RG_SLOTS = 4;
+    // (Eight mirrors: the six ragged calls of one training step - two analyses, the synthesis, the loss and the two backward calls - queue up
+    // without the host waiting for a copy of the same step.)
+    static constexpr int RG_SLOTS = 8;
     struct Ragged {
         size_t cap = 0;                               // bytes of the device block and of each mirror
         char *d = nullptr, *h = nullptr;              // h: RG_SLOTS mirrors of cap bytes
         unsigned calls = 0;
-        hipEvent_t ev[RG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+        hipEvent_t ev[RG_SLOTS] = {};
     } rg;
 
     // Ragged evaluate (bsrnn_evaluate_ragged): the metric kernels' table [R int64 row lengths | n_clips MetricClip] travels like the block
@@ -209,7 +211,7 @@ struct bsrnn_ctx {
         size_t cap = 0;                               // bytes of the table on the device and of each mirror
         char *d = nullptr, *h = nullptr;
         unsigned calls = 0;
-        hipEvent_t ev[RG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+        hipEvent_t ev[RG_SLOTS] = {};
         size_t part_cap = 0, est_cap = 0;             // doubles / floats the scratch holds
         double *d_part = nullptr, *h_part = nullptr;
         float* d_est = nullptr;
@@ -1637,18 +1639,13 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
 // DSP ends told the rows' lengths (fft.hip: the padded frames go in as zero rows, the padded hops come out as zeros); every stage between
 // them runs as for a rectangular call, the overlapped dual path included.
 
-// This call's block (bsrnn_ctx::Ragged) for R rows of M = R * Tmax frame rows, copied in on stream s; where its parts are on the device.
-static int ragged_upload(bsrnn_ctx* c, const int64_t* lens, int R, int M, hipStream_t s, Part& p)
+// The transport of the context's block (bsrnn_ctx::Ragged): `bytes` of it, written into the next pinned mirror by fill(mirror) and copied to
+// the device on stream s in front of the call's kernels.  Returns where the block is on the device.
+extern "C++" {
+template <class FILL>
+static int ragged_upload_block(bsrnn_ctx* c, size_t bytes, hipStream_t s, FILL fill, const char** d_block)
 {
     bsrnn_ctx::Ragged& rg = c->rg;
-    std::vector<ChainTask> tk[2];
-    const size_t b_lens = (size_t)R * sizeof(int64_t);
-    size_t off[2], bytes = b_lens;
-    for (int ch = 0; ch < 2; ++ch) {
-        if (c->fused) build_chain_tasks(c->h_chain[ch], M, tk[ch]);
-        off[ch] = bytes;
-        bytes += (tk[ch].size() + 1) * sizeof(int2);                  // (one entry of slack, as upload_table's)
-    }
     if (bytes > rg.cap) {
         HIP_TRY(hipDeviceSynchronize());                              // queued copies read the old mirrors, queued kernels the old block
         if (rg.d) { (void)hipFree(rg.d); (void)hipHostFree(rg.h); rg.d = rg.h = nullptr; rg.cap = 0; }
@@ -1664,18 +1661,47 @@ static int ragged_upload(bsrnn_ctx* c, const int64_t* lens, int R, int M, hipStr
     const int k = (int)(rg.calls++ % bsrnn_ctx::RG_SLOTS);
     HIP_TRY(hipEventSynchronize(rg.ev[k]));                           // (the copy of RG_SLOTS calls ago; an event never recorded counts as complete)
     char* h = rg.h + (size_t)k * rg.cap;
-    memcpy(h, lens, b_lens);
-    for (int ch = 0; ch < 2; ++ch) {
-        memcpy(h + off[ch], tk[ch].data(), tk[ch].size() * sizeof(int2));
-        memset(h + off[ch] + tk[ch].size() * sizeof(int2), 0, sizeof(int2));
-    }
+    fill(h);
     HIP_TRY(hipMemcpyAsync(rg.d, h, bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(rg.ev[k], s));
-    p.lens = reinterpret_cast<const int64_t*>(rg.d);
+    *d_block = rg.d;
+    return 0;
+}
+}  // extern "C++"
+// This call's block for R rows of M = R * Tmax frame rows, copied in on stream s; where its parts are on the device.
+static int ragged_upload(bsrnn_ctx* c, const int64_t* lens, int R, int M, hipStream_t s, Part& p)
+{
+    std::vector<ChainTask> tk[2];
+    const size_t b_lens = (size_t)R * sizeof(int64_t);
+    size_t off[2], bytes = b_lens;
     for (int ch = 0; ch < 2; ++ch) {
-        p.tasks[ch] = c->fused ? reinterpret_cast<const int2*>(rg.d + off[ch]) : nullptr;
+        if (c->fused) build_chain_tasks(c->h_chain[ch], M, tk[ch]);
+        off[ch] = bytes;
+        bytes += (tk[ch].size() + 1) * sizeof(int2);                  // (one entry of slack, as upload_table's)
+    }
+    const char* d = nullptr;
+    const int rc = ragged_upload_block(c, bytes, s, [&](char* h) {
+        memcpy(h, lens, b_lens);
+        for (int ch = 0; ch < 2; ++ch) {
+            memcpy(h + off[ch], tk[ch].data(), tk[ch].size() * sizeof(int2));
+            memset(h + off[ch] + tk[ch].size() * sizeof(int2), 0, sizeof(int2));
+        }
+    }, &d);
+    if (rc) return rc;
+    p.lens = reinterpret_cast<const int64_t*>(d);
+    for (int ch = 0; ch < 2; ++ch) {
+        p.tasks[ch] = c->fused ? reinterpret_cast<const int2*>(d + off[ch]) : nullptr;
         p.n_tasks[ch] = (int)tk[ch].size();
     }
+    return 0;
+}
+// The lengths alone, for the calls that run no model stage (the ragged DSP and loss calls of a training step need no chain task tables)
+static int ragged_upload_lens(bsrnn_ctx* c, const int64_t* lens, int R, hipStream_t s, const int64_t** d_lens)
+{
+    const char* d = nullptr;
+    const size_t b_lens = (size_t)R * sizeof(int64_t);
+    if (int rc = ragged_upload_block(c, b_lens, s, [&](char* h) { memcpy(h, lens, b_lens); }, &d)) return rc;
+    *d_lens = reinterpret_cast<const int64_t*>(d);
     return 0;
 }
 
@@ -1721,6 +1747,158 @@ int bsrnn_separate_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_stride, 
     };
     if ((rc = run())) return rc;
     return finish_call(c, s, run);
+}
+
+// --------------------------------------------------------------------------- ragged training step: the DSP ends and the loss told the lengths
+// The clips of one optimizer step as one rectangle R x Tmax through the training kernels: x = 0 in the padded frames and y = x * mask, so
+// those frames carry neither value nor gradient, and between the two DSP ends the step runs as for a rectangular batch.  What knows the
+// lengths: the ragged analysis and synthesis at the [R, 2050, Tmax] boundary autograd works on, the synthesis' transpose, and the loss, whose
+// means and gradients are per clip.  None of these calls waits for the device; each uploads its lengths (the loss calls their clip table)
+// through the context's block, in stream order.
+static_assert(TV_LOSS == BSRNN_TV_LOSS && TV_L1_TIME == BSRNN_TV_L1_TIME && TV_L1_RE == BSRNN_TV_L1_RE && TV_L1_IM == BSRNN_TV_L1_IM &&
+              TV_SDR == BSRNN_TV_SDR && TV_COUNT == BSRNN_N_TRAIN_VALUES, "train_ragged_host.h");
+
+// The argument checks the three DSP calls share (stride: what a length may not exceed; INT64_MAX where rows have no input stride)
+static int ragged_dsp_check(const char* who, const bsrnn_ctx* c, bool have_buffers, const int64_t* lens, int R, int64_t stride, RaggedShape& q)
+{
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!have_buffers || !lens || R < 1) return fail(BSRNN_EARG, "%s: need both buffers, R lengths and R >= 1, got R = %d", who, R);
+    q = ragged_shape(lens, R, stride);
+    if (q.why == RAGGED_SHORT) return fail(BSRNN_EARG, "%s: row %d has %lld samples, need more than 1024 (reflect padding)", who, q.bad_row, (long long)q.bad_len);
+    if (q.why == RAGGED_LONG)
+        return fail(BSRNN_EARG, "%s: row %d has %lld samples, more than the row stride of %lld", who, q.bad_row, (long long)q.bad_len, (long long)stride);
+    if (ragged_too_many(R, q.Tmax)) return fail(BSRNN_EARG, "%s: %d rows x %lld frames is too many frame rows for one call", who, R, (long long)q.Tmax);
+    return 0;
+}
+
+int bsrnn_stft_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_stride, const int64_t* lens_host, float* x, int32_t R, void* stream)
+{
+    RaggedShape q;
+    if (int rc0 = ragged_dsp_check("bsrnn_stft_ragged", c, wave && x, lens_host, R, wave_stride, q)) return rc0;
+    if (int rc0 = check_device(c)) return rc0;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const int T = (int)q.Tmax;
+    if (int rc = ensure_ws(c, (size_t)R * T)) return rc;
+    const int64_t* d_lens = nullptr;
+    if (int rc = ragged_upload_lens(c, lens_host, R, s, &d_lens)) return rc;
+    { StageScope sc(c, ST_STFT, s); launch_stft_ragged(c->tb, wave, wave_stride, d_lens, c->Xf, R, T, s); }
+    { StageScope sc(c, ST_LAYOUT, s); launch_from_frame_major(c->tb, c->Xf, x, R, T, s); }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int bsrnn_istft_ragged(bsrnn_ctx* c, const float* y, const int64_t* lens_host, float* wave_out, int32_t R, void* stream)
+{
+    RaggedShape q;
+    if (int rc0 = ragged_dsp_check("bsrnn_istft_ragged", c, y && wave_out, lens_host, R, INT64_MAX, q)) return rc0;
+    if (int rc0 = check_device(c)) return rc0;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const int T = (int)q.Tmax;
+    if (int rc = ensure_ws(c, (size_t)R * T)) return rc;
+    const int64_t* d_lens = nullptr;
+    if (int rc = ragged_upload_lens(c, lens_host, R, s, &d_lens)) return rc;
+    { StageScope sc(c, ST_LAYOUT, s); launch_to_frame_major(c->tb, y, c->Yf, R, T, s); }
+    { StageScope sc(c, ST_ISTFT, s); launch_istft_ragged(c->tb, c->Yf, wave_out, q.out_stride, d_lens, R, T, s); }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int bsrnn_istft_ragged_backward(bsrnn_ctx* c, const float* dwave, const int64_t* lens_host, float* dy, int32_t R, void* stream)
+{
+    RaggedShape q;
+    if (int rc0 = ragged_dsp_check("bsrnn_istft_ragged_backward", c, dwave && dy, lens_host, R, INT64_MAX, q)) return rc0;
+    if (int rc0 = check_device(c)) return rc0;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const int T = (int)q.Tmax;
+    if (int rc = ensure_ws(c, (size_t)R * T)) return rc;
+    float* ws = train_scratch(c, (size_t)R * q.out_stride);
+    if (!ws) return fail(BSRNN_EHIP, "bsrnn_istft_ragged_backward: out of device memory");
+    const int64_t* d_lens = nullptr;
+    if (int rc = ragged_upload_lens(c, lens_host, R, s, &d_lens)) return rc;
+    launch_istft_ragged_backward(c->tb, dwave, ws, c->Yf, d_lens, R, T, s);
+    launch_from_frame_major(c->tb, c->Yf, dy, R, T, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The clip table of the two loss calls, checked and uploaded: [R int64 row lengths | n_clips TrainClip | R int32 row -> clip]
+struct TrainTableDev { const int64_t* lens; const TrainClip* clips; const int32_t* row_clip; };
+static int train_table_check(const char* who, const bsrnn_ctx* c, bool have_buffers, const int64_t* clip_lens, const int32_t* clip_rows, int n_clips,
+                             int64_t wave_stride, TrainClipTable& t)
+{
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!have_buffers || !clip_lens || n_clips < 1)
+        return fail(BSRNN_EARG, "%s: need every tensor, the clips' lengths and n_clips >= 1, got n_clips = %d", who, n_clips);
+    t = train_clip_table(clip_lens, clip_rows, n_clips, wave_stride);
+    const ClipShape& q = t.shape;
+    if (q.why == CLIPS_ROWS) return fail(BSRNN_EARG, "%s: clip %d has %lld rows, need at least 1", who, q.bad_clip, (long long)q.bad_value);
+    if (q.why == CLIPS_SHORT)
+        return fail(BSRNN_EARG, "%s: clip %d has %lld samples, need more than 1024 (reflect padding)", who, q.bad_clip, (long long)q.bad_value);
+    if (q.why == CLIPS_LONG)
+        return fail(BSRNN_EARG, "%s: clip %d has %lld samples, more than the row stride of %lld", who, q.bad_clip, (long long)q.bad_value,
+                    (long long)wave_stride);
+    if (q.why == CLIPS_MANY) return fail(BSRNN_EARG, "%s: %lld rows x %lld frames is too many frame rows for one call", who, (long long)q.R, (long long)q.Tmax);
+    return 0;
+}
+static int train_table_upload(bsrnn_ctx* c, const TrainClipTable& t, hipStream_t s, TrainTableDev& dv)
+{
+    const int64_t R = t.shape.R;
+    const int n_clips = (int)t.clips.size();
+    const char* d = nullptr;
+    const int rc = ragged_upload_block(c, train_table_bytes(R, n_clips), s, [&](char* h) {
+        memcpy(h, t.row_lens.data(), (size_t)R * sizeof(int64_t));
+        memcpy(h + train_table_clips_at(R), t.clips.data(), (size_t)n_clips * sizeof(TrainClip));
+        memcpy(h + train_table_map_at(R, n_clips), t.row_clip.data(), (size_t)R * sizeof(int32_t));
+    }, &d);
+    if (rc) return rc;
+    dv.lens = reinterpret_cast<const int64_t*>(d);
+    dv.clips = reinterpret_cast<const TrainClip*>(d + train_table_clips_at(R));
+    dv.row_clip = reinterpret_cast<const int32_t*>(d + train_table_map_at(R, n_clips));
+    return 0;
+}
+
+int bsrnn_train_loss_ragged(bsrnn_ctx* c, const float* y, const float* sfreq, const float* xtime, const float* speech, int64_t wave_stride,
+                            const int64_t* clip_lens_host, const int32_t* clip_rows_host, int32_t n_clips, double* values, double* row_sums,
+                            void* stream)
+{
+    TrainClipTable t;
+    if (int rc0 = train_table_check("bsrnn_train_loss_ragged", c, y && sfreq && xtime && speech && values && row_sums, clip_lens_host, clip_rows_host,
+                                    n_clips, wave_stride, t))
+        return rc0;
+    if (int rc0 = check_device(c)) return rc0;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const int R = (int)t.shape.R, T = (int)t.shape.Tmax;
+    const size_t n_part = train_loss_partials(R, T);
+    float* ws = train_scratch(c, 2 * n_part);                           // (doubles)
+    if (!ws) return fail(BSRNN_EHIP, "bsrnn_train_loss_ragged: out of device memory");
+    TrainTableDev dv;
+    if (int rc = train_table_upload(c, t, s, dv)) return rc;
+    launch_train_loss_ragged(y, sfreq, xtime, speech, dv.lens, dv.clips, n_clips, R, T, wave_stride, reinterpret_cast<double*>(ws), values, row_sums, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int bsrnn_train_loss_ragged_backward(bsrnn_ctx* c, const float* y, const float* sfreq, const float* xtime, const float* speech, int64_t wave_stride,
+                                     const int64_t* clip_lens_host, const int32_t* clip_rows_host, int32_t n_clips, const double* row_sums,
+                                     const float* gclip, float* dy, float* dxtime, void* stream)
+{
+    TrainClipTable t;
+    if (int rc0 = train_table_check("bsrnn_train_loss_ragged_backward", c, y && sfreq && xtime && speech && row_sums && gclip && dy && dxtime,
+                                    clip_lens_host, clip_rows_host, n_clips, wave_stride, t))
+        return rc0;
+    if (int rc0 = check_device(c)) return rc0;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    TrainTableDev dv;
+    if (int rc = train_table_upload(c, t, s, dv)) return rc;
+    launch_train_loss_ragged_backward(y, sfreq, xtime, speech, dv.lens, dv.clips, dv.row_clip, gclip, row_sums, (int)t.shape.R, (int)t.shape.Tmax,
+                                      wave_stride, dy, dxtime, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // --------------------------------------------------------------------------- long-form separation: the sandwich in segments

@@ -1049,6 +1049,83 @@ void launch_istft_ragged(const FftTables& tb, const float* Y, float* out, int64_
     hipLaunchKernelGGL(istft_ragged_kernel, ch.grid, dim3(256), 0, s, tb, Y, out, out_stride, lens, Tmax, ch.len);
 }
 
+// ------------------------------------------------------------------------------ backward of the ragged iSTFT (ragged training step)
+// The transpose of istft_ragged_kernel, row by row: launch_istft_backward's three passes with the row's own bounds.  Row r of dwave (rows
+// `stride` floats apart) carries gradient in its first n_est_r = (T_r - 1) * 1024 samples; what lies behind them is never read.
+//   1. g[r][i] = dwave[r][i] / envelope, i < n_est_r only (the arithmetic of istft_bwd_prescale_kernel);
+//   2. the ZERO_PAD analysis of g on frames t < T_r with the bound n_est_r - stft_walk, as stft_kernel<true> runs it, so a frame that both
+//      compute has the same bits - and zero rows for frames T_r <= t < Tmax, in all ld columns;
+//   3. the bin weights of istft_bwd_postscale_kernel on frames t < T_r only (the padded rows stay the zeros of pass 2).
+// Row and chunk belong to the workgroup in all three, so every length condition is workgroup-uniform.
+__global__ __launch_bounds__(256) void istft_ragged_bwd_prescale_kernel(FftTables tb, const float* __restrict__ dwave, float* __restrict__ g,
+                                                                        int64_t stride, const int64_t* __restrict__ lens)
+{
+    const int r = blockIdx.y;
+    const int64_t hops = lens[r] / HOPS;                               // n_est_r / 1024
+    const float* src = dwave + (size_t)r * stride;
+    float* dst = g + (size_t)r * stride;
+    for (int64_t b = blockIdx.x; b < hops; b += gridDim.x)
+        for (int j = threadIdx.x; j < HOPS; j += 256) {
+            const float w0 = tb.hann[j], w1 = tb.hann[j + HOPS];
+            dst[b * HOPS + j] = src[b * HOPS + j] / (w0 * w0 + w1 * w1);
+        }
+}
+__global__ __launch_bounds__(256, FFT_OCC_STFT) void stft_ragged_zero_pad_kernel(FftTables tb, const float* __restrict__ g, float* __restrict__ X,
+                                                                                 int64_t stride, const int64_t* __restrict__ lens, int Tmax, int sch)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const int r = blockIdx.y;
+    const int Tr = 1 + (int)(lens[r] / HOPS);
+    const int64_t n = (int64_t)(Tr - 1) * HOPS;                        // n_est_r: samples outside [0, n) are zeros
+    const int t0 = blockIdx.x * sch;
+    const int te = (t0 + sch < Tmax) ? t0 + sch : Tmax;               // the chunk: frames [t0, te) of the rectangle
+    const int t1 = te < Tr ? te : Tr;                                 // its real frames: [t0, t1), none when t1 <= t0
+    float* Xr = X + (size_t)r * Tmax * tb.ld;
+    if (t0 < t1) {
+        const float* src = g + (size_t)r * stride;
+        auto sample2 = [&](int t, int c) {
+            float v[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int64_t idx = (int64_t)t * HOPS + 2 * c + e - NFFT / 2;
+                v[e] = (idx >= 0 && idx < n) ? src[idx] : 0.f;
+            }
+            return make_float2(v[0], v[1]);
+        };
+        auto row = [&](int t) { return Xr + (size_t)t * tb.ld; };
+        stft_walk(tb, z0, z1, tid, t0, t1, sample2, row);
+    }
+    for (int t = t0 > t1 ? t0 : t1; t < te; ++t) {
+        float4* row = reinterpret_cast<float4*>(Xr + (size_t)t * tb.ld);
+        for (int i = tid; i < tb.ld / 4; i += 256) row[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+// grid (Tmax, R): one frame row per workgroup
+__global__ __launch_bounds__(256) void istft_ragged_bwd_postscale_kernel(FftTables tb, float* __restrict__ X, const int64_t* __restrict__ lens, int Tmax)
+{
+    const int r = blockIdx.y, t = blockIdx.x;
+    if (t >= 1 + (int)(lens[r] / HOPS)) return;
+    float* row = X + ((size_t)r * Tmax + t) * tb.ld;
+    for (int k = threadIdx.x; k < NBINS; k += 256) {
+        float* p = row + tb.colmap[k];
+        const bool edge = k == 0 || k == NBINS - 1;
+        const float sc = (edge ? 1.0f : 2.0f) / (float)NFFT;
+        p[0] *= sc;
+        p[1] = edge ? 0.f : p[1] * sc;
+    }
+}
+void launch_istft_ragged_backward(const FftTables& tb, const float* dwave, float* scratch, float* dY, const int64_t* lens, int R, int Tmax, hipStream_t s)
+{
+    if (Tmax < 2) return;
+    const int64_t stride = (int64_t)(Tmax - 1) * HOPS;
+    const int pre = Tmax - 1 < 64 ? Tmax - 1 : 64;
+    hipLaunchKernelGGL(istft_ragged_bwd_prescale_kernel, dim3(pre, R), dim3(256), 0, s, tb, dwave, scratch, stride, lens);
+    const Chunks ch = chunks_for<stft_ragged_zero_pad_kernel>(Tmax, R, 0);
+    hipLaunchKernelGGL(stft_ragged_zero_pad_kernel, ch.grid, dim3(256), 0, s, tb, scratch, dY, stride, lens, Tmax, ch.len);
+    hipLaunchKernelGGL(istft_ragged_bwd_postscale_kernel, dim3(Tmax, R), dim3(256), 0, s, tb, dY, lens, Tmax);
+}
+
 // ------------------------------------------------------------------------------ offline DSP, one segment of rows of different lengths
 // The two pairs above put together for frames [ta, te) of a ragged batch (bsrnn_separate_long_ragged): a segment's bounds AND a row's own.
 // Both kernels run the shared walks, so a frame or a hop that one of the other pairs computes too has the same bits; row and chunk belong

@@ -6,6 +6,7 @@
 #include "descriptors.h"   // GemmJob, ChainDesc and the constants the host packs against (HIP-free)
 #include "stream_rows_host.h"   // RowSet: the rows a streaming rows call means, by value (HIP-free)
 #include "resample_bank_host.h" // BankRow: what a resampler bank's kernel knows of a row, by value (HIP-free)
+#include "train_ragged_host.h"  // TrainClip: what the ragged training loss kernels know of a clip (HIP-free)
 
 namespace bsrnn {
 
@@ -275,6 +276,10 @@ void launch_long_compact(const float* state_src, float* state_dst, const float* 
 // gradient of launch_istft's output w.r.t. its input (training step): dwave [R][(T-1)*1024] -> dY frame-major [R*T][ld];
 // scratch [R][(T-1)*1024]
 void launch_istft_backward(const FftTables& tb, const float* dwave, float* scratch, float* dY, int R, int T, hipStream_t s);
+// the same for launch_istft_ragged's output, row by row: dwave, scratch [R][(Tmax-1)*1024] (row r read / written below n_est_r only) ->
+// dY frame-major [R*Tmax][ld], zero rows for frames t >= T_r
+void launch_istft_ragged_backward(const FftTables& tb, const float* dwave, float* scratch, float* dY, const int64_t* lens, int R, int Tmax,
+                                  hipStream_t s);
 // [C][2050][T] (reference layout) <-> [C*T][ld] (band-padded)
 void launch_to_frame_major(const FftTables& tb, const float* x, float* xf, int C, int T, hipStream_t s);
 void launch_from_frame_major(const FftTables& tb, const float* yf, float* y, int C, int T, hipStream_t s);
@@ -338,6 +343,17 @@ void launch_metric_input_sdr_ragged(const float* speech, const float* mix, const
                                     double* part /* [n_clips][blocks] */, int blocks, hipStream_t s);
 void launch_metric_freq_ragged(const FftTables& tb, const float* Yf, const float* Sf, const int64_t* lens, int R, int Tmax,
                                double* part /* [R][blocks][2] */, int blocks, hipStream_t s);
+// The tri-loss and the SDR of a ragged training step per clip, and their gradients (bsrnn_train_loss_ragged / _backward; the clip table:
+// train_ragged_host.h).  y, sfreq, dy [R][2050][Tmax] in the reference layout; xtime, dxtime [R][(Tmax-1)*1024]; speech rows wave_stride
+// floats apart; lens [R], clips [n_clips], row_clip [R], gclip [n_clips][2] on the device.  The forward leaves values [n_clips][TV_COUNT] and
+// row_sums [R][2] (doubles, on the device) and needs train_loss_partials(R, Tmax) doubles of scratch; the backward writes all of dy and dxtime.
+size_t train_loss_partials(int R, int Tmax);
+void launch_train_loss_ragged(const float* y, const float* sfreq, const float* xtime, const float* speech, const int64_t* lens,
+                              const TrainClip* clips, int n_clips, int R, int Tmax, int64_t wave_stride, double* part, double* values,
+                              double* row_sums, hipStream_t s);
+void launch_train_loss_ragged_backward(const float* y, const float* sfreq, const float* xtime, const float* speech, const int64_t* lens,
+                                       const TrainClip* clips, const int32_t* row_clip, const float* gclip, const double* row_sums, int R,
+                                       int Tmax, int64_t wave_stride, float* dy, float* dxtime, hipStream_t s);
 
 // ------------------------------------------------------------------ sample-rate conversion (resample.hip; the definition: resample_host.h)
 // One launch serves bsrnn_resample and the streaming resampler.  The input of row r is the concatenation of two segments - a [a0, a1),

@@ -220,7 +220,240 @@ __global__ __launch_bounds__(256) void metric_freq_ragged_kernel(const float* __
     block_reduce_store<2>(q, part + ((size_t)r * gridDim.x + blockIdx.x) * 2);
 }
 
+// ------------------------------------------------------------------------------ the tri-loss of a ragged training step, forward and backward
+// bsrnn_train_loss_ragged: per clip, L1(x_time, s_time) + L1(Re Y, Re S) + L1(Im Y, Im S) and the `sdr` of train_infer (m_dataset.py:202-217),
+// on the tensors autograd holds - y, s [R][2050][Tmax] in the reference layout (T innermost), x_time [R][(Tmax-1)*1024], speech rows
+// wave_stride floats apart.  Row r has T_r frames and n_est_r samples of its own; what the rectangle holds behind them (zeros from the ragged
+// DSP, or anything) may travel inside a 16-byte load but never reaches a sum or a gradient: it is SELECTED away, never multiplied by a mask.
+// The row belongs to the workgroup, so the bounds are workgroup-uniform.  Partials as above: fp32 differences, double sums, one partial per
+// workgroup in a fixed order; train_loss_finish_kernel adds them per clip in index order, so the values are bit-reproducible and stay on the
+// device.
+
+// Time terms, grid (chunks, R) as metric_time_ragged_kernel: part [R][chunks][3] = sum s^2, sum (x-s)^2, sum |x-s| over i < n_est_r
+constexpr int TRAIN_TIME_Q = 3;
+__global__ __launch_bounds__(256) void train_loss_time_ragged_kernel(const float* __restrict__ xtime, const float* __restrict__ speech,
+                                                                     const int64_t* __restrict__ lens, int64_t out_stride, int64_t wave_stride,
+                                                                     int vec, double* __restrict__ part)
+{
+    const int r = blockIdx.y;
+    const int64_t n_est = lens[r] / HOPS * HOPS;
+    const float* x = xtime + (size_t)r * out_stride;
+    const float* s = speech + (size_t)r * wave_stride;
+    double q[TRAIN_TIME_Q] = {0, 0, 0};
+    auto one = [&](float xv, float sv) {
+        const float d = xv - sv;
+        q[0] += (double)sv * sv; q[1] += (double)d * d; q[2] += (double)__builtin_fabsf(d);
+    };
+    // vec: every row of both signals starts 16-byte aligned (the host checks the bases and wave_stride % 4; out_stride and n_est are
+    // multiples of 1024, so no vector straddles a row's end)
+    const int64_t n4 = vec ? n_est / 4 : 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const v4f xv = *reinterpret_cast<const v4f*>(x + 4 * i);
+        const v4f sv = *reinterpret_cast<const v4f*>(s + 4 * i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) one(xv[j], sv[j]);
+    }
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_est; i += (int64_t)gridDim.x * 256) one(x[i], s[i]);
+    block_reduce_store<TRAIN_TIME_Q>(q, part + ((size_t)r * gridDim.x + blockIdx.x) * TRAIN_TIME_Q);
+}
+
+// A workgroup's share of one row of a [R][2050][Tmax] tensor: the interleaved columns [f0, f0 + nf) - a contiguous span of n = nf * Tmax
+// floats at `base`.  Visits every element once, in a fixed order per thread: scalars up to the first 16-byte boundary, then whole vectors
+// (four(j): elements j .. j + 3), then the scalar tail.  vec = 0: scalars only.  n < 2^31 (the launcher picks nf so).
+template <class F4, class F1>
+__device__ __forceinline__ void walk_span(size_t base, int n, int vec, F4 four, F1 one)
+{
+    int head = vec ? (int)((4 - (base & 3)) & 3) : n;
+    if (head > n) head = n;
+    // (the loop vectorizer is kept off the scalar loops: it turns two iterations of a gradient into packed fp32, which a kernel without
+    // MFMA must not contain - tests/test_code_audit.py)
+#pragma clang loop vectorize(disable) interleave(disable)
+    for (int j = threadIdx.x; j < head; j += 256) one(j);
+    const int n4 = (n - head) / 4;
+    for (int i = threadIdx.x; i < n4; i += 256) four(head + 4 * i);
+#pragma clang loop vectorize(disable) interleave(disable)
+    for (int j = head + 4 * n4 + threadIdx.x; j < n; j += 256) one(j);
+}
+
+// Spectral terms, grid (FB, R), nf columns per workgroup: part [R][FB][2] = sum |Re Y - Re S|, sum |Im Y - Im S| over bins x frames t < T_r
+// (an even interleaved column is a real part, an odd one an imaginary part)
+__global__ __launch_bounds__(256) void train_loss_freq_ragged_kernel(const float* __restrict__ y, const float* __restrict__ s,
+                                                                     const int64_t* __restrict__ lens, int Tmax, int nf, int vec,
+                                                                     double* __restrict__ part)
+{
+    const int r = blockIdx.y;
+    const int Tr = 1 + (int)(lens[r] / HOPS);
+    const int f0 = blockIdx.x * nf;
+    const int n = (F2 - f0 < nf ? F2 - f0 : nf) * Tmax;
+    const size_t base = ((size_t)r * F2 + f0) * Tmax;
+    const float* yp = y + base;
+    const float* sp = s + base;
+    double q[2] = {0, 0};
+    auto acc = [&](float yv, float sv, int f, int t) {
+        const double d = (double)__builtin_fabsf(yv - sv);
+        const bool real = t < Tr, odd = (f0 + f) & 1;
+        q[0] += (real && !odd) ? d : 0.0;
+        q[1] += (real && odd) ? d : 0.0;
+    };
+    walk_span(base, n, vec,
+              [&](int j) {
+                  const v4f yv = *reinterpret_cast<const v4f*>(yp + j);
+                  const v4f sv = *reinterpret_cast<const v4f*>(sp + j);
+                  int f = j / Tmax, t = j - f * Tmax;
+#pragma unroll
+                  for (int k = 0; k < 4; ++k) { acc(yv[k], sv[k], f, t); if (++t == Tmax) { t = 0; ++f; } }
+              },
+              [&](int j) { const int f = j / Tmax; acc(yp[j], sp[j], f, j - f * Tmax); });
+    block_reduce_store<2>(q, part + ((size_t)r * gridDim.x + blockIdx.x) * 2);
+}
+
+// One thread per clip: the clip's rows in order, each row's partials in index order.  values [n_clips][TV_COUNT] by finish_clip_metrics'
+// arithmetic (metrics_host.h); row_sums [R][2] = sum s^2, sum (x-s)^2 of each row, what the backward pass reads.
+__global__ __launch_bounds__(64) void train_loss_finish_kernel(const TrainClip* __restrict__ clips, int n_clips, const double* __restrict__ p_time,
+                                                               int chunks, const double* __restrict__ p_freq, int FB, double* __restrict__ values,
+                                                               double* __restrict__ row_sums)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= n_clips) return;
+    const TrainClip k = clips[c];
+    double sdr = 0, l1 = 0, re = 0, im = 0;
+    for (int r = 0; r < k.rows; ++r) {
+        const size_t row = (size_t)(k.first + r);
+        double q[TRAIN_TIME_Q] = {0, 0, 0};
+        for (int ch = 0; ch < chunks; ++ch)
+            for (int i = 0; i < TRAIN_TIME_Q; ++i) q[i] += p_time[(row * chunks + ch) * TRAIN_TIME_Q + i];
+        row_sums[row * 2] = q[0];
+        row_sums[row * 2 + 1] = q[1];
+        sdr += 10.0 * log10((q[0] + 1e-9) / (q[1] + 1e-9));
+        l1 += q[2];
+        double a = 0, b = 0;
+        for (int i = 0; i < FB; ++i) { a += p_freq[(row * FB + i) * 2]; b += p_freq[(row * FB + i) * 2 + 1]; }
+        re += a; im += b;
+    }
+    const double l1_time = l1 / ((double)k.rows * (double)k.n_est);
+    const double l1_re = re / ((double)k.rows * 1025.0 * (double)k.T);
+    const double l1_im = im / ((double)k.rows * 1025.0 * (double)k.T);
+    double* v = values + (size_t)c * TV_COUNT;
+    v[TV_LOSS] = l1_time + l1_re + l1_im;
+    v[TV_L1_TIME] = l1_time;
+    v[TV_L1_RE] = l1_re;
+    v[TV_L1_IM] = l1_im;
+    v[TV_SDR] = sdr / k.rows;
+}
+
+// d LOSS_c / d y, grid and spans as train_loss_freq_ragged_kernel: dy = gL_c * sgn(y - s) / (rows_c * 1025 * T_c) for t < T_r, else 0
+// (sgn(0) = 0, as torch's abs has it); every element of dy is written.  gclip [n_clips][2]: the upstream gradients of LOSS and SDR.
+__global__ __launch_bounds__(256) void train_loss_freq_ragged_bwd_kernel(const float* __restrict__ y, const float* __restrict__ s,
+                                                                         const int64_t* __restrict__ lens, const TrainClip* __restrict__ clips,
+                                                                         const int32_t* __restrict__ row_clip, const float* __restrict__ gclip,
+                                                                         int Tmax, int nf, int vec, float* __restrict__ dy)
+{
+    const int r = blockIdx.y;
+    const int Tr = 1 + (int)(lens[r] / HOPS);
+    const int c = row_clip[r];
+    const float w = (float)((double)gclip[2 * c] * clips[c].inv_freq);
+    const int f0 = blockIdx.x * nf;
+    const int n = (F2 - f0 < nf ? F2 - f0 : nf) * Tmax;
+    const size_t base = ((size_t)r * F2 + f0) * Tmax;
+    const float* yp = y + base;
+    const float* sp = s + base;
+    float* dp = dy + base;
+    auto grad = [&](float yv, float sv, int t) {
+        const float d = yv - sv;
+        const float g = d > 0.f ? w : (d < 0.f ? -w : 0.f);
+        return t < Tr ? g : 0.f;
+    };
+    walk_span(base, n, vec,
+              [&](int j) {
+                  const v4f yv = *reinterpret_cast<const v4f*>(yp + j);
+                  const v4f sv = *reinterpret_cast<const v4f*>(sp + j);
+                  int t = j % Tmax;
+                  float o[4];
+#pragma unroll
+                  for (int k = 0; k < 4; ++k) { o[k] = grad(yv[k], sv[k], t); if (++t == Tmax) t = 0; }
+                  *reinterpret_cast<float4*>(dp + j) = make_float4(o[0], o[1], o[2], o[3]);
+              },
+              [&](int j) { dp[j] = grad(yp[j], sp[j], j % Tmax); });
+}
+
+// d (gL_c LOSS_c + gS_c SDR_c) / d x_time, grid (chunks, R): for i < n_est_r
+//   gL_c sgn(x - s) / (rows_c n_est_c)  -  gS_c (10 / ln 10) 2 (x - s) / (rows_c (sum (x-s)^2_r + 1e-9)),
+// zeros from n_est_r to the end of the row (stored, nothing is read there); the two weights are formed once per workgroup in double.
+__global__ __launch_bounds__(256) void train_loss_time_ragged_bwd_kernel(const float* __restrict__ xtime, const float* __restrict__ speech,
+                                                                         const int64_t* __restrict__ lens, const TrainClip* __restrict__ clips,
+                                                                         const int32_t* __restrict__ row_clip, const float* __restrict__ gclip,
+                                                                         const double* __restrict__ row_sums, int64_t out_stride,
+                                                                         int64_t wave_stride, int vec, float* __restrict__ dx)
+{
+    const int r = blockIdx.y;
+    const int64_t n_est = lens[r] / HOPS * HOPS;
+    const int c = row_clip[r];
+    const TrainClip k = clips[c];
+    const float wl = (float)((double)gclip[2 * c] * k.inv_time);
+    const float ws = (float)((double)gclip[2 * c + 1] * (10.0 / 2.302585092994046) * 2.0 / ((double)k.rows * (row_sums[2 * (size_t)r + 1] + 1e-9)));
+    const float* x = xtime + (size_t)r * out_stride;
+    const float* s = speech + (size_t)r * wave_stride;
+    float* o = dx + (size_t)r * out_stride;
+    auto grad = [&](float xv, float sv) {
+        const float d = xv - sv;
+        const float g = d > 0.f ? wl : (d < 0.f ? -wl : 0.f);
+        return g - ws * d;
+    };
+    const int64_t n4 = vec ? n_est / 4 : 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const v4f xv = *reinterpret_cast<const v4f*>(x + 4 * i);
+        const v4f sv = *reinterpret_cast<const v4f*>(s + 4 * i);
+        float g[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) g[j] = grad(xv[j], sv[j]);
+        *reinterpret_cast<float4*>(o + 4 * i) = make_float4(g[0], g[1], g[2], g[3]);
+    }
+#pragma clang loop vectorize(disable) interleave(disable)             // (as in walk_span)
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_est; i += (int64_t)gridDim.x * 256) o[i] = grad(x[i], s[i]);
+    for (int64_t i = n_est + (int64_t)blockIdx.x * 256 + threadIdx.x; i < out_stride; i += (int64_t)gridDim.x * 256) o[i] = 0.f;
+}
+
 }  // namespace
+
+// Interleaved columns per workgroup of the two spectral loss kernels: about 4096 floats of a row per workgroup, at most 129 columns (16
+// workgroups per row) and never 2^31 floats
+int train_loss_freq_columns(int Tmax)
+{
+    const int nf = (4096 + Tmax - 1) / Tmax;
+    return nf < 1 ? 1 : (nf > 129 ? 129 : nf);
+}
+int train_loss_freq_blocks(int Tmax) { const int nf = train_loss_freq_columns(Tmax); return (F2 + nf - 1) / nf; }
+
+void launch_train_loss_ragged(const float* y, const float* sfreq, const float* xtime, const float* speech, const int64_t* lens,
+                              const TrainClip* clips, int n_clips, int R, int Tmax, int64_t wave_stride, double* part, double* values,
+                              double* row_sums, hipStream_t s)
+{
+    const int64_t out_stride = (int64_t)(Tmax - 1) * HOPS;
+    const int chunks = metric_time_chunks(out_stride), nf = train_loss_freq_columns(Tmax), FB = train_loss_freq_blocks(Tmax);
+    double *p_time = part, *p_freq = part + (size_t)R * chunks * TRAIN_TIME_Q;
+    // decided once per call: one row off alignment puts the whole call on scalar loads
+    const int vec_t = (wave_stride % 4 == 0) && (((uintptr_t)xtime | (uintptr_t)speech) & 15) == 0;
+    const int vec_f = (((uintptr_t)y | (uintptr_t)sfreq) & 15) == 0;
+    hipLaunchKernelGGL(train_loss_time_ragged_kernel, dim3(chunks, R), dim3(256), 0, s, xtime, speech, lens, out_stride, wave_stride, vec_t, p_time);
+    hipLaunchKernelGGL(train_loss_freq_ragged_kernel, dim3(FB, R), dim3(256), 0, s, y, sfreq, lens, Tmax, nf, vec_f, p_freq);
+    hipLaunchKernelGGL(train_loss_finish_kernel, dim3((n_clips + 63) / 64), dim3(64), 0, s, clips, n_clips, p_time, chunks, p_freq, FB, values, row_sums);
+}
+size_t train_loss_partials(int R, int Tmax)
+{
+    return (size_t)R * ((size_t)metric_time_chunks((int64_t)(Tmax - 1) * HOPS) * TRAIN_TIME_Q + (size_t)train_loss_freq_blocks(Tmax) * 2);
+}
+void launch_train_loss_ragged_backward(const float* y, const float* sfreq, const float* xtime, const float* speech, const int64_t* lens,
+                                       const TrainClip* clips, const int32_t* row_clip, const float* gclip, const double* row_sums, int R,
+                                       int Tmax, int64_t wave_stride, float* dy, float* dxtime, hipStream_t s)
+{
+    const int64_t out_stride = (int64_t)(Tmax - 1) * HOPS;
+    const int chunks = metric_time_chunks(out_stride), nf = train_loss_freq_columns(Tmax), FB = train_loss_freq_blocks(Tmax);
+    const int vec_t = (wave_stride % 4 == 0) && (((uintptr_t)xtime | (uintptr_t)speech | (uintptr_t)dxtime) & 15) == 0;
+    const int vec_f = (((uintptr_t)y | (uintptr_t)sfreq | (uintptr_t)dy) & 15) == 0;
+    hipLaunchKernelGGL(train_loss_freq_ragged_bwd_kernel, dim3(FB, R), dim3(256), 0, s, y, sfreq, lens, clips, row_clip, gclip, Tmax, nf, vec_f, dy);
+    hipLaunchKernelGGL(train_loss_time_ragged_bwd_kernel, dim3(chunks, R), dim3(256), 0, s, xtime, speech, lens, clips, row_clip, gclip, row_sums,
+                       out_stride, wave_stride, vec_t, dxtime);
+}
 
 int metric_time_chunks(int64_t n_est) { int64_t c = (n_est + 16383) / 16384; return (int)(c < 1 ? 1 : (c > 256 ? 256 : c)); }
 

@@ -98,7 +98,9 @@ class LstmLayerFunction(torch.autograd.Function):
     def backward(ctx, dh):
         x, h, gates, cells, w_ih, w_hh = ctx.saved_tensors
         dx, dw_ih, dw_hh, db = lstm_layer_backward(x, h, gates, cells, dh, w_ih, w_hh, need_dx=ctx.need_dx)
-        return dx, dw_ih, dw_hh, db, db
+        # b_ih and b_hh each get a tensor of their own: handed the same one, their .grad share its storage, and every later backward
+        # that ACCUMULATES into them (a second clip or bucket before the optimizer step) adds its bias gradient twice
+        return dx, dw_ih, dw_hh, db, db.clone()
 
 
 def stack_direction_weights(lstm, layer):
@@ -325,6 +327,199 @@ def sdr(x_time, s_time):
     n2s = torch.sum(torch.square(s_time), dim=1) + 1e-9
     n2d = torch.sum(torch.square(x_time - s_time), dim=1) + 1e-9
     return (10 * torch.log10(n2s / n2d)).mean()
+
+
+# ------------------------------------------------------------------------------------------ clips of different lengths in one pass
+# The rectangle R x Tmax of bsrnn_separate_ragged in the training direction (include/bsrnn_hip.h, "ragged training"): the model is causal
+# along time, its band-axis blocks see one frame at a time and rows are independent, and y = x * mask with x = 0 in the padded frames, so
+# `forward_train` runs unchanged; the two DSP ends and the loss are told the lengths.
+def _row_lengths(who, lengths, clip_rows, R, n_max):
+    """(lengths, rows per clip, lengths per row) as ints, or ValueError for what the library refuses."""
+    try:
+        lens = [int(x) for x in lengths]
+        rows = [1] * len(lens) if clip_rows is None else [int(x) for x in clip_rows]
+    except TypeError:
+        raise ValueError("%s: lengths and clip_rows must be sequences of ints" % who) from None
+    if not lens or len(rows) != len(lens):
+        raise ValueError("%s: %d lengths and %d row counts, need one of each per clip and at least one clip" % (who, len(lens), len(rows)))
+    for c, (n, ch) in enumerate(zip(lens, rows)):
+        if ch < 1:
+            raise ValueError("%s: clip %d has %d rows, need at least 1" % (who, c, ch))
+        if not 1024 < n <= n_max:
+            raise ValueError("%s: clip %d has %d samples, need 1024 < length <= %d" % (who, c, n, n_max))
+    if sum(rows) != R:
+        raise ValueError("%s: the clips own %d rows, the batch has %d" % (who, sum(rows), R))
+    return lens, rows, [n for n, ch in zip(lens, rows) for _ in range(ch)]
+
+
+def _i64_array(vals):
+    return (ctypes.c_int64 * len(vals))(*vals)
+
+
+def _need_cuda(t, who):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError("%s: the training kernels run on the GPU: expected a cuda tensor" % who)
+
+
+def stft_ragged(wave, lengths):
+    """`stft` for rows of different lengths: wave [R, n_max] (cuda), lengths[r] samples in row r (1024 < length <= n_max; what lies behind
+    them is never read) -> [R, 2050, Tmax], Tmax = 1 + max(lengths) // 1024.  Row r's frames below 1 + lengths[r] // 1024 are `stft` of that
+    clip alone, bit for bit; the others are zeros.  No gradient."""
+    if not isinstance(wave, torch.Tensor) or wave.dim() != 2:
+        raise ValueError("stft_ragged: expected wave [R, n_max]")
+    R, n_max = wave.shape
+    _, _, lens = _row_lengths("stft_ragged", lengths, None, R, n_max)
+    _need_cuda(wave, "stft_ragged")
+    dev = wave.device
+    w = _f32c(wave)
+    with torch.cuda.device(dev):
+        x = torch.empty((R, 2050, 1 + max(lens) // 1024), device=dev)
+        _native.check(_lib.bsrnn_stft_ragged(_context(dev), _p(w), n_max, _i64_array(lens), _p(x), R, _s(dev)))
+    return x
+
+
+class IstftRaggedFunction(torch.autograd.Function):
+    """`IstftFunction` for rows of different lengths: apply(y [R, 2050, Tmax], lengths) -> [R, (Tmax-1)*1024]; row r holds the
+    (lengths[r] // 1024) * 1024 samples of y[r, :, :T_r] alone, then zeros (bsrnn_istft_ragged).  Backward is its transpose, row by row
+    (bsrnn_istft_ragged_backward): no gradient reaches the padded frames, and none is read behind a row's samples."""
+
+    @staticmethod
+    def forward(ctx, y, lengths):
+        R, F2, T = y.shape
+        lens = [int(n) for n in lengths]
+        if len(lens) != R or T != 1 + max(lens) // 1024 or min(lens) <= 1024:
+            raise ValueError("IstftRaggedFunction: y [R, 2050, Tmax] needs R lengths > 1024 with Tmax = 1 + max(lengths) // 1024")
+        _need_cuda(y, "IstftRaggedFunction")
+        dev = y.device
+        yc = _f32c(y)
+        with torch.cuda.device(dev):
+            out = torch.empty((R, (T - 1) * 1024), device=dev)
+            _native.check(_lib.bsrnn_istft_ragged(_context(dev), _p(yc), _i64_array(lens), _p(out), R, _s(dev)))
+        ctx.shape, ctx.lens = (R, F2, T), lens
+        return out
+
+    @staticmethod
+    def backward(ctx, dwave):
+        R, F2, T = ctx.shape
+        dev = dwave.device
+        g = _f32c(dwave)
+        with torch.cuda.device(dev):
+            dy = torch.empty((R, F2, T), device=dev)
+            _native.check(_lib.bsrnn_istft_ragged_backward(_context(dev), _p(g), _i64_array(ctx.lens), _p(dy), R, _s(dev)))
+        return dy, None
+
+
+class TriLossRaggedFunction(torch.autograd.Function):
+    """The L1 tri-loss and the `sdr` of train_infer PER CLIP of a ragged batch (bsrnn_train_loss_ragged and its backward):
+    apply(y, s, x_time, speech, lengths, clip_rows) -> (losses [n_clips], sdrs [n_clips]), float32 on the device.  y, s [R, 2050, Tmax],
+    x_time [R, (Tmax-1)*1024], speech [R, n_max]; clip c owns clip_rows[c] consecutive rows of lengths[c] samples.  Each value is what
+    `train_loss` / `sdr` give for that clip alone; gradients flow to y and x_time (s and speech are data)."""
+
+    @staticmethod
+    def forward(ctx, y, s, x_time, speech, lengths, clip_rows):
+        dev = y.device
+        lens, rows = [int(n) for n in lengths], [int(n) for n in clip_rows]
+        n_clips, R = len(lens), y.shape[0]
+        yc, sc, xc, pc = _f32c(y), _f32c(s), _f32c(x_time), _f32c(speech)
+        with torch.cuda.device(dev):
+            values = torch.empty((n_clips, len(_native.TRAIN_VALUE_NAMES)), device=dev, dtype=torch.float64)
+            row_sums = torch.empty((R, 2), device=dev, dtype=torch.float64)
+            _native.check(_lib.bsrnn_train_loss_ragged(_context(dev), _p(yc), _p(sc), _p(xc), _p(pc), pc.shape[1], _i64_array(lens), _i32_array(rows),
+                                                       n_clips, _p(values), _p(row_sums), _s(dev)))
+        ctx.save_for_backward(yc, sc, xc, pc, row_sums)
+        ctx.lens, ctx.rows = lens, rows
+        ctx.values = values                                   # all five per clip, float64 (BSRNN_TV_* order)
+        return values[:, 0].to(torch.float32), values[:, 4].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g_loss, g_sdr):
+        yc, sc, xc, pc, row_sums = ctx.saved_tensors
+        dev = yc.device
+        n_clips = len(ctx.lens)
+        with torch.cuda.device(dev):
+            zero = torch.zeros((n_clips,), device=dev)
+            gclip = torch.stack([zero if g_loss is None else g_loss.to(torch.float32), zero if g_sdr is None else g_sdr.to(torch.float32)], 1).contiguous()
+            dy, dx = torch.empty_like(yc), torch.empty_like(xc)
+            _native.check(_lib.bsrnn_train_loss_ragged_backward(_context(dev), _p(yc), _p(sc), _p(xc), _p(pc), pc.shape[1], _i64_array(ctx.lens),
+                                                                _i32_array(ctx.rows), n_clips, _p(row_sums), _p(gclip), _p(dy), _p(dx), _s(dev)))
+        return dy, None, dx, None, None, None
+
+
+def train_loss_ragged(model, mix, speech, lengths, clip_rows=None):
+    """`train_loss` for clips of different lengths in ONE pass: mix, speech [R, n_max] on the GPU; clip c owns clip_rows[c] consecutive rows
+    (None: one row per clip) of lengths[c] samples each, 1024 < lengths[c] <= n_max.  Returns (losses [n_clips], sdrs [n_clips], x_time
+    [R, (Tmax-1)*1024]): per clip what `train_loss` and `sdr` give for it alone, float32 with the graph attached, so
+    losses.sum().backward() leaves the sum of the per-clip gradients (the reference's accumulation, train.py:97-115) in one backward pass.
+    The model runs on all R * Tmax frame rows: batch clips of similar length (train_backward_many does)."""
+    if (not isinstance(mix, torch.Tensor) or not isinstance(speech, torch.Tensor) or mix.dim() != 2 or tuple(mix.shape) != tuple(speech.shape)):
+        raise ValueError("train_loss_ragged: expected mix and speech [R, n_max] of the same shape")
+    R, n_max = mix.shape
+    lens, rows, row_lens = _row_lengths("train_loss_ragged", lengths, clip_rows, R, n_max)
+    _need_cuda(mix, "train_loss_ragged")
+    _need_cuda(speech, "train_loss_ragged")
+    x = stft_ragged(mix, row_lens)
+    y = forward_train(model, x)
+    x_time = IstftRaggedFunction.apply(y, row_lens)
+    s = stft_ragged(speech, row_lens)
+    losses, sdrs = TriLossRaggedFunction.apply(y, s, x_time, speech, lens, rows)
+    return losses, sdrs, x_time
+
+
+def _pair_shapes(pairs, who):
+    """[(channels, common length)] of (mix, speech) pairs, each tensor [n] or [ch, n]; ValueError for anything else."""
+    shapes = []
+    for i, p in enumerate(pairs):
+        ok = isinstance(p, (tuple, list)) and len(p) == 2 and all(isinstance(t, torch.Tensor) and t.dim() in (1, 2) for t in p)
+        ok = ok and p[0].dim() == p[1].dim() and (p[0].dim() == 1 or (p[0].shape[0] == p[1].shape[0] and p[0].shape[0] >= 1))
+        n = min(p[0].shape[-1], p[1].shape[-1]) if ok else 0
+        if not ok or n <= 1024:
+            raise ValueError("%s: pair %d must be (mix, speech) tensors, both [n] or both [ch, n], with n > 1024" % (who, i))
+        shapes.append((1 if p[0].dim() == 1 else p[0].shape[0], n))
+    return shapes
+
+
+def train_backward_many(model, pairs, loss_sdr=False, max_rows=64, max_padding=0.25):
+    """Loss and backward for a list of (mix, speech) pairs of different lengths - the clips of one optimizer step: each tensor [ch, n]
+    (or [n]), both of a pair cut to their common length.  `spec.ragged_buckets` groups the pairs as `evaluate_many` does; each bucket is
+    packed into two [rows, n_max] buffers and runs ONE `train_loss_ragged` and ONE backward() of losses.sum() (of -sdrs.sum() with
+    loss_sdr): the gradients accumulate in .grad across buckets, as the reference's clip-by-clip loop leaves them.  Returns the per-pair
+    (loss, sdr) floats in input order, read back once per bucket after its backward is queued."""
+    from . import spec as _spec
+    pairs = list(pairs)
+    shapes = _pair_shapes(pairs, "train_backward_many")
+    buckets = _spec.ragged_buckets([_spec.n_frames(n) for _, n in shapes], [ch for ch, _ in shapes], max_rows, max_padding)
+    if not pairs:
+        return []
+    dev = next((t.device for p in pairs for t in p if t.is_cuda), None) or next(p for p in model.parameters() if p.numel() > 0).device
+    results = [None] * len(pairs)
+    for bucket in buckets:
+        rows = [shapes[i][0] for i in bucket]
+        lens = [shapes[i][1] for i in bucket]
+        bufs = torch.zeros((2, sum(rows), max(lens)), device=dev, dtype=torch.float32)
+        r0 = 0
+        for i, ch, n in zip(bucket, rows, lens):
+            for k in range(2):
+                bufs[k, r0:r0 + ch, :n] = pairs[i][k].detach().reshape(ch, -1)[:, :n].to(device=dev, dtype=torch.float32)
+            r0 += ch
+        losses, sdrs, _ = train_loss_ragged(model, bufs[0], bufs[1], lens, rows)
+        (-sdrs.sum() if loss_sdr else losses.sum()).backward()
+        vals = torch.stack([losses.detach(), sdrs.detach()], 1).cpu().tolist()
+        for i, v in zip(bucket, vals):
+            results[i] = (v[0], v[1])
+    return results
+
+
+def train_step_many(model, optimizer, pairs, group=None, loss_sdr=False, max_rows=64, max_padding=0.25):
+    """One optimizer step over the clips in `pairs` (the reference's --batch_size accumulation, train.py:97-115): train_backward_many,
+    the gradients averaged over the ranks of `group` when one is given (dist.all_reduce_gradients), optimizer.step(), zero_grad().
+    Returns train_backward_many's per-pair (loss, sdr)."""
+    out = train_backward_many(model, pairs, loss_sdr=loss_sdr, max_rows=max_rows, max_padding=max_padding)
+    if group is not None:
+        from .dist import all_reduce_gradients
+        all_reduce_gradients(model.parameters(), group=group)
+    optimizer.step()
+    optimizer.zero_grad()
+    return out
 
 
 # ------------------------------------------------------------------------------------------ optimizer and the step

@@ -5,7 +5,9 @@ the MI355X training kernels (speechseparation_amd/train.py).
 Reference flow per epoch: for every training clip `train_infer` (STFT -> BSRNN -> iSTFT, L1 tri-loss, SDR; m_dataset.py:182-226),
 `toBackward.backward()` (the loss, or -SDR with --loss_sdr), an optimizer step every `batch_size` clips (AdamW lr 1e-3,
 weight_decay 1e-2; :50), then a validation pass without gradients and the checkpoints `model.pth` (best validation loss) /
-`model-always.pth` (+ `optimizer*.pth`).  Same flags: --datapath --mini --batch_size --resume --loss_sdr.
+`model-always.pth` (+ `optimizer*.pth`).  Same flags: --datapath --mini --batch_size --resume --loss_sdr.  --ragged runs the `batch_size` clips of an optimizer
+step as one padded batch with one backward pass (speechseparation_amd.train.train_step_many) instead of clip by clip: the same gradients
+and the same printed averages, to rounding.
 
 Data: <datapath>/{train,val}/<clip>/{mixture,speech}.wav - the folders the reference trains from (`samples(args.datapath, 'train')` /
 `'val'`, train.py:58,74; DnR layout of m_dataset.samples(), :8-19), as 16-bit / float WAV (the reference's .flac needs torchaudio, absent
@@ -70,6 +72,8 @@ def main(argv=None):
     ap.add_argument("--synthetic-weights", type=int, default=None, metavar="SEED", help="initial weights from the seeded generator instead of torch's init")
     ap.add_argument("--graph", action="store_true", help="replay each iteration as one hipGraph (speechseparation_amd.train.GraphedTrainStep): "
                     "single process, --batch_size 1, one graph per clip length (at most 4 lengths, other clips run launch by launch)")
+    ap.add_argument("--ragged", action="store_true", help="run the clips of one optimizer step (--batch_size of them, or the epoch's tail) as one "
+                    "padded batch with one backward pass (speechseparation_amd.train.train_step_many) instead of clip by clip")
     ap.add_argument("--device", type=str, default=None)
     ap.add_argument("--outdir", type=str, default=".")
     args = ap.parse_args(argv)
@@ -103,7 +107,7 @@ def main(argv=None):
     if args.resume:
         model.load_state_dict(torch.load(os.path.join(args.outdir, "model.pth"), weights_only=True))
     model = model.to(device)
-    use_graph = args.graph and world == 1 and args.batch_size == 1
+    use_graph = args.graph and world == 1 and args.batch_size == 1 and not args.ragged
     if args.graph and not use_graph and rank == 0:
         print("--graph needs a single process and --batch_size 1: running launch by launch")
     optimizer = hip_train.AdamW(model.parameters(), lr=0.001, weight_decay=0.01, capturable=use_graph)
@@ -119,6 +123,16 @@ def main(argv=None):
         random.Random(epoch).shuffle(order)                      # DataLoader(shuffle=True)
         order = order[: len(order) // world * world][rank::world]     # the same number of clips (and collectives) on every rank
         epoch_loss, epoch_sdr, batch_i = 0.0, 0.0, 0
+        if args.ragged:
+            # the clips of one optimizer step in one backward pass; the tail of the epoch is a smaller step (train.py:122-123)
+            for b0 in range(0, len(order), args.batch_size):
+                pairs = [load_pair(train_set[idx], device) for idx in order[b0:b0 + args.batch_size]]
+                for loss, sdr in hip_train.train_step_many(model, optimizer, pairs, group=dist.group.WORLD if world > 1 else None,
+                                                           loss_sdr=args.loss_sdr):
+                    batch_i += 1
+                    epoch_loss += loss
+                    epoch_sdr += sdr
+            order = []
         for idx in order:
             mix, speech = load_pair(train_set[idx], device)
             if use_graph and (tuple(mix.shape) in graphs or len(graphs) < 4):
@@ -142,10 +156,10 @@ def main(argv=None):
                     all_reduce_gradients(model.parameters())
                 optimizer.step()
                 optimizer.zero_grad()
-        if world > 1:
+        if world > 1 and not args.ragged:
             from speechseparation_amd.dist import all_reduce_gradients
             all_reduce_gradients(model.parameters())
-        optimizer.step()                                         # train.py:122-123: the tail of the epoch
+        optimizer.step()                                         # train.py:122-123: the tail of the epoch (--ragged: already stepped, no gradient is left)
         optimizer.zero_grad()
         if rank == 0:
             print("Epoch", epoch, "Loss", epoch_loss / max(1, batch_i), "sdr", epoch_sdr / max(1, batch_i))
