@@ -628,6 +628,59 @@ int     bsrnn_resampler_bank_flush_rows(bsrnn_resampler_bank* b, const int32_t* 
                                         float* out_dev, int64_t out_stride, int64_t* n_out_host, void* stream);
 int     bsrnn_resampler_bank_reset_rows(bsrnn_resampler_bank* b, const int32_t* rows_host, int32_t n_rows);
 
+/* ---- a pool of live sessions: one call per tick, a pointer per session ------------------------
+ * What a many-session server needs on top of bsrnn_stream_process_hops, as an object of the library: `slots` sessions of rows_per_session
+ * rows each on ONE wide bsrnn_stream of C = slots * rows_per_session rows (session in slot k owns rows k * rows_per_session ...), a
+ * device-resident FIFO per row for the samples that do not yet fill a hop, and ONE call per tick that takes whatever every session has.
+ * bsrnn_pool_feed: session i of the call (i < n_sessions; all arrays [n_sessions], ordinary host memory, the caller's again at return under
+ *     either range policy) sits in open slot slots_host[i] and brings n_in[i] >= 0 samples per row at in_dev[i], its rows in_stride[i] floats
+ *     apart (a null pointer is fine with n_in = 0).  With p = bsrnn_pool_pending(slot) it has h = (p + n_in[i]) / 1024 hops in hand: it gets
+ *     n_out_host[i] = h * 1024 samples per row at out_dev[i], rows out_stride[i] floats apart - exactly what h consecutive bsrnn_stream_step
+ *     calls give its rows for the stream FIFO ++ input, delayed by one hop - and nothing behind them is written; the remaining
+ *     (p + n_in[i]) % 1024 samples wait in the FIFO.  n_out_host is host arithmetic, filled at return without synchronising.  Only 4-byte
+ *     alignment of pointers and strides is assumed.  Sessions not named are held (bsrnn_stream_process_rows).
+ *     The call runs in rounds of at most max_hops hops: per round one gather launch (FIFO ++ input into the pool's own [C, L*1024]
+ *     rectangle, zeros behind a row's hops, and what stays waiting into the FIFO), ONE bsrnn_stream_process_hops(n_hops = L = the most hops
+ *     anyone still has, capped at max_hops; a session's count is what it has left, capped at L; everyone else 0), one scatter launch, all
+ *     on the caller's stream.  If nobody has a hop the call is the one gather launch.  n_sessions == 0 does nothing.
+ *     mix_host == NULL: every row takes the scalar `mix` (bsrnn_stream_step_host's formula; 1 for plain separation).  Otherwise mix_host[i]
+ *     is session i's value and the rows of everybody else are at 1; `mix` is ignored.
+ *     Range policy: as bsrnn_stream_process_hops - under BSRNN_RANGE_DEFERRED the call waits for nothing; under BSRNN_RANGE_EXACT it waits in
+ *     every round as the hops call does, and a re-run reads the pool's rectangle again: the FIFO is consumed once.
+ *     BSRNN_EARG before any device work, the pool untouched, the text naming the session: a null pool or array; a slot that is not open or
+ *     named twice; n_in < 0; in_stride below n_in; out_stride below n_out; a null pointer where samples are to be read or written; ANY
+ *     output range of the call overlapping ANY input range of the call (a later round reads input behind what an earlier round has
+ *     written, so in place is not offered).
+ * bsrnn_pool_feed_host: the same with in / out in ordinary host memory, synchronous: per round the sessions' samples are copied into a
+ *     pinned block, go up in one copy, the same three launches run, the result comes down in one copy and is handed out.  The same
+ *     arithmetic: bit-identical to the device form.  Behaves as under BSRNN_RANGE_EXACT (it waits anyway).
+ * bsrnn_pool_create does ALL first-use work: the stream and bsrnn_stream_reserve(max_hops), the two rectangles, the FIFOs, the table
+ *     block (one entry per row and a wet / dry value per row, with pinned mirrors used in turn) and the host form's pinned staging with its
+ *     device mirrors.  Afterwards no feed allocates, captures or instantiates (bsrnn_debug_counter 0..2 unchanged).  BSRNN_EARG for
+ *     C > BSRNN_STREAM_ROWS_MAX or max_hops outside [1, BSRNN_STREAM_HOPS_MAX].  bsrnn_pool_destroy also destroys the stream.
+ * bsrnn_pool_open: the lowest free slot; its rows start from silence (reset in the order of the stream the pool was last fed on) and
+ *     nothing waits.  bsrnn_pool_close frees a slot; what waited is dropped.  bsrnn_pool_pending: samples per row waiting, < 1024; -1 for
+ *     a null pool or a slot that is not open.
+ * bsrnn_pool_stream: the wide stream, for bsrnn_stream_get_row / _set_row of a session's rows.  With bsrnn_pool_get_pending /
+ *     _set_pending (synchronous; host [rows_per_session, 1024], the first n floats of each row count, n < 1024) a session moves between
+ *     pools in the middle of a hop and continues bit for bit.
+ * A pool call counts as a call on the context (concurrency contract above). */
+typedef struct bsrnn_pool bsrnn_pool;
+int     bsrnn_pool_create(bsrnn_ctx* ctx, int32_t slots, int32_t rows_per_session, int32_t max_hops, bsrnn_pool** out);
+void    bsrnn_pool_destroy(bsrnn_pool* p);
+int     bsrnn_pool_open(bsrnn_pool* p, int32_t* slot_out);
+int     bsrnn_pool_close(bsrnn_pool* p, int32_t slot);
+int64_t bsrnn_pool_pending(const bsrnn_pool* p, int32_t slot);
+bsrnn_stream* bsrnn_pool_stream(bsrnn_pool* p);
+int     bsrnn_pool_get_pending(bsrnn_pool* p, int32_t slot, float* host, int32_t* n);
+int     bsrnn_pool_set_pending(bsrnn_pool* p, int32_t slot, const float* host, int32_t n);
+int     bsrnn_pool_feed(bsrnn_pool* p, int32_t n_sessions, const int32_t* slots_host, const float* const* in_dev, const int64_t* in_stride,
+                        const int64_t* n_in, float* const* out_dev, const int64_t* out_stride, int64_t* n_out_host,
+                        const float* mix_host, float mix, void* stream);
+int     bsrnn_pool_feed_host(bsrnn_pool* p, int32_t n_sessions, const int32_t* slots_host, const float* const* in_host,
+                             const int64_t* in_stride, const int64_t* n_in, float* const* out_host, const int64_t* out_stride,
+                             int64_t* n_out_host, const float* mix_host, float mix);
+
 /* ---- measurement support ---------------------------------------------------------------
  * bsrnn_set_profiling(ctx, mask): bit i of `mask` brackets stage i of every compute call with
  * hipEvents on the call's stream (mask < 0 = all stages, 0 = off; each bracket costs ~10 us of

@@ -32,6 +32,8 @@ SYMBOLS = [
     "bsrnn_resampler_ready", "bsrnn_resampler_process", "bsrnn_resampler_flush",
     "bsrnn_resampler_bank_create", "bsrnn_resampler_bank_destroy", "bsrnn_resampler_bank_assign", "bsrnn_resampler_bank_pair_of",
     "bsrnn_resampler_bank_ready", "bsrnn_resampler_bank_process", "bsrnn_resampler_bank_flush_rows", "bsrnn_resampler_bank_reset_rows",
+    "bsrnn_pool_create", "bsrnn_pool_destroy", "bsrnn_pool_open", "bsrnn_pool_close", "bsrnn_pool_pending", "bsrnn_pool_stream",
+    "bsrnn_pool_get_pending", "bsrnn_pool_set_pending", "bsrnn_pool_feed", "bsrnn_pool_feed_host",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
@@ -131,6 +133,16 @@ def _load():
         "bsrnn_resampler_bank_process": (C.c_int, [vp, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), vp]),
         "bsrnn_resampler_bank_flush_rows": (C.c_int, [vp, C.POINTER(i32), i32, vp, i64, C.POINTER(i64), vp]),
         "bsrnn_resampler_bank_reset_rows": (C.c_int, [vp, C.POINTER(i32), i32]),
+        "bsrnn_pool_create": (C.c_int, [vp, i32, i32, i32, C.POINTER(vp)]),
+        "bsrnn_pool_destroy": (None, [vp]),
+        "bsrnn_pool_open": (C.c_int, [vp, C.POINTER(i32)]),
+        "bsrnn_pool_close": (C.c_int, [vp, i32]),
+        "bsrnn_pool_pending": (i64, [vp, i32]),
+        "bsrnn_pool_stream": (vp, [vp]),
+        "bsrnn_pool_get_pending": (C.c_int, [vp, i32, vp, C.POINTER(i32)]),
+        "bsrnn_pool_set_pending": (C.c_int, [vp, i32, vp, i32]),
+        "bsrnn_pool_feed": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp]),
+        "bsrnn_pool_feed_host": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),
         "bsrnn_stage_name": (C.c_char_p, [i32]),

@@ -1489,3 +1489,239 @@ class StreamPool(metaclass=_StreamPoolType):
         for r, b in zip(self._rows_of(sid), blobs):
             st.set_row(r, b)
         return sid
+
+
+class NativeStreamPool:
+    """StreamPool's sessions at the model's rate as an object of the LIBRARY (bsrnn_pool_*, include/bsrnn_hip.h): the slots, the samples
+    that wait for a whole hop (a device-resident FIFO per row) and the packing of every session's audio around the one
+    bsrnn_stream_process_hops of a tick all live behind ONE library call per feed, which takes a pointer per session.  Nothing is
+    copied on the host: a CUDA chunk goes by its pointer and row stride (views are fine; float32 with unit inner stride), and the
+    results are views of one tensor allocated per feed.  A dict of CPU tensors takes the library's host form (bsrnn_pool_feed_host).
+    Same numbers as StreamPool: both make the same hops calls on the same samples (a feed of more than max_hops hops runs in rounds of
+    max_hops, where StreamPool's rounds are 255 hops long).  The pool is created at the first call that needs the device; shape and
+    type errors are raised before that.  Sessions with a sample rate of their own: StreamPool(rates=...)."""
+
+    MODEL_RATE = 44100
+
+    def __init__(self, model, slots, rows_per_session=1, device=None, max_hops=8):
+        for name, v in (("slots", slots), ("rows_per_session", rows_per_session), ("max_hops", max_hops)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError("NativeStreamPool: %s must be a positive int, got %r" % (name, v))
+        if slots * rows_per_session > _native.STREAM_ROWS_MAX:
+            raise ValueError("NativeStreamPool: %d slots x %d rows is more than the %d rows a rows call takes" % (
+                slots, rows_per_session, _native.STREAM_ROWS_MAX))
+        if max_hops > _native.STREAM_HOPS_MAX:
+            raise ValueError("NativeStreamPool: max_hops = %d, a hops call takes at most %d" % (max_hops, _native.STREAM_HOPS_MAX))
+        self.model, self.slots, self.rows, self.max_hops = model, int(slots), int(rows_per_session), int(max_hops)
+        self._device = device
+        self.device = None                  # set with the pool
+        self._h = None
+        self._slot = {}                     # session id -> slot
+        self._free = list(range(self.slots))
+        self._next = 0
+        self._steps = 0
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                _lib.bsrnn_pool_destroy(self._h)
+        except Exception:
+            pass
+
+    def _pool(self):
+        if self._h is None:
+            self.device = torch.device("cuda", torch.cuda.current_device()) if self._device is None else torch.device(self._device)
+            with torch.cuda.device(self.device):
+                ctx = self.model._context(self.device)
+                h = ctypes.c_void_p()
+                _check(_lib.bsrnn_pool_create(ctx, self.slots, self.rows, self.max_hops, ctypes.byref(h)))
+                self._h = h
+                # the sessions opened so far: the library hands out the lowest free slot, as open() did
+                used = set(self._slot.values())
+                got = ctypes.c_int32()
+                for k in range(max(used) + 1 if used else 0):
+                    _check(_lib.bsrnn_pool_open(h, ctypes.byref(got)))
+                    assert got.value == k
+                for k in range(max(used) + 1 if used else 0):
+                    if k not in used:
+                        _check(_lib.bsrnn_pool_close(h, k))
+        return self._h
+
+    def _look_at_weights(self):
+        # the same look at the model's parameters as StreamingSeparator.step() takes (see there), once per call
+        if self._steps % 32 == 0 or self.model._weights_touched(self._steps):
+            self.model._plist = None
+            with torch.cuda.device(self.device):
+                self.model._context(self.device)
+        self._steps += 1
+
+    def _rows_of(self, sid):
+        slot = self._slot[sid]              # KeyError: no such session
+        return range(slot * self.rows, (slot + 1) * self.rows)
+
+    def sessions(self):
+        return list(self._slot)
+
+    def open(self, sample_rate=None):
+        """-> a new session's id; its rows start from silence and nothing waits.  ValueError when every slot is taken, and for a
+        sample_rate other than None or the model's 44100."""
+        if sample_rate is not None and sample_rate != self.MODEL_RATE:
+            raise ValueError("NativeStreamPool.open: sample_rate %r: the native pool serves sessions at the model's %d Hz; sessions with a "
+                             "rate of their own are StreamPool(rates=...)'s" % (sample_rate, self.MODEL_RATE))
+        if not self._free:
+            raise ValueError("NativeStreamPool: all %d slots are in use" % self.slots)
+        slot = self._free.pop(0)
+        if self._h is not None:
+            got = ctypes.c_int32()
+            with torch.cuda.device(self.device):
+                _check(_lib.bsrnn_pool_open(self._h, ctypes.byref(got)))
+            assert got.value == slot
+        sid, self._next = self._next, self._next + 1
+        self._slot[sid] = slot
+        return sid
+
+    def close(self, sid):
+        """The session leaves; samples of it that waited are dropped."""
+        slot = self._slot.pop(sid)
+        self._free.append(slot)
+        self._free.sort()
+        if self._h is not None:
+            _check(_lib.bsrnn_pool_close(self._h, slot))
+
+    def pending(self, sid):
+        """Samples per row of the session that wait for its next feed() (fewer than one hop)."""
+        slot = self._slot[sid]
+        return 0 if self._h is None else int(_lib.bsrnn_pool_pending(self._h, slot))
+
+    def _check_mix(self, mix, who):
+        if isinstance(mix, dict):
+            for sid, v in mix.items():
+                self._rows_of(sid)
+                if isinstance(v, bool) or not isinstance(v, (int, float)):
+                    raise ValueError("NativeStreamPool.%s: mix of session %r must be a float, got %s" % (who, sid, type(v).__name__))
+        elif mix is not None and (isinstance(mix, bool) or not isinstance(mix, (int, float))):
+            raise ValueError("NativeStreamPool.%s: mix must be None, a float or a dict {session id: float}, got %s" % (who, type(mix).__name__))
+
+    def feed(self, chunks, mix=None):
+        """chunks {sid: tensor [rows_per_session, n]}, ANY n >= 0 and another one per session, all CUDA tensors on the pool's device or all
+        CPU tensors -> {sid: tensor [rows_per_session, h*1024] on the same device}: every session advances by the h = (pending + n) //
+        1024 hops it has in hand, in ONE library call (bsrnn_pool_feed / _feed_host); the remainder waits on the device.  Sessions not
+        named are held.  mix: None (1.0), one float, or {sid: float} (sessions not in it: 1.0).  The chunks must be float32 with unit
+        inner stride (a row stride of any size: column slices and views with a storage offset go by pointer, uncopied); the results
+        are views of one tensor made by this call."""
+        if not isinstance(chunks, dict):
+            raise ValueError("NativeStreamPool.feed: chunks must be a dict {session id: tensor}, got %s" % type(chunks).__name__)
+        on_cuda = None
+        for sid, t in chunks.items():
+            self._rows_of(sid)
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != self.rows:
+                raise ValueError("NativeStreamPool.feed: session %r needs a tensor [%d, n], got %s" % (
+                    sid, self.rows, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+            if t.dtype != torch.float32:
+                raise ValueError("NativeStreamPool.feed: session %r needs float32 samples, got %s (the chunk goes by pointer)" % (sid, t.dtype))
+            n = t.shape[1]
+            if n and (t.stride(1) != 1 or (self.rows > 1 and t.stride(0) < n)):
+                raise ValueError("NativeStreamPool.feed: session %r: strides %r; the chunk goes by pointer and row stride, so samples of a row "
+                                 "must be adjacent and rows must not overlap" % (sid, tuple(t.stride())))
+            if on_cuda is not None and t.is_cuda != on_cuda:
+                raise ValueError("NativeStreamPool.feed: CUDA and CPU chunks in one call; a feed takes one kind")
+            on_cuda = t.is_cuda
+        self._check_mix(mix, "feed")
+        if not chunks:
+            return {}
+        h = self._pool()
+        for sid, t in chunks.items():
+            if t.is_cuda and t.device != self.device:
+                raise ValueError("NativeStreamPool.feed: session %r brings a chunk on %s, the pool lives on %s" % (sid, t.device, self.device))
+        self._look_at_weights()
+        n_s = len(chunks)
+        sids = list(chunks)
+        n_out = [(self.pending(sid) + chunks[sid].shape[1]) // _spec.HOP * _spec.HOP for sid in sids]
+        block = torch.empty((self.rows * sum(n_out),), dtype=torch.float32, device=self.device if on_cuda else "cpu")
+        res, at = {}, 0
+        for sid, m in zip(sids, n_out):
+            res[sid] = block[at:at + self.rows * m].view(self.rows, m)
+            at += self.rows * m
+        keep = [chunks[sid].detach() for sid in sids]
+        slots = (ctypes.c_int32 * n_s)(*[self._slot[sid] for sid in sids])
+        in_p = (ctypes.c_void_p * n_s)(*[t.data_ptr() if t.shape[1] else None for t in keep])
+        in_s = (ctypes.c_int64 * n_s)(*[max(t.stride(0), t.shape[1]) if self.rows > 1 else t.shape[1] for t in keep])
+        n_in = (ctypes.c_int64 * n_s)(*[t.shape[1] for t in keep])
+        out_p = (ctypes.c_void_p * n_s)(*[res[sid].data_ptr() if m else None for sid, m in zip(sids, n_out)])
+        out_s = (ctypes.c_int64 * n_s)(*n_out)
+        got = (ctypes.c_int64 * n_s)()
+        if isinstance(mix, dict):
+            mix_p, mix_v = (ctypes.c_float * n_s)(*[float(mix.get(sid, 1.0)) for sid in sids]), 1.0
+        else:
+            mix_p, mix_v = None, 1.0 if mix is None else float(mix)
+        with torch.cuda.device(self.device):
+            if on_cuda:
+                _check(_lib.bsrnn_pool_feed(h, n_s, slots, in_p, in_s, n_in, out_p, out_s, got, mix_p, mix_v, _stream_ptr(self.device)))
+            else:
+                _check(_lib.bsrnn_pool_feed_host(h, n_s, slots, in_p, in_s, n_in, out_p, out_s, got, mix_p, mix_v))
+        assert list(got) == n_out
+        return res
+
+    def step(self, chunks, mix=None):
+        """A feed whose chunks are whole hops, one L for all: chunks {sid: tensor [rows_per_session, L*1024]} -> {sid: tensor of the same
+        shape}, delayed by one hop.  An empty dict makes no library call."""
+        if not isinstance(chunks, dict):
+            raise ValueError("NativeStreamPool.step: chunks must be a dict {session id: tensor}, got %s" % type(chunks).__name__)
+        n = None
+        for sid, t in chunks.items():
+            self._rows_of(sid)
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != self.rows:
+                raise ValueError("NativeStreamPool.step: session %r needs a tensor [%d, L*1024], got %s" % (
+                    sid, self.rows, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+            if t.shape[1] % _spec.HOP or t.shape[1] == 0:
+                raise ValueError("NativeStreamPool.step: session %r holds %d samples per row, need whole hops of 1024" % (sid, t.shape[1]))
+            if n is not None and t.shape[1] != n:
+                raise ValueError("NativeStreamPool.step: session %r holds %d samples per row, the others %d (one L per step)" % (sid, t.shape[1], n))
+            n = t.shape[1]
+        self._check_mix(mix, "step")
+        return self.feed(chunks, mix)
+
+    def _row_floats(self):
+        return 2 * _spec.N_FFT + 8 * len(self.model.band_widths) * band_features
+
+    def export(self, sid):
+        """-> (blobs, pending): the session's carry, one blob (CPU tensor) per row as StreamPool.export gives them, and the samples that
+        wait, a CPU tensor [rows_per_session, pending(sid)] - everything adopt() of this or another pool of the same model needs to
+        continue the session bit for bit, in the middle of a hop too."""
+        rows = self._rows_of(sid)
+        h = self._pool()
+        st = _lib.bsrnn_pool_stream(h)
+        blobs = []
+        for r in rows:
+            b = np.empty(self._row_floats(), np.float32)
+            _check(_lib.bsrnn_stream_get_row(st, r, b.ctypes.data_as(ctypes.c_void_p)))
+            blobs.append(torch.from_numpy(b))
+        fifo = np.empty((self.rows, _spec.HOP), np.float32)
+        n = ctypes.c_int32()
+        _check(_lib.bsrnn_pool_get_pending(h, self._slot[sid], fifo.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n)))
+        return blobs, torch.from_numpy(fifo[:, :n.value].copy())
+
+    def adopt(self, blobs, pending=None):
+        """A session exported elsewhere - adopt(*other.export(sid)), or the blobs of StreamPool.export alone - continues here, bit for
+        bit -> its new id."""
+        blobs = list(blobs)
+        nf = self._row_floats()
+        if len(blobs) != self.rows or not all(isinstance(b, torch.Tensor) and b.dim() == 1 and b.numel() == nf for b in blobs):
+            raise ValueError("NativeStreamPool.adopt: need %d blobs of %d floats each" % (self.rows, nf))
+        if pending is not None and (not isinstance(pending, torch.Tensor) or pending.dim() != 2 or pending.shape[0] != self.rows or
+                                    pending.shape[1] >= _spec.HOP):
+            raise ValueError("NativeStreamPool.adopt: pending must be a tensor [%d, n] with n < %d, got %s" % (
+                self.rows, _spec.HOP, tuple(pending.shape) if isinstance(pending, torch.Tensor) else type(pending).__name__))
+        if not self._free:
+            raise ValueError("NativeStreamPool: all %d slots are in use" % self.slots)
+        h = self._pool()
+        sid = self.open()
+        st = _lib.bsrnn_pool_stream(h)
+        for r, b in zip(self._rows_of(sid), blobs):
+            a = np.ascontiguousarray(b.detach().to("cpu", torch.float32).numpy())
+            _check(_lib.bsrnn_stream_set_row(st, r, a.ctypes.data_as(ctypes.c_void_p)))
+        if pending is not None and pending.shape[1]:
+            fifo = np.zeros((self.rows, _spec.HOP), np.float32)
+            fifo[:, :pending.shape[1]] = pending.detach().to("cpu", torch.float32).numpy()
+            _check(_lib.bsrnn_pool_set_pending(h, self._slot[sid], fifo.ctypes.data_as(ctypes.c_void_p), int(pending.shape[1])))
+        return sid

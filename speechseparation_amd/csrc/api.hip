@@ -3290,6 +3290,339 @@ int bsrnn_resampler_bank_flush_rows(bsrnn_resampler_bank* bk, const int32_t* row
     return bank_run(bk, nullptr, 0, nullptr, out, out_stride, n_out_host, true, (hipStream_t)stream);
 }
 
+// --------------------------------------------------------------------------- the native session pool
+// Slots, pending counts and the round plan: pool_host.h; the two copy kernels: pool.hip.  A pool owns ONE wide bsrnn_stream and, on the
+// device, the two rectangles of its hops calls, a FIFO row per stream row and the table block; per round of a feed it uploads the
+// table, launches the gather, makes one bsrnn_stream_process_hops and launches the scatter, all on the caller's stream.
+struct bsrnn_pool {
+    bsrnn_ctx* ctx = nullptr;
+    bsrnn_stream* st = nullptr;
+    int slots = 0, rows = 0, C = 0, max_hops = 0;
+    PoolSlots sl;
+    // One device allocation: [chunk C x max_hops*1024 | out, the same | fifo C x 1024 | staging in C x (max_hops+1)*1024 | staging out
+    // C x max_hops*1024 | table block: C entries, then C wet/dry values].  One pinned allocation: [MIRRORS table blocks | staging in |
+    // staging out].  The table block travels as bsrnn_ctx::Ragged's does: mirror k is written again only when the copy that read it
+    // has completed (ev[k]), so the caller's arrays are free at return and feeds still queue up behind each other.
+    static constexpr int MIRRORS = 8;
+    float *base = nullptr, *chunk = nullptr, *out = nullptr, *fifo = nullptr, *d_hin = nullptr, *d_hout = nullptr;
+    char* d_tab = nullptr;
+    char* h_base = nullptr;
+    float *h_in = nullptr, *h_out = nullptr;
+    size_t tab_bytes = 0;
+    unsigned uploads = 0;
+    hipEvent_t ev[MIRRORS] = {};
+    hipStream_t last = nullptr;        // the stream of the last feed: bsrnn_pool_open resets its rows in that stream's order
+    bool reset_queued = false;         // ... and a feed on another stream waits for that stream first
+    // a call's scratch, sized at create (no feed allocates)
+    std::vector<uint8_t> seen;                                 // [slots]
+    std::vector<int32_t> counts;                               // [C]
+    struct Span { uintptr_t a, e; int32_t i; };
+    std::vector<Span> spans;                                   // [slots]: the input ranges of a call, by start, with a running largest end
+};
+
+static int64_t pool_row_span_bytes(int rows, int64_t stride, int64_t n) { return n > 0 ? ((int64_t)(rows - 1) * stride + n) * (int64_t)sizeof(float) : 0; }
+
+// Everything a feed refuses, before any device work; fills n_out[i] and *h_max.  who: the entry point's name.
+static int pool_check_feed(bsrnn_pool* pl, const char* who, int32_t n, const int32_t* slots, const float* const* in, const int64_t* in_stride,
+                           const int64_t* n_in, float* const* out, const int64_t* out_stride, int64_t* n_out, int64_t* h_max)
+{
+    if (!slots || !in || !in_stride || !n_in || !out || !out_stride || !n_out)
+        return fail(BSRNN_EARG, "%s: null argument (the slots, the pointers, strides and counts of both sides and n_out_host are needed)", who);
+    if (n > pl->slots) return fail(BSRNN_EARG, "%s: n_sessions = %d, the pool has %d slots", who, n, pl->slots);
+    std::fill(pl->seen.begin(), pl->seen.end(), (uint8_t)0);
+    *h_max = 0;
+    for (int i = 0; i < n; ++i) {
+        const int32_t slot = slots[i];
+        if (!pool_slot_is_open(pl->sl, slot)) return fail(BSRNN_EARG, "%s: session %d names slot %d, which is not open", who, i, slot);
+        if (pl->seen[slot]) return fail(BSRNN_EARG, "%s: session %d names slot %d, which an earlier session of the call names too", who, i, slot);
+        pl->seen[slot] = 1;
+        if (n_in[i] < 0 || n_in[i] > (INT64_MAX >> 12))
+            return fail(BSRNN_EARG, "%s: session %d (slot %d) brings n_in = %lld samples, need 0 or more", who, i, slot, (long long)n_in[i]);
+        if (in_stride[i] < n_in[i])
+            return fail(BSRNN_EARG, "%s: session %d (slot %d): in_stride = %lld is below its %lld samples", who, i, slot, (long long)in_stride[i],
+                        (long long)n_in[i]);
+        if (n_in[i] > 0 && !in[i]) return fail(BSRNN_EARG, "%s: session %d (slot %d) brings %lld samples from a null pointer", who, i, slot, (long long)n_in[i]);
+        const int64_t H = pool_hops_in_hand(pl->sl.pending[slot], n_in[i]);
+        n_out[i] = H * POOL_HOP;
+        if (out_stride[i] < n_out[i])
+            return fail(BSRNN_EARG, "%s: session %d (slot %d): out_stride = %lld is below the %lld samples it gets", who, i, slot,
+                        (long long)out_stride[i], (long long)n_out[i]);
+        if (H > 0 && !out[i]) return fail(BSRNN_EARG, "%s: session %d (slot %d) gets %lld samples at a null pointer", who, i, slot, (long long)n_out[i]);
+        *h_max = std::max(*h_max, H);
+    }
+    // no output range of the call may share a byte with any input range of the call: inputs by start with a running largest end, then one
+    // binary search per output
+    pl->spans.clear();
+    for (int i = 0; i < n; ++i) {
+        const int64_t nb = pool_row_span_bytes(pl->rows, in_stride[i], n_in[i]);
+        if (nb) pl->spans.push_back({(uintptr_t)in[i], (uintptr_t)in[i] + (uintptr_t)nb, i});
+    }
+    std::sort(pl->spans.begin(), pl->spans.end(), [](const bsrnn_pool::Span& x, const bsrnn_pool::Span& y) { return x.a < y.a; });
+    for (size_t k = 1; k < pl->spans.size(); ++k)
+        if (pl->spans[k].e < pl->spans[k - 1].e) { pl->spans[k].e = pl->spans[k - 1].e; pl->spans[k].i = pl->spans[k - 1].i; }
+    for (int i = 0; i < n && !pl->spans.empty(); ++i) {
+        const int64_t nb = pool_row_span_bytes(pl->rows, out_stride[i], n_out[i]);
+        if (!nb) continue;
+        const uintptr_t a = (uintptr_t)out[i], e = a + (uintptr_t)nb;
+        // the last input that starts below the output's end; the running end says whether it, or one before it, reaches the output
+        size_t lo = 0, hi = pl->spans.size();
+        while (lo < hi) { const size_t mid = (lo + hi) / 2; if (pl->spans[mid].a < e) lo = mid + 1; else hi = mid; }
+        if (lo > 0 && pl->spans[lo - 1].e > a)
+            return fail(BSRNN_EARG, "%s: the output of session %d (slot %d) overlaps the input of session %d (slot %d); a later round reads input "
+                                    "behind what an earlier one has written, so in place is not offered", who, i, slots[i], pl->spans[lo - 1].i,
+                        slots[pl->spans[lo - 1].i]);
+    }
+    return 0;
+}
+
+// The next table mirror, once the copy that last read it has completed
+static int pool_next_mirror(bsrnn_pool* pl, char** h, int* k)
+{
+    *k = (int)(pl->uploads++ % bsrnn_pool::MIRRORS);
+    HIP_TRY(hipEventSynchronize(pl->ev[*k]));
+    *h = pl->h_base + (size_t)*k * pl->tab_bytes;
+    return 0;
+}
+
+// One feed behind its argument checks.  host_form: in / out are host pointers; each round's samples go through the pinned staging.
+static int pool_feed_rounds(bsrnn_pool* pl, int32_t n, const int32_t* slots, const float* const* in, const int64_t* in_stride, const int64_t* n_in,
+                            float* const* out, const int64_t* out_stride, int64_t h_max, const float* mix_host, float mix, hipStream_t s, bool host_form)
+{
+    const int C = pl->C, R = pl->rows, mh = pl->max_hops;
+    const size_t SI = (size_t)(mh + 1) * POOL_HOP, SO = (size_t)mh * POOL_HOP;      // row strides of the staging blocks
+    const int64_t rounds = pool_rounds(h_max, mh);
+    float* d_mix = reinterpret_cast<float*>(pl->d_tab + (size_t)C * sizeof(PoolEntry));
+    for (int64_t j = 0; j < rounds; ++j) {
+        const int L = pool_round_hops(h_max, mh, j);
+        char* h = nullptr;
+        int k = 0;
+        if (int rc = pool_next_mirror(pl, &h, &k)) return rc;
+        PoolEntry* tab = reinterpret_cast<PoolEntry*>(h);
+        float* h_mix = reinterpret_cast<float*>(h + (size_t)C * sizeof(PoolEntry));
+        std::fill(pl->counts.begin(), pl->counts.end(), 0);
+        if (mix_host) std::fill(h_mix, h_mix + C, 1.0f);
+        int n_ent = 0, r_lo = C, r_hi = -1;
+        for (int i = 0; i < n; ++i) {
+            const int32_t slot = slots[i];
+            const PoolPart q = pool_part(pl->sl.pending[slot], n_in[i], mh, j);
+            for (int rr = 0; rr < R; ++rr) {
+                const int row = slot * R + rr;
+                pl->counts[row] = q.hops;
+                if (mix_host) h_mix[row] = mix_host[i];
+                if (j > 0 && q.hops == 0) continue;         // (done in an earlier round: its rows are held and their rectangle rows never read)
+                const float* in_row = in[i] ? in[i] + (size_t)rr * in_stride[i] : nullptr;
+                if (!host_form) {
+                    tab[n_ent++] = pool_entry(q, row, in_row, out[i] ? out[i] + (size_t)rr * out_stride[i] : nullptr);
+                    continue;
+                }
+                // host form: this round's samples of the row, [for the rectangle | for the FIFO], into the staging row; the entry names its mirror
+                float* stage = pl->h_in + (size_t)row * SI;
+                if (q.n_in) memcpy(stage, in_row + q.in_off, (size_t)q.n_in * sizeof(float));
+                if (q.n_pend) memcpy(stage + q.n_in, in_row + q.pend_src, (size_t)q.n_pend * sizeof(float));
+                PoolEntry e = pool_entry(q, row, nullptr, nullptr);
+                e.src = pl->d_hin + (size_t)row * SI;
+                e.pend_src = e.src + q.n_in;
+                e.dst = pl->d_hout + (size_t)row * SO;
+                tab[n_ent++] = e;
+                if (q.n_in || q.n_pend) { r_lo = std::min(r_lo, row); r_hi = std::max(r_hi, row); }
+            }
+        }
+        if (host_form && r_hi >= r_lo)
+            HIP_TRY(hipMemcpyAsync(pl->d_hin + (size_t)r_lo * SI, pl->h_in + (size_t)r_lo * SI, (size_t)(r_hi - r_lo + 1) * SI * sizeof(float),
+                                   hipMemcpyHostToDevice, s));
+        const size_t bytes = mix_host ? (size_t)C * (sizeof(PoolEntry) + sizeof(float)) : (size_t)std::max(n_ent, 1) * sizeof(PoolEntry);
+        HIP_TRY(hipMemcpyAsync(pl->d_tab, h, bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(pl->ev[k], s));
+        launch_pool_gather(reinterpret_cast<const PoolEntry*>(pl->d_tab), n_ent, pl->chunk, pl->fifo, L, s);
+        HIP_TRY(hipGetLastError());
+        if (L == 0) continue;                               // nobody has a hop: the feed was this one launch
+        // the FIFO has been written; the hops call reads the pool's own rectangle, so a re-run of the range policy consumes nothing twice
+        if (int rc = bsrnn_stream_process_hops(pl->st, pl->chunk, pl->out, L, pl->counts.data(), mix_host ? d_mix : nullptr, mix_host ? 1.0f : mix, s))
+            return rc;
+        launch_pool_scatter(reinterpret_cast<const PoolEntry*>(pl->d_tab), n_ent, pl->out, L, s);
+        HIP_TRY(hipGetLastError());
+        if (!host_form) continue;
+        r_lo = C; r_hi = -1;
+        for (int e = 0; e < n_ent; ++e)
+            if (tab[e].n_out) { r_lo = std::min(r_lo, (int)tab[e].row); r_hi = std::max(r_hi, (int)tab[e].row); }
+        HIP_TRY(hipMemcpyAsync(pl->h_out + (size_t)r_lo * SO, pl->d_hout + (size_t)r_lo * SO, (size_t)(r_hi - r_lo + 1) * SO * sizeof(float),
+                               hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int i = 0; i < n; ++i) {
+            const PoolPart q = pool_part(pl->sl.pending[slots[i]], n_in[i], mh, j);
+            for (int rr = 0; rr < R && q.hops; ++rr)
+                memcpy(out[i] + (size_t)rr * out_stride[i] + q.out_off, pl->h_out + (size_t)(slots[i] * R + rr) * SO, (size_t)q.hops * POOL_HOP * sizeof(float));
+        }
+    }
+    for (int i = 0; i < n; ++i) pl->sl.pending[slots[i]] = pool_pending_after(pl->sl.pending[slots[i]], n_in[i]);
+    return 0;
+}
+
+static int pool_feed(bsrnn_pool* pl, const char* who, int32_t n, const int32_t* slots, const float* const* in, const int64_t* in_stride,
+                     const int64_t* n_in, float* const* out, const int64_t* out_stride, int64_t* n_out, const float* mix_host, float mix,
+                     hipStream_t s, bool host_form)
+{
+    if (!pl) return fail(BSRNN_EARG, "%s: null pool", who);
+    if (n < 0) return fail(BSRNN_EARG, "%s: n_sessions = %d", who, n);
+    if (n == 0) return 0;
+    int64_t h_max = 0;
+    if (int rc = pool_check_feed(pl, who, n, slots, in, in_stride, n_in, out, out_stride, n_out, &h_max)) return rc;
+    bsrnn_ctx* c = pl->ctx;
+    if (int rc = check_ready(c)) return rc;
+    ENTER_CALL(c, s);
+    if (pl->reset_queued && pl->last != s) HIP_TRY(hipStreamSynchronize(pl->last));      // (rows that bsrnn_pool_open reset in another stream's order)
+    pl->reset_queued = false;
+    pl->last = s;
+    if (!host_form) return pool_feed_rounds(pl, n, slots, in, in_stride, n_in, out, out_stride, h_max, mix_host, mix, s, false);
+    // the host form waits for its own kernels anyway, so it repairs a range violation whatever the policy says (as bsrnn_stream_step_host)
+    const int keep = c->range_policy;
+    c->range_policy = BSRNN_RANGE_EXACT;
+    int rc = pool_feed_rounds(pl, n, slots, in, in_stride, n_in, out, out_stride, h_max, mix_host, mix, s, true);
+    c->range_policy = keep;
+    if (!rc) HIP_TRY(hipStreamSynchronize(s));
+    return rc;
+}
+
+int bsrnn_pool_create(bsrnn_ctx* c, int32_t slots, int32_t rows_per_session, int32_t max_hops, bsrnn_pool** out)
+{
+    if (!c) return fail(BSRNN_EARG, "bsrnn_pool_create: null context");
+    if (!out || slots < 1 || rows_per_session < 1)
+        return fail(BSRNN_EARG, "bsrnn_pool_create: need slots >= 1, rows_per_session >= 1 and a place for the object, got %d x %d", slots, rows_per_session);
+    if ((int64_t)slots * rows_per_session > STREAM_ROWS_MAX)
+        return fail(BSRNN_EARG, "bsrnn_pool_create: %d slots x %d rows is more than BSRNN_STREAM_ROWS_MAX = %d rows", slots, rows_per_session, STREAM_ROWS_MAX);
+    if (max_hops < 1 || max_hops > STREAM_HOPS_MAX)
+        return fail(BSRNN_EARG, "bsrnn_pool_create: max_hops = %d is outside [1, BSRNN_STREAM_HOPS_MAX = %d]", max_hops, STREAM_HOPS_MAX);
+    if (int rc = check_ready(c)) return rc;
+    std::unique_ptr<bsrnn_pool> pl(new bsrnn_pool());
+    pl->ctx = c; pl->slots = slots; pl->rows = rows_per_session; pl->max_hops = max_hops;
+    const int C = pl->C = slots * rows_per_session;
+    pool_slots_init(pl->sl, slots);
+    pl->seen.assign(slots, 0);
+    pl->counts.assign(C, 0);
+    pl->spans.reserve(slots);
+    int rc = bsrnn_stream_create(c, C, &pl->st);
+    if (!rc) rc = bsrnn_stream_reserve(pl->st, max_hops);
+    if (rc) { if (pl->st) bsrnn_stream_destroy(pl->st); return rc; }
+    const size_t rect = (size_t)C * max_hops * POOL_HOP, fifo = (size_t)C * POOL_HOP, stage_in = (size_t)C * (max_hops + 1) * POOL_HOP;
+    pl->tab_bytes = ((size_t)C * (sizeof(PoolEntry) + sizeof(float)) + 255) & ~size_t(255);
+    const size_t d_floats = 3 * rect + fifo + stage_in, d_bytes = d_floats * sizeof(float) + pl->tab_bytes;
+    const size_t h_bytes = bsrnn_pool::MIRRORS * pl->tab_bytes + (stage_in + rect) * sizeof(float);
+    g_dbg[DBG_ALLOC] += 2;
+    hipError_t e = hipMalloc((void**)&pl->base, d_bytes);
+    if (e == hipSuccess) e = hipMemset(pl->base, 0, d_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&pl->h_base, h_bytes, hipHostMallocDefault);
+    for (hipEvent_t& ev : pl->ev)
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess) {
+        memset(pl->h_base, 0, h_bytes);
+        float* p = pl->base;
+        pl->chunk = p; p += rect;
+        pl->out = p; p += rect;
+        pl->fifo = p; p += fifo;
+        pl->d_hin = p; p += stage_in;
+        pl->d_hout = p; p += rect;
+        pl->d_tab = reinterpret_cast<char*>(p);
+        pl->h_in = reinterpret_cast<float*>(pl->h_base + bsrnn_pool::MIRRORS * pl->tab_bytes);
+        pl->h_out = pl->h_in + stage_in;
+        // the two kernels' first launches happen here: every row as an empty entry, which zero-fills the rectangle and moves nothing
+        PoolEntry* tab = reinterpret_cast<PoolEntry*>(pl->h_base);
+        for (int r = 0; r < C; ++r) tab[r] = pool_entry(PoolPart{}, r, nullptr, nullptr);
+        e = hipMemcpy(pl->d_tab, pl->h_base, pl->tab_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            launch_pool_gather(reinterpret_cast<const PoolEntry*>(pl->d_tab), C, pl->chunk, pl->fifo, max_hops, nullptr);
+            launch_pool_scatter(reinterpret_cast<const PoolEntry*>(pl->d_tab), C, pl->out, max_hops, nullptr);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    }
+    if (e != hipSuccess) {
+        bsrnn_pool_destroy(pl.release());
+        return fail(BSRNN_EHIP, "bsrnn_pool_create: %s", hipGetErrorString(e));
+    }
+    *out = pl.release();
+    return 0;
+}
+
+void bsrnn_pool_destroy(bsrnn_pool* pl)
+{
+    if (!pl) return;
+    (void)hipSetDevice(pl->ctx->device);
+    (void)hipDeviceSynchronize();
+    for (hipEvent_t ev : pl->ev)
+        if (ev) (void)hipEventDestroy(ev);
+    if (pl->h_base) (void)hipHostFree(pl->h_base);
+    if (pl->base) (void)hipFree(pl->base);
+    bsrnn_stream* st = pl->st;
+    delete pl;
+    bsrnn_stream_destroy(st);          // (last: a context that bsrnn_destroy retired goes with its last stream)
+}
+
+int bsrnn_pool_open(bsrnn_pool* pl, int32_t* slot_out)
+{
+    if (!pl || !slot_out) return fail(BSRNN_EARG, "bsrnn_pool_open: null %s", !pl ? "pool" : "slot_out");
+    for (int i = 0; i < pl->slots; ++i) {
+        if (pl->sl.open[i]) continue;
+        // the slot's rows start from silence, in the order of the stream the pool was last fed on; the FIFO needs nothing (pending 0: unread)
+        for (int r = 0; r < pl->rows; ++r) pl->counts[r] = i * pl->rows + r;
+        if (int rc = bsrnn_stream_reset_rows(pl->st, pl->counts.data(), pl->rows, pl->last)) return rc;
+        pl->reset_queued = true;
+        *slot_out = pool_slot_open(pl->sl);
+        return 0;
+    }
+    return fail(BSRNN_EARG, "bsrnn_pool_open: all %d slots are in use", pl->slots);
+}
+
+int bsrnn_pool_close(bsrnn_pool* pl, int32_t slot)
+{
+    if (!pl) return fail(BSRNN_EARG, "bsrnn_pool_close: null pool");
+    if (!pool_slot_close(pl->sl, slot)) return fail(BSRNN_EARG, "bsrnn_pool_close: slot %d is not open", slot);
+    return 0;
+}
+
+int64_t bsrnn_pool_pending(const bsrnn_pool* pl, int32_t slot) { return pl && pool_slot_is_open(pl->sl, slot) ? pl->sl.pending[slot] : -1; }
+
+bsrnn_stream* bsrnn_pool_stream(bsrnn_pool* pl) { return pl ? pl->st : nullptr; }
+
+int bsrnn_pool_get_pending(bsrnn_pool* pl, int32_t slot, float* host, int32_t* n)
+{
+    if (!pl || !host || !n) return fail(BSRNN_EARG, "bsrnn_pool_get_pending: null %s", !pl ? "pool" : "argument");
+    if (!pool_slot_is_open(pl->sl, slot)) return fail(BSRNN_EARG, "bsrnn_pool_get_pending: slot %d is not open", slot);
+    HIP_TRY(hipSetDevice(pl->ctx->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(host, pl->fifo + (size_t)slot * pl->rows * POOL_HOP, (size_t)pl->rows * POOL_HOP * sizeof(float), hipMemcpyDeviceToHost));
+    *n = pl->sl.pending[slot];
+    return 0;
+}
+
+int bsrnn_pool_set_pending(bsrnn_pool* pl, int32_t slot, const float* host, int32_t n)
+{
+    if (!pl || !host) return fail(BSRNN_EARG, "bsrnn_pool_set_pending: null %s", !pl ? "pool" : "argument");
+    if (!pool_slot_is_open(pl->sl, slot)) return fail(BSRNN_EARG, "bsrnn_pool_set_pending: slot %d is not open", slot);
+    if (n < 0 || n >= POOL_HOP) return fail(BSRNN_EARG, "bsrnn_pool_set_pending: n = %d samples, a session has fewer than %d waiting", n, POOL_HOP);
+    HIP_TRY(hipSetDevice(pl->ctx->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(pl->fifo + (size_t)slot * pl->rows * POOL_HOP, host, (size_t)pl->rows * POOL_HOP * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    pl->sl.pending[slot] = n;
+    return 0;
+}
+
+int bsrnn_pool_feed(bsrnn_pool* pl, int32_t n_sessions, const int32_t* slots_host, const float* const* in_dev, const int64_t* in_stride,
+                    const int64_t* n_in, float* const* out_dev, const int64_t* out_stride, int64_t* n_out_host, const float* mix_host, float mix,
+                    void* stream)
+{
+    return pool_feed(pl, "bsrnn_pool_feed", n_sessions, slots_host, in_dev, in_stride, n_in, out_dev, out_stride, n_out_host, mix_host, mix,
+                     (hipStream_t)stream, false);
+}
+
+int bsrnn_pool_feed_host(bsrnn_pool* pl, int32_t n_sessions, const int32_t* slots_host, const float* const* in_host, const int64_t* in_stride,
+                         const int64_t* n_in, float* const* out_host, const int64_t* out_stride, int64_t* n_out_host, const float* mix_host,
+                         float mix)
+{
+    return pool_feed(pl, "bsrnn_pool_feed_host", n_sessions, slots_host, in_host, in_stride, n_in, out_host, out_stride, n_out_host, mix_host, mix,
+                     nullptr, true);
+}
+
 // --------------------------------------------------------------------------- measurement
 int bsrnn_set_profiling(bsrnn_ctx* c, int32_t on)
 {

@@ -7,6 +7,7 @@
 #include "stream_rows_host.h"   // RowSet: the rows a streaming rows call means, by value (HIP-free)
 #include "resample_bank_host.h" // BankRow: what a resampler bank's kernel knows of a row, by value (HIP-free)
 #include "train_ragged_host.h"  // TrainClip: what the ragged training loss kernels know of a clip (HIP-free)
+#include "pool_host.h"          // PoolEntry: what the native session pool's copy kernels know of a row (HIP-free)
 
 namespace bsrnn {
 
@@ -386,5 +387,12 @@ struct BankLaunch {
 };
 static_assert(sizeof(BankLaunch) <= BANK_ARG_OTHER, "resample_bank_host.h sizes a group of descriptors beside these");
 void launch_resample_bank(BankLaunch L, const int* tiles, const BankRow* rows, int C, hipStream_t s);
+
+// ------------------------------------------------------------------ the native session pool's two copies (pool.hip; the plan: pool_host.h)
+// tab [n_entries] on the device: one entry per row of every session a round names.  gather: chunk [C][L*1024] row e.row = the FIFO's
+// n_fifo samples ++ n_in samples of e.src, zeros to the end of the row (L = 0: the rectangle is not touched), then fifo [C][1024] row
+// e.row gets n_pend samples of e.pend_src at pend_off.  scatter: out [C][L*1024] row e.row, its first n_out samples -> e.dst.
+void launch_pool_gather(const PoolEntry* tab, int n_entries, float* chunk, float* fifo, int L, hipStream_t s);
+void launch_pool_scatter(const PoolEntry* tab, int n_entries, const float* out, int L, hipStream_t s);
 
 }  // namespace bsrnn

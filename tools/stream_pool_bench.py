@@ -35,6 +35,15 @@ one inbound and one outbound resampler-bank call around the one process_hops; (b
 Resampler per session and direction around one feed; (c) the two bank calls alone, through the C ABI.
 
     python tools/stream_pool_bench.py --rates [--out profiles/stream_rates_ab.txt]
+
+--native times the pool as an object of the library (bsrnn_pool_*): the setting of H1 - the 64-row stream, 32 sessions of 2 rows whose
+counts are drawn from {1, 2, 3} (fixed seed), every session giving whole hops per tick - four ways in one process, alternating:
+  (a) StreamPool.feed            (b) NativeStreamPool.feed            (c) bsrnn_pool_feed through ctypes with prebuilt arrays
+  (f) the bare bsrnn_stream_process_hops of the same counts: the floor; c - f is the price of the two copy launches and the table.
+Then the plain calls, each run a process of its own, this build against --baseline-lib, twice each: part 2 above and, beside it, the
+bsrnn_stream_process_hops of (f).
+
+    python tools/stream_pool_bench.py --native [--baseline-lib PATH] [--out profiles/stream_pool_native_ab.txt]
 """
 import argparse
 import ctypes
@@ -99,6 +108,14 @@ def setup():
     return model
 
 
+def tick_counts():
+    """The hop counts of one tick of H1 / --native: per session, and per row of the 64-row stream."""
+    import random
+    rnd = random.Random(7)
+    per_session = [rnd.choice((1, 2, 3)) for _ in range(SLOTS)]
+    return per_session, [per_session[r // ROWS] for r in range(SLOTS * ROWS)]
+
+
 def plain_only():
     """Part 2 in this process, on the library BSRNN_HIP_LIB names (default: the in-tree build), through the C ABI alone - the same
     harness for a build with and without the rows calls: one line per shape."""
@@ -152,6 +169,20 @@ def plain_only():
         res = measure(jobs, lambda: check(lib.bsrnn_sync(ctx, None)))
         print("PLAIN %d %d %s" % (C, L, " ".join("%s %.2f %.2f %.2f" % ((k,) + v) for k, v in res.items())), flush=True)
         lib.bsrnn_stream_destroy(st)
+    if hasattr(lib, "bsrnn_stream_process_hops"):              # the hops call of one tick of H1 / --native
+        lib.bsrnn_stream_process_hops.argtypes = [vp, vp, vp, i32, vp, vp, ctypes.c_float, vp]
+        lib.bsrnn_stream_process_hops.restype = ctypes.c_int
+        counts = tick_counts()[1]
+        C, L = len(counts), max(counts)
+        st = vp()
+        check(lib.bsrnn_stream_create(ctx, C, ctypes.byref(st)))
+        check(lib.bsrnn_stream_reserve(st, L))
+        wave = on_device(np.ascontiguousarray(weights.synth_waveform(C, L * HOP, seed=5), np.float32))
+        out = on_device(np.zeros((C, L * HOP), np.float32))
+        cnt = (i32 * C)(*counts)
+        res = measure({"h": lambda: check(lib.bsrnn_stream_process_hops(st, wave, out, L, cnt, None, one, None))}, lambda: check(lib.bsrnn_sync(ctx, None)))
+        print("HOPS %d %d %.2f %.2f %.2f" % ((C, L) + res["h"]), flush=True)
+        lib.bsrnn_stream_destroy(st)
 
 
 def plain_runs(baseline_lib):
@@ -162,6 +193,7 @@ def plain_runs(baseline_lib):
         assert os.path.exists(base), base
         runs = [("baseline", base), ("this build", None), ("baseline", base), ("this build", None)]
     part2 = []
+    HOPS_RUNS[:] = []
     for name, path in runs:
         env = dict(os.environ)
         env.pop("BSRNN_HIP_LIB", None)
@@ -176,7 +208,27 @@ def plain_runs(baseline_lib):
                 f = ln.split()
                 vals = {f[i]: tuple(float(x) for x in f[i + 1:i + 4]) for i in range(3, len(f), 4)}
                 part2.append((name, int(f[1]), int(f[2]), vals))
+            elif ln.startswith("HOPS "):
+                f = ln.split()
+                HOPS_RUNS.append((name, int(f[1]), int(f[2]), tuple(float(x) for x in f[3:6])))
     return part2
+
+
+HOPS_RUNS = []          # plain_runs: [(library, C, L, (median, min, max))] of the bare hops call, one per child process
+
+
+def report_hops_runs(say):
+    say("# bsrnn_stream_process_hops, C = 64, counts from {1, 2, 3} (the tick of --native), each line a process of its own")
+    say("%-11s %4s %4s %28s" % ("library", "C", "L", "h us"))
+    for name, Cc, L, v in HOPS_RUNS:
+        say("%-11s %4d %4d %28s" % (name, Cc, L, cell(v)))
+    h = {n: [v[0] for (nm, _, _, v) in HOPS_RUNS if nm == n] for n in ("baseline", "this build")}
+    two = [v for v in h.values() if len(v) == 2]
+    if two:
+        line = "run-to-run spread of h (same library, two processes) %.1f us" % max(abs(v[0] - v[1]) for v in two)
+        if len(h["baseline"]) == 2 and len(h["this build"]) == 2:
+            line += "; h this build - h baseline (means of the two runs) %+.1f us" % (sum(h["this build"]) / 2 - sum(h["baseline"]) / 2)
+        say(line)
 
 
 def report_plain(say, part2):
@@ -198,7 +250,6 @@ def report_plain(say, part2):
 
 def hops_parts(say):
     """H1 and H2 of --hops, in this process."""
-    import random
     import torch
     from speechseparation_amd import _native, weights
     from speechseparation_amd.bsrnn import StreamingSeparator
@@ -211,9 +262,7 @@ def hops_parts(say):
     say("# us per call (or per tick): median [min .. max] of %d windows of ~%.1f s; inputs resident, deferred range policy" % (REPEATS, WINDOW_S))
     wide = StreamingSeparator(model, channels=C, device="cuda:0")
     wide.reserve(8)
-    rnd = random.Random(7)
-    per_session = [rnd.choice((1, 2, 3)) for _ in range(SLOTS)]
-    counts = [per_session[r // ROWS] for r in range(C)]
+    per_session, counts = tick_counts()
     L = max(counts)
     waves = {k: torch.from_numpy(weights.synth_waveform(C, k * HOP, seed=5)).cuda() for k in (1, 2, 3, 8)}
     outs = {k: torch.empty_like(w) for k, w in waves.items()}
@@ -320,12 +369,84 @@ def rates_part(say):
     say("")
 
 
+def native_part(say):
+    """--native, in this process."""
+    import torch
+    from speechseparation_amd import _native, weights
+    from speechseparation_amd.bsrnn import NativeStreamPool, StreamingSeparator, StreamPool
+    lib, check = _native.lib, _native.check
+    model = setup()
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    one = ctypes.c_float(1.0)
+    C = SLOTS * ROWS
+    say("# %s, %s, compute mode %s" % (torch.cuda.get_device_name(0), torch.version.hip, _native.compute_mode()))
+    say("# us per tick: median [min .. max] of %d windows of ~%.1f s; inputs resident, deferred range policy" % (REPEATS, WINDOW_S))
+    per_session, counts = tick_counts()
+    L = max(counts)
+    audio = torch.from_numpy(weights.synth_waveform(C, L * HOP, seed=5)).cuda()
+    blocks = [audio[ROWS * i:ROWS * (i + 1), :h * HOP].contiguous() for i, h in enumerate(per_session)]
+    # (a) the Python pool
+    pool = StreamPool(model, SLOTS, rows_per_session=ROWS, device="cuda:0")
+    sids = [pool.open() for _ in range(SLOTS)]
+    chunks = {sids[i]: blocks[i] for i in range(SLOTS)}
+    # (b) the native pool through its Python class
+    npool = NativeStreamPool(model, SLOTS, rows_per_session=ROWS, device="cuda:0", max_hops=8)
+    nsids = [npool.open() for _ in range(SLOTS)]
+    nchunks = {nsids[i]: blocks[i] for i in range(SLOTS)}
+    # (c) the library call alone, every array built once
+    cpool = NativeStreamPool(model, SLOTS, rows_per_session=ROWS, device="cuda:0", max_hops=8)
+    for _ in range(SLOTS):
+        cpool.open()
+    h_pool = cpool._pool()
+    i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+    outs = [torch.empty_like(b) for b in blocks]
+    a_slots = (i32 * SLOTS)(*range(SLOTS))
+    a_in = (vp * SLOTS)(*[b.data_ptr() for b in blocks])
+    a_out = (vp * SLOTS)(*[o.data_ptr() for o in outs])
+    a_n = (i64 * SLOTS)(*[b.shape[1] for b in blocks])
+    a_got = (i64 * SLOTS)()
+    # (f) the floor: the bare hops call of the same counts
+    wide = StreamingSeparator(model, channels=C, device="cuda:0")
+    wide.reserve(8)
+    wave = audio.contiguous()
+    wout = torch.empty_like(wave)
+    cnt = (i32 * C)(*counts)
+
+    def job_a():
+        pool.feed(chunks)
+
+    def job_b():
+        npool.feed(nchunks)
+
+    def job_c():
+        check(lib.bsrnn_pool_feed(h_pool, SLOTS, a_slots, a_in, a_n, a_n, a_out, a_n, a_got, None, one, None))
+
+    def job_f():
+        check(lib.bsrnn_stream_process_hops(wide._h, ptr(wave), ptr(wout), L, cnt, None, one, None))
+
+    r = measure({"a": job_a, "b": job_b, "c": job_c, "f": job_f}, torch.cuda.synchronize)
+    model.sync()
+    assert list(a_got) == list(a_n)
+    say("# %d-row stream, %d sessions of %d rows, counts from {1, 2, 3} (seed 7: %s sessions at 1 / 2 / 3 hops), whole hops per session per tick" % (
+        C, SLOTS, ROWS, " / ".join(str(per_session.count(k)) for k in (1, 2, 3))))
+    say("%-64s %28s" % ("a  StreamPool.feed", cell(r["a"])))
+    say("%-64s %28s" % ("b  NativeStreamPool.feed", cell(r["b"])))
+    say("%-64s %28s" % ("c  bsrnn_pool_feed through ctypes, prebuilt arrays", cell(r["c"])))
+    say("%-64s %28s" % ("f  bsrnn_stream_process_hops alone (L = %d): the floor" % L, cell(r["f"])))
+    say("b's windows lie wholly below a's: %s (largest b %.1f us, smallest a %.1f us); a / b = %.2f" % (
+        "yes" if r["b"][2] < r["a"][1] else "NO", r["b"][2], r["a"][1], r["a"][0] / r["b"][0]))
+    say("c - f = %+.1f us: the gather and scatter launches and the table of one tick; b - c = %+.1f us: the Python around the call" % (
+        r["c"][0] - r["f"][0], r["b"][0] - r["c"][0]))
+    say("")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rates", action="store_true", help="time StreamPool.feed with sessions at their own sample rates instead")
     ap.add_argument("--baseline-lib", default=None, help="another build of libbsrnn_hip.so (the parent commit's) for part 2")
     ap.add_argument("--hops", action="store_true", help="time bsrnn_stream_process_hops (H1 - H3 above) instead of part 1")
+    ap.add_argument("--native", action="store_true", help="time the native session pool (bsrnn_pool_feed, NativeStreamPool) instead of part 1")
     ap.add_argument("--plain-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.plain_only:
@@ -343,6 +464,15 @@ def main():
                 f.write("\n".join(lines) + "\n")
         return
     part2 = plain_runs(args.baseline_lib)
+    if args.native:
+        native_part(say)
+        report_plain(say, part2)
+        say("")
+        report_hops_runs(say)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if args.hops:
         hops_parts(say)
         say("# H3 = part 2:")
