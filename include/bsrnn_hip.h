@@ -681,6 +681,46 @@ int     bsrnn_pool_feed_host(bsrnn_pool* p, int32_t n_sessions, const int32_t* s
                              const int64_t* in_stride, const int64_t* n_in, float* const* out_host, const int64_t* out_stride,
                              int64_t* n_out_host, const float* mix_host, float mix);
 
+/* ---- sessions of a pool at their own sample rates -----------------------------------------------
+ * bsrnn_pool_create_rates: a pool whose sessions may give and get audio at one of n_rates declared rates (rates_host [n_rates], n_rates in
+ *     [1, BSRNN_BANK_PAIRS_MAX], each a rate bsrnn_resample converts to and from the model's 44100).  max_block: the most samples per row,
+ *     at its own rate, such a session brings in one feed.  It does ALL first-use work of such a pool on top of bsrnn_pool_create's: the
+ *     tables and carries of an inbound bank (rate -> 44100) and an outbound bank (44100 -> rate) of C rows each, two staging rectangles
+ *     conv_in / conv_out [C, cap] (cap: what max_block samples make at 44.1 kHz, and what a drain needs, in whole hops) and a larger table
+ *     block.  Afterwards bsrnn_debug_counter(0..2) do not move through feeds and drains.
+ * bsrnn_pool_open_rate: bsrnn_pool_open for a session at sample_rate; 44100 gives a plain session (so does bsrnn_pool_open).  Host-only
+ *     apart from the stream-row reset bsrnn_pool_open makes: the slot's rows of both banks are assigned their pair and start afresh.
+ *     bsrnn_pool_close resets them.  bsrnn_pool_rate_of: the session's rate; -1 for a null pool or a slot that is not open.
+ * bsrnn_pool_feed with such a session: n_in[i] counts samples AT ITS RATE (at most max_block), n_out_host[i] is what
+ *     bsrnn_pool_ready(pool, slot, n_in[i]) reports beforehand - the output samples at its rate that have become determined, a count that
+ *     varies from tick to tick - and out_stride[i] must hold that count.  The tick: ONE inbound bank launch for all such sessions that
+ *     bring samples (session pointers -> conv_in, a rate pair, a count and a stream position per row), the rounds as above with conv_in
+ *     and conv_out in the place of these sessions' pointers, ONE outbound bank launch (conv_out -> session pointers): 2 + 3 * rounds
+ *     launches.  The stream's one-hop delay is taken out of such a session's audio: the first hop after open or drain is not handed on.
+ *     bsrnn_pool_pending stays "samples at the MODEL's rate waiting, < 1024".  A feed that names no such session makes exactly the calls
+ *     it made before.  Under BSRNN_RANGE_EXACT a re-run reads the pool's rectangle again: FIFO, bank carries, positions and the dropped
+ *     hop advance once.  Bit for bit what a pool without rates gives with a single-pair bsrnn_resampler per session and direction
+ *     around it (bsrnn_resampler_process of every tick's chunk, the first hop dropped, bsrnn_resampler_process of the result).
+ *     Further refusals (BSRNN_EARG before any device work, the pool untouched, the session named): n_in above max_block; the overlap
+ *     check uses the real n_out.  bsrnn_pool_feed_host refuses a session with a rate.
+ * bsrnn_pool_ready: n_out the next feed of n_in samples would report for the slot (any session); -1 for a null pool, a slot that is
+ *     not open, n_in < 0 or above max_block.  bsrnn_pool_drain_len: what bsrnn_pool_drain would give now; -1 likewise.
+ * bsrnn_pool_drain: the session's audio ends; out_dev (rows out_stride >= the count apart) gets the tail it is still owed and
+ *     *n_out_host the count.  In order, every other session held: the inbound rows are flushed, what waits is padded with zeros to a whole
+ *     hop, one more hop of zeros follows for the stream's delay, those hops run (in rounds), the outbound rows take them and are flushed.
+ *     The slot stays open: its stream rows are reset in the stream's order, both bank rows are reset, the next hop is dropped again and
+ *     nothing is pending.  A session that fed n samples at rate r since open or drain has received, feeds and tail together,
+ *     bsrnn_resample_len(m, 44100, r) samples with m = bsrnn_resample_len(n, r, 44100) rounded up to whole hops.  A plain session drains
+ *     too, in a pool of either kind: the padded hops and one more, as the stream gives them.  mix: the scalar of bsrnn_pool_feed.
+ *     BSRNN_EARG: a null pool or argument, a slot that is not open, out_stride below the count. */
+int     bsrnn_pool_create_rates(bsrnn_ctx* ctx, int32_t slots, int32_t rows_per_session, int32_t max_hops, const int32_t* rates_host,
+                                int32_t n_rates, int64_t max_block, bsrnn_pool** out);
+int     bsrnn_pool_open_rate(bsrnn_pool* p, int32_t sample_rate, int32_t* slot_out);
+int32_t bsrnn_pool_rate_of(const bsrnn_pool* p, int32_t slot);
+int64_t bsrnn_pool_ready(const bsrnn_pool* p, int32_t slot, int64_t n_in);
+int64_t bsrnn_pool_drain_len(const bsrnn_pool* p, int32_t slot);
+int     bsrnn_pool_drain(bsrnn_pool* p, int32_t slot, float* out_dev, int64_t out_stride, int64_t* n_out_host, float mix, void* stream);
+
 /* ---- measurement support ---------------------------------------------------------------
  * bsrnn_set_profiling(ctx, mask): bit i of `mask` brackets stage i of every compute call with
  * hipEvents on the call's stream (mask < 0 = all stages, 0 = off; each bracket costs ~10 us of

@@ -1499,7 +1499,7 @@ class NativeStreamPool:
     results are views of one tensor allocated per feed.  A dict of CPU tensors takes the library's host form (bsrnn_pool_feed_host).
     Same numbers as StreamPool: both make the same hops calls on the same samples (a feed of more than max_hops hops runs in rounds of
     max_hops, where StreamPool's rounds are 255 hops long).  The pool is created at the first call that needs the device; shape and
-    type errors are raised before that.  Sessions with a sample rate of their own: StreamPool(rates=...)."""
+    type errors are raised before that.  Sessions with a sample rate of their own: the subclass NativeRatePool (or StreamPool(rates=...))."""
 
     MODEL_RATE = 44100
 
@@ -1534,18 +1534,28 @@ class NativeStreamPool:
             with torch.cuda.device(self.device):
                 ctx = self.model._context(self.device)
                 h = ctypes.c_void_p()
-                _check(_lib.bsrnn_pool_create(ctx, self.slots, self.rows, self.max_hops, ctypes.byref(h)))
+                self._create(ctx, h)
                 self._h = h
                 # the sessions opened so far: the library hands out the lowest free slot, as open() did
                 used = set(self._slot.values())
                 got = ctypes.c_int32()
                 for k in range(max(used) + 1 if used else 0):
-                    _check(_lib.bsrnn_pool_open(h, ctypes.byref(got)))
+                    self._open_slot(h, k, got)
                     assert got.value == k
                 for k in range(max(used) + 1 if used else 0):
                     if k not in used:
                         _check(_lib.bsrnn_pool_close(h, k))
         return self._h
+
+    def _create(self, ctx, h):
+        _check(_lib.bsrnn_pool_create(ctx, self.slots, self.rows, self.max_hops, ctypes.byref(h)))
+
+    def _open_slot(self, h, slot, got):
+        _check(_lib.bsrnn_pool_open(h, ctypes.byref(got)))
+
+    def _n_out(self, sid, n):
+        """Samples per row the session's next feed of n gives."""
+        return (self.pending(sid) + n) // _spec.HOP * _spec.HOP
 
     def _look_at_weights(self):
         # the same look at the model's parameters as StreamingSeparator.step() takes (see there), once per call
@@ -1636,7 +1646,7 @@ class NativeStreamPool:
         self._look_at_weights()
         n_s = len(chunks)
         sids = list(chunks)
-        n_out = [(self.pending(sid) + chunks[sid].shape[1]) // _spec.HOP * _spec.HOP for sid in sids]
+        n_out = [self._n_out(sid, chunks[sid].shape[1]) for sid in sids]
         block = torch.empty((self.rows * sum(n_out),), dtype=torch.float32, device=self.device if on_cuda else "cpu")
         res, at = {}, 0
         for sid, m in zip(sids, n_out):
@@ -1725,3 +1735,120 @@ class NativeStreamPool:
             fifo[:, :pending.shape[1]] = pending.detach().to("cpu", torch.float32).numpy()
             _check(_lib.bsrnn_pool_set_pending(h, self._slot[sid], fifo.ctypes.data_as(ctypes.c_void_p), int(pending.shape[1])))
         return sid
+
+
+class NativeRatePool(NativeStreamPool):
+    """A NativeStreamPool whose sessions may give and get audio at a sample rate of their own, one of `rates` (at most 16, checked as
+    StreamPool(rates=...) checks them): the library's bsrnn_pool_create_rates / _open_rate / _drain.  A tick is still ONE library call:
+    what all such sessions bring goes to the model's 44.1 kHz in one inbound launch of a resampler bank (reading at the sessions' own
+    pointers), everybody's hops run as before, and one outbound launch converts the result to the sessions' rates at the pointers of
+    their outputs; the stream's one-hop delay is taken out of such a session's audio and drain() ends it.  Same numbers as
+    StreamPool(rates=...), bit for bit, where the rounds coincide (a feed of at most max_hops hops).  max_block: the most samples per
+    row, at its own rate, a session with a rate brings in one feed; the pool's staging is sized by it at creation.  Sessions with a
+    rate take CUDA chunks only, and stay in their pool (export refuses them)."""
+
+    def __init__(self, model, slots, rows_per_session=1, device=None, max_hops=8, rates=(48000,), max_block=48000):
+        rates = StreamPool._checked_rates(rates)
+        if rates is None:
+            raise ValueError("NativeRatePool: rates must be a tuple of sample rates, got None (a pool without is NativeStreamPool)")
+        if isinstance(max_block, bool) or not isinstance(max_block, (int, np.integer)) or not 1 <= max_block <= 1 << 24:
+            raise ValueError("NativeRatePool: max_block must be an int in [1, 2^24], got %r" % (max_block,))
+        super().__init__(model, slots, rows_per_session, device, max_hops)
+        self.rates, self.max_block = rates, int(max_block)
+        self._rate = {}                     # session id -> index into rates, for the sessions that have one
+
+    def _create(self, ctx, h):
+        rates = (ctypes.c_int32 * len(self.rates))(*self.rates)
+        _check(_lib.bsrnn_pool_create_rates(ctx, self.slots, self.rows, self.max_hops, rates, len(self.rates), self.max_block, ctypes.byref(h)))
+
+    def _open_slot(self, h, slot, got):
+        rate = self.MODEL_RATE
+        for sid, k in self._rate.items():
+            if self._slot[sid] == slot:
+                rate = self.rates[k]
+        _check(_lib.bsrnn_pool_open_rate(h, rate, ctypes.byref(got)))
+
+    def _n_out(self, sid, n):
+        return int(_lib.bsrnn_pool_ready(self._h, self._slot[sid], n))
+
+    def open(self, sample_rate=None):
+        """-> a new session's id; its rows start from silence and nothing waits.  sample_rate: None or the model's 44100 for a session
+        at the model's rate, else one of the pool's `rates`.  ValueError when every slot is taken or the rate is not one of them."""
+        k = None
+        if sample_rate is not None and sample_rate != self.MODEL_RATE:
+            if sample_rate not in self.rates:
+                raise ValueError("NativeRatePool.open: sample_rate %r is not one of the pool's rates %r" % (sample_rate, self.rates))
+            k = self.rates.index(sample_rate)
+        if not self._free:
+            raise ValueError("NativeRatePool: all %d slots are in use" % self.slots)
+        slot = self._free.pop(0)
+        sid, self._next = self._next, self._next + 1
+        self._slot[sid] = slot
+        if k is not None:
+            self._rate[sid] = k
+        if self._h is not None:
+            got = ctypes.c_int32()
+            with torch.cuda.device(self.device):
+                self._open_slot(self._h, slot, got)
+            assert got.value == slot
+        return sid
+
+    def close(self, sid):
+        """The session leaves; samples of it that waited are dropped and its rows of the resampler banks start afresh."""
+        super().close(sid)
+        self._rate.pop(sid, None)
+
+    def rate_of(self, sid):
+        """The session's sample rate (44100 for one opened without)."""
+        self._rows_of(sid)
+        return self.rates[self._rate[sid]] if sid in self._rate else self.MODEL_RATE
+
+    def feed(self, chunks, mix=None):
+        """NativeStreamPool.feed; a session opened with a sample rate gives its chunk AT THAT RATE (a CUDA tensor of at most max_block
+        samples per row) and gets back, at that rate, the output samples that have become determined - bsrnn_pool_ready's count, which
+        varies from tick to tick.  pending() stays a count at the model's rate."""
+        if isinstance(chunks, dict):
+            for sid, t in chunks.items():
+                if sid in self._rate and isinstance(t, torch.Tensor) and t.dim() == 2:
+                    if t.shape[1] > self.max_block:
+                        raise ValueError("NativeRatePool.feed: session %r brings %d samples per row, the pool was created for max_block = %d"
+                                         % (sid, t.shape[1], self.max_block))
+                    if not t.is_cuda:
+                        raise ValueError("NativeRatePool.feed: session %r has a sample rate of its own (%d Hz) and brings a CPU chunk; the "
+                                         "host form serves sessions at the model's rate" % (sid, self.rates[self._rate[sid]]))
+        return super().feed(chunks, mix)
+
+    def step(self, chunks, mix=None):
+        """NativeStreamPool.step, for sessions at the model's rate."""
+        if isinstance(chunks, dict):
+            for sid in chunks:
+                if sid in self._rate:
+                    raise ValueError("NativeRatePool.step: session %r has a sample rate of its own (%d Hz): its audio does not come in whole "
+                                     "hops, use feed()" % (sid, self.rates[self._rate[sid]]))
+        return super().step(chunks, mix)
+
+    def export(self, sid):
+        """NativeStreamPool.export, for a session at the model's rate."""
+        self._rows_of(sid)
+        if sid in self._rate:
+            raise ValueError("NativeRatePool.export: session %r has a sample rate of its own (%d Hz); the resamplers' carries do not move "
+                             "with a session" % (sid, self.rates[self._rate[sid]]))
+        return super().export(sid)
+
+    def drain(self, sid, mix=None):
+        """The session's audio ends: -> the tail it is still owed, [rows_per_session, n] on the pool's device, at the session's rate -
+        StreamPool.drain's steps and its LENGTH rule, in one library call (bsrnn_pool_drain).  The session stays open and its next feed()
+        begins a new piece of audio.  mix: None or one float."""
+        slot = self._slot[sid]
+        if mix is not None and (isinstance(mix, bool) or not isinstance(mix, (int, float))):
+            raise ValueError("NativeRatePool.drain: mix must be None or a float, got %s" % type(mix).__name__)
+        h = self._pool()
+        self._look_at_weights()
+        n = int(_lib.bsrnn_pool_drain_len(h, slot))
+        out = torch.empty((self.rows, n), dtype=torch.float32, device=self.device)
+        got = ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            _check(_lib.bsrnn_pool_drain(h, slot, out.data_ptr() if n else None, n, ctypes.byref(got), 1.0 if mix is None else float(mix),
+                                         _stream_ptr(self.device)))
+        assert got.value == n
+        return out

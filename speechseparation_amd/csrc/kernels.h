@@ -377,6 +377,9 @@ void launch_resample(ResampleArgs g, int R, hipStream_t s);
 // floats, rows cap apart, a row reads the set its descriptor names and writes the other; in (null in a flush) / out: rows in_stride /
 // out_stride apart, row r reads in[r][0 .. n_in_r) and writes out[r][0 .. n_j_r).  vec is the launcher's.  tiles [n_pairs] on the host:
 // the pairs' tile sizes, for the grid.
+// THE POINTER FORM (the native session pool's sessions at their own rates): with in_rows / out_rows, tables of C pointers on the
+// device, row r reads at in_rows[r] / writes at out_rows[r] instead of in + r * in_stride / out + r * out_stride - a session's own
+// buffer.  Either side may have one.  Only the entries of rows that run are read; a row's 16-byte loads then depend on its own pointer.
 struct BankPair { const float* tab; int up, down, Kh, ld, chunk, tile; };
 struct BankLaunch {
     const BankPair* pairs;
@@ -384,6 +387,8 @@ struct BankLaunch {
     float* out; int64_t out_stride;
     float* carry; int64_t cap, carry_set;
     int vec;
+    const float* const* in_rows;
+    float* const* out_rows;
 };
 static_assert(sizeof(BankLaunch) <= BANK_ARG_OTHER, "resample_bank_host.h sizes a group of descriptors beside these");
 void launch_resample_bank(BankLaunch L, const int* tiles, const BankRow* rows, int C, hipStream_t s);
@@ -391,7 +396,7 @@ void launch_resample_bank(BankLaunch L, const int* tiles, const BankRow* rows, i
 // ------------------------------------------------------------------ the native session pool's two copies (pool.hip; the plan: pool_host.h)
 // tab [n_entries] on the device: one entry per row of every session a round names.  gather: chunk [C][L*1024] row e.row = the FIFO's
 // n_fifo samples ++ n_in samples of e.src, zeros to the end of the row (L = 0: the rectangle is not touched), then fifo [C][1024] row
-// e.row gets n_pend samples of e.pend_src at pend_off.  scatter: out [C][L*1024] row e.row, its first n_out samples -> e.dst.
+// e.row gets n_pend samples of e.pend_src at pend_off.  scatter: out [C][L*1024] row e.row, samples [out_skip, n_out) -> e.dst.
 void launch_pool_gather(const PoolEntry* tab, int n_entries, float* chunk, float* fifo, int L, hipStream_t s);
 void launch_pool_scatter(const PoolEntry* tab, int n_entries, const float* out, int L, hipStream_t s);
 

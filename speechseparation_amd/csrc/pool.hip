@@ -1,8 +1,9 @@
 // The two copy kernels of the native session pool (bsrnn_pool_feed; the plan and the table: pool_host.h).  Around ONE
 // bsrnn_stream_process_hops per round, the gather launch packs every named session's audio - what waits in its FIFO, then its input -
 // into the [C, L*1024] rectangle the hops call reads and stores what stays waiting; the scatter launch hands every session its hops of the
-// [C, L*1024] result at the session's own pointer and stride.  Under 1 MB per tick: both launches are launch-bound, so they are plain
-// coalesced copies.  A workgroup owns one 1024-sample segment of one table entry (one row of one session), so every length test below
+// [C, L*1024] result at the session's own pointer and stride (for a session with a sample rate of its own both are its rows of the pool's
+// staging rectangles, and the hop of the stream's delay is not handed on: out_skip).  Under 1 MB per tick: both launches are
+// launch-bound, so they are plain coalesced copies.  A workgroup owns one 1024-sample segment of one table entry (one row of one session), so every length test below
 // is workgroup-uniform.  Session pointers and strides are the caller's: only 4-byte alignment is assumed, and a segment moves in
 // 16-byte pieces only when its foreign side happens to be 16-byte aligned (the rectangles are: their rows are whole hops of an aligned
 // allocation).
@@ -60,13 +61,13 @@ __global__ __launch_bounds__(POOL_THREADS) void pool_gather_kernel(const PoolEnt
     }
 }
 
-// grid (L, entries).  out [C][L*1024]; nothing behind an entry's n_out samples is written.
+// grid (L, entries).  out [C][L*1024]; nothing behind an entry's n_out - out_skip samples is written.
 __global__ __launch_bounds__(POOL_THREADS) void pool_scatter_kernel(const PoolEntry* __restrict__ tab, const float* __restrict__ out, const int L)
 {
     const PoolEntry e = tab[blockIdx.y];
     const int seg = blockIdx.x, j0 = seg * POOL_HOP;
-    if (j0 >= e.n_out) return;
-    copy_segment(e.dst + j0, out + ((size_t)e.row * L + seg) * POOL_HOP, threadIdx.x);
+    if (j0 >= e.n_out || j0 < e.out_skip) return;            // (out_skip: the dropped first hop of a session with a rate; whole segments)
+    copy_segment(e.dst + (j0 - e.out_skip), out + ((size_t)e.row * L + seg) * POOL_HOP, threadIdx.x);
 }
 
 }  // namespace

@@ -110,8 +110,11 @@ struct PoolEntry {
     int32_t n_fifo, n_in;
     int32_t n_pend, pend_off;
     int32_t n_out;            // hops * 1024
+    int32_t out_skip;         // scatter: the row's first out_skip samples (0 or 1024) are not handed on; dst is where sample out_skip goes.
+                              // A session with a sample rate of its own, in the round of its first hop (pool_rates_host.h); else 0.
+    int32_t reserved;         // (keeps the pointers of the next entry 8-byte aligned; 0)
 };
-static_assert(sizeof(PoolEntry) == 48, "three pointers and six 32-bit words");
+static_assert(sizeof(PoolEntry) == 56, "three pointers and eight 32-bit words");
 
 // Entry of row `row`, whose input and output of this feed start at in_row / out_row (either may be null when nothing is taken / given)
 inline PoolEntry pool_entry(const PoolPart& q, int32_t row, const float* in_row, float* out_row)
@@ -124,6 +127,7 @@ inline PoolEntry pool_entry(const PoolPart& q, int32_t row, const float* in_row,
     e.n_fifo = q.n_fifo; e.n_in = q.n_in;
     e.n_pend = q.n_pend; e.pend_off = q.pend_off;
     e.n_out = q.hops * POOL_HOP;
+    e.out_skip = 0; e.reserved = 0;
     return e;
 }
 

@@ -180,6 +180,9 @@ __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs g, con
 // kernel-argument segment - and so is its pair's entry of the table in device memory.  The row's input axis counts from its carry
 // origin (resample_bank_host.h), which is all that differs from resample_kernel: resample_tile is that kernel's tile, statement for
 // statement, and forms every output from the same taps in the same order (resample_mac).
+// The pointer form (L.in_rows / L.out_rows, kernels.h): a row's block, or its output, is where its entry of a table in device memory says.
+// The entry is read behind the BANK_ROW_RUNS test, so a held row never reads a stale pointer; 16-byte loads are then the row's own
+// choice (its base aligned to 16 bytes), uniform for the workgroup and made before any barrier.
 __global__ __launch_bounds__(256) void resample_bank_kernel(const BankLaunch L, const BankRows rows)
 {
     __shared__ float xs[RESAMPLE_SPAN];
@@ -194,7 +197,9 @@ __global__ __launch_bounds__(256) void resample_bank_kernel(const BankLaunch L, 
     const int cur = bank_row_cur(d), n_carry = bank_row_n_carry(d);
     ResampleArgs g;
     g.a = L.carry + cur * L.carry_set + r * L.cap; g.a0 = 0; g.a1 = n_carry;
-    g.b = L.in + r * L.in_stride; g.n_total = (int64_t)n_carry + d.n_in;
+    // the pointer form: the row's block is wherever its entry of the table says (read by rows that run alone, with blockIdx.y: uniform)
+    g.b = L.in_rows ? L.in_rows[r] : L.in + r * L.in_stride; g.n_total = (int64_t)n_carry + d.n_in;
+    const int vec = L.in_rows ? (g.b != nullptr && (reinterpret_cast<uintptr_t>(g.b) & 15u) == 0) : L.vec;
     g.tab = p.tab; g.up = p.up; g.down = p.down; g.Kh = p.Kh; g.ld = p.ld; g.chunk = p.chunk; g.tile = p.tile;
     g.c0 = d.keep;
     if (bx == n_tiles) {
@@ -206,7 +211,8 @@ __global__ __launch_bounds__(256) void resample_bank_kernel(const BankLaunch L, 
     const int nj = left < p.tile ? (int)left : p.tile;
     const int64_t c = (int64_t)bank_row_phase(d) + jd * p.down;           // (J + jd) * down = (origin + lead) * up + c
     const int64_t qd = c / p.up;
-    resample_tile(g, L.vec, g.a, g.b, L.out + r * L.out_stride + jd, xs, bank_row_lead(d) + qd, (unsigned)(c - qd * p.up),
+    float* out = L.out_rows ? L.out_rows[r] : L.out + r * L.out_stride;
+    resample_tile(g, vec, g.a, g.b, out + jd, xs, bank_row_lead(d) + qd, (unsigned)(c - qd * p.up),
                   (unsigned)((bank_row_column(d) + jd) % p.up), nj, tid);
 }
 
@@ -245,6 +251,8 @@ void launch_resample_bank(BankLaunch L, const int* tiles, const BankRow* rows, i
             BankLaunch G = L;
             if (G.in) G.in += (int64_t)r0 * L.in_stride;
             if (G.out) G.out += (int64_t)r0 * L.out_stride;
+            if (G.in_rows) G.in_rows += r0;
+            if (G.out_rows) G.out_rows += r0;
             G.carry += (int64_t)r0 * L.cap;
             hipLaunchKernelGGL(resample_bank_kernel, dim3(blocks, n), dim3(256), 0, s, G, group);
         }

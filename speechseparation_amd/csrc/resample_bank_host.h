@@ -48,7 +48,7 @@ BSRNN_RS_HD constexpr int bank_row_pair(const BankRow& d) { return (int)((d.w4 >
 BSRNN_RS_HD constexpr int bank_row_cur(const BankRow& d) { return (int)((d.w4 >> 24) & 1u); }
 
 // Rows per launch.  A dispatch has 4096 bytes of kernel-argument space; 256 of them are the arguments the compiler appends (grid
-// sizes and the like), and 256 more are kept for the kernel's other arguments (BankLaunch, kernels.h: 72 bytes today).  The rest
+// sizes and the like), and 256 more are kept for the kernel's other arguments (BankLaunch, kernels.h: 88 bytes today).  The rest
 // holds BankRow descriptors: 3584 / 20 = 179 rows, so a 64-row pool is one launch and the widest stream (2048 rows) twelve.
 constexpr int BANK_ARG_SPACE = 4096, BANK_ARG_IMPLICIT = 256, BANK_ARG_OTHER = 256;
 constexpr int BANK_GROUP_ROWS = (BANK_ARG_SPACE - BANK_ARG_IMPLICIT - BANK_ARG_OTHER) / (int)sizeof(BankRow);

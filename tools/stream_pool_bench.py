@@ -44,6 +44,15 @@ Then the plain calls, each run a process of its own, this build against --baseli
 bsrnn_stream_process_hops of (f).
 
     python tools/stream_pool_bench.py --native [--baseline-lib PATH] [--out profiles/stream_pool_native_ab.txt]
+
+--native-rates times the native pool's sessions at their own sample rates in the setting of --rates (the 64-row stream, 32 sessions of 2
+rows, rates drawn from {16 000, 32 000, 48 000, 96 000}, one hop's worth of audio per session per tick), three ways in one process,
+alternating:
+  (a) StreamPool(rates=...).feed            (b) NativeRatePool.feed            (c) bsrnn_pool_feed through ctypes with prebuilt arrays
+Two figures per arm: the wall time per tick (the windows above) and the stream time of one tick - two events around a single tick that
+starts on an idle device, so the launch gaps of a host-bound tick are part of it.
+
+    python tools/stream_pool_bench.py --native-rates [--out profiles/stream_pool_native_rates_ab.txt]
 """
 import argparse
 import ctypes
@@ -88,6 +97,23 @@ def measure(jobs, sync):
                 f()
             sync()
             t[k].append((time.perf_counter() - t0) / n[k] * 1e6)
+    return {k: (float(np.median(v)), min(v), max(v)) for k, v in t.items()}
+
+
+def stream_time(jobs, sync, repeats=25):
+    """{name: job} -> {name: (median, min, max)} in us: two events around ONE job that starts on an idle device, alternating."""
+    import numpy as np
+    import torch
+    t = {k: [] for k in jobs}
+    for _ in range(repeats):
+        for k, f in jobs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            sync()
+            e0.record()
+            f()
+            e1.record()
+            sync()
+            t[k].append(e0.elapsed_time(e1) * 1e3)
     return {k: (float(np.median(v)), min(v), max(v)) for k, v in t.items()}
 
 
@@ -369,6 +395,71 @@ def rates_part(say):
     say("")
 
 
+def native_rates_part(say):
+    """--native-rates, in this process."""
+    import random
+    import torch
+    from speechseparation_amd import _native, weights
+    from speechseparation_amd.bsrnn import NativeRatePool, StreamPool
+    lib, check = _native.lib, _native.check
+    model = setup()
+    one = ctypes.c_float(1.0)
+    C = SLOTS * ROWS
+    say("# %s, %s, compute mode %s" % (torch.cuda.get_device_name(0), torch.version.hip, _native.compute_mode()))
+    say("# us per tick: median [min .. max]; wall: %d windows of ~%.1f s; stream: 25 single ticks between two events; inputs resident, "
+        "deferred range policy" % (REPEATS, WINDOW_S))
+    rnd = random.Random(7)
+    per_session = [rnd.choice(RATES) for _ in range(SLOTS)]
+    n_of = {r: (HOP * r + MODEL_RATE // 2) // MODEL_RATE for r in RATES}           # one hop's worth of audio at rate r
+    audio = torch.from_numpy(weights.synth_waveform(C, max(n_of.values()), seed=5)).cuda()
+    blocks = [audio[ROWS * i:ROWS * (i + 1), :n_of[r]].contiguous() for i, r in enumerate(per_session)]
+    # (a) the Python pool with its banks
+    pool = StreamPool(model, SLOTS, rows_per_session=ROWS, device="cuda:0", rates=RATES)
+    sids = [pool.open(sample_rate=r) for r in per_session]
+    chunks = {sids[i]: blocks[i] for i in range(SLOTS)}
+    # (b) the native pool through its Python class
+    npool = NativeRatePool(model, SLOTS, rows_per_session=ROWS, device="cuda:0", max_hops=8, rates=RATES, max_block=max(n_of.values()))
+    nsids = [npool.open(sample_rate=r) for r in per_session]
+    nchunks = {nsids[i]: blocks[i] for i in range(SLOTS)}
+    # (c) the library call alone, every array built once; a tick gives one hop's worth or two, so three fit every output row
+    cpool = NativeRatePool(model, SLOTS, rows_per_session=ROWS, device="cuda:0", max_hops=8, rates=RATES, max_block=max(n_of.values()))
+    for r in per_session:
+        cpool.open(sample_rate=r)
+    h_pool = cpool._pool()
+    i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+    outs = [torch.empty((ROWS, 3 * b.shape[1] + 64), device="cuda") for b in blocks]
+    a_slots = (i32 * SLOTS)(*range(SLOTS))
+    a_in = (vp * SLOTS)(*[b.data_ptr() for b in blocks])
+    a_out = (vp * SLOTS)(*[o.data_ptr() for o in outs])
+    a_n = (i64 * SLOTS)(*[b.shape[1] for b in blocks])
+    a_os = (i64 * SLOTS)(*[o.shape[1] for o in outs])
+    a_got = (i64 * SLOTS)()
+
+    def job_a():
+        pool.feed(chunks)
+
+    def job_b():
+        npool.feed(nchunks)
+
+    def job_c():
+        check(lib.bsrnn_pool_feed(h_pool, SLOTS, a_slots, a_in, a_n, a_n, a_out, a_os, a_got, None, one, None))
+
+    jobs = {"a": job_a, "b": job_b, "c": job_c}
+    r = measure(jobs, torch.cuda.synchronize)
+    g = stream_time(jobs, torch.cuda.synchronize)
+    model.sync()
+    say("# %d-row stream, %d sessions of %d rows, rates from {%s} (seed 7: %s sessions), one hop's worth of audio per session per tick" % (
+        C, SLOTS, ROWS, ", ".join(str(x) for x in RATES), " / ".join(str(per_session.count(x)) for x in RATES)))
+    say("%-56s %28s %28s" % ("", "wall", "stream"))
+    say("%-56s %28s %28s" % ("a  StreamPool(rates=...).feed", cell(r["a"]), cell(g["a"])))
+    say("%-56s %28s %28s" % ("b  NativeRatePool.feed", cell(r["b"]), cell(g["b"])))
+    say("%-56s %28s %28s" % ("c  bsrnn_pool_feed through ctypes, prebuilt arrays", cell(r["c"]), cell(g["c"])))
+    say("wall: a / b = %.2f, a / c = %.2f, b - c = %+.1f us (the Python around the call); b's windows lie wholly below a's: %s" % (
+        r["a"][0] / r["b"][0], r["a"][0] / r["c"][0], r["b"][0] - r["c"][0], "yes" if r["b"][2] < r["a"][1] else "NO"))
+    say("stream: a / b = %.2f, a / c = %.2f" % (g["a"][0] / g["b"][0], g["a"][0] / g["c"][0]))
+    say("")
+
+
 def native_part(say):
     """--native, in this process."""
     import torch
@@ -447,6 +538,7 @@ def main():
     ap.add_argument("--baseline-lib", default=None, help="another build of libbsrnn_hip.so (the parent commit's) for part 2")
     ap.add_argument("--hops", action="store_true", help="time bsrnn_stream_process_hops (H1 - H3 above) instead of part 1")
     ap.add_argument("--native", action="store_true", help="time the native session pool (bsrnn_pool_feed, NativeStreamPool) instead of part 1")
+    ap.add_argument("--native-rates", action="store_true", help="time the native pool's sessions at their own sample rates against StreamPool(rates=...)")
     ap.add_argument("--plain-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.plain_only:
@@ -456,6 +548,13 @@ def main():
     def say(s):
         print(s, flush=True)
         lines.append(s)
+
+    if args.native_rates:
+        native_rates_part(say)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
 
     if args.rates:
         rates_part(say)
