@@ -721,6 +721,37 @@ int64_t bsrnn_pool_ready(const bsrnn_pool* p, int32_t slot, int64_t n_in);
 int64_t bsrnn_pool_drain_len(const bsrnn_pool* p, int32_t slot);
 int     bsrnn_pool_drain(bsrnn_pool* p, int32_t slot, float* out_dev, int64_t out_stride, int64_t* n_out_host, float mix, void* stream);
 
+/* ---- long FIR convolution of ragged rows (room impulse responses) ------------------------
+ * The reference applies a room impulse response to a training clip with torch.nn.functional.conv1d(x, h, padding='same') and
+ * the whole response as the kernel (m_dataset.py:92-114).  These calls compute the same function - for a row x of n samples
+ * and a filter h of k taps, left = (k - 1) / 2:
+ *     y[m] = sum_{j < k} x[m + j - left] * h[j],   x = 0 outside [0, n),   m in [0, n)
+ * (a cross-correlation; the extra sample of padding is on the right for even k) - as a uniformly partitioned overlap-save
+ * convolution on the library's 2048-point transform, for rows of different lengths and different filters in one call.
+ * Against the float64 definition the result is within a few 1e-7 of the output's peak for 1 ... 262144 taps.
+ *
+ * A bank (the create call) holds n_filters filters, 1 <= n_taps <= 262144 each, given as host arrays; the partition spectra
+ * are built on the device once, here (synchronous).  On a host-only context the bank holds the tap counts only: the count
+ * and taps queries answer, the convolve call checks its arguments and then returns BSRNN_ESTATE.  A bank keeps its context
+ * alive like a stream does.  The taps query returns -1 for a filter outside [0, count).
+ *
+ * The convolve call writes out_dev[r * out_stride + m], m < lens_host[r], = row r of in_dev (rows in_stride floats apart)
+ * under filter filter_host[r]; a filter of -1 copies the row unchanged, bit for bit.  Samples of out_dev past lens_host[r]
+ * are not touched, in_dev is not written.  A row's bits depend on the row, its length and its filter alone - not on the
+ * other rows of the call, on R or on the strides.  lens_host and filter_host are free when the call returns; the call is
+ * asynchronous on `stream`.  Refused with BSRNN_EARG and a sentence that names the argument: a null pointer, R < 1, a
+ * length < 1 (or > 2^40), a stride shorter than a length, a filter outside [-1, count), out_dev overlapping the floats
+ * the rows of in_dev span, and in_dev / out_dev on another device than the bank's context.  Workspace: two buffers of
+ * spectra (2050 floats per 1024 samples of every row, and per partition of overhang), grow-only, held by the context; a
+ * call whose rows need more than 65536 spectra per buffer (0.5 GB) runs as consecutive row groups, with the same bits. */
+typedef struct bsrnn_fir_bank bsrnn_fir_bank;
+int     bsrnn_fir_bank_create(bsrnn_ctx* ctx, int32_t n_filters, const float* const* taps_host, const int32_t* n_taps_host, bsrnn_fir_bank** out);
+void    bsrnn_fir_bank_destroy(bsrnn_fir_bank* bank);
+int32_t bsrnn_fir_bank_count(const bsrnn_fir_bank* bank);
+int32_t bsrnn_fir_bank_taps(const bsrnn_fir_bank* bank, int32_t filter);
+int     bsrnn_convolve_ragged(bsrnn_fir_bank* bank, const float* in_dev, int64_t in_stride, const int64_t* lens_host,
+                              const int32_t* filter_host, float* out_dev, int64_t out_stride, int32_t R, void* stream);
+
 /* ---- measurement support ---------------------------------------------------------------
  * bsrnn_set_profiling(ctx, mask): bit i of `mask` brackets stage i of every compute call with
  * hipEvents on the call's stream (mask < 0 = all stages, 0 = off; each bracket costs ~10 us of

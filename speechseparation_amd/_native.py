@@ -35,6 +35,7 @@ SYMBOLS = [
     "bsrnn_pool_create", "bsrnn_pool_destroy", "bsrnn_pool_open", "bsrnn_pool_close", "bsrnn_pool_pending", "bsrnn_pool_stream",
     "bsrnn_pool_get_pending", "bsrnn_pool_set_pending", "bsrnn_pool_feed", "bsrnn_pool_feed_host",
     "bsrnn_pool_create_rates", "bsrnn_pool_open_rate", "bsrnn_pool_rate_of", "bsrnn_pool_ready", "bsrnn_pool_drain_len", "bsrnn_pool_drain",
+    "bsrnn_fir_bank_create", "bsrnn_fir_bank_destroy", "bsrnn_fir_bank_count", "bsrnn_fir_bank_taps", "bsrnn_convolve_ragged",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
@@ -150,6 +151,11 @@ def _load():
         "bsrnn_pool_ready": (i64, [vp, i32, i64]),
         "bsrnn_pool_drain_len": (i64, [vp, i32]),
         "bsrnn_pool_drain": (C.c_int, [vp, i32, vp, i64, C.POINTER(i64), C.c_float, vp]),
+        "bsrnn_fir_bank_create": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp)]),
+        "bsrnn_fir_bank_destroy": (None, [vp]),
+        "bsrnn_fir_bank_count": (i32, [vp]),
+        "bsrnn_fir_bank_taps": (i32, [vp, i32]),
+        "bsrnn_convolve_ragged": (C.c_int, [vp, vp, i64, C.POINTER(i64), C.POINTER(i32), vp, i64, i32, vp]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),
         "bsrnn_stage_name": (C.c_char_p, [i32]),

@@ -1,0 +1,165 @@
+"""The reference's two training augmentations on the device: room impulse responses (m_dataset.py:92-114) and the re-mix of
+MixDataSet (:141-180).
+
+The reference convolves a clip with a whole room impulse response - tens of thousands of taps - through
+torch.nn.functional.conv1d(padding='same').  `FirBank` computes the same function with the library's partitioned FFT convolution
+(include/bsrnn_hip.h, bsrnn_convolve_ragged): rows of different lengths, each under its own filter, in one call.  `rir_draw` makes the
+reference's random decisions for a clip, `reverb_pairs` applies them to the clips of an optimizer step, `remix` is MixDataSet's arithmetic.
+"""
+import ctypes
+import random
+
+import numpy as np
+import torch
+
+from . import _native
+from .bsrnn import BSRNN, _ptr, _stream_ptr
+
+_lib = _native.lib
+_check = _native.check
+MAX_TAPS = 262144                           # CONV_MAX_TAPS of csrc/convolve_host.h
+
+
+class FirBank:
+    """A set of FIR filters on the model's device (bsrnn_fir_bank_*): `filters` is a list of 1-D float32 arrays or tensors of 1 ... 262144
+    taps.  Their partition spectra are built once, here.  `convolve` applies them as torch.nn.functional.conv1d(x, h, padding='same') does."""
+
+    def __init__(self, model, filters):
+        filters = list(filters)
+        if not filters:
+            raise ValueError("FirBank: need at least one filter")
+        taps = []
+        for i, h in enumerate(filters):
+            a = h.detach().cpu().numpy() if isinstance(h, torch.Tensor) else np.asarray(h)
+            if a.ndim != 1 or a.dtype != np.float32 or not 1 <= a.shape[0] <= MAX_TAPS:
+                raise ValueError("FirBank: filter %d must be a 1-D float32 array of 1 ... %d taps, got %s %s" % (i, MAX_TAPS, a.shape, a.dtype))
+            taps.append(np.ascontiguousarray(a))
+        self.model = model
+        self.device = torch.device("cuda", model._ctx_device if model._ctx_device is not None else torch.cuda.current_device())
+        n = len(taps)
+        ptrs = (ctypes.c_void_p * n)(*[t.ctypes.data for t in taps])
+        counts = (ctypes.c_int32 * n)(*[t.shape[0] for t in taps])
+        with torch.cuda.device(self.device):
+            ctx = model._context(self.device)
+            h = ctypes.c_void_p()
+            _check(_lib.bsrnn_fir_bank_create(ctx, n, ptrs, counts, ctypes.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            _lib.bsrnn_fir_bank_destroy(self._h)
+        except Exception:
+            pass
+
+    def __len__(self):
+        return int(_lib.bsrnn_fir_bank_count(self._h))
+
+    def taps(self, i):
+        k = int(_lib.bsrnn_fir_bank_taps(self._h, int(i)))
+        if k < 0:
+            raise IndexError("FirBank.taps: filter %r of %d" % (i, len(self)))
+        return k
+
+    def convolve(self, wave, lengths=None, filters=None, out=None):
+        """wave [R, n_max] float32 on the bank's device -> out [R, n_max]: out[r, :lengths[r]] = conv1d(wave[r, :lengths[r]], filter
+        filters[r], padding='same'); a filter of -1 copies the row, bit for bit.  lengths defaults to n_max for every row, filters to
+        filter 0.  What lies behind a row's length is not read, and in a given `out` not written (a new `out` holds zeros there).  Views
+        with a row stride (buf[:, a:b], a channel slice) go by pointer, uncopied; `out` must not overlap the input."""
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] < 1 or wave.shape[1] < 1:
+            raise ValueError("FirBank.convolve: expected wave [R, n_max] with n_max >= 1, got %s" % (
+                tuple(wave.shape) if isinstance(wave, torch.Tensor) else type(wave).__name__,))
+        if wave.dtype != torch.float32:
+            raise ValueError("FirBank.convolve: expected a float32 tensor, got %s" % wave.dtype)
+        if not wave.is_cuda:
+            raise _native.NativeError("FirBank.convolve: the waveform must be on a HIP device")
+        if wave.device != self.device:
+            raise ValueError("FirBank.convolve: the waveform is on %s, the bank on %s" % (wave.device, self.device))
+        R, n_max = wave.shape
+        lens = [n_max] * R if lengths is None else [int(n) for n in lengths]
+        filt = [0] * R if filters is None else [int(f) for f in filters]
+        if len(lens) != R or len(filt) != R:
+            raise ValueError("FirBank.convolve: %d lengths and %d filters for %d rows" % (len(lens), len(filt), R))
+        for r in range(R):
+            if not 1 <= lens[r] <= n_max:
+                raise ValueError("FirBank.convolve: row %d has length %d, need 1 <= length <= %d" % (r, lens[r], n_max))
+            if not -1 <= filt[r] < len(self):
+                raise ValueError("FirBank.convolve: row %d names filter %d of %d" % (r, filt[r], len(self)))
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != wave.device
+                                or tuple(out.shape) != (R, n_max) or (out.stride(1) != 1 and n_max > 1) or (R > 1 and out.stride(0) < n_max)):
+            raise ValueError("FirBank.convolve: out must be a float32 tensor %s with contiguous rows that do not overlap on %s" % ((R, n_max), wave.device))
+        w, w_stride = BSRNN._rows_view(wave.detach())
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.zeros((R, n_max), device=self.device, dtype=torch.float32)
+            o_stride = out.stride(0) if R > 1 else n_max
+            _check(_lib.bsrnn_convolve_ragged(self._h, _ptr(w), w_stride, (ctypes.c_int64 * R)(*lens), (ctypes.c_int32 * R)(*filt), _ptr(out),
+                                              o_stride, R, _stream_ptr(self.device)))
+        return out
+
+
+def rir_draw(idx, n_rirs, channels_of, prob=0.1):
+    """The reference's decisions for training clip `idx` (m_dataset.py:83-102), in its order, on a random.Random(idx) (the reference seeds
+    the global generator with idx): the weighted choices([True, False]), choices(rirs), and one randint(0, C - 1) per ear, C =
+    channels_of(rir) the channel count of the chosen response.  Returns None (no reverberation) or (rir, channel 1, channel 2)."""
+    rng = random.Random(idx)
+    if not rng.choices([True, False], weights=[prob, 1.0 - prob])[0]:
+        return None
+    rir = rng.choices(range(n_rirs))[0]
+    c = channels_of(rir)
+    return rir, rng.randint(0, c - 1), rng.randint(0, c - 1)
+
+
+def reverb_pairs(bank, mixes, draws, chain=True):
+    """Applies the drawn responses to the mixtures of an optimizer step, in place.  mixes: a list of [2, n] float32 tensors on the bank's
+    device; draws: per clip None or (filter for row 0, filter for row 1) of `bank`.
+
+    chain=True is the reference AS WRITTEN: row 0 becomes conv(a[0], rir1), and row 1 becomes conv(THAT RESULT, rir2) - m_dataset.py:111
+    convolves a1 again, not a2, so the right channel of a reverberant clip is the left one under both responses.  chain=False convolves
+    a[1] with rir2.  All chosen rows of the step go through ONE convolve call per stage (two with chain=True), not one per clip."""
+    chosen = [i for i, d in enumerate(draws) if d is not None]
+    if not chosen:
+        return mixes
+    n_max = max(mixes[i].shape[1] for i in chosen)
+    dev = mixes[chosen[0]].device
+    lens = [mixes[i].shape[1] for i in chosen]
+    if chain:
+        src = torch.zeros((len(chosen), n_max), device=dev, dtype=torch.float32)
+        for j, i in enumerate(chosen):
+            src[j, :lens[j]] = mixes[i][0]
+        first = bank.convolve(src, lens, [draws[i][0] for i in chosen])
+        second = bank.convolve(first, lens, [draws[i][1] for i in chosen])
+        for j, i in enumerate(chosen):
+            mixes[i][0] = first[j, :lens[j]]
+            mixes[i][1] = second[j, :lens[j]]
+        return mixes
+    src = torch.zeros((2 * len(chosen), n_max), device=dev, dtype=torch.float32)
+    for j, i in enumerate(chosen):
+        src[2 * j:2 * j + 2, :lens[j]] = mixes[i]
+    res = bank.convolve(src, [n for n in lens for _ in range(2)], [f for i in chosen for f in draws[i]])
+    for j, i in enumerate(chosen):
+        mixes[i][:] = res[2 * j:2 * j + 2, :lens[j]]
+    return mixes
+
+
+def _random_resize(x, length, rng):
+    # m_dataset.py:123-139 (a clip of exactly `length` samples raises in randint(0, -1), as in the reference)
+    if x.shape[1] < length:
+        missing = length - x.shape[1]
+        left = rng.randint(0, missing)
+        z = torch.zeros((x.shape[0], 1), dtype=x.dtype)
+        return torch.cat((z.repeat((1, left)).to(x.device), x, z.repeat((1, missing - left)).to(x.device)), dim=1)
+    left = rng.randint(0, x.shape[1] - length - 1)
+    return x[:, left:left + length]
+
+
+def remix(dialog, backgrounds, length, rng):
+    """MixDataSet.__getitem__'s arithmetic (m_dataset.py:158-178) on loaded tensors [ch, n], on their device: every background is
+    random_resize'd to `length` (zero padding split at random, or a random cut), then scaled by uniform(0.1, 1.0); the dialog's scale is
+    drawn and - as in the reference, where the multiplication is commented out - not applied; the dialog is resized; the mixture is
+    dialog + sum(backgrounds).  `rng` (a random.Random, or the random module) is drawn from in the reference's order.  Returns
+    (mixture, dialog)."""
+    backgrounds = [_random_resize(x, length, rng) for x in backgrounds]
+    backgrounds = [x * rng.uniform(0.1, 1.0) for x in backgrounds]
+    rng.uniform(0.1, 1.0)                    # scale_dialog: drawn, unused
+    dialog = _random_resize(dialog, length, rng)
+    return dialog + sum(backgrounds), dialog

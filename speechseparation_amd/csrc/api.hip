@@ -222,6 +222,13 @@ struct bsrnn_ctx {
     // on the host and uploaded at first use (bsrnn_debug_counter(0)); grow-only, a handful of entries of at most 100 KB, freed with the context.
     struct ResampleTable { ResampleRatio q; ResampleTiling g; float* d; };
     std::vector<ResampleTable> rs_tables;
+
+    // Long FIR convolution (bsrnn_convolve_ragged): the two spectrum buffers of a row group, `frames` spectra of CONV_LD floats each.
+    // Grow-only; the row table of a call travels in the ragged calls' block above (rg).
+    struct Conv {
+        float *X = nullptr, *Y = nullptr;
+        int64_t frames = 0;
+    } cv;
 };
 
 struct bsrnn_stream {
@@ -986,6 +993,8 @@ static void destroy_now(bsrnn_ctx* c)
     if (c->er.h_part) (void)hipHostFree(c->er.h_part);
     if (c->er.d_est) (void)hipFree(c->er.d_est);
     for (auto& t : c->rs_tables) (void)hipFree(t.d);
+    if (c->cv.X) (void)hipFree(c->cv.X);
+    if (c->cv.Y) (void)hipFree(c->cv.Y);
     for (hipEvent_t e : c->er.ev)
         if (e) (void)hipEventDestroy(e);
     if (c->ev_ovl_fork) (void)hipEventDestroy(c->ev_ovl_fork);
@@ -3111,6 +3120,160 @@ int bsrnn_resampler_process(bsrnn_resampler* rs, const float* in, int64_t in_str
 int bsrnn_resampler_flush(bsrnn_resampler* rs, float* out, int64_t out_stride, int64_t* n_out_host, void* stream)
 {
     return resampler_run(rs, nullptr, 0, 0, out, out_stride, n_out_host, true, (hipStream_t)stream);
+}
+
+// --------------------------------------------------------------------------- long FIR convolution of ragged rows
+// torch.nn.functional.conv1d(x, h, padding='same') with the whole filter as the kernel (m_dataset.py:92-114: a room impulse response of tens
+// of thousands of taps), as a uniformly partitioned overlap-save convolution on the library's own transform.  The definition, the plan and
+// the row groups: convolve_host.h; the kernels: fft.hip.  A bank holds the partition spectra of its filters, built once.
+struct bsrnn_fir_bank {
+    bsrnn_ctx* ctx;
+    std::vector<int32_t> taps;       // taps per filter
+    std::vector<size_t> off;         // where a filter's image starts in d_images (floats)
+    float* d_images;                 // [sum of P][CONV_LD]; null on a host-only context (the bank then only answers count / taps and refusals)
+};
+
+int bsrnn_fir_bank_create(bsrnn_ctx* c, int32_t n_filters, const float* const* taps_host, const int32_t* n_taps_host, bsrnn_fir_bank** out)
+{
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!out || !taps_host || !n_taps_host || n_filters < 1)
+        return fail(BSRNN_EARG, "bsrnn_fir_bank_create: need n_filters >= 1 filters (taps_host, n_taps_host) and a place for the object, got n_filters = %d", n_filters);
+    size_t n_taps = 0, n_img = 0;
+    for (int i = 0; i < n_filters; ++i) {
+        if (!taps_host[i]) return fail(BSRNN_EARG, "bsrnn_fir_bank_create: taps_host[%d] is null", i);
+        if (n_taps_host[i] < 1 || n_taps_host[i] > CONV_MAX_TAPS)
+            return fail(BSRNN_EARG, "bsrnn_fir_bank_create: n_taps_host[%d] = %d is outside [1, %d]", i, n_taps_host[i], CONV_MAX_TAPS);
+        n_taps += (size_t)n_taps_host[i];
+        n_img += (size_t)conv_image_floats(n_taps_host[i]);
+    }
+    if (c->zombie) return fail(BSRNN_ESTATE, "context was destroyed");
+    std::unique_ptr<bsrnn_fir_bank> bk(new bsrnn_fir_bank());
+    bk->ctx = c; bk->d_images = nullptr;
+    size_t at = 0;
+    for (int i = 0; i < n_filters; ++i) { bk->taps.push_back(n_taps_host[i]); bk->off.push_back(at); at += (size_t)conv_image_floats(n_taps_host[i]); }
+    if (c->device >= 0) {
+        if (int rc = check_device(c)) return rc;
+        CallGuard guard_(c);
+        if (!guard_.ok) return guard_.refuse();
+        // one allocation: the images, then the taps as the caller gave them (read by the launches below, not kept apart afterwards)
+        float* p = nullptr;
+        ++g_dbg[DBG_ALLOC];
+        hipError_t e = hipMalloc((void**)&p, (n_img + n_taps) * sizeof(float));
+        size_t t_at = n_img;
+        for (int i = 0; e == hipSuccess && i < n_filters; ++i) {
+            e = hipMemcpy(p + t_at, taps_host[i], (size_t)n_taps_host[i] * sizeof(float), hipMemcpyHostToDevice);
+            if (e == hipSuccess) { launch_fir_taps(c->tb, p + t_at, n_taps_host[i], p + bk->off[i], nullptr); e = hipGetLastError(); }
+            t_at += (size_t)n_taps_host[i];
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) { if (p) (void)hipFree(p); return fail(BSRNN_EHIP, "bsrnn_fir_bank_create: %s", hipGetErrorString(e)); }
+        bk->d_images = p;
+    }
+    ++c->live_streams;
+    *out = bk.release();
+    return 0;
+}
+
+void bsrnn_fir_bank_destroy(bsrnn_fir_bank* bk)
+{
+    if (!bk) return;
+    bsrnn_ctx* c = bk->ctx;
+    if (c->device >= 0) {
+        (void)hipSetDevice(c->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(bk->d_images);
+    }
+    delete bk;
+    if (--c->live_streams == 0 && c->zombie) destroy_now(c);     // as bsrnn_resampler_destroy
+}
+
+int32_t bsrnn_fir_bank_count(const bsrnn_fir_bank* bk) { return bk ? (int32_t)bk->taps.size() : -1; }
+int32_t bsrnn_fir_bank_taps(const bsrnn_fir_bank* bk, int32_t filter)
+{
+    return (bk && filter >= 0 && filter < (int32_t)bk->taps.size()) ? bk->taps[filter] : -1;
+}
+
+int bsrnn_convolve_ragged(bsrnn_fir_bank* bk, const float* in, int64_t in_stride, const int64_t* lens_host, const int32_t* filter_host, float* out,
+                          int64_t out_stride, int32_t R, void* stream)
+{
+    // arguments first, device or not (a bank of a host-only context answers them before BSRNN_ESTATE)
+    if (!bk) return fail(BSRNN_EARG, "null FIR bank");
+    if (!in || !lens_host || !filter_host || !out)
+        return fail(BSRNN_EARG, "bsrnn_convolve_ragged: null argument (need in_dev, lens_host, filter_host and out_dev)");
+    if (R < 1) return fail(BSRNN_EARG, "bsrnn_convolve_ragged: need R >= 1 rows, got R = %d", R);
+    const int32_t count = (int32_t)bk->taps.size();
+    size_t in_ext = 0, out_ext = 0;                                   // floats the rows span: behind the last row of a view lies somebody else's memory
+    for (int r = 0; r < R; ++r) {
+        const int64_t n = lens_host[r];
+        if (n < 1 || n > CONV_MAX_LEN)
+            return fail(BSRNN_EARG, "bsrnn_convolve_ragged: lens_host[%d] = %lld is outside [1, 2^40]", r, (long long)n);
+        if (in_stride < n)
+            return fail(BSRNN_EARG, "bsrnn_convolve_ragged: in_stride %lld is less than lens_host[%d] = %lld", (long long)in_stride, r, (long long)n);
+        if (out_stride < n)
+            return fail(BSRNN_EARG, "bsrnn_convolve_ragged: out_stride %lld is less than lens_host[%d] = %lld", (long long)out_stride, r, (long long)n);
+        if (filter_host[r] < -1 || filter_host[r] >= count)
+            return fail(BSRNN_EARG, "bsrnn_convolve_ragged: filter_host[%d] = %d is outside [-1, %d)", r, filter_host[r], count);
+        in_ext = std::max(in_ext, (size_t)r * in_stride + (size_t)n);
+        out_ext = std::max(out_ext, (size_t)r * out_stride + (size_t)n);
+    }
+    if (ranges_overlap(in, in_ext * sizeof(float), out, out_ext * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_convolve_ragged: out_dev must not overlap the floats the rows of in_dev span (rows are read while others are written)");
+    bsrnn_ctx* c = bk->ctx;
+    if (int rc = check_device(c)) return rc;
+    for (const void* ptr : {(const void*)in, (const void*)out}) {     // the images live on the bank's device
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); continue; }
+        if (at.type == hipMemoryTypeDevice && at.device != c->device)
+            return fail(BSRNN_EARG, "bsrnn_convolve_ragged: %s lies on device %d, the bank was created on a context of device %d",
+                        ptr == (const void*)in ? "in_dev" : "out_dev", at.device, c->device);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    // the plan: what every row computes, the row groups, where a row's spectra lie in its group's buffers
+    std::vector<ConvRow> rows(R);
+    std::vector<int64_t> nx(R), nb(R);
+    for (int r = 0; r < R; ++r) {
+        ConvRow& q = rows[r];
+        q = ConvRow{};
+        q.n = lens_host[r];
+        if (filter_host[r] < 0) { q.nb = (int)conv_copy_blocks(q.n); nx[r] = nb[r] = 0; continue; }
+        const int k = bk->taps[filter_host[r]];
+        const ConvPlan pl = conv_plan(q.n, k);
+        q.H = bk->d_images + bk->off[filter_host[r]];
+        q.shift = pl.shift; q.P = pl.P; q.u0 = (int)pl.u0; q.nb = (int)pl.nb; q.f0 = (int)pl.f0; q.nx = (int)pl.nx;
+        nx[r] = pl.nx; nb[r] = pl.nb;
+    }
+    const std::vector<ConvGroup> groups = conv_groups(nx.data(), nb.data(), R);
+    int64_t need = 0;
+    for (const ConvGroup& g : groups) {
+        need = std::max(need, std::max(g.x_frames, g.y_frames));
+        int64_t xo = 0, yo = 0;
+        for (int r = g.first; r < g.first + g.rows; ++r) { rows[r].xoff = xo; rows[r].yoff = yo; xo += nx[r]; yo += nb[r]; }
+    }
+    bsrnn_ctx::Conv& cv = c->cv;
+    if (need > cv.frames) {
+        HIP_TRY(hipDeviceSynchronize());                              // queued kernels use the old buffers
+        if (cv.X) (void)hipFree(cv.X);
+        if (cv.Y) (void)hipFree(cv.Y);
+        cv.X = cv.Y = nullptr; cv.frames = 0;
+        const int64_t want = need >= CONV_FRAME_BUDGET ? need : std::min<int64_t>(CONV_FRAME_BUDGET, need + need / 4 + 16);
+        g_dbg[DBG_ALLOC] += 2;
+        HIP_TRY(hipMalloc((void**)&cv.X, (size_t)want * CONV_LD * sizeof(float)));
+        const hipError_t e = hipMalloc((void**)&cv.Y, (size_t)want * CONV_LD * sizeof(float));
+        if (e != hipSuccess) { (void)hipFree(cv.X); cv.X = nullptr; return fail(BSRNN_EHIP, "hipMalloc: %s", hipGetErrorString(e)); }
+        cv.frames = want;
+    }
+    const char* d = nullptr;
+    const size_t bytes = (size_t)R * sizeof(ConvRow);
+    if (int rc = ragged_upload_block(c, bytes, s, [&](char* h) { memcpy(h, rows.data(), bytes); }, &d)) return rc;
+    const ConvRow* d_rows = reinterpret_cast<const ConvRow*>(d);
+    for (const ConvGroup& g : groups) {
+        int max_nx = 0, max_nb = 0;
+        for (int r = g.first; r < g.first + g.rows; ++r) { max_nx = std::max(max_nx, rows[r].nx); max_nb = std::max(max_nb, rows[r].nb); }
+        launch_fir_group(c->tb, d_rows, g.first, g.rows, max_nx, max_nb, in, in_stride, out, out_stride, cv.X, cv.Y, s);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
 }
 
 // A bank of streaming resamplers: every row on one of the declared pairs and at its own place in its own stream, one launch per call

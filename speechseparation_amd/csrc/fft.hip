@@ -1235,4 +1235,206 @@ void launch_long_compact(const float* state_src, float* state_dst, const float* 
                        (size_t)R_old * K * (HID / 4), n4, reinterpret_cast<const float4*>(carry_src), reinterpret_cast<float4*>(carry_dst), c4);
 }
 
+// ------------------------------------------------------------------------------ long FIR convolution of ragged rows (bsrnn_convolve_ragged)
+// Uniformly partitioned overlap-save on the 2048-point transform above (the definition and the plan: convolve_host.h): a rectangular-window
+// analysis walk at hop 1024 with zeros outside the row, a complex multiply-accumulate per bin over the filter's partitions, and a synthesis
+// walk that keeps the second half of every inverse frame.  Spectra are plain rows of 1025 (re, im) pairs (tb.colmap = null, CONV_LD floats).
+// Every kernel finds its row in a table of ConvRow on the device; what a row computes depends on that entry alone, so a row has the same
+// bits in every batch, group and launch shape.
+//
+// Analysis: stft_walk without the window.  sample2(t, c) = complex sample c of frame t, row(t) = where its spectrum goes.
+template <class SAMPLE2, class ROW>
+__device__ __forceinline__ void fir_analysis_walk(const FftTables& tb, float2* z0, float2* z1, int tid, int t0, int t1, SAMPLE2 sample2, ROW row)
+{
+    const Twiddles twd = load_twiddles<false>(tb.tw1024, tid);
+    const SplitCtx spl = load_split(tb, tid, false);
+    float2 raw[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) raw[k] = sample2(t0, tid + 256 * k);
+    for (int t = t0; t < t1; ++t) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) z0[tid + 256 * k] = raw[k];
+        __syncthreads();
+        raw[0] = raw[2]; raw[1] = raw[3];
+        { const int tn = t + 1 < t1 ? t + 1 : t; raw[2] = sample2(tn, tid + 512); raw[3] = sample2(tn, tid + 768); }      // (after the last frame a dummy reload)
+        const float2* Z = fft1024<false>(z0, z1, twd, tid);
+        rfft_split_store(Z, spl, row(t), tid);
+        __syncthreads();                          // Z (= z1) is overwritten by the next frame's first pass
+    }
+}
+
+// frames [f0 + chunk, ...) of a row: frame t holds x[(t - 1) 1024, (t + 1) 1024), zeros outside [0, n)
+__global__ __launch_bounds__(256, FFT_OCC_STFT) void fir_analysis_kernel(FftTables tb, const ConvRow* __restrict__ rows, int row0, const float* __restrict__ in,
+                                                                         int64_t in_stride, float* __restrict__ X, int sch)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const int r = row0 + blockIdx.y;
+    const ConvRow q = rows[r];
+    const int t0 = q.f0 + blockIdx.x * sch;
+    const int t1 = (t0 + sch < q.f0 + q.nx) ? t0 + sch : q.f0 + q.nx;
+    if (!q.H || t0 >= t1) return;                                     // (uniform over the workgroup, before any barrier)
+    const float* src = in + (size_t)r * in_stride;
+    const int64_t n = q.n;
+    auto sample2 = [&](int t, int c) {
+        float v[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int64_t idx = (int64_t)(t - 1) * HOPS + 2 * c + e;
+            v[e] = (idx >= 0 && idx < n) ? src[idx] : 0.f;
+        }
+        return make_float2(v[0], v[1]);
+    };
+    auto row = [&](int t) { return X + (size_t)(q.xoff + (t - q.f0)) * CONV_LD; };
+    fir_analysis_walk(tb, z0, z1, tid, t0, t1, sample2, row);
+}
+
+// The filter image: partition p of g[i] = h[k - 1 - i], zero-padded to 2048, through the same walk (one frame per workgroup: a partition's
+// second half is zeros, not the next partition's first half).
+__global__ __launch_bounds__(256, FFT_OCC_STFT) void fir_taps_kernel(FftTables tb, const float* __restrict__ h, int k, float* __restrict__ H)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const int p = blockIdx.x;
+    auto sample2 = [&](int t, int c) {
+        float v[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int i = t * HOPS + 2 * c + e;
+            v[e] = (c < 512 && i < k) ? h[k - 1 - i] : 0.f;
+        }
+        return make_float2(v[0], v[1]);
+    };
+    auto row = [&](int t) { return H + (size_t)t * CONV_LD; };
+    fir_analysis_walk(tb, z0, z1, tid, p, p + 1, sample2, row);
+}
+
+// Multiply-accumulate: Y[u][f] = sum_p H[p][f] X[u - p][f] over the partitions whose frame the row has (conv_span), p ascending.  One thread
+// owns one bin of TL consecutive blocks: their accumulators and the TL frames X[u - p] of the current p stay in registers, and a step to
+// p + 1 brings one new frame in (the window moves down by one), so every H and X value fetched is used TL times; loads are coalesced along
+// the bins.  The window is a ring whose phase is the unrolled step number - no register is moved.  The four fused multiply-adds of a complex
+// product are spelled out, so a block's sum is the same chain of roundings wherever the block sits in a tile.
+template <int TL>
+__global__ __launch_bounds__(256) void fir_mac_kernel(const ConvRow* __restrict__ rows, int row0, const float* __restrict__ X, float* __restrict__ Y)
+{
+    const ConvRow q = rows[row0 + blockIdx.z];
+    const int b0 = blockIdx.x * TL;                                   // the tile's first block, counted from u0
+    const int f = blockIdx.y * 256 + threadIdx.x;
+    if (!q.H || b0 >= q.nb || f > 1024) return;
+    const int nt = q.nb - b0 < TL ? q.nb - b0 : TL;
+    const int ut = q.u0 + b0, f1 = q.f0 + q.nx - 1;
+    const int p_lo = ut - f1 > 0 ? ut - f1 : 0;
+    const int p_hi = ut + nt - 1 < q.P - 1 ? ut + nt - 1 : q.P - 1;
+    const float2* __restrict__ Xr = reinterpret_cast<const float2*>(X + (size_t)q.xoff * CONV_LD) + f;
+    const float2* __restrict__ Hf = reinterpret_cast<const float2*>(q.H) + f;
+    auto frame = [&](int v) {                                         // X[v][f], zero for a frame the row does not have (uniform)
+        return (v >= q.f0 && v <= f1) ? Xr[(size_t)(v - q.f0) * (CONV_LD / 2)] : make_float2(0.f, 0.f);
+    };
+    float2 acc[TL], ring[TL];
+#pragma unroll
+    for (int j = 0; j < TL; ++j) { acc[j] = make_float2(0.f, 0.f); ring[j] = frame(ut + j - p_lo); }
+    // step s of a pass: the frame of output j is ring[(j - s) mod TL]; the frame that enters replaces the one output TL - 1 used
+    auto pass = [&](int p, auto full) {
+#pragma unroll
+        for (int s = 0; s < TL; ++s) {
+            if (!decltype(full)::value && p + s > p_hi) break;
+            const float2 h = Hf[(size_t)(p + s) * (CONV_LD / 2)];
+            const float2 fresh = frame(ut - (p + s) - 1);
+#pragma unroll
+            for (int j = 0; j < TL; ++j) {
+                const float2 w = ring[(j - s + TL) % TL];
+                acc[j].x = fmaf(-h.y, w.y, fmaf(h.x, w.x, acc[j].x));
+                acc[j].y = fmaf(h.y, w.x, fmaf(h.x, w.y, acc[j].y));
+            }
+            ring[(2 * TL - 1 - s) % TL] = fresh;
+        }
+    };
+    int p = p_lo;
+    for (; p + TL - 1 <= p_hi; p += TL) pass(p, std::true_type());
+    if (p <= p_hi) pass(p, std::false_type());
+    float2* __restrict__ Yr = reinterpret_cast<float2*>(Y + (size_t)(q.yoff + b0) * CONV_LD) + f;
+#pragma unroll
+    for (int j = 0; j < TL; ++j)
+        if (j < nt) Yr[(size_t)j * (CONV_LD / 2)] = acc[j];
+}
+
+// Synthesis: istft_walk without window, envelope and overlap.  Block u of the row is the second half of irfft(Y[u]) and goes to
+// out[u 1024 - shift ...], clipped to [0, n): 8-byte stores where the block lies inside the row at an 8-byte boundary (an odd shift, or a
+// caller's row at an odd float, has none), single floats elsewhere.  A copied row (H = null) moves its pieces of 1024 samples instead.
+__global__ __launch_bounds__(256, FFT_OCC_ISTFT) void fir_synthesis_kernel(FftTables tb, const ConvRow* __restrict__ rows, int row0, const float* __restrict__ Y,
+                                                                           const float* __restrict__ in, int64_t in_stride, float* __restrict__ out,
+                                                                           int64_t out_stride, int ich)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    const int tid = threadIdx.x;
+    const int r = row0 + blockIdx.y;
+    const ConvRow q = rows[r];
+    const int b0 = blockIdx.x * ich;
+    const int b1 = (b0 + ich < q.nb) ? b0 + ich : q.nb;
+    if (b0 >= b1) return;                                             // (uniform over the workgroup, before any barrier)
+    float* o = out + (size_t)r * out_stride;
+    const int64_t n = q.n;
+    if (!q.H) {
+        const float* src = in + (size_t)r * in_stride;
+        for (int b = b0; b < b1; ++b)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = (int64_t)b * HOPS + tid + 256 * k;
+                if (i < n) o[i] = src[i];
+            }
+        return;
+    }
+    const Twiddles twd = load_twiddles<true>(tb.tw1024, tid);
+    const SplitCtx spl = load_split(tb, tid, true);
+    const float sc = 1.0f / 1024.0f;
+    const float* Yr = Y + (size_t)q.yoff * CONV_LD;
+    MergeRegs mr;
+    irfft_load<false>(Yr + (size_t)b0 * CONV_LD, spl, mr, tid);
+    for (int b = b0; b < b1; ++b) {
+        irfft_store<true>(mr, spl, z0, tid);
+        __syncthreads();
+        irfft_load<false>(Yr + (size_t)(b + 1 < b1 ? b + 1 : b) * CONV_LD, spl, mr, tid);      // (after the last block: a dummy reload)
+        const float2* z = fft1024<true>(z0, z1, twd, tid);
+        const int64_t m0 = (int64_t)(q.u0 + b) * HOPS - q.shift;
+        const bool pairs = m0 >= 0 && m0 + HOPS <= n && (reinterpret_cast<size_t>(o + m0) & 7) == 0;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 256 * k;
+            const float2 v = make_float2(z[c + 512].x * sc, z[c + 512].y * sc);
+            const int64_t m = m0 + 2 * c;
+            if (pairs) *reinterpret_cast<float2*>(o + m) = v;
+            else {
+                if (m >= 0 && m < n) o[m] = v.x;
+                if (m + 1 >= 0 && m + 1 < n) o[m + 1] = v.y;
+            }
+        }
+        __syncthreads();                          // z (= z1) is overwritten by the next block's first pass
+    }
+}
+
+static FftTables fir_tables(const FftTables& tb)
+{
+    FftTables t = tb;
+    t.colmap = nullptr;
+    t.ld = CONV_LD;
+    return t;
+}
+void launch_fir_taps(const FftTables& tb, const float* taps, int k, float* H, hipStream_t s)
+{
+    hipLaunchKernelGGL(fir_taps_kernel, dim3(conv_partitions(k)), dim3(256), 0, s, fir_tables(tb), taps, k, H);
+}
+void launch_fir_group(const FftTables& tb, const ConvRow* rows, int row0, int n_rows, int max_nx, int max_nb, const float* in, int64_t in_stride,
+                      float* out, int64_t out_stride, float* X, float* Y, hipStream_t s)
+{
+    const FftTables t = fir_tables(tb);
+    if (max_nx > 0) {
+        const Chunks ca = chunks_for<fir_analysis_kernel>(max_nx, n_rows, 0);
+        hipLaunchKernelGGL(fir_analysis_kernel, ca.grid, dim3(256), 0, s, t, rows, row0, in, in_stride, X, ca.len);
+        const dim3 grid((unsigned)((max_nb + CONV_TILE - 1) / CONV_TILE), 5, (unsigned)n_rows);      // 5 x 256 threads: the 1025 bins
+        hipLaunchKernelGGL(fir_mac_kernel<CONV_TILE>, grid, dim3(256), 0, s, rows, row0, X, Y);
+    }
+    const Chunks cs = chunks_for<fir_synthesis_kernel>(max_nb, n_rows, 0);
+    hipLaunchKernelGGL(fir_synthesis_kernel, cs.grid, dim3(256), 0, s, t, rows, row0, Y, in, in_stride, out, out_stride, cs.len);
+}
+
 }  // namespace bsrnn

@@ -8,6 +8,7 @@
 #include "resample_bank_host.h" // BankRow: what a resampler bank's kernel knows of a row, by value (HIP-free)
 #include "train_ragged_host.h"  // TrainClip: what the ragged training loss kernels know of a clip (HIP-free)
 #include "pool_host.h"          // PoolEntry: what the native session pool's copy kernels know of a row (HIP-free)
+#include "convolve_host.h"      // ConvRow: what the FIR convolution's kernels know of a row (HIP-free)
 
 namespace bsrnn {
 
@@ -320,6 +321,14 @@ void launch_stream_block_synthesis_hops(const FftTables& tb, const float* Y, con
                                         const RowHops& hops, hipStream_t s);
 // zeroes buf, prev and state of the rows in `rows` of one carry set, in one launch (bsrnn_stream_reset_rows)
 void launch_stream_reset_rows(float* buf, float* prev, float* state, int C, int K, const RowSet& rows, hipStream_t s);
+
+// Long FIR convolution of ragged rows (bsrnn_convolve_ragged; fft.hip, the plan: convolve_host.h).  launch_fir_taps: the image
+// H [P][CONV_LD] of one filter from its k taps on the device.  launch_fir_group: rows [row0, row0 + n_rows) of the table `rows` (on the
+// device) - analysis into X, multiply-accumulate into Y, synthesis into out; max_nx / max_nb the largest frame / block count among them
+// (copied rows: no frames, their pieces of 1024 samples as blocks).  in / out are the call's, rows in_stride / out_stride apart.
+void launch_fir_taps(const FftTables& tb, const float* taps, int k, float* H, hipStream_t s);
+void launch_fir_group(const FftTables& tb, const ConvRow* rows, int row0, int n_rows, int max_nx, int max_nb, const float* in, int64_t in_stride,
+                      float* out, int64_t out_stride, float* X, float* Y, hipStream_t s);
 
 // ------------------------------------------------------------------ validation metrics (metrics.hip)
 // Per-workgroup partial sums in double; the host adds them.  est [R][n_est]; speech, mix [R][n_in] (first n_est used).

@@ -12,7 +12,12 @@ and the same printed averages, to rounding.
 Data: <datapath>/{train,val}/<clip>/{mixture,speech}.wav - the folders the reference trains from (`samples(args.datapath, 'train')` /
 `'val'`, train.py:58,74; DnR layout of m_dataset.samples(), :8-19), as 16-bit / float WAV (the reference's .flac needs torchaudio, absent
 here); a `tr/` folder (DnR v2's name) is used when there is no `train/`; --train-folder / --val-folder override, or --synthetic N clips of seeded noise (no dataset ships with the reference).
-Not carried over: wandb logging, the discriminator, the RIR / re-mix augmentations, ReduceLROnPlateau (commented out in the
+--rir DIR applies the reference's room-impulse-response augmentation (MyDataSet(with_rir=True), m_dataset.py:92-114) on the device: the WAV
+files of DIR whose names contain `imp` are resampled from --rir_rate to 44.1 kHz (BSRNN.resample) and loaded into one
+speechseparation_amd.augment.FirBank at start; a training clip is reverberated with probability --rir_prob, by the reference's draws on
+the clip's index (augment.rir_draw) and with its chained channels (augment.reverb_pairs), all chosen clips of an optimizer step in one
+convolution call per stage.  Without --rir nothing changes.  The re-mix of MixDataSet is augment.remix (no loader here builds on it).
+Not carried over: wandb logging, the discriminator, ReduceLROnPlateau (commented out in the
 reference loop) and its batch-size growth heuristic.  Under `torchrun` (one process per GPU) the clips are split over the ranks
 and the gradients averaged before every optimizer step (data-parallel, RCCL).
 """
@@ -22,7 +27,7 @@ import random
 
 import torch
 
-from speechseparation_amd import audio, train as hip_train, weights
+from speechseparation_amd import audio, augment, train as hip_train, weights
 from speechseparation_amd.bsrnn import BSRNN
 
 
@@ -56,8 +61,26 @@ def load_pair(item, device):
 SYNTH_SAMPLES = 4 * 16000
 
 
-def main(argv=None):
-    global SYNTH_SAMPLES
+def load_rirs(model, folder, rate, device):
+    """(FirBank, first filter of every response, channels of every response) of the room impulse responses under `folder`: the WAV files
+    whose names contain `imp` (m_dataset.py:76; sorted - os.listdir's order is the file system's), every channel resampled from `rate` to
+    44.1 kHz on the device (the reference's Resample(16000, 44100), with this library's resampling kernel) as one filter."""
+    names = sorted(x for x in os.listdir(folder) if "imp" in x and x.lower().endswith(".wav"))
+    if not names:
+        raise SystemExit("--rir: no WAV file with `imp` in its name under %s" % folder)
+    filters, first, channels = [], [], []
+    for name in names:
+        w, _ = audio.load_wav(os.path.join(folder, name))
+        w = model.resample(w.to(device), rate, 44100).cpu()
+        if w.shape[1] > augment.MAX_TAPS:
+            raise SystemExit("--rir: %s has %d taps at 44.1 kHz, the limit is %d" % (name, w.shape[1], augment.MAX_TAPS))
+        first.append(len(filters))
+        channels.append(w.shape[0])
+        filters.extend(w[c].contiguous() for c in range(w.shape[0]))
+    return augment.FirBank(model, filters), first, channels
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description="Train a BSRNN model")
     ap.add_argument("--datapath", type=str, default=None, help="Path to the dataset")
     ap.add_argument("--mini", action="store_true", help="Use a small dataset")
@@ -76,6 +99,16 @@ def main(argv=None):
                     "padded batch with one backward pass (speechseparation_amd.train.train_step_many) instead of clip by clip")
     ap.add_argument("--device", type=str, default=None)
     ap.add_argument("--outdir", type=str, default=".")
+    ap.add_argument("--rir", type=str, default=None, metavar="DIR", help="folder of room impulse responses (WAV files with `imp` in their names): "
+                    "reverberate training clips on the device as the reference's MyDataSet(with_rir=True) does")
+    ap.add_argument("--rir_prob", type=float, default=0.1, metavar="P", help="chance of a training clip being reverberated (the reference's 0.1)")
+    ap.add_argument("--rir_rate", type=int, default=16000, metavar="HZ", help="sample rate the responses are taken to be at (the reference's 16000)")
+    return ap
+
+
+def main(argv=None):
+    global SYNTH_SAMPLES
+    ap = build_parser()
     args = ap.parse_args(argv)
     SYNTH_SAMPLES = int(args.seconds * 16000)
 
@@ -115,6 +148,15 @@ def main(argv=None):
     if args.resume and os.path.exists(os.path.join(args.outdir, "optimizer.pth")):
         optimizer.load_state_dict(torch.load(os.path.join(args.outdir, "optimizer.pth"), weights_only=True))
 
+    reverb = None
+    if args.rir:
+        bank, rir_first, rir_channels = load_rirs(model, args.rir, args.rir_rate, device)
+
+        def reverb(indices, mixes):
+            """the reference's draws for these training clips, applied to their mixtures in place: one convolution call per stage"""
+            draws = [augment.rir_draw(idx, len(rir_first), rir_channels.__getitem__, args.rir_prob) for idx in indices]
+            augment.reverb_pairs(bank, mixes, [d and (rir_first[d[0]] + d[1], rir_first[d[0]] + d[2]) for d in draws])
+
     best = 1.0e30
     for epoch in range(args.epochs):
         if rank == 0:
@@ -127,6 +169,8 @@ def main(argv=None):
             # the clips of one optimizer step in one backward pass; the tail of the epoch is a smaller step (train.py:122-123)
             for b0 in range(0, len(order), args.batch_size):
                 pairs = [load_pair(train_set[idx], device) for idx in order[b0:b0 + args.batch_size]]
+                if reverb:
+                    reverb(order[b0:b0 + args.batch_size], [mix for mix, _ in pairs])
                 for loss, sdr in hip_train.train_step_many(model, optimizer, pairs, group=dist.group.WORLD if world > 1 else None,
                                                            loss_sdr=args.loss_sdr):
                     batch_i += 1
@@ -135,6 +179,8 @@ def main(argv=None):
             order = []
         for idx in order:
             mix, speech = load_pair(train_set[idx], device)
+            if reverb:
+                reverb([idx], [mix])
             if use_graph and (tuple(mix.shape) in graphs or len(graphs) < 4):
                 if tuple(mix.shape) not in graphs:
                     graphs[tuple(mix.shape)] = hip_train.GraphedTrainStep(model, optimizer, mix.shape[0], mix.shape[1], loss_sdr=args.loss_sdr)
