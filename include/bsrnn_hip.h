@@ -752,6 +752,81 @@ int32_t bsrnn_fir_bank_taps(const bsrnn_fir_bank* bank, int32_t filter);
 int     bsrnn_convolve_ragged(bsrnn_fir_bank* bank, const float* in_dev, int64_t in_stride, const int64_t* lens_host,
                               const int32_t* filter_host, float* out_dev, int64_t out_stride, int32_t R, void* stream);
 
+/* ---- dialog / background section mining ---------------------------------------------------
+ * The reference's gendataset-separate.py runs the separator over a long recording, forms two figures for every hop of 1024
+ * samples (:100-105) and cuts the recording into dialog and background sections with a run-length state machine (:111-149);
+ * those files are what MixDataSet trains on.  bsrnn_hop_activity forms the figures on the device for a ragged batch,
+ * bsrnn_sections_scan is the state machine, a plain host function.
+ *
+ * bsrnn_hop_activity: row r has hops_host[r] hops (NULL: every row has Hmax).  Hop h of row r covers, for j = 0 ... 1023,
+ *     e[j] = est_dev[r * est_stride + h * 1024 + j],   w[j] = mix_dev[r * mix_stride + h * 1024 + j]
+ * and with, all rounded to fp32 exactly where the reference's tensors are, b = w - e, q = (e * e) / (b * b) (three roundings,
+ * IEEE division) and s = w * w, the sums of the 1024 q and of the 1024 s are formed in double and
+ *     act_dev[(r * Hmax + h) * 2 + BSRNN_ACT_RATIO] = sum q / 1024,     ... + BSRNN_ACT_LEVEL] = sum s / 1024
+ * are stored: raw means, not dB - thresholds stay on the host.  IEEE special values pass through: one sample with b == 0 and
+ * e != 0 makes the hop's ratio +inf, 0 / 0 makes it NaN (digital silence), an all-zero estimate gives exactly 0.  All of
+ * act_dev [R][Hmax][2] is written, the slots at and behind a row's hop count as (0, 0).  Nothing behind hops_host[r] * 1024
+ * samples of a row is read, in either buffer.  Rounding: a sum differs from the exactly ordered float64 sum of the same fp32
+ * terms by at most 1023 * 2^-53 relative; a row's values depend on the row alone, and rows whose bases and strides allow
+ * 16-byte loads give the same bits as rows that do not.
+ * The call is asynchronous on `stream`, needs no committed weights, and allocates nothing once a call of its size has been
+ * made (bsrnn_debug_counter(0)); hops_host is the caller's again at return.
+ * The estimate and the mixture are compared sample for sample as given.  A comparison against later or earlier input is the
+ * caller's pointer arithmetic, not a parameter: the reference's loop subtracts its streaming separator's output - which is
+ * late (the overlap-add of gendataset-separate.py:63-78 completes a chunk only after later ones have come in) - from the
+ * CURRENT input chunk (:99-101), an artefact of that delay.  This library's streams are one hop late (bsrnn_stream_step).
+ * With est_dev the L hops a stream returned for the L hops at `input`: est_dev + 1024, mix_dev = input and L - 1 hops
+ * compare aligned signals (output hop k + 1 is input hop k); est_dev and mix_dev = input as they are reproduce the
+ * reference's pairing of a late estimate with the current chunk.
+ * Refused with BSRNN_EARG before any device work - on a host-only context in front of its BSRNN_ESTATE: a null ctx, buffer
+ * or act_dev; R < 1 or Hmax < 1; a stride < Hmax * 1024; a hop count < 0 or > Hmax (the text names the row and the value);
+ * act_dev overlapping the floats the rows of either input span.
+ *
+ * The rule (bsrnn_section_rule; bsrnn_section_rule_default fills in the reference's constants: 10, 3, -30, -100, 1e-10,
+ * -200, 10), per hop:  db = 10 ln(ratio) and level = floor_db if level_mean < level_floor, else 10 ln(level_mean) - natural
+ * logs, as the reference writes them.  A ratio of exactly 0 gives db = -inf: the reference's math.log(0) raises there, the
+ * one deliberate deviation.  +inf and NaN pass through; a NaN db fails every comparison, so such a hop can only bridge
+ * (through its level) or reset.  Then, in this order:
+ *   1. db > dialog_db: if n_background > 0 it goes to 0 and the open section closes; ++n_dialog; if n_dialog >= min_run
+ *      and no section is open, a dialog section opens AT THIS HOP (the first min_run - 1 hops of a run are not part of it)
+ *   2. else, (db > bridge_db or level < silence_db) and n_dialog >= min_run: the hop belongs to the open section, the
+ *      counters do not move
+ *   3. else, db < background_db: the mirror image of 1 for background
+ *   4. else: both counters go to 0 and the open section closes.
+ * A closed section is {kind, first_hop, end_hop} with end_hop exclusive, in hops since the state's reset (samples: * 1024).
+ * bsrnn_sections_scan consumes n_hops pairs of act_host [n_hops][2] (one row of a downloaded act_dev), with flush != 0 then
+ * closes an open section behind the last hop, writes the first `cap` sections the call closed to `out` and their number to
+ * *n_out - which may exceed cap: the state advances over all hops whatever cap is, so a caller sizes with cap = 0 on a copy
+ * of its state and repeats.  Feeding a stream's hops in any split gives the sections of one call.  rule NULL: the defaults.
+ * BSRNN_EARG: a null state or n_out, a negative n_hops or cap, min_run < 1, act_host NULL with n_hops > 0, out NULL with
+ * cap > 0.  These three functions need no context and no GPU. */
+#define BSRNN_ACT_RATIO 0
+#define BSRNN_ACT_LEVEL 1
+#define BSRNN_SECTION_NONE       0
+#define BSRNN_SECTION_DIALOG     1
+#define BSRNN_SECTION_BACKGROUND 2
+typedef struct bsrnn_section_rule {
+    double  dialog_db, bridge_db, background_db, silence_db;
+    double  level_floor, floor_db;
+    int32_t min_run;
+} bsrnn_section_rule;
+typedef struct bsrnn_section_state {
+    int64_t n_dialog, n_background;
+    int32_t open_kind;               /* BSRNN_SECTION_* */
+    int64_t open_hop;                /* first hop of the open section */
+    int64_t hop;                     /* hops consumed so far */
+} bsrnn_section_state;
+typedef struct bsrnn_section {
+    int32_t kind;                    /* BSRNN_SECTION_DIALOG or _BACKGROUND */
+    int64_t first_hop, end_hop;
+} bsrnn_section;
+int  bsrnn_hop_activity(bsrnn_ctx* ctx, const float* mix_dev, int64_t mix_stride, const float* est_dev, int64_t est_stride,
+                        const int32_t* hops_host, int32_t R, int32_t Hmax, double* act_dev, void* stream);
+void bsrnn_section_rule_default(bsrnn_section_rule* rule);
+void bsrnn_section_state_reset(bsrnn_section_state* state);
+int  bsrnn_sections_scan(const bsrnn_section_rule* rule, bsrnn_section_state* state, const double* act_host, int64_t n_hops,
+                         int32_t flush, bsrnn_section* out, int64_t cap, int64_t* n_out);
+
 /* ---- measurement support ---------------------------------------------------------------
  * bsrnn_set_profiling(ctx, mask): bit i of `mask` brackets stage i of every compute call with
  * hipEvents on the call's stream (mask < 0 = all stages, 0 = off; each bracket costs ~10 us of

@@ -36,6 +36,7 @@ SYMBOLS = [
     "bsrnn_pool_get_pending", "bsrnn_pool_set_pending", "bsrnn_pool_feed", "bsrnn_pool_feed_host",
     "bsrnn_pool_create_rates", "bsrnn_pool_open_rate", "bsrnn_pool_rate_of", "bsrnn_pool_ready", "bsrnn_pool_drain_len", "bsrnn_pool_drain",
     "bsrnn_fir_bank_create", "bsrnn_fir_bank_destroy", "bsrnn_fir_bank_count", "bsrnn_fir_bank_taps", "bsrnn_convolve_ragged",
+    "bsrnn_hop_activity", "bsrnn_section_rule_default", "bsrnn_section_state_reset", "bsrnn_sections_scan",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
@@ -43,6 +44,23 @@ STREAM_HOPS_MAX = 255                       # BSRNN_STREAM_HOPS_MAX
 BANK_PAIRS_MAX = 16                         # BSRNN_BANK_PAIRS_MAX
 TRAIN_VALUE_NAMES = ("loss", "l1_time", "l1_re", "l1_im", "sdr")     # BSRNN_TV_* order
 METRIC_NAMES = ("loss", "sdr", "input_sdr", "sisdr", "l1_time", "l1_re", "l1_im", "separation_db")   # BSRNN_M_* order
+
+
+ACT_RATIO, ACT_LEVEL = 0, 1                 # BSRNN_ACT_*
+SECTION_NONE, SECTION_DIALOG, SECTION_BACKGROUND = 0, 1, 2          # BSRNN_SECTION_*
+
+
+class SectionRuleC(C.Structure):            # bsrnn_section_rule
+    _fields_ = [("dialog_db", C.c_double), ("bridge_db", C.c_double), ("background_db", C.c_double), ("silence_db", C.c_double),
+                ("level_floor", C.c_double), ("floor_db", C.c_double), ("min_run", C.c_int32)]
+
+
+class SectionStateC(C.Structure):           # bsrnn_section_state
+    _fields_ = [("n_dialog", C.c_int64), ("n_background", C.c_int64), ("open_kind", C.c_int32), ("open_hop", C.c_int64), ("hop", C.c_int64)]
+
+
+class SectionC(C.Structure):                # bsrnn_section
+    _fields_ = [("kind", C.c_int32), ("first_hop", C.c_int64), ("end_hop", C.c_int64)]
 
 
 class NativeError(RuntimeError):
@@ -156,6 +174,11 @@ def _load():
         "bsrnn_fir_bank_count": (i32, [vp]),
         "bsrnn_fir_bank_taps": (i32, [vp, i32]),
         "bsrnn_convolve_ragged": (C.c_int, [vp, vp, i64, C.POINTER(i64), C.POINTER(i32), vp, i64, i32, vp]),
+        "bsrnn_hop_activity": (C.c_int, [vp, vp, i64, vp, i64, C.POINTER(i32), i32, i32, vp, vp]),
+        "bsrnn_section_rule_default": (None, [C.POINTER(SectionRuleC)]),
+        "bsrnn_section_state_reset": (None, [C.POINTER(SectionStateC)]),
+        "bsrnn_sections_scan": (C.c_int, [C.POINTER(SectionRuleC), C.POINTER(SectionStateC), C.POINTER(C.c_double), i64, i32,
+                                          C.POINTER(SectionC), i64, C.POINTER(i64)]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),
         "bsrnn_stage_name": (C.c_char_p, [i32]),

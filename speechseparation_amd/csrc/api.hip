@@ -7,6 +7,7 @@
 #include "commit_host.h"
 #include "plan_host.h"
 #include "metrics_host.h"
+#include "sections_host.h"
 #include "resample_host.h"
 #include "pool_rates_host.h"
 
@@ -2424,6 +2425,90 @@ int bsrnn_evaluate_ragged(bsrnn_ctx* c, const float* mix, const float* speech, i
     // bsrnn_evaluate (finish_call: a structural fall-back, or the whole flow again on the exact-fp32 kernels from the same inputs and lengths)
     if ((rc = run())) return rc;
     return finish_call(c, s, run, true);
+}
+
+// --------------------------------------------------------------------------- dialog / background section mining
+// The per-hop figures of gendataset-separate.py:100-105 for a ragged batch (the kernel: metrics.hip) and the script's run-length state
+// machine over them (sections_host.h; plain host functions).  The hop counts travel in the ragged calls' block.
+static_assert(ACT_RATIO == BSRNN_ACT_RATIO && ACT_LEVEL == BSRNN_ACT_LEVEL && ACT_Q == 2, "sections_host.h and bsrnn_hip.h disagree");
+static_assert(SECTION_DIALOG == BSRNN_SECTION_DIALOG && SECTION_BACKGROUND == BSRNN_SECTION_BACKGROUND && SECTION_NONE == 0,
+              "sections_host.h and bsrnn_hip.h disagree");
+
+int bsrnn_hop_activity(bsrnn_ctx* c, const float* mix, int64_t mix_stride, const float* est, int64_t est_stride, const int32_t* hops_host,
+                       int32_t R, int32_t Hmax, double* act, void* stream)
+{
+    // arguments first, device or not (a host-only context answers them before BSRNN_ESTATE)
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!mix || !est || !act) return fail(BSRNN_EARG, "bsrnn_hop_activity: null argument (need mix_dev, est_dev and act_dev)");
+    if (R < 1 || Hmax < 1) return fail(BSRNN_EARG, "bsrnn_hop_activity: need R >= 1 rows and Hmax >= 1 hops, got R = %d, Hmax = %d", R, Hmax);
+    const int64_t row = (int64_t)Hmax * HOPS;
+    if (mix_stride < row)
+        return fail(BSRNN_EARG, "bsrnn_hop_activity: mix_stride %lld is less than Hmax * 1024 = %lld", (long long)mix_stride, (long long)row);
+    if (est_stride < row)
+        return fail(BSRNN_EARG, "bsrnn_hop_activity: est_stride %lld is less than Hmax * 1024 = %lld", (long long)est_stride, (long long)row);
+    for (int r = 0; hops_host && r < R; ++r)
+        if (hops_host[r] < 0 || hops_host[r] > Hmax)
+            return fail(BSRNN_EARG, "bsrnn_hop_activity: hops_host[%d] = %d is outside [0, %d]", r, hops_host[r], Hmax);
+    // the floats the rows span: behind the last row of a view lies somebody else's memory
+    const size_t act_bytes = (size_t)R * Hmax * 2 * sizeof(double);
+    if (ranges_overlap(act, act_bytes, mix, ((size_t)(R - 1) * mix_stride + (size_t)row) * sizeof(float)) ||
+        ranges_overlap(act, act_bytes, est, ((size_t)(R - 1) * est_stride + (size_t)row) * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_hop_activity: act_dev must not overlap the floats the rows of mix_dev or est_dev span");
+    if (int rc = check_device(c)) return rc;                          // (no model stage: needs no committed weights)
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const int32_t* d_hops = nullptr;
+    if (hops_host) {
+        const char* d = nullptr;
+        const size_t bytes = (size_t)R * sizeof(int32_t);
+        if (int rc = ragged_upload_block(c, bytes, s, [&](char* h) { memcpy(h, hops_host, bytes); }, &d)) return rc;
+        d_hops = reinterpret_cast<const int32_t*>(d);
+    }
+    launch_hop_activity(mix, mix_stride, est, est_stride, d_hops, R, Hmax, act, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+void bsrnn_section_rule_default(bsrnn_section_rule* rule)
+{
+    if (!rule) return;
+    const SectionRule q;
+    rule->dialog_db = q.dialog_db; rule->bridge_db = q.bridge_db; rule->background_db = q.background_db; rule->silence_db = q.silence_db;
+    rule->level_floor = q.level_floor; rule->floor_db = q.floor_db; rule->min_run = q.min_run;
+}
+
+void bsrnn_section_state_reset(bsrnn_section_state* state)
+{
+    if (!state) return;
+    state->n_dialog = state->n_background = 0;
+    state->open_kind = BSRNN_SECTION_NONE;
+    state->open_hop = state->hop = 0;
+}
+
+int bsrnn_sections_scan(const bsrnn_section_rule* rule, bsrnn_section_state* state, const double* act_host, int64_t n_hops, int32_t flush,
+                        bsrnn_section* out, int64_t cap, int64_t* n_out)
+{
+    SectionRule q;
+    if (rule) {
+        q.dialog_db = rule->dialog_db; q.bridge_db = rule->bridge_db; q.background_db = rule->background_db; q.silence_db = rule->silence_db;
+        q.level_floor = rule->level_floor; q.floor_db = rule->floor_db; q.min_run = rule->min_run;
+    }
+    switch (sections_check(q, state, act_host, n_hops, cap, n_out)) {
+    case SECTIONS_NULL_STATE: return fail(BSRNN_EARG, "bsrnn_sections_scan: null state");
+    case SECTIONS_NULL_COUNT: return fail(BSRNN_EARG, "bsrnn_sections_scan: null n_out");
+    case SECTIONS_NEGATIVE: return fail(BSRNN_EARG, "bsrnn_sections_scan: n_hops = %lld and cap = %lld must not be negative", (long long)n_hops, (long long)cap);
+    case SECTIONS_MIN_RUN: return fail(BSRNN_EARG, "bsrnn_sections_scan: min_run = %d, need at least 1", q.min_run);
+    case SECTIONS_NULL_ACT: return fail(BSRNN_EARG, "bsrnn_sections_scan: act_host is null with n_hops = %lld", (long long)n_hops);
+    case SECTIONS_OK: break;
+    }
+    if (!out && cap > 0) return fail(BSRNN_EARG, "bsrnn_sections_scan: out is null with cap = %lld", (long long)cap);
+    SectionState st;
+    st.n_dialog = state->n_dialog; st.n_background = state->n_background; st.open_kind = state->open_kind;
+    st.open_hop = state->open_hop; st.hop = state->hop;
+    *n_out = sections_scan(q, st, act_host, n_hops, flush != 0, out, cap);
+    state->n_dialog = st.n_dialog; state->n_background = st.n_background; state->open_kind = st.open_kind;
+    state->open_hop = st.open_hop; state->hop = st.hop;
+    return 0;
 }
 
 

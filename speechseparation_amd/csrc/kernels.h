@@ -353,6 +353,10 @@ void launch_metric_input_sdr_ragged(const float* speech, const float* mix, const
                                     double* part /* [n_clips][blocks] */, int blocks, hipStream_t s);
 void launch_metric_freq_ragged(const FftTables& tb, const float* Yf, const float* Sf, const int64_t* lens, int R, int Tmax,
                                double* part /* [R][blocks][2] */, int blocks, hipStream_t s);
+// Per-hop activity (bsrnn_hop_activity): for hop h < hops[r] of row r, act[r][h] = {mean(est^2 / (mix - est)^2), mean(mix^2)} over its 1024
+// samples, (0, 0) from hops[r] to Hmax; hops [R] on the device, null: every row has Hmax hops.  Rows mix_stride / est_stride floats apart.
+void launch_hop_activity(const float* mix, int64_t mix_stride, const float* est, int64_t est_stride, const int32_t* hops, int R, int Hmax,
+                         double* act /* [R][Hmax][2] */, hipStream_t s);
 // The tri-loss and the SDR of a ragged training step per clip, and their gradients (bsrnn_train_loss_ragged / _backward; the clip table:
 // train_ragged_host.h).  y, sfreq, dy [R][2050][Tmax] in the reference layout; xtime, dxtime [R][(Tmax-1)*1024]; speech rows wave_stride
 // floats apart; lens [R], clips [n_clips], row_clip [R], gclip [n_clips][2] on the device.  The forward leaves values [n_clips][TV_COUNT] and

@@ -413,7 +413,74 @@ __global__ __launch_bounds__(256) void train_loss_time_ragged_bwd_kernel(const f
     for (int64_t i = n_est + (int64_t)blockIdx.x * 256 + threadIdx.x; i < out_stride; i += (int64_t)gridDim.x * 256) o[i] = 0.f;
 }
 
+// ------------------------------------------------------------------------------ per-hop activity of a ragged batch (bsrnn_hop_activity)
+// The two figures the reference's gendataset-separate.py:100-105 forms for every chunk of 1024 samples - mean(est^2 / (mix - est)^2) and
+// mean(mix^2) - for hop h < hops[r] of every row r.  One WAVE per hop: 64 lanes x 16 samples of each signal, as four 16-byte loads per
+// signal whose lanes lie side by side (load k of lane l: samples k * 256 + 4 l ... + 3).  The fp32 terms are rounded exactly where the
+// reference's tensors are - the difference, the two squares, the IEEE division, the square of the mixture; no contraction - and added in
+// double: a lane's sixteen in index order, then wave-wide as block_reduce_store's first stage does, and lane 0 stores the two means.
+// No LDS and no barrier: a wave depends on nothing outside itself.  Every bound - the row, the hop, the row's hop count - is
+// wave-uniform.  Slots from hops[r] to Hmax get (0, 0) and nothing is read for them; nothing is read behind hops[r] * 1024 samples.
+// vec = 0: the same samples in the same order by scalar loads, so the two paths agree bit for bit.
+// grid (hop groups of ACT_WAVES, rows); hops null: every row has Hmax hops.  act [R][Hmax][2]
+constexpr int ACT_WAVES = 4;
+__global__ __launch_bounds__(64 * ACT_WAVES) void hop_activity_kernel(const float* __restrict__ mix, int64_t mix_stride,
+                                                                      const float* __restrict__ est, int64_t est_stride,
+                                                                      const int32_t* __restrict__ hops, int R, int Hmax, int vec,
+                                                                      double* __restrict__ act)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t h = (int64_t)blockIdx.x * ACT_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (h >= Hmax) return;
+    for (int r = blockIdx.y; r < R; r += gridDim.y) {
+        double* dst = act + ((size_t)r * Hmax + h) * 2;
+        const int Hr = hops ? hops[r] : Hmax;
+        if (h >= Hr) {
+            if (lane == 0) { dst[0] = 0.0; dst[1] = 0.0; }
+            continue;
+        }
+        const float* w = mix + (size_t)r * mix_stride + (size_t)h * HOPS + 4 * lane;
+        const float* e = est + (size_t)r * est_stride + (size_t)h * HOPS + 4 * lane;
+        v4f wv[4], ev[4];
+        if (vec) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { wv[k] = *reinterpret_cast<const v4f*>(w + 256 * k); ev[k] = *reinterpret_cast<const v4f*>(e + 256 * k); }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { wv[k][j] = w[256 * k + j]; ev[k][j] = e[256 * k + j]; }
+        }
+        double q[2] = {0, 0};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float ww = wv[k][j], ee = ev[k][j];
+                const float b = ww - ee;                   // the reference's `background` (:101)
+                const float num = ee * ee, den = b * b;
+                q[0] += (double)(num / den);               // (:103) x / 0 = inf, 0 / 0 = NaN: passed on
+                q[1] += (double)(ww * ww);                 // (:105)
+            }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) q[i] += __shfl_down(q[i], off, 64);
+        if (lane == 0) { dst[0] = q[0] / (double)HOPS; dst[1] = q[1] / (double)HOPS; }
+    }
+}
+
 }  // namespace
+
+void launch_hop_activity(const float* mix, int64_t mix_stride, const float* est, int64_t est_stride, const int32_t* hops, int R, int Hmax,
+                         double* act, hipStream_t s)
+{
+    // decided once per call: one row off alignment puts the whole call on scalar loads (a hop starts a multiple of 1024 floats into its row)
+    const int vec = (mix_stride % 4 == 0) && (est_stride % 4 == 0) && (((uintptr_t)mix | (uintptr_t)est) & 15) == 0;
+    hipLaunchKernelGGL(hop_activity_kernel, dim3((unsigned)(((int64_t)Hmax + ACT_WAVES - 1) / ACT_WAVES), R < 65535 ? R : 65535), dim3(64 * ACT_WAVES), 0, s, mix,
+                       mix_stride, est, est_stride, hops, R, Hmax, vec, act);
+}
 
 // Interleaved columns per workgroup of the two spectral loss kernels: about 4096 floats of a row per workgroup, at most 129 columns (16
 // workgroups per row) and never 2^31 floats
