@@ -2,39 +2,22 @@
 // state_dict key names, host-side folding/packing, workspace, and the launch sequence of
 // BSRNN.forward / forward_recurrent (bsrnn.py:385-510) and of the callers' STFT sandwich.
 // There is no CPU compute path here: every entry point either enqueues HIP kernels or fails.
-#include "../../include/bsrnn_hip.h"
-#include "kernels.h"
-#include "commit_host.h"
-#include "plan_host.h"
+// This unit: context, parameters and commit, call plan and dual path, the offline / ragged / long-form / evaluate / training entry points,
+// measurement, memory helpers - and what api_internal.h declares for the other host units (api_stream.hip, api_resample.hip, api_pool.hip).
+#include "api_internal.h"
 #include "metrics_host.h"
 #include "sections_host.h"
-#include "resample_host.h"
-#include "pool_rates_host.h"
 
-#include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <memory>
-#include <string>
-#include <vector>
 
-using namespace bsrnn;
+namespace bsrnn::host {
 
-// --------------------------------------------------------------------------- first-use accounting (bsrnn_debug_counter)
-// What the library has done that does not belong on a real-time thread: device / pinned allocations, stream captures, graph
-// instantiations.  Process-wide; tests read them around the LADSPA plugin's run() (tests/test_gpu_entrypoints.py).  The fifth counts work, not
-// first use: the frame rows (rows x frames) bsrnn_separate_long_ragged has handed to the model, which is what shows that rows retire.
-static std::atomic<long long> g_dbg[5];
-enum { DBG_ALLOC = 0, DBG_CAPTURE = 1, DBG_INSTANTIATE = 2, DBG_GRAPH_LAUNCH = 3, DBG_LONG_RAGGED_ROWS = 4 };
+std::atomic<long long> g_dbg[5];
 
-// --------------------------------------------------------------------------- error plumbing
 static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...)
+int fail(int code, const char* fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
@@ -42,232 +25,32 @@ static int fail(int code, const char* fmt, ...)
     va_end(ap);
     return code;
 }
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(BSRNN_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+
+// --------------------------------------------------------------------------- the upload ring (api_internal.h)
+hipError_t UploadRing::reserve(size_t bytes)
+{
+    if (bytes <= cap) return hipSuccess;
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return e;
+    if (d) { (void)hipFree(d); (void)hipHostFree(h); d = h = nullptr; cap = 0; }
+    g_dbg[DBG_ALLOC] += 2;
+    if ((e = hipHostMalloc((void**)&h, MIRRORS * bytes, hipHostMallocDefault)) != hipSuccess) { h = nullptr; return e; }
+    if ((e = hipMalloc((void**)&d, bytes)) != hipSuccess) { (void)hipHostFree(h); h = d = nullptr; return e; }
+    for (hipEvent_t& v : ev)
+        if (!v && (e = hipEventCreateWithFlags(&v, hipEventDisableTiming)) != hipSuccess) return e;
+    cap = bytes;
+    return hipSuccess;
+}
+void UploadRing::release()
+{
+    if (d) { (void)hipFree(d); (void)hipHostFree(h); d = h = nullptr; cap = 0; }      // (both or neither: reserve)
+    for (hipEvent_t& v : ev)
+        if (v) { (void)hipEventDestroy(v); v = nullptr; }
+}
 
 // --------------------------------------------------------------------------- context
-namespace {
-
-struct Param {
-    std::string key;
-    int64_t d0 = 0, d1 = 0;
-    int ndim = 1;
-    std::vector<float> data;
-    bool set = false;
-    int64_t numel() const { return ndim == 2 ? d0 * d1 : d0; }
-};
-
-enum Stage { ST_LAYOUT, ST_STFT, ST_BANDSPLIT, ST_BAND_LSTM, ST_BAND_FC, ST_TIME_LSTM, ST_TIME_FC, ST_MASK, ST_ISTFT, ST_STREAM_DSP, NSTAGE };
 const char* kStageNames[NSTAGE] = {"layout", "stft", "bandsplit_mlp", "band_lstm", "band_fc", "time_lstm", "time_fc",
                                    "mask_mlp", "istft", "stream_dsp"};
-
-struct EvRec { hipEvent_t a, b; int stage; };
-
-}  // namespace
-
-struct bsrnn_ctx {
-    int device = 0;                 // HIP ordinal; -1 = host-only context (parameter staging / file validation, no compute)
-    // Concurrency contract (include/bsrnn_hip.h): one call at a time per context.  `busy` turns an overlapping call from a
-    // second host thread into BSRNN_ESTATE; a call on a different HIP stream than the previous one first waits for that
-    // stream on the host (the context has ONE workspace); `gen` counts reallocations of anything a captured streaming
-    // graph may point at (workspace, tap buffer, weight arena) so that the graph is re-captured instead of replayed.
-    std::atomic<int> busy{0};
-    int range_policy = BSRNN_RANGE_EXACT;      // what a model entry point does about the fp16x2 range guard (bsrnn_set_range_policy)
-    unsigned gen = 1;
-    int live_streams = 0;           // bsrnn_stream objects that point at this context
-    bool zombie = false;            // bsrnn_destroy() was called while streams were alive: freed with the last stream
-    bool have_last = false;
-    std::vector<int> widths, off;   // bins per band, start bin
-    int K = 0;
-    std::vector<Param> params;
-    std::map<std::string, int> index;
-    bool committed = false;
-
-    // activation column layout
-    std::vector<int> aoff, poff;
-    int LDA = 0, LDP = 0;
-
-    // device-resident weights and tables
-    float* d_arena = nullptr;
-    GemmJob* d_jobs = nullptr;
-    int2* d_tiles = nullptr;
-    SlotTables slots;               // jobs and tiles of every layer slot inside d_jobs / d_tiles (commit_host.h)
-
-    // fused per-band MLP chains (mlp_chain.hip): device descriptor arrays, grouped by class (kernels.h, ChainLaunch)
-    bool stage_error = false;       // run_stage() found no task table for its row count (cannot happen: ensure_tasks runs first); reported by the entry point
-    bool fused = false;             // false: per-layer launches (BSRNN_MLP=layers, fp32 mode, or a band too wide for the LDS image)
-    ChainDesc* d_chain[2] = {nullptr, nullptr};
-    std::vector<ChainDesc> h_chain[2];          // host copies (geometry per band: the task tables are made from them)
-    struct TaskTable { int2* d[2]; int n[2]; };
-    std::map<int, TaskTable> chain_tasks;       // per row count M: device task tables of the two chains
-    size_t task_cap = 64, ovl_cap = 16;         // bounds of the two table caches (chain_tasks, ovl_tables); bsrnn_stream_reserve raises them to
-                                                // hold one table per block length it was asked for
-
-    // recurrent weights per dual-path block, segments of the arena (commit_host.h, BlockSegs; the *16 ones hold fp16x2 pieces in MFMA operand order)
-    const float *bandW[2][2], *bandB[2][2], *bandW16[2][2], *timeW[2], *timeB[2], *timeW16[2];
-    const float* timeFc16[2] = {nullptr, nullptr};  // the time blocks' fc as fp16x2 B fragments (fused into the time-axis launch, lstm.hip)
-    const float* timeFcB[2] = {nullptr, nullptr};
-    const float* bandFc16[2] = {nullptr, nullptr};  // the band blocks' fc (128 -> 64) likewise, for the few-sequence kernel (band_block_small_kernel)
-    const float* bandFcB[2] = {nullptr, nullptr};
-    int *h_range = nullptr, *d_range = nullptr;    // range guard of the fp16x2 kernels: host-mapped word the kernels set
-    float* d_tables = nullptr;
-    float* d_train_ws = nullptr;       // grow-only scratch of the training entry points (stream-ordered reuse: one call at a time)
-    size_t train_ws_floats = 0;
-    std::vector<float*> train_ws_retired;   // outgrown scratch buffers: a captured training graph (train.GraphedTrainStep) may still point at
-                                            // them, so they live until the context goes (growth is geometric: at most ~4x the final size in all)
-    std::vector<void*> retired;             // likewise the outgrown workspaces / tap buffers / progress words (bsrnn_stft, _istft, _istft_backward and
-                                            // every model entry point put workspace addresses into captured kernel nodes)
-    int* d_colmap = nullptr;
-    FftTables tb;
-
-    // workspace (grow-only)
-    size_t cap_rows = 0;
-    float* d_ws = nullptr;
-    float *Xf, *Yf, *A1, *A2, *P, *Z0, *Z1, *HB0, *HB1, *H1;
-    int* band_flags = nullptr;      // band_pair_h2_kernel's hand-over flags (2 per tile of 16 frame rows + slack per row block), zero at allocation
-    bool band_pair_off = false;     // a pair launch reported that its partner workgroups did not meet (value 4): one launch per layer from then on
-    size_t tap_rows = 0;
-    float* d_tap = nullptr;
-
-    // profiling
-    unsigned prof = 0;            // bitmask of stages bracketed by events
-    std::vector<EvRec> pool;
-    size_t pool_used = 0;
-    double acc_ms[NSTAGE];
-    int64_t acc_n[NSTAGE];
-    hipStream_t last_stream = nullptr;
-
-    // Overlapped dual path (run_overlapped below; kernels.h, OvlProducer / OvlConsumer): the second band block runs beside the first
-    // time-axis launch and the mask chain beside the second, on the context's first auxiliary stream.
-    bool overlap_env = true;        // BSRNN_OVERLAP=0: one launch after the other on the caller's stream (A/B; bit-identical results)
-    int overlap_sabotage = 0;       // BSRNN_OVERLAP=timeout (test hook): the producers publish nothing, the consumers give up after ~2 ms
-    bool overlap_off = false;       // a consumer's wait expired once (range flag value 5): this context runs launch after launch from then on
-    int* d_ovl = nullptr;           // [2 time blocks][OVL_HEAD ints: resident counter | progress word per time-axis workgroup]
-    int ovl_stride = 0;             // ints per block
-    struct OvlTable { int2* mask_tasks; int n_mask; int* band_order; int n_ord; };
-    std::map<std::pair<int, int>, OvlTable> ovl_tables;       // per (rows C, frames T): consumer dispatch orders by readiness
-    hipEvent_t ev_ovl_fork = nullptr, ev_ovl_join = nullptr;
-    int ovl_epoch = 0;              // overlapped calls so far on this context (upper bits of the progress words, kernels.h); reset every 2^18
-    int ovl_epoch_period = 1 << 18; // (test hook BSRNN_OVL_EPOCHS: a short period exercises the reset)
-    int ovl_resident_total[2] = {0, 0};      // time-axis workgroups the two resident counters have been promised so far (the gates' targets)
-    bool ovl_unjoined = false;      // the auxiliary stream may still be draining the last overlapped call (a host-side join follows where one is needed)
-    // How a consumer launch is held back until every workgroup of its producer is resident: a one-wave gate kernel that spins on the
-    // resident counter (default).  A resident foreign wave costs a band launch its pairing (its partners sit 8 ids apart and complete inside
-    // one round of 512 slots; with 511 the last eight pairs straddle two rounds: +18 us), so the gates are kept off the band launches'
-    // dispatch by events (fork in front of gate 0, a mid event between band 1 and gate 1).  (A stream wait on signal memory instead of the
-    // gate kernel was measured and rejected, profiles/r04_gate_kernel_vs_cp.txt: on this runtime hipStreamWaitValue32 is a blit kernel that
-    // spins so hard that the time-axis launch beside it takes 3x as long.)
-    hipEvent_t ev_ovl_mid = nullptr;
-
-    // concurrent row blocks of one call (bsrnn_separate): two row blocks on two streams once the batch's time-axis launch no longer fits one
-    // round of workgroups (bsrnn_separate: from 171 rows on at K = 12; until round 4, with four sequences per workgroup only, from 128 rows on),
-    // the second one stage behind the first: one block's matrix work fills the other's latency-bound time-axis LSTM (192 of 256
-    // CUs, serial chain) and the ramps / tails of the fused chain launches (+8-12 % at 128 rows).  At the benchmark's 64 rows
-    // two blocks of 32 gain 3 % (1.157 -> 1.119 ms per step) but every kernel then runs beside another
-    // block's kernels: the per-kernel durations (and with them the roofline figure of bench.py) stop describing the kernel,
-    // so one block there.  Rows are independent; tests/test_gpu_edges.py checks 64- and 130-row calls bit for bit against
-    // their row blocks.  (That check first failed: see the note at the top of fft.hip.)
-    hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
-
-    // Long-form separation (bsrnn_separate_long / _long_host): what one segment of a clip hands to the next - the time-axis LSTM state and
-    // the synthesis carry (the windowed second half of the segment's last frame) - exists twice, like a bsrnn_stream's carry: segment i
-    // reads set i & 1 and writes the other one, so a segment that leaves the fp16 range is run again from its untouched starting point.
-    // The host-buffer entry point stages through two pinned input windows and two pinned output blocks with device mirrors of the same
-    // sizes, copied on a stream of their own.  All of it is sized by (rows, frames per segment), never by the clip.
-    struct LongForm {
-        int rows = 0;                                         // rows the carry sets were made for (grow-only)
-        float *state[2] = {nullptr, nullptr}, *carry[2] = {nullptr, nullptr};      // one allocation, state[0] its base
-        size_t in_floats = 0, out_floats = 0;                 // floats per input window / output block of the staging (grow-only)
-        float *h_base = nullptr, *d_base = nullptr;           // the pinned and the device allocation: [in 0 | in 1 | out 0 | out 1]
-        float *h_in[2], *h_out[2], *d_in[2], *d_out[2];
-        hipStream_t copy = nullptr;
-        // per block: its H2D has completed / the segment that read d_in and wrote d_out is final / its D2H has completed
-        hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_d2h[2] = {nullptr, nullptr};
-    } lf;
-
-    // Ragged batches (bsrnn_separate_ragged): what the kernels of one call read besides the waveform - the rows' lengths and, for the fused
-    // chains, the task tables of its R * Tmax frame rows - travels as ONE block [R int64 lengths | split tasks | mask tasks], copied on the
-    // caller's stream into `d` in front of the call's kernels.  (Not the table cache above: a ragged caller meets another Tmax with nearly
-    // every call, and a cached table per frame-row count would make first-use work the rule and flush the bounded cache.)  The copy reads a
-    // pinned mirror; there are RG_SLOTS of them, used in turn, and mirror k is written again only when the copy that read it has completed
-    // (ev[k]), so the caller's array is free when the call returns and calls still queue up behind each other.  Grow-only.
-    // (Eight mirrors: the six ragged calls of one training step - two analyses, the synthesis, the loss and the two backward calls - queue up
-    // without the host waiting for a copy of the same step.)
-    static constexpr int RG_SLOTS = 8;
-    struct Ragged {
-        size_t cap = 0;                               // bytes of the device block and of each mirror
-        char *d = nullptr, *h = nullptr;              // h: RG_SLOTS mirrors of cap bytes
-        unsigned calls = 0;
-        hipEvent_t ev[RG_SLOTS] = {};
-    } rg;
-
-    // Ragged evaluate (bsrnn_evaluate_ragged): the metric kernels' table [R int64 row lengths | n_clips MetricClip] travels like the block
-    // above - pinned mirrors used in turn, a mirror rewritten only after the copy that read it has completed - and their scratch is one
-    // device block [partial sums, doubles | the estimate when the caller wants none] with a pinned mirror of the partials for the one
-    // download of a call.  All grow-only: a call that fits allocates nothing.
-    struct EvalRagged {
-        size_t cap = 0;                               // bytes of the table on the device and of each mirror
-        char *d = nullptr, *h = nullptr;
-        unsigned calls = 0;
-        hipEvent_t ev[RG_SLOTS] = {};
-        size_t part_cap = 0, est_cap = 0;             // doubles / floats the scratch holds
-        double *d_part = nullptr, *h_part = nullptr;
-        float* d_est = nullptr;
-    } er;
-
-    // Sample-rate conversion (bsrnn_resample, bsrnn_resampler_*): the polyphase table of each reduced (up, down) this context has met, designed
-    // on the host and uploaded at first use (bsrnn_debug_counter(0)); grow-only, a handful of entries of at most 100 KB, freed with the context.
-    struct ResampleTable { ResampleRatio q; ResampleTiling g; float* d; };
-    std::vector<ResampleTable> rs_tables;
-
-    // Long FIR convolution (bsrnn_convolve_ragged): the two spectrum buffers of a row group, `frames` spectra of CONV_LD floats each.
-    // Grow-only; the row table of a call travels in the ragged calls' block above (rg).
-    struct Conv {
-        float *X = nullptr, *Y = nullptr;
-        int64_t frames = 0;
-    } cv;
-};
-
-struct bsrnn_stream {
-    bsrnn_ctx* ctx;
-    int C;
-    // What a step carries to the next one - the sliding analysis buffer, the previous synthesis frame and the LSTM state - exists
-    // twice: step k reads set k & 1 and writes the other one, so a step whose operands leave the fp16 range can be run again,
-    // exactly, from its untouched starting point (range policy, finish_call), without a copy per step.
-    float *base = nullptr;             // the one allocation
-    float *buf[2], *prev[2], *state[2];
-    int cur = 0;                       // the set the NEXT step reads
-    float *X, *Y, *chunk, *out;
-    int* row_frames = nullptr;         // [C]: the hops of every row of a bsrnn_stream_process_hops call (its analysis launch writes them, its time-axis launches read them)
-    float *h_in = nullptr, *h_out = nullptr;   // pinned staging for the host-buffer entry point
-    // One step = analysis, ~18 launches of the model, synthesis.  The model part works on fixed buffers (X -> Y, state set p -> set
-    // 1 - p), so it is captured once per parity into a hipGraph and replayed (launch-bound inner loop); the two DSP kernels are
-    // launched around it with the caller's own chunk / output pointers and the wet/dry control as a kernel argument (no staging copies).
-    hipGraphExec_t exec[2] = {nullptr, nullptr};
-    hipGraph_t graph[2] = {nullptr, nullptr};
-    hipStream_t cap = nullptr;
-    bool use_graph = true;
-    unsigned gen = 0;                  // context generation the graphs were captured against
-};
-
-namespace {
-
-struct StageScope {   // brackets one stage of a call with events when profiling is on
-    bsrnn_ctx* c; hipStream_t s; EvRec* r = nullptr;
-    StageScope(bsrnn_ctx* c_, int stage, hipStream_t s_) : c(c_), s(s_)
-    {
-        if (((c->prof >> stage) & 1u) && c->pool_used < c->pool.size()) {
-            r = &c->pool[c->pool_used++];
-            r->stage = stage;
-            (void)hipEventRecord(r->a, s);
-        }
-    }
-    ~StageScope() { if (r) (void)hipEventRecord(r->b, s); }
-};
 
 int add_param(bsrnn_ctx* c, const std::string& key, int64_t d0, int64_t d1, int ndim)
 {
@@ -469,7 +252,7 @@ static const PlanKnobs& plan_knobs()
     }();
     return knobs;
 }
-static Flow plan_call(const bsrnn_ctx* c, int C, int T, bool gemv, bool overlap)
+Flow plan_call(const bsrnn_ctx* c, int C, int T, bool gemv, bool overlap)
 {
     return plan_call(c->K, C, T, gemv, overlap, plan_knobs(), PlanState{force_f32(), c->fused, c->band_pair_off, c->overlap_env, c->overlap_off});
 }
@@ -728,7 +511,7 @@ void run_overlapped(bsrnn_ctx* c, Part p, const bsrnn_ctx::OvlTable* tb, int fir
     for (int st = MS_MASK + 1; st <= last; ++st) run_stage(c, p, st);
 }
 // host-side join of the auxiliary stream with the last overlapped call (see run_overlapped)
-static int ovl_join_host(bsrnn_ctx* c)
+int ovl_join_host(bsrnn_ctx* c)
 {
     if (c->ovl_unjoined && c->aux[0]) HIP_TRY(hipStreamSynchronize(c->aux[0]));
     c->ovl_unjoined = false;
@@ -746,7 +529,7 @@ static const bsrnn_ctx::OvlTable* ovl_table(const bsrnn_ctx* c, const Flow& f, i
 
 // The model proper for a single part on one stream.
 int run_model(bsrnn_ctx* c, const float* Xf, float* Yf, float* tap, int C, int T,
-              const float* state_in, float* state_out, hipStream_t s, const int* row_frames = nullptr)
+              const float* state_in, float* state_out, hipStream_t s, const int* row_frames)
 {
     Part p = make_part(c, 0, C, T, s);
     p.row_frames = row_frames;
@@ -765,7 +548,7 @@ int run_model(bsrnn_ctx* c, const float* Xf, float* Yf, float* tap, int C, int T
 }
 
 // The guard word the fp16x2 kernels set, read and cleared (the host-mapped word: the caller has waited for the kernels it means).
-static int take_guard(bsrnn_ctx* c)
+int take_guard(bsrnn_ctx* c)
 {
     if (!c->h_range) return 0;
     const int v = *(volatile int*)c->h_range;
@@ -777,7 +560,7 @@ static int take_guard(bsrnn_ctx* c)
 // of the overlapped dual path gave up waiting for the time-axis launch beside it.  4 and 5 switch the context for good to the flow
 // without that assumption (same arithmetic: one launch per layer / launch after launch; ++gen re-captures streaming graphs, which contain
 // the old flow).  Returns BSRNN_EHIP with the message for 3, 4 and 5 - `who` names the call whose results are invalid -, else 0.
-static int guard_fallback(bsrnn_ctx* c, int v, const char* who)
+int guard_fallback(bsrnn_ctx* c, int v, const char* who)
 {
     if (v == 3) return fail(BSRNN_EHIP, "%s: a time-axis LSTM launch gave up waiting on its own workgroup-local counters (internal error)", who);
     if (v != 4 && v != 5) return 0;
@@ -796,43 +579,9 @@ int check_range(bsrnn_ctx* c)
     return fail(BSRNN_ERANGE, "an earlier call (range policy 'deferred') fed the fp16x2 matrix path an activation beyond +-65504; its "
                               "results are invalid - repeat it under the default policy, rescale the input or set BSRNN_GEMM=f32 BSRNN_LSTM=f32");
 }
-// True when the byte ranges [a, a + na) and [b, b + nb) share a byte (null pointers share none).  A call whose re-run (finish_call)
-// reads an input that the first run's outputs may have overwritten is refused on this test, not just on pointer equality.
-static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-// End of a model entry point under the default range policy (include/bsrnn_hip.h; any_policy: whatever the context's policy): wait for
-// the call's own kernels, look at the guard word the fp16x2 kernels set, and if it is set run the call again before returning - never
-// wrong numbers with rc 0.  Structural fall-backs first (guard_fallback: the context switches flow; at most two such re-runs, one per
-// kind), then for an operand that left the fp16 range the library's exact-fp32 kernels (fp32 weights are always resident; no range limit).
-template <class F>
-int finish_call(bsrnn_ctx* c, hipStream_t s, F&& rerun, bool any_policy = false)
-{
-    if ((c->range_policy != BSRNN_RANGE_EXACT && !any_policy) || !c->h_range || force_f32()) return 0;
-    if (gemm_mode() == GEMM_F32 && lstm_mode() == LSTM_F32) return 0;
-    for (int reruns = 0;; ++reruns) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (int rcj = ovl_join_host(c)) return rcj;      // (the second time-axis launch of an overlapped call ran on the auxiliary stream: its guard word too)
-        const int v = take_guard(c);
-        if (!v) return 0;
-        if (v != 3 && v != 4 && v != 5) break;
-        const int rc = guard_fallback(c, v, "the call");
-        if (v == 3 || reruns == 2) return rc;
-        if (int rc2 = rerun()) return rc2;
-    }
-    set_force_f32(true);
-    const int rc = rerun();
-    set_force_f32(false);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    return 0;
-}
 // The opening of every compute entry point: a context that can compute, on its device.  model: the entry points that run the committed
 // model say which of the two it is, need the weights, and report a range violation that an earlier call left behind.
-int check_device(bsrnn_ctx* c, bool model = false)
+int check_device(bsrnn_ctx* c, bool model)
 {
     if (!c) return fail(BSRNN_EARG, "null context");
     if (c->device < 0 || c->zombie)
@@ -844,21 +593,16 @@ int check_device(bsrnn_ctx* c, bool model = false)
 }
 int check_ready(bsrnn_ctx* c) { return check_device(c, true); }
 
-// One call at a time per context: an overlapping call from another host thread is refused instead of racing on the
-// workspace.  (Re-entrant on the same thread: bsrnn_evaluate -> bsrnn_separate, stream_step_host -> stream_step.)
-thread_local bsrnn_ctx* tl_owner = nullptr;
-struct CallGuard {
-    bsrnn_ctx* c; bool ok, outer;
-    explicit CallGuard(bsrnn_ctx* c_) : c(c_), ok(true), outer(false)
-    {
-        if (!c || tl_owner == c) return;
-        int expect = 0;
-        ok = c->busy.compare_exchange_strong(expect, 1);
-        if (ok) { outer = true; tl_owner = c; }
-    }
-    ~CallGuard() { if (outer) { tl_owner = nullptr; c->busy.store(0); } }
-    int refuse() const { return fail(BSRNN_ESTATE, "context is in use by a call from another host thread (one call at a time per context)"); }
-};
+static thread_local bsrnn_ctx* tl_owner = nullptr;
+CallGuard::CallGuard(bsrnn_ctx* c_) : c(c_), ok(true), outer(false)
+{
+    if (!c || tl_owner == c) return;
+    int expect = 0;
+    ok = c->busy.compare_exchange_strong(expect, 1);
+    if (ok) { outer = true; tl_owner = c; }
+}
+CallGuard::~CallGuard() { if (outer) { tl_owner = nullptr; c->busy.store(0); } }
+int CallGuard::refuse() const { return fail(BSRNN_ESTATE, "context is in use by a call from another host thread (one call at a time per context)"); }
 // The context has one workspace: work enqueued by the previous call on ANOTHER stream must have finished before this
 // call's kernels may touch it.  Same stream (the normal case): stream order does it, nothing to do here.
 int order_after_last(bsrnn_ctx* c, hipStream_t s)
@@ -867,12 +611,55 @@ int order_after_last(bsrnn_ctx* c, hipStream_t s)
     c->last_stream = s; c->have_last = true;
     return 0;
 }
-#define ENTER_CALL(c, s)                                   \
-    CallGuard guard_(c);                                   \
-    if (!guard_.ok) return guard_.refuse();                \
-    { int rc_ = order_after_last(c, s); if (rc_) return rc_; }
 
-}  // namespace
+void destroy_now(bsrnn_ctx* c)
+{
+    if (c->device < 0) { delete c; return; }
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    for (auto& r : c->pool) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+    for (int j = 0; j < MAX_PARTS; ++j) {
+        if (c->aux[j]) (void)hipStreamDestroy(c->aux[j]);
+        if (c->ev_join[j]) (void)hipEventDestroy(c->ev_join[j]);
+    }
+    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+    if (c->lf.copy) (void)hipStreamDestroy(c->lf.copy);
+    for (int k = 0; k < 2; ++k)
+        for (hipEvent_t e : {c->lf.ev_h2d[k], c->lf.ev_comp[k], c->lf.ev_d2h[k]})
+            if (e) (void)hipEventDestroy(e);
+    if (c->lf.state[0]) (void)hipFree(c->lf.state[0]);
+    if (c->lf.d_base) (void)hipFree(c->lf.d_base);
+    if (c->lf.h_base) (void)hipHostFree(c->lf.h_base);
+    c->rg.release();
+    c->er.table.release();
+    if (c->er.d_part) (void)hipFree(c->er.d_part);
+    if (c->er.h_part) (void)hipHostFree(c->er.h_part);
+    if (c->er.d_est) (void)hipFree(c->er.d_est);
+    for (auto& t : c->rs_tables) (void)hipFree(t.d);
+    if (c->cv.X) (void)hipFree(c->cv.X);
+    if (c->cv.Y) (void)hipFree(c->cv.Y);
+    if (c->ev_ovl_fork) (void)hipEventDestroy(c->ev_ovl_fork);
+    if (c->ev_ovl_join) (void)hipEventDestroy(c->ev_ovl_join);
+    free_ovl_tables(c);
+    if (c->d_ovl) (void)hipFree(c->d_ovl);
+    if (c->ev_ovl_mid) (void)hipEventDestroy(c->ev_ovl_mid);
+    if (c->d_ws) (void)hipFree(c->d_ws);
+    if (c->d_tap) (void)hipFree(c->d_tap);
+    if (c->d_arena) (void)hipFree(c->d_arena);
+    if (c->d_jobs) (void)hipFree(c->d_jobs);
+    if (c->d_tiles) (void)hipFree(c->d_tiles);
+    for (int ch = 0; ch < 2; ++ch)
+        if (c->d_chain[ch]) (void)hipFree(c->d_chain[ch]);
+    free_chain_tasks(c);
+    if (c->d_tables) (void)hipFree(c->d_tables);
+    if (c->d_train_ws) (void)hipFree(c->d_train_ws);
+    for (float* p : c->train_ws_retired) (void)hipFree(p);
+    for (void* p : c->retired) (void)hipFree(p);
+    if (c->d_colmap) (void)hipFree(c->d_colmap);
+    if (c->h_range) (void)hipHostFree(c->h_range);
+    delete c;
+}
+}  // namespace bsrnn::host
 
 // =========================================================================== ABI
 extern "C" {
@@ -964,60 +751,6 @@ int bsrnn_create(int device, const int32_t* widths, int32_t n_bands, bsrnn_ctx**
     }
     *out = c;
     return 0;
-}
-
-static void destroy_now(bsrnn_ctx* c)
-{
-    if (c->device < 0) { delete c; return; }
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    for (auto& r : c->pool) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    for (int j = 0; j < MAX_PARTS; ++j) {
-        if (c->aux[j]) (void)hipStreamDestroy(c->aux[j]);
-        if (c->ev_join[j]) (void)hipEventDestroy(c->ev_join[j]);
-    }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->lf.copy) (void)hipStreamDestroy(c->lf.copy);
-    for (int k = 0; k < 2; ++k)
-        for (hipEvent_t e : {c->lf.ev_h2d[k], c->lf.ev_comp[k], c->lf.ev_d2h[k]})
-            if (e) (void)hipEventDestroy(e);
-    if (c->lf.state[0]) (void)hipFree(c->lf.state[0]);
-    if (c->lf.d_base) (void)hipFree(c->lf.d_base);
-    if (c->lf.h_base) (void)hipHostFree(c->lf.h_base);
-    if (c->rg.d) (void)hipFree(c->rg.d);
-    if (c->rg.h) (void)hipHostFree(c->rg.h);
-    for (hipEvent_t e : c->rg.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->er.d) (void)hipFree(c->er.d);
-    if (c->er.h) (void)hipHostFree(c->er.h);
-    if (c->er.d_part) (void)hipFree(c->er.d_part);
-    if (c->er.h_part) (void)hipHostFree(c->er.h_part);
-    if (c->er.d_est) (void)hipFree(c->er.d_est);
-    for (auto& t : c->rs_tables) (void)hipFree(t.d);
-    if (c->cv.X) (void)hipFree(c->cv.X);
-    if (c->cv.Y) (void)hipFree(c->cv.Y);
-    for (hipEvent_t e : c->er.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->ev_ovl_fork) (void)hipEventDestroy(c->ev_ovl_fork);
-    if (c->ev_ovl_join) (void)hipEventDestroy(c->ev_ovl_join);
-    free_ovl_tables(c);
-    if (c->d_ovl) (void)hipFree(c->d_ovl);
-    if (c->ev_ovl_mid) (void)hipEventDestroy(c->ev_ovl_mid);
-    if (c->d_ws) (void)hipFree(c->d_ws);
-    if (c->d_tap) (void)hipFree(c->d_tap);
-    if (c->d_arena) (void)hipFree(c->d_arena);
-    if (c->d_jobs) (void)hipFree(c->d_jobs);
-    if (c->d_tiles) (void)hipFree(c->d_tiles);
-    for (int ch = 0; ch < 2; ++ch)
-        if (c->d_chain[ch]) (void)hipFree(c->d_chain[ch]);
-    free_chain_tasks(c);
-    if (c->d_tables) (void)hipFree(c->d_tables);
-    if (c->d_train_ws) (void)hipFree(c->d_train_ws);
-    for (float* p : c->train_ws_retired) (void)hipFree(p);
-    for (void* p : c->retired) (void)hipFree(p);
-    if (c->d_colmap) (void)hipFree(c->d_colmap);
-    if (c->h_range) (void)hipHostFree(c->h_range);
-    delete c;
 }
 
 void bsrnn_destroy(bsrnn_ctx* c)
@@ -1650,35 +1383,26 @@ int bsrnn_separate(bsrnn_ctx* c, const float* wave, float* wave_out, int32_t R, 
 // DSP ends told the rows' lengths (fft.hip: the padded frames go in as zero rows, the padded hops come out as zeros); every stage between
 // them runs as for a rectangular call, the overlapped dual path included.
 
-// The transport of the context's block (bsrnn_ctx::Ragged): `bytes` of it, written into the next pinned mirror by fill(mirror) and copied to
-// the device on stream s in front of the call's kernels.  Returns where the block is on the device.
-extern "C++" {
-template <class FILL>
-static int ragged_upload_block(bsrnn_ctx* c, size_t bytes, hipStream_t s, FILL fill, const char** d_block)
+// What every ragged entry point refuses about its rows' lengths (q = ragged_shape(lens, R, stride)) and its clips (q = clip_shape(...)),
+// under the caller's name.  seg_frames: the long form counts the frame rows of one segment.
+static int ragged_shape_refuse(const char* who, const RaggedShape& q, int R, int64_t stride, int seg_frames = 0)
 {
-    bsrnn_ctx::Ragged& rg = c->rg;
-    if (bytes > rg.cap) {
-        HIP_TRY(hipDeviceSynchronize());                              // queued copies read the old mirrors, queued kernels the old block
-        if (rg.d) { (void)hipFree(rg.d); (void)hipHostFree(rg.h); rg.d = rg.h = nullptr; rg.cap = 0; }
-        const size_t cap = (bytes + bytes / 2 + 255) & ~size_t(255);
-        g_dbg[DBG_ALLOC] += 2;
-        HIP_TRY(hipHostMalloc((void**)&rg.h, bsrnn_ctx::RG_SLOTS * cap, hipHostMallocDefault));
-        const hipError_t e = hipMalloc((void**)&rg.d, cap);
-        if (e != hipSuccess) { (void)hipHostFree(rg.h); rg.h = rg.d = nullptr; return fail(BSRNN_EHIP, "hipMalloc: %s", hipGetErrorString(e)); }
-        for (hipEvent_t& ev : rg.ev)
-            if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        rg.cap = cap;
-    }
-    const int k = (int)(rg.calls++ % bsrnn_ctx::RG_SLOTS);
-    HIP_TRY(hipEventSynchronize(rg.ev[k]));                           // (the copy of RG_SLOTS calls ago; an event never recorded counts as complete)
-    char* h = rg.h + (size_t)k * rg.cap;
-    fill(h);
-    HIP_TRY(hipMemcpyAsync(rg.d, h, bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(rg.ev[k], s));
-    *d_block = rg.d;
+    if (q.why == RAGGED_SHORT) return fail(BSRNN_EARG, "%s: row %d has %lld samples, need more than 1024 (reflect padding)", who, q.bad_row, (long long)q.bad_len);
+    if (q.why == RAGGED_LONG) return fail(BSRNN_EARG, "%s: row %d has %lld samples, more than the row stride of %lld", who, q.bad_row, (long long)q.bad_len, (long long)stride);
+    const int64_t frames = seg_frames ? std::min<int64_t>(seg_frames, q.Tmax) : q.Tmax;
+    if (ragged_too_many(R, frames))
+        return fail(BSRNN_EARG, "%s: %d rows x %lld frames is too many frame rows for one %s", who, R, (long long)frames, seg_frames ? "segment" : "call");
     return 0;
 }
-}  // extern "C++"
+static int clip_shape_refuse(const char* who, const ClipShape& q, int64_t stride)
+{
+    if (q.why == CLIPS_ROWS) return fail(BSRNN_EARG, "%s: clip %d has %lld rows, need at least 1", who, q.bad_clip, (long long)q.bad_value);
+    if (q.why == CLIPS_SHORT) return fail(BSRNN_EARG, "%s: clip %d has %lld samples, need more than 1024 (reflect padding)", who, q.bad_clip, (long long)q.bad_value);
+    if (q.why == CLIPS_LONG) return fail(BSRNN_EARG, "%s: clip %d has %lld samples, more than the row stride of %lld", who, q.bad_clip, (long long)q.bad_value, (long long)stride);
+    if (q.why == CLIPS_MANY) return fail(BSRNN_EARG, "%s: %lld rows x %lld frames is too many frame rows for one call", who, (long long)q.R, (long long)q.Tmax);
+    return 0;
+}
+
 // This call's block for R rows of M = R * Tmax frame rows, copied in on stream s; where its parts are on the device.
 static int ragged_upload(bsrnn_ctx* c, const int64_t* lens, int R, int M, hipStream_t s, Part& p)
 {
@@ -1690,15 +1414,15 @@ static int ragged_upload(bsrnn_ctx* c, const int64_t* lens, int R, int M, hipStr
         off[ch] = bytes;
         bytes += (tk[ch].size() + 1) * sizeof(int2);                  // (one entry of slack, as upload_table's)
     }
-    const char* d = nullptr;
-    const int rc = ragged_upload_block(c, bytes, s, [&](char* h) {
+    const int rc = c->rg.upload(bytes, s, [&](char* h) {
         memcpy(h, lens, b_lens);
         for (int ch = 0; ch < 2; ++ch) {
             memcpy(h + off[ch], tk[ch].data(), tk[ch].size() * sizeof(int2));
             memset(h + off[ch] + tk[ch].size() * sizeof(int2), 0, sizeof(int2));
         }
-    }, &d);
+    });
     if (rc) return rc;
+    const char* d = c->rg.d;
     p.lens = reinterpret_cast<const int64_t*>(d);
     for (int ch = 0; ch < 2; ++ch) {
         p.tasks[ch] = c->fused ? reinterpret_cast<const int2*>(d + off[ch]) : nullptr;
@@ -1709,10 +1433,9 @@ static int ragged_upload(bsrnn_ctx* c, const int64_t* lens, int R, int M, hipStr
 // The lengths alone, for the calls that run no model stage (the ragged DSP and loss calls of a training step need no chain task tables)
 static int ragged_upload_lens(bsrnn_ctx* c, const int64_t* lens, int R, hipStream_t s, const int64_t** d_lens)
 {
-    const char* d = nullptr;
     const size_t b_lens = (size_t)R * sizeof(int64_t);
-    if (int rc = ragged_upload_block(c, b_lens, s, [&](char* h) { memcpy(h, lens, b_lens); }, &d)) return rc;
-    *d_lens = reinterpret_cast<const int64_t*>(d);
+    if (int rc = c->rg.upload(b_lens, s, [&](char* h) { memcpy(h, lens, b_lens); })) return rc;
+    *d_lens = reinterpret_cast<const int64_t*>(c->rg.d);
     return 0;
 }
 
@@ -1723,12 +1446,7 @@ int bsrnn_separate_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_stride, 
     if (!wave || !lens_host || !wave_out || R < 1)
         return fail(BSRNN_EARG, "bsrnn_separate_ragged: need a waveform, R lengths, an output buffer and R >= 1, got R = %d", R);
     const RaggedShape q = ragged_shape(lens_host, R, wave_stride);
-    if (q.why == RAGGED_SHORT)
-        return fail(BSRNN_EARG, "bsrnn_separate_ragged: row %d has %lld samples, need more than 1024 (reflect padding)", q.bad_row, (long long)q.bad_len);
-    if (q.why == RAGGED_LONG)
-        return fail(BSRNN_EARG, "bsrnn_separate_ragged: row %d has %lld samples, more than the row stride of %lld", q.bad_row, (long long)q.bad_len,
-                    (long long)wave_stride);
-    if (ragged_too_many(R, q.Tmax)) return fail(BSRNN_EARG, "bsrnn_separate_ragged: %d rows x %lld frames is too many frame rows for one call", R, (long long)q.Tmax);
+    if (int rc0 = ragged_shape_refuse("bsrnn_separate_ragged", q, R, wave_stride)) return rc0;
     // the re-run (finish_call) reads the waveform again
     if (c->range_policy == BSRNN_RANGE_EXACT &&
         ranges_overlap(wave, (size_t)R * wave_stride * sizeof(float), wave_out, (size_t)R * q.out_stride * sizeof(float)))
@@ -1775,11 +1493,7 @@ static int ragged_dsp_check(const char* who, const bsrnn_ctx* c, bool have_buffe
     if (!c) return fail(BSRNN_EARG, "null context");
     if (!have_buffers || !lens || R < 1) return fail(BSRNN_EARG, "%s: need both buffers, R lengths and R >= 1, got R = %d", who, R);
     q = ragged_shape(lens, R, stride);
-    if (q.why == RAGGED_SHORT) return fail(BSRNN_EARG, "%s: row %d has %lld samples, need more than 1024 (reflect padding)", who, q.bad_row, (long long)q.bad_len);
-    if (q.why == RAGGED_LONG)
-        return fail(BSRNN_EARG, "%s: row %d has %lld samples, more than the row stride of %lld", who, q.bad_row, (long long)q.bad_len, (long long)stride);
-    if (ragged_too_many(R, q.Tmax)) return fail(BSRNN_EARG, "%s: %d rows x %lld frames is too many frame rows for one call", who, R, (long long)q.Tmax);
-    return 0;
+    return ragged_shape_refuse(who, q, R, stride);
 }
 
 int bsrnn_stft_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_stride, const int64_t* lens_host, float* x, int32_t R, void* stream)
@@ -1844,27 +1558,19 @@ static int train_table_check(const char* who, const bsrnn_ctx* c, bool have_buff
     if (!have_buffers || !clip_lens || n_clips < 1)
         return fail(BSRNN_EARG, "%s: need every tensor, the clips' lengths and n_clips >= 1, got n_clips = %d", who, n_clips);
     t = train_clip_table(clip_lens, clip_rows, n_clips, wave_stride);
-    const ClipShape& q = t.shape;
-    if (q.why == CLIPS_ROWS) return fail(BSRNN_EARG, "%s: clip %d has %lld rows, need at least 1", who, q.bad_clip, (long long)q.bad_value);
-    if (q.why == CLIPS_SHORT)
-        return fail(BSRNN_EARG, "%s: clip %d has %lld samples, need more than 1024 (reflect padding)", who, q.bad_clip, (long long)q.bad_value);
-    if (q.why == CLIPS_LONG)
-        return fail(BSRNN_EARG, "%s: clip %d has %lld samples, more than the row stride of %lld", who, q.bad_clip, (long long)q.bad_value,
-                    (long long)wave_stride);
-    if (q.why == CLIPS_MANY) return fail(BSRNN_EARG, "%s: %lld rows x %lld frames is too many frame rows for one call", who, (long long)q.R, (long long)q.Tmax);
-    return 0;
+    return clip_shape_refuse(who, t.shape, wave_stride);
 }
 static int train_table_upload(bsrnn_ctx* c, const TrainClipTable& t, hipStream_t s, TrainTableDev& dv)
 {
     const int64_t R = t.shape.R;
     const int n_clips = (int)t.clips.size();
-    const char* d = nullptr;
-    const int rc = ragged_upload_block(c, train_table_bytes(R, n_clips), s, [&](char* h) {
+    const int rc = c->rg.upload(train_table_bytes(R, n_clips), s, [&](char* h) {
         memcpy(h, t.row_lens.data(), (size_t)R * sizeof(int64_t));
         memcpy(h + train_table_clips_at(R), t.clips.data(), (size_t)n_clips * sizeof(TrainClip));
         memcpy(h + train_table_map_at(R, n_clips), t.row_clip.data(), (size_t)R * sizeof(int32_t));
-    }, &d);
+    });
     if (rc) return rc;
+    const char* d = c->rg.d;
     dv.lens = reinterpret_cast<const int64_t*>(d);
     dv.clips = reinterpret_cast<const TrainClip*>(d + train_table_clips_at(R));
     dv.row_clip = reinterpret_cast<const int32_t*>(d + train_table_map_at(R, n_clips));
@@ -2118,15 +1824,7 @@ int bsrnn_separate_long_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_str
         return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: need a waveform, R lengths, an output buffer and R >= 1, got R = %d", R);
     if (seg_frames < 1) return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: seg_frames = %d (at least one frame per segment)", seg_frames);
     const RaggedLongPlan q = ragged_long_plan(lens_host, R, wave_stride, seg_frames);
-    if (q.shape.why == RAGGED_SHORT)
-        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: row %d has %lld samples, need more than 1024 (reflect padding)", q.shape.bad_row,
-                    (long long)q.shape.bad_len);
-    if (q.shape.why == RAGGED_LONG)
-        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: row %d has %lld samples, more than the row stride of %lld", q.shape.bad_row,
-                    (long long)q.shape.bad_len, (long long)wave_stride);
-    if (q.too_many)
-        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: %d rows x %lld frames is too many frame rows for one segment", R,
-                    (long long)std::min<int64_t>(seg_frames, q.shape.Tmax));
+    if (int rc0 = ragged_shape_refuse("bsrnn_separate_long_ragged", q.shape, R, wave_stride, seg_frames)) return rc0;
     // whatever the range policy: later segments read the waveform after earlier hops are written
     const int64_t out_stride = q.shape.out_stride;
     if (ranges_overlap(wave, (size_t)R * wave_stride * sizeof(float), wave_out, (size_t)R * out_stride * sizeof(float)))
@@ -2290,7 +1988,6 @@ int bsrnn_evaluate(bsrnn_ctx* c, const float* mix, const float* speech, int32_t 
     return cleanup(finish_call(c, s, run, true));
 }
 
-
 // --------------------------------------------------------------------------- ragged evaluate: the metrics per clip of a ragged batch
 // A clip is the unit of the reference's metrics (one `sample`: all rows of one file, one length; validate.py and train.py:132-150 average
 // per-clip numbers), so a ragged evaluate returns the eight numbers PER CLIP, each what bsrnn_evaluate gives for that clip alone: the
@@ -2302,24 +1999,13 @@ static_assert(CM_LOSS == BSRNN_M_LOSS && CM_SDR == BSRNN_M_SDR && CM_INPUT_SDR =
               CM_L1_TIME == BSRNN_M_L1_TIME && CM_L1_RE == BSRNN_M_L1_RE && CM_L1_IM == BSRNN_M_L1_IM &&
               CM_SEPARATION_DB == BSRNN_M_SEPARATION_DB && CM_COUNT == BSRNN_N_METRICS && CLIP_ROW_Q == METRIC_TIME_Q + 2, "metrics_host.h");
 
-// The context's table block and scratch (bsrnn_ctx::EvalRagged) for a call of these sizes; grow-only
-static int eval_ragged_reserve(bsrnn_ctx* c, size_t table_bytes, size_t n_part, size_t n_est)
+// The context's scratch (bsrnn_ctx::EvalRagged) for a call of these sizes; grow-only
+static int eval_ragged_reserve(bsrnn_ctx* c, size_t n_part, size_t n_est)
 {
     bsrnn_ctx::EvalRagged& er = c->er;
-    if (table_bytes <= er.cap && n_part <= er.part_cap && n_est <= er.est_cap) return 0;
-    HIP_TRY(hipDeviceSynchronize());                                  // queued copies read the old mirrors, queued kernels the old blocks
+    if (n_part <= er.part_cap && n_est <= er.est_cap) return 0;
+    HIP_TRY(hipDeviceSynchronize());                                  // queued kernels read and write the old blocks
     auto grown = [](size_t n) { return (n + n / 2 + 255) & ~size_t(255); };
-    if (table_bytes > er.cap) {
-        if (er.d) { (void)hipFree(er.d); (void)hipHostFree(er.h); er.d = er.h = nullptr; er.cap = 0; }
-        const size_t cap = grown(table_bytes);
-        g_dbg[DBG_ALLOC] += 2;
-        HIP_TRY(hipHostMalloc((void**)&er.h, bsrnn_ctx::RG_SLOTS * cap, hipHostMallocDefault));
-        const hipError_t e = hipMalloc((void**)&er.d, cap);
-        if (e != hipSuccess) { (void)hipHostFree(er.h); er.h = er.d = nullptr; return fail(BSRNN_EHIP, "hipMalloc: %s", hipGetErrorString(e)); }
-        for (hipEvent_t& ev : er.ev)
-            if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        er.cap = cap;
-    }
     if (n_part > er.part_cap) {
         if (er.d_part) { (void)hipFree(er.d_part); (void)hipHostFree(er.h_part); er.d_part = er.h_part = nullptr; er.part_cap = 0; }
         const size_t cap = grown(n_part);
@@ -2350,14 +2036,7 @@ int bsrnn_evaluate_ragged(bsrnn_ctx* c, const float* mix, const float* speech, i
     std::vector<int64_t> row_lens;
     std::vector<int> first_row;
     const ClipShape q = clip_shape(clip_lens_host, clip_rows_host, n_clips, wave_stride, row_lens, first_row);
-    if (q.why == CLIPS_ROWS) return fail(BSRNN_EARG, "bsrnn_evaluate_ragged: clip %d has %lld rows, need at least 1", q.bad_clip, (long long)q.bad_value);
-    if (q.why == CLIPS_SHORT)
-        return fail(BSRNN_EARG, "bsrnn_evaluate_ragged: clip %d has %lld samples, need more than 1024 (reflect padding)", q.bad_clip, (long long)q.bad_value);
-    if (q.why == CLIPS_LONG)
-        return fail(BSRNN_EARG, "bsrnn_evaluate_ragged: clip %d has %lld samples, more than the row stride of %lld", q.bad_clip, (long long)q.bad_value,
-                    (long long)wave_stride);
-    if (q.why == CLIPS_MANY)
-        return fail(BSRNN_EARG, "bsrnn_evaluate_ragged: %lld rows x %lld frames is too many frame rows for one call", (long long)q.R, (long long)q.Tmax);
+    if (int rc0 = clip_shape_refuse("bsrnn_evaluate_ragged", q, wave_stride)) return rc0;
     const int R = (int)q.R, T = (int)q.Tmax;
     // the metrics read mix and speech after the estimate is written, and a re-run reads them again: whatever the policy
     if (ranges_overlap(est_out, (size_t)R * q.out_stride * sizeof(float), mix, (size_t)R * wave_stride * sizeof(float)) ||
@@ -2372,21 +2051,17 @@ int bsrnn_evaluate_ragged(bsrnn_ctx* c, const float* mix, const float* speech, i
     const size_t n_time = (size_t)R * chunks * METRIC_TIME_Q, n_si = (size_t)R * chunks * 2, n_freq = (size_t)R * FB * 2, n_in = (size_t)n_clips * IB;
     const size_t n_part = n_time + n_si + n_freq + n_in;
     const size_t b_lens = (size_t)R * sizeof(int64_t), b_table = b_lens + (size_t)n_clips * sizeof(MetricClip);
-    if ((rc = eval_ragged_reserve(c, b_table, n_part, est_out ? 0 : (size_t)R * q.out_stride))) return rc;
+    if ((rc = eval_ragged_reserve(c, n_part, est_out ? 0 : (size_t)R * q.out_stride))) return rc;
     bsrnn_ctx::EvalRagged& er = c->er;
     float* est = est_out ? est_out : er.d_est;
-    {   // the table: mirror k is written again only when the copy of RG_SLOTS calls ago has completed (an event never recorded counts as complete)
-        const int k = (int)(er.calls++ % bsrnn_ctx::RG_SLOTS);
-        HIP_TRY(hipEventSynchronize(er.ev[k]));
-        char* h = er.h + (size_t)k * er.cap;
+    rc = er.table.upload(b_table, s, [&](char* h) {
         memcpy(h, row_lens.data(), b_lens);
         MetricClip* mc = reinterpret_cast<MetricClip*>(h + b_lens);
         for (int i = 0; i < n_clips; ++i) mc[i] = MetricClip{first_row[i], clip_rows_host ? clip_rows_host[i] : 1, clip_lens_host[i]};
-        HIP_TRY(hipMemcpyAsync(er.d, h, b_table, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(er.ev[k], s));
-    }
-    const int64_t* d_lens = reinterpret_cast<const int64_t*>(er.d);
-    const MetricClip* d_clips = reinterpret_cast<const MetricClip*>(er.d + b_lens);
+    });
+    if (rc) return rc;
+    const int64_t* d_lens = reinterpret_cast<const int64_t*>(er.table.d);
+    const MetricClip* d_clips = reinterpret_cast<const MetricClip*>(er.table.d + b_lens);
     double *p_time = er.d_part, *p_si = p_time + n_time, *p_freq = p_si + n_si, *p_in = p_freq + n_freq;
 
     // a re-run sees the same table: the block on the device is not touched before the next call
@@ -2459,10 +2134,9 @@ int bsrnn_hop_activity(bsrnn_ctx* c, const float* mix, int64_t mix_stride, const
     ENTER_CALL(c, s);
     const int32_t* d_hops = nullptr;
     if (hops_host) {
-        const char* d = nullptr;
         const size_t bytes = (size_t)R * sizeof(int32_t);
-        if (int rc = ragged_upload_block(c, bytes, s, [&](char* h) { memcpy(h, hops_host, bytes); }, &d)) return rc;
-        d_hops = reinterpret_cast<const int32_t*>(d);
+        if (int rc = c->rg.upload(bytes, s, [&](char* h) { memcpy(h, hops_host, bytes); })) return rc;
+        d_hops = reinterpret_cast<const int32_t*>(c->rg.d);
     }
     launch_hop_activity(mix, mix_stride, est, est_stride, d_hops, R, Hmax, act, s);
     HIP_TRY(hipGetLastError());
@@ -2508,1685 +2182,6 @@ int bsrnn_sections_scan(const bsrnn_section_rule* rule, bsrnn_section_state* sta
     *n_out = sections_scan(q, st, act_host, n_hops, flush != 0, out, cap);
     state->n_dialog = st.n_dialog; state->n_background = st.n_background; state->open_kind = st.open_kind;
     state->open_hop = st.open_hop; state->hop = st.hop;
-    return 0;
-}
-
-
-// --------------------------------------------------------------------------- streaming
-// Device layout of a stream object: two carry sets [buf | prev | state] (see bsrnn_stream), then the per-step scratch [X | Y | chunk | out]
-// and the hop counts of a hops call [row_frames].
-static size_t stream_carry_floats(const bsrnn_ctx* c, int C) { return (size_t)C * NFFT * 2 + state_floats(C, c->K); }
-static size_t stream_total_floats(const bsrnn_ctx* c, int C)
-{
-    return 2 * stream_carry_floats(c, C) + (size_t)C * ((size_t)c->LDP * 2 + HOPS * 2 + 1) + 4;      // (+ 1: row_frames, one word per row)
-}
-
-int bsrnn_stream_create(bsrnn_ctx* c, int32_t C, bsrnn_stream** out)
-{
-    int rc = check_ready(c);
-    if (rc) return rc;
-    if (!out || C < 1) return fail(BSRNN_EARG, "bsrnn_stream_create: bad arguments");
-    CallGuard guard_(c);
-    if (!guard_.ok) return guard_.refuse();
-    bsrnn_stream* st = new bsrnn_stream();
-    st->ctx = c; st->C = C;
-    const size_t nstate = state_floats(C, c->K);
-    const size_t total = stream_total_floats(c, C);
-    float* p = nullptr;
-    ++g_dbg[DBG_ALLOC];
-    hipError_t e = hipMalloc((void**)&p, total * sizeof(float));
-    if (e != hipSuccess) { delete st; return fail(BSRNN_EHIP, "hipMalloc: %s", hipGetErrorString(e)); }
-    st->base = p;
-    for (int k = 0; k < 2; ++k) {
-        st->buf[k] = p; p += (size_t)C * NFFT;
-        st->prev[k] = p; p += (size_t)C * NFFT;
-        st->state[k] = p; p += nstate;
-    }
-    st->X = p; p += (size_t)C * c->LDP;
-    st->Y = p; p += (size_t)C * c->LDP;
-    st->chunk = p; p += (size_t)C * HOPS;
-    st->out = p; p += (size_t)C * HOPS;
-    st->row_frames = reinterpret_cast<int*>(p); p += C;
-    // The model part of a step as plain launches (default) or as one hipGraph per carry parity (BSRNN_STREAM_GRAPH=1).  Measured from C
-    // (tools/stream_cloop.cpp, profiles/r04_stream_kernels.txt): the graph launch of the 14 dependent kernel nodes costs the host MORE than
-    // 14 plain launches (78 vs 68 us inside the call) and the chunk 143.2 vs 139.5 us - the gaps between dependent kernels are the same
-    // inside a replayed graph - so the cheaper form is the default; the graph path stays for A/B (BSRNN_NO_GRAPH is accepted and means the default).
-    st->use_graph = getenv("BSRNN_STREAM_GRAPH") != nullptr && getenv("BSRNN_NO_GRAPH") == nullptr;
-    if (hipHostMalloc((void**)&st->h_in, (size_t)C * HOPS * sizeof(float), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&st->h_out, (size_t)C * HOPS * sizeof(float), hipHostMallocDefault) != hipSuccess) {
-        (void)hipFree(st->base); delete st; return fail(BSRNN_EHIP, "hipHostMalloc failed");
-    }
-    e = hipMemset(st->base, 0, total * sizeof(float));
-    if (e != hipSuccess) { (void)hipFree(st->base); delete st; return fail(BSRNN_EHIP, "hipMemset: %s", hipGetErrorString(e)); }
-    rc = ensure_ws(c, C);
-    if (!rc) rc = ensure_tasks(c, C);
-    if (rc) { (void)hipHostFree(st->h_in); (void)hipHostFree(st->h_out); (void)hipFree(st->base); delete st; return rc; }
-    ++c->live_streams;
-    // Everything a first step would otherwise do on the caller's (audio) thread happens here, as the reference does in its constructor
-    // (speech-ladspa-onnx.cpp:55-120: session, FFT plans, state): one throw-away step per carry parity through the host-buffer entry
-    // point - it loads every kernel's code object, captures and instantiates both parity graphs and touches the pinned staging
-    // buffers - then the carry sets are zeroed again.  bsrnn_stream_step / _step_host allocate, capture and instantiate nothing
-    // afterwards unless the context's workspace or weights change under the stream (generation counter).
-    {
-        std::vector<float> zero((size_t)C * HOPS, 0.f), sink((size_t)C * HOPS);
-        for (int k = 0; k < 2 && !rc; ++k) rc = bsrnn_stream_step_host(st, zero.data(), sink.data(), 1.0f);
-        if (!rc && hipMemset(st->base, 0, total * sizeof(float)) != hipSuccess) rc = fail(BSRNN_EHIP, "hipMemset failed");
-        if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(BSRNN_EHIP, "hipDeviceSynchronize failed");
-        st->cur = 0;
-        if (rc) { bsrnn_stream_destroy(st); return rc; }
-    }
-    *out = st;
-    return 0;
-}
-
-static void stream_drop_graph(bsrnn_stream* st)
-{
-    for (int k = 0; k < 2; ++k) {
-        if (st->exec[k]) { (void)hipGraphExecDestroy(st->exec[k]); st->exec[k] = nullptr; }
-        if (st->graph[k]) { (void)hipGraphDestroy(st->graph[k]); st->graph[k] = nullptr; }
-    }
-}
-
-void bsrnn_stream_destroy(bsrnn_stream* st)
-{
-    if (!st) return;
-    bsrnn_ctx* c = st->ctx;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    stream_drop_graph(st);
-    if (st->cap) (void)hipStreamDestroy(st->cap);
-    if (st->h_in) (void)hipHostFree(st->h_in);
-    if (st->h_out) (void)hipHostFree(st->h_out);
-    (void)hipFree(st->base);
-    delete st;
-    if (--c->live_streams == 0 && c->zombie) destroy_now(c);     // bsrnn_destroy() came first: the context goes with its last stream
-}
-
-int bsrnn_stream_reset(bsrnn_stream* st, void* stream)
-{
-    if (!st) return fail(BSRNN_EARG, "null stream");
-    HIP_TRY(hipSetDevice(st->ctx->device));
-    HIP_TRY(hipMemsetAsync(st->base, 0, stream_total_floats(st->ctx, st->C) * sizeof(float), (hipStream_t)stream));
-    st->cur = 0;
-    return 0;
-}
-
-// One step from carry set p = st->cur into set 1 - p: chunk -> out (device pointers of the caller or the object's own buffers).
-// The model part is a graph replay when possible.  Does NOT flip st->cur: the caller does, once the step is known to be good.
-// rows (bsrnn_stream_process_rows): only the rows of rows->active take the step; the others are held by the two DSP launches (the model part
-// is the same, captured graph included: a held row enters it as a zero spectrum, and the synthesis launch - behind every launch of the
-// model in stream order - puts its LSTM state back).
-struct RowArgs { RowSet active; const float* mix_rows; };
-static int stream_step_run(bsrnn_stream* st, const float* chunk, float* out, float mix, hipStream_t s, const RowArgs* rows = nullptr)
-{
-    bsrnn_ctx* c = st->ctx;
-    const int p = st->cur, q = p ^ 1;
-    int rc;
-    {
-        StageScope sc(c, ST_STREAM_DSP, s);
-        if (rows) launch_stream_analysis_rows(c->tb, st->buf[p], st->buf[q], chunk, st->X, st->C, rows->active, s);
-        else launch_stream_analysis(c->tb, st->buf[p], st->buf[q], chunk, st->X, st->C, s);
-    }
-    if (st->use_graph && c->prof == 0 && !force_f32()) {
-        // The captured launches hold the context's workspace and weight-arena pointers.  A larger call on the context (workspace
-        // regrown) or a re-commit of the parameters (arena rebuilt) since the capture changes ctx->gen: capture again
-        // instead of replaying launches that point into freed memory.
-        if ((st->exec[0] || st->exec[1]) && st->gen != c->gen) {
-            HIP_TRY(hipDeviceSynchronize());
-            stream_drop_graph(st);
-        }
-        if (!st->exec[p]) {
-            if (!st->cap) { ++g_dbg[DBG_ALLOC]; HIP_TRY(hipStreamCreateWithFlags(&st->cap, hipStreamNonBlocking)); }
-            ++g_dbg[DBG_CAPTURE];
-            HIP_TRY(hipStreamBeginCapture(st->cap, hipStreamCaptureModeThreadLocal));
-            rc = run_model(c, st->X, st->Y, nullptr, st->C, 1, st->state[p], st->state[q], st->cap);
-            hipGraph_t g = nullptr;
-            hipError_t e = hipStreamEndCapture(st->cap, &g);           // (always ended, whatever run_model said: the stream must leave capture mode)
-            if (rc || e != hipSuccess) {
-                if (g) (void)hipGraphDestroy(g);                       // a failed capture leaves nothing behind
-                (void)hipGetLastError();
-                if (rc) return rc;
-                return fail(BSRNN_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-            }
-            ++g_dbg[DBG_INSTANTIATE];
-            e = hipGraphInstantiate(&st->exec[p], g, nullptr, nullptr, 0);
-            if (e != hipSuccess) {
-                (void)hipGraphDestroy(g);
-                st->exec[p] = nullptr;
-                return fail(BSRNN_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-            }
-            st->graph[p] = g;
-            st->gen = c->gen;
-        }
-        ++g_dbg[DBG_GRAPH_LAUNCH];
-        HIP_TRY(hipGraphLaunch(st->exec[p], s));
-    } else if ((rc = run_model(c, st->X, st->Y, nullptr, st->C, 1, st->state[p], st->state[q], s))) {
-        return rc;
-    }
-    {
-        StageScope sc(c, ST_STREAM_DSP, s);
-        if (rows) launch_stream_synthesis_rows(c->tb, st->Y, st->X, mix, rows->mix_rows, st->prev[p], st->prev[q], out, st->state[p], st->state[q], st->C, c->K,
-                                               rows->active, s);
-        else launch_stream_synthesis(c->tb, st->Y, st->X, mix, st->prev[p], st->prev[q], out, st->C, s);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int bsrnn_stream_step(bsrnn_stream* st, const float* chunk, float* out, float mix, void* stream)
-{
-    if (!st || !chunk || !out) return fail(BSRNN_EARG, "bsrnn_stream_step: null argument");
-    bsrnn_ctx* c = st->ctx;
-    int rc = check_ready(c);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    ENTER_CALL(c, s);
-    if ((rc = ensure_ws(c, st->C)) || (rc = ensure_tasks(c, st->C))) return rc;
-    const float* src = chunk;
-    const size_t nb = (size_t)st->C * HOPS * sizeof(float);
-    if (ranges_overlap(chunk, nb, out, nb) && c->range_policy == BSRNN_RANGE_EXACT) {
-        // in place, or partly: a re-run (range policy) must still see the input, so it is kept aside first
-        HIP_TRY(hipMemcpyAsync(st->chunk, chunk, (size_t)st->C * HOPS * sizeof(float), hipMemcpyDeviceToDevice, s));
-        src = st->chunk;
-    }
-    if ((rc = stream_step_run(st, src, out, mix, s))) return rc;
-    // default range policy: wait, look at the guard, and if an operand left the fp16 range run the step again on the exact-fp32
-    // kernels from the same (untouched) carry set
-    if ((rc = finish_call(c, s, [&]() -> int { return stream_step_run(st, src, out, mix, s); }))) return rc;
-    st->cur ^= 1;
-    return 0;
-}
-
-int bsrnn_stream_step_host(bsrnn_stream* st, const float* chunk_host, float* out_host, float mix)
-{
-    if (!st || !chunk_host || !out_host) return fail(BSRNN_EARG, "bsrnn_stream_step_host: null argument");
-    bsrnn_ctx* c = st->ctx;
-    int rc = check_ready(c);
-    if (rc) return rc;
-    ENTER_CALL(c, (hipStream_t) nullptr);
-    const size_t nb = (size_t)st->C * HOPS * sizeof(float);
-    memcpy(st->h_in, chunk_host, nb);
-    HIP_TRY(hipMemcpyAsync(st->chunk, st->h_in, nb, hipMemcpyHostToDevice, nullptr));
-    // This entry point waits for its own kernels anyway, so it repairs a range violation whatever the policy says
-    const int keep = c->range_policy;
-    c->range_policy = BSRNN_RANGE_EXACT;
-    rc = bsrnn_stream_step(st, st->chunk, st->out, mix, nullptr);
-    c->range_policy = keep;
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(st->h_out, st->out, nb, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    memcpy(out_host, st->h_out, nb);
-    return 0;
-}
-
-// L hops from carry set p = st->cur into set 1 - p: chunk [C][L*1024] -> out [C][L*1024], the spectra in the context's workspace (one call
-// at a time per context).  Does NOT flip st->cur (see stream_step_run).
-// rows: as for stream_step_run.  On the overlapped plan the second time-axis launch writes its half of state[q] on the auxiliary stream;
-// run_overlapped joins that stream into `s` by an event for every call that returns LSTM state - this one does - so the synthesis launch,
-// which copies the held rows' state over what the model wrote, follows both.
-// hops (bsrnn_stream_process_hops): row r advances by its own count.  The analysis launch leaves the counts in st->row_frames, the two
-// time-axis launches return every row's state after ITS last frame, and the synthesis - which follows both, as above - holds the rows at 0.
-struct HopArgs { RowHops hops; const float* mix_rows; };
-static int stream_block_run(bsrnn_stream* st, const float* chunk, float* out, int L, float mix, hipStream_t s, const RowArgs* rows = nullptr,
-                            const HopArgs* hops = nullptr)
-{
-    bsrnn_ctx* c = st->ctx;
-    const int p = st->cur, q = p ^ 1;
-    {
-        StageScope sc(c, ST_STREAM_DSP, s);
-        if (hops) launch_stream_block_analysis_hops(c->tb, st->buf[p], st->buf[q], chunk, c->Xf, st->C, L, hops->hops, st->row_frames, s);
-        else if (rows) launch_stream_block_analysis_rows(c->tb, st->buf[p], st->buf[q], chunk, c->Xf, st->C, L, rows->active, s);
-        else launch_stream_block_analysis(c->tb, st->buf[p], st->buf[q], chunk, c->Xf, st->C, L, s);
-    }
-    if (int rc = run_model(c, c->Xf, c->Yf, nullptr, st->C, L, st->state[p], st->state[q], s, hops ? st->row_frames : nullptr)) return rc;
-    {
-        StageScope sc(c, ST_STREAM_DSP, s);
-        if (hops) launch_stream_block_synthesis_hops(c->tb, c->Yf, c->Xf, mix, hops->mix_rows, st->prev[p], st->prev[q], out, st->state[p], st->state[q], st->C,
-                                                     c->K, L, hops->hops, s);
-        else if (rows) launch_stream_block_synthesis_rows(c->tb, c->Yf, c->Xf, mix, rows->mix_rows, st->prev[p], st->prev[q], out, st->state[p], st->state[q], st->C,
-                                                     c->K, L, rows->active, s);
-        else launch_stream_block_synthesis(c->tb, c->Yf, c->Xf, mix, st->prev[p], st->prev[q], out, st->C, L, s);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int bsrnn_stream_process(bsrnn_stream* st, const float* chunk, float* out, int32_t n_hops, float mix, void* stream)
-{
-    if (!st || !chunk || !out) return fail(BSRNN_EARG, "bsrnn_stream_process: null argument");
-    if (n_hops < 1) return fail(BSRNN_EARG, "bsrnn_stream_process: n_hops = %d (at least one hop)", n_hops);
-    bsrnn_ctx* c = st->ctx;
-    int rc = check_ready(c);
-    if (rc) return rc;
-    const size_t nb = (size_t)st->C * n_hops * HOPS * sizeof(float);
-    if (c->range_policy == BSRNN_RANGE_EXACT && ranges_overlap(chunk, nb, out, nb))
-        return fail(BSRNN_EARG, "bsrnn_stream_process: out_dev must not overlap chunk_dev under the exact range policy (the re-run of a call that leaves the fp16 range reads chunk_dev again)");
-    if (n_hops == 1) return bsrnn_stream_step(st, chunk, out, mix, stream);       // the step itself: bit-identical by construction
-    hipStream_t s = (hipStream_t)stream;
-    ENTER_CALL(c, s);
-    const size_t M = (size_t)st->C * n_hops;
-    if (M > (size_t)INT32_MAX / 2) return fail(BSRNN_EARG, "bsrnn_stream_process: %d rows x %d hops is too many frame rows for one call", st->C, n_hops);
-    if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M))) return rc;
-    if ((rc = stream_block_run(st, chunk, out, n_hops, mix, s))) return rc;
-    // range policy as for the step: the re-run repeats analysis, model and synthesis from the untouched carry set
-    if ((rc = finish_call(c, s, [&]() -> int { return stream_block_run(st, chunk, out, n_hops, mix, s); }))) return rc;
-    st->cur ^= 1;
-    return 0;
-}
-
-int bsrnn_stream_reserve(bsrnn_stream* st, int32_t max_hops)
-{
-    if (!st || max_hops < 1) return fail(BSRNN_EARG, "bsrnn_stream_reserve: bad arguments");
-    bsrnn_ctx* c = st->ctx;
-    int rc = check_ready(c);
-    if (rc) return rc;
-    ENTER_CALL(c, (hipStream_t) nullptr);
-    const int C = st->C;
-    if ((size_t)C * max_hops > (size_t)INT32_MAX / 2) return fail(BSRNN_EARG, "bsrnn_stream_reserve: %d rows x %d hops is too many frame rows for one call", C, max_hops);
-    if ((rc = ensure_ws(c, (size_t)C * max_hops))) return rc;
-    // one task table and (where the plan overlaps the dual path) one pair of dispatch orders per block length: they are keyed by the row
-    // count, and a later call of any length up to max_hops must find its own.  The caches' bounds grow so that this set fits beside what
-    // is there already (a few KB per table).
-    std::vector<int> ms;
-    size_t missing = 0, ovl_missing = 0;
-    for (int L = 1; L <= max_hops; ++L) {
-        ms.push_back(C * L);
-        missing += c->fused && c->chain_tasks.find(C * L) == c->chain_tasks.end();
-        ovl_missing += plan_call(c, C, L, true, true).overlap && c->ovl_tables.find(std::make_pair(C, L)) == c->ovl_tables.end();
-    }
-    c->task_cap = std::max(c->task_cap, c->chain_tasks.size() + missing);
-    c->ovl_cap = std::max(c->ovl_cap, c->ovl_tables.size() + ovl_missing + 1);
-    if ((rc = ensure_tasks(c, ms.data(), (int)ms.size()))) return rc;
-    for (int L = 1; L <= max_hops; ++L)
-        if ((rc = ensure_ovl(c, plan_call(c, C, L, true, true), C, L))) return rc;
-    // Load the kernels of every plan a block can take (GEMV rows, few-row band block, chains, overlapped dual path) and fill the launchers'
-    // function-local statics: throw-away blocks of zeros from the current carry set into the OTHER one, which the next real call
-    // overwrites completely (cur is not flipped).
-    const int cand[4] = {2, 8, 31, max_hops};
-    float* tmp = nullptr;
-    const size_t nfl = (size_t)C * max_hops * HOPS;
-    ++g_dbg[DBG_ALLOC];
-    HIP_TRY(hipMalloc((void**)&tmp, 2 * nfl * sizeof(float)));
-    hipError_t e = hipMemset(tmp, 0, 2 * nfl * sizeof(float));
-    int last = 1;
-    for (int i = 0; i < 4 && !rc && e == hipSuccess; ++i) {
-        const int L = std::min(cand[i], (int)max_hops);
-        if (L <= last) continue;
-        last = L;
-        rc = stream_block_run(st, tmp, tmp + nfl, L, 1.0f, nullptr);
-        if (!rc) rc = stream_block_run(st, tmp, tmp + nfl, L, 0.5f, nullptr);
-        if (C <= STREAM_ROWS_MAX && L <= STREAM_HOPS_MAX) {      // ... and of the same plans as bsrnn_stream_process_hops runs them (the ragged time-axis kernels, the HopRows DSP pair)
-            HopArgs ha;
-            RowHopsInfo info;
-            std::vector<int32_t> cnt((size_t)C);
-            for (int r = 0; r < C; ++r) cnt[r] = L - (r & 1);
-            ha.mix_rows = nullptr;
-            if (pack_row_hops(cnt.data(), C, L, ha.hops, info) < 0) {
-                if (!rc) rc = stream_block_run(st, tmp, tmp + nfl, L, 1.0f, nullptr, nullptr, &ha);
-                if (!rc) rc = stream_block_run(st, tmp, tmp + nfl, L, 0.5f, nullptr, nullptr, &ha);
-            }
-        }
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (!rc) rc = ovl_join_host(c);
-    (void)hipFree(tmp);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(BSRNN_EHIP, "bsrnn_stream_reserve: %s", hipGetErrorString(e));
-    return check_range(c);
-}
-
-int bsrnn_stream_get_state(bsrnn_stream* st, float* state_host)
-{
-    if (!st || !state_host) return fail(BSRNN_EARG, "null argument");
-    HIP_TRY(hipSetDevice(st->ctx->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const size_t nstate = state_floats(st->C, st->ctx->K);
-    HIP_TRY(hipMemcpy(state_host, st->state[st->cur], nstate * sizeof(float), hipMemcpyDeviceToHost));
-    return check_range(st->ctx);          // steps made under the 'deferred' policy report a range violation here (or at the next call / bsrnn_sync)
-}
-
-// --------------------------------------------------------------------------- streaming, row by row (session slots)
-static_assert(BSRNN_STREAM_ROWS_MAX == STREAM_ROWS_MAX, "include/bsrnn_hip.h and stream_rows_host.h disagree");
-
-int bsrnn_stream_process_rows(bsrnn_stream* st, const float* chunk, float* out, int32_t n_hops, const uint8_t* active_host, const float* mix_rows,
-                              float mix, void* stream)
-{
-    if (!st || !chunk || !out) return fail(BSRNN_EARG, "bsrnn_stream_process_rows: null argument");
-    if (n_hops < 1) return fail(BSRNN_EARG, "bsrnn_stream_process_rows: n_hops = %d (at least one hop)", n_hops);
-    RowArgs ra;
-    ra.mix_rows = mix_rows;
-    const int n_active = pack_row_set(active_host, st->C, ra.active);      // (the caller's array is not looked at again)
-    if (n_active < 0)
-        return fail(BSRNN_EARG, "bsrnn_stream_process_rows: the stream has %d rows, the rows calls take at most BSRNN_STREAM_ROWS_MAX = %d", st->C, STREAM_ROWS_MAX);
-    bsrnn_ctx* c = st->ctx;
-    const size_t nb = (size_t)st->C * n_hops * HOPS * sizeof(float);
-    if (c->range_policy == BSRNN_RANGE_EXACT && ranges_overlap(chunk, nb, out, nb))
-        return fail(BSRNN_EARG, "bsrnn_stream_process_rows: out_dev must not overlap chunk_dev under the exact range policy (the re-run of a call that leaves the fp16 range reads chunk_dev again)");
-    if (ranges_overlap(mix_rows, (size_t)st->C * sizeof(float), chunk, nb) || ranges_overlap(mix_rows, (size_t)st->C * sizeof(float), out, nb))
-        return fail(BSRNN_EARG, "bsrnn_stream_process_rows: mix_rows_dev must overlap neither chunk_dev nor out_dev");
-    // every row, one wet / dry value: the plain call itself
-    if (n_active == st->C && !mix_rows) return bsrnn_stream_process(st, chunk, out, n_hops, mix, stream);
-    int rc = check_ready(c);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    ENTER_CALL(c, s);
-    // no row: nothing advances, the carry sets stay as they are
-    if (n_active == 0) { HIP_TRY(hipMemsetAsync(out, 0, nb, s)); return 0; }
-    const size_t M = (size_t)st->C * n_hops;
-    if (M > (size_t)INT32_MAX / 2) return fail(BSRNN_EARG, "bsrnn_stream_process_rows: %d rows x %d hops is too many frame rows for one call", st->C, n_hops);
-    if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M))) return rc;
-    // one hop: the step's kernels and its captured graph; more: the block path.  Both read carry set cur and write the other one, for
-    // held rows too, so the re-run of the range policy starts from the untouched set with the same rows held.
-    auto run = [&]() -> int { return n_hops == 1 ? stream_step_run(st, chunk, out, mix, s, &ra) : stream_block_run(st, chunk, out, n_hops, mix, s, &ra); };
-    if ((rc = run())) return rc;
-    if ((rc = finish_call(c, s, run))) return rc;
-    st->cur ^= 1;
-    return 0;
-}
-
-static_assert(BSRNN_STREAM_HOPS_MAX == STREAM_HOPS_MAX, "include/bsrnn_hip.h and stream_rows_host.h disagree");
-
-int bsrnn_stream_process_hops(bsrnn_stream* st, const float* chunk, float* out, int32_t n_hops, const int32_t* hops_host, const float* mix_rows,
-                              float mix, void* stream)
-{
-    if (n_hops < 1 || n_hops > STREAM_HOPS_MAX)
-        return fail(BSRNN_EARG, "bsrnn_stream_process_hops: n_hops = %d (1 to BSRNN_STREAM_HOPS_MAX = %d hops per call)", n_hops, STREAM_HOPS_MAX);
-    if (!st || !chunk || !out || !hops_host) return fail(BSRNN_EARG, "bsrnn_stream_process_hops: null argument");
-    if (st->C > STREAM_ROWS_MAX)
-        return fail(BSRNN_EARG, "bsrnn_stream_process_hops: the stream has %d rows, the rows calls take at most BSRNN_STREAM_ROWS_MAX = %d", st->C, STREAM_ROWS_MAX);
-    HopArgs ha;
-    RowHopsInfo info;
-    ha.mix_rows = mix_rows;
-    const int bad = pack_row_hops(hops_host, st->C, n_hops, ha.hops, info);      // (the caller's array is not looked at again, but for the delegation below)
-    if (bad >= 0) return fail(BSRNN_EARG, "bsrnn_stream_process_hops: row %d has %d hops, outside [0, n_hops = %d]", bad, hops_host[bad], n_hops);
-    bsrnn_ctx* c = st->ctx;
-    const size_t nb = (size_t)st->C * n_hops * HOPS * sizeof(float);
-    if (c->range_policy == BSRNN_RANGE_EXACT && ranges_overlap(chunk, nb, out, nb))
-        return fail(BSRNN_EARG, "bsrnn_stream_process_hops: out_dev must not overlap chunk_dev under the exact range policy (the re-run of a call that leaves the fp16 range reads chunk_dev again)");
-    if (ranges_overlap(mix_rows, (size_t)st->C * sizeof(float), chunk, nb) || ranges_overlap(mix_rows, (size_t)st->C * sizeof(float), out, nb))
-        return fail(BSRNN_EARG, "bsrnn_stream_process_hops: mix_rows_dev must overlap neither chunk_dev nor out_dev");
-    // every count 0 or n_hops (none at all included): the rows call itself, bit-identical by construction, one-hop graph path and all
-    if (info.all_or_none) {
-        std::vector<uint8_t> active((size_t)st->C);
-        for (int r = 0; r < st->C; ++r) active[r] = hops_host[r] != 0;
-        return bsrnn_stream_process_rows(st, chunk, out, n_hops, active.data(), mix_rows, mix, stream);
-    }
-    int rc = check_ready(c);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    ENTER_CALL(c, s);
-    const size_t M = (size_t)st->C * n_hops;
-    if ((rc = ensure_ws(c, M)) || (rc = ensure_tasks(c, (int)M))) return rc;
-    // mixed counts always take the block path (n_hops >= 2 here); the re-run of the range policy repeats the masked analysis, the model and
-    // the masked synthesis from the untouched carry set with the same counts
-    auto run = [&]() -> int { return stream_block_run(st, chunk, out, n_hops, mix, s, nullptr, &ha); };
-    if ((rc = run())) return rc;
-    if ((rc = finish_call(c, s, run))) return rc;
-    st->cur ^= 1;
-    return 0;
-}
-
-int bsrnn_stream_reset_rows(bsrnn_stream* st, const int32_t* rows_host, int32_t n_rows, void* stream)
-{
-    if (!st) return fail(BSRNN_EARG, "bsrnn_stream_reset_rows: null stream");
-    if (!rows_host || n_rows < 1) return fail(BSRNN_EARG, "bsrnn_stream_reset_rows: no rows (null list or n_rows = %d)", n_rows);
-    if (st->C > STREAM_ROWS_MAX)
-        return fail(BSRNN_EARG, "bsrnn_stream_reset_rows: the stream has %d rows, the rows calls take at most BSRNN_STREAM_ROWS_MAX = %d", st->C, STREAM_ROWS_MAX);
-    RowSet rs;
-    const int bad = pack_row_list(rows_host, n_rows, st->C, rs);
-    if (bad >= 0) return fail(BSRNN_EARG, "bsrnn_stream_reset_rows: row %d (entry %d of the list) is outside [0, %d)", rows_host[bad], bad, st->C);
-    HIP_TRY(hipSetDevice(st->ctx->device));
-    launch_stream_reset_rows(st->buf[st->cur], st->prev[st->cur], st->state[st->cur], st->C, st->ctx->K, rs, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int64_t bsrnn_stream_row_floats(const bsrnn_stream* st) { return st ? stream_row_floats(st->ctx->K) : -1; }
-
-// One row's carry <-> blob [buf 2048 | prev 2048 | state 4*2 slabs of K*64]: two plain copies and one strided one (the row's slab is
-// K*64 contiguous floats at dim 2 = row*K of each of the eight [C*K][64] slabs).
-static int stream_move_row(bsrnn_stream* st, int row, float* blob, bool get)
-{
-    bsrnn_ctx* c = st->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const int p = st->cur;
-    const size_t slab = (size_t)c->K * HID * sizeof(float), pitch = slab * st->C;
-    float* buf = st->buf[p] + (size_t)row * NFFT;
-    float* prev = st->prev[p] + (size_t)row * NFFT;
-    float* state = st->state[p] + (size_t)row * c->K * HID;
-    if (get) {
-        HIP_TRY(hipMemcpy(blob, buf, NFFT * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(blob + NFFT, prev, NFFT * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy2D(blob + 2 * NFFT, slab, state, pitch, slab, 8, hipMemcpyDeviceToHost));
-    } else {
-        HIP_TRY(hipMemcpy(buf, blob, NFFT * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(prev, blob + NFFT, NFFT * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy2D(state, pitch, blob + 2 * NFFT, slab, slab, 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipDeviceSynchronize());
-    }
-    return 0;
-}
-
-int bsrnn_stream_get_row(bsrnn_stream* st, int32_t row, float* blob_host)
-{
-    if (!st || !blob_host) return fail(BSRNN_EARG, "bsrnn_stream_get_row: null argument");
-    if (row < 0 || row >= st->C) return fail(BSRNN_EARG, "bsrnn_stream_get_row: row %d is outside [0, %d)", row, st->C);
-    if (int rc = stream_move_row(st, row, blob_host, true)) return rc;
-    return check_range(st->ctx);          // as bsrnn_stream_get_state: calls made under the 'deferred' policy report a range violation here
-}
-
-int bsrnn_stream_set_row(bsrnn_stream* st, int32_t row, const float* blob_host)
-{
-    if (!st || !blob_host) return fail(BSRNN_EARG, "bsrnn_stream_set_row: null argument");
-    if (row < 0 || row >= st->C) return fail(BSRNN_EARG, "bsrnn_stream_set_row: row %d is outside [0, %d)", row, st->C);
-    return stream_move_row(st, row, const_cast<float*>(blob_host), false);
-}
-
-// --------------------------------------------------------------------------- sample-rate conversion
-// The definition and all index arithmetic: resample_host.h; the kernel: resample.hip.  One launch per call, for the one-shot form and
-// for the streaming object alike.
-struct bsrnn_resampler {
-    bsrnn_ctx* ctx;
-    int C;
-    ResampleRatio q;
-    ResampleTiling g;
-    const float* tab;              // the context's table of (up, down)
-    // The inputs that outputs not yet determined still need, per row: two buffers of cap floats per row, a call reads set `cur` and
-    // writes the other (the launch that reads the carry also writes the next one).  N inputs taken and J outputs given so far; the
-    // carry holds inputs [max(0, resample_base(J)), N).
-    float* carry[2];
-    int64_t cap;
-    int cur;
-    int64_t N, J;
-};
-
-static int resample_check_rates(int32_t rate_in, int32_t rate_out, const char* who, ResampleRatio& q)
-{
-    q = resample_ratio(rate_in, rate_out);
-    if (q.why == RESAMPLE_BAD_RATE)
-        return fail(BSRNN_EARG, "%s: rates must be at least 1, got rate_in = %d, rate_out = %d", who, rate_in, rate_out);
-    if (q.why == RESAMPLE_TOO_FINE)
-        return fail(BSRNN_EARG, "%s: %d -> %d reduces to %lld / %lld, beyond the limit of %d for max(up, down)", who, rate_in, rate_out,
-                    (long long)q.up, (long long)q.down, RESAMPLE_MAX_FACTOR);
-    return 0;
-}
-
-// The context's table of q's (up, down): designed in double, rounded to fp32 and uploaded when the pair is met first (synchronous).
-static int resample_table_of(bsrnn_ctx* c, const ResampleRatio& q, const bsrnn_ctx::ResampleTable** out)
-{
-    for (const auto& t : c->rs_tables)
-        if (t.q.up == q.up && t.q.down == q.down) { *out = &t; return 0; }
-    bsrnn_ctx::ResampleTable t{q, resample_tiling(q), nullptr};
-    const std::vector<float> tab = resample_table_by_output(q, resample_design(q), t.g.ld);
-    ++g_dbg[DBG_ALLOC];
-    HIP_TRY(hipMalloc((void**)&t.d, tab.size() * sizeof(float)));
-    if (hipError_t e = hipMemcpy(t.d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice)) {
-        (void)hipFree(t.d);
-        return fail(BSRNN_EHIP, "resampling table upload: %s", hipGetErrorString(e));
-    }
-    c->rs_tables.push_back(t);
-    *out = &c->rs_tables.back();
-    return 0;
-}
-
-static ResampleArgs resample_args(const ResampleRatio& q, const ResampleTiling& g, const float* tab)
-{
-    ResampleArgs a{};
-    a.tab = tab; a.up = (int)q.up; a.down = (int)q.down; a.Kh = q.Kh; a.ld = g.ld; a.chunk = g.chunk; a.tile = g.tile;
-    return a;
-}
-
-int64_t bsrnn_resample_len(int64_t n_in, int32_t rate_in, int32_t rate_out)
-{
-    const ResampleRatio q = resample_ratio(rate_in, rate_out);
-    if (q.why != RESAMPLE_OK || n_in < 1 || n_in > (INT64_MAX >> 12)) return -1;
-    return resample_n_out(n_in, q.up, q.down);
-}
-
-int bsrnn_resample(bsrnn_ctx* c, const float* in, int64_t in_stride, float* out, int64_t out_stride, int32_t R, int64_t n_in,
-                   int32_t rate_in, int32_t rate_out, void* stream)
-{
-    // arguments first, device or not (a host-only context answers them before BSRNN_ESTATE)
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (!in || !out || R < 1) return fail(BSRNN_EARG, "bsrnn_resample: need an input, an output and R >= 1, got R = %d", R);
-    ResampleRatio q;
-    if (int rc = resample_check_rates(rate_in, rate_out, "bsrnn_resample", q)) return rc;
-    if (n_in < 1 || n_in > (INT64_MAX >> 12)) return fail(BSRNN_EARG, "bsrnn_resample: need n_in >= 1 samples, got %lld", (long long)n_in);
-    const int64_t n_out = resample_n_out(n_in, q.up, q.down);
-    if (in_stride < n_in) return fail(BSRNN_EARG, "bsrnn_resample: in_stride %lld is less than n_in = %lld", (long long)in_stride, (long long)n_in);
-    if (out_stride < n_out)
-        return fail(BSRNN_EARG, "bsrnn_resample: out_stride %lld is less than the %lld samples of a row's result", (long long)out_stride, (long long)n_out);
-    // the extent of what the rows span, not R * in_stride: behind the last row of a column view (buf[:, a:b]) lies somebody else's memory
-    if (ranges_overlap(in, ((size_t)(R - 1) * in_stride + n_in) * sizeof(float), out, ((size_t)(R - 1) * out_stride + n_out) * sizeof(float)))
-        return fail(BSRNN_EARG, "bsrnn_resample: out_dev must not overlap the (R - 1) * in_stride + n_in floats the rows of in_dev span "
-                                "(rows are read while others are written)");
-    if (int rc = check_device(c)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    ENTER_CALL(c, s);
-    if (q.up == q.down) {           // equal rates: a copy
-        HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride * sizeof(float), in, (size_t)in_stride * sizeof(float), (size_t)n_in * sizeof(float), R,
-                                 hipMemcpyDeviceToDevice, s));
-        return 0;
-    }
-    const bsrnn_ctx::ResampleTable* t = nullptr;
-    if (int rc = resample_table_of(c, q, &t)) return rc;
-    ResampleArgs a = resample_args(t->q, t->g, t->d);
-    a.b = in; a.b_stride = in_stride; a.n_total = n_in;
-    a.out = out; a.out_stride = out_stride; a.n_j = n_out;
-    a.n_tiles = (int)((n_out + t->g.tile - 1) / t->g.tile);
-    launch_resample(a, R, s);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-static int64_t resampler_keep_from(const bsrnn_resampler* rs, int64_t J)
-{
-    const int64_t b = resample_base(J, rs->q.up, rs->q.down, rs->q.Kh);
-    return b > 0 ? b : 0;
-}
-
-int bsrnn_resampler_create(bsrnn_ctx* c, int32_t C, int32_t rate_in, int32_t rate_out, bsrnn_resampler** out)
-{
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (!out || C < 1) return fail(BSRNN_EARG, "bsrnn_resampler_create: need C >= 1 rows and a place for the object, got C = %d", C);
-    ResampleRatio q;
-    if (int rc = resample_check_rates(rate_in, rate_out, "bsrnn_resampler_create", q)) return rc;
-    if (int rc = check_device(c)) return rc;
-    CallGuard guard_(c);
-    if (!guard_.ok) return guard_.refuse();
-    const bsrnn_ctx::ResampleTable* t = nullptr;
-    if (int rc = resample_table_of(c, q, &t)) return rc;
-    bsrnn_resampler* rs = new bsrnn_resampler();
-    rs->ctx = c; rs->C = C; rs->q = t->q; rs->g = t->g; rs->tab = t->d;
-    rs->cap = resample_carry_floats(q);
-    rs->cur = 0; rs->N = rs->J = 0;
-    float* p = nullptr;
-    ++g_dbg[DBG_ALLOC];
-    const size_t bytes = 2 * (size_t)C * rs->cap * sizeof(float);
-    hipError_t e = hipMalloc((void**)&p, bytes);
-    if (e == hipSuccess && (e = hipMemset(p, 0, bytes)) != hipSuccess) (void)hipFree(p);
-    if (e != hipSuccess) { delete rs; return fail(BSRNN_EHIP, "bsrnn_resampler_create: %s", hipGetErrorString(e)); }
-    rs->carry[0] = p; rs->carry[1] = p + (size_t)C * rs->cap;
-    // the kernel's first launch (code object loading) happens here, not in the first bsrnn_resampler_process: an empty carry hand-over
-    ResampleArgs a = resample_args(rs->q, rs->g, rs->tab);
-    a.a = rs->carry[0]; a.a_stride = rs->cap; a.carry = rs->carry[1]; a.carry_stride = rs->cap;
-    launch_resample(a, C, nullptr);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) { (void)hipFree(p); delete rs; return fail(BSRNN_EHIP, "bsrnn_resampler_create: %s", hipGetErrorString(e)); }
-    ++c->live_streams;
-    *out = rs;
-    return 0;
-}
-
-void bsrnn_resampler_destroy(bsrnn_resampler* rs)
-{
-    if (!rs) return;
-    bsrnn_ctx* c = rs->ctx;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(rs->carry[0]);
-    delete rs;
-    if (--c->live_streams == 0 && c->zombie) destroy_now(c);     // as bsrnn_stream_destroy: the context goes with the last object that points at it
-}
-
-int bsrnn_resampler_reset(bsrnn_resampler* rs, void* stream)
-{
-    if (!rs) return fail(BSRNN_EARG, "null resampler");
-    (void)stream;          // nothing to enqueue: with no input taken the carry holds no sample a call would read
-    rs->N = rs->J = 0;
-    return 0;
-}
-
-int64_t bsrnn_resampler_ready(const bsrnn_resampler* rs, int64_t n_in)
-{
-    if (!rs || n_in < 0 || n_in > (INT64_MAX >> 12) - rs->N) return -1;
-    return resample_ready(rs->N + n_in, rs->q.up, rs->q.down, rs->q.half) - rs->J;
-}
-
-// process (flush == false): the block joins the carry and the outputs it determines are written; flush: what is left up to the final
-// length, the future taken as zeros.
-static int resampler_run(bsrnn_resampler* rs, const float* in, int64_t in_stride, int64_t n_in, float* out, int64_t out_stride,
-                         int64_t* n_out_host, bool flush, hipStream_t s)
-{
-    const char* who = flush ? "bsrnn_resampler_flush" : "bsrnn_resampler_process";
-    if (!rs) return fail(BSRNN_EARG, "null resampler");
-    if (!n_out_host) return fail(BSRNN_EARG, "%s: nowhere to report the sample count", who);
-    if (n_in < 0 || n_in > (INT64_MAX >> 12) - rs->N) return fail(BSRNN_EARG, "%s: need n_in >= 0 samples, got %lld", who, (long long)n_in);
-    if (n_in > 0 && (!in || in_stride < n_in))
-        return fail(BSRNN_EARG, "%s: need an input block with in_stride >= n_in, got in_stride = %lld, n_in = %lld", who, (long long)in_stride, (long long)n_in);
-    const ResampleRatio& q = rs->q;
-    const int64_t N1 = rs->N + n_in;
-    const int64_t J1 = flush ? resample_n_out(N1, q.up, q.down) : resample_ready(N1, q.up, q.down, q.half);
-    const int64_t count = J1 - rs->J;
-    if (count > 0 && (!out || out_stride < count))
-        return fail(BSRNN_EARG, "%s: need an output block with out_stride >= the %lld samples this call writes per row, got out_stride = %lld", who,
-                    (long long)count, (long long)out_stride);
-    if (n_in > 0 && count > 0 &&
-        ranges_overlap(in, ((size_t)(rs->C - 1) * in_stride + n_in) * sizeof(float), out, ((size_t)(rs->C - 1) * out_stride + count) * sizeof(float)))
-        return fail(BSRNN_EARG, "%s: out_dev must not overlap in_dev (rows are read while others are written)", who);
-    bsrnn_ctx* c = rs->ctx;
-    if (int rc = check_device(c)) return rc;
-    ENTER_CALL(c, s);
-    *n_out_host = count;
-    if (flush) {
-        if (count > 0) {
-            ResampleArgs a = resample_args(q, rs->g, rs->tab);
-            a.a = rs->carry[rs->cur]; a.a_stride = rs->cap; a.a0 = resampler_keep_from(rs, rs->J); a.a1 = rs->N; a.n_total = rs->N;
-            a.out = out; a.out_stride = out_stride; a.j0 = rs->J; a.n_j = count;
-            a.n_tiles = (int)((count + rs->g.tile - 1) / rs->g.tile);
-            launch_resample(a, rs->C, s);
-            HIP_TRY(hipGetLastError());
-        }
-        rs->N = rs->J = 0;
-        return 0;
-    }
-    if (n_in == 0) return 0;
-    ResampleArgs a = resample_args(q, rs->g, rs->tab);
-    a.a = rs->carry[rs->cur]; a.a_stride = rs->cap; a.a0 = resampler_keep_from(rs, rs->J); a.a1 = rs->N;
-    a.b = in; a.b_stride = in_stride; a.n_total = N1;
-    a.out = out; a.out_stride = out_stride; a.j0 = rs->J; a.n_j = count;
-    a.n_tiles = (int)((count + rs->g.tile - 1) / rs->g.tile);
-    a.carry = rs->carry[rs->cur ^ 1]; a.carry_stride = rs->cap; a.c0 = resampler_keep_from(rs, J1);
-    if (N1 - a.c0 > rs->cap) return fail(BSRNN_ESTATE, "%s: the carry would hold %lld samples of %lld (internal error)", who, (long long)(N1 - a.c0), (long long)rs->cap);
-    launch_resample(a, rs->C, s);
-    HIP_TRY(hipGetLastError());
-    rs->N = N1; rs->J = J1; rs->cur ^= 1;
-    return 0;
-}
-
-int bsrnn_resampler_process(bsrnn_resampler* rs, const float* in, int64_t in_stride, int64_t n_in, float* out, int64_t out_stride,
-                            int64_t* n_out_host, void* stream)
-{
-    return resampler_run(rs, in, in_stride, n_in, out, out_stride, n_out_host, false, (hipStream_t)stream);
-}
-
-int bsrnn_resampler_flush(bsrnn_resampler* rs, float* out, int64_t out_stride, int64_t* n_out_host, void* stream)
-{
-    return resampler_run(rs, nullptr, 0, 0, out, out_stride, n_out_host, true, (hipStream_t)stream);
-}
-
-// --------------------------------------------------------------------------- long FIR convolution of ragged rows
-// torch.nn.functional.conv1d(x, h, padding='same') with the whole filter as the kernel (m_dataset.py:92-114: a room impulse response of tens
-// of thousands of taps), as a uniformly partitioned overlap-save convolution on the library's own transform.  The definition, the plan and
-// the row groups: convolve_host.h; the kernels: fft.hip.  A bank holds the partition spectra of its filters, built once.
-struct bsrnn_fir_bank {
-    bsrnn_ctx* ctx;
-    std::vector<int32_t> taps;       // taps per filter
-    std::vector<size_t> off;         // where a filter's image starts in d_images (floats)
-    float* d_images;                 // [sum of P][CONV_LD]; null on a host-only context (the bank then only answers count / taps and refusals)
-};
-
-int bsrnn_fir_bank_create(bsrnn_ctx* c, int32_t n_filters, const float* const* taps_host, const int32_t* n_taps_host, bsrnn_fir_bank** out)
-{
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (!out || !taps_host || !n_taps_host || n_filters < 1)
-        return fail(BSRNN_EARG, "bsrnn_fir_bank_create: need n_filters >= 1 filters (taps_host, n_taps_host) and a place for the object, got n_filters = %d", n_filters);
-    size_t n_taps = 0, n_img = 0;
-    for (int i = 0; i < n_filters; ++i) {
-        if (!taps_host[i]) return fail(BSRNN_EARG, "bsrnn_fir_bank_create: taps_host[%d] is null", i);
-        if (n_taps_host[i] < 1 || n_taps_host[i] > CONV_MAX_TAPS)
-            return fail(BSRNN_EARG, "bsrnn_fir_bank_create: n_taps_host[%d] = %d is outside [1, %d]", i, n_taps_host[i], CONV_MAX_TAPS);
-        n_taps += (size_t)n_taps_host[i];
-        n_img += (size_t)conv_image_floats(n_taps_host[i]);
-    }
-    if (c->zombie) return fail(BSRNN_ESTATE, "context was destroyed");
-    std::unique_ptr<bsrnn_fir_bank> bk(new bsrnn_fir_bank());
-    bk->ctx = c; bk->d_images = nullptr;
-    size_t at = 0;
-    for (int i = 0; i < n_filters; ++i) { bk->taps.push_back(n_taps_host[i]); bk->off.push_back(at); at += (size_t)conv_image_floats(n_taps_host[i]); }
-    if (c->device >= 0) {
-        if (int rc = check_device(c)) return rc;
-        CallGuard guard_(c);
-        if (!guard_.ok) return guard_.refuse();
-        // one allocation: the images, then the taps as the caller gave them (read by the launches below, not kept apart afterwards)
-        float* p = nullptr;
-        ++g_dbg[DBG_ALLOC];
-        hipError_t e = hipMalloc((void**)&p, (n_img + n_taps) * sizeof(float));
-        size_t t_at = n_img;
-        for (int i = 0; e == hipSuccess && i < n_filters; ++i) {
-            e = hipMemcpy(p + t_at, taps_host[i], (size_t)n_taps_host[i] * sizeof(float), hipMemcpyHostToDevice);
-            if (e == hipSuccess) { launch_fir_taps(c->tb, p + t_at, n_taps_host[i], p + bk->off[i], nullptr); e = hipGetLastError(); }
-            t_at += (size_t)n_taps_host[i];
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) { if (p) (void)hipFree(p); return fail(BSRNN_EHIP, "bsrnn_fir_bank_create: %s", hipGetErrorString(e)); }
-        bk->d_images = p;
-    }
-    ++c->live_streams;
-    *out = bk.release();
-    return 0;
-}
-
-void bsrnn_fir_bank_destroy(bsrnn_fir_bank* bk)
-{
-    if (!bk) return;
-    bsrnn_ctx* c = bk->ctx;
-    if (c->device >= 0) {
-        (void)hipSetDevice(c->device);
-        (void)hipDeviceSynchronize();
-        (void)hipFree(bk->d_images);
-    }
-    delete bk;
-    if (--c->live_streams == 0 && c->zombie) destroy_now(c);     // as bsrnn_resampler_destroy
-}
-
-int32_t bsrnn_fir_bank_count(const bsrnn_fir_bank* bk) { return bk ? (int32_t)bk->taps.size() : -1; }
-int32_t bsrnn_fir_bank_taps(const bsrnn_fir_bank* bk, int32_t filter)
-{
-    return (bk && filter >= 0 && filter < (int32_t)bk->taps.size()) ? bk->taps[filter] : -1;
-}
-
-int bsrnn_convolve_ragged(bsrnn_fir_bank* bk, const float* in, int64_t in_stride, const int64_t* lens_host, const int32_t* filter_host, float* out,
-                          int64_t out_stride, int32_t R, void* stream)
-{
-    // arguments first, device or not (a bank of a host-only context answers them before BSRNN_ESTATE)
-    if (!bk) return fail(BSRNN_EARG, "null FIR bank");
-    if (!in || !lens_host || !filter_host || !out)
-        return fail(BSRNN_EARG, "bsrnn_convolve_ragged: null argument (need in_dev, lens_host, filter_host and out_dev)");
-    if (R < 1) return fail(BSRNN_EARG, "bsrnn_convolve_ragged: need R >= 1 rows, got R = %d", R);
-    const int32_t count = (int32_t)bk->taps.size();
-    size_t in_ext = 0, out_ext = 0;                                   // floats the rows span: behind the last row of a view lies somebody else's memory
-    for (int r = 0; r < R; ++r) {
-        const int64_t n = lens_host[r];
-        if (n < 1 || n > CONV_MAX_LEN)
-            return fail(BSRNN_EARG, "bsrnn_convolve_ragged: lens_host[%d] = %lld is outside [1, 2^40]", r, (long long)n);
-        if (in_stride < n)
-            return fail(BSRNN_EARG, "bsrnn_convolve_ragged: in_stride %lld is less than lens_host[%d] = %lld", (long long)in_stride, r, (long long)n);
-        if (out_stride < n)
-            return fail(BSRNN_EARG, "bsrnn_convolve_ragged: out_stride %lld is less than lens_host[%d] = %lld", (long long)out_stride, r, (long long)n);
-        if (filter_host[r] < -1 || filter_host[r] >= count)
-            return fail(BSRNN_EARG, "bsrnn_convolve_ragged: filter_host[%d] = %d is outside [-1, %d)", r, filter_host[r], count);
-        in_ext = std::max(in_ext, (size_t)r * in_stride + (size_t)n);
-        out_ext = std::max(out_ext, (size_t)r * out_stride + (size_t)n);
-    }
-    if (ranges_overlap(in, in_ext * sizeof(float), out, out_ext * sizeof(float)))
-        return fail(BSRNN_EARG, "bsrnn_convolve_ragged: out_dev must not overlap the floats the rows of in_dev span (rows are read while others are written)");
-    bsrnn_ctx* c = bk->ctx;
-    if (int rc = check_device(c)) return rc;
-    for (const void* ptr : {(const void*)in, (const void*)out}) {     // the images live on the bank's device
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); continue; }
-        if (at.type == hipMemoryTypeDevice && at.device != c->device)
-            return fail(BSRNN_EARG, "bsrnn_convolve_ragged: %s lies on device %d, the bank was created on a context of device %d",
-                        ptr == (const void*)in ? "in_dev" : "out_dev", at.device, c->device);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    ENTER_CALL(c, s);
-    // the plan: what every row computes, the row groups, where a row's spectra lie in its group's buffers
-    std::vector<ConvRow> rows(R);
-    std::vector<int64_t> nx(R), nb(R);
-    for (int r = 0; r < R; ++r) {
-        ConvRow& q = rows[r];
-        q = ConvRow{};
-        q.n = lens_host[r];
-        if (filter_host[r] < 0) { q.nb = (int)conv_copy_blocks(q.n); nx[r] = nb[r] = 0; continue; }
-        const int k = bk->taps[filter_host[r]];
-        const ConvPlan pl = conv_plan(q.n, k);
-        q.H = bk->d_images + bk->off[filter_host[r]];
-        q.shift = pl.shift; q.P = pl.P; q.u0 = (int)pl.u0; q.nb = (int)pl.nb; q.f0 = (int)pl.f0; q.nx = (int)pl.nx;
-        nx[r] = pl.nx; nb[r] = pl.nb;
-    }
-    const std::vector<ConvGroup> groups = conv_groups(nx.data(), nb.data(), R);
-    int64_t need = 0;
-    for (const ConvGroup& g : groups) {
-        need = std::max(need, std::max(g.x_frames, g.y_frames));
-        int64_t xo = 0, yo = 0;
-        for (int r = g.first; r < g.first + g.rows; ++r) { rows[r].xoff = xo; rows[r].yoff = yo; xo += nx[r]; yo += nb[r]; }
-    }
-    bsrnn_ctx::Conv& cv = c->cv;
-    if (need > cv.frames) {
-        HIP_TRY(hipDeviceSynchronize());                              // queued kernels use the old buffers
-        if (cv.X) (void)hipFree(cv.X);
-        if (cv.Y) (void)hipFree(cv.Y);
-        cv.X = cv.Y = nullptr; cv.frames = 0;
-        const int64_t want = need >= CONV_FRAME_BUDGET ? need : std::min<int64_t>(CONV_FRAME_BUDGET, need + need / 4 + 16);
-        g_dbg[DBG_ALLOC] += 2;
-        HIP_TRY(hipMalloc((void**)&cv.X, (size_t)want * CONV_LD * sizeof(float)));
-        const hipError_t e = hipMalloc((void**)&cv.Y, (size_t)want * CONV_LD * sizeof(float));
-        if (e != hipSuccess) { (void)hipFree(cv.X); cv.X = nullptr; return fail(BSRNN_EHIP, "hipMalloc: %s", hipGetErrorString(e)); }
-        cv.frames = want;
-    }
-    const char* d = nullptr;
-    const size_t bytes = (size_t)R * sizeof(ConvRow);
-    if (int rc = ragged_upload_block(c, bytes, s, [&](char* h) { memcpy(h, rows.data(), bytes); }, &d)) return rc;
-    const ConvRow* d_rows = reinterpret_cast<const ConvRow*>(d);
-    for (const ConvGroup& g : groups) {
-        int max_nx = 0, max_nb = 0;
-        for (int r = g.first; r < g.first + g.rows; ++r) { max_nx = std::max(max_nx, rows[r].nx); max_nb = std::max(max_nb, rows[r].nb); }
-        launch_fir_group(c->tb, d_rows, g.first, g.rows, max_nx, max_nb, in, in_stride, out, out_stride, cv.X, cv.Y, s);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-// A bank of streaming resamplers: every row on one of the declared pairs and at its own place in its own stream, one launch per call
-// (per BANK_GROUP_ROWS rows).  The per-row arithmetic: resample_bank_host.h; the kernel: resample_bank_kernel of resample.hip.
-struct bsrnn_resampler_bank {
-    bsrnn_ctx* ctx;
-    int C, n_pairs;
-    ResampleRatio q[BANK_PAIRS_MAX];
-    int tile[BANK_PAIRS_MAX];
-    BankPair* pairs;                 // [n_pairs] on the device, written by _create and constant afterwards
-    float* carry;                    // two sets of C * cap floats; row r's current set is pos[r].cur
-    int64_t cap;                     // the largest resample_carry_floats of the declared pairs
-    std::vector<BankPos> pos, next;  // [C]: where every row stands; next is a call's scratch (nothing is allocated after _create)
-    std::vector<BankRow> desc;       // [C], a call's descriptors
-    std::vector<uint8_t> seen;       // [C], for "a row listed twice"
-};
-
-// rows_host [n_rows] -> seen[] marks them; refuses a null list, a row outside [0, C) and a row listed twice
-static int bank_mark_rows(bsrnn_resampler_bank* bk, const int32_t* rows, int32_t n_rows, const char* who)
-{
-    if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(BSRNN_EARG, "%s: need a list of n_rows >= 0 rows, got n_rows = %d", who, n_rows);
-    std::fill(bk->seen.begin(), bk->seen.end(), (uint8_t)0);
-    for (int i = 0; i < n_rows; ++i) {
-        const int32_t r = rows[i];
-        if (r < 0 || r >= bk->C) return fail(BSRNN_EARG, "%s: row %d (entry %d of the list) is outside [0, %d)", who, r, i, bk->C);
-        if (bk->seen[r]) return fail(BSRNN_EARG, "%s: row %d is listed twice", who, r);
-        bk->seen[r] = 1;
-    }
-    return 0;
-}
-
-int bsrnn_resampler_bank_create(bsrnn_ctx* c, int32_t C, const int32_t* rates_in, const int32_t* rates_out, int32_t n_pairs,
-                                bsrnn_resampler_bank** out)
-{
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (!out || C < 1) return fail(BSRNN_EARG, "bsrnn_resampler_bank_create: need C >= 1 rows and a place for the object, got C = %d", C);
-    if (n_pairs < 1 || n_pairs > BANK_PAIRS_MAX)
-        return fail(BSRNN_EARG, "bsrnn_resampler_bank_create: n_pairs = %d is outside [1, %d]", n_pairs, BANK_PAIRS_MAX);
-    if (!rates_in || !rates_out) return fail(BSRNN_EARG, "bsrnn_resampler_bank_create: need the %d rate pairs", n_pairs);
-    ResampleRatio q[BANK_PAIRS_MAX];
-    for (int k = 0; k < n_pairs; ++k)
-        if (int rc = resample_check_rates(rates_in[k], rates_out[k], "bsrnn_resampler_bank_create", q[k])) return rc;
-    if (int rc = check_device(c)) return rc;
-    CallGuard guard_(c);
-    if (!guard_.ok) return guard_.refuse();
-    std::unique_ptr<bsrnn_resampler_bank> bk(new bsrnn_resampler_bank());
-    bk->ctx = c; bk->C = C; bk->n_pairs = n_pairs; bk->cap = 0;
-    BankPair host[BANK_PAIRS_MAX];
-    for (int k = 0; k < n_pairs; ++k) {
-        const bsrnn_ctx::ResampleTable* t = nullptr;
-        if (int rc = resample_table_of(c, q[k], &t)) return rc;
-        bk->q[k] = t->q; bk->tile[k] = t->g.tile;
-        host[k] = BankPair{t->d, (int)t->q.up, (int)t->q.down, t->q.Kh, t->g.ld, t->g.chunk, t->g.tile};
-        bk->cap = std::max(bk->cap, resample_carry_floats(t->q));
-    }
-    bk->pos.assign(C, BankPos());
-    bk->next.assign(C, BankPos());
-    bk->desc.assign(C, BankRow{0, 0, 0, 0, 0});
-    bk->seen.assign(C, 0);
-    // one allocation: the pair table (512 bytes), then the two carry sets
-    char* p = nullptr;
-    ++g_dbg[DBG_ALLOC];
-    const size_t head = BANK_PAIRS_MAX * sizeof(BankPair), bytes = head + 2 * (size_t)C * bk->cap * sizeof(float);
-    hipError_t e = hipMalloc((void**)&p, bytes);
-    if (e == hipSuccess && (e = hipMemset(p, 0, bytes)) == hipSuccess) e = hipMemcpy(p, host, n_pairs * sizeof(BankPair), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        bk->pairs = (BankPair*)p; bk->carry = (float*)(p + head);
-        // the kernel's first launch (code object loading) happens here: every row hands an empty carry over (a block of nothing)
-        for (int r = 0; r < C; ++r) bk->desc[r] = BankRow{0, 0, 0, 0, BANK_ROW_RUNS | BANK_ROW_CARRIES};
-        BankLaunch L{bk->pairs, nullptr, 0, nullptr, 0, bk->carry, bk->cap, (int64_t)C * bk->cap, 0};
-        launch_resample_bank(L, bk->tile, bk->desc.data(), C, nullptr);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    }
-    if (e != hipSuccess) { (void)hipFree(p); return fail(BSRNN_EHIP, "bsrnn_resampler_bank_create: %s", hipGetErrorString(e)); }
-    ++c->live_streams;
-    *out = bk.release();
-    return 0;
-}
-
-void bsrnn_resampler_bank_destroy(bsrnn_resampler_bank* bk)
-{
-    if (!bk) return;
-    bsrnn_ctx* c = bk->ctx;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(bk->pairs);
-    delete bk;
-    if (--c->live_streams == 0 && c->zombie) destroy_now(c);     // as bsrnn_resampler_destroy
-}
-
-int bsrnn_resampler_bank_assign(bsrnn_resampler_bank* bk, const int32_t* rows, int32_t n_rows, int32_t pair)
-{
-    if (!bk) return fail(BSRNN_EARG, "null resampler bank");
-    if (pair < 0 || pair >= bk->n_pairs) return fail(BSRNN_EARG, "bsrnn_resampler_bank_assign: pair %d is outside [0, %d)", pair, bk->n_pairs);
-    if (int rc = bank_mark_rows(bk, rows, n_rows, "bsrnn_resampler_bank_assign")) return rc;
-    // nothing to enqueue, as bsrnn_resampler_reset: with no input taken the carry holds no sample a call would read
-    for (int i = 0; i < n_rows; ++i) bank_row_assign(bk->pos[rows[i]], pair);
-    return 0;
-}
-
-int bsrnn_resampler_bank_reset_rows(bsrnn_resampler_bank* bk, const int32_t* rows, int32_t n_rows)
-{
-    if (!bk) return fail(BSRNN_EARG, "null resampler bank");
-    if (int rc = bank_mark_rows(bk, rows, n_rows, "bsrnn_resampler_bank_reset_rows")) return rc;
-    for (int i = 0; i < n_rows; ++i) bank_row_reset(bk->pos[rows[i]]);
-    return 0;
-}
-
-int bsrnn_resampler_bank_pair_of(const bsrnn_resampler_bank* bk, int32_t row)
-{
-    return bk && row >= 0 && row < bk->C ? bk->pos[row].pair : -1;
-}
-
-int64_t bsrnn_resampler_bank_ready(const bsrnn_resampler_bank* bk, int32_t row, int64_t n_in)
-{
-    if (!bk || row < 0 || row >= bk->C) return -1;
-    const BankPos& p = bk->pos[row];
-    if (n_in < 0 || n_in > (INT64_MAX >> 12) - p.N) return -1;
-    return bank_row_ready(bk->q[p.pair], p, n_in);
-}
-
-// process (rows == null: every row takes n_in[r]) or flush (the rows marked in seen[]): descriptors and next positions first, then
-// every refusal, then the launches
-static int bank_run(bsrnn_resampler_bank* bk, const float* in, int64_t in_stride, const int64_t* n_in, float* out, int64_t out_stride,
-                    int64_t* n_out_host, bool flush, hipStream_t s)
-{
-    const char* who = flush ? "bsrnn_resampler_bank_flush_rows" : "bsrnn_resampler_bank_process";
-    if (!n_out_host) return fail(BSRNN_EARG, "%s: nowhere to report the sample counts", who);
-    if (!flush && !n_in) return fail(BSRNN_EARG, "%s: need the rows' sample counts", who);
-    int64_t max_in = 0, max_out = 0;
-    for (int r = 0; r < bk->C; ++r) {
-        const BankPos& p = bk->pos[r];
-        const ResampleRatio& q = bk->q[p.pair];
-        const int64_t n = flush ? 0 : n_in[r];
-        const int why = flush ? (bk->seen[r] ? bank_row_flush(q, p, bk->desc[r], bk->next[r]) : bank_row_process(q, p, 0, bk->desc[r], bk->next[r]))
-                              : bank_row_process(q, p, n, bk->desc[r], bk->next[r]);
-        if (why == BANK_BAD_COUNT) return fail(BSRNN_EARG, "%s: need n_in >= 0 samples for every row, got %lld for row %d", who, (long long)n, r);
-        if (why == BANK_BLOCK_TOO_LONG)
-            return fail(BSRNN_EARG, "%s: row %d would take %lld samples or give more than %lld; one call moves at most %lld per row", who, r,
-                        (long long)n, (long long)BANK_BLOCK_MAX, (long long)BANK_BLOCK_MAX);
-        if (why != BANK_OK) return fail(BSRNN_ESTATE, "%s: the carry of row %d would overflow (internal error)", who, r);
-        max_in = std::max(max_in, n);
-        max_out = std::max(max_out, (int64_t)bk->desc[r].n_j);
-    }
-    if (max_in > 0 && (!in || in_stride < max_in))
-        return fail(BSRNN_EARG, "%s: need an input block with in_stride >= the largest count, got in_stride = %lld, largest n_in = %lld", who,
-                    (long long)in_stride, (long long)max_in);
-    if (max_out > 0 && (!out || out_stride < max_out))
-        return fail(BSRNN_EARG, "%s: need an output block with out_stride >= the %lld samples this call writes to a row, got out_stride = %lld", who,
-                    (long long)max_out, (long long)out_stride);
-    if (max_in > 0 && max_out > 0 &&
-        ranges_overlap(in, ((size_t)(bk->C - 1) * in_stride + max_in) * sizeof(float), out, ((size_t)(bk->C - 1) * out_stride + max_out) * sizeof(float)))
-        return fail(BSRNN_EARG, "%s: out_dev must not overlap the span of in_dev (rows are read while others are written)", who);
-    bsrnn_ctx* c = bk->ctx;
-    if (int rc = check_device(c)) return rc;
-    ENTER_CALL(c, s);
-    for (int r = 0; r < bk->C; ++r) n_out_host[r] = bk->desc[r].n_j;
-    BankLaunch L{bk->pairs, max_in > 0 ? in : nullptr, in_stride, out, out_stride, bk->carry, bk->cap, (int64_t)bk->C * bk->cap, 0};
-    launch_resample_bank(L, bk->tile, bk->desc.data(), bk->C, s);
-    HIP_TRY(hipGetLastError());
-    bk->pos.swap(bk->next);
-    return 0;
-}
-
-int bsrnn_resampler_bank_process(bsrnn_resampler_bank* bk, const float* in, int64_t in_stride, const int64_t* n_in_host, float* out,
-                                 int64_t out_stride, int64_t* n_out_host, void* stream)
-{
-    if (!bk) return fail(BSRNN_EARG, "null resampler bank");
-    return bank_run(bk, in, in_stride, n_in_host, out, out_stride, n_out_host, false, (hipStream_t)stream);
-}
-
-int bsrnn_resampler_bank_flush_rows(bsrnn_resampler_bank* bk, const int32_t* rows, int32_t n_rows, float* out, int64_t out_stride,
-                                    int64_t* n_out_host, void* stream)
-{
-    if (!bk) return fail(BSRNN_EARG, "null resampler bank");
-    if (int rc = bank_mark_rows(bk, rows, n_rows, "bsrnn_resampler_bank_flush_rows")) return rc;
-    return bank_run(bk, nullptr, 0, nullptr, out, out_stride, n_out_host, true, (hipStream_t)stream);
-}
-
-// --------------------------------------------------------------------------- the native session pool
-// Slots, pending counts and the round plan: pool_host.h; the two copy kernels: pool.hip.  A pool owns ONE wide bsrnn_stream and, on the
-// device, the two rectangles of its hops calls, a FIFO row per stream row and the table block; per round of a feed it uploads the
-// table, launches the gather, makes one bsrnn_stream_process_hops and launches the scatter, all on the caller's stream.
-struct bsrnn_pool {
-    bsrnn_ctx* ctx = nullptr;
-    bsrnn_stream* st = nullptr;
-    int slots = 0, rows = 0, C = 0, max_hops = 0;
-    PoolSlots sl;
-    // One device allocation: [chunk C x max_hops*1024 | out, the same | fifo C x 1024 | staging in C x (max_hops+1)*1024 | staging out
-    // C x max_hops*1024 | table block: C entries, then C wet/dry values].  One pinned allocation: [MIRRORS table blocks | staging in |
-    // staging out].  The table block travels as bsrnn_ctx::Ragged's does: mirror k is written again only when the copy that read it
-    // has completed (ev[k]), so the caller's arrays are free at return and feeds still queue up behind each other.
-    static constexpr int MIRRORS = 8;
-    float *base = nullptr, *chunk = nullptr, *out = nullptr, *fifo = nullptr, *d_hin = nullptr, *d_hout = nullptr;
-    char* d_tab = nullptr;
-    char* h_base = nullptr;
-    float *h_in = nullptr, *h_out = nullptr;
-    size_t tab_bytes = 0;
-    unsigned uploads = 0;
-    hipEvent_t ev[MIRRORS] = {};
-    hipStream_t last = nullptr;        // the stream of the last feed: bsrnn_pool_open resets its rows in that stream's order
-    bool reset_queued = false;         // ... and a feed on another stream waits for that stream first
-    // a call's scratch, sized at create (no feed allocates)
-    std::vector<uint8_t> seen;                                 // [slots]
-    std::vector<int32_t> counts;                               // [C]
-    struct Span { uintptr_t a, e; int32_t i; };
-    std::vector<Span> spans;                                   // [slots]: the input ranges of a call, by start, with a running largest end
-    // What the rounds of a call read and write per session of the call ([slots]; filled by its checks): a session at the model's rate
-    // brings the caller's pointers and count, a session with a rate its rows of conv_in / conv_out and the count the inbound bank gives
-    struct View { const float* in; float* out; int64_t in_stride, out_stride, n; int32_t drop; };
-    std::vector<View> view;
-    // Sessions at their own sample rates (bsrnn_pool_create_rates; pool_rates_host.h).  bin == null: a pool without.  A second device
-    // allocation: [conv_in C x cap_in | conv_out C x cap_out | two tables of C pointers, the bank launches' pointer form].  The pointer
-    // tables travel through the tail of a table mirror (ptr_off), once per call that names such a session.
-    int n_rates = 0;
-    int32_t rate[BANK_PAIRS_MAX] = {};
-    int64_t max_block = 0, cap_in = 0, cap_out = 0;
-    bsrnn_resampler_bank *bin = nullptr, *bout = nullptr;      // rate -> 44100 and 44100 -> rate, C rows each
-    float *conv_base = nullptr, *conv_in = nullptr, *conv_out = nullptr;
-    char* d_ptrs = nullptr;
-    size_t ptr_off = 0;
-    std::vector<int32_t> pair;                                 // [slots]: the session's pair, -1 at the model's rate
-    std::vector<int32_t> skip;                                 // [slots]: samples of the stream's delay still to be dropped, 1024 or 0
-};
-
-static int64_t pool_row_span_bytes(int rows, int64_t stride, int64_t n) { return n > 0 ? ((int64_t)(rows - 1) * stride + n) * (int64_t)sizeof(float) : 0; }
-
-static int pool_next_mirror(bsrnn_pool* pl, char** h, int* k);
-
-// ---- sessions with a rate: the two banks' descriptors of a call (host arithmetic, scratch of the banks: nothing of it counts until
-// pool_rates_launch)
-static void pool_rates_hold_all(bsrnn_pool* pl)
-{
-    for (bsrnn_resampler_bank* bk : {pl->bin, pl->bout})
-        for (int r = 0; r < pl->C; ++r) { bk->desc[r] = bank_row_hold(bk->pos[r]); bk->next[r] = bk->pos[r]; }
-}
-// The slot's rows take n samples inbound and b outbound
-static int pool_rates_describe(bsrnn_pool* pl, const char* who, int i, int32_t slot, int64_t n, int64_t b)
-{
-    const int k = pl->pair[slot];
-    for (int rr = 0; rr < pl->rows; ++rr) {
-        const int r = slot * pl->rows + rr;
-        if (bank_row_process(pl->bin->q[k], pl->bin->pos[r], n, pl->bin->desc[r], pl->bin->next[r]) != BANK_OK ||
-            bank_row_process(pl->bout->q[k], pl->bout->pos[r], b, pl->bout->desc[r], pl->bout->next[r]) != BANK_OK)
-            return fail(BSRNN_EARG, "%s: session %d (slot %d): %lld samples at %d Hz are more than its resamplers can still take", who, i, slot,
-                        (long long)n, pl->rate[k]);
-    }
-    return 0;
-}
-// The pointer tables of a call, through the tail of a table mirror: first [C] then second [C] (entries of rows that do not run are never read)
-static int pool_rates_pointers(bsrnn_pool* pl, const float*** first, float*** second, int* k)
-{
-    char* h = nullptr;
-    if (int rc = pool_next_mirror(pl, &h, k)) return rc;
-    *first = reinterpret_cast<const float**>(h + pl->ptr_off);
-    *second = reinterpret_cast<float**>(h + pl->ptr_off) + pl->C;
-    std::fill(*first, *first + 2 * (size_t)pl->C, nullptr);
-    return 0;
-}
-static int pool_rates_upload(bsrnn_pool* pl, int k, hipStream_t s)
-{
-    HIP_TRY(hipMemcpyAsync(pl->d_ptrs, pl->h_base + (size_t)k * pl->tab_bytes + pl->ptr_off, 2 * (size_t)pl->C * sizeof(void*), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(pl->ev[k], s));
-    return 0;
-}
-// One launch of a bank with the descriptors in its scratch; afterwards its rows stand where the descriptors leave them
-static int pool_rates_launch(bsrnn_pool* pl, bsrnn_resampler_bank* bk, const float* in, int64_t in_stride, const float* const* in_rows, float* out,
-                             int64_t out_stride, float* const* out_rows, hipStream_t s)
-{
-    BankLaunch L{bk->pairs, in, in_stride, out, out_stride, bk->carry, bk->cap, (int64_t)pl->C * bk->cap, 0, in_rows, out_rows};
-    launch_resample_bank(L, bk->tile, bk->desc.data(), pl->C, s);
-    HIP_TRY(hipGetLastError());
-    bk->pos.swap(bk->next);
-    return 0;
-}
-
-// Everything a feed refuses, before any device work; fills n_out[i], *h_max and the sessions' views.  who: the entry point's name.
-static int pool_check_feed(bsrnn_pool* pl, const char* who, int32_t n, const int32_t* slots, const float* const* in, const int64_t* in_stride,
-                           const int64_t* n_in, float* const* out, const int64_t* out_stride, int64_t* n_out, int64_t* h_max, bool host_form,
-                           bool* any_rated)
-{
-    if (!slots || !in || !in_stride || !n_in || !out || !out_stride || !n_out)
-        return fail(BSRNN_EARG, "%s: null argument (the slots, the pointers, strides and counts of both sides and n_out_host are needed)", who);
-    if (n > pl->slots) return fail(BSRNN_EARG, "%s: n_sessions = %d, the pool has %d slots", who, n, pl->slots);
-    std::fill(pl->seen.begin(), pl->seen.end(), (uint8_t)0);
-    *h_max = 0;
-    *any_rated = false;
-    if (pl->bin) pool_rates_hold_all(pl);
-    for (int i = 0; i < n; ++i) {
-        const int32_t slot = slots[i];
-        if (!pool_slot_is_open(pl->sl, slot)) return fail(BSRNN_EARG, "%s: session %d names slot %d, which is not open", who, i, slot);
-        if (pl->seen[slot]) return fail(BSRNN_EARG, "%s: session %d names slot %d, which an earlier session of the call names too", who, i, slot);
-        pl->seen[slot] = 1;
-        if (n_in[i] < 0 || n_in[i] > (INT64_MAX >> 12))
-            return fail(BSRNN_EARG, "%s: session %d (slot %d) brings n_in = %lld samples, need 0 or more", who, i, slot, (long long)n_in[i]);
-        if (in_stride[i] < n_in[i])
-            return fail(BSRNN_EARG, "%s: session %d (slot %d): in_stride = %lld is below its %lld samples", who, i, slot, (long long)in_stride[i],
-                        (long long)n_in[i]);
-        if (n_in[i] > 0 && !in[i]) return fail(BSRNN_EARG, "%s: session %d (slot %d) brings %lld samples from a null pointer", who, i, slot, (long long)n_in[i]);
-        const int k = pl->pair[slot];
-        PoolRateFeed f;
-        if (k < 0) {
-            f = pool_plain_feed(pl->sl.pending[slot], n_in[i]);
-            pl->view[i] = {in[i], out[i], in_stride[i], out_stride[i], n_in[i], 0};
-        } else {
-            // a session with a rate: its samples count at that rate, the rounds see its rows of the staging rectangles
-            if (host_form)
-                return fail(BSRNN_EARG, "%s: session %d (slot %d) has a sample rate of its own (%d Hz); the host form serves sessions at the "
-                                        "model's rate, feed it with bsrnn_pool_feed", who, i, slot, pl->rate[k]);
-            if (n_in[i] > pl->max_block)
-                return fail(BSRNN_EARG, "%s: session %d (slot %d) brings n_in = %lld samples at %d Hz, the pool was created for max_block = %lld",
-                            who, i, slot, (long long)n_in[i], pl->rate[k], (long long)pl->max_block);
-            const int row0 = slot * pl->rows;
-            f = pool_rate_feed(pl->bin->q[k], pl->bout->q[k], PoolRateSess{pl->bin->pos[row0], pl->bout->pos[row0], pl->skip[slot]},
-                               pl->sl.pending[slot], n_in[i]);
-            pl->view[i] = {pl->conv_in + (size_t)row0 * pl->cap_in, pl->conv_out + (size_t)row0 * pl->cap_out, pl->cap_in, pl->cap_out, f.a,
-                           f.drop};
-            if (int rc = pool_rates_describe(pl, who, i, slot, n_in[i], f.b)) return rc;
-            *any_rated = true;
-        }
-        n_out[i] = f.n_out;
-        if (out_stride[i] < n_out[i])
-            return fail(BSRNN_EARG, "%s: session %d (slot %d): out_stride = %lld is below the %lld samples it gets", who, i, slot,
-                        (long long)out_stride[i], (long long)n_out[i]);
-        if (n_out[i] > 0 && !out[i]) return fail(BSRNN_EARG, "%s: session %d (slot %d) gets %lld samples at a null pointer", who, i, slot, (long long)n_out[i]);
-        *h_max = std::max(*h_max, f.hops);
-    }
-    // no output range of the call may share a byte with any input range of the call: inputs by start with a running largest end, then one
-    // binary search per output
-    pl->spans.clear();
-    for (int i = 0; i < n; ++i) {
-        const int64_t nb = pool_row_span_bytes(pl->rows, in_stride[i], n_in[i]);
-        if (nb) pl->spans.push_back({(uintptr_t)in[i], (uintptr_t)in[i] + (uintptr_t)nb, i});
-    }
-    std::sort(pl->spans.begin(), pl->spans.end(), [](const bsrnn_pool::Span& x, const bsrnn_pool::Span& y) { return x.a < y.a; });
-    for (size_t k = 1; k < pl->spans.size(); ++k)
-        if (pl->spans[k].e < pl->spans[k - 1].e) { pl->spans[k].e = pl->spans[k - 1].e; pl->spans[k].i = pl->spans[k - 1].i; }
-    for (int i = 0; i < n && !pl->spans.empty(); ++i) {
-        const int64_t nb = pool_row_span_bytes(pl->rows, out_stride[i], n_out[i]);
-        if (!nb) continue;
-        const uintptr_t a = (uintptr_t)out[i], e = a + (uintptr_t)nb;
-        // the last input that starts below the output's end; the running end says whether it, or one before it, reaches the output
-        size_t lo = 0, hi = pl->spans.size();
-        while (lo < hi) { const size_t mid = (lo + hi) / 2; if (pl->spans[mid].a < e) lo = mid + 1; else hi = mid; }
-        if (lo > 0 && pl->spans[lo - 1].e > a)
-            return fail(BSRNN_EARG, "%s: the output of session %d (slot %d) overlaps the input of session %d (slot %d); a later round reads input "
-                                    "behind what an earlier one has written, so in place is not offered", who, i, slots[i], pl->spans[lo - 1].i,
-                        slots[pl->spans[lo - 1].i]);
-    }
-    return 0;
-}
-
-// The slot's session is on `pair` (-1: at the model's rate) from now on and at the beginning of its audio: host-only, as
-// bsrnn_resampler_bank_assign - with no input taken the carries hold no sample a call would read.
-static void pool_rates_assign(bsrnn_pool* pl, int slot, int pair)
-{
-    pl->pair[slot] = pair;
-    pl->skip[slot] = pair < 0 ? 0 : POOL_HOP;
-    if (!pl->bin) return;
-    for (int rr = 0; rr < pl->rows; ++rr) {
-        const int r = slot * pl->rows + rr;
-        bank_row_assign(pl->bin->pos[r], pair < 0 ? 0 : pair);
-        bank_row_assign(pl->bout->pos[r], pair < 0 ? 0 : pair);
-    }
-}
-
-// The next table mirror, once the copy that last read it has completed
-static int pool_next_mirror(bsrnn_pool* pl, char** h, int* k)
-{
-    *k = (int)(pl->uploads++ % bsrnn_pool::MIRRORS);
-    HIP_TRY(hipEventSynchronize(pl->ev[*k]));
-    *h = pl->h_base + (size_t)*k * pl->tab_bytes;
-    return 0;
-}
-
-// One feed behind its argument checks.  host_form: in / out are host pointers; each round's samples go through the pinned staging.
-// What the sessions bring and where their hops go: pl->view (a session with a rate: its rows of conv_in and conv_out, and in the round of
-// its first hop since open or drain that hop is not handed on).
-static int pool_feed_rounds(bsrnn_pool* pl, int32_t n, const int32_t* slots, int64_t h_max, const float* mix_host, float mix, hipStream_t s,
-                            bool host_form)
-{
-    const int C = pl->C, R = pl->rows, mh = pl->max_hops;
-    const size_t SI = (size_t)(mh + 1) * POOL_HOP, SO = (size_t)mh * POOL_HOP;      // row strides of the staging blocks
-    const int64_t rounds = pool_rounds(h_max, mh);
-    float* d_mix = reinterpret_cast<float*>(pl->d_tab + (size_t)C * sizeof(PoolEntry));
-    for (int64_t j = 0; j < rounds; ++j) {
-        const int L = pool_round_hops(h_max, mh, j);
-        char* h = nullptr;
-        int k = 0;
-        if (int rc = pool_next_mirror(pl, &h, &k)) return rc;
-        PoolEntry* tab = reinterpret_cast<PoolEntry*>(h);
-        float* h_mix = reinterpret_cast<float*>(h + (size_t)C * sizeof(PoolEntry));
-        std::fill(pl->counts.begin(), pl->counts.end(), 0);
-        if (mix_host) std::fill(h_mix, h_mix + C, 1.0f);
-        int n_ent = 0, r_lo = C, r_hi = -1;
-        for (int i = 0; i < n; ++i) {
-            const int32_t slot = slots[i];
-            const bsrnn_pool::View& v = pl->view[i];
-            const PoolPart q = pool_part(pl->sl.pending[slot], v.n, mh, j);
-            for (int rr = 0; rr < R; ++rr) {
-                const int row = slot * R + rr;
-                pl->counts[row] = q.hops;
-                if (mix_host) h_mix[row] = mix_host[i];
-                if (j > 0 && q.hops == 0) continue;         // (done in an earlier round: its rows are held and their rectangle rows never read)
-                const float* in_row = v.in ? v.in + (size_t)rr * v.in_stride : nullptr;
-                if (!host_form) {
-                    PoolEntry e = pool_entry(q, row, in_row, v.out ? v.out + (size_t)rr * v.out_stride : nullptr);
-                    if (v.drop && q.hops) {                 // the dropped hop is the first of round 0; what follows moves up by it
-                        if (q.out_off == 0) e.out_skip = v.drop;
-                        else e.dst -= v.drop;
-                    }
-                    tab[n_ent++] = e;
-                    continue;
-                }
-                // host form: this round's samples of the row, [for the rectangle | for the FIFO], into the staging row; the entry names its mirror
-                float* stage = pl->h_in + (size_t)row * SI;
-                if (q.n_in) memcpy(stage, in_row + q.in_off, (size_t)q.n_in * sizeof(float));
-                if (q.n_pend) memcpy(stage + q.n_in, in_row + q.pend_src, (size_t)q.n_pend * sizeof(float));
-                PoolEntry e = pool_entry(q, row, nullptr, nullptr);
-                e.src = pl->d_hin + (size_t)row * SI;
-                e.pend_src = e.src + q.n_in;
-                e.dst = pl->d_hout + (size_t)row * SO;
-                tab[n_ent++] = e;
-                if (q.n_in || q.n_pend) { r_lo = std::min(r_lo, row); r_hi = std::max(r_hi, row); }
-            }
-        }
-        if (host_form && r_hi >= r_lo)
-            HIP_TRY(hipMemcpyAsync(pl->d_hin + (size_t)r_lo * SI, pl->h_in + (size_t)r_lo * SI, (size_t)(r_hi - r_lo + 1) * SI * sizeof(float),
-                                   hipMemcpyHostToDevice, s));
-        const size_t bytes = mix_host ? (size_t)C * (sizeof(PoolEntry) + sizeof(float)) : (size_t)std::max(n_ent, 1) * sizeof(PoolEntry);
-        HIP_TRY(hipMemcpyAsync(pl->d_tab, h, bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(pl->ev[k], s));
-        launch_pool_gather(reinterpret_cast<const PoolEntry*>(pl->d_tab), n_ent, pl->chunk, pl->fifo, L, s);
-        HIP_TRY(hipGetLastError());
-        if (L == 0) continue;                               // nobody has a hop: the feed was this one launch
-        // the FIFO has been written; the hops call reads the pool's own rectangle, so a re-run of the range policy consumes nothing twice
-        if (int rc = bsrnn_stream_process_hops(pl->st, pl->chunk, pl->out, L, pl->counts.data(), mix_host ? d_mix : nullptr, mix_host ? 1.0f : mix, s))
-            return rc;
-        launch_pool_scatter(reinterpret_cast<const PoolEntry*>(pl->d_tab), n_ent, pl->out, L, s);
-        HIP_TRY(hipGetLastError());
-        if (!host_form) continue;
-        r_lo = C; r_hi = -1;
-        for (int e = 0; e < n_ent; ++e)
-            if (tab[e].n_out) { r_lo = std::min(r_lo, (int)tab[e].row); r_hi = std::max(r_hi, (int)tab[e].row); }
-        HIP_TRY(hipMemcpyAsync(pl->h_out + (size_t)r_lo * SO, pl->d_hout + (size_t)r_lo * SO, (size_t)(r_hi - r_lo + 1) * SO * sizeof(float),
-                               hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        for (int i = 0; i < n; ++i) {
-            const bsrnn_pool::View& v = pl->view[i];
-            const PoolPart q = pool_part(pl->sl.pending[slots[i]], v.n, mh, j);
-            for (int rr = 0; rr < R && q.hops; ++rr)
-                memcpy(v.out + (size_t)rr * v.out_stride + q.out_off, pl->h_out + (size_t)(slots[i] * R + rr) * SO, (size_t)q.hops * POOL_HOP * sizeof(float));
-        }
-    }
-    for (int i = 0; i < n; ++i) {
-        pl->sl.pending[slots[i]] = pool_pending_after(pl->sl.pending[slots[i]], pl->view[i].n);
-        pl->skip[slots[i]] -= pl->view[i].drop;
-    }
-    return 0;
-}
-
-static int pool_feed(bsrnn_pool* pl, const char* who, int32_t n, const int32_t* slots, const float* const* in, const int64_t* in_stride,
-                     const int64_t* n_in, float* const* out, const int64_t* out_stride, int64_t* n_out, const float* mix_host, float mix,
-                     hipStream_t s, bool host_form)
-{
-    if (!pl) return fail(BSRNN_EARG, "%s: null pool", who);
-    if (n < 0) return fail(BSRNN_EARG, "%s: n_sessions = %d", who, n);
-    if (n == 0) return 0;
-    int64_t h_max = 0;
-    bool any_rated = false;
-    if (int rc = pool_check_feed(pl, who, n, slots, in, in_stride, n_in, out, out_stride, n_out, &h_max, host_form, &any_rated)) return rc;
-    bsrnn_ctx* c = pl->ctx;
-    if (int rc = check_ready(c)) return rc;
-    ENTER_CALL(c, s);
-    if (pl->reset_queued && pl->last != s) HIP_TRY(hipStreamSynchronize(pl->last));      // (rows that bsrnn_pool_open reset in another stream's order)
-    pl->reset_queued = false;
-    pl->last = s;
-    if (!host_form && !any_rated) return pool_feed_rounds(pl, n, slots, h_max, mix_host, mix, s, false);
-    if (!host_form) {
-        // Sessions with a rate are named.  ONE inbound launch: every such session's samples, at its own pointer, to its rows of conv_in
-        // at 44.1 kHz; the rounds, which read conv_in and write conv_out for them; ONE outbound launch: conv_out to the sessions' pointers.
-        const float** p_in = nullptr;
-        float** p_out = nullptr;
-        int k = 0;
-        if (int rc = pool_rates_pointers(pl, &p_in, &p_out, &k)) return rc;
-        for (int i = 0; i < n; ++i) {
-            if (pl->pair[slots[i]] < 0) continue;
-            for (int rr = 0; rr < pl->rows; ++rr) {
-                const int row = slots[i] * pl->rows + rr;
-                if (n_in[i] > 0) p_in[row] = in[i] + (size_t)rr * in_stride[i];
-                if (n_out[i] > 0) p_out[row] = out[i] + (size_t)rr * out_stride[i];
-            }
-        }
-        if (int rc = pool_rates_upload(pl, k, s)) return rc;
-        const float* const* d_in = reinterpret_cast<const float* const*>(pl->d_ptrs);
-        float* const* d_out = reinterpret_cast<float* const*>(pl->d_ptrs) + pl->C;
-        if (int rc = pool_rates_launch(pl, pl->bin, nullptr, 0, d_in, pl->conv_in, pl->cap_in, nullptr, s)) return rc;
-        if (int rc = pool_feed_rounds(pl, n, slots, h_max, mix_host, mix, s, false)) return rc;
-        return pool_rates_launch(pl, pl->bout, pl->conv_out, pl->cap_out, nullptr, nullptr, 0, d_out, s);
-    }
-    // the host form waits for its own kernels anyway, so it repairs a range violation whatever the policy says (as bsrnn_stream_step_host)
-    const int keep = c->range_policy;
-    c->range_policy = BSRNN_RANGE_EXACT;
-    int rc = pool_feed_rounds(pl, n, slots, h_max, mix_host, mix, s, true);
-    c->range_policy = keep;
-    if (!rc) HIP_TRY(hipStreamSynchronize(s));
-    return rc;
-}
-
-// rated: the table block's mirrors also carry the two pointer tables of a call that names sessions with a rate
-static int pool_create(bsrnn_ctx* c, int32_t slots, int32_t rows_per_session, int32_t max_hops, bool rated, bsrnn_pool** out)
-{
-    if (!c) return fail(BSRNN_EARG, "bsrnn_pool_create: null context");
-    if (!out || slots < 1 || rows_per_session < 1)
-        return fail(BSRNN_EARG, "bsrnn_pool_create: need slots >= 1, rows_per_session >= 1 and a place for the object, got %d x %d", slots, rows_per_session);
-    if ((int64_t)slots * rows_per_session > STREAM_ROWS_MAX)
-        return fail(BSRNN_EARG, "bsrnn_pool_create: %d slots x %d rows is more than BSRNN_STREAM_ROWS_MAX = %d rows", slots, rows_per_session, STREAM_ROWS_MAX);
-    if (max_hops < 1 || max_hops > STREAM_HOPS_MAX)
-        return fail(BSRNN_EARG, "bsrnn_pool_create: max_hops = %d is outside [1, BSRNN_STREAM_HOPS_MAX = %d]", max_hops, STREAM_HOPS_MAX);
-    if (int rc = check_ready(c)) return rc;
-    std::unique_ptr<bsrnn_pool> pl(new bsrnn_pool());
-    pl->ctx = c; pl->slots = slots; pl->rows = rows_per_session; pl->max_hops = max_hops;
-    const int C = pl->C = slots * rows_per_session;
-    pool_slots_init(pl->sl, slots);
-    pl->seen.assign(slots, 0);
-    pl->counts.assign(C, 0);
-    pl->spans.reserve(slots);
-    pl->view.assign(slots, bsrnn_pool::View{});
-    pl->pair.assign(slots, -1);
-    pl->skip.assign(slots, 0);
-    int rc = bsrnn_stream_create(c, C, &pl->st);
-    if (!rc) rc = bsrnn_stream_reserve(pl->st, max_hops);
-    if (rc) { if (pl->st) bsrnn_stream_destroy(pl->st); return rc; }
-    const size_t rect = (size_t)C * max_hops * POOL_HOP, fifo = (size_t)C * POOL_HOP, stage_in = (size_t)C * (max_hops + 1) * POOL_HOP;
-    pl->ptr_off = ((size_t)C * (sizeof(PoolEntry) + sizeof(float)) + 7) & ~size_t(7);
-    pl->tab_bytes = (pl->ptr_off + (rated ? 2 * (size_t)C * sizeof(void*) : 0) + 255) & ~size_t(255);
-    const size_t d_floats = 3 * rect + fifo + stage_in, d_bytes = d_floats * sizeof(float) + pl->tab_bytes;
-    const size_t h_bytes = bsrnn_pool::MIRRORS * pl->tab_bytes + (stage_in + rect) * sizeof(float);
-    g_dbg[DBG_ALLOC] += 2;
-    hipError_t e = hipMalloc((void**)&pl->base, d_bytes);
-    if (e == hipSuccess) e = hipMemset(pl->base, 0, d_bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&pl->h_base, h_bytes, hipHostMallocDefault);
-    for (hipEvent_t& ev : pl->ev)
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e == hipSuccess) {
-        memset(pl->h_base, 0, h_bytes);
-        float* p = pl->base;
-        pl->chunk = p; p += rect;
-        pl->out = p; p += rect;
-        pl->fifo = p; p += fifo;
-        pl->d_hin = p; p += stage_in;
-        pl->d_hout = p; p += rect;
-        pl->d_tab = reinterpret_cast<char*>(p);
-        pl->h_in = reinterpret_cast<float*>(pl->h_base + bsrnn_pool::MIRRORS * pl->tab_bytes);
-        pl->h_out = pl->h_in + stage_in;
-        // the two kernels' first launches happen here: every row as an empty entry, which zero-fills the rectangle and moves nothing
-        PoolEntry* tab = reinterpret_cast<PoolEntry*>(pl->h_base);
-        for (int r = 0; r < C; ++r) tab[r] = pool_entry(PoolPart{}, r, nullptr, nullptr);
-        e = hipMemcpy(pl->d_tab, pl->h_base, pl->tab_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            launch_pool_gather(reinterpret_cast<const PoolEntry*>(pl->d_tab), C, pl->chunk, pl->fifo, max_hops, nullptr);
-            launch_pool_scatter(reinterpret_cast<const PoolEntry*>(pl->d_tab), C, pl->out, max_hops, nullptr);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    }
-    if (e != hipSuccess) {
-        bsrnn_pool_destroy(pl.release());
-        return fail(BSRNN_EHIP, "bsrnn_pool_create: %s", hipGetErrorString(e));
-    }
-    *out = pl.release();
-    return 0;
-}
-
-int bsrnn_pool_create(bsrnn_ctx* c, int32_t slots, int32_t rows_per_session, int32_t max_hops, bsrnn_pool** out)
-{
-    return pool_create(c, slots, rows_per_session, max_hops, false, out);
-}
-
-void bsrnn_pool_destroy(bsrnn_pool* pl)
-{
-    if (!pl) return;
-    (void)hipSetDevice(pl->ctx->device);
-    (void)hipDeviceSynchronize();
-    if (pl->conv_base) (void)hipFree(pl->conv_base);
-    if (pl->bin) bsrnn_resampler_bank_destroy(pl->bin);
-    if (pl->bout) bsrnn_resampler_bank_destroy(pl->bout);
-    for (hipEvent_t ev : pl->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (pl->h_base) (void)hipHostFree(pl->h_base);
-    if (pl->base) (void)hipFree(pl->base);
-    bsrnn_stream* st = pl->st;
-    delete pl;
-    bsrnn_stream_destroy(st);          // (last: a context that bsrnn_destroy retired goes with its last stream)
-}
-
-// pair: the session's rate pair, -1 at the model's rate
-static int pool_open(bsrnn_pool* pl, int pair, int32_t* slot_out)
-{
-    for (int i = 0; i < pl->slots; ++i) {
-        if (pl->sl.open[i]) continue;
-        // the slot's rows start from silence, in the order of the stream the pool was last fed on; the FIFO needs nothing (pending 0: unread)
-        for (int r = 0; r < pl->rows; ++r) pl->counts[r] = i * pl->rows + r;
-        if (int rc = bsrnn_stream_reset_rows(pl->st, pl->counts.data(), pl->rows, pl->last)) return rc;
-        pl->reset_queued = true;
-        *slot_out = pool_slot_open(pl->sl);
-        pool_rates_assign(pl, i, pair);
-        return 0;
-    }
-    return fail(BSRNN_EARG, "bsrnn_pool_open: all %d slots are in use", pl->slots);
-}
-
-int bsrnn_pool_open(bsrnn_pool* pl, int32_t* slot_out)
-{
-    if (!pl || !slot_out) return fail(BSRNN_EARG, "bsrnn_pool_open: null %s", !pl ? "pool" : "slot_out");
-    return pool_open(pl, -1, slot_out);
-}
-
-int bsrnn_pool_close(bsrnn_pool* pl, int32_t slot)
-{
-    if (!pl) return fail(BSRNN_EARG, "bsrnn_pool_close: null pool");
-    if (!pool_slot_close(pl->sl, slot)) return fail(BSRNN_EARG, "bsrnn_pool_close: slot %d is not open", slot);
-    pool_rates_assign(pl, slot, -1);
-    return 0;
-}
-
-int64_t bsrnn_pool_pending(const bsrnn_pool* pl, int32_t slot) { return pl && pool_slot_is_open(pl->sl, slot) ? pl->sl.pending[slot] : -1; }
-
-bsrnn_stream* bsrnn_pool_stream(bsrnn_pool* pl) { return pl ? pl->st : nullptr; }
-
-int bsrnn_pool_get_pending(bsrnn_pool* pl, int32_t slot, float* host, int32_t* n)
-{
-    if (!pl || !host || !n) return fail(BSRNN_EARG, "bsrnn_pool_get_pending: null %s", !pl ? "pool" : "argument");
-    if (!pool_slot_is_open(pl->sl, slot)) return fail(BSRNN_EARG, "bsrnn_pool_get_pending: slot %d is not open", slot);
-    HIP_TRY(hipSetDevice(pl->ctx->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(host, pl->fifo + (size_t)slot * pl->rows * POOL_HOP, (size_t)pl->rows * POOL_HOP * sizeof(float), hipMemcpyDeviceToHost));
-    *n = pl->sl.pending[slot];
-    return 0;
-}
-
-int bsrnn_pool_set_pending(bsrnn_pool* pl, int32_t slot, const float* host, int32_t n)
-{
-    if (!pl || !host) return fail(BSRNN_EARG, "bsrnn_pool_set_pending: null %s", !pl ? "pool" : "argument");
-    if (!pool_slot_is_open(pl->sl, slot)) return fail(BSRNN_EARG, "bsrnn_pool_set_pending: slot %d is not open", slot);
-    if (n < 0 || n >= POOL_HOP) return fail(BSRNN_EARG, "bsrnn_pool_set_pending: n = %d samples, a session has fewer than %d waiting", n, POOL_HOP);
-    HIP_TRY(hipSetDevice(pl->ctx->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(pl->fifo + (size_t)slot * pl->rows * POOL_HOP, host, (size_t)pl->rows * POOL_HOP * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipDeviceSynchronize());
-    pl->sl.pending[slot] = n;
-    return 0;
-}
-
-int bsrnn_pool_feed(bsrnn_pool* pl, int32_t n_sessions, const int32_t* slots_host, const float* const* in_dev, const int64_t* in_stride,
-                    const int64_t* n_in, float* const* out_dev, const int64_t* out_stride, int64_t* n_out_host, const float* mix_host, float mix,
-                    void* stream)
-{
-    return pool_feed(pl, "bsrnn_pool_feed", n_sessions, slots_host, in_dev, in_stride, n_in, out_dev, out_stride, n_out_host, mix_host, mix,
-                     (hipStream_t)stream, false);
-}
-
-int bsrnn_pool_feed_host(bsrnn_pool* pl, int32_t n_sessions, const int32_t* slots_host, const float* const* in_host, const int64_t* in_stride,
-                         const int64_t* n_in, float* const* out_host, const int64_t* out_stride, int64_t* n_out_host, const float* mix_host,
-                         float mix)
-{
-    return pool_feed(pl, "bsrnn_pool_feed_host", n_sessions, slots_host, in_host, in_stride, n_in, out_host, out_stride, n_out_host, mix_host, mix,
-                     nullptr, true);
-}
-
-// ---- sessions at their own sample rates (pool_rates_host.h)
-int bsrnn_pool_create_rates(bsrnn_ctx* c, int32_t slots, int32_t rows_per_session, int32_t max_hops, const int32_t* rates, int32_t n_rates,
-                            int64_t max_block, bsrnn_pool** out)
-{
-    if (!c) return fail(BSRNN_EARG, "bsrnn_pool_create_rates: null context");
-    if (!out) return fail(BSRNN_EARG, "bsrnn_pool_create_rates: null place for the object");
-    if (n_rates < 1 || n_rates > BANK_PAIRS_MAX)
-        return fail(BSRNN_EARG, "bsrnn_pool_create_rates: n_rates = %d is outside [1, BSRNN_BANK_PAIRS_MAX = %d]", n_rates, BANK_PAIRS_MAX);
-    if (!rates) return fail(BSRNN_EARG, "bsrnn_pool_create_rates: null list of the %d rates", n_rates);
-    int32_t model[BANK_PAIRS_MAX];
-    ResampleRatio qin[BANK_PAIRS_MAX];
-    for (int k = 0; k < n_rates; ++k) {
-        model[k] = POOL_MODEL_RATE;
-        ResampleRatio q;
-        if (int rc = resample_check_rates(rates[k], POOL_MODEL_RATE, "bsrnn_pool_create_rates", qin[k])) return rc;
-        if (int rc = resample_check_rates(POOL_MODEL_RATE, rates[k], "bsrnn_pool_create_rates", q)) return rc;
-    }
-    if (max_block < 1 || max_block > ((int64_t)1 << 24))
-        return fail(BSRNN_EARG, "bsrnn_pool_create_rates: max_block = %lld samples is outside [1, 2^24]", (long long)max_block);
-    bsrnn_pool* pl = nullptr;
-    if (int rc = pool_create(c, slots, rows_per_session, max_hops, true, &pl)) return rc;
-    const int C = pl->C;
-    pl->n_rates = n_rates;
-    for (int k = 0; k < n_rates; ++k) pl->rate[k] = rates[k];
-    pl->max_block = max_block;
-    pl->cap_in = pool_rates_cap_in(qin, n_rates, max_block);
-    pl->cap_out = pool_rates_cap_out(pl->cap_in);
-    int rc = bsrnn_resampler_bank_create(c, C, rates, model, n_rates, &pl->bin);
-    if (!rc) rc = bsrnn_resampler_bank_create(c, C, model, rates, n_rates, &pl->bout);
-    if (!rc) {
-        const size_t floats = (size_t)C * (pl->cap_in + pl->cap_out), bytes = floats * sizeof(float) + 2 * (size_t)C * sizeof(void*);
-        ++g_dbg[DBG_ALLOC];
-        hipError_t e = hipMalloc((void**)&pl->conv_base, bytes);
-        if (e == hipSuccess) e = hipMemset(pl->conv_base, 0, bytes);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) rc = fail(BSRNN_EHIP, "bsrnn_pool_create_rates: %s", hipGetErrorString(e));
-        pl->conv_in = pl->conv_base;
-        pl->conv_out = pl->conv_in + (size_t)C * pl->cap_in;
-        pl->d_ptrs = reinterpret_cast<char*>(pl->conv_out + (size_t)C * pl->cap_out);
-    }
-    if (rc) { bsrnn_pool_destroy(pl); return rc; }
-    *out = pl;
-    return 0;
-}
-
-int bsrnn_pool_open_rate(bsrnn_pool* pl, int32_t sample_rate, int32_t* slot_out)
-{
-    if (!pl || !slot_out) return fail(BSRNN_EARG, "bsrnn_pool_open_rate: null %s", !pl ? "pool" : "slot_out");
-    if (sample_rate == POOL_MODEL_RATE) return pool_open(pl, -1, slot_out);
-    for (int k = 0; k < pl->n_rates; ++k)
-        if (pl->rate[k] == sample_rate) return pool_open(pl, k, slot_out);
-    return fail(BSRNN_EARG, "bsrnn_pool_open_rate: sample_rate %d is not one of the %d rates the pool was created with", sample_rate, pl->n_rates);
-}
-
-int32_t bsrnn_pool_rate_of(const bsrnn_pool* pl, int32_t slot)
-{
-    if (!pl || !pool_slot_is_open(pl->sl, slot)) return -1;
-    return pl->pair[slot] < 0 ? POOL_MODEL_RATE : pl->rate[pl->pair[slot]];
-}
-
-static PoolRateSess pool_rate_sess(const bsrnn_pool* pl, int32_t slot)
-{
-    const int row0 = slot * pl->rows;
-    return PoolRateSess{pl->bin->pos[row0], pl->bout->pos[row0], pl->skip[slot]};
-}
-
-int64_t bsrnn_pool_ready(const bsrnn_pool* pl, int32_t slot, int64_t n_in)
-{
-    if (!pl || !pool_slot_is_open(pl->sl, slot) || n_in < 0 || n_in > (INT64_MAX >> 12)) return -1;
-    const int k = pl->pair[slot];
-    if (k < 0) return pool_plain_feed(pl->sl.pending[slot], n_in).n_out;
-    if (n_in > pl->max_block) return -1;
-    return pool_rate_feed(pl->bin->q[k], pl->bout->q[k], pool_rate_sess(pl, slot), pl->sl.pending[slot], n_in).n_out;
-}
-
-static PoolRateDrain pool_drain_plan(const bsrnn_pool* pl, int32_t slot)
-{
-    const int k = pl->pair[slot];
-    return k < 0 ? pool_plain_drain(pl->sl.pending[slot])
-                 : pool_rate_drain(pl->bin->q[k], pl->bout->q[k], pool_rate_sess(pl, slot), pl->sl.pending[slot]);
-}
-
-int64_t bsrnn_pool_drain_len(const bsrnn_pool* pl, int32_t slot)
-{
-    if (!pl || !pool_slot_is_open(pl->sl, slot)) return -1;
-    return pool_drain_plan(pl, slot).n_out;
-}
-
-int bsrnn_pool_drain(bsrnn_pool* pl, int32_t slot, float* out, int64_t out_stride, int64_t* n_out_host, float mix, void* stream)
-{
-    if (!pl) return fail(BSRNN_EARG, "bsrnn_pool_drain: null pool");
-    if (!n_out_host) return fail(BSRNN_EARG, "bsrnn_pool_drain: session in slot %d: nowhere to report the sample count (null n_out_host)", slot);
-    if (!pool_slot_is_open(pl->sl, slot)) return fail(BSRNN_EARG, "bsrnn_pool_drain: session in slot %d: the slot is not open", slot);
-    const int k = pl->pair[slot], R = pl->rows, C = pl->C, row0 = slot * R;
-    const PoolRateDrain g = pool_drain_plan(pl, slot);
-    if (out_stride < g.n_out)
-        return fail(BSRNN_EARG, "bsrnn_pool_drain: session in slot %d: out_stride = %lld is below the %lld samples it gets", slot,
-                    (long long)out_stride, (long long)g.n_out);
-    if (g.n_out > 0 && !out) return fail(BSRNN_EARG, "bsrnn_pool_drain: session in slot %d gets %lld samples at a null pointer", slot, (long long)g.n_out);
-    bsrnn_ctx* c = pl->ctx;
-    if (int rc = check_ready(c)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    ENTER_CALL(c, s);
-    if (pl->reset_queued && pl->last != s) HIP_TRY(hipStreamSynchronize(pl->last));
-    pl->reset_queued = false;
-    pl->last = s;
-    const size_t SI = (size_t)(pl->max_hops + 1) * POOL_HOP;
-    const size_t zeros = (size_t)(g.pad + POOL_HOP) * sizeof(float);
-    float* const* d_first = reinterpret_cast<float* const*>(pl->d_ptrs);
-    float* const* d_second = d_first + C;
-    if (k < 0) {
-        // at the model's rate: the zeros come from the slot's rows of the host form's device staging (pad + 1024 <= 2047 floats of a row)
-        float* z = pl->d_hin + (size_t)row0 * SI;
-        HIP_TRY(hipMemset2DAsync(z, SI * sizeof(float), 0, zeros, R, s));
-        pl->view[0] = {z, out, (int64_t)SI, out_stride, g.n_feed, 0};
-    } else {
-        // both pointer tables of the outbound launches go up at once: where the flush writes (behind the n1 samples), where the process does
-        const float** p_flush = nullptr;
-        float** p_proc = nullptr;
-        int m = 0;
-        if (int rc = pool_rates_pointers(pl, &p_flush, &p_proc, &m)) return rc;
-        for (int rr = 0; rr < R; ++rr) {
-            p_proc[row0 + rr] = out ? out + (size_t)rr * out_stride : nullptr;
-            p_flush[row0 + rr] = out ? out + (size_t)rr * out_stride + g.n1 : nullptr;
-        }
-        if (int rc = pool_rates_upload(pl, m, s)) return rc;
-        // 1. the inbound rows are flushed into conv_in; 2. and 3. zeros to a whole hop and one more hop behind them
-        pool_rates_hold_all(pl);
-        for (int r = row0; r < row0 + R; ++r)
-            if (bank_row_flush(pl->bin->q[k], pl->bin->pos[r], pl->bin->desc[r], pl->bin->next[r]) != BANK_OK)
-                return fail(BSRNN_ESTATE, "bsrnn_pool_drain: session in slot %d: the inbound flush is too long (internal error)", slot);
-        if (int rc = pool_rates_launch(pl, pl->bin, nullptr, 0, nullptr, pl->conv_in, pl->cap_in, nullptr, s)) return rc;
-        float* x = pl->conv_in + (size_t)row0 * pl->cap_in;
-        HIP_TRY(hipMemset2DAsync(x + g.owed_in, (size_t)pl->cap_in * sizeof(float), 0, zeros, R, s));
-        pl->view[0] = {x, pl->conv_out + (size_t)row0 * pl->cap_out, pl->cap_in, pl->cap_out, g.n_feed, g.drop};
-    }
-    // 4. those hops, every other session held
-    if (int rc = pool_feed_rounds(pl, 1, &slot, g.hops, nullptr, mix, s, false)) return rc;
-    if (k >= 0) {
-        // 5. the outbound rows take them, and are flushed
-        pool_rates_hold_all(pl);
-        for (int r = row0; r < row0 + R; ++r)
-            if (bank_row_process(pl->bout->q[k], pl->bout->pos[r], g.b, pl->bout->desc[r], pl->bout->next[r]) != BANK_OK)
-                return fail(BSRNN_ESTATE, "bsrnn_pool_drain: session in slot %d: the outbound block is too long (internal error)", slot);
-        if (int rc = pool_rates_launch(pl, pl->bout, pl->conv_out, pl->cap_out, nullptr, nullptr, 0, d_second, s)) return rc;
-        pool_rates_hold_all(pl);
-        for (int r = row0; r < row0 + R; ++r)
-            if (bank_row_flush(pl->bout->q[k], pl->bout->pos[r], pl->bout->desc[r], pl->bout->next[r]) != BANK_OK)
-                return fail(BSRNN_ESTATE, "bsrnn_pool_drain: session in slot %d: the outbound flush is too long (internal error)", slot);
-        if (int rc = pool_rates_launch(pl, pl->bout, nullptr, 0, nullptr, nullptr, 0, d_first, s)) return rc;
-    }
-    // the session stands at the beginning of a new piece of audio: its stream rows in this stream's order, the rest is host state
-    for (int rr = 0; rr < R; ++rr) pl->counts[rr] = row0 + rr;
-    if (int rc = bsrnn_stream_reset_rows(pl->st, pl->counts.data(), R, s)) return rc;
-    pool_rates_assign(pl, slot, k);
-    pl->sl.pending[slot] = 0;
-    *n_out_host = g.n_out;
     return 0;
 }
 

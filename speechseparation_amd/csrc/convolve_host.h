@@ -1,5 +1,5 @@
 // Long FIR convolution of rows of different lengths (bsrnn_fir_bank_*, bsrnn_convolve_ragged): the definition and the plan, as integer
-// arithmetic on the host.  HIP-free: api.hip plans a call with it, fft.hip takes ConvRow by value, tests/cpp/convolve_plan_check.cpp
+// arithmetic on the host.  HIP-free: api_resample.hip plans a call with it, fft.hip takes ConvRow by value, tests/cpp/convolve_plan_check.cpp
 // compiles it alone.
 //
 // THE DEFINITION is torch.nn.functional.conv1d(x, h, padding='same') (m_dataset.py:92-114 applies a room impulse response with it): for a

@@ -663,25 +663,19 @@ __global__ __launch_bounds__(256) void stream_reset_rows_kernel(RowSet rows, flo
     for (int slab = 0; slab < 8; ++slab) zero_floats4(state + ((size_t)slab * C + c) * n4 * 4, n4, tid);
 }
 
-void launch_stream_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, hipStream_t s)
+// (a one-hop call is never HOPS: kernels.h, StreamRows)
+void launch_stream_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, const StreamRows& rows,
+                            hipStream_t s)
 {
-    hipLaunchKernelGGL(stream_analysis_kernel<AllRows>, dim3(C), dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, AllRows{});
+    if (rows.kind == StreamRows::ALL) hipLaunchKernelGGL(stream_analysis_kernel<AllRows>, dim3(C), dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, AllRows{});
+    else hipLaunchKernelGGL(stream_analysis_kernel<HeldRows>, dim3(C), dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, HeldRows{rows.active, nullptr, nullptr, nullptr, C, 0});
 }
 void launch_stream_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, const float* prev_in, float* prev_out, float* out,
-                             int C, hipStream_t s)
+                             const float* state_in, float* state_out, int C, int K, const StreamRows& rows, hipStream_t s)
 {
-    hipLaunchKernelGGL(stream_synthesis_kernel<AllRows>, dim3(C), dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, AllRows{});
-}
-void launch_stream_analysis_rows(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, const RowSet& active,
-                                 hipStream_t s)
-{
-    hipLaunchKernelGGL(stream_analysis_kernel<HeldRows>, dim3(C), dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, HeldRows{active, nullptr, nullptr, nullptr, C, 0});
-}
-void launch_stream_synthesis_rows(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
-                                  float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, const RowSet& active, hipStream_t s)
-{
-    hipLaunchKernelGGL(stream_synthesis_kernel<HeldRows>, dim3(C), dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out,
-                       HeldRows{active, mix_rows, state_in, state_out, C, K});
+    if (rows.kind == StreamRows::ALL) hipLaunchKernelGGL(stream_synthesis_kernel<AllRows>, dim3(C), dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, AllRows{});
+    else hipLaunchKernelGGL(stream_synthesis_kernel<HeldRows>, dim3(C), dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out,
+                            HeldRows{rows.active, rows.mix_rows, state_in, state_out, C, K});
 }
 void launch_stream_reset_rows(float* buf, float* prev, float* state, int C, int K, const RowSet& rows, hipStream_t s)
 {
@@ -858,52 +852,46 @@ __global__ __launch_bounds__(256, FFT_OCC_ISTFT) void stream_block_synthesis_ker
     }
 }
 
-void launch_stream_block_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L, hipStream_t s)
+// One launcher per direction: the instantiation by rows.kind.  (The chunk lengths may differ between the instantiations: a hop has the
+// same bits whichever workgroup computes it, see above.)
+template <class ROWS>
+static void stream_block_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L, const ROWS& rows,
+                                  hipStream_t s)
 {
-    const Chunks ch = chunks_for<stream_block_analysis_kernel<AllRows>>(L, C, 0);
-    hipLaunchKernelGGL(stream_block_analysis_kernel<AllRows>, ch.grid, dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, L, ch.len, AllRows{});
+    const Chunks ch = chunks_for<stream_block_analysis_kernel<ROWS>>(L, C, 0);
+    hipLaunchKernelGGL(stream_block_analysis_kernel<ROWS>, ch.grid, dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, L, ch.len, rows);
+}
+void launch_stream_block_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L,
+                                  const StreamRows& rows, int* row_frames, hipStream_t s)
+{
+    switch (rows.kind) {
+    case StreamRows::ALL: stream_block_analysis(tb, buf_in, buf_out, chunk, X, C, L, AllRows{}, s); break;
+    case StreamRows::HELD: stream_block_analysis(tb, buf_in, buf_out, chunk, X, C, L, HeldRows{rows.active, nullptr, nullptr, nullptr, C, 0}, s); break;
+    case StreamRows::HOPS: stream_block_analysis(tb, buf_in, buf_out, chunk, X, C, L, HopRows{rows.hops, nullptr, nullptr, nullptr, C, 0, row_frames}, s); break;
+    }
+}
+// MIX = false: every row's wet / dry value is 1 (no blend with X)
+template <class ROWS>
+static void stream_block_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, bool blend, const float* prev_in, float* prev_out,
+                                   float* out, int C, int L, const ROWS& rows, hipStream_t s)
+{
+    const Chunks ch = chunks_for<stream_block_synthesis_kernel<false, ROWS>>(L, C, 1);
+    if (!blend) hipLaunchKernelGGL((stream_block_synthesis_kernel<false, ROWS>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
+    else hipLaunchKernelGGL((stream_block_synthesis_kernel<true, ROWS>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
 }
 void launch_stream_block_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, const float* prev_in, float* prev_out, float* out,
-                                   int C, int L, hipStream_t s)
+                                   const float* state_in, float* state_out, int C, int K, int L, const StreamRows& rows, hipStream_t s)
 {
-    const Chunks ch = chunks_for<stream_block_synthesis_kernel<false, AllRows>>(L, C, 1);
-    if (mix == 1.f) hipLaunchKernelGGL((stream_block_synthesis_kernel<false, AllRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, AllRows{});
-    else hipLaunchKernelGGL((stream_block_synthesis_kernel<true, AllRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, AllRows{});
-}
-// (the chunk lengths may differ from the plain launches': a hop has the same bits whichever workgroup computes it, see above)
-void launch_stream_block_analysis_rows(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L,
-                                       const RowSet& active, hipStream_t s)
-{
-    const Chunks ch = chunks_for<stream_block_analysis_kernel<HeldRows>>(L, C, 0);
-    hipLaunchKernelGGL(stream_block_analysis_kernel<HeldRows>, ch.grid, dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, L, ch.len,
-                       HeldRows{active, nullptr, nullptr, nullptr, C, 0});
-}
-void launch_stream_block_synthesis_rows(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
-                                        float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, int L,
-                                        const RowSet& active, hipStream_t s)
-{
-    const HeldRows rows{active, mix_rows, state_in, state_out, C, K};
-    const Chunks ch = chunks_for<stream_block_synthesis_kernel<false, HeldRows>>(L, C, 1);
-    if (!mix_rows && mix == 1.f) hipLaunchKernelGGL((stream_block_synthesis_kernel<false, HeldRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
-    else hipLaunchKernelGGL((stream_block_synthesis_kernel<true, HeldRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
-}
-
-// bsrnn_stream_process_hops: row r advances by row_hops_of(hops, r) of the L hops; the analysis leaves the counts in row_frames [C]
-void launch_stream_block_analysis_hops(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L,
-                                       const RowHops& hops, int* row_frames, hipStream_t s)
-{
-    const Chunks ch = chunks_for<stream_block_analysis_kernel<HopRows>>(L, C, 0);
-    hipLaunchKernelGGL(stream_block_analysis_kernel<HopRows>, ch.grid, dim3(256), 0, s, tb, buf_in, buf_out, chunk, X, L, ch.len,
-                       HopRows{hops, nullptr, nullptr, nullptr, C, 0, row_frames});
-}
-void launch_stream_block_synthesis_hops(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
-                                        float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, int L,
-                                        const RowHops& hops, hipStream_t s)
-{
-    const HopRows rows{hops, mix_rows, state_in, state_out, C, K, nullptr};
-    const Chunks ch = chunks_for<stream_block_synthesis_kernel<false, HopRows>>(L, C, 1);
-    if (!mix_rows && mix == 1.f) hipLaunchKernelGGL((stream_block_synthesis_kernel<false, HopRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
-    else hipLaunchKernelGGL((stream_block_synthesis_kernel<true, HopRows>), ch.grid, dim3(256), 0, s, tb, Y, X, mix, prev_in, prev_out, out, L, ch.len, rows);
+    const bool blend = rows.mix_rows || mix != 1.f;
+    switch (rows.kind) {
+    case StreamRows::ALL: stream_block_synthesis(tb, Y, X, mix, blend, prev_in, prev_out, out, C, L, AllRows{}, s); break;
+    case StreamRows::HELD:
+        stream_block_synthesis(tb, Y, X, mix, blend, prev_in, prev_out, out, C, L, HeldRows{rows.active, rows.mix_rows, state_in, state_out, C, K}, s);
+        break;
+    case StreamRows::HOPS:
+        stream_block_synthesis(tb, Y, X, mix, blend, prev_in, prev_out, out, C, L, HopRows{rows.hops, rows.mix_rows, state_in, state_out, C, K, nullptr}, s);
+        break;
+    }
 }
 
 // ------------------------------------------------------------------------------ offline DSP, one segment of a clip

@@ -1,4 +1,4 @@
-// Internal launcher interface between api.hip and the gfx950 kernels.  Not part of the ABI.
+// Internal launcher interface between the host units (api*.hip) and the gfx950 kernels.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -285,40 +285,36 @@ void launch_istft_ragged_backward(const FftTables& tb, const float* dwave, float
 // [C][2050][T] (reference layout) <-> [C*T][ld] (band-padded)
 void launch_to_frame_major(const FftTables& tb, const float* x, float* xf, int C, int T, hipStream_t s);
 void launch_from_frame_major(const FftTables& tb, const float* yf, float* y, int C, int T, hipStream_t s);
+// Which rows of a streaming call take how many of its hops: all of them every hop (the plain calls), only the rows of a set
+// (bsrnn_stream_process_rows), or every row its own count (bsrnn_stream_process_hops).  Set and counts travel by value in the kernel
+// arguments (stream_rows_host.h); mix_rows, if not null, holds one wet / dry value per row [C] on the device and replaces `mix`
+// (never with ALL).  The launchers below pick the kernel instantiation by `kind`.
+struct StreamRows {
+    enum Kind { ALL, HELD, HOPS } kind = ALL;
+    RowSet active;                     // HELD
+    RowHops hops;                      // HOPS (the block launches only: a one-hop call never meets mixed counts)
+    const float* mix_rows = nullptr;
+};
 // streaming DSP, one frame per row (infer-streaming.py:116-145).  What a step carries to the next one is read from one buffer and
 // written to another (the stream object alternates two sets): a step can be run again from its unchanged starting point.
 //   analysis: buf_out [C][2048] = [buf_in[:, 1024:], chunk [C][1024]]; X [C][ld] = rfft(buf_out * hann)
 //   synthesis: s = irfft(mix(Y, X)); out = (s[0:1024] + prev_in[1024:2048]) * inv_wsum; prev_out = s
-void launch_stream_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, hipStream_t s);
+// A held row (HELD, not in the set): buf_out / prev_out = buf_in / prev_in, zero rows in X, zeros in out, chunk unread - and, in the
+// synthesis, its LSTM state copied from state_in to state_out [4][2][C*K][64], so that launch follows the model's.  Active rows: the
+// bits of the plain launches.
+void launch_stream_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, const StreamRows& rows,
+                            hipStream_t s);
 void launch_stream_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, const float* prev_in, float* prev_out, float* out,
-                             int C, hipStream_t s);
+                             const float* state_in, float* state_out, int C, int K, const StreamRows& rows, hipStream_t s);
 // The same for L consecutive hops per row in one launch each (bsrnn_stream_process): chunk / out [C][L*1024], X / Y frame-major
 // [C*L][ld] (row c*L + l).  buf_out = the last 2048 samples of buf_in ++ chunk, prev_out = the last synthesis frame.
-void launch_stream_block_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L, hipStream_t s);
+// HOPS: row r with n = row_hops_of(hops, r) - frames / hops below n as the plain launches give them, zero rows of X / zeros of out from
+// n on, chunk unread from n * 1024 on, buf_out / prev_out the carry after n hops; n = 0 is a held row.  The analysis writes
+// row_frames[r] = n ([C] on the device) for the call's time-axis launches (launch_time_lstm).
+void launch_stream_block_analysis(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L,
+                                  const StreamRows& rows, int* row_frames, hipStream_t s);
 void launch_stream_block_synthesis(const FftTables& tb, const float* Y, const float* X, float mix, const float* prev_in, float* prev_out, float* out,
-                                   int C, int L, hipStream_t s);
-// The four launches above for a call that advances only the rows in `active` (bsrnn_stream_process_rows; the set travels by value,
-// stream_rows_host.h).  A held row: buf_out / prev_out = buf_in / prev_in, zero rows in X, zeros in out, chunk unread - and, in the
-// synthesis, its LSTM state copied from state_in to state_out [4][2][C*K][64], so that launch follows the model's.  mix_rows, if not
-// null, holds one wet / dry value per row [C] on the device and replaces `mix`.  Active rows: the bits of the plain launches.
-void launch_stream_analysis_rows(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, const RowSet& active,
-                                 hipStream_t s);
-void launch_stream_synthesis_rows(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
-                                  float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, const RowSet& active, hipStream_t s);
-void launch_stream_block_analysis_rows(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L,
-                                       const RowSet& active, hipStream_t s);
-void launch_stream_block_synthesis_rows(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
-                                        float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, int L,
-                                        const RowSet& active, hipStream_t s);
-// The two block launches for a call in which every row advances by its own number of hops (bsrnn_stream_process_hops; the counts travel
-// by value, stream_rows_host.h): row r with n = row_hops_of(hops, r) - frames / hops below n as the plain launches give them, zero rows
-// of X / zeros of out from n on, chunk unread from n * 1024 on, buf_out / prev_out the carry after n hops; n = 0 is a held row.  The
-// analysis writes row_frames[r] = n ([C] on the device) for the call's time-axis launches (launch_time_lstm).
-void launch_stream_block_analysis_hops(const FftTables& tb, const float* buf_in, float* buf_out, const float* chunk, float* X, int C, int L,
-                                       const RowHops& hops, int* row_frames, hipStream_t s);
-void launch_stream_block_synthesis_hops(const FftTables& tb, const float* Y, const float* X, float mix, const float* mix_rows, const float* prev_in,
-                                        float* prev_out, float* out, const float* state_in, float* state_out, int C, int K, int L,
-                                        const RowHops& hops, hipStream_t s);
+                                   const float* state_in, float* state_out, int C, int K, int L, const StreamRows& rows, hipStream_t s);
 // zeroes buf, prev and state of the rows in `rows` of one carry set, in one launch (bsrnn_stream_reset_rows)
 void launch_stream_reset_rows(float* buf, float* prev, float* state, int C, int K, const RowSet& rows, hipStream_t s);
 

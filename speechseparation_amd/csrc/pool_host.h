@@ -1,6 +1,6 @@
 // The native session pool (bsrnn_pool_*): slots, the per-session count of samples that do not yet fill a hop, and the ROUND PLAN of one
 // feed - what every row of every named session contributes to each bsrnn_stream_process_hops call of the feed, and what it leaves
-// waiting.  Host-only arithmetic, no HIP types: api.hip plans and fills the table, pool.hip reads it,
+// waiting.  Host-only arithmetic, no HIP types: api_pool.hip plans and fills the table, pool.hip reads it,
 // tests/cpp/pool_plan_check.cpp checks both with g++.
 //
 // One feed.  Session i has p_i samples per row waiting in its FIFO (p_i < 1024) and brings n_i more: H_i = (p_i + n_i) / 1024 hops in

@@ -1,7 +1,7 @@
 // Sessions at their own sample rates in the native session pool (bsrnn_pool_create_rates, bsrnn_pool_open_rate, bsrnn_pool_drain): what
 // one feed and one drain mean to a session in COUNTS - how many samples each stage takes and gives - and how large the pool's two
 // staging rectangles have to be.  Host-only arithmetic, no HIP types, on top of resample_host.h (the conversions' definition),
-// resample_bank_host.h (a row's position in its stream) and pool_host.h (hops and what waits): api.hip plans with it,
+// resample_bank_host.h (a row's position in its stream) and pool_host.h (hops and what waits): api_pool.hip plans with it,
 // tests/cpp/pool_rates_check.cpp checks it with g++.
 //
 // A session at rate r sits on pair k of the pool's inbound bank (r -> 44100) and on pair k of its outbound bank (44100 -> r), with a

@@ -2,7 +2,7 @@
 // place in its own stream, converted by ONE launch.  A row of the bank follows exactly the arithmetic of a single-pair bsrnn_resampler
 // of its pair (resample_host.h: resample_ready, resample_n_out, resample_base, the keep-from rule, resample_carry_floats); this header
 // only turns "row r takes n_in samples now" or "row r is flushed" into what the kernel has to know about that row, and into the row's next
-// position.  Host-only arithmetic, no HIP types: api.hip builds the descriptors, resample.hip reads them,
+// position.  Host-only arithmetic, no HIP types: api_resample.hip builds the descriptors, resample.hip reads them,
 // tests/cpp/resample_bank_check.cpp checks both with g++.
 //
 // The descriptors travel BY VALUE in the kernel arguments, as RowSet and RowHops do (stream_rows_host.h): no allocation, no staging

@@ -9,7 +9,7 @@
 // index leaves [0, 2 * half]: every tap sits in the table exactly once, rows are padded with zeros to the common L, the loop over t
 // has no branch.  Inputs outside [0, n_in) count as zeros.
 // Index arithmetic is 64-bit throughout (j * down passes 2^31 a minute into a 192 kHz clip).  No HIP types: resample.hip uses the
-// index helpers on the device, api.hip designs and lays out the table, tests/cpp/resample_check.cpp checks all of it with g++.
+// index helpers on the device, api_resample.hip designs and lays out the table, tests/cpp/resample_check.cpp checks all of it with g++.
 #pragma once
 #include <cmath>
 #include <cstdint>

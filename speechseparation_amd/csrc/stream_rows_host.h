@@ -1,7 +1,7 @@
 // Row sets of the streaming rows calls (bsrnn_stream_process_rows, bsrnn_stream_reset_rows): which of a stream's C rows a call means
 // travels BY VALUE in the kernel arguments, as a fixed bitset - no allocation, no staging copy, and nothing that has to outlive the call
 // under the deferred range policy.  256 bytes of kernel arguments; that caps those calls at STREAM_ROWS_MAX rows.
-// Host-only arithmetic (no HIP types): api.hip packs, fft.hip tests bits, tests/cpp/stream_rows_check.cpp checks both with g++.
+// Host-only arithmetic (no HIP types): api_stream.hip packs, fft.hip tests bits, tests/cpp/stream_rows_check.cpp checks both with g++.
 // RowHops (bsrnn_stream_process_hops): how many hops each row advances, by value in the same way - 8 bits per row, 2 KB of kernel
 // arguments, which is why that call takes at most STREAM_HOPS_MAX hops (tests/cpp/stream_hops_check.cpp).
 #pragma once

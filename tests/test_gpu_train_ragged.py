@@ -100,6 +100,52 @@ def test_istft_ragged_and_its_transpose_row_by_row():
     print("ragged iSTFT backward: %.1e from bsrnn_istft_backward per clip, %.1e from torch.istft's transpose in float64" % (worst_alone, worst_torch))
 
 
+def _fresh_context(train, dev):
+    v = train.generate_bandsplits()[0]
+    ctx = ctypes.c_void_p()
+    train._native.check(train._lib.bsrnn_create(dev.index, _i32(v), len(v), ctypes.byref(ctx)))
+    return ctx
+
+
+def test_queued_ragged_calls_pass_the_eighth_upload_mirror_and_a_growth():
+    """The lengths of a ragged call travel through eight pinned mirrors used in turn and one device block that grows (api_internal.h,
+    UploadRing).  Twenty bsrnn_stft_ragged calls of 1 to 6 rows and 1025 to 5 * 1024 samples, other lengths in every call, queue up on a side
+    stream with no host synchronisation between them: each mirror is written three times.  The block is allocated in units of 256 bytes, so
+    the lengths of up to 32 rows never outgrow the first one; two more calls, of 40 and of 72 rows, stand behind the tenth and the
+    seventeenth and make it grow twice after the eighth call.  One synchronisation, then every output bit for bit against the same call
+    made alone on a context of its own."""
+    from speechseparation_amd import train
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rows = [1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 40, 5, 6, 6, 1, 3, 6, 2, 72, 6, 4, 6]
+    stride = 5 * 1024 + 3
+    rng = np.random.RandomState(7)
+    calls = []
+    for i, R in enumerate(rows):
+        lens = [int(n) for n in rng.randint(1025, 5 * 1024 + 1, size=R)]
+        T = max(_frames(n) for n in lens)
+        calls.append((lens, _ragged_waves(lens, stride, 100 + i), torch.full((R, 2050, T), NAN, device=dev), torch.full((R, 2050, T), NAN, device=dev)))
+    assert len({tuple(c[0]) for c in calls}) == len(calls)
+    side = torch.cuda.Stream(dev)
+    torch.cuda.synchronize(dev)
+    ctx = _fresh_context(train, dev)
+    try:
+        for lens, wave, x, _ in calls:
+            train._native.check(train._lib.bsrnn_stft_ragged(ctx, train._p(wave), stride, _i64(lens), train._p(x), len(lens),
+                                                             ctypes.c_void_p(side.cuda_stream)))
+        side.synchronize()
+    finally:
+        train._lib.bsrnn_destroy(ctx)
+    for i, (lens, wave, x, alone) in enumerate(calls):
+        ctx = _fresh_context(train, dev)
+        try:
+            train._native.check(train._lib.bsrnn_stft_ragged(ctx, train._p(wave), stride, _i64(lens), train._p(alone), len(lens),
+                                                             ctypes.c_void_p(side.cuda_stream)))
+            side.synchronize()
+        finally:
+            train._lib.bsrnn_destroy(ctx)
+        assert not torch.isnan(alone).any() and torch.equal(x, alone), (i, lens)
+
+
 # ------------------------------------------------------------------------------------------------ 2. the loss alone
 def _loss_native(train, y, s, xt, sp, lens, rows):
     dev = y.device
