@@ -130,7 +130,7 @@ int  bsrnn_debug_peek(bsrnn_ctx* ctx, int32_t which, float* host_out, int64_t nf
  * allocations, 1 stream captures begun, 2 graph instantiations, 3 graph launches.  A bsrnn_stream does all of the first three in
  * bsrnn_stream_create (as the reference's plugin does in its constructor, speech-ladspa-onnx.cpp:55-120); its step calls leave them
  * unchanged (tests/test_gpu_entrypoints.py drives the LADSPA plugin's run() and checks).  which = 4 counts work instead: the frame rows
- * (rows x frames, summed over the segments) bsrnn_separate_long_ragged has handed to the model - below R * Tmax when rows retire.
+ * (rows x frames, summed over the segments) bsrnn_separate_long_ragged / bsrnn_evaluate_long_ragged have handed to the model - below R * Tmax when rows retire.
  * Any other value: -1. */
 long long bsrnn_debug_counter(int32_t which);
 
@@ -407,6 +407,30 @@ int  bsrnn_evaluate(bsrnn_ctx* ctx, const float* mix_dev, const float* speech_de
 int  bsrnn_evaluate_ragged(bsrnn_ctx* ctx, const float* mix_dev, const float* speech_dev, int64_t wave_stride,
                            const int64_t* clip_lens_host, const int32_t* clip_rows_host, int32_t n_clips,
                            float* est_out_dev, double* metrics_host, void* stream);
+/* bsrnn_evaluate_long_ragged = bsrnn_evaluate_ragged in segments: clips of DIFFERENT lengths, each of any length, from a workspace of
+ * R * min(seg_frames, Tmax) frame rows.  Arguments and result as bsrnn_evaluate_ragged: metrics_host [n_clips][BSRNN_N_METRICS], each clip
+ * as bsrnn_evaluate gives it for that clip alone, to rounding.  The separation is bsrnn_separate_long_ragged's - the same cut of the Tmax
+ * frames, the alive prefix of the rows (per-clip lengths expanded to rows), carried state and overlap-add tail; bsrnn_debug_counter(4)
+ * counts its frame rows, so order the clips LONGEST FIRST.
+ *   - seg_frames >= Tmax: the call IS bsrnn_evaluate_ragged (it delegates: numbers and estimate bit-identical).
+ *   - Per segment [ta, te): STFT of the mixture on the prefix -> the model -> iSTFT of the segment's hops -> the range guard, handled per
+ *     segment under EITHER policy (a segment that left the fp16 range is run again in exact fp32 from its untouched state) -> the clean
+ *     signal through the segment's analysis -> the segment's time and spectral sums ADDED into accumulators of a fixed size per row, one
+ *     slot per workgroup, in stream order without atomics: run and re-run give the same bits.  INPUT_SDR is formed once over the whole
+ *     inputs.  One download at the end; synchronous.
+ *   - SISDR is formed from the row's totals instead of a second pass over an estimate that no longer exists: alpha in fp32 as
+ *     bsrnn_evaluate forms it, then a^2 sum s^2 over max(0, a^2 sum s^2 - 2 a sum x s + sum x^2) in double (within 4e-7 dB of the two-pass
+ *     figure up to 40 dB, 2e-4 dB at 80 dB).
+ *   - Memory beyond the two inputs: the workspace of one segment, bsrnn_separate_long_ragged's carry sets, the accumulators, and - without
+ *     est_out_dev - an estimate buffer of ONE segment, R * seg_frames * 1024 floats.  Nothing grows with Tmax.  With est_out_dev the
+ *     estimate is [R, (Tmax-1)*1024] as bsrnn_separate_long_ragged writes it.  A second call that fits allocates nothing
+ *     (bsrnn_debug_counter(0)).
+ * BSRNN_EARG, before any device work (also on a host-only context, in front of its BSRNN_ESTATE): everything bsrnn_evaluate_ragged refuses,
+ * in its words (the text names the clip); seg_frames < 1; R * min(seg_frames, Tmax) beyond bsrnn_separate_long_ragged's limit;
+ * est_out_dev overlapping the R * wave_stride floats of mix_dev or speech_dev, under either policy. */
+int  bsrnn_evaluate_long_ragged(bsrnn_ctx* ctx, const float* mix_dev, const float* speech_dev, int64_t wave_stride,
+                                const int64_t* clip_lens_host, const int32_t* clip_rows_host, int32_t n_clips,
+                                int32_t seg_frames, float* est_out_dev, double* metrics_host, void* stream);
 
 /* ---- ragged training: the clips of one optimizer step in one backward pass -----------------
  * The reference accumulates gradients clip by clip (train.py:97-115).  The same step as ONE rectangle R x Tmax: the model is causal along

@@ -25,7 +25,7 @@ SYMBOLS = [
     "bsrnn_linear_group_train_forward", "bsrnn_linear_group_train_backward", "bsrnn_train_reduction_layout",
     "bsrnn_set_range_policy", "bsrnn_get_range_policy", "bsrnn_overlap_state", "bsrnn_debug_peek", "bsrnn_debug_counter",
     "bsrnn_stream_process", "bsrnn_stream_reserve", "bsrnn_separate_long", "bsrnn_separate_long_host", "bsrnn_workspace_rows",
-    "bsrnn_separate_ragged", "bsrnn_evaluate_ragged", "bsrnn_separate_long_ragged",
+    "bsrnn_separate_ragged", "bsrnn_evaluate_ragged", "bsrnn_separate_long_ragged", "bsrnn_evaluate_long_ragged",
     "bsrnn_stft_ragged", "bsrnn_istft_ragged", "bsrnn_istft_ragged_backward", "bsrnn_train_loss_ragged", "bsrnn_train_loss_ragged_backward",
     "bsrnn_stream_process_rows", "bsrnn_stream_process_hops", "bsrnn_stream_reset_rows", "bsrnn_stream_row_floats", "bsrnn_stream_get_row", "bsrnn_stream_set_row",
     "bsrnn_resample_len", "bsrnn_resample", "bsrnn_resampler_create", "bsrnn_resampler_destroy", "bsrnn_resampler_reset",
@@ -190,6 +190,7 @@ def _load():
         "bsrnn_sync": (C.c_int, [vp, vp]),
         "bsrnn_evaluate": (C.c_int, [vp, vp, vp, i32, i64, vp, C.POINTER(C.c_double), vp]),
         "bsrnn_evaluate_ragged": (C.c_int, [vp, vp, vp, i64, vp, vp, i32, vp, C.POINTER(C.c_double), vp]),
+        "bsrnn_evaluate_long_ragged": (C.c_int, [vp, vp, vp, i64, vp, vp, i32, i32, vp, C.POINTER(C.c_double), vp]),
         "bsrnn_stft_ragged": (C.c_int, [vp, vp, i64, vp, vp, i32, vp]),
         "bsrnn_istft_ragged": (C.c_int, [vp, vp, vp, vp, i32, vp]),
         "bsrnn_istft_ragged_backward": (C.c_int, [vp, vp, vp, vp, i32, vp]),

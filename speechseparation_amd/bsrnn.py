@@ -603,9 +603,33 @@ class BSRNN(nn.Module):
         a list of dicts, one per clip, each what `evaluate` gives for that clip alone (to rounding): a clip is the unit of the reference's
         metrics, nothing is summed across clips (include/bsrnn_hip.h, bsrnn_evaluate_ragged).  With return_estimate each dict also has
         "x_time": the clip's rows cut to its own (n // 1024) * 1024 samples."""
+        return self._evaluate_clips("evaluate_ragged", mix, speech, lengths, clip_rows, return_estimate, None)
+
+    def evaluate_long_ragged(self, mix, speech, lengths, clip_rows=None, segment_frames=256, return_estimate=False):
+        """`evaluate_ragged` in segments, for clips that are long AND unequal: arguments, checks and result as `evaluate_ragged`, each clip's
+        numbers what `evaluate` gives for that clip alone (to rounding), from a workspace of R * segment_frames frame rows and - without
+        return_estimate - an estimate buffer of one segment: nothing grows with the clips' length.  The separation is
+        `separate_long_ragged`'s, so put the clips LONGEST FIRST; segment_frames is checked as there, and segment_frames >= Tmax is
+        `evaluate_ragged` itself (bit-identical).  The sums are formed segment by segment and the SI-SDR from the rows' totals
+        (include/bsrnn_hip.h, bsrnn_evaluate_long_ragged)."""
+        return self._evaluate_clips("evaluate_long_ragged", mix, speech, lengths, clip_rows, return_estimate, segment_frames)
+
+    def evaluate_long(self, mix, speech, segment_frames=256, return_estimate=False):
+        """`evaluate` for one clip of any length in bounded memory: mix, speech [R, n] -> the dict of `evaluate`, through
+        `evaluate_long_ragged` with the R rows as one clip."""
+        if (not isinstance(mix, torch.Tensor) or not isinstance(speech, torch.Tensor) or mix.dim() != 2
+                or tuple(mix.shape) != tuple(speech.shape) or mix.shape[0] < 1):
+            raise ValueError("evaluate_long: expected mix and speech [R, n] of the same shape, got %s and %s" % (
+                tuple(mix.shape) if isinstance(mix, torch.Tensor) else type(mix).__name__,
+                tuple(speech.shape) if isinstance(speech, torch.Tensor) else type(speech).__name__))
+        return self._evaluate_clips("evaluate_long", mix, speech, [mix.shape[1]], [mix.shape[0]], return_estimate, segment_frames)[0]
+
+    def _evaluate_clips(self, who, mix, speech, lengths, clip_rows, return_estimate, segment_frames):
+        """The ragged evaluate calls: checks first, then bsrnn_evaluate_ragged (who = "evaluate_ragged": no segments) or
+        bsrnn_evaluate_long_ragged."""
         if (not isinstance(mix, torch.Tensor) or not isinstance(speech, torch.Tensor) or mix.dim() != 2
                 or tuple(mix.shape) != tuple(speech.shape)):
-            raise ValueError("evaluate_ragged: expected mix and speech [R, n_max] of the same shape, got %s and %s" % (
+            raise ValueError(who + ": expected mix and speech [R, n_max] of the same shape, got %s and %s" % (
                 tuple(mix.shape) if isinstance(mix, torch.Tensor) else type(mix).__name__,
                 tuple(speech.shape) if isinstance(speech, torch.Tensor) else type(speech).__name__))
         R, n_max = mix.shape
@@ -613,16 +637,24 @@ class BSRNN(nn.Module):
             lens = [int(x) for x in lengths]
             rows = [1] * len(lens) if clip_rows is None else [int(x) for x in clip_rows]
         except TypeError:
-            raise ValueError("evaluate_ragged: lengths and clip_rows must be sequences of ints") from None
+            raise ValueError(who + ": lengths and clip_rows must be sequences of ints") from None
         if not lens or len(rows) != len(lens):
-            raise ValueError("evaluate_ragged: %d lengths and %d row counts, need one of each per clip and at least one clip" % (len(lens), len(rows)))
+            raise ValueError(who + ": %d lengths and %d row counts, need one of each per clip and at least one clip" % (len(lens), len(rows)))
         for c, (n, ch) in enumerate(zip(lens, rows)):
             if ch < 1:
-                raise ValueError("evaluate_ragged: clip %d has %d rows, need at least 1" % (c, ch))
+                raise ValueError(who + ": clip %d has %d rows, need at least 1" % (c, ch))
             if not _spec.HOP < n <= n_max:
-                raise ValueError("evaluate_ragged: clip %d has %d samples, need 1024 < length <= %d" % (c, n, n_max))
+                raise ValueError(who + ": clip %d has %d samples, need 1024 < length <= %d" % (c, n, n_max))
+        seg = None
+        if who != "evaluate_ragged":
+            try:
+                seg = int(segment_frames)
+            except (TypeError, ValueError):
+                raise ValueError(who + ": segment_frames must be an int, got %r" % (segment_frames,)) from None
+            if seg < 1:
+                raise ValueError(who + ": segment_frames = %d (at least one frame per segment)" % seg)
         if sum(rows) != R:
-            raise ValueError("evaluate_ragged: the clips own %d rows, mix has %d" % (sum(rows), R))
+            raise ValueError(who + ": the clips own %d rows, mix has %d" % (sum(rows), R))
         dev = self._device_for(mix)
         m, s = self._prep(mix, dev), self._prep(speech, dev)
         n_clips = len(lens)
@@ -630,8 +662,12 @@ class BSRNN(nn.Module):
         with torch.cuda.device(dev):
             ctx = self._context(dev)
             est = torch.empty((R, (max(lens) // _spec.HOP) * _spec.HOP), device=dev, dtype=torch.float32) if return_estimate else None
-            _check(_lib.bsrnn_evaluate_ragged(ctx, _ptr(m), _ptr(s), n_max, (ctypes.c_int64 * n_clips)(*lens), (ctypes.c_int32 * n_clips)(*rows),
-                                              n_clips, _ptr(est) if return_estimate else None, vals, _stream_ptr(dev)))
+            head = (ctx, _ptr(m), _ptr(s), n_max, (ctypes.c_int64 * n_clips)(*lens), (ctypes.c_int32 * n_clips)(*rows), n_clips)
+            tail = (_ptr(est) if return_estimate else None, vals, _stream_ptr(dev))
+            if seg is None:
+                _check(_lib.bsrnn_evaluate_ragged(*head, *tail))
+            else:
+                _check(_lib.bsrnn_evaluate_long_ragged(*head, seg, *tail))
         out, r0, nm = [], 0, len(_native.METRIC_NAMES)
         for c, (n, ch) in enumerate(zip(lens, rows)):
             d = {k: vals[c * nm + i] for i, k in enumerate(_native.METRIC_NAMES)}
@@ -647,6 +683,24 @@ class BSRNN(nn.Module):
         of the same rank and channel count and cut to their common length.  `spec.ragged_buckets` groups the pairs exactly as
         `separate_many` groups clips; each bucket is packed into two [rows, n_max] buffers and runs as ONE `evaluate_ragged` call.
         Returns the per-pair metric dicts in input order."""
+        return self._evaluate_pairs("evaluate_many", pairs, lambda frames, rows: _spec.ragged_buckets(frames, rows, max_rows, max_padding),
+                                    self.evaluate_ragged)
+
+    def evaluate_many_long(self, pairs, segment_frames=256, max_rows=64):
+        """`evaluate_many` for pairs that are long and of very different lengths: pairs as `evaluate_many` takes them.  `spec.long_buckets`
+        sorts them longest first and fills buckets of at most `max_rows` rows - no padding cap, the segments bound the padding - and each
+        bucket runs as ONE `evaluate_long_ragged` call, rows longest first.  Returns the per-pair metric dicts in input order."""
+        try:
+            seg = int(segment_frames)
+        except (TypeError, ValueError):
+            raise ValueError("evaluate_many_long: segment_frames must be an int, got %r" % (segment_frames,)) from None
+        if seg < 1:
+            raise ValueError("evaluate_many_long: segment_frames = %d (at least one frame per segment)" % seg)
+        return self._evaluate_pairs("evaluate_many_long", pairs, lambda frames, rows: _spec.long_buckets(frames, rows, max_rows),
+                                    lambda m, s, lens, rows: self.evaluate_long_ragged(m, s, lens, rows, seg))
+
+    def _evaluate_pairs(self, who, pairs, buckets_of, run):
+        """The batched evaluate calls: the pairs checked, grouped by buckets_of(frames, rows), each bucket packed and handed to run."""
         pairs = list(pairs)
         shapes = []
         for i, p in enumerate(pairs):
@@ -654,9 +708,9 @@ class BSRNN(nn.Module):
             ok = ok and p[0].dim() == p[1].dim() and (p[0].dim() == 1 or (p[0].shape[0] == p[1].shape[0] and p[0].shape[0] >= 1))
             n = min(p[0].shape[-1], p[1].shape[-1]) if ok else 0
             if not ok or n <= _spec.HOP:
-                raise ValueError("evaluate_many: pair %d must be (mix, speech) tensors, both [n] or both [ch, n], with n > 1024" % i)
+                raise ValueError("%s: pair %d must be (mix, speech) tensors, both [n] or both [ch, n], with n > 1024" % (who, i))
             shapes.append((1 if p[0].dim() == 1 else p[0].shape[0], n))
-        buckets = _spec.ragged_buckets([_spec.n_frames(n) for _, n in shapes], [ch for ch, _ in shapes], max_rows, max_padding)
+        buckets = buckets_of([_spec.n_frames(n) for _, n in shapes], [ch for ch, _ in shapes])
         if not pairs:
             return []
         dev = next((t.device for p in pairs for t in p if t.is_cuda), None) or self._device_for(pairs[0][0])
@@ -670,7 +724,7 @@ class BSRNN(nn.Module):
                 for k in range(2):
                     bufs[k, r0:r0 + ch, :n] = pairs[i][k].detach().reshape(ch, -1)[:, :n].to(device=dev, dtype=torch.float32)
                 r0 += ch
-            for i, d in zip(bucket, self.evaluate_ragged(bufs[0], bufs[1], lens, rows)):
+            for i, d in zip(bucket, run(bufs[0], bufs[1], lens, rows)):
                 results[i] = d
         return results
 

@@ -1815,30 +1815,17 @@ int bsrnn_separate_long_host(bsrnn_ctx* c, const float* wave_host, float* wave_o
 // segment's state has another slab pitch: the surviving rows' state and overlap-add tail are packed from the written set into the one the
 // finished segment read (launch_long_compact, on the caller's stream), and p does NOT flip - so a segment always reads a set that nothing
 // of its own writes, and its range re-run (finish_call) starts from untouched state and carry.
-int bsrnn_separate_long_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_stride, const int64_t* lens_host, float* wave_out, int32_t R,
-                               int32_t seg_frames, void* stream)
+// The segments of such a call on stream s, after its arguments have been checked (T = q.shape.Tmax > seg).  `out` takes the hops segment i
+// completes: whole = true, it is the call's result, rows out_stride floats apart, and the segment writes from its first hop on; whole =
+// false, it is a buffer of one segment and every segment writes from its start.  any_policy: the range guard is handled per segment whatever
+// the context's policy (finish_call).  after(ta, te, Ri, d_lens, seg_out) runs once per segment, when the segment is final - its estimate at
+// seg_out (its first hop of row 0), its spectrum in Yf, Xf free - and before the next one starts.
+typedef std::function<int(int ta, int te, int Ri, const int64_t* d_lens, const float* seg_out)> AfterSegment;
+static int long_ragged_segments(bsrnn_ctx* c, const RaggedLongPlan& q, const float* wave, int64_t wave_stride, const int64_t* lens_host, float* out,
+                                int64_t out_stride, bool whole, int R, int seg, hipStream_t s, bool any_policy, const AfterSegment& after)
 {
-    // arguments first, device or not (a host-only context answers them before BSRNN_ESTATE)
-    if (!c) return fail(BSRNN_EARG, "null context");
-    if (!wave || !lens_host || !wave_out || R < 1)
-        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: need a waveform, R lengths, an output buffer and R >= 1, got R = %d", R);
-    if (seg_frames < 1) return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: seg_frames = %d (at least one frame per segment)", seg_frames);
-    const RaggedLongPlan q = ragged_long_plan(lens_host, R, wave_stride, seg_frames);
-    if (int rc0 = ragged_shape_refuse("bsrnn_separate_long_ragged", q.shape, R, wave_stride, seg_frames)) return rc0;
-    // whatever the range policy: later segments read the waveform after earlier hops are written
-    const int64_t out_stride = q.shape.out_stride;
-    if (ranges_overlap(wave, (size_t)R * wave_stride * sizeof(float), wave_out, (size_t)R * out_stride * sizeof(float)))
-        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: wave_out must not overlap wave (later segments read the waveform after earlier hops are written)");
-    if (seg_frames >= q.shape.Tmax) {                                 // one segment IS the ragged call: bit-identical by construction
-        const int rc1 = bsrnn_separate_ragged(c, wave, wave_stride, lens_host, wave_out, R, stream);
-        if (!rc1) g_dbg[DBG_LONG_RAGGED_ROWS] += q.frame_rows;
-        return rc1;
-    }
-    int rc = check_ready(c);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    ENTER_CALL(c, s);
-    const int T = (int)q.shape.Tmax, seg = seg_frames, K = c->K;
+    int rc;
+    const int T = (int)q.shape.Tmax, K = c->K;
     // everything the segments need, before the first launch: the workspace of one segment, the task tables and (where a segment's plan
     // overlaps the dual path) the dispatch orders of every distinct shape rows[i] x frames, the carry sets.  The caches' bounds grow so
     // that this call's set fits beside what is there (as bsrnn_stream_reserve's).
@@ -1868,13 +1855,13 @@ int bsrnn_separate_long_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_str
     int p = 0;
     for (int i = 0; i < q.nseg; ++i) {
         const int ta = i * seg, te = std::min(T, ta + seg), Ri = q.rows[i];
-        float* out = wave_out + (size_t)std::max(ta - 1, 0) * HOPS;
+        float* seg_out = whole ? out + (size_t)std::max(ta - 1, 0) * HOPS : out;
         auto run = [&]() -> int {
             { StageScope sc(c, ST_STFT, s); launch_stft_ragged_segment(c->tb, wave, wave_stride, d_lens, c->Xf, Ri, ta, te, s); }
             if (int rc2 = run_model(c, c->Xf, c->Yf, nullptr, Ri, te - ta, lf.state[p], lf.state[p ^ 1], s)) return rc2;
             {
                 StageScope sc(c, ST_ISTFT, s);
-                launch_istft_ragged_segment(c->tb, c->Yf, out, out_stride, d_lens, ta ? lf.carry[p] : nullptr, lf.carry[p ^ 1], R, Ri, ta, te, s);
+                launch_istft_ragged_segment(c->tb, c->Yf, seg_out, out_stride, d_lens, ta ? lf.carry[p] : nullptr, lf.carry[p ^ 1], R, Ri, ta, te, s);
             }
             HIP_TRY(hipGetLastError());
             return 0;
@@ -1882,13 +1869,41 @@ int bsrnn_separate_long_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_str
         if ((rc = run())) return rc;
         g_dbg[DBG_LONG_RAGGED_ROWS] += (long long)Ri * (te - ta);
         // range policy per segment, as in long_segments: the re-run starts from this segment's untouched state and carry set
-        if ((rc = finish_call(c, s, run))) return rc;
+        if ((rc = finish_call(c, s, run, any_policy))) return rc;
+        if ((rc = after(ta, te, Ri, d_lens, seg_out))) return rc;
         if (i + 1 < q.nseg && q.rows[i + 1] < Ri) {
             launch_long_compact(lf.state[p ^ 1], lf.state[p], lf.carry[p ^ 1], lf.carry[p], Ri, q.rows[i + 1], K, s);
             HIP_TRY(hipGetLastError());
         } else p ^= 1;
     }
     return 0;
+}
+
+int bsrnn_separate_long_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_stride, const int64_t* lens_host, float* wave_out, int32_t R,
+                               int32_t seg_frames, void* stream)
+{
+    // arguments first, device or not (a host-only context answers them before BSRNN_ESTATE)
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!wave || !lens_host || !wave_out || R < 1)
+        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: need a waveform, R lengths, an output buffer and R >= 1, got R = %d", R);
+    if (seg_frames < 1) return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: seg_frames = %d (at least one frame per segment)", seg_frames);
+    const RaggedLongPlan q = ragged_long_plan(lens_host, R, wave_stride, seg_frames);
+    if (int rc0 = ragged_shape_refuse("bsrnn_separate_long_ragged", q.shape, R, wave_stride, seg_frames)) return rc0;
+    // whatever the range policy: later segments read the waveform after earlier hops are written
+    const int64_t out_stride = q.shape.out_stride;
+    if (ranges_overlap(wave, (size_t)R * wave_stride * sizeof(float), wave_out, (size_t)R * out_stride * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_separate_long_ragged: wave_out must not overlap wave (later segments read the waveform after earlier hops are written)");
+    if (seg_frames >= q.shape.Tmax) {                                 // one segment IS the ragged call: bit-identical by construction
+        const int rc1 = bsrnn_separate_ragged(c, wave, wave_stride, lens_host, wave_out, R, stream);
+        if (!rc1) g_dbg[DBG_LONG_RAGGED_ROWS] += q.frame_rows;
+        return rc1;
+    }
+    int rc = check_ready(c);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    return long_ragged_segments(c, q, wave, wave_stride, lens_host, wave_out, out_stride, true, R, seg_frames, s, false,
+                                [](int, int, int, const int64_t*, const float*) { return 0; });
 }
 
 int64_t bsrnn_workspace_rows(const bsrnn_ctx* c) { return c ? (int64_t)c->cap_rows : 0; }
@@ -2100,6 +2115,97 @@ int bsrnn_evaluate_ragged(bsrnn_ctx* c, const float* mix, const float* speech, i
     // bsrnn_evaluate (finish_call: a structural fall-back, or the whole flow again on the exact-fp32 kernels from the same inputs and lengths)
     if ((rc = run())) return rc;
     return finish_call(c, s, run, true);
+}
+
+// --------------------------------------------------------------------------- ragged long-form evaluate: the metrics per clip, in segments
+// bsrnn_evaluate_ragged's numbers from bsrnn_separate_long_ragged's flow: the same cut, plan, alive prefix and carry sets
+// (long_ragged_segments), so the workspace is R x seg frame rows and the model is paid for on about the real frames.  A segment's estimate
+// spectrum is gone when the next segment starts, so the sums are formed per segment: when a segment is FINAL (finish_call has returned,
+// whatever the range policy - Yf holds its spectrum whichever pass produced it, and its sums are added exactly once) the clean signal
+// goes through the segment's analysis into Xf and one launch each adds the segment's time and spectral sums into the call's accumulators
+// (metrics.hip: a slot per workgroup, plain additions in stream order).  The SI-SDR needs no second pass over an estimate that no longer
+// exists: metrics_host.h, sisdr_sums_from_totals.  INPUT_SDR does not depend on the estimate: bsrnn_evaluate_ragged's launch over the whole
+// inputs.  One download at the end.  Nothing is sized by Tmax: accumulators [R][METRIC_SEG_SLOTS][7 + 2] and, when the caller wants no
+// estimate, a buffer of ONE segment's hops [R][seg * 1024] that the synthesis writes with that row stride.
+int bsrnn_evaluate_long_ragged(bsrnn_ctx* c, const float* mix, const float* speech, int64_t wave_stride, const int64_t* clip_lens_host,
+                               const int32_t* clip_rows_host, int32_t n_clips, int32_t seg_frames, float* est_out, double* metrics, void* stream)
+{
+    // arguments first, device or not (a host-only context answers them before BSRNN_ESTATE)
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!mix || !speech || !clip_lens_host || !metrics || n_clips < 1)
+        return fail(BSRNN_EARG, "bsrnn_evaluate_long_ragged: need a mixture, a clean signal, the clips' lengths, room for the metrics and n_clips >= 1, got n_clips = %d", n_clips);
+    if (seg_frames < 1) return fail(BSRNN_EARG, "bsrnn_evaluate_long_ragged: seg_frames = %d (at least one frame per segment)", seg_frames);
+    std::vector<int64_t> row_lens;
+    std::vector<int> first_row;
+    const ClipShape q = clip_shape(clip_lens_host, clip_rows_host, n_clips, wave_stride, row_lens, first_row);
+    if (int rc0 = clip_shape_refuse("bsrnn_evaluate_long_ragged", q, wave_stride)) return rc0;
+    const int R = (int)q.R, T = (int)q.Tmax;
+    const RaggedLongPlan plan = ragged_long_plan(row_lens.data(), R, wave_stride, seg_frames);
+    if (int rc0 = ragged_shape_refuse("bsrnn_evaluate_long_ragged", plan.shape, R, wave_stride, seg_frames)) return rc0;
+    // whatever the range policy: later segments and the metrics read mix and speech after earlier hops of the estimate are written
+    if (ranges_overlap(est_out, (size_t)R * q.out_stride * sizeof(float), mix, (size_t)R * wave_stride * sizeof(float)) ||
+        ranges_overlap(est_out, (size_t)R * q.out_stride * sizeof(float), speech, (size_t)R * wave_stride * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_evaluate_long_ragged: est_out must not overlap mix or speech (later segments, the metrics and a re-run read them after the estimate is written)");
+    if (seg_frames >= T) {                                            // one segment IS the ragged evaluate: bit-identical by construction
+        const int rc1 = bsrnn_evaluate_ragged(c, mix, speech, wave_stride, clip_lens_host, clip_rows_host, n_clips, est_out, metrics, stream);
+        if (!rc1) g_dbg[DBG_LONG_RAGGED_ROWS] += plan.frame_rows;
+        return rc1;
+    }
+    int rc = check_ready(c);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+
+    const int seg = seg_frames, S = METRIC_SEG_SLOTS, IB = 64;
+    const size_t n_time = (size_t)R * S * METRIC_TIME_Q, n_freq = (size_t)R * S * 2, n_in = (size_t)n_clips * IB;
+    const size_t n_part = n_time + n_freq + n_in;
+    const size_t b_lens = (size_t)R * sizeof(int64_t), b_table = b_lens + (size_t)n_clips * sizeof(MetricClip);
+    const int64_t seg_stride = (int64_t)seg * HOPS;
+    if ((rc = eval_ragged_reserve(c, n_part, est_out ? 0 : (size_t)R * seg_stride))) return rc;
+    bsrnn_ctx::EvalRagged& er = c->er;
+    rc = er.table.upload(b_table, s, [&](char* h) {
+        memcpy(h, row_lens.data(), b_lens);
+        MetricClip* mc = reinterpret_cast<MetricClip*>(h + b_lens);
+        for (int i = 0; i < n_clips; ++i) mc[i] = MetricClip{first_row[i], clip_rows_host ? clip_rows_host[i] : 1, clip_lens_host[i]};
+    });
+    if (rc) return rc;
+    const MetricClip* d_clips = reinterpret_cast<const MetricClip*>(er.table.d + b_lens);
+    double *p_time = er.d_part, *p_freq = p_time + n_time, *p_in = p_freq + n_freq;
+    HIP_TRY(hipMemsetAsync(p_time, 0, (n_time + n_freq) * sizeof(double), s));
+    launch_metric_input_sdr_ragged(speech, mix, d_clips, n_clips, wave_stride, p_in, IB, s);
+    HIP_TRY(hipGetLastError());
+
+    auto sums = [&](int ta, int te, int Ri, const int64_t* d_lens, const float* seg_est) -> int {
+        // waveform_speech_freq of the segment's frames (Xf is free once the mask stage has run), then the segment's sums       m_dataset.py:196-213
+        launch_stft_ragged_segment(c->tb, speech, wave_stride, d_lens, c->Xf, Ri, ta, te, s);
+        launch_metric_ragged_segment(c->tb, seg_est, est_out ? q.out_stride : seg_stride, speech, mix, d_lens, wave_stride, c->Yf, c->Xf, Ri, ta, te,
+                                     p_time, p_freq, s);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    if ((rc = long_ragged_segments(c, plan, mix, wave_stride, row_lens.data(), est_out ? est_out : er.d_est, est_out ? q.out_stride : seg_stride,
+                                   est_out != nullptr, R, seg, s, true, sums)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(er.h_part, er.d_part, n_part * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const double *h_time = er.h_part, *h_freq = h_time + n_time, *h_in = h_freq + n_freq;
+    std::vector<double> rows;
+    for (int i = 0; i < n_clips; ++i) {
+        const int r0 = first_row[i], nr = clip_rows_host ? clip_rows_host[i] : 1;
+        rows.assign((size_t)nr * CLIP_ROW_Q, 0.0);
+        double re = 0, im = 0;
+        for (int r = 0; r < nr; ++r) {
+            const size_t row = (size_t)(r0 + r);
+            for (int j = 0; j < METRIC_TIME_Q; ++j) rows[(size_t)r * CLIP_ROW_Q + j] = add_in_order(h_time + row * S * METRIC_TIME_Q + j, S, METRIC_TIME_Q);
+            sisdr_sums_from_totals(&rows[(size_t)r * CLIP_ROW_Q]);
+            re += add_in_order(h_freq + row * S * 2, S, 2);
+            im += add_in_order(h_freq + row * S * 2 + 1, S, 2);
+        }
+        const int64_t n = clip_lens_host[i], Tc = ragged_frames(n);
+        finish_clip_metrics(rows.data(), nr, re, im, add_in_order(h_in + (size_t)i * IB, IB, 1), n, Tc, (Tc - 1) * HOPS,
+                            metrics + (size_t)i * BSRNN_N_METRICS);
+    }
+    return 0;
 }
 
 // --------------------------------------------------------------------------- dialog / background section mining

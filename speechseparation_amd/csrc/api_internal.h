@@ -22,7 +22,8 @@ namespace bsrnn::host {
 // --------------------------------------------------------------------------- first-use accounting (bsrnn_debug_counter)
 // What the library has done that does not belong on a real-time thread: device / pinned allocations, stream captures, graph
 // instantiations.  Process-wide; tests read them around the LADSPA plugin's run() (tests/test_gpu_entrypoints.py).  The fifth counts work, not
-// first use: the frame rows (rows x frames) bsrnn_separate_long_ragged has handed to the model, which is what shows that rows retire.
+// first use: the frame rows (rows x frames) bsrnn_separate_long_ragged / bsrnn_evaluate_long_ragged have handed to the model, which is what shows
+// that rows retire.
 extern std::atomic<long long> g_dbg[5];
 enum { DBG_ALLOC = 0, DBG_CAPTURE = 1, DBG_INSTANTIATE = 2, DBG_GRAPH_LAUNCH = 3, DBG_LONG_RAGGED_ROWS = 4 };
 
@@ -227,7 +228,8 @@ struct bsrnn_ctx {
     // Ragged evaluate (bsrnn_evaluate_ragged): the metric kernels' table [R int64 row lengths | n_clips MetricClip] travels through a ring
     // of its own - the bsrnn_separate_ragged inside an evaluate call overwrites rg's device block - and their scratch is one device block
     // [partial sums, doubles | the estimate when the caller wants none] with a pinned mirror of the partials for the one download of a
-    // call.  All grow-only: a call that fits allocates nothing.
+    // call.  All grow-only: a call that fits allocates nothing.  bsrnn_evaluate_long_ragged uses the same blocks: its accumulators in the
+    // place of the partial sums, and an estimate of ONE segment ([R][seg * 1024]) where the caller wants none.
     struct EvalRagged {
         UploadRing table;
         size_t part_cap = 0, est_cap = 0;             // doubles / floats the scratch holds

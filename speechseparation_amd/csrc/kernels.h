@@ -349,6 +349,15 @@ void launch_metric_input_sdr_ragged(const float* speech, const float* mix, const
                                     double* part /* [n_clips][blocks] */, int blocks, hipStream_t s);
 void launch_metric_freq_ragged(const FftTables& tb, const float* Yf, const float* Sf, const int64_t* lens, int R, int Tmax,
                                double* part /* [R][blocks][2] */, int blocks, hipStream_t s);
+// The time and the spectral sums of segment [ta, te) of a ragged batch cut into segments (bsrnn_evaluate_long_ragged; plan_host.h:
+// segment_owned), ADDED into the call's accumulators acc_time [R][METRIC_SEG_SLOTS][7] / acc_freq [R][METRIC_SEG_SLOTS][2], which the caller
+// zeroes once: the hops the segment completes and the frames it holds, as far as they are a row's own, of the Ri rows of its alive prefix.
+// est points at the segment's first hop of row 0, rows est_stride floats apart; speech, mix are the call's; Yf, Sf the segment-local
+// spectra [Ri*(te-ta)][ld].  Segments follow each other on one stream, so a slot's additions have a fixed order.
+constexpr int METRIC_SEG_SLOTS = 16;
+void launch_metric_ragged_segment(const FftTables& tb, const float* est, int64_t est_stride, const float* speech, const float* mix,
+                                  const int64_t* lens, int64_t wave_stride, const float* Yf, const float* Sf, int Ri, int ta, int te,
+                                  double* acc_time, double* acc_freq, hipStream_t s);
 // Per-hop activity (bsrnn_hop_activity): for hop h < hops[r] of row r, act[r][h] = {mean(est^2 / (mix - est)^2), mean(mix^2)} over its 1024
 // samples, (0, 0) from hops[r] to Hmax; hops [R] on the device, null: every row has Hmax hops.  Rows mix_stride / est_stride floats apart.
 void launch_hop_activity(const float* mix, int64_t mix_stride, const float* est, int64_t est_stride, const int32_t* hops, int R, int Hmax,

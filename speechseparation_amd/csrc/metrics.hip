@@ -12,7 +12,8 @@ namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-template <int NQ>
+// ADD: the workgroup's sums are added to what dst holds (read, add, store: dst is this workgroup's alone) instead of replacing it
+template <int NQ, bool ADD = false>
 __device__ __forceinline__ void block_reduce_store(double (&q)[NQ], double* dst)
 {
     __shared__ double sh[4][NQ];
@@ -25,7 +26,10 @@ __device__ __forceinline__ void block_reduce_store(double (&q)[NQ], double* dst)
 #pragma unroll
         for (int i = 0; i < NQ; ++i) sh[wave][i] = q[i];
     __syncthreads();
-    if (threadIdx.x < NQ) dst[threadIdx.x] = (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+    if (threadIdx.x < NQ) {
+        const double v = (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+        dst[threadIdx.x] = ADD ? dst[threadIdx.x] + v : v;
+    }
 }
 
 // grid (chunks, R).  est [R][n_est]; speech, mix [R][n_in], only their first n_est samples are used (m_dataset.py:198).
@@ -218,6 +222,72 @@ __global__ __launch_bounds__(256) void metric_freq_ragged_kernel(const float* __
         }
     }
     block_reduce_store<2>(q, part + ((size_t)r * gridDim.x + blockIdx.x) * 2);
+}
+
+// ------------------------------------------------------------------------------ the same sums formed segment by segment (bsrnn_evaluate_long_ragged)
+// A ragged batch cut into segments of frames [ta, te) (plan_host.h: ragged_long_plan, segment_owned): a segment's estimate and its spectrum
+// exist only until the next segment runs, so a row's sums are formed from one launch per segment.  acc [R][METRIC_SEG_SLOTS][NQ] are the
+// call's accumulators, zeroed once at its start: workgroup (slot, row) of every segment's launch adds its sum into slot (row, slot), which
+// is its alone - read, add, store, no atomics - and the segments follow each other on one stream, so the order of a slot's additions is
+// fixed and a call gives the same bits every time.  A workgroup with nothing to do in a segment leaves its slot alone.  Row and slot belong
+// to the workgroup: every bound is workgroup-uniform, and the loops run over the row's own samples / frames only.
+
+// grid (METRIC_SEG_SLOTS, Ri).  est points at the segment's first hop of row 0 (rows est_stride floats apart: the call's result, or a buffer
+// of one segment); speech, mix are the call's, read at the clip position.  The hops the segment completes and that are the row's own.
+__global__ __launch_bounds__(256) void metric_time_ragged_segment_kernel(const float* __restrict__ est, int64_t est_stride,
+                                                                         const float* __restrict__ speech, const float* __restrict__ mix,
+                                                                         const int64_t* __restrict__ lens, int64_t wave_stride, int ta, int te,
+                                                                         int vec, double* __restrict__ acc)
+{
+    const int r = blockIdx.y;
+    const SegmentOwned own = segment_owned(ta, te, 1 + (int)(lens[r] / HOPS));
+    const int64_t n = (int64_t)own.hops * HOPS;                       // a multiple of 1024: the 16-byte loads leave no tail
+    const int64_t first = (int64_t)blockIdx.x * 256 * (vec ? 4 : 1);  // the first sample of this workgroup's first thread
+    if (first >= n) return;
+    const float* x = est + (size_t)r * est_stride;
+    const float* s = speech + (size_t)r * wave_stride + (size_t)own.hop0 * HOPS;
+    const float* m = mix + (size_t)r * wave_stride + (size_t)own.hop0 * HOPS;
+    double q[METRIC_TIME_Q] = {0, 0, 0, 0, 0, 0, 0};
+    auto one = [&](float xv, float sv, float mv) {
+        const float d = xv - sv, e = mv - xv;          // fp32 differences, as the reference forms them
+        q[0] += (double)sv * sv; q[1] += (double)d * d; q[2] += (double)xv * sv; q[3] += (double)xv * xv;
+        q[4] += (double)__builtin_fabsf(d); q[5] += (double)mv * mv; q[6] += (double)e * e;
+    };
+    if (vec) {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * 256) {
+            const v4f xv = *reinterpret_cast<const v4f*>(x + 4 * i);
+            const v4f sv = *reinterpret_cast<const v4f*>(s + 4 * i);
+            const v4f mv = *reinterpret_cast<const v4f*>(m + 4 * i);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) one(xv[j], sv[j], mv[j]);
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) one(x[i], s[i], m[i]);
+    }
+    block_reduce_store<METRIC_TIME_Q, true>(q, acc + ((size_t)r * gridDim.x + blockIdx.x) * METRIC_TIME_Q);
+}
+
+// grid (METRIC_SEG_SLOTS, Ri).  Yf, Sf: the segment's spectra, segment-local rows (r * (te - ta) + (t - ta)) * ld; the row's own frames of
+// the segment, bins through colmap as in metric_freq_ragged_kernel.
+__global__ __launch_bounds__(256) void metric_freq_ragged_segment_kernel(const float* __restrict__ Yf, const float* __restrict__ Sf,
+                                                                         const int* __restrict__ colmap, int ld, const int64_t* __restrict__ lens,
+                                                                         int ta, int te, double* __restrict__ acc)
+{
+    const int r = blockIdx.y;
+    const SegmentOwned own = segment_owned(ta, te, 1 + (int)(lens[r] / HOPS));
+    if ((int)blockIdx.x >= own.frames) return;
+    double q[2] = {0, 0};
+    for (int t = blockIdx.x; t < own.frames; t += gridDim.x) {
+        const float* y = Yf + ((size_t)r * (te - ta) + t) * ld;
+        const float* s = Sf + ((size_t)r * (te - ta) + t) * ld;
+        for (int k = threadIdx.x; k < NBINS; k += 256) {
+            const int c = colmap[k];
+            const float2 yv = *reinterpret_cast<const float2*>(y + c), sv = *reinterpret_cast<const float2*>(s + c);
+            q[0] += (double)__builtin_fabsf(yv.x - sv.x);
+            q[1] += (double)__builtin_fabsf(yv.y - sv.y);
+        }
+    }
+    block_reduce_store<2, true>(q, acc + ((size_t)r * gridDim.x + blockIdx.x) * 2);
 }
 
 // ------------------------------------------------------------------------------ the tri-loss of a ragged training step, forward and backward
@@ -567,6 +637,18 @@ void launch_metric_freq_ragged(const FftTables& tb, const float* Yf, const float
                                int blocks, hipStream_t s)
 {
     hipLaunchKernelGGL(metric_freq_ragged_kernel, dim3(blocks, R), dim3(256), 0, s, Yf, Sf, tb.colmap, tb.ld, lens, Tmax, part);
+}
+
+void launch_metric_ragged_segment(const FftTables& tb, const float* est, int64_t est_stride, const float* speech, const float* mix,
+                                  const int64_t* lens, int64_t wave_stride, const float* Yf, const float* Sf, int Ri, int ta, int te,
+                                  double* acc_time, double* acc_freq, hipStream_t s)
+{
+    // decided once per launch: one row off alignment puts it on scalar loads (a hop starts a multiple of 1024 floats into its row)
+    const int vec = (wave_stride % 4 == 0) && (est_stride % 4 == 0) && (((uintptr_t)est | (uintptr_t)speech | (uintptr_t)mix) & 15) == 0;
+    if (segment_owned(ta, te, te).hops > 0)                           // (a row that reaches the segment's end; a one-frame first segment completes no hop)
+        hipLaunchKernelGGL(metric_time_ragged_segment_kernel, dim3(METRIC_SEG_SLOTS, Ri), dim3(256), 0, s, est, est_stride, speech, mix, lens,
+                           wave_stride, ta, te, vec, acc_time);
+    hipLaunchKernelGGL(metric_freq_ragged_segment_kernel, dim3(METRIC_SEG_SLOTS, Ri), dim3(256), 0, s, Yf, Sf, tb.colmap, tb.ld, lens, ta, te, acc_freq);
 }
 
 }  // namespace bsrnn

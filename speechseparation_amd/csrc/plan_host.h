@@ -275,6 +275,17 @@ inline RaggedLongPlan ragged_long_plan(const int64_t* lens, int R, int64_t strid
     return q;
 }
 
+// What segment [ta, te) of that cut owns of a row of Tr frames (bsrnn_evaluate_long_ragged forms a row's sums segment by segment): the clip
+// hops it completes, [max(ta - 1, 0), te - 1), as far as they are the row's own (h < Tr - 1), and its frames as far as the row has them
+// (t < Tr).  Over the segments of a cut every hop and every frame of the row is owned exactly once.  hops / frames = 0: nothing.
+struct SegmentOwned { int hop0, hops, frame0, frames; };
+BSRNN_HD inline SegmentOwned segment_owned(int ta, int te, int Tr)
+{
+    const int h0 = ta > 0 ? ta - 1 : 0;
+    const int h1 = te < Tr ? te - 1 : Tr - 1, f1 = te < Tr ? te : Tr;
+    return SegmentOwned{h0, h1 > h0 ? h1 - h0 : 0, ta, f1 > ta ? f1 - ta : 0};
+}
+
 // --------------------------------------------------------------------------- ragged evaluate: clips of different lengths (bsrnn_evaluate_ragged)
 // The unit of the validation metrics is a CLIP: clip c owns rows[c] >= 1 consecutive rows (rows == nullptr: one each) of lens[c] samples each,
 // 1024 < lens[c] <= stride.  The call runs bsrnn_separate_ragged on the R = sum rows[c] rows, whose per-row lengths are the per-clip ones

@@ -22,6 +22,12 @@ def evaluate_many(model, pairs, max_rows=64, max_padding=0.25):
     return model.evaluate_many(pairs, max_rows=max_rows, max_padding=max_padding)
 
 
+def evaluate_many_long(model, pairs, segment_frames=256, max_rows=64):
+    """evaluate_many for pairs that are long and of very different lengths -> the per-pair metric dicts in input order, from one
+    bsrnn_evaluate_long_ragged call per bucket of at most max_rows rows (BSRNN.evaluate_many_long): bounded memory, rows retire."""
+    return model.evaluate_many_long(pairs, segment_frames=segment_frames, max_rows=max_rows)
+
+
 def train_infer(model, discriminator, sample, lossfn=None, verbose=False):
     """m_dataset.py:202-226.  sample = (waveform, waveform_speech), each [1, R, n].  lossfn must be the reference's
     L1Loss(reduction='mean') (train.py:54) or None.  Returns 0-dim tensors like the reference (its validation loop calls

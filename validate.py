@@ -3,9 +3,11 @@
 train.py:132-150 without the training around it: `train_infer(model, None, sample, l1loss)` per pair, then the averages
 the reference prints ("Validation Loss", "Validation SDR") plus the SI-SDR it logs.  Separation, both STFTs and every
 reduction run on the MI355X: one bsrnn_evaluate call per pair, or with --batch-rows N the pairs batched by length into a few
-bsrnn_evaluate_ragged calls of at most N rows (the same per-pair numbers to rounding, then the same averages).
+bsrnn_evaluate_ragged calls of at most N rows (the same per-pair numbers to rounding, then the same averages).  With
+--segment-frames S the pairs go through bsrnn_evaluate_long_ragged instead, in segments of S frames: recordings of any and of very
+different lengths in bounded device memory, at most --batch-rows (64 when that is 0) rows per call.
 
-    validate.py --pairs mix1.wav speech1.wav [mix2.wav speech2.wav ...] [--weights model-always.pth] [--batch-rows 64]
+    validate.py --pairs mix1.wav speech1.wav [mix2.wav speech2.wav ...] [--weights model-always.pth] [--batch-rows 64] [--segment-frames 256]
 """
 import argparse
 
@@ -23,9 +25,14 @@ def main(argv=None):
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--batch-rows", type=int, default=0, metavar="N",
                     help="0: one call per pair; N > 0: pairs of similar length batched into calls of at most N rows")
+    ap.add_argument("--segment-frames", type=int, default=0, metavar="S",
+                    help="0: whole clips; S > 0: long-form evaluation in segments of S frames, --batch-rows (64 when 0) rows per call")
     args = ap.parse_args(argv)
     if len(args.pairs) % 2:
         ap.error("--pairs needs an even number of files")
+    if args.segment_frames < 0:
+        ap.error("--segment-frames must not be negative")
+    batched = args.batch_rows > 0 or args.segment_frames > 0
 
     torch.set_grad_enabled(False)
     model = BSRNN().eval()
@@ -42,15 +49,19 @@ def main(argv=None):
         if mix.shape[0] == 1:                                       # mono -> two identical rows, as infer.py:26-27
             mix, speech = torch.cat((mix, mix), 0), torch.cat((speech, speech), 0)
         n = min(mix.shape[1], speech.shape[1])
-        if args.batch_rows > 0:
+        if batched:
             loaded.append((mix[:, :n], speech[:, :n]))
             continue
         sample = (mix[None, :, :n].to(args.device), speech[None, :, :n].to(args.device))
         loss, sdr, sdr2, sisdr = metrics.train_infer(model, None, sample, l1loss)
         val_loss += loss.item(); val_sdr += sdr.item(); val_sdr2 += sdr2.item(); val_sisdr += sisdr.item()
-    if args.batch_rows > 0:
+    if batched:
         with torch.cuda.device(args.device):
-            for m in metrics.evaluate_many(model, loaded, max_rows=args.batch_rows):
+            if args.segment_frames > 0:
+                results = metrics.evaluate_many_long(model, loaded, segment_frames=args.segment_frames, max_rows=args.batch_rows or 64)
+            else:
+                results = metrics.evaluate_many(model, loaded, max_rows=args.batch_rows)
+            for m in results:
                 val_loss += m["loss"]; val_sdr += m["sdr"]; val_sdr2 += m["input_sdr"]; val_sisdr += m["sisdr"]
     print("Validation Loss", val_loss / n_pairs, "Validation SDR", val_sdr / n_pairs)
     print("Validation input SDR", val_sdr2 / n_pairs, "Validation SI-SDR", val_sisdr / n_pairs)
