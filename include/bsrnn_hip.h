@@ -370,8 +370,12 @@ int64_t bsrnn_workspace_rows(const bsrnn_ctx* ctx);
  *   SEPARATION_DB 10 ln(sum mix^2 / sum (mix - x)^2) over all rows (natural log, as infer.py:47 prints it).
  * est_out_dev (optional) receives the separated signal [R, (T-1)*1024]; it must not overlap mix_dev or speech_dev under
  * either policy (BSRNN_EARG: the metrics, and a re-run, read them after the estimate is written).  Synchronous: returns when the
- * numbers are on the host.  Reductions accumulate in double on the device; rows are independent, so any R
- * works (the reference's un-interleave hard-codes 2 rows, m_dataset.py:192). */
+ * numbers are on the host; the call waits once, for the sums.  Reductions accumulate in double on the device; rows are independent,
+ * so any R works (the reference's un-interleave hard-codes 2 rows, m_dataset.py:192).  The call is bsrnn_evaluate_ragged's arithmetic
+ * on one clip of R rows - the same metric kernels, the same host tail - with bsrnn_separate as its separation.  The sums and, without
+ * est_out_dev, the estimate ([R, (T-1)*1024] floats: about 32 MB at 64 rows x 128 000 samples) live in grow-only blocks of the context
+ * that the three evaluate calls share: a second call that fits allocates nothing (bsrnn_debug_counter(0)), and the blocks are retained
+ * until bsrnn_destroy.  Pass est_out_dev to keep the estimate out of the context. */
 #define BSRNN_M_LOSS          0
 #define BSRNN_M_SDR           1
 #define BSRNN_M_INPUT_SDR     2
@@ -386,7 +390,8 @@ int  bsrnn_evaluate(bsrnn_ctx* ctx, const float* mix_dev, const float* speech_de
 /* bsrnn_evaluate_ragged = bsrnn_evaluate for n_clips clips of DIFFERENT lengths in one call (a validation set).  The unit of the metrics is
  * a CLIP - one sample of the reference: all rows of one file, all of one length; its validation loop averages per-clip numbers
  * (train.py:132-150) - so the call returns one set of the eight metrics per clip, metrics_host [n_clips][BSRNN_N_METRICS], each what
- * bsrnn_evaluate gives for that clip alone (to rounding: the kernels are chosen for the whole batch).  Nothing is summed across clips:
+ * bsrnn_evaluate gives for that clip alone (to rounding: the kernels of the SEPARATION are chosen for the whole batch, so the estimate
+ * may differ within the waveform contract; the metric kernels and the host arithmetic behind them are the same).  Nothing is summed across clips:
  * INPUT_SDR sums over the rows of its own clip at each of the clip's sample positions.
  *   - Clip c owns clip_rows_host[c] >= 1 consecutive rows (NULL: one row per clip) of clip_lens_host[c] samples each, 1024 < length <=
  *     wave_stride; R = the sum of the row counts.  mix_dev and speech_dev hold R rows, wave_stride floats apart; what lies behind a row's

@@ -1908,111 +1908,65 @@ int bsrnn_separate_long_ragged(bsrnn_ctx* c, const float* wave, int64_t wave_str
 
 int64_t bsrnn_workspace_rows(const bsrnn_ctx* c) { return c ? (int64_t)c->cap_rows : 0; }
 
-// --------------------------------------------------------------------------- validation metrics
-// m_dataset.py:182-226 (`infer` + `train_infer` without the discriminator) and infer.py:44-47.
-int bsrnn_evaluate(bsrnn_ctx* c, const float* mix, const float* speech, int32_t R, int64_t n, float* est_out,
-                   double* metrics, void* stream)
-{
-    if (!metrics || !speech) return fail(BSRNN_EARG, "bsrnn_evaluate: null argument");
-    float* est = est_out;
-    double* d_part = nullptr;
-    float* d_alpha = nullptr;
-    const int T = 1 + (int)(n / HOPS);
-    const int64_t n_est = (int64_t)(T - 1) * HOPS;
-    int rc = 0;
-    auto cleanup = [&](int code) {
-        if (!est_out && est) (void)hipFree(est);
-        if (d_part) (void)hipFree(d_part);
-        if (d_alpha) (void)hipFree(d_alpha);
-        return code;
-    };
-    if ((rc = check_ready(c))) return rc;
-    if (!mix || R < 1 || n <= NFFT / 2) return fail(BSRNN_EARG, "bsrnn_evaluate: need n > 1024 samples, got %lld", (long long)n);
-    // the metrics read mix and speech after the estimate is written, and the re-run below reads them again: whatever the policy
-    if (ranges_overlap(est_out, (size_t)R * n_est * sizeof(float), mix, (size_t)R * n * sizeof(float)) ||
-        ranges_overlap(est_out, (size_t)R * n_est * sizeof(float), speech, (size_t)R * n * sizeof(float)))
-        return fail(BSRNN_EARG, "bsrnn_evaluate: est_out must not overlap mix or speech (the metrics and a re-run of the call read them after the estimate is written)");
-    hipStream_t s = (hipStream_t)stream;
-    ENTER_CALL(c, s);
-    if (!est_out && hipMalloc((void**)&est, (size_t)R * n_est * sizeof(float)) != hipSuccess) {
-        est = nullptr;
-        return fail(BSRNN_EHIP, "bsrnn_evaluate: out of device memory");
-    }
-    auto run = [&]() -> int {
-    // x_time and the estimate's spectrum (left in Yf, frame-major)                               m_dataset.py:186-195
-    if ((rc = bsrnn_separate(c, mix, est, R, n, stream))) return rc;
-    // waveform_speech_freq: the clean signal through the same analysis (Xf is free once the mask launch ran)   :196
-    launch_stft(c->tb, speech, c->Xf, R, n, T, s);
-
-    const int chunks = metric_time_chunks(n_est), FB = 512, IB = 256;
-    const size_t n_time = (size_t)R * chunks * METRIC_TIME_Q, n_si = (size_t)R * chunks * 2, n_freq = (size_t)FB * 2, n_in = IB;
-    const size_t n_part = n_time + n_si + n_freq + n_in;
-    if ((!d_part && hipMalloc((void**)&d_part, n_part * sizeof(double)) != hipSuccess) || (!d_alpha && hipMalloc((void**)&d_alpha, R * sizeof(float)) != hipSuccess))
-        return fail(BSRNN_EHIP, "bsrnn_evaluate: out of device memory");
-    double *p_time = d_part, *p_si = p_time + n_time, *p_freq = p_si + n_si, *p_in = p_freq + n_freq;
-    launch_metric_time(est, speech, mix, R, n_est, n, p_time, s);
-    launch_metric_freq(c->tb, c->Yf, c->Xf, R * T, p_freq, FB, s);
-    launch_metric_input_sdr(speech, mix, R, n, p_in, IB, s);
-    std::vector<double> h(n_part);
-    if (hipMemcpyAsync(h.data(), d_part, (n_time) * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return fail(BSRNN_EHIP, "bsrnn_evaluate: %s", hipGetErrorString(hipGetLastError()));
-    std::vector<double> q((size_t)R * METRIC_TIME_Q, 0.0);
-    for (int r = 0; r < R; ++r)
-        for (int ch = 0; ch < chunks; ++ch)
-            for (int i = 0; i < METRIC_TIME_Q; ++i) q[(size_t)r * METRIC_TIME_Q + i] += h[((size_t)r * chunks + ch) * METRIC_TIME_Q + i];
-    // SI-SDR: alpha = (<x, s> + eps) / (<s, s> + eps) in fp32, eps = float32 machine epsilon
-    const float eps = 1.1920928955078125e-07f;
-    std::vector<float> alpha(R);
-    for (int r = 0; r < R; ++r) alpha[r] = ((float)q[(size_t)r * METRIC_TIME_Q + 2] + eps) / ((float)q[(size_t)r * METRIC_TIME_Q + 0] + eps);
-    if (hipMemcpyAsync(d_alpha, alpha.data(), R * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
-        return fail(BSRNN_EHIP, "bsrnn_evaluate: %s", hipGetErrorString(hipGetLastError()));
-    launch_metric_sisdr(est, speech, d_alpha, R, n_est, n, p_si, s);
-    if (hipMemcpyAsync(h.data() + n_time, p_si, (n_si + n_freq + n_in) * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return fail(BSRNN_EHIP, "bsrnn_evaluate: %s", hipGetErrorString(hipGetLastError()));
-
-    double sdr = 0, sisdr = 0, l1_time = 0, m2 = 0, md2 = 0;
-    for (int r = 0; r < R; ++r) {
-        const double* qr = &q[(size_t)r * METRIC_TIME_Q];
-        sdr += 10.0 * log10((qr[0] + 1e-9) / (qr[1] + 1e-9));                                   // m_dataset.py:214-217
-        double ts2 = 0, nz2 = 0;
-        for (int ch = 0; ch < chunks; ++ch) { ts2 += h[n_time + ((size_t)r * chunks + ch) * 2]; nz2 += h[n_time + ((size_t)r * chunks + ch) * 2 + 1]; }
-        sisdr += 10.0 * log10((ts2 + (double)eps) / (nz2 + (double)eps));
-        l1_time += qr[4]; m2 += qr[5]; md2 += qr[6];
-    }
-    double l1_re = 0, l1_im = 0, in_sdr = 0;
-    for (int b = 0; b < FB; ++b) { l1_re += h[n_time + n_si + 2 * b]; l1_im += h[n_time + n_si + 2 * b + 1]; }
-    for (int b = 0; b < IB; ++b) in_sdr += h[n_time + n_si + n_freq + b];
-    l1_time /= (double)R * (double)n_est;                                                      // L1Loss(reduction='mean'), train.py:54
-    l1_re /= (double)R * NBINS * T;
-    l1_im /= (double)R * NBINS * T;
-    metrics[BSRNN_M_LOSS] = l1_time + l1_re + l1_im;                                           // m_dataset.py:211-213
-    metrics[BSRNN_M_SDR] = sdr / R;
-    metrics[BSRNN_M_INPUT_SDR] = in_sdr / (double)n;
-    metrics[BSRNN_M_SISDR] = sisdr / R;
-    metrics[BSRNN_M_L1_TIME] = l1_time;
-    metrics[BSRNN_M_L1_RE] = l1_re;
-    metrics[BSRNN_M_L1_IM] = l1_im;
-    metrics[BSRNN_M_SEPARATION_DB] = 10.0 * log(m2 / md2);                                     // natural log, infer.py:47
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(BSRNN_EHIP, "bsrnn_evaluate: %s", hipGetErrorString(e));
-    };
-    // A synchronous entry point: whatever the context's range policy, the guard word is handled before the metrics are returned, as under
-    // the default policy (finish_call: a structural fall-back, or the exact-fp32 kernels for an operand that left the fp16 range)
-    if ((rc = run())) return cleanup(rc);
-    return cleanup(finish_call(c, s, run, true));
-}
-
-// --------------------------------------------------------------------------- ragged evaluate: the metrics per clip of a ragged batch
-// A clip is the unit of the reference's metrics (one `sample`: all rows of one file, one length; validate.py and train.py:132-150 average
-// per-clip numbers), so a ragged evaluate returns the eight numbers PER CLIP, each what bsrnn_evaluate gives for that clip alone: the
-// reference's `sdr2` sums over the rows of its own clip, which all have one length, and nothing is summed across clips.
-// Flow: bsrnn_separate_ragged(mix) with the per-clip lengths expanded to rows (Yf keeps the estimate's spectrum, padded frames zero) ->
-// the clean signal through the ragged analysis into Xf -> the four ragged metric kernels (alpha of the SI-SDR pass formed on the device)
-// -> one download of the partial sums -> metrics_host.h per clip, in a fixed order.
+// --------------------------------------------------------------------------- validation metrics: the eight numbers per clip
+// m_dataset.py:182-226 (`infer` + `train_infer` without the discriminator) and infer.py:44-47.  A clip is the unit of the reference's
+// metrics (one `sample`: all rows of one file, one length; validate.py and train.py:132-150 average per-clip numbers): the reference's
+// `sdr2` sums over the rows of its own clip, which all have one length, and nothing is summed across clips.  The three entry points are
+// views of one arithmetic - bsrnn_evaluate: one clip of R rows, a rectangle; bsrnn_evaluate_ragged: clips of different lengths;
+// bsrnn_evaluate_long_ragged: the same in segments - and share one tail: the table [row lengths | clips] goes up through er.table, one
+// family of metric kernels (metrics.hip) leaves its sums in er.d_part, ONE download, and metrics_host.h turns them into the numbers per
+// clip in a fixed order.  No call has a round trip in its middle (alpha of the SI-SDR pass is formed on the device) and a call that fits
+// the context's grow-only blocks allocates nothing.
 static_assert(CM_LOSS == BSRNN_M_LOSS && CM_SDR == BSRNN_M_SDR && CM_INPUT_SDR == BSRNN_M_INPUT_SDR && CM_SISDR == BSRNN_M_SISDR &&
               CM_L1_TIME == BSRNN_M_L1_TIME && CM_L1_RE == BSRNN_M_L1_RE && CM_L1_IM == BSRNN_M_L1_IM &&
-              CM_SEPARATION_DB == BSRNN_M_SEPARATION_DB && CM_COUNT == BSRNN_N_METRICS && CLIP_ROW_Q == METRIC_TIME_Q + 2, "metrics_host.h");
+              CM_SEPARATION_DB == BSRNN_M_SEPARATION_DB && CM_COUNT == BSRNN_N_METRICS, "metrics_host.h");
+
+// Where a call's sums lie in er.d_part and its pinned mirror: [time R x slots x 7 | si R x slots x 2, two-pass calls only | freq R x FB x 2 |
+// in n_clips x IB], slots = the time grid's workgroups (or accumulator slots) per row
+struct EvalSums {
+    int slots, FB, IB;
+    size_t n_time, n_si, n_freq, n_in;
+    EvalSums(int R, int n_clips, int slots_, bool two_pass, int FB_)
+        : slots(slots_), FB(FB_), IB(metric_input_sdr_blocks(n_clips)), n_time((size_t)R * slots_ * METRIC_TIME_Q),
+          n_si(two_pass ? (size_t)R * slots_ * 2 : 0), n_freq((size_t)R * FB_ * 2), n_in((size_t)n_clips * IB) {}
+    size_t total() const { return n_time + n_si + n_freq + n_in; }
+    double* time(double* p) const { return p; }
+    double* si(double* p) const { return p + n_time; }
+    double* freq(double* p) const { return p + n_time + n_si; }
+    double* in(double* p) const { return p + n_time + n_si + n_freq; }
+};
+
+static std::vector<MetricClip> clip_table(const std::vector<int>& first_row, const int32_t* clip_rows_host, const int64_t* clip_lens_host, int n_clips)
+{
+    std::vector<MetricClip> clips(n_clips);
+    for (int i = 0; i < n_clips; ++i) clips[i] = MetricClip{first_row[i], clip_rows_host ? clip_rows_host[i] : 1, clip_lens_host[i]};
+    return clips;
+}
+
+// The metric kernels' table of a call, [R int64 row lengths | MetricClip per clip], through er.table in front of the call's kernels.  The
+// block on the device is not touched before the next call, so a re-run sees the same table.
+struct EvalTable { const int64_t* lens = nullptr; const MetricClip* clips = nullptr; };      // on the device
+static int eval_table_upload(bsrnn_ctx* c, const std::vector<int64_t>& row_lens, const std::vector<MetricClip>& clips, hipStream_t s, EvalTable& t)
+{
+    bsrnn_ctx::EvalRagged& er = c->er;
+    const size_t b_lens = row_lens.size() * sizeof(int64_t), b_clips = clips.size() * sizeof(MetricClip);
+    if (int rc = er.table.upload(b_lens + b_clips, s, [&](char* h) { memcpy(h, row_lens.data(), b_lens); memcpy(h + b_lens, clips.data(), b_clips); }))
+        return rc;
+    t.lens = reinterpret_cast<const int64_t*>(er.table.d);
+    t.clips = reinterpret_cast<const MetricClip*>(er.table.d + b_lens);
+    return 0;
+}
+
+// The end of every evaluate call: the one download of the sums, then the numbers per clip (metrics_host.h)
+static int eval_finish(bsrnn_ctx* c, hipStream_t s, const EvalSums& q, const std::vector<MetricClip>& clips, double* metrics)
+{
+    bsrnn_ctx::EvalRagged& er = c->er;
+    HIP_TRY(hipMemcpyAsync(er.h_part, er.d_part, q.total() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    clip_metrics_from_partials(clips.data(), (int)clips.size(), q.time(er.h_part), q.n_si ? q.si(er.h_part) : nullptr, q.slots, q.freq(er.h_part),
+                               q.FB, q.in(er.h_part), q.IB, metrics);
+    return 0;
+}
 
 // The context's scratch (bsrnn_ctx::EvalRagged) for a call of these sizes; grow-only
 static int eval_ragged_reserve(bsrnn_ctx* c, size_t n_part, size_t n_est)
@@ -2041,6 +1995,55 @@ static int eval_ragged_reserve(bsrnn_ctx* c, size_t n_part, size_t n_est)
     return 0;
 }
 
+// The rectangle [R][n] as the batch of one clip {0, R, n}: R equal lengths, wave_stride = n, out_stride = n_est.  The separation stays
+// bsrnn_separate (it runs the concurrent row blocks for large R); without est_out the estimate lives in er.d_est, which is grow-only and
+// goes with the context.
+int bsrnn_evaluate(bsrnn_ctx* c, const float* mix, const float* speech, int32_t R, int64_t n, float* est_out,
+                   double* metrics, void* stream)
+{
+    if (!metrics || !speech) return fail(BSRNN_EARG, "bsrnn_evaluate: null argument");
+    const int T = 1 + (int)(n / HOPS);
+    const int64_t n_est = (int64_t)(T - 1) * HOPS;
+    int rc = 0;
+    if ((rc = check_ready(c))) return rc;
+    if (!mix || R < 1 || n <= NFFT / 2) return fail(BSRNN_EARG, "bsrnn_evaluate: need n > 1024 samples, got %lld", (long long)n);
+    // the metrics read mix and speech after the estimate is written, and the re-run below reads them again: whatever the policy
+    if (ranges_overlap(est_out, (size_t)R * n_est * sizeof(float), mix, (size_t)R * n * sizeof(float)) ||
+        ranges_overlap(est_out, (size_t)R * n_est * sizeof(float), speech, (size_t)R * n * sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_evaluate: est_out must not overlap mix or speech (the metrics and a re-run of the call read them after the estimate is written)");
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+
+    const EvalSums sums(R, 1, metric_time_chunks(n_est), true, std::min(T, 16));
+    if ((rc = eval_ragged_reserve(c, sums.total(), est_out ? 0 : (size_t)R * n_est))) return rc;
+    bsrnn_ctx::EvalRagged& er = c->er;
+    float* est = est_out ? est_out : er.d_est;
+    std::vector<int64_t> row_lens(R);
+    std::fill(row_lens.begin(), row_lens.end(), n);
+    const std::vector<MetricClip> clips{MetricClip{0, R, n}};
+    EvalTable tab;
+    if ((rc = eval_table_upload(c, row_lens, clips, s, tab))) return rc;
+
+    auto run = [&]() -> int {
+        // x_time and the estimate's spectrum (left in Yf, frame-major)                               m_dataset.py:186-195
+        if (int rc2 = bsrnn_separate(c, mix, est, R, n, stream)) return rc2;
+        // waveform_speech_freq: the clean signal through the same analysis (Xf is free once the mask launch ran)   :196
+        launch_stft(c->tb, speech, c->Xf, R, n, T, s);
+        launch_metric_time_ragged(est, speech, mix, tab.lens, R, T, n_est, n, sums.time(er.d_part), s);
+        launch_metric_sisdr_ragged(est, speech, tab.lens, R, T, n_est, n, sums.time(er.d_part), sums.si(er.d_part), s);
+        launch_metric_freq_ragged(c->tb, c->Yf, c->Xf, tab.lens, R, T, sums.freq(er.d_part), sums.FB, s);
+        launch_metric_input_sdr_ragged(speech, mix, tab.clips, 1, n, sums.in(er.d_part), sums.IB, s);
+        HIP_TRY(hipGetLastError());
+        return eval_finish(c, s, sums, clips, metrics);
+    };
+    // A synchronous entry point: whatever the context's range policy, the guard word is handled before the metrics are returned, as under
+    // the default policy (finish_call: a structural fall-back, or the exact-fp32 kernels for an operand that left the fp16 range)
+    if ((rc = run())) return rc;
+    return finish_call(c, s, run, true);
+}
+
+// Flow of the ragged call: bsrnn_separate_ragged(mix) with the per-clip lengths expanded to rows (Yf keeps the estimate's spectrum, padded
+// frames zero) -> the clean signal through the ragged analysis into Xf -> the four metric kernels -> the shared finish.
 int bsrnn_evaluate_ragged(bsrnn_ctx* c, const float* mix, const float* speech, int64_t wave_stride, const int64_t* clip_lens_host,
                           const int32_t* clip_rows_host, int32_t n_clips, float* est_out, double* metrics, void* stream)
 {
@@ -2062,54 +2065,25 @@ int bsrnn_evaluate_ragged(bsrnn_ctx* c, const float* mix, const float* speech, i
     hipStream_t s = (hipStream_t)stream;
     ENTER_CALL(c, s);
 
-    const int chunks = metric_time_chunks(q.out_stride), FB = std::min(T, 16), IB = 64;
-    const size_t n_time = (size_t)R * chunks * METRIC_TIME_Q, n_si = (size_t)R * chunks * 2, n_freq = (size_t)R * FB * 2, n_in = (size_t)n_clips * IB;
-    const size_t n_part = n_time + n_si + n_freq + n_in;
-    const size_t b_lens = (size_t)R * sizeof(int64_t), b_table = b_lens + (size_t)n_clips * sizeof(MetricClip);
-    if ((rc = eval_ragged_reserve(c, n_part, est_out ? 0 : (size_t)R * q.out_stride))) return rc;
+    const EvalSums sums(R, n_clips, metric_time_chunks(q.out_stride), true, std::min(T, 16));
+    if ((rc = eval_ragged_reserve(c, sums.total(), est_out ? 0 : (size_t)R * q.out_stride))) return rc;
     bsrnn_ctx::EvalRagged& er = c->er;
     float* est = est_out ? est_out : er.d_est;
-    rc = er.table.upload(b_table, s, [&](char* h) {
-        memcpy(h, row_lens.data(), b_lens);
-        MetricClip* mc = reinterpret_cast<MetricClip*>(h + b_lens);
-        for (int i = 0; i < n_clips; ++i) mc[i] = MetricClip{first_row[i], clip_rows_host ? clip_rows_host[i] : 1, clip_lens_host[i]};
-    });
-    if (rc) return rc;
-    const int64_t* d_lens = reinterpret_cast<const int64_t*>(er.table.d);
-    const MetricClip* d_clips = reinterpret_cast<const MetricClip*>(er.table.d + b_lens);
-    double *p_time = er.d_part, *p_si = p_time + n_time, *p_freq = p_si + n_si, *p_in = p_freq + n_freq;
+    const std::vector<MetricClip> clips = clip_table(first_row, clip_rows_host, clip_lens_host, n_clips);
+    EvalTable tab;
+    if ((rc = eval_table_upload(c, row_lens, clips, s, tab))) return rc;
 
-    // a re-run sees the same table: the block on the device is not touched before the next call
     auto run = [&]() -> int {
         // x_time of every row and the estimate's spectrum (left in Yf, frame-major, padded frames zero)      m_dataset.py:186-195
         if (int rc2 = bsrnn_separate_ragged(c, mix, wave_stride, row_lens.data(), est, R, stream)) return rc2;
         // waveform_speech_freq: the clean signal through the same analysis (Xf is free once the mask launch ran)   :196
-        launch_stft_ragged(c->tb, speech, wave_stride, d_lens, c->Xf, R, T, s);
-        launch_metric_time_ragged(est, speech, mix, d_lens, R, T, q.out_stride, wave_stride, p_time, s);
-        launch_metric_sisdr_ragged(est, speech, d_lens, R, T, q.out_stride, wave_stride, p_time, p_si, s);
-        launch_metric_freq_ragged(c->tb, c->Yf, c->Xf, d_lens, R, T, p_freq, FB, s);
-        launch_metric_input_sdr_ragged(speech, mix, d_clips, n_clips, wave_stride, p_in, IB, s);
+        launch_stft_ragged(c->tb, speech, wave_stride, tab.lens, c->Xf, R, T, s);
+        launch_metric_time_ragged(est, speech, mix, tab.lens, R, T, q.out_stride, wave_stride, sums.time(er.d_part), s);
+        launch_metric_sisdr_ragged(est, speech, tab.lens, R, T, q.out_stride, wave_stride, sums.time(er.d_part), sums.si(er.d_part), s);
+        launch_metric_freq_ragged(c->tb, c->Yf, c->Xf, tab.lens, R, T, sums.freq(er.d_part), sums.FB, s);
+        launch_metric_input_sdr_ragged(speech, mix, tab.clips, n_clips, wave_stride, sums.in(er.d_part), sums.IB, s);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(er.h_part, er.d_part, n_part * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        const double *h_time = er.h_part, *h_si = h_time + n_time, *h_freq = h_si + n_si, *h_in = h_freq + n_freq;
-        std::vector<double> rows;
-        for (int i = 0; i < n_clips; ++i) {
-            const int r0 = first_row[i], nr = clip_rows_host ? clip_rows_host[i] : 1;
-            rows.assign((size_t)nr * CLIP_ROW_Q, 0.0);
-            double re = 0, im = 0;
-            for (int r = 0; r < nr; ++r) {
-                const size_t row = (size_t)(r0 + r);
-                for (int j = 0; j < METRIC_TIME_Q; ++j) rows[(size_t)r * CLIP_ROW_Q + j] = add_in_order(h_time + row * chunks * METRIC_TIME_Q + j, chunks, METRIC_TIME_Q);
-                for (int j = 0; j < 2; ++j) rows[(size_t)r * CLIP_ROW_Q + METRIC_TIME_Q + j] = add_in_order(h_si + row * chunks * 2 + j, chunks, 2);
-                re += add_in_order(h_freq + row * FB * 2, FB, 2);
-                im += add_in_order(h_freq + row * FB * 2 + 1, FB, 2);
-            }
-            const int64_t n = clip_lens_host[i], Tc = ragged_frames(n);
-            finish_clip_metrics(rows.data(), nr, re, im, add_in_order(h_in + (size_t)i * IB, IB, 1), n, Tc, (Tc - 1) * HOPS,
-                                metrics + (size_t)i * BSRNN_N_METRICS);
-        }
-        return 0;
+        return eval_finish(c, s, sums, clips, metrics);
     };
     // A synchronous entry point: whatever the context's range policy, the guard word is handled before the metrics are returned, as in
     // bsrnn_evaluate (finish_call: a structural fall-back, or the whole flow again on the exact-fp32 kernels from the same inputs and lengths)
@@ -2156,26 +2130,20 @@ int bsrnn_evaluate_long_ragged(bsrnn_ctx* c, const float* mix, const float* spee
     hipStream_t s = (hipStream_t)stream;
     ENTER_CALL(c, s);
 
-    const int seg = seg_frames, S = METRIC_SEG_SLOTS, IB = 64;
-    const size_t n_time = (size_t)R * S * METRIC_TIME_Q, n_freq = (size_t)R * S * 2, n_in = (size_t)n_clips * IB;
-    const size_t n_part = n_time + n_freq + n_in;
-    const size_t b_lens = (size_t)R * sizeof(int64_t), b_table = b_lens + (size_t)n_clips * sizeof(MetricClip);
+    const int seg = seg_frames;
+    const EvalSums sums(R, n_clips, METRIC_SEG_SLOTS, false, METRIC_SEG_SLOTS);
     const int64_t seg_stride = (int64_t)seg * HOPS;
-    if ((rc = eval_ragged_reserve(c, n_part, est_out ? 0 : (size_t)R * seg_stride))) return rc;
+    if ((rc = eval_ragged_reserve(c, sums.total(), est_out ? 0 : (size_t)R * seg_stride))) return rc;
     bsrnn_ctx::EvalRagged& er = c->er;
-    rc = er.table.upload(b_table, s, [&](char* h) {
-        memcpy(h, row_lens.data(), b_lens);
-        MetricClip* mc = reinterpret_cast<MetricClip*>(h + b_lens);
-        for (int i = 0; i < n_clips; ++i) mc[i] = MetricClip{first_row[i], clip_rows_host ? clip_rows_host[i] : 1, clip_lens_host[i]};
-    });
-    if (rc) return rc;
-    const MetricClip* d_clips = reinterpret_cast<const MetricClip*>(er.table.d + b_lens);
-    double *p_time = er.d_part, *p_freq = p_time + n_time, *p_in = p_freq + n_freq;
-    HIP_TRY(hipMemsetAsync(p_time, 0, (n_time + n_freq) * sizeof(double), s));
-    launch_metric_input_sdr_ragged(speech, mix, d_clips, n_clips, wave_stride, p_in, IB, s);
+    const std::vector<MetricClip> clips = clip_table(first_row, clip_rows_host, clip_lens_host, n_clips);
+    EvalTable tab;                                                    // (its lengths are not read: long_ragged_segments uploads the segments' own)
+    if ((rc = eval_table_upload(c, row_lens, clips, s, tab))) return rc;
+    double *p_time = sums.time(er.d_part), *p_freq = sums.freq(er.d_part);
+    HIP_TRY(hipMemsetAsync(p_time, 0, (sums.n_time + sums.n_freq) * sizeof(double), s));
+    launch_metric_input_sdr_ragged(speech, mix, tab.clips, n_clips, wave_stride, sums.in(er.d_part), sums.IB, s);
     HIP_TRY(hipGetLastError());
 
-    auto sums = [&](int ta, int te, int Ri, const int64_t* d_lens, const float* seg_est) -> int {
+    auto segment_sums = [&](int ta, int te, int Ri, const int64_t* d_lens, const float* seg_est) -> int {
         // waveform_speech_freq of the segment's frames (Xf is free once the mask stage has run), then the segment's sums       m_dataset.py:196-213
         launch_stft_ragged_segment(c->tb, speech, wave_stride, d_lens, c->Xf, Ri, ta, te, s);
         launch_metric_ragged_segment(c->tb, seg_est, est_out ? q.out_stride : seg_stride, speech, mix, d_lens, wave_stride, c->Yf, c->Xf, Ri, ta, te,
@@ -2184,28 +2152,9 @@ int bsrnn_evaluate_long_ragged(bsrnn_ctx* c, const float* mix, const float* spee
         return 0;
     };
     if ((rc = long_ragged_segments(c, plan, mix, wave_stride, row_lens.data(), est_out ? est_out : er.d_est, est_out ? q.out_stride : seg_stride,
-                                   est_out != nullptr, R, seg, s, true, sums)))
+                                   est_out != nullptr, R, seg, s, true, segment_sums)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(er.h_part, er.d_part, n_part * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const double *h_time = er.h_part, *h_freq = h_time + n_time, *h_in = h_freq + n_freq;
-    std::vector<double> rows;
-    for (int i = 0; i < n_clips; ++i) {
-        const int r0 = first_row[i], nr = clip_rows_host ? clip_rows_host[i] : 1;
-        rows.assign((size_t)nr * CLIP_ROW_Q, 0.0);
-        double re = 0, im = 0;
-        for (int r = 0; r < nr; ++r) {
-            const size_t row = (size_t)(r0 + r);
-            for (int j = 0; j < METRIC_TIME_Q; ++j) rows[(size_t)r * CLIP_ROW_Q + j] = add_in_order(h_time + row * S * METRIC_TIME_Q + j, S, METRIC_TIME_Q);
-            sisdr_sums_from_totals(&rows[(size_t)r * CLIP_ROW_Q]);
-            re += add_in_order(h_freq + row * S * 2, S, 2);
-            im += add_in_order(h_freq + row * S * 2 + 1, S, 2);
-        }
-        const int64_t n = clip_lens_host[i], Tc = ragged_frames(n);
-        finish_clip_metrics(rows.data(), nr, re, im, add_in_order(h_in + (size_t)i * IB, IB, 1), n, Tc, (Tc - 1) * HOPS,
-                            metrics + (size_t)i * BSRNN_N_METRICS);
-    }
-    return 0;
+    return eval_finish(c, s, sums, clips, metrics);
 }
 
 // --------------------------------------------------------------------------- dialog / background section mining

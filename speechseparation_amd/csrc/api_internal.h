@@ -225,11 +225,12 @@ struct bsrnn_ctx {
     // every call, and a cached table per frame-row count would make first-use work the rule and flush the bounded cache.)  Grow-only.
     UploadRing rg;
 
-    // Ragged evaluate (bsrnn_evaluate_ragged): the metric kernels' table [R int64 row lengths | n_clips MetricClip] travels through a ring
-    // of its own - the bsrnn_separate_ragged inside an evaluate call overwrites rg's device block - and their scratch is one device block
-    // [partial sums, doubles | the estimate when the caller wants none] with a pinned mirror of the partials for the one download of a
-    // call.  All grow-only: a call that fits allocates nothing.  bsrnn_evaluate_long_ragged uses the same blocks: its accumulators in the
-    // place of the partial sums, and an estimate of ONE segment ([R][seg * 1024]) where the caller wants none.
+    // The evaluate calls (bsrnn_evaluate, bsrnn_evaluate_ragged, bsrnn_evaluate_long_ragged): the metric kernels' table [R int64 row lengths |
+    // n_clips MetricClip] travels through a ring of its own - the bsrnn_separate_ragged inside an evaluate call overwrites rg's device block -
+    // and their scratch is two device blocks, the sums (doubles; accumulators in the segmented call) with a pinned mirror for the one
+    // download of a call, and the estimate when the caller wants none: [R][n_est], or ONE segment [R][seg * 1024] in the segmented call.
+    // All grow-only: a call that fits allocates nothing, and the blocks are RETAINED until the context goes - the estimate block too, about
+    // 32 MB after a bsrnn_evaluate of 64 rows x 128 000 samples without est_out.
     struct EvalRagged {
         UploadRing table;
         size_t part_cap = 0, est_cap = 0;             // doubles / floats the scratch holds

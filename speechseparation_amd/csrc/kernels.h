@@ -9,6 +9,7 @@
 #include "train_ragged_host.h"  // TrainClip: what the ragged training loss kernels know of a clip (HIP-free)
 #include "pool_host.h"          // PoolEntry: what the native session pool's copy kernels know of a row (HIP-free)
 #include "convolve_host.h"      // ConvRow: what the FIR convolution's kernels know of a row (HIP-free)
+#include "metrics_host.h"       // MetricClip, METRIC_TIME_Q: what the metric kernels and their host tail agree on (HIP-free)
 
 namespace bsrnn {
 
@@ -327,19 +328,14 @@ void launch_fir_group(const FftTables& tb, const ConvRow* rows, int row0, int n_
                       float* out, int64_t out_stride, float* X, float* Y, hipStream_t s);
 
 // ------------------------------------------------------------------ validation metrics (metrics.hip)
-// Per-workgroup partial sums in double; the host adds them.  est [R][n_est]; speech, mix [R][n_in] (first n_est used).
-constexpr int METRIC_TIME_Q = 7;     // sum s^2, (x-s)^2, x*s, x^2, |x-s|, m^2, (m-x)^2
+// One family for the three evaluate calls: per-workgroup partial sums in double, which the host adds (metrics_host.h: METRIC_TIME_Q sums
+// per row - s^2, (x-s)^2, x*s, x^2, |x-s|, m^2, (m-x)^2 - and MetricClip).  A batch is rows and clips of their own lengths: lens [R] the
+// rows' lengths on the device (T_r = 1 + lens[r] / 1024 frames inside the rectangle R x Tmax, n_est_r = (T_r - 1) * 1024 samples), est rows
+// out_stride floats apart, speech and mix rows wave_stride floats apart.  bsrnn_evaluate's rectangle [R][n] is the batch of one clip {0, R, n}
+// with R equal lengths, wave_stride = n and out_stride = n_est.  Every slot of every partial array is written.
+// chunks = metric_time_chunks((Tmax - 1) * 1024).
 int metric_time_chunks(int64_t n_est);                                   // workgroups per row of the two row-wise kernels
-void launch_metric_time(const float* est, const float* speech, const float* mix, int R, int64_t n_est, int64_t n_in,
-                        double* part /* [R][chunks][7] */, hipStream_t s);
-void launch_metric_sisdr(const float* est, const float* speech, const float* alpha /* [R] */, int R, int64_t n_est, int64_t n_in,
-                         double* part /* [R][chunks][2] */, hipStream_t s);
-void launch_metric_input_sdr(const float* speech, const float* mix, int R, int64_t n, double* part /* [blocks] */, int blocks, hipStream_t s);
-void launch_metric_freq(const FftTables& tb, const float* Yf, const float* Sf, int M, double* part /* [blocks][2] */, int blocks, hipStream_t s);
-// The same for rows and clips of different lengths (bsrnn_evaluate_ragged): lens [R] the rows' lengths on the device (T_r = 1 + lens[r] / 1024
-// frames inside the rectangle R x Tmax, n_est_r = (T_r - 1) * 1024 samples), est rows out_stride floats apart, speech and mix rows wave_stride
-// floats apart.  Every slot of every partial array is written.  chunks = metric_time_chunks((Tmax - 1) * 1024).
-struct MetricClip { int first, rows; int64_t len; };                    // a clip: its first row, its rows, their common length
+int metric_input_sdr_blocks(int n_clips);                                // workgroups per clip of the input-SDR kernel, for every entry point
 void launch_metric_time_ragged(const float* est, const float* speech, const float* mix, const int64_t* lens, int R, int Tmax,
                                int64_t out_stride, int64_t wave_stride, double* part /* [R][chunks][7] */, hipStream_t s);
 void launch_metric_sisdr_ragged(const float* est, const float* speech, const int64_t* lens, int R, int Tmax, int64_t out_stride,

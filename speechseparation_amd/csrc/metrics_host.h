@@ -1,19 +1,27 @@
-// The host end of the validation metrics of one CLIP (bsrnn_evaluate_ragged): from the sums the metric kernels leave - per row, per clip - to
-// the eight numbers of include/bsrnn_hip.h (BSRNN_M_*), by the arithmetic bsrnn_evaluate documents: m_dataset.py:202-226, infer.py:44-47.
+// The host end of the validation metrics (bsrnn_evaluate, bsrnn_evaluate_ragged, bsrnn_evaluate_long_ragged): from the sums the metric
+// kernels leave - per row, per clip - to the eight numbers of include/bsrnn_hip.h (BSRNN_M_*) of every CLIP, by the arithmetic bsrnn_evaluate
+// documents: m_dataset.py:202-226, infer.py:44-47.  The one tail of the three entry points.
 // Host arithmetic only, in a fixed order, so tests run it without a GPU (tests/cpp/metrics_finish_check.cpp).
 #pragma once
+#include "descriptors.h"
+
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace bsrnn {
+
+// A clip as the metric kernels and this file see it: its first row, its rows, their common length (the rectangular call: {0, R, n})
+struct MetricClip { int first, rows; int64_t len; };
 
 // the order of BSRNN_M_* (api.hip asserts that the two agree)
 enum ClipMetric { CM_LOSS, CM_SDR, CM_INPUT_SDR, CM_SISDR, CM_L1_TIME, CM_L1_RE, CM_L1_IM, CM_SEPARATION_DB, CM_COUNT };
 
 // Sums of one row over its n_est samples (x the estimate, s the clean signal, m the mixture): the seven of the time kernel -
 // s^2, (x-s)^2, x*s, x^2, |x-s|, m^2, (m-x)^2 - then the SI-SDR pass's (alpha s)^2 and (alpha s - x)^2
-constexpr int CLIP_ROW_Q = 9;
+constexpr int METRIC_TIME_Q = 7;
+constexpr int CLIP_ROW_Q = METRIC_TIME_Q + 2;
 constexpr double SISDR_EPS = 1.1920928955078125e-07;          // float32 machine epsilon (torchmetrics)
 
 // Partial sums p[0], p[stride], ... added in index order
@@ -64,6 +72,34 @@ inline void finish_clip_metrics(const double* row_sums, int rows, double re_sum,
     out[CM_L1_RE] = l1_re;
     out[CM_L1_IM] = l1_im;
     out[CM_SEPARATION_DB] = 10.0 * std::log(m2 / md2);                                         // natural log, infer.py:47
+}
+
+// The downloaded sums of a call to metrics [n_clips][CM_COUNT]: per clip, its rows in order, every row's partials added in index order.
+// time [R][slots][7]; si [R][slots][2], the SI-SDR pass's partials, or null: the row's two sums come from its totals (sisdr_sums_from_totals);
+// freq [R][freq_blocks][2]; in_sdr [n_clips][in_blocks].  R = all clips' rows.
+inline void clip_metrics_from_partials(const MetricClip* clips, int n_clips, const double* time, const double* si, int slots, const double* freq,
+                                       int freq_blocks, const double* in_sdr, int in_blocks, double* metrics)
+{
+    std::vector<double> rows;
+    for (int i = 0; i < n_clips; ++i) {
+        const MetricClip& k = clips[i];
+        rows.assign((size_t)k.rows * CLIP_ROW_Q, 0.0);
+        double re = 0, im = 0;
+        for (int r = 0; r < k.rows; ++r) {
+            const size_t row = (size_t)(k.first + r);
+            double* q = &rows[(size_t)r * CLIP_ROW_Q];
+            for (int j = 0; j < METRIC_TIME_Q; ++j) q[j] = add_in_order(time + row * slots * METRIC_TIME_Q + j, slots, METRIC_TIME_Q);
+            if (si)
+                for (int j = 0; j < 2; ++j) q[METRIC_TIME_Q + j] = add_in_order(si + row * slots * 2 + j, slots, 2);
+            else
+                sisdr_sums_from_totals(q);
+            re += add_in_order(freq + row * freq_blocks * 2, freq_blocks, 2);
+            im += add_in_order(freq + row * freq_blocks * 2 + 1, freq_blocks, 2);
+        }
+        const int64_t T = 1 + k.len / HOPS;
+        finish_clip_metrics(rows.data(), k.rows, re, im, add_in_order(in_sdr + (size_t)i * in_blocks, in_blocks, 1), k.len, T, (T - 1) * HOPS,
+                            metrics + (size_t)i * CM_COUNT);
+    }
 }
 
 }  // namespace bsrnn

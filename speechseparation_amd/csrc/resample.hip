@@ -220,7 +220,7 @@ void launch_resample(ResampleArgs g, int R, hipStream_t s)
 {
     const int blocks = g.n_tiles + (g.carry ? 1 : 0);
     if (blocks < 1 || R < 1) return;
-    // 16-byte loads where every row of the caller's block starts aligned, as metric_time_kernel decides: the base and the stride
+    // 16-byte loads where every row of the caller's block starts aligned, as launch_metric_time_ragged decides: the base and the stride
     const int vec = g.b && ((uintptr_t)g.b & 15) == 0 && g.b_stride % 4 == 0;
     for (int r = 0; r < R; r += 65535) {             // (rows are the grid's y: 65535 per launch)
         const int rows = R - r < 65535 ? R - r : 65535;

@@ -1,6 +1,6 @@
 // Test helper: checks the clip arithmetic of a ragged evaluate (speechseparation_amd/csrc/plan_host.h: clip_shape) against literals and the
-// per-clip finalisation of the metrics (metrics_host.h: finish_clip_metrics) against closed forms, and prints "ok"; the first mismatch is
-// printed and the exit status is 1.  Host code only.
+// per-clip finalisation of the metrics (metrics_host.h: finish_clip_metrics) against closed forms and the gather in front of it
+// (clip_metrics_from_partials) against plain loops, and prints "ok"; every mismatch is printed and the exit status is 1.  Host code only.
 #include "metrics_host.h"
 #include "plan_host.h"
 
@@ -126,10 +126,57 @@ static void check_finish()
     }
 }
 
+// clip_metrics_from_partials against the plain loops it took the place of, on synthetic partial arrays: two clips of 2 and 1 rows, time
+// slot counts 1 and 3, spectral block counts 1 and 16, the SI-SDR sums from the second pass's partials and from the row's totals.  Exact.
+static void check_gather()
+{
+    const MetricClip clips[2] = {{0, 2, 5000}, {2, 1, 3 * 1024 + 5}};
+    const int R = 3, IB = 4;
+    unsigned seed = 12345u;
+    auto next = [&]() { seed = seed * 1664525u + 1013904223u; return 0.25 + (double)(seed >> 8) / 16777216.0; };   // in [0.25, 1.25)
+    for (int slots : {1, 3})
+        for (int FB : {1, 16})
+            for (int two_pass : {1, 0}) {
+                std::vector<double> time((size_t)R * slots * METRIC_TIME_Q), si((size_t)R * slots * 2), freq((size_t)R * FB * 2), in(2 * IB);
+                for (double& v : time) v = next();
+                for (double& v : si) v = next();
+                for (double& v : freq) v = next();
+                for (double& v : in) v = next() - 0.75;
+                double got[2 * CM_COUNT], want[2 * CM_COUNT];
+                clip_metrics_from_partials(clips, 2, time.data(), two_pass ? si.data() : nullptr, slots, freq.data(), FB, in.data(), IB, got);
+                for (int i = 0; i < 2; ++i) {
+                    std::vector<double> rows((size_t)clips[i].rows * CLIP_ROW_Q, 0.0);
+                    double re = 0, im = 0;
+                    for (int r = 0; r < clips[i].rows; ++r) {
+                        const size_t row = (size_t)(clips[i].first + r);
+                        double* q = &rows[(size_t)r * CLIP_ROW_Q];
+                        for (int s = 0; s < slots; ++s)
+                            for (int j = 0; j < METRIC_TIME_Q; ++j) q[j] += time[(row * slots + s) * METRIC_TIME_Q + j];
+                        if (two_pass)
+                            for (int s = 0; s < slots; ++s) { q[7] += si[(row * slots + s) * 2]; q[8] += si[(row * slots + s) * 2 + 1]; }
+                        else
+                            sisdr_sums_from_totals(q);
+                        double a = 0, b = 0;
+                        for (int k = 0; k < FB; ++k) { a += freq[(row * FB + k) * 2]; b += freq[(row * FB + k) * 2 + 1]; }
+                        re += a; im += b;
+                    }
+                    double sdr2 = 0;
+                    for (int k = 0; k < IB; ++k) sdr2 += in[(size_t)i * IB + k];
+                    const int64_t n = clips[i].len, T = 1 + n / 1024;
+                    finish_clip_metrics(rows.data(), clips[i].rows, re, im, sdr2, n, T, (T - 1) * 1024, want + i * CM_COUNT);
+                }
+                for (int k = 0; k < 2 * CM_COUNT; ++k) {
+                    if (got[k] != want[k]) printf("slots %d FB %d two_pass %d: number %d is %.17g, the plain loops give %.17g\n", slots, FB, two_pass, k, got[k], want[k]);
+                    EXPECT(got[k] == want[k] && std::isfinite(got[k]));
+                }
+            }
+}
+
 int main()
 {
     check_clip_shape();
     check_finish();
+    check_gather();
     if (!g_bad) printf("ok\n");
     return g_bad ? 1 : 0;
 }

@@ -140,9 +140,12 @@ def test_per_clip_against_evaluate_alone(model, batch, clean):
 
 @pytest.mark.parametrize("extra", [0, 3])
 def test_equal_lengths_are_evaluate(model, extra):
-    """One clip of 3 rows: the estimate is bit-identical to `evaluate`'s, so the metrics differ by the order of the double additions (sums
-    of fewer than 1e5 non-negative doubles reorder within N * 2^-53) and at most one fp32 ulp of alpha.  extra = 0: rows 16-byte aligned, the
-    time kernel's 16-byte loads; extra = 3: a stride of n + 3, its scalar loads."""
+    """One clip of 3 rows: the estimate is bit-identical to `evaluate`'s.  extra = 0: rows 16-byte aligned, and `evaluate` IS this batch -
+    the same metric launches on the same grids, the same host tail - so the five figures that come from the waveforms alone are EQUAL; the
+    spectral terms (and the loss that holds them) keep their bounds, because the clean signal goes through the rectangular analysis in
+    one call and the ragged analysis in the other.  extra = 3: a stride of n + 3, the time kernel's scalar loads against 16-byte ones, so
+    the metrics differ by the order of the double additions (sums of fewer than 1e5 non-negative doubles reorder within N * 2^-53) and at
+    most one fp32 ulp of alpha."""
     n = 16384
     mix, speech = signals(3, n)
     one = model.evaluate(dev(mix), dev(speech), return_estimate=True)
@@ -156,7 +159,9 @@ def test_equal_lengths_are_evaluate(model, extra):
         print("stride n + %d %-13s ragged %.12e evaluate %.12e diff %.2e" % (extra, k, got[0][k], one[k], d))
     for k in KEYS:
         d = abs(got[0][k] - one[k])
-        if k in DB_KEYS:
+        if extra == 0 and k in ("sdr", "sisdr", "l1_time", "separation_db", "input_sdr"):
+            assert got[0][k] == one[k], (k, got[0][k], one[k])
+        elif k in DB_KEYS:
             assert d < 1e-5, (k, got[0][k], one[k])
         else:
             assert d <= 1e-9 * abs(one[k]), (k, got[0][k], one[k])

@@ -62,6 +62,58 @@ def test_high_sdr_regime_and_reference_call_shape(sd_hot):
         metrics.train_infer(model, object(), (mix[None], speech[None]))
 
 
+@pytest.fixture(scope="module")
+def model(sd_default):
+    return _model_and_oracle(sd_default)[0]
+
+
+def _pair(rows, n):
+    """A correlated pair (SDR ~ 1 dB, SI-SDR ~ -4 dB), as tests/test_gpu_evaluate_ragged.py's: its bounds keep their room there."""
+    from speechseparation_amd import weights
+    speech = weights.synth_waveform(rows, n, seed=612, scale=0.07)
+    mix = (speech + weights.synth_waveform(rows, n, seed=611, scale=0.05)).astype(np.float32)
+    return torch.from_numpy(mix).cuda(), torch.from_numpy(speech).cuda()
+
+
+def test_the_estimate_buffer_does_not_change_the_numbers_and_a_second_call_allocates_nothing(model):
+    """3 x 16384: the estimate in the caller's buffer or in the context's own block, the eight numbers are the same bits; and once a
+    shape has run, the same shape again allocates nothing (bsrnn_debug_counter(0)) in either form."""
+    from speechseparation_amd import _native
+    mix, speech = _pair(3, 16384)
+    with_est = model.evaluate(mix, speech, return_estimate=True)
+    without = model.evaluate(mix, speech)
+    assert "x_time" not in without
+    for k in KEYS:
+        print("%-13s with est_out %.17g without %.17g" % (k, with_est[k], without[k]))
+        assert with_est[k] == without[k], (k, with_est[k], without[k])
+    allocs = _native.lib.bsrnn_debug_counter(0)
+    again = model.evaluate(mix, speech)
+    assert _native.lib.bsrnn_debug_counter(0) == allocs
+    again_est = model.evaluate(mix, speech, return_estimate=True)
+    assert _native.lib.bsrnn_debug_counter(0) == allocs
+    assert [again[k] for k in KEYS] == [without[k] for k in KEYS] == [again_est[k] for k in KEYS]
+    assert torch.equal(again_est["x_time"], with_est["x_time"])
+
+
+def test_row_blocks_against_the_ragged_call_of_one_clip(model):
+    """R = 130, n = 6 * 1024 + 9: bsrnn_separate's concurrent row blocks, and rows that are not 16-byte aligned (scalar loads), against
+    evaluate_ragged of one clip of 130 rows - the same metric launches behind another separation.  Bounds of
+    tests/test_gpu_evaluate_ragged.py::test_per_clip_against_evaluate_alone: 3e-5 on the estimate (the project's bound between kernel
+    choices), DB_TOL on the decibel figures, REL_TOL on the L1 terms and the loss."""
+    R, n = 130, 6 * 1024 + 9
+    mix, speech = _pair(R, n)
+    one = model.evaluate(mix, speech, return_estimate=True)
+    rag = model.evaluate_ragged(mix, speech, [n], [R], return_estimate=True)
+    assert len(rag) == 1 and tuple(one["x_time"].shape) == tuple(rag[0]["x_time"].shape) == (R, 6 * 1024)
+    e = float((one["x_time"] - rag[0]["x_time"]).abs().max())
+    print("max|evaluate est - ragged est| %.3e" % e)
+    assert e < 3e-5, e
+    for k in KEYS:
+        print("%-13s evaluate %.12e ragged %.12e diff %.2e" % (k, one[k], rag[0][k], abs(one[k] - rag[0][k])))
+    assert all(np.isfinite(one[k]) for k in KEYS)
+    _compare(one, rag[0])
+
+
 def test_full_size_properties(sd_default):
     """Metric configuration (64 rows x 128000 samples): size-independent properties instead of the oracle.
     A target equal to the estimate gives a zero time-domain L1 term and the epsilon-limited SDR; rows are independent,
