@@ -781,6 +781,57 @@ int32_t bsrnn_fir_bank_taps(const bsrnn_fir_bank* bank, int32_t filter);
 int     bsrnn_convolve_ragged(bsrnn_fir_bank* bank, const float* in_dev, int64_t in_stride, const int64_t* lens_host,
                               const int32_t* filter_host, float* out_dev, int64_t out_stride, int32_t R, void* stream);
 
+/* ---- the streaming (hop-by-hop) form of the FIR convolution ---------------------------------
+ * A bsrnn_fir_stream has C rows on one bsrnn_fir_bank.  Each row sits on one filter of the bank, or on -1 (bypass), and at its own place
+ * in its own stream: a live recording that arrives in windows is reverberated as it comes, instead of being buffered to its end.
+ * DEFINITION, for a row on a filter of k taps that has taken N samples so far, with B = 1024: the row has been handed exactly
+ *     E(N) = max(0, floor(N / B) * B - shift)
+ * output samples; a flush hands out the remaining N - E(N) and leaves the row at the beginning of a stream.
+ *   BSRNN_FIR_SAME, shift = k / 2: the concatenated output of a row, flush included, equals bsrnn_convolve_ragged of the concatenated
+ *     input under the same filter BIT FOR BIT, for every way of cutting the input into calls (counts of 0 included) - the same
+ *     transforms, and the partitions summed in the same order with the same fused multiply-adds.
+ *   BSRNN_FIR_CAUSAL, shift = 0: y[m] = sum_{j < k} x[m - (k - 1) + j] * h[j], m < N - no output sample depends on a later input
+ *     sample, and the latency is under one hop instead of k / 2 samples.  A host that wants y = x * r for a response r gives the bank r
+ *     reversed.  The flush ends the row at N samples as the one-shot ends a row; a reverb tail past the end is what feeding zeros in
+ *     front of the flush gives.  The alignment belongs to the stream (chosen at creation), not to a row.
+ *   A bypass row (filter -1) hands out the samples it is given, bit for bit, in the same call (ready = n_in); its flush gives 0.
+ * The hot case is a tick - many rows, one hop each: ONE launch per call, one workgroup per row.  Bulk feeding (few rows, many hops per
+ * call) is correct but serial per row; bsrnn_convolve_ragged remains the fast path for whole rows.
+ * Limits (BSRNN_EARG, the text names the value; answered before any device work, the object untouched): a null object, array or pointer;
+ * C < 1; max_taps outside [1, 262144]; align outside {0, 1}; a row outside [0, C) or listed twice; a filter outside [-1, count); a
+ * filter with more taps than max_taps; a count < 0 or > 2^30; a stride below the largest count read or written; out_dev overlapping the
+ * span of in_dev; pointers on another device than the context's.  On a host-only context the argument checks and the count queries
+ * answer, and then BSRNN_ESTATE, as for the bank.
+ *   bsrnn_fir_stream_create does all first-use work - the ring of the last conv_partitions(max_taps) input spectra per row
+ *     ([C][ceil(max_taps / 1024)][2050] floats), the previous 1024 inputs and a FIFO of < 1024 samples per row, the table block, the
+ *     kernel's first launch; afterwards bsrnn_debug_counter(0) does not move through process and flush.  All rows start on bypass.  The
+ *     stream keeps its bank alive (a bank destroyed before its last stream goes with that stream), and through the bank the context.
+ *   bsrnn_fir_stream_assign: the listed rows move to `filter` and start a new stream there.  _reset_rows: the listed rows start a new
+ *     stream on the filter they have.  Both are host-only (a row at the beginning of a stream reads nothing an earlier one left).
+ *     _filter_of: a row's filter; -2 for a null object or a row outside [0, C).
+ *   bsrnn_fir_stream_ready: the count the next _process would report for `row` if it gave the row n_in samples; -1 for a null object, a
+ *     row outside [0, C), n_in < 0 or n_in > 2^30.
+ *   bsrnn_fir_stream_process: row r reads its first n_in_host[r] samples of in_dev [C rows, in_stride apart] and nothing behind them; a
+ *     count of 0 HOLDS the row.  Every row is written exactly n_out_host[r] samples, out_dev[r][0 .. n_out_host[r]), and nothing behind
+ *     them; the counts are host arithmetic, reported without synchronising.  Asynchronous on `stream`; n_in_host and n_out_host are the
+ *     caller's own again at return.
+ *   bsrnn_fir_stream_flush_rows: the listed rows get what they are still owed and are left at the beginning of a stream; the other rows
+ *     are untouched and report 0.
+ *   A stream call counts as a call on the context (concurrency contract above). */
+typedef struct bsrnn_fir_stream bsrnn_fir_stream;
+#define BSRNN_FIR_SAME 0
+#define BSRNN_FIR_CAUSAL 1
+int     bsrnn_fir_stream_create(bsrnn_fir_bank* bank, int32_t C, int32_t max_taps, int32_t align, bsrnn_fir_stream** out);
+void    bsrnn_fir_stream_destroy(bsrnn_fir_stream* s);
+int     bsrnn_fir_stream_assign(bsrnn_fir_stream* s, const int32_t* rows_host, int32_t n_rows, int32_t filter);
+int32_t bsrnn_fir_stream_filter_of(const bsrnn_fir_stream* s, int32_t row);
+int64_t bsrnn_fir_stream_ready(const bsrnn_fir_stream* s, int32_t row, int64_t n_in);
+int     bsrnn_fir_stream_process(bsrnn_fir_stream* s, const float* in_dev, int64_t in_stride, const int64_t* n_in_host,
+                                 float* out_dev, int64_t out_stride, int64_t* n_out_host, void* stream);
+int     bsrnn_fir_stream_flush_rows(bsrnn_fir_stream* s, const int32_t* rows_host, int32_t n_rows,
+                                    float* out_dev, int64_t out_stride, int64_t* n_out_host, void* stream);
+int     bsrnn_fir_stream_reset_rows(bsrnn_fir_stream* s, const int32_t* rows_host, int32_t n_rows);
+
 /* ---- dialog / background section mining ---------------------------------------------------
  * The reference's gendataset-separate.py runs the separator over a long recording, forms two figures for every hop of 1024
  * samples (:100-105) and cuts the recording into dialog and background sections with a run-length state machine (:111-149);

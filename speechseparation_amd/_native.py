@@ -36,6 +36,8 @@ SYMBOLS = [
     "bsrnn_pool_get_pending", "bsrnn_pool_set_pending", "bsrnn_pool_feed", "bsrnn_pool_feed_host",
     "bsrnn_pool_create_rates", "bsrnn_pool_open_rate", "bsrnn_pool_rate_of", "bsrnn_pool_ready", "bsrnn_pool_drain_len", "bsrnn_pool_drain",
     "bsrnn_fir_bank_create", "bsrnn_fir_bank_destroy", "bsrnn_fir_bank_count", "bsrnn_fir_bank_taps", "bsrnn_convolve_ragged",
+    "bsrnn_fir_stream_create", "bsrnn_fir_stream_destroy", "bsrnn_fir_stream_assign", "bsrnn_fir_stream_filter_of", "bsrnn_fir_stream_ready",
+    "bsrnn_fir_stream_process", "bsrnn_fir_stream_flush_rows", "bsrnn_fir_stream_reset_rows",
     "bsrnn_hop_activity", "bsrnn_section_rule_default", "bsrnn_section_state_reset", "bsrnn_sections_scan",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
@@ -174,6 +176,14 @@ def _load():
         "bsrnn_fir_bank_count": (i32, [vp]),
         "bsrnn_fir_bank_taps": (i32, [vp, i32]),
         "bsrnn_convolve_ragged": (C.c_int, [vp, vp, i64, C.POINTER(i64), C.POINTER(i32), vp, i64, i32, vp]),
+        "bsrnn_fir_stream_create": (C.c_int, [vp, i32, i32, i32, C.POINTER(vp)]),
+        "bsrnn_fir_stream_destroy": (None, [vp]),
+        "bsrnn_fir_stream_assign": (C.c_int, [vp, C.POINTER(i32), i32, i32]),
+        "bsrnn_fir_stream_filter_of": (i32, [vp, i32]),
+        "bsrnn_fir_stream_ready": (i64, [vp, i32, i64]),
+        "bsrnn_fir_stream_process": (C.c_int, [vp, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), vp]),
+        "bsrnn_fir_stream_flush_rows": (C.c_int, [vp, C.POINTER(i32), i32, vp, i64, C.POINTER(i64), vp]),
+        "bsrnn_fir_stream_reset_rows": (C.c_int, [vp, C.POINTER(i32), i32]),
         "bsrnn_hop_activity": (C.c_int, [vp, vp, i64, vp, i64, C.POINTER(i32), i32, i32, vp, vp]),
         "bsrnn_section_rule_default": (None, [C.POINTER(SectionRuleC)]),
         "bsrnn_section_state_reset": (None, [C.POINTER(SectionStateC)]),

@@ -5,6 +5,7 @@ The reference convolves a clip with a whole room impulse response - tens of thou
 torch.nn.functional.conv1d(padding='same').  `FirBank` computes the same function with the library's partitioned FFT convolution
 (include/bsrnn_hip.h, bsrnn_convolve_ragged): rows of different lengths, each under its own filter, in one call.  `rir_draw` makes the
 reference's random decisions for a clip, `reverb_pairs` applies them to the clips of an optimizer step, `remix` is MixDataSet's arithmetic.
+`FirStream` is the hop-by-hop form of `FirBank.convolve` for live streams (bsrnn_fir_stream_*).
 """
 import ctypes
 import random
@@ -95,6 +96,160 @@ class FirBank:
             _check(_lib.bsrnn_convolve_ragged(self._h, _ptr(w), w_stride, (ctypes.c_int64 * R)(*lens), (ctypes.c_int32 * R)(*filt), _ptr(out),
                                               o_stride, R, _stream_ptr(self.device)))
         return out
+
+
+class FirStream:
+    """The streaming (hop-by-hop) form of `FirBank.convolve` (bsrnn_fir_stream_*): `rows` rows on `bank`, each on one filter of it or on
+    -1 (bypass, where all rows start), each at its own place in its own stream.  A row that has taken N samples has been handed
+    max(0, N // 1024 * 1024 - shift); flush() hands out the rest.  causal=False (shift = k // 2): a row's concatenated output, flush
+    included, is `bank.convolve` of its concatenated input bit for bit, however the input is cut.  causal=True (shift = 0):
+    y[m] = sum_j x[m - (k - 1) + j] h[j] - latency under one hop; give the bank a response reversed to convolve with it.  `max_taps`
+    (default: the bank's largest filter) bounds the filters rows may be assigned.  One launch per call; made for ticks of many rows, and
+    merely correct for many hops of few rows."""
+
+    def __init__(self, bank, rows, max_taps=None, causal=False):
+        if not isinstance(bank, FirBank):
+            raise ValueError("FirStream: bank must be a FirBank, got %s" % type(bank).__name__)
+        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or rows < 1:
+            raise ValueError("FirStream: rows must be a positive int, got %r" % (rows,))
+        if max_taps is None:
+            max_taps = max(bank.taps(i) for i in range(len(bank)))
+        if isinstance(max_taps, bool) or not isinstance(max_taps, (int, np.integer)) or not 1 <= max_taps <= MAX_TAPS:
+            raise ValueError("FirStream: max_taps must be an int in [1, %d], got %r" % (MAX_TAPS, max_taps))
+        self.bank = bank                        # (the library keeps the bank alive too)
+        self.C = int(rows)
+        self.max_taps = int(max_taps)
+        self.causal = bool(causal)
+        self.device = bank.device
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(_lib.bsrnn_fir_stream_create(bank._h, self.C, self.max_taps, 1 if causal else 0, ctypes.byref(h)))
+        self._h = h
+        self._taken = [0] * self.C              # samples per row since the beginning of its stream, mirrored to size a flush's result
+
+    def __del__(self):
+        try:
+            _lib.bsrnn_fir_stream_destroy(self._h)
+        except Exception:
+            pass
+
+    def _rows(self, rows, who):
+        if rows is None:
+            rows = range(self.C)
+        try:
+            rows = list(rows)
+        except TypeError:
+            raise ValueError("FirStream.%s: rows must be a sequence of ints, got %s" % (who, type(rows).__name__)) from None
+        for r in rows:
+            if isinstance(r, bool) or not isinstance(r, (int, np.integer)):
+                raise ValueError("FirStream.%s: a row must be an int, got %s" % (who, type(r).__name__))
+            if not 0 <= r < self.C:
+                raise ValueError("FirStream.%s: row %d is outside [0, %d)" % (who, r, self.C))
+        if len(set(rows)) != len(rows):
+            raise ValueError("FirStream.%s: a row is listed twice in %s" % (who, rows))
+        return [int(r) for r in rows], (ctypes.c_int32 * len(rows))(*rows)
+
+    def assign(self, rows, filter):
+        """The listed rows move to filter `filter` of the bank (-1: bypass) and start a new stream there (host only)."""
+        if isinstance(filter, bool) or not isinstance(filter, (int, np.integer)) or not -1 <= filter < len(self.bank):
+            raise ValueError("FirStream.assign: filter %r is outside [-1, %d)" % (filter, len(self.bank)))
+        if filter >= 0 and self.bank.taps(filter) > self.max_taps:
+            raise ValueError("FirStream.assign: filter %d has %d taps, the stream was made for max_taps = %d" % (
+                filter, self.bank.taps(filter), self.max_taps))
+        rows, arr = self._rows(rows, "assign")
+        _check(_lib.bsrnn_fir_stream_assign(self._h, arr, len(rows), int(filter)))
+        for r in rows:
+            self._taken[r] = 0
+
+    def filter_of(self, row):
+        return int(_lib.bsrnn_fir_stream_filter_of(self._h, self._rows([row], "filter_of")[0][0]))
+
+    def ready(self, row, n):
+        """Samples the next process() would hand `row` if it gave the row n samples."""
+        row = self._rows([row], "ready")[0][0]
+        return int(_lib.bsrnn_fir_stream_ready(self._h, row, int(n)))
+
+    def reset(self, rows=None):
+        """The listed rows (default: all) forget their stream so far and start a new one on the filter they have (host only)."""
+        rows, arr = self._rows(rows, "reset")
+        _check(_lib.bsrnn_fir_stream_reset_rows(self._h, arr, len(rows)))
+        for r in rows:
+            self._taken[r] = 0
+
+    def _out(self, out, want, who):
+        width = max(want)
+        if out is None:
+            return torch.empty((self.C, width), device=self.device, dtype=torch.float32)
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != self.device or out.dim() != 2
+                or out.shape[0] != self.C or out.shape[1] < width or (out.stride(1) != 1 and out.shape[1] > 1)
+                or (self.C > 1 and out.stride(0) < out.shape[1])):
+            raise ValueError("FirStream.%s: out must be a float32 tensor [%d, >= %d] with contiguous rows that do not overlap on %s" % (
+                who, self.C, width, self.device))
+        return out
+
+    def process(self, wave, counts=None, out=None):
+        """wave [C, n] float32 on the stream's device, counts C ints in [0, n] (default: n for every row) -> (out, counts out): row r reads
+        its first counts[r] samples and nothing behind them and is handed out[r, :counts_out[r]]; a given `out` is not written behind
+        them, a new one is unspecified there.  A count of 0 holds the row.  Views with a row stride go by pointer, uncopied."""
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != self.C:
+            raise ValueError("FirStream.process: expected wave [C = %d, n], got %s" % (
+                self.C, tuple(wave.shape) if isinstance(wave, torch.Tensor) else type(wave).__name__))
+        if wave.dtype != torch.float32:
+            raise ValueError("FirStream.process: expected a float32 tensor, got %s" % wave.dtype)
+        if not wave.is_cuda:
+            raise _native.NativeError("FirStream.process: the waveform must be on a HIP device")
+        if wave.device != self.device:
+            raise ValueError("FirStream.process: the waveform is on %s, the stream on %s" % (wave.device, self.device))
+        n = wave.shape[1]
+        if counts is None:
+            counts = [n] * self.C
+        try:
+            counts = list(counts.tolist() if isinstance(counts, (torch.Tensor, np.ndarray)) else counts)
+        except TypeError:
+            raise ValueError("FirStream.process: counts must be a sequence of %d ints, got %s" % (self.C, type(counts).__name__)) from None
+        if len(counts) != self.C:
+            raise ValueError("FirStream.process: %d counts for %d rows" % (len(counts), self.C))
+        for r, c in enumerate(counts):
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c <= n:
+                raise ValueError("FirStream.process: row %d has count %r, need an int in [0, %d]" % (r, c, n))
+        want = [int(_lib.bsrnn_fir_stream_ready(self._h, r, int(c))) for r, c in enumerate(counts)]
+        n_in = (ctypes.c_int64 * self.C)(*[int(c) for c in counts])
+        n_out = (ctypes.c_int64 * self.C)(*([-1] * self.C))
+        with torch.cuda.device(self.device):
+            if n > 0:
+                w, w_stride = BSRNN._rows_view(wave.detach())
+            else:
+                w, w_stride = wave, 0
+            out = self._out(out, want, "process")
+            o_stride = out.stride(0) if self.C > 1 else max(out.shape[1], 1)
+            _check(_lib.bsrnn_fir_stream_process(self._h, _ptr(w), w_stride, n_in, _ptr(out), o_stride, n_out, _stream_ptr(self.device)))
+        got = list(n_out)
+        assert got == want, (got, want)
+        for r, c in enumerate(counts):
+            self._taken[r] += int(c)
+        return out, got
+
+    def flush(self, rows=None, out=None):
+        """The listed rows (default: all) are handed what they are still owed and start afresh; the others are untouched.
+        -> (out [C, max count], the counts as a list: 0 for rows not listed)."""
+        rows, arr = self._rows(rows, "flush")
+        n_out = (ctypes.c_int64 * self.C)(*([-1] * self.C))
+        # what a row is owed, from the mirrored count: everything it took less what it was handed (the library's counts are held against it)
+        want = [0] * self.C
+        for r in rows:
+            f = self.filter_of(r)
+            if f >= 0:
+                shift = 0 if self.causal else self.bank.taps(f) // 2
+                want[r] = self._taken[r] - max(0, self._taken[r] // 1024 * 1024 - shift)
+        with torch.cuda.device(self.device):
+            out = self._out(out, want, "flush")
+            o_stride = out.stride(0) if self.C > 1 else max(out.shape[1], 1)
+            _check(_lib.bsrnn_fir_stream_flush_rows(self._h, arr, len(rows), _ptr(out), o_stride, n_out, _stream_ptr(self.device)))
+        got = list(n_out)
+        assert got == want, (got, want)
+        for r in rows:
+            self._taken[r] = 0
+        return out, got
 
 
 def rir_draw(idx, n_rirs, channels_of, prob=0.1):

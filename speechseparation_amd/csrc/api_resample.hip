@@ -1,5 +1,5 @@
 // C ABI of libbsrnn_hip.so, sample-rate conversion and FIR (bsrnn_resample*, bsrnn_resampler_*, bsrnn_resampler_bank_*,
-// bsrnn_fir_bank_*, bsrnn_convolve_ragged).  Each object owns its handle type and reaches the context through api_internal.h.
+// bsrnn_fir_bank_*, bsrnn_convolve_ragged, bsrnn_fir_stream_*).  Each object owns its handle type and reaches the context through api_internal.h.
 #include "api_internal.h"
 
 int bsrnn::host::resample_check_rates(int32_t rate_in, int32_t rate_out, const char* who, ResampleRatio& q)
@@ -237,6 +237,8 @@ struct bsrnn_fir_bank {
     std::vector<int32_t> taps;       // taps per filter
     std::vector<size_t> off;         // where a filter's image starts in d_images (floats)
     float* d_images;                 // [sum of P][CONV_LD]; null on a host-only context (the bank then only answers count / taps and refusals)
+    int streams = 0;                 // live bsrnn_fir_stream objects on this bank: they read d_images
+    bool zombie = false;             // bsrnn_fir_bank_destroy was called while streams lived; the last of them frees the bank
 };
 
 int bsrnn_fir_bank_create(bsrnn_ctx* c, int32_t n_filters, const float* const* taps_host, const int32_t* n_taps_host, bsrnn_fir_bank** out)
@@ -283,6 +285,7 @@ int bsrnn_fir_bank_create(bsrnn_ctx* c, int32_t n_filters, const float* const* t
 void bsrnn_fir_bank_destroy(bsrnn_fir_bank* bk)
 {
     if (!bk) return;
+    if (bk->streams > 0) { bk->zombie = true; return; }                // a stream keeps its bank alive (bsrnn_fir_stream_destroy ends it)
     bsrnn_ctx* c = bk->ctx;
     if (c->device >= 0) {
         (void)hipSetDevice(c->device);
@@ -379,6 +382,211 @@ int bsrnn_convolve_ragged(bsrnn_fir_bank* bk, const float* in, int64_t in_stride
         HIP_TRY(hipGetLastError());
     }
     return 0;
+}
+
+// --------------------------------------------------------------------------- the streaming form of the FIR convolution
+// C rows on one bank, each on a filter of it (or on -1: bypass) and at its own place in its own stream.  The definition and all index
+// arithmetic: convolve_stream_host.h; the kernel: fft.hip (one launch per call).  On the device: the ring of the last P input spectra per
+// row, the previous 1024 inputs and a FIFO of < 1024 samples per row.  On the host: filter and samples taken per row.
+struct bsrnn_fir_stream {
+    bsrnn_fir_bank* bank;
+    int C, max_taps, align, Pmax;
+    std::vector<int32_t> filter;     // -1: bypass
+    std::vector<int64_t> N;          // samples the row has taken since the beginning of its stream
+    std::vector<FirStreamRow> desc;  // the call being planned, and what its rows are at afterwards
+    std::vector<int64_t> next_N, counts;
+    std::vector<uint8_t> seen;
+    float* d_ring;                  // one allocation: [C][Pmax][CONV_LD], then d_state [C][FIR_STREAM_ROW_FLOATS]; null on a host-only context
+    float* d_state;
+};
+
+static int fir_stream_mark_rows(bsrnn_fir_stream* st, const int32_t* rows, int32_t n_rows, const char* who)
+{
+    if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(BSRNN_EARG, "%s: need a list of n_rows >= 0 rows, got n_rows = %d", who, n_rows);
+    std::fill(st->seen.begin(), st->seen.end(), (uint8_t)0);
+    for (int i = 0; i < n_rows; ++i) {
+        const int32_t r = rows[i];
+        if (r < 0 || r >= st->C) return fail(BSRNN_EARG, "%s: row %d (entry %d of the list) is outside [0, %d)", who, r, i, st->C);
+        if (st->seen[r]) return fail(BSRNN_EARG, "%s: row %d is listed twice", who, r);
+        st->seen[r] = 1;
+    }
+    return 0;
+}
+
+// the table of a call -> the device, and the one launch
+static int fir_stream_launch(bsrnn_fir_stream* st, const float* in, int64_t in_stride, float* out, int64_t out_stride, hipStream_t s)
+{
+    bsrnn_ctx* c = st->bank->ctx;
+    const size_t bytes = (size_t)st->C * sizeof(FirStreamRow);
+    if (int rc = c->rg.upload(bytes, s, [&](char* h) { memcpy(h, st->desc.data(), bytes); })) return rc;
+    launch_fir_stream(c->tb, reinterpret_cast<const FirStreamRow*>(c->rg.d), st->C, in, in_stride, out, out_stride, st->d_ring,
+                      (int64_t)st->Pmax * CONV_LD, st->d_state, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int bsrnn_fir_stream_create(bsrnn_fir_bank* bk, int32_t C, int32_t max_taps, int32_t align, bsrnn_fir_stream** out)
+{
+    if (!bk) return fail(BSRNN_EARG, "null FIR bank");
+    if (!out || C < 1) return fail(BSRNN_EARG, "bsrnn_fir_stream_create: need C >= 1 rows and a place for the object, got C = %d", C);
+    if (max_taps < 1 || max_taps > CONV_MAX_TAPS)
+        return fail(BSRNN_EARG, "bsrnn_fir_stream_create: max_taps = %d is outside [1, %d]", max_taps, CONV_MAX_TAPS);
+    if (align != FIR_ALIGN_SAME && align != FIR_ALIGN_CAUSAL)
+        return fail(BSRNN_EARG, "bsrnn_fir_stream_create: align = %d is neither BSRNN_FIR_SAME (0) nor BSRNN_FIR_CAUSAL (1)", align);
+    bsrnn_ctx* c = bk->ctx;
+    if (c->zombie) return fail(BSRNN_ESTATE, "context was destroyed");
+    std::unique_ptr<bsrnn_fir_stream> st(new bsrnn_fir_stream());
+    st->bank = bk; st->C = C; st->max_taps = max_taps; st->align = align; st->Pmax = conv_partitions(max_taps);
+    st->filter.assign(C, -1);
+    st->N.assign(C, 0);
+    st->next_N.assign(C, 0);
+    st->counts.assign(C, 0);
+    st->desc.assign(C, fir_stream_row_held());
+    st->seen.assign(C, 0);
+    st->d_ring = st->d_state = nullptr;
+    if (c->device >= 0) {
+        if (int rc = check_device(c)) return rc;
+        CallGuard guard_(c);
+        if (!guard_.ok) return guard_.refuse();
+        const size_t ring = (size_t)fir_stream_ring_floats(C, max_taps), bytes = (ring + (size_t)C * FIR_STREAM_ROW_FLOATS) * sizeof(float);
+        float* p = nullptr;
+        ++g_dbg[DBG_ALLOC];
+        hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e == hipSuccess && (e = hipMemset(p, 0, bytes)) != hipSuccess) (void)hipFree(p);
+        if (e != hipSuccess) return fail(BSRNN_EHIP, "bsrnn_fir_stream_create: %s", hipGetErrorString(e));
+        st->d_ring = p; st->d_state = p + ring;
+        // the table block of C rows and the kernel's first launch (code object loading) happen here: a call in which every row is held
+        int rc = fir_stream_launch(st.get(), nullptr, 0, nullptr, 0, nullptr);
+        if (!rc && (e = hipStreamSynchronize(nullptr)) != hipSuccess) rc = fail(BSRNN_EHIP, "bsrnn_fir_stream_create: %s", hipGetErrorString(e));
+        if (rc) { (void)hipFree(p); return rc; }
+    }
+    ++bk->streams;
+    *out = st.release();
+    return 0;
+}
+
+void bsrnn_fir_stream_destroy(bsrnn_fir_stream* st)
+{
+    if (!st) return;
+    bsrnn_fir_bank* bk = st->bank;
+    bsrnn_ctx* c = bk->ctx;
+    if (c->device >= 0) {
+        (void)hipSetDevice(c->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(st->d_ring);
+    }
+    delete st;
+    if (--bk->streams == 0 && bk->zombie) bsrnn_fir_bank_destroy(bk);      // the bank was destroyed before its last stream
+}
+
+int bsrnn_fir_stream_assign(bsrnn_fir_stream* st, const int32_t* rows, int32_t n_rows, int32_t filter)
+{
+    if (!st) return fail(BSRNN_EARG, "null FIR stream");
+    const int32_t count = (int32_t)st->bank->taps.size();
+    if (filter < -1 || filter >= count) return fail(BSRNN_EARG, "bsrnn_fir_stream_assign: filter %d is outside [-1, %d)", filter, count);
+    if (filter >= 0 && st->bank->taps[filter] > st->max_taps)
+        return fail(BSRNN_EARG, "bsrnn_fir_stream_assign: filter %d has %d taps, the stream was created for max_taps = %d", filter,
+                    st->bank->taps[filter], st->max_taps);
+    if (int rc = fir_stream_mark_rows(st, rows, n_rows, "bsrnn_fir_stream_assign")) return rc;
+    // nothing to enqueue: a row at the beginning of a stream reads no ring slot, tail or FIFO sample that an earlier stream left
+    for (int i = 0; i < n_rows; ++i) { st->filter[rows[i]] = filter; st->N[rows[i]] = 0; }
+    return 0;
+}
+
+int bsrnn_fir_stream_reset_rows(bsrnn_fir_stream* st, const int32_t* rows, int32_t n_rows)
+{
+    if (!st) return fail(BSRNN_EARG, "null FIR stream");
+    if (int rc = fir_stream_mark_rows(st, rows, n_rows, "bsrnn_fir_stream_reset_rows")) return rc;
+    for (int i = 0; i < n_rows; ++i) st->N[rows[i]] = 0;
+    return 0;
+}
+
+int32_t bsrnn_fir_stream_filter_of(const bsrnn_fir_stream* st, int32_t row) { return st && row >= 0 && row < st->C ? st->filter[row] : -2; }
+
+int64_t bsrnn_fir_stream_ready(const bsrnn_fir_stream* st, int32_t row, int64_t n_in)
+{
+    if (!st || row < 0 || row >= st->C || n_in < 0 || n_in > FIR_STREAM_COUNT_MAX) return -1;
+    const int32_t f = st->filter[row];
+    return f < 0 ? n_in : fir_stream_ready(st->N[row], n_in, fir_stream_shift(st->bank->taps[f], st->align));
+}
+
+// process (every row takes n_in[r]) or flush (the rows marked in seen[]): the table and the next positions first, then every refusal,
+// then the launch
+static int fir_stream_run(bsrnn_fir_stream* st, const float* in, int64_t in_stride, const int64_t* n_in, float* out, int64_t out_stride,
+                          int64_t* n_out_host, bool flush, hipStream_t s)
+{
+    const char* who = flush ? "bsrnn_fir_stream_flush_rows" : "bsrnn_fir_stream_process";
+    if (!n_out_host) return fail(BSRNN_EARG, "%s: nowhere to report the sample counts", who);
+    if (!flush && !n_in) return fail(BSRNN_EARG, "%s: need the rows' sample counts", who);
+    const bsrnn_fir_bank* bk = st->bank;
+    int64_t max_in = 0, max_out = 0;
+    bool work = false;
+    for (int r = 0; r < st->C; ++r) {
+        const int64_t n = flush ? 0 : n_in[r];
+        if (n < 0 || n > FIR_STREAM_COUNT_MAX)
+            return fail(BSRNN_EARG, "%s: n_in_host[%d] = %lld is outside [0, 2^30]", who, r, (long long)n);
+        const int32_t f = st->filter[r];
+        const int k = f >= 0 ? bk->taps[f] : 0;
+        const float* H = f >= 0 && bk->d_images ? bk->d_images + bk->off[f] : nullptr;
+        FirStreamRow& q = st->desc[r];
+        q = fir_stream_row_held();
+        st->next_N[r] = st->N[r];
+        int64_t count = 0;
+        if (flush) {
+            if (st->seen[r]) {
+                st->next_N[r] = 0;
+                if (f >= 0) { q = fir_stream_row_flush(H, k, st->align, st->N[r]); count = st->N[r] - fir_stream_emitted(st->N[r], fir_stream_shift(k, st->align)); }
+            }
+        } else if (n > 0) {
+            st->next_N[r] = st->N[r] + n;
+            if (f < 0) { q.n_in = (int32_t)n; count = n; }
+            else { q = fir_stream_row_process(H, k, st->align, st->N[r], n); count = fir_stream_ready(st->N[r], n, q.shift); }
+        }
+        work = work || q.n_in > 0 || q.ue > q.ub;
+        st->counts[r] = count;
+        max_in = std::max(max_in, n);
+        max_out = std::max(max_out, count);
+    }
+    if (max_in > 0 && (!in || in_stride < max_in))
+        return fail(BSRNN_EARG, "%s: need an input block with in_stride >= the largest count, got in_stride = %lld, largest n_in = %lld", who,
+                    (long long)in_stride, (long long)max_in);
+    if (max_out > 0 && (!out || out_stride < max_out))
+        return fail(BSRNN_EARG, "%s: need an output block with out_stride >= the %lld samples this call writes to a row, got out_stride = %lld", who,
+                    (long long)max_out, (long long)out_stride);
+    if (max_in > 0 && max_out > 0 &&
+        ranges_overlap(in, ((size_t)(st->C - 1) * in_stride + max_in) * sizeof(float), out, ((size_t)(st->C - 1) * out_stride + max_out) * sizeof(float)))
+        return fail(BSRNN_EARG, "%s: out_dev must not overlap the span of in_dev (rows are read while others are written)", who);
+    bsrnn_ctx* c = bk->ctx;
+    if (int rc = check_device(c)) return rc;
+    for (const void* ptr : {(const void*)(max_in > 0 ? in : nullptr), (const void*)(max_out > 0 ? out : nullptr)}) {      // the images live on the bank's device
+        hipPointerAttribute_t at;
+        if (!ptr) continue;
+        if (hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); continue; }
+        if (at.type == hipMemoryTypeDevice && at.device != c->device)
+            return fail(BSRNN_EARG, "%s: %s lies on device %d, the bank was created on a context of device %d", who,
+                        ptr == (const void*)in ? "in_dev" : "out_dev", at.device, c->device);
+    }
+    ENTER_CALL(c, s);
+    if (work)
+        if (int rc = fir_stream_launch(st, max_in > 0 ? in : nullptr, in_stride, max_out > 0 ? out : nullptr, out_stride, s)) return rc;
+    for (int r = 0; r < st->C; ++r) n_out_host[r] = st->counts[r];
+    st->N.swap(st->next_N);
+    return 0;
+}
+
+int bsrnn_fir_stream_process(bsrnn_fir_stream* st, const float* in, int64_t in_stride, const int64_t* n_in_host, float* out, int64_t out_stride,
+                             int64_t* n_out_host, void* stream)
+{
+    if (!st) return fail(BSRNN_EARG, "null FIR stream");
+    return fir_stream_run(st, in, in_stride, n_in_host, out, out_stride, n_out_host, false, (hipStream_t)stream);
+}
+
+int bsrnn_fir_stream_flush_rows(bsrnn_fir_stream* st, const int32_t* rows, int32_t n_rows, float* out, int64_t out_stride, int64_t* n_out_host,
+                                void* stream)
+{
+    if (!st) return fail(BSRNN_EARG, "null FIR stream");
+    if (int rc = fir_stream_mark_rows(st, rows, n_rows, "bsrnn_fir_stream_flush_rows")) return rc;
+    return fir_stream_run(st, nullptr, 0, nullptr, out, out_stride, n_out_host, true, (hipStream_t)stream);
 }
 
 // rows_host [n_rows] -> seen[] marks them; refuses a null list, a row outside [0, C) and a row listed twice

@@ -1425,4 +1425,125 @@ void launch_fir_group(const FftTables& tb, const ConvRow* rows, int row0, int n_
     hipLaunchKernelGGL(fir_synthesis_kernel, cs.grid, dim3(256), 0, s, t, rows, row0, Y, in, in_stride, out, out_stride, cs.len);
 }
 
+// ------------------------------------------------------------------------------ the streaming form (bsrnn_fir_stream_*)
+// The same scheme walked in stream order (convolve_stream_host.h): ONE launch per call, one workgroup per row, which walks the row's
+// blocks [ub, ue) one after the other - the frame (the previous 1024 inputs, the FIFO, the call's input, zeros behind a flushed row's end)
+// through fir_analysis_walk into slot u mod P of the row's ring, the multiply-accumulate over the ring with a thread per bin (bins
+// tid + 256 i and, in every thread, bin 1024: no divergent tail), the sum through LDS into the synthesis of fir_synthesis_kernel, clipped
+// stores, and at the end the tail and the FIFO brought up to date.  The fused multiply-adds are fir_mac_kernel's, partitions ascending from
+// the first whose frame exists, so a block has the one-shot's bits (a frame the one-shot takes as zeros leaves its accumulator at +0).
+// The hot case is a tick (many rows, one block each); a call that brings a row many blocks is correct and serial.
+// The ring is read back by other threads of the workgroup than wrote it: the barrier that ends the analysis walk orders the two (no
+// __restrict__ on ring, tail and FIFO).
+__global__ __launch_bounds__(256) void fir_stream_kernel(FftTables tb, const FirStreamRow* __restrict__ rows, const float* __restrict__ in, int64_t in_stride,
+                                                         float* __restrict__ out, int64_t out_stride, float* ring, int64_t ring_stride, float* state)
+{
+    __shared__ __attribute__((aligned(16))) float2 z0[1024], z1[1024];
+    __shared__ __attribute__((aligned(16))) float2 ys[1028];
+    const int tid = threadIdx.x;
+    const int r = blockIdx.x;
+    const FirStreamRow q = rows[r];
+    if (q.n_in == 0 && q.ub >= q.ue) return;                          // held (uniform over the workgroup, before any barrier)
+    const float* src = in + (size_t)r * in_stride;
+    float* o = out + (size_t)r * out_stride;
+    if (!q.H) {                                                       // bypass: the samples it was given, in the same call
+        for (int i = tid; i < q.n_in; i += 256) o[i] = src[i];
+        return;
+    }
+    float* rg = ring + (size_t)r * ring_stride;
+    float* tl = state + (size_t)r * FIR_STREAM_ROW_FLOATS;            // x[base - 1024, base)
+    float* ff = tl + CONV_B;                                          // x[base, N0)
+    const int64_t N0 = q.N0, N1 = q.N0 + q.n_in;
+    const int64_t base = N0 / CONV_B * CONV_B;
+    // sample i >= base - 1024 of the stream; zeros in front of it and behind what it has taken
+    auto sample = [&](int64_t i) -> float {
+        if (i < 0 || i >= N1) return 0.f;
+        if (i >= N0) return src[i - N0];
+        if (i >= base) return ff[i - base];
+        return tl[i - (base - CONV_B)];
+    };
+    const Twiddles twd = load_twiddles<true>(tb.tw1024, tid);
+    const SplitCtx spl = load_split(tb, tid, true);
+    const float sc = 1.0f / 1024.0f;
+    const int P = q.P;
+    const float2* Hf = reinterpret_cast<const float2*>(q.H);
+    const float2* Rf = reinterpret_cast<const float2*>(rg);
+    for (int64_t u = q.ub; u < q.ue; ++u) {
+        if (u <= q.f1) {
+            auto sample2 = [&](int, int c) {
+                const int64_t i = (u - 1) * CONV_B + 2 * c;
+                return make_float2(sample(i), sample(i + 1));
+            };
+            auto row = [&](int) { return rg + (size_t)(u % P) * CONV_LD; };
+            fir_analysis_walk(tb, z0, z1, tid, 0, 1, sample2, row);   // (ends with a barrier: the spectrum is in the ring for everyone)
+        }
+        if (u < q.u0) continue;
+        const int p_lo = u - q.f1 > 0 ? (int)(u - q.f1) : 0;
+        const int p_hi = u < P - 1 ? (int)u : P - 1;
+        float2 acc[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) acc[i] = make_float2(0.f, 0.f);
+        int slot = (int)((u - p_lo) % P);
+#pragma unroll 2
+        for (int p = p_lo; p <= p_hi; ++p) {
+            const float2* hp = Hf + (size_t)p * (CONV_LD / 2);
+            const float2* xp = Rf + (size_t)slot * (CONV_LD / 2);
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                const int f = i < 4 ? tid + 256 * i : 1024;
+                const float2 h = hp[f], w = xp[f];
+                acc[i].x = fmaf(-h.y, w.y, fmaf(h.x, w.x, acc[i].x));
+                acc[i].y = fmaf(h.y, w.x, fmaf(h.x, w.y, acc[i].y));
+            }
+            slot = slot == 0 ? P - 1 : slot - 1;
+        }
+#pragma unroll
+        for (int i = 0; i < 5; ++i) ys[i < 4 ? tid + 256 * i : 1024] = acc[i];
+        __syncthreads();
+        MergeRegs mr;
+        irfft_load<true>(reinterpret_cast<const float*>(ys), spl, mr, tid);
+        irfft_store<true>(mr, spl, z0, tid);
+        __syncthreads();
+        const float2* z = fft1024<true>(z0, z1, twd, tid);
+        const int64_t m0 = u * CONV_B - q.shift;
+        float* ob = o + (m0 - q.E0);                                  // (dereferenced inside the clip only)
+        const bool pairs = m0 >= 0 && m0 + CONV_B <= q.n_end && (reinterpret_cast<size_t>(ob) & 7) == 0;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 256 * k;
+            const float2 v = make_float2(z[c + 512].x * sc, z[c + 512].y * sc);
+            const int64_t m = m0 + 2 * c;
+            if (pairs) *reinterpret_cast<float2*>(ob + 2 * c) = v;
+            else {
+                if (m >= 0 && m < q.n_end) ob[2 * c] = v.x;
+                if (m + 1 >= 0 && m + 1 < q.n_end) ob[2 * c + 1] = v.y;
+            }
+        }
+        __syncthreads();                          // z (= z1), z0 and ys are written again by the next block
+    }
+    if (!q.keep) return;
+    // the state behind the call: everything is read before anything is written (the new tail may come out of the old FIFO)
+    const int64_t base1 = N1 / CONV_B * CONV_B;
+    float tv[4], fv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = tid + 256 * k;
+        tv[k] = base1 != base ? sample(base1 - CONV_B + j) : 0.f;
+        fv[k] = sample(base1 + j);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = tid + 256 * k;
+        if (base1 != base) tl[j] = tv[k];
+        ff[j] = fv[k];
+    }
+}
+
+void launch_fir_stream(const FftTables& tb, const FirStreamRow* rows, int C, const float* in, int64_t in_stride, float* out, int64_t out_stride,
+                       float* ring, int64_t ring_stride, float* state, hipStream_t s)
+{
+    hipLaunchKernelGGL(fir_stream_kernel, dim3((unsigned)C), dim3(256), 0, s, fir_tables(tb), rows, in, in_stride, out, out_stride, ring, ring_stride, state);
+}
+
 }  // namespace bsrnn

@@ -9,6 +9,7 @@
 #include "train_ragged_host.h"  // TrainClip: what the ragged training loss kernels know of a clip (HIP-free)
 #include "pool_host.h"          // PoolEntry: what the native session pool's copy kernels know of a row (HIP-free)
 #include "convolve_host.h"      // ConvRow: what the FIR convolution's kernels know of a row (HIP-free)
+#include "convolve_stream_host.h"   // FirStreamRow: what the streaming FIR kernel knows of a row in one call (HIP-free)
 #include "metrics_host.h"       // MetricClip, METRIC_TIME_Q: what the metric kernels and their host tail agree on (HIP-free)
 
 namespace bsrnn {
@@ -326,6 +327,11 @@ void launch_stream_reset_rows(float* buf, float* prev, float* state, int C, int 
 void launch_fir_taps(const FftTables& tb, const float* taps, int k, float* H, hipStream_t s);
 void launch_fir_group(const FftTables& tb, const ConvRow* rows, int row0, int n_rows, int max_nx, int max_nb, const float* in, int64_t in_stride,
                       float* out, int64_t out_stride, float* X, float* Y, hipStream_t s);
+// The streaming form (bsrnn_fir_stream_*; the plan: convolve_stream_host.h): one launch, one workgroup per row of the table `rows` [C] (on
+// the device).  ring [C][ring_stride] floats (a row's P slots of CONV_LD at its start), state [C][FIR_STREAM_ROW_FLOATS] (the previous
+// 1024 inputs, then the FIFO).  in / out may be null when no row reads / writes.
+void launch_fir_stream(const FftTables& tb, const FirStreamRow* rows, int C, const float* in, int64_t in_stride, float* out, int64_t out_stride,
+                       float* ring, int64_t ring_stride, float* state, hipStream_t s);
 
 // ------------------------------------------------------------------ validation metrics (metrics.hip)
 // One family for the three evaluate calls: per-workgroup partial sums in double, which the host adds (metrics_host.h: METRIC_TIME_Q sums
