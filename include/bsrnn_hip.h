@@ -907,6 +907,40 @@ void bsrnn_section_state_reset(bsrnn_section_state* state);
 int  bsrnn_sections_scan(const bsrnn_section_rule* rule, bsrnn_section_state* state, const double* act_host, int64_t n_hops,
                          int32_t flush, bsrnn_section* out, int64_t cap, int64_t* n_out);
 
+/* ---- re-mix: the mixtures and targets of an optimizer step in one launch ------------------
+ * The reference's MixDataSet (m_dataset.py:141-180) makes a training item from one dialog and four backgrounds: every
+ * background is padded or cut to the item's length at a random place and scaled, and the mixture is
+ * dialog + sum(backgrounds).  bsrnn_remix_ragged forms the items of a whole optimizer step from sources that stay on the
+ * device, straight into the padded [rows][width] buffers bsrnn_stft_ragged ... bsrnn_train_loss_ragged take.  The draws
+ * (which sources, where, how loud) are the host's; the call is the arithmetic.
+ *
+ * Row r owns terms [first_term, first_term + n_terms) of terms_host, n_terms >= 1: the first is the target (the dialog),
+ * the others the backgrounds, in order.  The value of term t at output sample i is
+ *     v_t(i) = src[i - at] * gain   if 0 <= i - at < len,   else +0
+ * - the product is one fp32 multiply; at > 0 is the reference's left padding, at < 0 its cut; src is read nowhere else and
+ * may be null only if len == 0.  For 0 <= i < rows_host[r].n
+ *     target_dev[r * target_stride + i] = v_0(i)
+ *     mix_dev[r * mix_stride + i]       = v_0(i) + ((((+0 + v_1(i)) + v_2(i)) + ...)
+ * every + one fp32 addition in that order and no product fused into an addition: Python's `dialog + sum(backgrounds)`, bit
+ * for bit (torch multiplies a float32 tensor by a Python float as x * float32(g); 0 + b and d + 0 turn -0 into +0, so a
+ * target of -0 without background gives mix +0 and target -0; a gain of 1.0f is the identity, which is what the
+ * reference's dialog carries, its `dialog *= scale_dialog` being commented out).  inf and NaN pass through by position.
+ * For n <= i < width both outputs are +0 - callers need no memset - and nothing is written behind width in a row.  A
+ * row's bits depend on its terms alone, not on the other rows, on alignment or on the strides.  Terms may share sources
+ * (a mono source serves both rows of a clip through one pointer) and rows may share terms.
+ * Valid: R >= 1, n_terms >= 1, 0 <= n <= width <= both strides (n = 0 is a legal all-zero row; width and the strides at
+ * most 2^40, (R - 1) * stride at most 2^60), every row's term range inside [0, n_terms), 0 <= len <= 2^40, |at| <= 2^40.
+ * Everything else is refused with BSRNN_EARG and a sentence that names the row or term, before the device is touched -
+ * null tables, null outputs and a null ctx too, on a host-only context in front of its BSRNN_ESTATE.  Outputs that
+ * overlap each other or any source are UNDEFINED and not checked (a source is any device memory).  One launch of grid
+ * (ceil(width / BSRNN_REMIX_TILE), R); the tables travel with the call and are the caller's again at return; asynchronous
+ * on `stream`; needs no committed weights and allocates nothing once a call of its table size has been made. */
+#define BSRNN_REMIX_TILE 2048        /* consecutive outputs of a row one workgroup forms */
+typedef struct bsrnn_remix_term { const float* src; int64_t len; int64_t at; float gain; int32_t pad_; } bsrnn_remix_term;
+typedef struct bsrnn_remix_row  { int64_t n; int32_t first_term; int32_t n_terms; } bsrnn_remix_row;
+int  bsrnn_remix_ragged(bsrnn_ctx* ctx, const bsrnn_remix_row* rows_host, int32_t R, const bsrnn_remix_term* terms_host, int32_t n_terms,
+                        float* mix_dev, int64_t mix_stride, float* target_dev, int64_t target_stride, int64_t width, void* stream);
+
 /* ---- measurement support ---------------------------------------------------------------
  * bsrnn_set_profiling(ctx, mask): bit i of `mask` brackets stage i of every compute call with
  * hipEvents on the call's stream (mask < 0 = all stages, 0 = off; each bracket costs ~10 us of

@@ -39,6 +39,7 @@ SYMBOLS = [
     "bsrnn_fir_stream_create", "bsrnn_fir_stream_destroy", "bsrnn_fir_stream_assign", "bsrnn_fir_stream_filter_of", "bsrnn_fir_stream_ready",
     "bsrnn_fir_stream_process", "bsrnn_fir_stream_flush_rows", "bsrnn_fir_stream_reset_rows",
     "bsrnn_hop_activity", "bsrnn_section_rule_default", "bsrnn_section_state_reset", "bsrnn_sections_scan",
+    "bsrnn_remix_ragged",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
@@ -63,6 +64,17 @@ class SectionStateC(C.Structure):           # bsrnn_section_state
 
 class SectionC(C.Structure):                # bsrnn_section
     _fields_ = [("kind", C.c_int32), ("first_hop", C.c_int64), ("end_hop", C.c_int64)]
+
+
+REMIX_TILE = 2048                           # BSRNN_REMIX_TILE
+
+
+class RemixTermC(C.Structure):              # bsrnn_remix_term
+    _fields_ = [("src", C.c_void_p), ("len", C.c_int64), ("at", C.c_int64), ("gain", C.c_float), ("pad_", C.c_int32)]
+
+
+class RemixRowC(C.Structure):               # bsrnn_remix_row
+    _fields_ = [("n", C.c_int64), ("first_term", C.c_int32), ("n_terms", C.c_int32)]
 
 
 class NativeError(RuntimeError):
@@ -189,6 +201,7 @@ def _load():
         "bsrnn_section_state_reset": (None, [C.POINTER(SectionStateC)]),
         "bsrnn_sections_scan": (C.c_int, [C.POINTER(SectionRuleC), C.POINTER(SectionStateC), C.POINTER(C.c_double), i64, i32,
                                           C.POINTER(SectionC), i64, C.POINTER(i64)]),
+        "bsrnn_remix_ragged": (C.c_int, [vp, C.POINTER(RemixRowC), i32, C.POINTER(RemixTermC), i32, vp, i64, vp, i64, i64, vp]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),
         "bsrnn_stage_name": (C.c_char_p, [i32]),

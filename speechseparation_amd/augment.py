@@ -6,9 +6,12 @@ torch.nn.functional.conv1d(padding='same').  `FirBank` computes the same functio
 (include/bsrnn_hip.h, bsrnn_convolve_ragged): rows of different lengths, each under its own filter, in one call.  `rir_draw` makes the
 reference's random decisions for a clip, `reverb_pairs` applies them to the clips of an optimizer step, `remix` is MixDataSet's arithmetic.
 `FirStream` is the hop-by-hop form of `FirBank.convolve` for live streams (bsrnn_fir_stream_*).
+`SourceShelf`, `remix_draw` and `remix_many` are MixDataSet as a loader: sources held on the device, the reference's draws on the host,
+and the mixtures and targets of an optimizer step written by one bsrnn_remix_ragged into the buffers train.train_loss_ragged takes.
 """
 import ctypes
 import random
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -318,3 +321,179 @@ def remix(dialog, backgrounds, length, rng):
     rng.uniform(0.1, 1.0)                    # scale_dialog: drawn, unused
     dialog = _random_resize(dialog, length, rng)
     return dialog + sum(backgrounds), dialog
+
+
+# ------------------------------------------------------------------------------------------ the re-mix on the device
+# MixDataSet as a loader: the sources stay on the device (SourceShelf), the reference's draws are made on the host (remix_draw), and ONE
+# bsrnn_remix_ragged writes the mixtures and targets of a whole optimizer step into the padded buffers train.train_loss_ragged takes
+# (remix_many).  `remix` above is the oracle: same draws, same bits.
+DIALOG, BACKGROUND = "dialog", "background"
+
+
+class SourceShelf:
+    """Dialog and background sources of a re-mixed training set, ALL held on `device` for as long as the shelf lives (a shelf larger than
+    device memory is out of scope).  add_dialog / add_background take [n] or [ch, n] float32 tensors: CPU tensors are uploaded once; cuda
+    tensors and views of them are kept by reference, uncopied, as long as their samples are contiguous.  A mono source serves both rows
+    of a clip through the same pointer, as the reference's load_waveform duplicates it."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("SourceShelf: the sources live on a HIP device, got %s" % (self.device,))
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._src = {DIALOG: [], BACKGROUND: []}            # per source its rows: 1-D tensors of contiguous samples on the device
+
+    def _hold(self, t, who):
+        if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.dtype != torch.float32 or t.shape[0] < 1:
+            raise ValueError("SourceShelf.%s: expected a float32 tensor [n] or [ch, n], got %s" % (
+                who, (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
+        t = t.detach()
+        if not t.is_cuda:
+            t = t.to(self.device)
+        elif t.device != self.device:
+            raise ValueError("SourceShelf.%s: the tensor is on %s, the shelf on %s" % (who, t.device, self.device))
+        if t.shape[-1] > 1 and t.stride(-1) != 1:
+            t = t.contiguous()
+        return t
+
+    def _add(self, kind, t, who):
+        t = self._hold(t, who)
+        self._src[kind].append([t] if t.dim() == 1 else [t[c] for c in range(t.shape[0])])
+        return len(self._src[kind]) - 1
+
+    def add_dialog(self, t):
+        return self._add(DIALOG, t, "add_dialog")
+
+    def add_background(self, t):
+        return self._add(BACKGROUND, t, "add_background")
+
+    def add_sections(self, wave, sections):
+        """The DIALOG / BACKGROUND sections `mining.mine` returned for the recording `wave` ([n] or [ch, n]), as views into it: the
+        reference's section files receive the mixture's chunks (gendataset-separate.py), so the mined chain needs no copy and no file.
+        `sections`: a `mining.Mined`, a list of `mining.Section` (all channels of `wave` are cut alike), or one such list per row of
+        `wave` (every row a mono source of its own).  Returns (dialogs added, backgrounds added)."""
+        from . import mining
+        w = self._hold(wave, "add_sections")
+        if hasattr(sections, "sections") and hasattr(sections, "activity"):
+            sections = sections.sections
+        sections = list(sections)
+        per_row = bool(sections) and not hasattr(sections[0], "kind")
+        if per_row and (w.dim() == 1 and len(sections) != 1 or w.dim() == 2 and len(sections) != w.shape[0]):
+            raise ValueError("SourceShelf.add_sections: %d section lists for a recording %s" % (len(sections), tuple(w.shape)))
+        added = {mining.DIALOG: 0, mining.BACKGROUND: 0}
+        for r, secs in enumerate(sections if per_row else [sections]):
+            for s in secs:
+                a, b = s.samples
+                if s.kind not in added or not 0 <= a < b <= w.shape[-1]:
+                    raise ValueError("SourceShelf.add_sections: section %r does not lie in a recording of %d samples" % (s, w.shape[-1]))
+                view = (w[r] if w.dim() == 2 else w)[a:b] if per_row else w[..., a:b]
+                self._add(DIALOG if s.kind == mining.DIALOG else BACKGROUND, view, "add_sections")
+                added[s.kind] += 1
+        return added[mining.DIALOG], added[mining.BACKGROUND]
+
+    @property
+    def n_dialogs(self):
+        return len(self._src[DIALOG])
+
+    @property
+    def n_backgrounds(self):
+        return len(self._src[BACKGROUND])
+
+    def __len__(self):
+        return self.n_dialogs + self.n_backgrounds
+
+    def _rows(self, kind, i):
+        if kind not in self._src or isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= i < len(self._src[kind]):
+            raise IndexError("SourceShelf: no %s %r (%s)" % (kind, i, ", ".join("%d %ss" % (len(v), k) for k, v in self._src.items())))
+        return self._src[kind][i]
+
+    def length_of(self, kind, i):
+        return int(self._rows(kind, i)[0].shape[0])
+
+    def channels_of(self, kind, i):
+        return len(self._rows(kind, i))
+
+
+class RemixSpec(NamedTuple):
+    """What `remix_draw` decided for one item: the dialog, the backgrounds in order, and per term - the dialog first - where its sample 0
+    lands in the item (`at` > 0: padding on the left, < 0: a cut) and its gain."""
+    dialog: int
+    backgrounds: tuple
+    at: tuple
+    gain: tuple
+    length: int
+
+
+def _resize_draw(n, length, rng):
+    # random_resize's one draw (m_dataset.py:129-139) as the offset of the source in the item
+    if n < length:
+        return rng.randint(0, length - n)
+    return -rng.randint(0, n - length - 1)                    # n == length: randint(0, -1) raises ValueError, as in the reference
+
+
+def remix_draw(idx, shelf, length=50 * 44100, n_backgrounds=4, scale_dialog=False):
+    """MixDataSet.__getitem__'s decisions for item `idx` (m_dataset.py:149-176), in its order, on a random.Random(idx) (the reference
+    seeds the global generator with idx): two unused choice(backgrounds), four choice(dialogs) of which the first is used, n_backgrounds
+    choice(backgrounds), one random_resize draw per background, one uniform(0.1, 1.0) per background, one for the dialog's scale - applied
+    only with scale_dialog=True; the reference's multiplication is commented out - and the dialog's resize draw.  `shelf` is a SourceShelf,
+    or anything with n_dialogs, n_backgrounds and length_of(kind, i).  A source of exactly `length` samples raises ValueError, as the
+    reference's randint(0, -1) does."""
+    if shelf.n_dialogs < 1 or shelf.n_backgrounds < 1:
+        raise ValueError("remix_draw: the shelf holds %d dialogs and %d backgrounds, need at least one of each" % (shelf.n_dialogs, shelf.n_backgrounds))
+    rng = random.Random(idx)
+    dialogs, backgrounds = range(shelf.n_dialogs), range(shelf.n_backgrounds)
+    rng.choice(backgrounds)
+    rng.choice(backgrounds)
+    dialog = rng.choice(dialogs)
+    for _ in range(3):
+        rng.choice(dialogs)
+    bgs = [rng.choice(backgrounds) for _ in range(n_backgrounds)]
+    at = [_resize_draw(shelf.length_of(BACKGROUND, b), length, rng) for b in bgs]
+    gain = [rng.uniform(0.1, 1.0) for _ in bgs]
+    scale = rng.uniform(0.1, 1.0)
+    at.insert(0, _resize_draw(shelf.length_of(DIALOG, dialog), length, rng))
+    gain.insert(0, scale if scale_dialog else 1.0)
+    return RemixSpec(dialog, tuple(bgs), tuple(at), tuple(gain), int(length))
+
+
+def remix_many(shelf, specs, length, out=None):
+    """The items `specs` (RemixSpec, drawn for `length`) of one optimizer step in ONE bsrnn_remix_ragged: returns (mix [R, length],
+    target [R, length], lengths, clip_rows) - the arguments of train.train_loss_ragged.  An item has the rows of its dialog (two for a
+    mono one); a background has as many channels or is mono.  `out`: a (mix, target) pair of float32 [R, length] tensors on the
+    shelf's device, which go by pointer with their row strides (contiguous samples, rows that do not overlap); all of both is written."""
+    from . import train as _train
+    specs = list(specs)
+    length = int(length)
+    if not specs or length < 1:
+        raise ValueError("remix_many: need at least one spec and length >= 1")
+    rows, terms, clip_rows = [], [], []
+    for c, sp in enumerate(specs):
+        if sp.length != length or len(sp.at) != 1 + len(sp.backgrounds) or len(sp.gain) != len(sp.at):
+            raise ValueError("remix_many: spec %d was drawn for length %d with %d offsets and %d gains for %d terms, the call is for length %d" % (
+                c, sp.length, len(sp.at), len(sp.gain), 1 + len(sp.backgrounds), length))
+        srcs = [shelf._rows(DIALOG, sp.dialog)] + [shelf._rows(BACKGROUND, b) for b in sp.backgrounds]
+        ch = max(2, len(srcs[0]))
+        for t, s in enumerate(srcs):
+            if len(s) not in (1, ch):
+                raise ValueError("remix_many: spec %d: term %d has %d channels, the item %d" % (c, t, len(s), ch))
+        for r in range(ch):
+            rows.append((length, len(terms), len(srcs)))
+            for s, at, g in zip(srcs, sp.at, sp.gain):
+                x = s[r if len(s) > 1 else 0]
+                terms.append((x.data_ptr() if x.shape[0] else None, x.shape[0], int(at), float(g), 0))
+        clip_rows.append(ch)
+    R = len(rows)
+    dev = shelf.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = (torch.empty((R, length), device=dev, dtype=torch.float32), torch.empty((R, length), device=dev, dtype=torch.float32))
+        for o in out:
+            if (not isinstance(o, torch.Tensor) or o.dtype != torch.float32 or o.device != dev or tuple(o.shape) != (R, length)
+                    or (o.stride(1) != 1 and length > 1) or (R > 1 and o.stride(0) < length)):
+                raise ValueError("remix_many: out must be two float32 tensors %s with contiguous rows that do not overlap on %s" % ((R, length), dev))
+        mix, target = out
+        _check(_lib.bsrnn_remix_ragged(_train._context(dev), (_native.RemixRowC * R)(*rows), R, (_native.RemixTermC * len(terms))(*terms), len(terms),
+                                       _ptr(mix), mix.stride(0) if R > 1 else length, _ptr(target), target.stride(0) if R > 1 else length,
+                                       length, _stream_ptr(dev)))
+    return mix, target, [length] * len(specs), clip_rows

@@ -1,5 +1,5 @@
 // C ABI of libbsrnn_hip.so, sample-rate conversion and FIR (bsrnn_resample*, bsrnn_resampler_*, bsrnn_resampler_bank_*,
-// bsrnn_fir_bank_*, bsrnn_convolve_ragged, bsrnn_fir_stream_*).  Each object owns its handle type and reaches the context through api_internal.h.
+// bsrnn_fir_bank_*, bsrnn_convolve_ragged, bsrnn_remix_ragged, bsrnn_fir_stream_*).  Each object owns its handle type and reaches the context through api_internal.h.
 #include "api_internal.h"
 
 int bsrnn::host::resample_check_rates(int32_t rate_in, int32_t rate_out, const char* who, ResampleRatio& q)
@@ -381,6 +381,61 @@ int bsrnn_convolve_ragged(bsrnn_fir_bank* bk, const float* in, int64_t in_stride
         launch_fir_group(c->tb, d_rows, g.first, g.rows, max_nx, max_nb, in, in_stride, out, out_stride, cv.X, cv.Y, s);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+// --------------------------------------------------------------------------- the re-mix of an optimizer step
+// MixDataSet's arithmetic (m_dataset.py:158-178) for all rows of a step in one launch.  The definition, the checks, the tile count and
+// the traffic model: remix_host.h; the kernel: remix.hip.  The two tables travel as one block [R rows | n_terms terms] in the ragged
+// calls' ring.
+static_assert(sizeof(bsrnn_remix_term) == sizeof(RemixTerm) && offsetof(bsrnn_remix_term, src) == offsetof(RemixTerm, src) &&
+              offsetof(bsrnn_remix_term, len) == offsetof(RemixTerm, len) && offsetof(bsrnn_remix_term, at) == offsetof(RemixTerm, at) &&
+              offsetof(bsrnn_remix_term, gain) == offsetof(RemixTerm, gain), "remix_host.h and bsrnn_hip.h disagree");
+static_assert(sizeof(bsrnn_remix_row) == sizeof(RemixRow) && offsetof(bsrnn_remix_row, n) == offsetof(RemixRow, n) &&
+              offsetof(bsrnn_remix_row, first_term) == offsetof(RemixRow, first_term) && offsetof(bsrnn_remix_row, n_terms) == offsetof(RemixRow, n_terms),
+              "remix_host.h and bsrnn_hip.h disagree");
+static_assert(REMIX_TILE == BSRNN_REMIX_TILE, "remix_host.h and bsrnn_hip.h disagree");
+static_assert(sizeof(RemixRow) % alignof(RemixTerm) == 0, "the terms follow the rows in one block");
+
+int bsrnn_remix_ragged(bsrnn_ctx* c, const bsrnn_remix_row* rows_host, int32_t R, const bsrnn_remix_term* terms_host, int32_t n_terms,
+                       float* mix, int64_t mix_stride, float* target, int64_t target_stride, int64_t width, void* stream)
+{
+    // arguments first, device or not (a host-only context answers them before BSRNN_ESTATE)
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!mix || !target) return fail(BSRNN_EARG, "bsrnn_remix_ragged: null argument (need mix_dev and target_dev)");
+    const RemixRow* rows = reinterpret_cast<const RemixRow*>(rows_host);
+    const RemixTerm* terms = reinterpret_cast<const RemixTerm*>(terms_host);
+    const RemixVerdict v = remix_check(rows, R, terms, n_terms, mix_stride, target_stride, width);
+    const int i = (int)v.index;
+    switch (v.why) {
+    case REMIX_OK: break;
+    case REMIX_NULL_TABLE: return fail(BSRNN_EARG, "bsrnn_remix_ragged: null argument (need rows_host and terms_host)");
+    case REMIX_BAD_COUNT: return fail(BSRNN_EARG, "bsrnn_remix_ragged: need R >= 1 rows and n_terms >= 1 terms, got R = %d, n_terms = %d", R, n_terms);
+    case REMIX_BAD_WIDTH: return fail(BSRNN_EARG, "bsrnn_remix_ragged: width = %lld is outside [0, 2^40]", (long long)width);
+    case REMIX_MIX_STRIDE:
+        return fail(BSRNN_EARG, "bsrnn_remix_ragged: mix_stride %lld is less than width = %lld (or beyond 2^40, or R rows of it beyond 2^60)",
+                    (long long)mix_stride, (long long)width);
+    case REMIX_TARGET_STRIDE:
+        return fail(BSRNN_EARG, "bsrnn_remix_ragged: target_stride %lld is less than width = %lld (or beyond 2^40, or R rows of it beyond 2^60)",
+                    (long long)target_stride, (long long)width);
+    case REMIX_ROW_LENGTH:
+        return fail(BSRNN_EARG, "bsrnn_remix_ragged: rows_host[%d].n = %lld is outside [0, width = %lld]", i, (long long)rows[i].n, (long long)width);
+    case REMIX_ROW_TERMS:
+        return fail(BSRNN_EARG, "bsrnn_remix_ragged: rows_host[%d] owns terms [%d, %d + %d): need at least one, inside [0, %d)", i, rows[i].first_term,
+                    rows[i].first_term, rows[i].n_terms, n_terms);
+    case REMIX_TERM_LENGTH: return fail(BSRNN_EARG, "bsrnn_remix_ragged: terms_host[%d].len = %lld is outside [0, 2^40]", i, (long long)terms[i].len);
+    case REMIX_TERM_OFFSET: return fail(BSRNN_EARG, "bsrnn_remix_ragged: terms_host[%d].at = %lld is outside [-2^40, 2^40]", i, (long long)terms[i].at);
+    default: return fail(BSRNN_EARG, "bsrnn_remix_ragged: terms_host[%d].src is null with len = %lld", i, (long long)terms[i].len);
+    }
+    if (int rc = check_device(c)) return rc;                          // (no model stage: needs no committed weights)
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    if (remix_tiles(width) < 1) return 0;                             // width = 0: nothing to write
+    const size_t row_bytes = (size_t)R * sizeof(RemixRow), bytes = row_bytes + (size_t)n_terms * sizeof(RemixTerm);
+    if (int rc = c->rg.upload(bytes, s, [&](char* h) { memcpy(h, rows, row_bytes); memcpy(h + row_bytes, terms, bytes - row_bytes); })) return rc;
+    launch_remix_ragged(reinterpret_cast<const RemixRow*>(c->rg.d), reinterpret_cast<const RemixTerm*>(c->rg.d + row_bytes), R, mix, mix_stride,
+                        target, target_stride, width, s);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

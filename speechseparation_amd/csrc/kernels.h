@@ -11,6 +11,7 @@
 #include "convolve_host.h"      // ConvRow: what the FIR convolution's kernels know of a row (HIP-free)
 #include "convolve_stream_host.h"   // FirStreamRow: what the streaming FIR kernel knows of a row in one call (HIP-free)
 #include "metrics_host.h"       // MetricClip, METRIC_TIME_Q: what the metric kernels and their host tail agree on (HIP-free)
+#include "remix_host.h"         // RemixRow, RemixTerm: what the re-mix kernel knows of a row and of a term (HIP-free)
 
 namespace bsrnn {
 
@@ -364,6 +365,10 @@ void launch_metric_ragged_segment(const FftTables& tb, const float* est, int64_t
 // samples, (0, 0) from hops[r] to Hmax; hops [R] on the device, null: every row has Hmax hops.  Rows mix_stride / est_stride floats apart.
 void launch_hop_activity(const float* mix, int64_t mix_stride, const float* est, int64_t est_stride, const int32_t* hops, int R, int Hmax,
                          double* act /* [R][Hmax][2] */, hipStream_t s);
+// The re-mix of an optimizer step (bsrnn_remix_ragged; remix.hip, the definition: remix_host.h): mixture and target of the R rows of the
+// table `rows`, each from its run of `terms` (both on the device), columns [0, width) of every row of both outputs in one launch.
+void launch_remix_ragged(const RemixRow* rows, const RemixTerm* terms, int R, float* mix, int64_t mix_stride, float* target, int64_t target_stride,
+                         int64_t width, hipStream_t s);
 // The tri-loss and the SDR of a ragged training step per clip, and their gradients (bsrnn_train_loss_ragged / _backward; the clip table:
 // train_ragged_host.h).  y, sfreq, dy [R][2050][Tmax] in the reference layout; xtime, dxtime [R][(Tmax-1)*1024]; speech rows wave_stride
 // floats apart; lens [R], clips [n_clips], row_clip [R], gclip [n_clips][2] on the device.  The forward leaves values [n_clips][TV_COUNT] and

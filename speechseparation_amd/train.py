@@ -522,6 +522,22 @@ def train_step_many(model, optimizer, pairs, group=None, loss_sdr=False, max_row
     return out
 
 
+def train_step_packed(model, optimizer, mix, speech, lengths, clip_rows, group=None, loss_sdr=False):
+    """`train_step_many`'s tail on buffers that are packed already - what augment.remix_many returns: ONE `train_loss_ragged` on
+    mix, speech [R, n_max] (clip c owns clip_rows[c] consecutive rows of lengths[c] samples), ONE backward() of losses.sum() (of
+    -sdrs.sum() with loss_sdr), the gradients averaged over `group` when one is given, optimizer.step(), zero_grad().  Returns the
+    per-clip (loss, sdr) floats."""
+    losses, sdrs, _ = train_loss_ragged(model, mix, speech, lengths, clip_rows)
+    (-sdrs.sum() if loss_sdr else losses.sum()).backward()
+    vals = torch.stack([losses.detach(), sdrs.detach()], 1).cpu().tolist()
+    if group is not None:
+        from .dist import all_reduce_gradients
+        all_reduce_gradients(model.parameters(), group=group)
+    optimizer.step()
+    optimizer.zero_grad()
+    return [(v[0], v[1]) for v in vals]
+
+
 # ------------------------------------------------------------------------------------------ optimizer and the step
 class AdamW:
     """torch.optim.AdamW(params, lr=0.001, weight_decay=0.01) of train.py:50 on the library's kernel (all tensors of a step in one

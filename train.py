@@ -16,7 +16,13 @@ here); a `tr/` folder (DnR v2's name) is used when there is no `train/`; --train
 files of DIR whose names contain `imp` are resampled from --rir_rate to 44.1 kHz (BSRNN.resample) and loaded into one
 speechseparation_amd.augment.FirBank at start; a training clip is reverberated with probability --rir_prob, by the reference's draws on
 the clip's index (augment.rir_draw) and with its chained channels (augment.reverb_pairs), all chosen clips of an optimizer step in one
-convolution call per stage.  Without --rir nothing changes.  The re-mix of MixDataSet is augment.remix (no loader here builds on it).
+convolution call per stage.  Without --rir nothing changes.
+--remix DIR trains on the reference's MixDataSet (m_dataset.py:141-180) instead of on mixture / speech pairs: the dialog and background
+WAV files under DIR (mix_samples' naming rules, plus the dialog-*.wav / background-*.wav that gendataset-separate.py writes) are loaded onto
+one augment.SourceShelf on the device at start; an epoch is len(dialogs) items; every --batch_size items are drawn as the reference draws
+them on the item's index (augment.remix_draw), mixed by ONE launch into the padded buffers of the ragged step (augment.remix_many) and
+trained on in one backward pass (train_step_packed).  --remix_seconds / --remix_backgrounds: the reference's 50 and 4.  Validation still
+reads --datapath's val split, when there is one.  Refused with --rir or --graph.  Without --remix nothing changes.
 Not carried over: wandb logging, the discriminator, ReduceLROnPlateau (commented out in the
 reference loop) and its batch-size growth heuristic.  Under `torchrun` (one process per GPU) the clips are split over the ranks
 and the gradients averaged before every optimizer step (data-parallel, RCCL).
@@ -80,6 +86,46 @@ def load_rirs(model, folder, rate, device):
     return augment.FirBank(model, filters), first, channels
 
 
+def remix_files(base):
+    """(dialog paths, background paths, FLAC files skipped) under `base`, recursively, by the rules of the reference's mix_samples
+    (m_dataset.py:21-55): a dialog is a .wav whose path contains `lownoise`, or a file whose name starts with `speech.wav` or
+    `speech_post_rnnoise.wav`; a background is a file named `sfx*`, `music*` or `vocalnoise*` that ends in .wav (what the reference's
+    broken `endswith` evidently means); plus the `dialog-*.wav` / `background-*.wav` files gendataset-separate.py writes here.  Sorted
+    (os.listdir's order is the file system's).  FLAC files are counted and skipped: audio.load_wav reads WAV only."""
+    dialogs, backgrounds, flac = [], [], 0
+    for root, dirs, names in os.walk(base):
+        dirs.sort()
+        for x in sorted(names):
+            p = os.path.join(root, x)
+            if x.lower().endswith(".flac"):
+                flac += 1
+            elif "lownoise" in p and p.endswith(".wav"):
+                dialogs.append(p)
+            elif x.startswith("speech.wav") or x.startswith("speech_post_rnnoise.wav") or (x.startswith("dialog-") and x.endswith(".wav")):
+                dialogs.append(p)
+            elif x.startswith(("sfx", "music", "vocalnoise", "background-")) and x.endswith(".wav"):
+                backgrounds.append(p)
+    return dialogs, backgrounds, flac
+
+
+def load_shelf(base, length, device):
+    """Every dialog and background under `base` on ONE augment.SourceShelf on the device (the shelf holds all of it: it has to fit)."""
+    dialogs, backgrounds, flac = remix_files(base)
+    if flac:
+        print("--remix: %d FLAC files under %s skipped (WAV only)" % (flac, base))
+    if not dialogs or not backgrounds:
+        raise SystemExit("--remix: found %d dialogs and %d backgrounds under %s, need at least one of each (speech.wav / dialog-*.wav / "
+                         "*lownoise*.wav; sfx*.wav / music*.wav / vocalnoise*.wav / background-*.wav)" % (len(dialogs), len(backgrounds), base))
+    shelf = augment.SourceShelf(device)
+    for paths, add in ((dialogs, shelf.add_dialog), (backgrounds, shelf.add_background)):
+        for p in paths:
+            w, _ = audio.load_wav(p)
+            if w.shape[1] == length:
+                raise SystemExit("--remix: %s has exactly the item's %d samples: the reference's random_resize raises there" % (p, length))
+            add(w[:2].contiguous())
+    return shelf
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="Train a BSRNN model")
     ap.add_argument("--datapath", type=str, default=None, help="Path to the dataset")
@@ -103,13 +149,30 @@ def build_parser():
                     "reverberate training clips on the device as the reference's MyDataSet(with_rir=True) does")
     ap.add_argument("--rir_prob", type=float, default=0.1, metavar="P", help="chance of a training clip being reverberated (the reference's 0.1)")
     ap.add_argument("--rir_rate", type=int, default=16000, metavar="HZ", help="sample rate the responses are taken to be at (the reference's 16000)")
+    ap.add_argument("--remix", type=str, default=None, metavar="DIR", help="train on re-mixed items as the reference's MixDataSet makes them: the "
+                    "dialog and background WAV files under DIR are held on the device, and every --batch_size items are mixed there in one launch")
+    ap.add_argument("--remix_seconds", type=float, default=50.0, metavar="S", help="length of a re-mixed item at 44.1 kHz (the reference's 50)")
+    ap.add_argument("--remix_backgrounds", type=int, default=4, metavar="N", help="backgrounds per re-mixed item (the reference's 4)")
     return ap
+
+
+REMIX_REFUSAL = "--remix does not go with --rir or --graph: the reference's MixDataSet has no reverberation, and the items of a step are a ragged batch"
+
+
+def parse_args(ap, argv=None):
+    """The parsed arguments, or the parser's exit for combinations that are refused."""
+    args = ap.parse_args(argv)
+    if args.remix and (args.rir or args.graph):
+        ap.error(REMIX_REFUSAL)
+    if args.remix and (int(args.remix_seconds * 44100) <= 1024 or args.remix_backgrounds < 0):
+        ap.error("--remix needs --remix_seconds of more than 1024 samples at 44.1 kHz and --remix_backgrounds >= 0")
+    return args
 
 
 def main(argv=None):
     global SYNTH_SAMPLES
     ap = build_parser()
-    args = ap.parse_args(argv)
+    args = parse_args(ap, argv)
     SYNTH_SAMPLES = int(args.seconds * 16000)
 
     import torch.distributed as dist
@@ -119,7 +182,13 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=device)
 
-    if args.synthetic:
+    shelf = None
+    if args.remix:
+        remix_length = int(args.remix_seconds * 44100)
+        shelf = load_shelf(args.remix, remix_length, device)
+        train_set = list(range(shelf.n_dialogs))                 # an epoch is len(dialogs) items (MixDataSet.__len__)
+        val_set = dataset(args.datapath, args.val_folder) if args.datapath else []
+    elif args.synthetic:
         train_set, val_set = list(range(args.synthetic)), list(range(args.synthetic, args.synthetic + args.synthetic // 4 + 1))
     elif args.datapath:
         # the reference's live path reads `train` and `val` (train.py:58,74); DnR's own split is called `tr`
@@ -165,7 +234,18 @@ def main(argv=None):
         random.Random(epoch).shuffle(order)                      # DataLoader(shuffle=True)
         order = order[: len(order) // world * world][rank::world]     # the same number of clips (and collectives) on every rank
         epoch_loss, epoch_sdr, batch_i = 0.0, 0.0, 0
-        if args.ragged:
+        if shelf is not None:
+            # the items of one optimizer step: the reference's draws on the host, one launch that mixes them, one backward pass
+            for b0 in range(0, len(order), args.batch_size):
+                specs = [augment.remix_draw(train_set[i], shelf, remix_length, args.remix_backgrounds) for i in order[b0:b0 + args.batch_size]]
+                mix, speech, lengths, clip_rows = augment.remix_many(shelf, specs, remix_length)
+                for loss, sdr in hip_train.train_step_packed(model, optimizer, mix, speech, lengths, clip_rows,
+                                                             group=dist.group.WORLD if world > 1 else None, loss_sdr=args.loss_sdr):
+                    batch_i += 1
+                    epoch_loss += loss
+                    epoch_sdr += sdr
+            order = []
+        elif args.ragged:
             # the clips of one optimizer step in one backward pass; the tail of the epoch is a smaller step (train.py:122-123)
             for b0 in range(0, len(order), args.batch_size):
                 pairs = [load_pair(train_set[idx], device) for idx in order[b0:b0 + args.batch_size]]
@@ -202,7 +282,7 @@ def main(argv=None):
                     all_reduce_gradients(model.parameters())
                 optimizer.step()
                 optimizer.zero_grad()
-        if world > 1 and not args.ragged:
+        if world > 1 and not args.ragged and shelf is None:
             from speechseparation_amd.dist import all_reduce_gradients
             all_reduce_gradients(model.parameters())
         optimizer.step()                                         # train.py:122-123: the tail of the epoch (--ragged: already stepped, no gradient is left)
