@@ -241,6 +241,30 @@ int  bsrnn_linear_group_train_backward(bsrnn_ctx* ctx, int32_t n, const float* c
  * of the shape only; no context or device needed.  BSRNN_EARG for M outside [1, 2^30], N1 or N2 outside [1, 65536], or a null out. */
 int  bsrnn_train_reduction_layout(int32_t M, int32_t N1, int32_t N2, int32_t out[2]);
 
+/* The critic's layers: nn.Conv1d(I, O, kernel 16, stride 3) (+ LeakyReLU(0.01) when leaky != 0) of the reference's Discriminator
+ * (bsrnn.py:512-536), forward and backward, exact fp32.  x [C][I][T] (T contiguous), W [O][I][16], b [O] in torch's layouts,
+ * T_out = (T - 16) / 3 + 1:
+ *   forward : y[c][o][t] = act(b[o] + sum_{i, k} W[o][i][k] * x[c][i][3 t + k])                                  -> y [C][O][T_out]
+ *   backward: with dp = dy * act'(y) (slope 0.01 where y <= 0; y is only read when leaky):  db[o] = sum_{c, t} dp[c][o][t],
+ *             dW[o][i][k] = sum_{c, t} dp[c][o][t] * x[c][i][3 t + k],  dx[c][i][s] = sum over o and the taps k with (s - k) % 3 == 0 and
+ *             0 <= (s - k) / 3 < T_out of W[o][i][k] * dp[c][o][(s - k) / 3].  dx [C][I][T] is written for every s < T (zeros where no
+ *             window reaches) and may be NULL (not wanted: the product is skipped); dW, db are overwritten, not accumulated.
+ * All pointers are dense device memory.  No atomics: the products over (i, k) run in slabs of input channels and the reductions over
+ * (c, t) in chunks of frames, both a function of the shape only (bsrnn_critic_conv_layout) and added in a fixed order, so results are
+ * bit-reproducible.  Workspace: the grow-only training buffer of the context.
+ * BSRNN_EARG for a null context or pointer, C, I or O < 1, T < 16, and a shape at which x, W, y or the partial sums would pass
+ * 2^31 - 1 elements; then BSRNN_ESTATE on a host-only context.  Nothing is launched on a refusal. */
+int  bsrnn_critic_conv_forward(bsrnn_ctx* ctx, const float* x_dev, const float* w_dev, const float* b_dev, float* y_dev,
+                               int32_t C, int32_t I, int32_t T, int32_t O, int32_t leaky, void* stream);
+int  bsrnn_critic_conv_backward(bsrnn_ctx* ctx, const float* x_dev, const float* w_dev, const float* y_dev, const float* dy_dev,
+                                float* dx_dev, float* dw_dev, float* db_dev, int32_t C, int32_t I, int32_t T, int32_t O,
+                                int32_t leaky, void* stream);
+/* How the two calls above cut their sums (measurement / test support; no context or device needed): out[0] = T_out; the forward's
+ * K = (i, k) runs in out[1] slabs of out[2] input channels (the last may hold fewer), added in slab order before the bias; the
+ * reductions of dW / db run in out[3] chunks of out[4] frames of every row (the last may hold fewer), added in chunk order.
+ * BSRNN_EARG as above, or for a null out. */
+int  bsrnn_critic_conv_layout(int32_t C, int32_t I, int32_t T, int32_t O, int32_t out[5]);
+
 /* torch.optim.AdamW(model.parameters(), lr, weight_decay) of train.py:50, one tensor per call: p, m (exp_avg), v (exp_avg_sq)
  * updated in place from the gradient g; `step` counts from 1 (bias correction).  n floats each, device pointers.  The betas are
  * double, as torch's: 1 - beta2 and the bias corrections are formed from them in double (from 0.999f, 1 - beta2 is 1.3e-5 off). */

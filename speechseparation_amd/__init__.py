@@ -10,7 +10,7 @@ from .spec import generate_bandsplits, BAND_FEATURES as band_features, MERGE_CHA
 
 
 def __getattr__(name):
-    if name in ("BSRNN", "StreamingSeparator", "StreamPool", "NativeStreamPool", "NativeRatePool"):
+    if name in ("BSRNN", "StreamingSeparator", "StreamPool", "NativeStreamPool", "NativeRatePool", "Discriminator"):
         from . import bsrnn as _b
         return getattr(_b, name)
     raise AttributeError(name)

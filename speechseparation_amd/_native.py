@@ -40,6 +40,7 @@ SYMBOLS = [
     "bsrnn_fir_stream_process", "bsrnn_fir_stream_flush_rows", "bsrnn_fir_stream_reset_rows",
     "bsrnn_hop_activity", "bsrnn_section_rule_default", "bsrnn_section_state_reset", "bsrnn_sections_scan",
     "bsrnn_remix_ragged",
+    "bsrnn_critic_conv_layout", "bsrnn_critic_conv_forward", "bsrnn_critic_conv_backward",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
@@ -202,6 +203,9 @@ def _load():
         "bsrnn_sections_scan": (C.c_int, [C.POINTER(SectionRuleC), C.POINTER(SectionStateC), C.POINTER(C.c_double), i64, i32,
                                           C.POINTER(SectionC), i64, C.POINTER(i64)]),
         "bsrnn_remix_ragged": (C.c_int, [vp, C.POINTER(RemixRowC), i32, C.POINTER(RemixTermC), i32, vp, i64, vp, i64, i64, vp]),
+        "bsrnn_critic_conv_layout": (C.c_int, [i32, i32, i32, i32, C.POINTER(i32)]),
+        "bsrnn_critic_conv_forward": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "bsrnn_critic_conv_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),
         "bsrnn_stage_name": (C.c_char_p, [i32]),

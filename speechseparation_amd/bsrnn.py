@@ -23,6 +23,7 @@ from torch import nn
 from . import _native
 from . import spec as _spec
 from .spec import generate_bandsplits  # noqa: F401  (re-export, bsrnn.py:247)
+from .discriminator import Discriminator  # noqa: F401  (re-export, bsrnn.py:512: `from bsrnn import Discriminator` of train.py:12)
 
 band_features = _spec.BAND_FEATURES      # bsrnn.py:60
 merge_channels = _spec.MERGE_CHANNELS    # bsrnn.py:61

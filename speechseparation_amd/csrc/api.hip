@@ -659,6 +659,23 @@ void destroy_now(bsrnn_ctx* c)
     if (c->h_range) (void)hipHostFree(c->h_range);
     delete c;
 }
+// Scratch of the training entry points: one grow-only buffer per context.  Calls on a context are serialised (ENTER_CALL) and a
+// stream switch waits for the previous stream, so reuse in stream order is safe; growing synchronises the device once.
+float* train_scratch(bsrnn_ctx* c, size_t floats)
+{
+    if (floats <= c->train_ws_floats) return c->d_train_ws;
+    // Grow: the old buffer is RETIRED, not freed.  Kernel nodes of a captured training iteration hold its address; a later, larger
+    // clip (its eager warm-up or an eager fall-back clip) must not turn those graphs into writers of freed memory.  A retired
+    // buffer stays valid scratch for the graphs that know it (they are replayed one at a time, in stream order, like every call).
+    float* fresh = nullptr;
+    const size_t want = floats + floats / 4;
+    if (hipMalloc((void**)&fresh, want * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (c->d_train_ws) c->train_ws_retired.push_back(c->d_train_ws);
+    c->d_train_ws = fresh;
+    c->train_ws_floats = want;
+    return c->d_train_ws;
+}
+
 }  // namespace bsrnn::host
 
 // =========================================================================== ABI
@@ -1064,22 +1081,6 @@ int bsrnn_dual_path(bsrnn_ctx* c, const float* z, float* z_out, const float* sta
 // nn.LSTM of NormRNNResidual (bsrnn.py:66-72) forward with saves and backward through time (lstm_train.hip); what
 // loss.backward() runs for these layers in train.py:97-115.  Operands are the caller's device buffers (torch layouts);
 // nothing of the committed inference weights is used.
-// Scratch of the training entry points: one grow-only buffer per context.  Calls on a context are serialised (ENTER_CALL) and a
-// stream switch waits for the previous stream, so reuse in stream order is safe; growing synchronises the device once.
-static float* train_scratch(bsrnn_ctx* c, size_t floats)
-{
-    if (floats <= c->train_ws_floats) return c->d_train_ws;
-    // Grow: the old buffer is RETIRED, not freed.  Kernel nodes of a captured training iteration hold its address; a later, larger
-    // clip (its eager warm-up or an eager fall-back clip) must not turn those graphs into writers of freed memory.  A retired
-    // buffer stays valid scratch for the graphs that know it (they are replayed one at a time, in stream order, like every call).
-    float* fresh = nullptr;
-    const size_t want = floats + floats / 4;
-    if (hipMalloc((void**)&fresh, want * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (c->d_train_ws) c->train_ws_retired.push_back(c->d_train_ws);
-    c->d_train_ws = fresh;
-    c->train_ws_floats = want;
-    return c->d_train_ws;
-}
 
 static int train_args_ok(bsrnn_ctx* c, int32_t N, int32_t L, int32_t IN, int32_t ndir, const char* who)
 {

@@ -1,4 +1,4 @@
-// What the host units of libbsrnn_hip.so share (api.hip, api_stream.hip, api_resample.hip, api_pool.hip): the handle types the C ABI
+// What the host units of libbsrnn_hip.so share (api.hip, api_stream.hip, api_resample.hip, api_pool.hip, api_critic.hip): the handle types the C ABI
 // names, error plumbing, the upload ring, and the helpers every entry point opens and closes with.  Everything but the handle types lives
 // in bsrnn::host; nothing here is exported (-fvisibility=hidden).  Not a public header.
 #pragma once
@@ -318,6 +318,7 @@ int check_range(bsrnn_ctx* c);
 int check_device(bsrnn_ctx* c, bool model = false);
 int check_ready(bsrnn_ctx* c);
 int order_after_last(bsrnn_ctx* c, hipStream_t s);
+float* train_scratch(bsrnn_ctx* c, size_t floats);      // the grow-only scratch of the training entry points; null when out of memory
 void destroy_now(bsrnn_ctx* c);      // the end of a context: bsrnn_destroy, or the last object that pointed at a context destroyed before it
 
 // True when the byte ranges [a, a + na) and [b, b + nb) share a byte (null pointers share none).  A call whose re-run (finish_call)

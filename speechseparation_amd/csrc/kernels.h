@@ -12,6 +12,7 @@
 #include "convolve_stream_host.h"   // FirStreamRow: what the streaming FIR kernel knows of a row in one call (HIP-free)
 #include "metrics_host.h"       // MetricClip, METRIC_TIME_Q: what the metric kernels and their host tail agree on (HIP-free)
 #include "remix_host.h"         // RemixRow, RemixTerm: what the re-mix kernel knows of a row and of a term (HIP-free)
+#include "critic_host.h"        // CriticLayout: tiles, K slabs and reduction chunks of the critic's convolution (HIP-free)
 
 namespace bsrnn {
 
@@ -424,5 +425,12 @@ void launch_resample_bank(BankLaunch L, const int* tiles, const BankRow* rows, i
 // e.row gets n_pend samples of e.pend_src at pend_off.  scatter: out [C][L*1024] row e.row, samples [out_skip, n_out) -> e.dst.
 void launch_pool_gather(const PoolEntry* tab, int n_entries, float* chunk, float* fifo, int L, hipStream_t s);
 void launch_pool_scatter(const PoolEntry* tab, int n_entries, const float* out, int L, hipStream_t s);
+// The critic's Conv1d(kernel 16, stride 3) layers (bsrnn_critic_conv_*; critic.hip, the definition and the layout: critic_host.h).
+// x [C][I][T], w [O][I][16], b [O], y / dy [C][O][T_out]; dx [C][I][T] may be null; scratch: critic_forward_scratch_floats /
+// critic_backward_scratch_floats.  y is only read when leaky.
+void launch_critic_forward(const float* x, const float* w, const float* b, float* y, float* scratch, int C, int I, int T, int O, int leaky,
+                           hipStream_t s);
+void launch_critic_backward(const float* x, const float* w, const float* y, const float* dy, float* dx, float* dw, float* db, float* scratch,
+                            int C, int I, int T, int O, int leaky, hipStream_t s);
 
 }  // namespace bsrnn

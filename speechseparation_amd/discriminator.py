@@ -1,0 +1,124 @@
+"""The reference's `Discriminator` (bsrnn.py:512-536) on the HIP library: the critic of `train-discriminator.py`.
+
+Four `Conv1d(kernel 16, stride 3)` layers, `in_channels` -> 1024 -> 128 -> 64 -> 32, LeakyReLU after the first three, then the mean over
+time, the mean over the rows, `Linear(32, 1)` and a sigmoid: [C, in_channels, T] -> [1].  Every convolution is a
+`torch.autograd.Function` over `bsrnn_critic_conv_forward` / `bsrnn_critic_conv_backward` (exact fp32, bit-reproducible), the Linear
+layer goes through `bsrnn_linear_train_*` (train.LinearFunction); the two means and the sigmoid are torch on the same device.  No CPU
+fallback: the library has to be there and the tensors on the GPU.
+"""
+import ctypes
+
+import torch
+from torch import nn
+
+from . import _native
+from .train import LinearFunction, _context, _f32c, _p, _s
+
+_lib = _native.lib
+
+WIDTHS = (1024, 128, 64, 32)            # output channels of the four layers (CRITIC_WIDTHS of csrc/critic_host.h)
+KERNEL, STRIDE = 16, 3
+MIN_FRAMES = 601                        # the shortest input that reaches the last layer: 601 -> 196 -> 61 -> 16 -> 1
+
+
+def frames_out(T):
+    """Frames behind one layer: (T - 16) // 3 + 1 for T >= 16, else 0."""
+    return (T - KERNEL) // STRIDE + 1 if T >= KERNEL else 0
+
+
+def conv_layout(C, I, T, O):
+    """bsrnn_critic_conv_layout as a dict: T_out, the forward's K slabs (count, input channels per slab) and the chunks of the dW / db
+    reduction (count, frames per chunk)."""
+    out = (ctypes.c_int32 * 5)()
+    _native.check(_lib.bsrnn_critic_conv_layout(C, I, T, O, out))
+    return dict(zip(("T_out", "slabs", "ch_per_slab", "dw_chunks", "dw_frames"), out))
+
+
+def reference_channel_order(y):
+    """The library's interleaved spectrum [R, 2 F, T] (re, im, re, im, ...) in the order the reference feeds its critic:
+    torch.cat((x.real, x.imag), dim=1) of m_dataset.py:205 - all real parts, then all imaginary parts."""
+    return torch.cat((y[:, 0::2, :], y[:, 1::2, :]), dim=1)
+
+
+class CriticConvFunction(torch.autograd.Function):
+    """y = act(conv1d(x, w, b, stride=3)) with the library's forward and backward: apply(x [C, I, T], w [O, I, 16], b [O], leaky)
+    -> [C, O, T_out]; leaky selects LeakyReLU(0.01).  dx is only formed when x wants a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, leaky):
+        if not x.is_cuda:
+            raise ValueError("the critic's kernels run on the GPU: x must be a cuda tensor")
+        x, w, b = _f32c(x), _f32c(w), _f32c(b)
+        C, I, T = x.shape
+        O = w.shape[0]
+        if tuple(w.shape) != (O, I, KERNEL) or tuple(b.shape) != (O,):
+            raise ValueError("critic layer: weight %s / bias %s do not match x [C, %d, T]" % (tuple(w.shape), tuple(b.shape), I))
+        dev = x.device
+        with torch.cuda.device(dev):
+            y = torch.empty((C, O, frames_out(T)), device=dev)
+            _native.check(_lib.bsrnn_critic_conv_forward(_context(dev), _p(x), _p(w), _p(b), _p(y), C, I, T, O, int(bool(leaky)), _s(dev)))
+        ctx.save_for_backward(x, w, y)
+        ctx.leaky = bool(leaky)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        C, I, T = x.shape
+        O = w.shape[0]
+        dy = _f32c(dy)
+        dev = x.device
+        with torch.cuda.device(dev):
+            dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            dw, db = torch.empty_like(w), torch.empty((O,), device=dev)
+            _native.check(_lib.bsrnn_critic_conv_backward(_context(dev), _p(x), _p(w), _p(y), _p(dy), _p(dx), _p(dw), _p(db), C, I, T, O,
+                                                          int(ctx.leaky), _s(dev)))
+        return dx, dw, db, None
+
+
+class Discriminator(nn.Module):
+    """bsrnn.py:512-536.  `state_dict()` is the reference's, key for key and shape for shape (`layers.{0,2,4,6}.{weight,bias}`,
+    `layers2.0.{weight,bias}`), so `discriminator.pth` interchanges.
+
+    in_channels: the reference hard-codes 4098 = 2 * 2049, the channels of the 4096-point transform of train-discriminator.py:64.  That
+    default is stale in the reference itself: m_dataset.train_infer feeds the critic `cat(real, imag)` of the model's 2048-point output,
+    2050 channels, so its own call raises with the default critic.  `Discriminator(2050)` is the size `metrics.train_infer`,
+    `train.train_loss` and this project's `train-discriminator.py` use (the library has no 4096-point transform)."""
+
+    def __init__(self, in_channels=4098):
+        super().__init__()
+        self.in_channels = int(in_channels)
+        dims = (self.in_channels,) + WIDTHS
+        mods = []
+        for l in range(len(WIDTHS)):
+            mods.append(nn.Conv1d(dims[l], dims[l + 1], KERNEL, stride=STRIDE))
+            if l + 1 < len(WIDTHS):
+                mods.append(nn.LeakyReLU())
+        self.layers = nn.Sequential(*mods)
+        self.layers2 = nn.Sequential(nn.Linear(WIDTHS[-1], 1), nn.Sigmoid())
+
+    def forward(self, x):
+        """x [C, in_channels, T] on the device, T >= 601 -> the score [1]."""
+        return self._score(x, fixed=False)
+
+    def score_fixed(self, x):
+        """forward with the critic's parameters held fixed: the gradient flows through the critic into x and nowhere else (the
+        adversarial term of train.train_loss)."""
+        return self._score(x, fixed=True)
+
+    def _score(self, x, fixed):
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise ValueError("Discriminator: expected x [C, %d, T], got %s" % (self.in_channels, tuple(getattr(x, "shape", ()))))
+        if x.shape[2] < MIN_FRAMES:
+            raise ValueError("Discriminator: x has %d frames, the four layers need at least %d (%d samples at hop 1024)" % (
+                x.shape[2], MIN_FRAMES, (MIN_FRAMES - 1) * 1024))
+        if not x.is_cuda:
+            raise ValueError("Discriminator: the critic's kernels run on the GPU: x must be a cuda tensor (there is no CPU fallback)")
+        par = (lambda p: p.detach()) if fixed else (lambda p: p)       # noqa: E731
+        h = x
+        convs = [m for m in self.layers if isinstance(m, nn.Conv1d)]
+        for l, m in enumerate(convs):
+            h = CriticConvFunction.apply(h, par(m.weight), par(m.bias), l + 1 < len(convs))
+        h = h.mean(dim=2).mean(dim=0)                                   # bsrnn.py:533-534
+        lin = self.layers2[0]
+        return torch.sigmoid(LinearFunction.apply(h.reshape(1, -1), par(lin.weight), par(lin.bias), False).reshape(1))

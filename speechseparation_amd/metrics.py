@@ -1,10 +1,11 @@
 """Host mirror of the reference's validation helpers (m_dataset.py:182-226), over the HIP path.
 
-`train_infer(model, None, sample)` keeps the reference's call shape and return tuple
+`train_infer(model, discriminator, sample)` keeps the reference's call shape and return tuple
 `(loss, sdr, sdr2, sdr3)` so that a validation loop written against m_dataset.py (train.py:137-150) runs
 unchanged; the arithmetic itself is one C-ABI call (`bsrnn_evaluate`): separation, the clean signal's STFT
-and every reduction stay on the device, only the eight numbers come back.  Training (the backward pass, the
-discriminator term) is out of scope: a non-None discriminator is refused rather than ignored.
+and every reduction stay on the device, only the eight numbers come back.  With a `Discriminator`
+(speechseparation_amd/discriminator.py) its score of the model's output is added to the loss, as m_dataset.py:205-213 does.
+The backward pass lives in speechseparation_amd/train.py.
 """
 import torch
 
@@ -31,12 +32,30 @@ def evaluate_many_long(model, pairs, segment_frames=256, max_rows=64):
 def train_infer(model, discriminator, sample, lossfn=None, verbose=False):
     """m_dataset.py:202-226.  sample = (waveform, waveform_speech), each [1, R, n].  lossfn must be the reference's
     L1Loss(reduction='mean') (train.py:54) or None.  Returns 0-dim tensors like the reference (its validation loop calls
-    `.item()` on them, train.py:140-144); they carry no graph: inference only."""
+    `.item()` on them, train.py:140-144); they carry no graph: inference only.  discriminator: None, or a Discriminator(2050) whose
+    score of the model's output (under no_grad) is added to the loss; the clip then needs 601 frames (614 400 samples).  sdr, sdr2 and
+    sdr3 do not depend on it.  (The reference's loss then has shape [1]; `.item()` serves both.)"""
     if discriminator is not None:
-        raise NotImplementedError("the discriminator term belongs to training, which this path does not cover")
+        from .discriminator import Discriminator
+        if not isinstance(discriminator, Discriminator):
+            raise NotImplementedError("the discriminator must be a speechseparation_amd Discriminator (or None), got %s" % type(discriminator).__name__)
     if lossfn is not None and not (isinstance(lossfn, torch.nn.L1Loss) and lossfn.reduction == "mean"):
         raise ValueError("only the reference's L1Loss(reduction='mean') is implemented on the device")
     m = evaluate(model, sample[0], sample[1])
     if verbose:
         print(" ".join("%s=%.4f" % kv for kv in m.items()))
-    return tuple(torch.tensor(m[k], dtype=torch.float64) for k in ("loss", "sdr", "input_sdr", "sisdr"))
+    out = tuple(torch.tensor(m[k], dtype=torch.float64) for k in ("loss", "sdr", "input_sdr", "sisdr"))
+    if discriminator is None:
+        return out
+    mix = sample[0].squeeze(0) if sample[0].dim() == 3 and sample[0].shape[0] == 1 else sample[0]
+    with torch.no_grad():                                      # m_dataset.py:205-208
+        score = discriminator(critic_input(model, mix))
+    return (out[0] + score.detach().to(torch.float64).cpu().reshape(()),) + out[1:]
+
+
+def critic_input(model, mix):
+    """`x_freq2` of m_dataset.py:205 for the mixture `mix` [R, n]: the model's output spectrum in the reference's channel order (all real
+    parts, then all imaginary parts) - a permutation of the library's interleaved [R, 2050, T], on the device."""
+    from .discriminator import reference_channel_order
+    dev = model._device_for(mix)
+    return reference_channel_order(model.forward(model.stft(mix.to(dev))))

@@ -307,10 +307,14 @@ class IstftFunction(torch.autograd.Function):
         return dy
 
 
-def train_loss(model, mix, speech):
-    """`train_infer` of the reference without the discriminator (m_dataset.py:182-216): STFT -> model -> iSTFT and the L1
-    tri-loss  L1(x_time, speech_time) + L1(Re X, Re S) + L1(Im X, Im S)  (nn.L1Loss, mean).  mix, speech [R, n] on the GPU.
-    Returns (loss, x_time); loss.backward() runs the library's backward kernels for every parameterised layer and the iSTFT."""
+def train_loss(model, mix, speech, discriminator=None, adversarial=False):
+    """`train_infer` of the reference (m_dataset.py:182-216): STFT -> model -> iSTFT and the L1 tri-loss
+    L1(x_time, speech_time) + L1(Re X, Re S) + L1(Im X, Im S)  (nn.L1Loss, mean).  mix, speech [R, n] on the GPU.
+    Returns (loss, x_time); loss.backward() runs the library's backward kernels for every parameterised layer and the iSTFT.
+    discriminator: a Discriminator(2050) whose score of the model's output is added to the loss - under no_grad, as the reference adds
+    it (m_dataset.py:205-213): a constant, the gradients are those of discriminator=None bit for bit.  adversarial=True lets the gradient
+    flow through the critic into the model instead, the critic's parameters held fixed (Discriminator.score_fixed).  Either way the clip
+    needs 601 frames."""
     x = stft(mix)
     y = forward_train(model, x)
     x_time = IstftFunction.apply(y)
@@ -318,6 +322,18 @@ def train_loss(model, mix, speech):
     s_time = speech[:, :x_time.shape[1]]
     l1 = lambda a, b: (a - b).abs().mean()                      # noqa: E731
     loss = l1(x_time, s_time) + l1(y[:, 0::2, :], s[:, 0::2, :]) + l1(y[:, 1::2, :], s[:, 1::2, :])
+    if discriminator is not None:
+        from .discriminator import Discriminator, reference_channel_order
+        if not isinstance(discriminator, Discriminator):
+            raise NotImplementedError("the discriminator must be a speechseparation_amd Discriminator (or None), got %s" % type(discriminator).__name__)
+        if adversarial:
+            loss = loss + discriminator.score_fixed(reference_channel_order(y)).reshape(())
+        else:
+            with torch.no_grad():
+                score = discriminator(reference_channel_order(y))
+            loss = loss + score.reshape(())
+    elif adversarial:
+        raise ValueError("train_loss: adversarial=True needs a discriminator")
     return loss, x_time
 
 
@@ -700,6 +716,41 @@ class AdamW:
         self._cache = {}
         if self._state_dev is not None:                      # capturable: the device's step count follows the loaded one
             self._device_state(self._state_dev.device, self.t)
+
+
+class ReduceLROnPlateau:
+    """torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode, patience=8, factor=0.8) of train-discriminator.py:30 for this module's
+    AdamW (through `set_lr`): step(metric) once per epoch; an epoch is bad when the metric is not better than the best so far by the
+    relative threshold (mode 'min': metric < best * (1 - threshold)); after more than `patience` bad epochs in a row the learning rate is
+    multiplied by `factor` (not below min_lr, and only when that changes it by more than eps) and the count starts again."""
+
+    def __init__(self, optimizer, mode="min", factor=0.8, patience=8, threshold=1e-4, min_lr=0.0, eps=1e-8):
+        if mode not in ("min", "max"):
+            raise ValueError("ReduceLROnPlateau: mode must be 'min' or 'max'")
+        if not 0.0 < factor < 1.0:
+            raise ValueError("ReduceLROnPlateau: factor must lie in (0, 1)")
+        self.optimizer, self.mode, self.factor, self.patience = optimizer, mode, float(factor), int(patience)
+        self.threshold, self.min_lr, self.eps = float(threshold), float(min_lr), float(eps)
+        self.best = float("inf") if mode == "min" else -float("inf")
+        self.num_bad_epochs = 0
+
+    def _better(self, a):
+        return a < self.best * (1.0 - self.threshold) if self.mode == "min" else a > self.best * (1.0 + self.threshold)
+
+    def get_last_lr(self):
+        return [self.optimizer.lr]
+
+    def step(self, metric):
+        metric = float(metric)
+        if self._better(metric):
+            self.best, self.num_bad_epochs = metric, 0
+        else:
+            self.num_bad_epochs += 1
+        if self.num_bad_epochs > self.patience:
+            new = max(self.optimizer.lr * self.factor, self.min_lr)
+            if self.optimizer.lr - new > self.eps:
+                self.optimizer.set_lr(new)
+            self.num_bad_epochs = 0
 
 
 def train_step(model, optimizer, mix, speech, group=None, loss_sdr=False):

@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Times the critic's kernels (speechseparation_amd/discriminator.py) beside stock torch on the same device: every layer's forward,
+dW / db and dx, and the whole critic step (two forwards, the loop's loss, backward), at 8 s and 60 s clips (44.1 kHz, hop 1024) for
+in_channels 2050 and 4098.  Medians of `--reps` runs after `--warmup`, device events around each run, nothing else on the GPU.  Beside
+every figure the two floors it sits between: the kernel's FLOP count over the 155 TF f32 matrix rate and, for the first layer, its weight
+bytes over HBM bandwidth (about 6.3 TB/s).
+
+    python tools/critic_bench.py > profiles/critic_bench.txt
+"""
+import argparse
+import ctypes
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from speechseparation_amd import _native, train as hip_train                      # noqa: E402
+from speechseparation_amd.discriminator import WIDTHS, Discriminator, conv_layout, frames_out     # noqa: E402
+
+F32_MATRIX_TF, HBM_TBS = 155.0, 6.3
+
+
+def timed(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--seconds", type=float, nargs="*", default=[8.0, 60.0])
+    ap.add_argument("--channels", type=int, nargs="*", default=[2050, 4098])
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    lib, ctx = _native.lib, hip_train._context(dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p()       # noqa: E731
+    print("critic_bench: %s, medians of %d after %d warm-up runs; ms (TF of the product) | floor at %.0f TF" % (
+        torch.cuda.get_device_name(0), args.reps, args.warmup, F32_MATRIX_TF))
+    for ch in args.channels:
+        for sec in args.seconds:
+            T = 1 + int(sec * 44100) // 1024
+            if T < 601:
+                T = 601
+                note = " (raised to the critic's shortest input, 601 frames)"
+            else:
+                note = ""
+            print("\nin_channels %d, %.0f s clip: T = %d frames%s, C = 2" % (ch, sec, T, note))
+            dims, Tl = (ch,) + WIDTHS, T
+            for l in range(4):
+                I, O, To = dims[l], dims[l + 1], frames_out(Tl)
+                x, w, b = torch.randn(2, I, Tl, device=dev), torch.randn(O, I, 16, device=dev) * 0.01, torch.randn(O, device=dev)
+                y, dy = torch.empty(2, O, To, device=dev), torch.randn(2, O, To, device=dev)
+                dx, dw, db = torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
+                leaky = int(l < 3)
+                flop = 2.0 * 2 * To * O * I * 16
+                g = conv_layout(2, I, Tl, O)
+                ours = {
+                    "forward": lambda: _native.check(lib.bsrnn_critic_conv_forward(ctx, p(x), p(w), p(b), p(y), 2, I, Tl, O, leaky, None)),
+                    "dW+db": lambda: _native.check(lib.bsrnn_critic_conv_backward(ctx, p(x), p(w), p(y), p(dy), None, p(dw), p(db), 2, I, Tl, O, leaky, None)),
+                    "dW+db+dx": lambda: _native.check(lib.bsrnn_critic_conv_backward(ctx, p(x), p(w), p(y), p(dy), p(dx), p(dw), p(db), 2, I, Tl, O, leaky, None)),
+                }
+                xs, ws = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+
+                def stock_bwd(inputs):
+                    out = F.leaky_relu(F.conv1d(xs, ws, b, stride=3), 0.01) if leaky else F.conv1d(xs, ws, b, stride=3)
+                    torch.autograd.grad(out, inputs, dy)
+                stock = {
+                    "forward": lambda: F.conv1d(x, w, b, stride=3),
+                    "dW+db": lambda: stock_bwd([ws]),              # (forward included: autograd needs its graph)
+                    "dW+db+dx": lambda: stock_bwd([ws, xs]),
+                }
+                t = {k: (timed(ours[k], args.warmup, args.reps), timed(stock[k], args.warmup, args.reps)) for k in ours}
+                t_dx = t["dW+db+dx"][0] - t["dW+db"][0]
+                floor = flop / (F32_MATRIX_TF * 1e12) * 1e3
+                print("  layer %d  %4d -> %4d, T %4d -> %4d  (%.1f GFLOP per product; %d K slabs of %d channels, %d dW chunks)" % (
+                    l, I, O, Tl, To, flop * 1e-9, g["slabs"], g["ch_per_slab"], g["dw_chunks"]))
+                print("    forward    %8.3f ms (%5.1f TF) | floor %.3f ms | stock conv1d %8.3f ms" % (t["forward"][0], flop / t["forward"][0] * 1e-9, floor, t["forward"][1]))
+                print("    dW + db    %8.3f ms (%5.1f TF) | floor %.3f ms | stock forward + autograd (dW) %8.3f ms" % (
+                    t["dW+db"][0], flop / t["dW+db"][0] * 1e-9, floor, t["dW+db"][1]))
+                print("    dx         %8.3f ms (%5.1f TF) | floor %.3f ms | stock forward + autograd (dW, dx) %8.3f ms (ours dW + db + dx: %.3f ms)" % (
+                    t_dx, flop / max(t_dx, 1e-6) * 1e-9, floor, t["dW+db+dx"][1], t["dW+db+dx"][0]))
+                if l == 0:
+                    print("    weights    %.0f MB: %.3f ms at %.1f TB/s (read once by forward and by dx, written once by dW)" % (
+                        w.numel() * 4e-6, w.numel() * 4 / (HBM_TBS * 1e12) * 1e3, HBM_TBS))
+                del x, w, y, dy, dx, dw, xs, ws
+                Tl = To
+            # the whole critic step of train-discriminator.py: two clips, the loop's loss, backward
+            D = Discriminator(ch).to(dev)
+            a, c = torch.randn(2, ch, T, device=dev), torch.randn(2, ch, T, device=dev)
+
+            def step():
+                for q in D.parameters():
+                    q.grad = None
+                (D(a) + (1 - D(c))).sum().backward()
+
+            def stock_step():
+                for q in D.parameters():
+                    q.grad = None
+                f = lambda v: D.layers2(D.layers(v).mean(dim=2).mean(dim=0))        # noqa: E731
+                (f(a) + (1 - f(c))).sum().backward()
+            print("  critic step (2 forwards + backward, dx of the first layer not needed): %.3f ms | stock torch modules %.3f ms" % (
+                timed(step, args.warmup, args.reps), timed(stock_step, args.warmup, args.reps)))
+            del D, a, c
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

@@ -23,8 +23,9 @@ one augment.SourceShelf on the device at start; an epoch is len(dialogs) items; 
 them on the item's index (augment.remix_draw), mixed by ONE launch into the padded buffers of the ragged step (augment.remix_many) and
 trained on in one backward pass (train_step_packed).  --remix_seconds / --remix_backgrounds: the reference's 50 and 4.  Validation still
 reads --datapath's val split, when there is one.  Refused with --rir or --graph.  Without --remix nothing changes.
-Not carried over: wandb logging, the discriminator, ReduceLROnPlateau (commented out in the
-reference loop) and its batch-size growth heuristic.  Under `torchrun` (one process per GPU) the clips are split over the ranks
+Not carried over: wandb logging, the discriminator argument (the reference's loop passes None; `speechseparation_amd.train.train_loss`
+takes a `Discriminator`, and `train-discriminator.py` trains one), ReduceLROnPlateau (commented out in the reference loop; the rule is
+`speechseparation_amd.train.ReduceLROnPlateau`) and its batch-size growth heuristic.  Under `torchrun` (one process per GPU) the clips are split over the ranks
 and the gradients averaged before every optimizer step (data-parallel, RCCL).
 """
 import argparse
