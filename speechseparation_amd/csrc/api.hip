@@ -248,7 +248,7 @@ static const PlanKnobs& plan_knobs()
         const char *tk = getenv("BSRNN_TIME_KERNEL"), *s8 = getenv("BSRNN_TIME_SEQ8");
         if (tk && *tk && strcmp(tk, "fused") && strcmp(tk, "v3")) fprintf(stderr, "bsrnn: unknown BSRNN_TIME_KERNEL='%s' (v3 | fused), using fused\n", tk);
         return PlanKnobs{!is("BSRNN_BAND_PAIR", "0"), !is("BSRNN_BAND_FC", "gemm"), !is("BSRNN_TIME_KERNEL", "v3"), s8 ? atoi(s8) : -1,
-                         gemm_mode(), lstm_mode(), device_cus()};
+                         gemm_mode(), lstm_mode(), device_cus(), is("BSRNN_BAND_PAIR", "tiles1") ? 1 : is("BSRNN_BAND_PAIR", "tiles2") ? 2 : 0};
     }();
     return knobs;
 }
@@ -360,7 +360,7 @@ void run_stage(bsrnn_ctx* c, const Part& p, int stage)
                 oc = OvlConsumer{c->d_ovl + OVL_HEAD, p.T, c->overlap_sabotage ? 200000 : OVL_SPIN_LIMIT, p.ovl->band_order, p.ovl_base, f.seqs == 8 ? 3 : 2};
             launch_band_pair(zi, p.HB0, p.HB1, c->bandW16[blk][0], c->bandB[blk][0], c->bandW16[blk][1], c->bandB[blk][1], M, K, c->d_range, s,
                              parts ? c->bandFc16[blk] : nullptr, parts ? c->bandFcB[blk] : nullptr, p.band_flags, cons ? &oc : nullptr, nullptr, 0,
-                             p.ovl ? p.band_done[blk] : nullptr);
+                             p.ovl ? p.band_done[blk] : nullptr, f.band_tiles);
             break;
         }
         launch_band_lstm(zi, p.HB0, c->bandW[blk][0], c->bandW16[blk][0], c->bandB[blk][0], M, K, 64, c->d_range, s, f.lstm_f32);

@@ -134,10 +134,11 @@ void launch_band_lstm(const float* xin, float* hout, const float* wpk, const voi
 // of fc(h): hb1[n][t][dir * 64 + f] = sum_k W_fc[f][dir * 64 + k] h_dir[n][t][k] (+ b[f] in the forward half); the time-axis launch
 // adds the halves and the residual (`part` of launch_time_lstm), so the block's fc launch disappears.
 // Both layers of a band block in one launch (lstm.hip::band_pair_h2_kernel, fp16x2 only): flags = 2 ints per tile of 16 sequences, zero
-// before the first launch and otherwise only touched by these launches.
+// before the first launch and otherwise only touched by these launches (one or two tiles per workgroup: the same flags, counted alike).
 void launch_band_pair(const float* z, float* hb0, float* hb1, const void* w0pk16, const float* bias0, const void* w1pk16, const float* bias1,
                       int N, int L, int* range_flag, hipStream_t stream, const void* fc16, const float* fcb, int* flags,
-                      const OvlConsumer* ovl = nullptr, int* zero_words = nullptr, int zero_n = 0, hipEvent_t done = nullptr);   // zero_words: progress words to clear (overlapped dual path)
+                      const OvlConsumer* ovl = nullptr, int* zero_words = nullptr, int zero_n = 0, hipEvent_t done = nullptr,   // zero_words: progress words to clear (overlapped dual path)
+                      int tiles = 1);                                     // tiles of 16 sequences per workgroup, 1 or 2 (plan_host.h::band_pair_tiles)
 // The whole band-axis block (both layers, both directions, fc + residual) of a few sequences in one workgroup: the streaming
 // step's N = C frame rows.  w0pk16 / w1pk16 / bias0 / bias1 are launch_band_lstm's arguments of the two layers; fc16 the block's
 // fc (128 -> 64) as fp16x2 B fragments [4 tile][4 blk][2 piece][64 lane][8], fcb its bias.  zout = fc(h1) + b + zin.

@@ -14,6 +14,7 @@
 // time kernel forms its own block's fc (FUSE); BSRNN_BAND_FC=gemm, the pair launch's fallback, BSRNN_GEMM=f32
 // and the exact-fp32 kernels run it as one grouped-GEMM launch (gemm.hip, EPI_RES).
 #include "kernels.h"
+#include "plan_host.h"
 #include <hip/hip_ext.h>
 
 #include <cstdio>
@@ -218,13 +219,94 @@ struct BandLds {
     static constexpr int BYTES = FC + (PART ? 4 * 2 * 2 * 64 : 1) * 16;
 };
 
-// One layer of one (tile of 16 sequences, direction): the body of band_lstm_h2_kernel and of both phases of band_pair_h2_kernel.
+// One layer of one (tile of 16 sequences, direction) in two halves, so that a workgroup can run several tiles on one set of weights:
+// band_load_weights (the resident fragments, the second pieces and biases in LDS, the fc fragments) and band_run_tile (x staging, the
+// step loop, the stores; fresh cell state).  band_lstm_h2_kernel runs one after the other, band_pair_h2_kernel<., 2> one load per
+// layer and two tiles.  The load itself has two halves: band_issue_weights only requests (global loads into registers), and
+// band_commit_weights writes the LDS part and waits - the pair launch polls its partner in between, with the loads in flight.
+template <int IN, bool PART>
+struct BandW {
+    static constexpr int NB = IN / 32 + HID / 32;
+    static constexpr int NLDS = IN == 128 ? BAND_NLDS : BAND_NLDS64;
+    h8v w[NB][4][2];                              // resident weights: w[blk][gate][piece] (the second pieces of the last NLDS blocks: unused)
+    uint4 w2[NLDS ? NLDS : 1][4];                 // second pieces on their way to LDS
+    uint4 fc[4];                                  // PART: this wave's fc A fragments on their way to LDS
+    float bias, bfc;
+};
+
+template <int IN, bool PART>
+__device__ __forceinline__ void band_issue_weights(BandW<IN, PART>& W, const int dir, const uint4* __restrict__ wpk, const float* __restrict__ bias,
+                                                   const uint4* __restrict__ wfc, const float* __restrict__ bfc)
+{
+    constexpr int NB = BandW<IN, PART>::NB, NLDS = BandW<IN, PART>::NLDS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint4* wp = wpk + ((size_t)(dir * 4 + wave) * NB * 4 * 2) * 64 + lane;
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int gte = 0; gte < 4; ++gte)
+#pragma unroll
+            for (int pc = 0; pc < 2; ++pc) {
+                const uint4 v = wp[((b * 4 + gte) * 2 + pc) * 64];
+                if (pc == 1 && b >= NB - NLDS) W.w2[NLDS ? b - (NB - NLDS) : 0][gte] = v;
+                else W.w[b][gte][pc] = __builtin_bit_cast(h8v, v);
+            }
+    W.bias = bias[dir * 256 + tid];
+    if (PART) {
+        // W_fc as [4 tile][4 k block][2 piece][64 lane][8] (api.hip): tile = this wave's 16 output features, k blocks 2 dir + b
+#pragma unroll
+        for (int i = 0; i < 4; ++i) W.fc[i] = wfc[((size_t)(wave * 4 + 2 * dir) * 2 + i) * 64 + lane];
+        W.bfc = tid < HID && dir == 0 ? bfc[tid] : 0.f;
+    }
+}
+
+template <int IN, bool PART>
+__device__ __forceinline__ void band_commit_weights(BandW<IN, PART>& W, char* const lds)
+{
+    constexpr int NB = BandW<IN, PART>::NB, NLDS = BandW<IN, PART>::NLDS;
+    using LD = BandLds<IN, PART>;
+    uint4* const w2lds = reinterpret_cast<uint4*>(lds + LD::W2);
+    float* const bias_lds = reinterpret_cast<float*>(lds + LD::BIAS);                        // this direction's b_ih + b_hh, [gate][unit]
+    uint4* const fclds = reinterpret_cast<uint4*>(lds + LD::FC);                             // fc A fragments [wave][k block][piece][lane]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int b = 0; b < NLDS; ++b)
+#pragma unroll
+        for (int gte = 0; gte < 4; ++gte) w2lds[((wave * NLDS + b) * 4 + gte) * 64 + lane] = W.w2[b][gte];
+    bias_lds[tid] = W.bias;
+    if (PART) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fclds[(wave * 4 + i) * 64 + lane] = W.fc[i];
+        if (tid < HID) bias_lds[4 * HID + tid] = W.bfc;                                      // the share's bias (forward half only)
+    }
+    // The loads above are still in flight when the step loop starts, and the compiler's wait-count bookkeeping merges
+    // that state into the loop (it waited for vmcnt(0), i.e. for the x prefetch of the same step, in front of the last
+    // recurrent MFMA of every step).  A use of every resident register here makes the waits happen once, up front.
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int gte = 0; gte < 4; ++gte) {
+            asm volatile("" : "+v"(W.w[b][gte][0]));
+            if (b < NB - NLDS) asm volatile("" : "+v"(W.w[b][gte][1]));
+        }
+}
+
+// The weight prologue of one layer: what a workgroup holds while it runs tiles of that layer and direction.  The LDS part is read
+// behind band_run_tile's first barrier.
+template <int IN, bool PART>
+__device__ __forceinline__ void band_load_weights(BandW<IN, PART>& W, char* const lds, const int dir, const uint4* __restrict__ wpk,
+                                                  const float* __restrict__ bias, const uint4* __restrict__ wfc, const float* __restrict__ bfc)
+{
+    band_issue_weights<IN, PART>(W, dir, wpk, bias, wfc, bfc);
+    band_commit_weights<IN, PART>(W, lds);
+}
+
+// One tile of 16 sequences through the layer whose weights W holds.  The LDS planes are this tile's alone: a caller that runs another
+// tile behind this one puts a workgroup barrier in between (late waves still read the planes of the last step).
 template <int IN, bool TRACE, bool PART>
-__device__ __forceinline__ void band_layer_body(char* const lds, const int dir, const int tile,
-                                                const float* __restrict__ xin, float* __restrict__ hout,
-                                                const uint4* __restrict__ wpk, const float* __restrict__ bias,
-                                                int N, int L, int* __restrict__ range_flag, unsigned long long* __restrict__ dbg,
-                                                const uint4* __restrict__ wfc, const float* __restrict__ bfc)
+__device__ __forceinline__ void band_run_tile(const BandW<IN, PART>& W, char* const lds, const int dir, const int tile,
+                                              const float* __restrict__ xin, float* __restrict__ hout,
+                                              int N, int L, int* __restrict__ range_flag, unsigned long long* __restrict__ dbg)
 {
     static_assert(!PART || IN == 2 * HID, "the fc share is formed by the second layer");
     // measurement only (TRACE, tools/lstm_h2_trace.hip): 100 MHz stamps per phase, accumulated per wave
@@ -242,46 +324,18 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
     using LD = BandLds<IN, PART>;
     auto& xpl = *reinterpret_cast<_Float16 (*)[2][2][IN * 16]>(lds + LD::XPL);              // [slot][piece][k / 8][seq][8]
     auto& hpl = *reinterpret_cast<_Float16 (*)[2][2][HID * 16]>(lds + LD::HPL);
-    uint4* const w2lds = reinterpret_cast<uint4*>(lds + LD::W2);
-    float* const bias_lds = reinterpret_cast<float*>(lds + LD::BIAS);                        // this direction's b_ih + b_hh, [gate][unit]
-    uint4* const fclds = reinterpret_cast<uint4*>(lds + LD::FC);                             // fc A fragments [wave][k block][piece][lane]
+    const uint4* const w2lds = reinterpret_cast<const uint4*>(lds + LD::W2);
+    const float* const bias_lds = reinterpret_cast<const float*>(lds + LD::BIAS);            // this direction's b_ih + b_hh, [gate][unit]
+    const uint4* const fclds = reinterpret_cast<const uint4*>(lds + LD::FC);                 // fc A fragments [wave][k block][piece][lane]
     const int n0 = tile * 16;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // Every per-thread index below starts from a thread id the optimiser cannot see through: in a loop over tiles it would otherwise keep
+    // what the prologue of the NEXT tile needs (staging addresses, offsets) in registers through this tile's step loop - the layer with
+    // the fc shares sits at the edge of 256 VGPRs and spilled six of them.  Recomputed per tile instead: a few dozen integer instructions.
+    int tid_ = threadIdx.x;
+    asm volatile("" : "+v"(tid_));
+    const int tid = tid_ & 255, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, q = lane >> 4;
-
-    // resident weights: w[blk][gate][piece]
-    h8v w[NB][4][2];
-    {
-        const uint4* wp = wpk + ((size_t)(dir * 4 + wave) * NB * 4 * 2) * 64 + lane;
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int gte = 0; gte < 4; ++gte)
-#pragma unroll
-                for (int pc = 0; pc < 2; ++pc) {
-                    const uint4 v = wp[((b * 4 + gte) * 2 + pc) * 64];
-                    if (pc == 1 && b >= NB - NLDS)
-                        w2lds[((wave * NLDS + (b - (NB - NLDS))) * 4 + gte) * 64 + lane] = v;
-                    else
-                        w[b][gte][pc] = __builtin_bit_cast(h8v, v);
-                }
-    }
-    bias_lds[tid] = bias[dir * 256 + tid];
-    if (PART) {
-        // W_fc as [4 tile][4 k block][2 piece][64 lane][8] (api.hip): tile = this wave's 16 output features, k blocks 2 dir + b
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fclds[(wave * 4 + i) * 64 + lane] = wfc[((size_t)(wave * 4 + 2 * dir) * 2 + i) * 64 + lane];
-    }
-    // The loads above are still in flight when the step loop starts, and the compiler's wait-count bookkeeping merges
-    // that state into the loop (it waited for vmcnt(0), i.e. for the x prefetch of the same step, in front of the last
-    // recurrent MFMA of every step).  A use of every resident register here makes the waits happen once, up front.
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int gte = 0; gte < 4; ++gte) {
-            asm volatile("" : "+v"(w[b][gte][0]));
-            if (b < NB - NLDS) asm volatile("" : "+v"(w[b][gte][1]));
-        }
+    const auto& w = W.w;
     v4f cv = {0.f, 0.f, 0.f, 0.f};               // cell states of this lane's four (unit, sequence) cells
 
     // x staging, one 16-byte unit per thread and i < XV.
@@ -370,7 +424,6 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
     // PART: the fc share of the h whose fragments are in registers (features 16 wave + 4 q + r of sequence l15, like the gates)
     v4f fhi = zero4, flo = zero4;
     const float* const fb_l = bias_lds + 4 * HID + 16 * wave + 4 * q;      // the share's bias from LDS (four registers the kernel does not have)
-    if (PART && tid < HID) bias_lds[4 * HID + tid] = dir == 0 ? bfc[tid] : 0.f;
     auto fc_mfma = [&](const int b, const h8v a0, const h8v a1) {
         const h8v f1 = __builtin_bit_cast(h8v, fclds[(wave * 4 + 2 * b) * 64 + lane]);
         const h8v f2 = __builtin_bit_cast(h8v, fclds[(wave * 4 + 2 * b + 1) * 64 + lane]);
@@ -396,7 +449,9 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
     };
 
     {   // prologue: h_{-1} = 0 (slot 1), x of the first two steps, input half of step 0
-        *reinterpret_cast<uint4*>(&hpl[1][0][0] + tid * 8) = make_uint4(0, 0, 0, 0);      // 2 pieces x 1024 halves = 256 x 16 B
+        unsigned zw;                              // (a zero made here, per tile: hoisted out of a loop over tiles the four registers of the
+        asm volatile("v_mov_b32 %0, 0" : "=v"(zw));      //  constant stayed live through the step loop - and were spilled - instead of being made again)
+        *reinterpret_cast<uint4*>(&hpl[1][0][0] + tid * 8) = make_uint4(zw, zw, zw, zw);      // 2 pieces x 1024 halves = 256 x 16 B
         u4v x0[XV];
         xload(tmap(0), x0);
         xstore(0, x0);
@@ -477,18 +532,37 @@ __device__ __forceinline__ void band_layer_body(char* const lds, const int dir, 
     }
 }
 
-// Workgroup -> (tile of 16 sequences, direction) in a 1-D grid of 16 workgroups per eight tiles.  The two directions of a tile read
-// the same x rows: they are 8 workgroup ids apart - the same XCD (id % 8), dispatched together - so the second read of a row is
-// served by that XCD's L2 instead of a second trip to memory.
-__device__ __forceinline__ bool band_tile_of_block(int N, int& dir, int& tile, const int* __restrict__ order = nullptr)
+// Workgroup -> (direction, slot) in a 1-D grid of 16 workgroups per eight slots; a slot names TILES consecutive tiles of 16 sequences (one
+// for the per-layer launches).  The two directions of a slot read the same x rows: they are 8 workgroup ids apart - the same XCD
+// (id % 8), dispatched together - so the second read of a row is served by that XCD's L2 instead of a second trip to memory.
+// Overlapped dual path (order): the slot takes its tiles from consecutive entries of a table sorted by the time a tile's frames leave the
+// time-axis launch running beside this one (the partner keeps its place: 8 workgroup ids apart); -1 pads the table to whole groups of
+// eight tiles, entries beyond that are absent.  Returns how many of the slot's tiles exist - they are the first ones: an odd tile count
+// leaves the last slot of two with tile A alone.
+template <int TILES>
+__device__ __forceinline__ int band_tiles_of_block(int N, int& dir, int (&tile)[TILES], const int* __restrict__ order)
 {
     const int w = blockIdx.x & 15;
     dir = w >> 3;
-    tile = (blockIdx.x >> 4) * 8 + (w & 7);
-    // overlapped dual path: the dispatch ordinal picks its tile from a table sorted by the time the tile's frames leave the time-axis
-    // launch running beside this one (the pair of a tile keeps its place: 8 workgroup ids apart); -1 pads the table to whole groups
-    if (order) tile = order[tile];
-    return tile >= 0 && tile * 16 < N;
+    const int slot = (blockIdx.x >> 4) * 8 + (w & 7);
+    const int n_tiles = (N + 15) / 16, n_ord = (n_tiles + 7) & ~7;
+    int nt = 0;
+#pragma unroll
+    for (int i = 0; i < TILES; ++i) {
+        const int e = slot * TILES + i;
+        int t = e;
+        if (order) t = e < n_ord ? order[e] : -1;
+        tile[i] = t;
+        if (nt == i && t >= 0 && t < n_tiles) nt = i + 1;
+    }
+    return nt;
+}
+__device__ __forceinline__ bool band_tile_of_block(int N, int& dir, int& tile)
+{
+    int t[1];
+    const int nt = band_tiles_of_block<1>(N, dir, t, nullptr);
+    tile = t[0];
+    return nt != 0;
 }
 
 template <int IN, bool TRACE = false, bool PART = false>
@@ -500,19 +574,29 @@ __global__ __launch_bounds__(256, BAND_OCC) void band_lstm_h2_kernel(const float
     __shared__ __attribute__((aligned(16))) char lds[BandLds<IN, PART>::BYTES];
     int dir, tile;
     if (!band_tile_of_block(N, dir, tile)) return;
-    band_layer_body<IN, TRACE, PART>(lds, dir, tile, xin, hout, wpk, bias, N, L, range_flag, dbg, wfc, bfc);
+    BandW<IN, PART> W;
+    band_load_weights<IN, PART>(W, lds, dir, wpk, bias, wfc, bfc);
+    band_run_tile<IN, TRACE, PART>(W, lds, dir, tile, xin, hout, N, L, range_flag, dbg);
 }
 
 // Both layers of a band block in ONE launch.  A workgroup runs layer 0 of its (tile, direction), publishes its half of the fp16
 // planes and waits for its partner - the other direction of the same tile: 8 workgroup ids away, the same XCD, dispatched in the
 // same breath (launch_band_lstm's grid) - then runs layer 1 on both halves.  The hand-over goes through L2: every thread fences its
 // plane stores, one thread releases flags[2 tile + dir] = its old value + 1 (the pair's two flags count the launches over this tile in
-// lockstep: nothing to clear, nothing passed by value, so the launch can sit in a replayed graph) and polls the partner's flag, bounded; the reads of layer 1 come behind an acquire fence (L1 invalidated).  No deadlock: workgroups
-// are dispatched in id order, a waiting workgroup's partner is at most 8 ids behind it, and everything dispatched before a waiting
-// pair either is a complete pair or waits for partners that are dispatched before any later workgroup - so slots always free up.
-// One launch, one weight prologue (layer 1's 196 KB are requested before the wait) and one tail less per block; the planes are read
-// back from L2 while they are hot.
-template <bool PART>
+// lockstep: nothing to clear, nothing passed by value, so the launch can sit in a replayed graph) and polls the partner's flag, bounded; the reads of layer 1 come behind an acquire fence (L1 invalidated).
+// TILES = 2: a workgroup owns tiles A and B of one direction and loads each layer's weights ONCE for both (343 KB of fragments per
+// workgroup, re-read from L2: with one tile per workgroup two thirds of what the launch pulls into its CUs).  Order of work: W0, layer 0
+// of A, barrier, layer 0 of B, publish both tiles, request W1, poll both partners' flags, layer 1 of A, barrier, layer 1 of B.  The LDS
+// planes are reused from tile to tile, hence the barriers (band_run_tile).  The partner owns the other direction of the SAME two tiles,
+// and every tile keeps its own flag pair, bumped once per launch whichever form runs: launches of either form, and the fall-back to
+// one launch per layer, find consistent counters.  A slot whose tile B does not exist (odd tile count) skips B everywhere, flags included.
+// No deadlock, in either form: workgroups are dispatched in id order, a waiting workgroup's partner is at most 8 ids behind it, and
+// everything dispatched before a waiting pair either is a complete pair or waits for partners that are dispatched before any later
+// workgroup - so slots always free up.  (A workgroup waits for nothing but its partner, and its partner for nothing but it: how many
+// tiles the two of them carry does not enter.)
+// One launch, one weight prologue per layer (layer 1's 196 KB are requested before the wait for the partner: the registers are free
+// once layer 0 has stored) and one tail less per block; the planes are read back from L2 while they are hot.
+template <bool PART, int TILES>
 __global__ __launch_bounds__(256, 2) void band_pair_h2_kernel(const float* __restrict__ z, float* hb0, float* __restrict__ hb1,
                                                               const uint4* __restrict__ w0, const float* __restrict__ b0,
                                                               const uint4* __restrict__ w1, const float* __restrict__ b1,
@@ -520,6 +604,7 @@ __global__ __launch_bounds__(256, 2) void band_pair_h2_kernel(const float* __res
                                                               const uint4* __restrict__ wfc, const float* __restrict__ bfc,
                                                               int* flags, int sabotage, OvlConsumer ovl, int* zero_words, int zero_n)
 {
+    static_assert(TILES == 1 || TILES == 2, "one or two tiles per workgroup");
     constexpr int B0 = BandLds<HID, false>::BYTES, B1 = BandLds<2 * HID, PART>::BYTES;
     __shared__ __attribute__((aligned(16))) char lds[B0 > B1 ? B0 : B1];
     __shared__ int partner_ok;
@@ -527,38 +612,66 @@ __global__ __launch_bounds__(256, 2) void band_pair_h2_kernel(const float* __res
     // producers and consumers (a memset of their own cost the stream 5 us plus two launch gaps)
     if (zero_words && blockIdx.x == 0)
         for (int i = threadIdx.x; i < zero_n; i += 256) zero_words[i] = 0;
-    int dir, tile;
-    if (!band_tile_of_block(N, dir, tile, ovl.order)) return;
-    if (ovl.prog) {
-        // launched beside the time-axis launch that writes z (kernels.h, OvlConsumer): wait until this tile's 16 frame rows have left it
-        if (threadIdx.x == 0) {
-            const int m_last = tile * 16 + 15 < N ? tile * 16 + 15 : N - 1;
-            partner_ok = ovl_wait_rows(ovl.prog, tile * 16, m_last, ovl.T, L, 0, L - 1, ovl.spin_limit, ovl.base, ovl.wg_shift) ? 1 : 0;
+    int dir, tl[TILES];
+    const int nt = band_tiles_of_block<TILES>(N, dir, tl, ovl.order);
+    if (!nt) return;
+    auto tile_of = [&](int i) { return TILES == 2 && i ? tl[TILES - 1] : tl[0]; };
+    {
+        BandW<HID, false> W;
+        band_load_weights<HID, false>(W, lds, dir, w0, b0, nullptr, nullptr);
+        for (int i = 0; i < nt; ++i) {
+            const int tile = tile_of(i);
+            if (i) __syncthreads();                   // late waves still read the planes of tile A's last step
+            if (ovl.prog) {
+                // launched beside the time-axis launch that writes z (kernels.h, OvlConsumer): wait until this tile's 16 frame rows have
+                // left it - tile by tile, B's rows (later in the order) only in front of B
+                if (threadIdx.x == 0) {
+                    const int m_last = tile * 16 + 15 < N ? tile * 16 + 15 : N - 1;
+                    partner_ok = ovl_wait_rows(ovl.prog, tile * 16, m_last, ovl.T, L, 0, L - 1, ovl.spin_limit, ovl.base, ovl.wg_shift) ? 1 : 0;
+                }
+                __syncthreads();
+                if (!partner_ok) {                    // (value 5: api.hip runs the call again launch after launch and stops overlapping)
+                    if (threadIdx.x == 0 && range_flag) *range_flag = 5;
+                    return;
+                }
+                __syncthreads();                      // (partner_ok is written again below)
+            }
+            band_run_tile<HID, false, false>(W, lds, dir, tile, z, hb0, N, L, range_flag, nullptr);
         }
-        __syncthreads();
-        if (!partner_ok) {                        // (value 5: api.hip runs the call again launch after launch and stops overlapping)
-            if (threadIdx.x == 0 && range_flag) *range_flag = 5;
-            return;
-        }
-        __syncthreads();                          // (partner_ok is written again below)
     }
-    band_layer_body<HID, false, false>(lds, dir, tile, z, hb0, w0, b0, N, L, range_flag, nullptr, nullptr, nullptr);
     // Hand-over through the XCD's L2, which both workgroups share: a store is counted out of vmcnt when L2 has it, so vmcnt(0) is
     // all the release this needs (an agent-scope release fence would write the whole L2 back for the sake of other XCDs: measured,
     // 2.6x slower); the flag carries the XCC id so that a placement that breaks the assumption is reported, not computed with.
     __builtin_amdgcn_s_waitcnt(0x0f70);           // vmcnt(0): this thread's plane stores are in L2
     __syncthreads();                              // ... every thread's; and nobody reads layer 0's LDS any more
+    int epoch[TILES], xcc = 0;
     if (threadIdx.x == 0) {
-        const int xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15;      // HW_REG_XCC_ID[3:0]
-        // the pair's two flags count the launches that covered this tile, in lockstep: mine + 1 is this launch's number for both
-        const int epoch = ((__hip_atomic_load(&flags[2 * tile + dir], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 4) + 1) & 0x7ffffff;
-        __hip_atomic_store(&flags[2 * tile + dir], (epoch << 4) | (sabotage ? (xcc ^ 8) : xcc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int spins = 0, v;
-        while (((v = __hip_atomic_load(&flags[2 * tile + (dir ^ 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 4) != epoch) {
-            __builtin_amdgcn_s_sleep(8);
-            if (++spins > (1 << 22)) break;       // (seconds: the partner never came - reported, not waited for)
+        xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15;      // HW_REG_XCC_ID[3:0]
+#pragma unroll
+        for (int i = 0; i < TILES; ++i) {
+            if (i >= nt) break;
+            // the pair's two flags count the launches that covered this tile, in lockstep: mine + 1 is this launch's number for both
+            int* const mine = &flags[2 * tl[i] + dir];
+            epoch[i] = ((__hip_atomic_load(mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 4) + 1) & 0x7ffffff;
+            __hip_atomic_store(mine, (epoch[i] << 4) | (sabotage ? (xcc ^ 8) : xcc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        partner_ok = (v >> 4) == epoch && (v & 15) == xcc;
+    }
+    BandW<2 * HID, PART> W;
+    band_issue_weights<2 * HID, PART>(W, dir, w1, b1, wfc, bfc);      // in flight during the wait
+    if (threadIdx.x == 0) {
+        int ok = 1;
+#pragma unroll
+        for (int i = 0; i < TILES; ++i) {
+            if (i >= nt) break;
+            const int* const theirs = &flags[2 * tl[i] + (dir ^ 1)];
+            int spins = 0, v;
+            while (((v = __hip_atomic_load(theirs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 4) != epoch[i]) {
+                __builtin_amdgcn_s_sleep(8);
+                if (++spins > (1 << 22)) break;   // (seconds: the partner never came - reported, not waited for)
+            }
+            ok &= (v >> 4) == epoch[i] && (v & 15) == xcc;
+        }
+        partner_ok = ok;
     }
     __syncthreads();
     if (!partner_ok) {                            // (value 4: api.hip runs the call again with one launch per layer and stops pairing)
@@ -567,29 +680,34 @@ __global__ __launch_bounds__(256, 2) void band_pair_h2_kernel(const float* __res
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");      // (orders the plane loads below behind the poll)
     asm volatile("buffer_inv sc0" ::: "memory");                 // the partner's planes from L2, not from a line this CU's L1 may hold
-    band_layer_body<2 * HID, false, PART>(lds, dir, tile, hb0, hb1, w1, b1, N, L, range_flag, nullptr, wfc, bfc);
+    band_commit_weights<2 * HID, PART>(W, lds);
+    for (int i = 0; i < nt; ++i) {
+        if (i) __syncthreads();
+        band_run_tile<2 * HID, false, PART>(W, lds, dir, tile_of(i), hb0, hb1, N, L, range_flag, nullptr);
+    }
 }
 
-// both layers of a band block as one launch (band_pair_h2_kernel); fc16 / fcb as launch_band_lstm's (shares of the fc) or null
+// both layers of a band block as one launch (band_pair_h2_kernel); fc16 / fcb as launch_band_lstm's (shares of the fc) or null;
+// tiles: tiles of 16 sequences per workgroup, 1 or 2 (plan_host.h::band_pair_tiles)
 void launch_band_pair(const float* z, float* hb0, float* hb1, const void* w0pk16, const float* bias0, const void* w1pk16, const float* bias1,
                       int N, int L, int* range_flag, hipStream_t stream, const void* fc16, const float* fcb, int* flags, const OvlConsumer* ovlp,
-                      int* zero_words, int zero_n, hipEvent_t done)
+                      int* zero_words, int zero_n, hipEvent_t done, int tiles)
 {
     if (N <= 0 || L <= 0) return;
     OvlConsumer ovl = {nullptr, 0, 0, nullptr, 0, 2};
     if (ovlp) ovl = *ovlp;
-    const dim3 grid((((N + 15) / 16 + 7) / 8) * 16), block(256);
+    const dim3 grid(band_pair_grid(N, tiles)), block(256);
     // test hook (tests/test_gpu_edges.py): BSRNN_BAND_PAIR=mismatch makes every workgroup publish a wrong XCC id, as if its partner sat on
     // another XCD - the launch reports it (guard value 4) and the context falls back to one launch per layer
     static const int sabotage = [] { const char* e = getenv("BSRNN_BAND_PAIR"); return (e && !strcmp(e, "mismatch")) ? 1 : 0; }();
     // done: an event the launch itself signals when it completes (the completion signal of its own dispatch packet: hipExtLaunchKernel) - a
     // separate hipEventRecord behind the launch is a marker packet of its own and cost the stream a 5-7 us gap (overlapped dual path)
-    if (fc16)
-        hipExtLaunchKernelGGL((band_pair_h2_kernel<true>), grid, block, 0, stream, nullptr, done, 0, z, hb0, hb1, (const uint4*)w0pk16, bias0, (const uint4*)w1pk16, bias1, N, L,
-                              range_flag, (const uint4*)fc16, fcb, flags, sabotage, ovl, zero_words, zero_n);
-    else
-        hipExtLaunchKernelGGL((band_pair_h2_kernel<false>), grid, block, 0, stream, nullptr, done, 0, z, hb0, hb1, (const uint4*)w0pk16, bias0, (const uint4*)w1pk16, bias1, N, L,
-                              range_flag, (const uint4*)nullptr, (const float*)nullptr, flags, sabotage, ovl, zero_words, zero_n);
+    auto go = [&](auto kernel, const void* fc, const float* fb) {
+        hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, nullptr, done, 0, z, hb0, hb1, (const uint4*)w0pk16, bias0, (const uint4*)w1pk16, bias1, N, L,
+                              range_flag, (const uint4*)fc, fb, flags, sabotage, ovl, zero_words, zero_n);
+    };
+    if (fc16) { if (tiles == 2) go(band_pair_h2_kernel<true, 2>, fc16, fcb); else go(band_pair_h2_kernel<true, 1>, fc16, fcb); }
+    else { if (tiles == 2) go(band_pair_h2_kernel<false, 2>, nullptr, nullptr); else go(band_pair_h2_kernel<false, 1>, nullptr, nullptr); }
 }
 
 void launch_band_lstm(const float* xin, float* hout, const float* wpk, const void* wpk16, const float* bias,

@@ -33,20 +33,37 @@ struct Flow {
     bool time_fc;        // the time-axis launch forms its block's fc + residual itself (no MS_TIMEFC launch)
     int seqs, nwg;       // the time-axis launch: sequences per workgroup (4, or 8 on time_lstm_h2w8_kernel) and workgroups
     bool overlap;        // the dual path runs overlapped (run_overlapped), given its tables and no graph capture (ovl_table)
+    int band_tiles;      // the pair launch: tiles of 16 sequences per workgroup, 1 or 2 (band_pair_tiles)
 };
 // What the process fixed at first use (api.hip reads the environment): BSRNN_BAND_PAIR=0 one launch per band
 // layer; BSRNN_BAND_FC=gemm the band block's fc + residual as a grouped-GEMM launch instead of the shares the pair launch writes and the
 // time-axis launch adds (the second layer alone with the shares sits at the edge of 256 VGPRs - as a kernel of its own it spilled four
 // registers - and is not shipped); BSRNN_TIME_KERNEL=v3 the time block's fc as a launch of its own; BSRNN_TIME_SEQ8 = 0 / 1: eight
-// sequences per time-axis workgroup never / always (unset, -1: where four would need more than one round of workgroups).
+// sequences per time-axis workgroup never / always (unset, -1: where four would need more than one round of workgroups);
+// BSRNN_BAND_PAIR=tiles1 / tiles2: the pair launch with one / two tiles per workgroup whatever the call's size (A/Bs and tests).
 struct PlanKnobs {
     bool band_pair, band_parts, time_fused;
     int seq8;
     int gemm_mode, lstm_mode;      // GemmMode, LstmMode
     int cus;                       // CUs of the device
+    int band_tiles = 0;            // 1 / 2: tiles per workgroup of the pair launch forced; 0: by the call's size (band_pair_tiles)
 };
 // What the thread and the context contribute: force_f32() (the exact re-run plans again), fused chains, and the context's sticky fall-backs
 struct PlanState { bool exact, fused, band_pair_off, overlap_env, overlap_off; };
+
+// Tiles of 16 sequences per workgroup of the band-pair launch over N sequences (the call's frame rows).  A workgroup loads both layers'
+// weights (343 KB of fragments) whatever it computes with them, and the launch holds 2 workgroups per CU: where one tile per workgroup
+// (2 directions x ceil(N / 16) workgroups) needs more than one dispatch round, a workgroup takes two tiles on one set of weights and the
+// launch half as many workgroups.  Within one round nothing would be gained, only the launch's parallelism halved.
+inline int band_pair_tiles(int N, int cus, int force = 0)
+{
+    if (force == 1 || force == 2) return force;
+    return 2 * ((N + 15) / 16) > 2 * cus ? 2 : 1;
+}
+// Workgroups of that launch: a slot is `tiles` consecutive tiles (an odd tile count leaves the last slot of two with one), and 16
+// consecutive workgroups are the two directions of eight slots - partners 8 ids apart (lstm.hip::band_tiles_of_block)
+inline int band_pair_slots(int N, int tiles) { const int nt = (N + 15) / 16; return tiles == 2 ? (nt + 1) / 2 : nt; }
+inline int band_pair_grid(int N, int tiles) { return (band_pair_slots(N, tiles) + 7) / 8 * 16; }
 
 // The plan of a call of C rows x T frames on K bands.  gemv / overlap: the entry point may run a few frame rows on the GEMV kernels / the
 // dual path overlapped.
@@ -67,6 +84,7 @@ inline Flow plan_call(int K, int C, int T, bool gemv, bool overlap, const PlanKn
     if (!f.lstm_f32 && gemm16 && M <= 8 && K <= BS_MAXL) f.band = BAND_SMALL;
     else if (pair && kn.band_parts && f.time_fc) f.band = BAND_PAIR_PARTS;
     else f.band = pair ? BAND_PAIR : BAND_LAYERS;
+    f.band_tiles = band_pair_tiles(M, cus, kn.band_tiles);
     f.seqs = f.time_fc && (kn.seq8 == 1 || (kn.seq8 < 0 && (N + 3) / 4 > cus)) ? 8 : 4;
     f.nwg = (N + f.seqs - 1) / f.seqs;
     // Overlapped: the parts flow with fused chains (the launches that know how to publish / wait), a time-axis launch that leaves CUs free

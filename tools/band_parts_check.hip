@@ -4,6 +4,7 @@
 //   (1) band layer 1 with PART against the same layer without it + fc(h) evaluated in double; run-to-run bit stability
 //   (2) time kernel with PART on (z, part) against the kernel without PART on the pre-added rows (z + pf) + pb: bit-identical;
 //       run-to-run bit stability
+//   (3) both layers in one launch, one and two tiles per workgroup, against layer 0 and layer 1 as two launches: bit-identical, every run
 //   hipcc -O3 --offload-arch=gfx950 -fno-slp-vectorize -o build/band_parts_check tools/band_parts_check.hip
 #include "../speechseparation_amd/csrc/lstm.hip"
 #include <algorithm>
@@ -122,8 +123,8 @@ static int band(int N, int L, int runs)
     return (bad != 0) + (untouched != 0) + (unstable != 0);
 }
 
-// (3) both layers in one launch (band_pair_h2_kernel, partner workgroups hand the layer-0 planes over through L2) against layer 0 and
-//     layer 1 (with the shares) as two launches: bit for bit, every run
+// (3) both layers in one launch (band_pair_h2_kernel, partner workgroups hand the layer-0 planes over through L2), with one and with two
+//     tiles per workgroup, against layer 0 and layer 1 (with the shares) as two launches: bit for bit, every run
 static int pair(int N, int L, int runs)
 {
     const size_t nrow = (size_t)N * L;
@@ -159,21 +160,35 @@ static int pair(int N, int L, int runs)
     CK(hipMemcpy(ref.data(), p_ref, ref.size() * 4, hipMemcpyDeviceToHost));
     int* flag; CK(hipMalloc(&flag, 4)); CK(hipMemset(flag, 0, 4));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    float best = 1e9f; size_t total = 0;
-    for (int r = 0; r < runs; ++r) {
-        CK(hipMemset(p_pair, 0xff, nrow * 128 * 4)); CK(hipMemset(hb0b, 0xff, nrow * 128 * 4));
-        CK(hipEventRecord(e0, 0));
-        hipLaunchKernelGGL((band_pair_h2_kernel<true>), g1, block, 0, 0, (const float*)z, hb0b, p_pair, (const uint4*)w0, b0, (const uint4*)w1, b1, N, L, flag,
-                           (const uint4*)wfc, bfc, flags, 0, OvlConsumer{nullptr, 0, 0, nullptr, 0, 2}, (int*)nullptr, 0);
-        CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
-        float ms; CK(hipEventElapsedTime(&ms, e0, e1)); best = std::min(best, ms * 1e3f);
-        CK(hipMemcpy(cur.data(), p_pair, cur.size() * 4, hipMemcpyDeviceToHost));
-        size_t d = 0; for (size_t i = 0; i < cur.size(); ++i) d += cur[i] != ref[i];
-        total += d;
-        if (d) printf("   run %d: %zu words differ from the two launches\n", r, d);
+    // one tile per workgroup, then two (each layer's weights loaded once for both; an odd tile count leaves the last workgroups with one):
+    // the same flags, counted on by both forms
+    size_t total = 0;
+    for (int tiles = 1; tiles <= 2; ++tiles) {
+        const int slots = tiles == 2 ? ((N + 15) / 16 + 1) / 2 : (N + 15) / 16;
+        const dim3 gp(((slots + 7) / 8) * 16);
+        float best = 1e9f; size_t differ = 0;
+        for (int r = 0; r < runs; ++r) {
+            CK(hipMemset(p_pair, 0xff, nrow * 128 * 4)); CK(hipMemset(hb0b, 0xff, nrow * 128 * 4));
+            CK(hipEventRecord(e0, 0));
+            if (tiles == 2)
+                hipLaunchKernelGGL((band_pair_h2_kernel<true, 2>), gp, block, 0, 0, (const float*)z, hb0b, p_pair, (const uint4*)w0, b0, (const uint4*)w1, b1, N, L, flag,
+                                   (const uint4*)wfc, bfc, flags, 0, OvlConsumer{nullptr, 0, 0, nullptr, 0, 2}, (int*)nullptr, 0);
+            else
+                hipLaunchKernelGGL((band_pair_h2_kernel<true, 1>), gp, block, 0, 0, (const float*)z, hb0b, p_pair, (const uint4*)w0, b0, (const uint4*)w1, b1, N, L, flag,
+                                   (const uint4*)wfc, bfc, flags, 0, OvlConsumer{nullptr, 0, 0, nullptr, 0, 2}, (int*)nullptr, 0);
+            CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1)); best = std::min(best, ms * 1e3f);
+            CK(hipMemcpy(cur.data(), p_pair, cur.size() * 4, hipMemcpyDeviceToHost));
+            size_t d = 0; for (size_t i = 0; i < cur.size(); ++i) d += cur[i] != ref[i];
+            differ += d;
+            if (d) printf("   %d tile(s) per workgroup, run %d: %zu words differ from the two launches\n", tiles, r, d);
+        }
+        printf("   pair launch, %d tile(s) per workgroup (%u workgroups) %.1f us; words differing from layer 0 + layer 1 as two launches over %d runs: %zu\n",
+               tiles, gp.x, best, runs, differ);
+        total += differ;
     }
     int hf = 0; CK(hipMemcpy(&hf, flag, 4, hipMemcpyDeviceToHost));
-    printf("   pair launch %.1f us; words differing from layer 0 + layer 1 as two launches over %d runs: %zu; flag %d\n", best, runs, total, hf);
+    printf("   flag %d\n", hf);
     hipFree(z); hipFree(hb0); hipFree(hb0b); hipFree(p_ref); hipFree(p_pair); hipFree(w0); hipFree(w1); hipFree(wfc); hipFree(b0); hipFree(b1); hipFree(bfc); hipFree(flags); hipFree(flag);
     return total != 0 || hf != 0;
 }
