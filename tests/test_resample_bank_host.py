@@ -219,7 +219,7 @@ def test_python_layer_signatures_and_refusals_before_any_device_work(native):
     for name, args in (("assign", ["self", "rows", "pair"]), ("ready", ["self", "row", "n"]), ("process", ["self", "wave", "counts"]),
                        ("flush_rows", ["self", "rows"]), ("reset_rows", ["self", "rows"])):
         assert list(inspect.signature(getattr(ResamplerBank, name)).parameters) == args
-    sig = inspect.signature(StreamPool)                  # the call of the class; __init__ keeps its four parameters (test_stream_rows_host.py)
+    sig = inspect.signature(StreamPool)                  # the call of the class: __init__'s parameters (test_stream_rows_host.py holds those)
     assert list(sig.parameters) == ["model", "slots", "rows_per_session", "device", "rates"] and sig.parameters["rates"].default is None
     assert sig.parameters["rows_per_session"].default == 1 and sig.parameters["device"].default is None
     assert StreamPool(BSRNN(), 3, 2, None, (48000,)).rates == (48000,) and StreamPool(BSRNN(), 3, rates=[16000]).rates == (16000,)

@@ -96,8 +96,8 @@ def test_python_classes_offer_the_methods():
     for name in ("step", "process", "reset", "state"):
         assert callable(getattr(StreamingSeparator, name, None)), name
     sig = inspect.signature(StreamPool.__init__)
-    assert list(sig.parameters) == ["self", "model", "slots", "rows_per_session", "device"]
-    assert sig.parameters["rows_per_session"].default == 1 and sig.parameters["device"].default is None
+    assert list(sig.parameters) == ["self", "model", "slots", "rows_per_session", "device", "rates"]
+    assert sig.parameters["rows_per_session"].default == 1 and sig.parameters["device"].default is None and sig.parameters["rates"].default is None
     assert list(inspect.signature(StreamPool.step).parameters) == ["self", "chunks", "mix"]
     assert inspect.signature(StreamPool.step).parameters["mix"].default is None
     for name in ("open", "close", "export", "adopt"):
