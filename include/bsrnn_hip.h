@@ -265,6 +265,24 @@ int  bsrnn_critic_conv_backward(bsrnn_ctx* ctx, const float* x_dev, const float*
  * BSRNN_EARG as above, or for a null out. */
 int  bsrnn_critic_conv_layout(int32_t C, int32_t I, int32_t T, int32_t O, int32_t out[5]);
 
+/* The critic's input as the reference forms it (train-discriminator.py:62-68): torch.stft(wave * scale, n_fft = 4096, hop_length = 1024,
+ * window = hann_window(4096)) - centred, reflect padding - followed by torch.cat((X.real, X.imag), dim = 1).  wave: R rows of n > 2048
+ * samples, wave_stride floats apart; T = 1 + n / 1024 frames; x [R][4098][T], T contiguous: rows 0 .. 2048 hold the real parts of bins
+ * 0 .. 2048, rows 2049 .. 4097 the imaginary parts, and rows 2049 and 4097 are exactly zero.  Each sample is multiplied by scale first,
+ * then by the window (the order torch rounds in), so the call with scale s equals the call on the fp32 product wave * s with scale 1 bit
+ * for bit.  Exact fp32, no atomics, bit-reproducible; a frame's bits do not depend on the rows or frames around it.  wave is only read.
+ * Workspace: the grow-only training buffer of the context, at most 128 * 32 * 4098 floats (67 MB) whatever the clip: the call runs in
+ * slabs of rows x frames (bsrnn_critic_spectrum_layout).  Its twiddle and window tables (49 KB) are built and uploaded by a context's
+ * first call (bsrnn_debug_counter(0) counts it); bsrnn_create allocates nothing for it.
+ * BSRNN_EARG for a null context or pointer, R < 1, n <= 2048, wave_stride < n, a scale that is not finite, and R * 4098 * T beyond
+ * 2^31 - 1; then BSRNN_ESTATE on a host-only context.  Nothing is launched on a refusal. */
+int  bsrnn_critic_spectrum(bsrnn_ctx* ctx, const float* wave_dev, int64_t wave_stride, float* x_dev,
+                           int32_t R, int64_t n, float scale, void* stream);
+/* How the call above is cut (measurement / test support; no context or device needed): out[0] = T; out[1] = the slabs, each one launch
+ * of the transform and one of the transpose; out[2] = frames per slab (rows go in blocks of min(R, 128), a block's frames in slabs of
+ * 32 * (128 / rows per block) frames); out[3] = the workspace in floats.  BSRNN_EARG as above, or for a null out. */
+int  bsrnn_critic_spectrum_layout(int32_t R, int64_t n, int64_t out[4]);
+
 /* torch.optim.AdamW(model.parameters(), lr, weight_decay) of train.py:50, one tensor per call: p, m (exp_avg), v (exp_avg_sq)
  * updated in place from the gradient g; `step` counts from 1 (bias correction).  n floats each, device pointers.  The betas are
  * double, as torch's: 1 - beta2 and the bias corrections are formed from them in double (from 0.999f, 1 - beta2 is 1.3e-5 off). */

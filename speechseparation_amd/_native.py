@@ -41,6 +41,7 @@ SYMBOLS = [
     "bsrnn_hop_activity", "bsrnn_section_rule_default", "bsrnn_section_state_reset", "bsrnn_sections_scan",
     "bsrnn_remix_ragged",
     "bsrnn_critic_conv_layout", "bsrnn_critic_conv_forward", "bsrnn_critic_conv_backward",
+    "bsrnn_critic_spectrum", "bsrnn_critic_spectrum_layout",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
@@ -206,6 +207,8 @@ def _load():
         "bsrnn_critic_conv_layout": (C.c_int, [i32, i32, i32, i32, C.POINTER(i32)]),
         "bsrnn_critic_conv_forward": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
         "bsrnn_critic_conv_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "bsrnn_critic_spectrum": (C.c_int, [vp, vp, i64, vp, i32, i64, C.c_float, vp]),
+        "bsrnn_critic_spectrum_layout": (C.c_int, [i32, i64, C.POINTER(i64)]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),
         "bsrnn_stage_name": (C.c_char_p, [i32]),

@@ -652,6 +652,7 @@ void destroy_now(bsrnn_ctx* c)
         if (c->d_chain[ch]) (void)hipFree(c->d_chain[ch]);
     free_chain_tasks(c);
     if (c->d_tables) (void)hipFree(c->d_tables);
+    if (c->d_cs_tables) (void)hipFree(c->d_cs_tables);
     if (c->d_train_ws) (void)hipFree(c->d_train_ws);
     for (float* p : c->train_ws_retired) (void)hipFree(p);
     for (void* p : c->retired) (void)hipFree(p);

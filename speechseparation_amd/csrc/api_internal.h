@@ -152,6 +152,8 @@ struct bsrnn_ctx {
                                             // every model entry point put workspace addresses into captured kernel nodes)
     int* d_colmap = nullptr;
     FftTables tb;
+    float* d_cs_tables = nullptr;      // tables of the critic's 4096-point analysis, built and uploaded by the first bsrnn_critic_spectrum (api_critic.hip)
+    CsTables cs{};
 
     // workspace (grow-only)
     size_t cap_rows = 0;

@@ -13,6 +13,7 @@
 #include "metrics_host.h"       // MetricClip, METRIC_TIME_Q: what the metric kernels and their host tail agree on (HIP-free)
 #include "remix_host.h"         // RemixRow, RemixTerm: what the re-mix kernel knows of a row and of a term (HIP-free)
 #include "critic_host.h"        // CriticLayout: tiles, K slabs and reduction chunks of the critic's convolution (HIP-free)
+#include "critic_spectrum_host.h"   // CsSlab: the rows x frames one launch pair of the critic's 4096-point analysis owns (HIP-free)
 
 namespace bsrnn {
 
@@ -433,5 +434,17 @@ void launch_critic_forward(const float* x, const float* w, const float* b, float
                            hipStream_t s);
 void launch_critic_backward(const float* x, const float* w, const float* y, const float* dy, float* dx, float* dw, float* db, float* scratch,
                             int C, int I, int T, int O, int leaky, hipStream_t s);
+
+// The critic's input (bsrnn_critic_spectrum; stft4096.hip, the definition and the slab rule: critic_spectrum_host.h): the 4096-point
+// analysis of slab q of a call - rows [r0, r1) x frames [t0, t1) of wave (rows `stride` floats apart, n samples each, T frames) - as
+// frame-major records scratch [(r - r0) * (t1 - t0) + (t - t0)][4098] (re, im interleaved), then their transpose into
+// x [R][4098][T] (real rows, then imaginary rows).
+struct CsTables {            // device tables, built in double on the host at the first bsrnn_critic_spectrum of a context
+    const float2* tw;        // exp(-2 pi i k / 2048), k < 2048
+    const float2* split;     // exp(-2 pi i k / 4096), k <= 2048
+    const float* hann;       // periodic Hann(4096)
+};
+void launch_critic_spectrum_slab(const CsTables& tb, const float* wave, int64_t stride, int64_t n, float scale, float* scratch, float* x, int T,
+                                 const CsSlab& q, hipStream_t s);
 
 }  // namespace bsrnn

@@ -5,6 +5,9 @@ time, the mean over the rows, `Linear(32, 1)` and a sigmoid: [C, in_channels, T]
 `torch.autograd.Function` over `bsrnn_critic_conv_forward` / `bsrnn_critic_conv_backward` (exact fp32, bit-reproducible), the Linear
 layer goes through `bsrnn_linear_train_*` (train.LinearFunction); the two means and the sigmoid are torch on the same device.  No CPU
 fallback: the library has to be there and the tensors on the GPU.
+
+`critic_spectrum` forms the critic's input as the reference's train-discriminator.py:62-68 does - the 4096-point analysis, real parts
+then imaginary parts, 4098 channels - with the library's `bsrnn_critic_spectrum`.
 """
 import ctypes
 
@@ -32,6 +35,32 @@ def conv_layout(C, I, T, O):
     out = (ctypes.c_int32 * 5)()
     _native.check(_lib.bsrnn_critic_conv_layout(C, I, T, O, out))
     return dict(zip(("T_out", "slabs", "ch_per_slab", "dw_chunks", "dw_frames"), out))
+
+
+def spectrum_layout(R, n):
+    """bsrnn_critic_spectrum_layout as a dict: the frames T = 1 + n // 1024, the slabs a call of R rows x n samples runs in, the frames
+    per slab and the workspace in floats (never more than 128 * 32 * 4098, whatever the clip)."""
+    out = (ctypes.c_int64 * 4)()
+    _native.check(_lib.bsrnn_critic_spectrum_layout(R, n, out))
+    return dict(zip(("T", "slabs", "frames_per_slab", "scratch_floats"), out))
+
+
+def critic_spectrum(wave, scale=1.0):
+    """The critic's input of train-discriminator.py:62-68 on the library's kernel: wave [R, n] (cuda, n > 2048) ->
+    torch.cat((X.real, X.imag), dim=1) of X = torch.stft(wave * scale, n_fft=4096, hop_length=1024, window=hann_window(4096)), i.e.
+    [R, 4098, 1 + n // 1024] on the wave's device.  `scale` is applied to every sample before the window, as the product wave * scale
+    rounds; no gradient (the critic's input is data).  No CPU fallback."""
+    if not isinstance(wave, torch.Tensor) or wave.dim() != 2:
+        raise ValueError("critic_spectrum: expected wave [R, n], got %s" % (tuple(getattr(wave, "shape", ())),))
+    if not wave.is_cuda:
+        raise ValueError("critic_spectrum: the transform runs on the GPU: wave must be a cuda tensor (there is no CPU fallback)")
+    R, n = wave.shape
+    dev = wave.device
+    w = _f32c(wave)
+    with torch.cuda.device(dev):
+        x = torch.empty((R, 4098, 1 + n // 1024), device=dev)
+        _native.check(_lib.bsrnn_critic_spectrum(_context(dev), _p(w), n, _p(x), R, n, float(scale), _s(dev)))
+    return x
 
 
 def reference_channel_order(y):
@@ -80,10 +109,11 @@ class Discriminator(nn.Module):
     """bsrnn.py:512-536.  `state_dict()` is the reference's, key for key and shape for shape (`layers.{0,2,4,6}.{weight,bias}`,
     `layers2.0.{weight,bias}`), so `discriminator.pth` interchanges.
 
-    in_channels: the reference hard-codes 4098 = 2 * 2049, the channels of the 4096-point transform of train-discriminator.py:64.  That
-    default is stale in the reference itself: m_dataset.train_infer feeds the critic `cat(real, imag)` of the model's 2048-point output,
+    in_channels: the reference hard-codes 4098 = 2 * 2049, the channels of the 4096-point transform of train-discriminator.py:64;
+    `critic_spectrum` forms that input, and `train-discriminator.py --n_fft 4096` trains this default critic on it.  The default is
+    stale in the reference's other caller: m_dataset.train_infer feeds the critic `cat(real, imag)` of the model's 2048-point output,
     2050 channels, so its own call raises with the default critic.  `Discriminator(2050)` is the size `metrics.train_infer`,
-    `train.train_loss` and this project's `train-discriminator.py` use (the library has no 4096-point transform)."""
+    `train.train_loss` and `train-discriminator.py` at its default `--n_fft 2048` use."""
 
     def __init__(self, in_channels=4098):
         super().__init__()

@@ -10,9 +10,10 @@ ReduceLROnPlateau('min', patience=8, factor=0.8) stepped with the epoch's mean l
 reference starts its best at 0 and so never saves a critic whose sums stay negative).  Same flags:
 --datapath --mini --batch_size --resume --loss_sdr; as in the reference the last two are accepted and do nothing.
 
-One difference, on purpose: the reference analyses with a 4096-point transform (4098 channels).  The library has no 4096-point transform;
-this loop uses its own 2048-point `train.stft` (hop 1024, 2050 channels) and therefore trains `Discriminator(2050)` - the size the
-reference's own `train_infer` feeds its critic, and the one `metrics.train_infer` / `train.train_loss` can use.
+--n_fft chooses the analysis.  4096 is the reference's: `critic_spectrum` (the 4096-point transform, hop 1024, 4098 channels) and the
+default `Discriminator()`, so a `discriminator.pth` of the reference's script trains on and validates here.  2048, the default, is the
+library's `train.stft` (hop 1024, 2050 channels) and `Discriminator(2050)` - the size the reference's own `train_infer` feeds its critic,
+and the one `metrics.train_infer` / `train.train_loss` can use.
 
 Data: <datapath>/{train,val}/<clip>/{mixture,speech}.wav as train.py reads them (a `tr/` resp. `cv/` folder is used when those are
 missing), or --synthetic N clips of seeded noise.  A clip needs 614 400 samples (601 frames, the critic's shortest input); shorter ones
@@ -25,7 +26,7 @@ import random
 import torch
 
 from speechseparation_amd import audio, train as hip_train, weights
-from speechseparation_amd.discriminator import MIN_FRAMES, Discriminator, reference_channel_order
+from speechseparation_amd.discriminator import MIN_FRAMES, Discriminator, critic_spectrum, reference_channel_order
 
 MIN_SAMPLES = (MIN_FRAMES - 1) * 1024
 
@@ -57,12 +58,14 @@ def load_pair(item, device):
     return pair[0][:, :n].contiguous(), pair[1][:, :n].contiguous()
 
 
-def spectra(item, device, rng):
+def spectra(item, device, rng, n_fft=2048):
     """The two critic inputs of a clip (train-discriminator.py:59-68), or None for a clip that is too short."""
     mix, speech = load_pair(item, device)
     if mix.shape[1] < MIN_SAMPLES:
         return None
     scale = rng.uniform(0.02, 1.0)
+    if n_fft == 4096:
+        return tuple(critic_spectrum(w, scale) for w in (mix, speech))
     return tuple(reference_channel_order(hip_train.stft(w * scale)) for w in (mix, speech))
 
 
@@ -78,6 +81,8 @@ def main(argv=None):
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--outdir", type=str, default=".")
     ap.add_argument("--seed", type=int, default=0, help="seed of the clip order and of the random scales")
+    ap.add_argument("--n_fft", type=int, choices=(2048, 4096), default=2048,
+                    help="the analysis: 4096 = the reference's transform and its Discriminator() of 4098 channels; 2048 = train.stft and Discriminator(2050)")
     args = ap.parse_args(argv)
     if args.synthetic:
         train_set, val_set = list(range(args.synthetic)), list(range(args.synthetic, args.synthetic + args.synthetic // 4 + 1))
@@ -94,8 +99,12 @@ def main(argv=None):
     device = torch.device(args.device)
     rng = random.Random(args.seed)
     torch.manual_seed(args.seed)
-    print("2048-point STFT (hop 1024) of the library: Discriminator(2050), not the reference's 4096-point / 4098-channel analysis")
-    model = Discriminator(2050).to(device)
+    if args.n_fft == 4096:
+        print("4096-point STFT (hop 1024) of the library: Discriminator() of 4098 channels, the reference's analysis")
+        model = Discriminator().to(device)
+    else:
+        print("2048-point STFT (hop 1024) of the library: Discriminator(2050), not the reference's 4096-point / 4098-channel analysis")
+        model = Discriminator(2050).to(device)
     optimizer = hip_train.AdamW(model.parameters(), lr=1e-4, weight_decay=0)
     scheduler = hip_train.ReduceLROnPlateau(optimizer, "min", patience=8, factor=0.8)
     epoch, best = 0, None
@@ -105,7 +114,7 @@ def main(argv=None):
         rng.shuffle(order)
         batch, epoch_loss = 0, 0.0
         for item in order:
-            pair = spectra(item, device, rng)
+            pair = spectra(item, device, rng, args.n_fft)
             if pair is None:
                 print("skipped (shorter than %d samples):" % MIN_SAMPLES, item)
                 continue
@@ -127,7 +136,7 @@ def main(argv=None):
             model.eval()
             val_loss = 0.0
             for item in val_set:
-                pair = spectra(item, device, rng)
+                pair = spectra(item, device, rng, args.n_fft)
                 if pair is None:
                     continue
                 val_loss += (model(pair[1]) - model(pair[0])).item()
