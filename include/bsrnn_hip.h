@@ -283,6 +283,47 @@ int  bsrnn_critic_spectrum(bsrnn_ctx* ctx, const float* wave_dev, int64_t wave_s
  * 32 * (128 / rows per block) frames); out[3] = the workspace in floats.  BSRNN_EARG as above, or for a null out. */
 int  bsrnn_critic_spectrum_layout(int32_t R, int64_t n, int64_t out[4]);
 
+/* The committed critic: the whole Discriminator (four layers, the mean over time, the mean over the rows, Linear(32, 1), sigmoid) frozen
+ * into an object that scores in one call - the critic as a separator's training loop uses it, under no_grad, while its weights stand.
+ *   bsrnn_critic_create   an object for a critic of in_channels input channels on ctx.  Allocates, once, everything the object ever owns
+ *                         (three blocks, bsrnn_debug_counter(0)): its own fp32 copy of every parameter and the first layer's weights as
+ *                         two fp16 pieces in the matrix cores' operand order - out[9] and out[8] bytes of bsrnn_critic_score_layout,
+ *                         about 2 x 268 MB at 4098 channels, 2 x 134 MB at 2050.  On a host-only context the object is made without them
+ *                         and answers only its argument checks.  It keeps its context alive like a bsrnn_stream; destroy it with
+ *                         bsrnn_critic_destroy (NULL is ignored).
+ *   bsrnn_critic_commit   a SNAPSHOT of the parameters (torch's layouts: conv_w_dev[l] [O_l][I_l][16], conv_b_dev[l] [O_l] for the widths
+ *                         in_channels -> 1024 -> 128 -> 64 -> 32, lin_w_dev [32], lin_b_dev [1]): copied on `stream`, the first layer split
+ *                         on the device (a1 = fp16(a), a2 = fp16(2^11 (a - a1))), max |W| recorded.  Synchronous; the caller's arrays may
+ *                         change or go afterwards.  May be repeated (the object then follows the new weights).  A first-layer weight beyond
+ *                         +-65504 (or NaN) makes the image unusable: that object scores with the exact kernels, always.
+ *   bsrnn_critic_score    x [C][in_channels][T] (T >= 601 contiguous frames) -> score_dev[0], and the first layer's output
+ *                         y1 [C][1024][(T - 16) / 3 + 1] when y1_dev is not NULL.  x_order 0: the channels in the reference's order (all real
+ *                         parts, then all imaginary parts: bsrnn_critic_spectrum's); x_order 1: the separator's interleaved spectrum (re, im,
+ *                         re, im, ...), channel i of the critic reading row 2 i for i < in_channels / 2, else row 2 (i - in_channels / 2) + 1 -
+ *                         no reorder copy.  The first layer (over 99 % of the work) follows the context's compute mode like the model entry
+ *                         points: fp32 in and out, products as two fp16 pieces on the f16 matrix cores with fp32 accumulation (three terms),
+ *                         range guard on x.  Under BSRNN_RANGE_EXACT the call waits and, if an |x| passed 65504, runs again on the exact
+ *                         kernels (bsrnn_critic_conv_forward's) before returning; under BSRNN_RANGE_DEFERRED it is asynchronous and
+ *                         bsrnn_sync / the next model call report BSRNN_ERANGE.  With BSRNN_GEMM=f32 every layer is exact.  Layers 2 - 4
+ *                         are always exact.  No atomics: K runs in slabs of input channels (out[4], out[5] of the layout), added in slab
+ *                         order; bit-reproducible.  Workspace: the grow-only training buffer of the context (out[6] floats; out[7] when an
+ *                         interleaved x goes through the exact kernels, which read a planar copy); nothing else is allocated.
+ * BSRNN_EARG, before anything touches the device and also on a host-only context: a null object or pointer (y1_dev may be NULL), C < 1,
+ * T < 601, x_order outside {0, 1}, x_order 1 with an odd in_channels, a tensor or workspace beyond 2^31 - 1 elements, score_dev or
+ * y1_dev overlapping x (the re-run reads x again) or each other.  Then BSRNN_ESTATE on a host-only context and before the first commit.
+ * Nothing is launched on a refusal. */
+typedef struct bsrnn_critic bsrnn_critic;
+int  bsrnn_critic_create(bsrnn_ctx* ctx, int32_t in_channels, bsrnn_critic** out);
+int  bsrnn_critic_commit(bsrnn_critic* critic, const float* const conv_w_dev[4], const float* const conv_b_dev[4],
+                         const float* lin_w_dev, const float* lin_b_dev, void* stream);
+int  bsrnn_critic_score(bsrnn_critic* critic, const float* x_dev, int32_t C, int32_t T, int32_t x_order,
+                        float* score_dev, float* y1_dev, void* stream);
+/* Sizes of a score (no context or device needed): out[0..3] = frames behind the four layers; out[4] = K slabs of the fp16x2 first layer,
+ * out[5] = input channels per slab (the last may hold fewer); out[6] = workspace in floats, out[7] = with the planar copy; out[8] = bytes
+ * of the fp16x2 image, out[9] = bytes of the fp32 snapshot.  BSRNN_EARG as above, or for a null out. */
+int  bsrnn_critic_score_layout(int32_t in_channels, int32_t C, int32_t T, int64_t out[10]);
+void bsrnn_critic_destroy(bsrnn_critic* critic);
+
 /* torch.optim.AdamW(model.parameters(), lr, weight_decay) of train.py:50, one tensor per call: p, m (exp_avg), v (exp_avg_sq)
  * updated in place from the gradient g; `step` counts from 1 (bias correction).  n floats each, device pointers.  The betas are
  * double, as torch's: 1 - beta2 and the bias corrections are formed from them in double (from 0.999f, 1 - beta2 is 1.3e-5 off). */

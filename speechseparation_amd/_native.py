@@ -42,6 +42,7 @@ SYMBOLS = [
     "bsrnn_remix_ragged",
     "bsrnn_critic_conv_layout", "bsrnn_critic_conv_forward", "bsrnn_critic_conv_backward",
     "bsrnn_critic_spectrum", "bsrnn_critic_spectrum_layout",
+    "bsrnn_critic_create", "bsrnn_critic_commit", "bsrnn_critic_score", "bsrnn_critic_score_layout", "bsrnn_critic_destroy",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
@@ -209,6 +210,11 @@ def _load():
         "bsrnn_critic_conv_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
         "bsrnn_critic_spectrum": (C.c_int, [vp, vp, i64, vp, i32, i64, C.c_float, vp]),
         "bsrnn_critic_spectrum_layout": (C.c_int, [i32, i64, C.POINTER(i64)]),
+        "bsrnn_critic_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
+        "bsrnn_critic_commit": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp]),
+        "bsrnn_critic_score": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
+        "bsrnn_critic_score_layout": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
+        "bsrnn_critic_destroy": (None, [vp]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),
         "bsrnn_stage_name": (C.c_char_p, [i32]),

@@ -3,6 +3,9 @@
 // the training entry points' grow-only buffer of the context.
 // And the critic's input (bsrnn_critic_spectrum): the 4096-point analysis of the reference's train-discriminator.py:62-68.  The definition,
 // the slab rule and every size: critic_spectrum_host.h; the kernels: stft4096.hip.
+// And the committed critic (bsrnn_critic_create / _commit / _score): the whole module frozen into an object, its first layer on the fp16x2
+// matrix path under the context's range policy, the exact layers above as its re-run.  The image, the plan and every size:
+// critic_score_host.h; the kernels: critic_score.hip.
 #include "api_internal.h"
 
 #include <cmath>
@@ -19,6 +22,48 @@ static int critic_sizes_ok(int32_t C, int32_t I, int32_t T, int32_t O, const cha
                     who, C, I, T, O);
     }
 }
+
+static int score_sizes_ok(int32_t I, int32_t C, int32_t T, int32_t x_order, const char* who)
+{
+    switch (csc_check(I, C, T, x_order)) {
+    case CSC_OK: return 0;
+    case CSC_BAD_CHANNELS: return fail(BSRNN_EARG, "%s: need in_channels >= 1, got %d", who, I);
+    case CSC_BAD_ROWS: return fail(BSRNN_EARG, "%s: need C >= 1 rows, got C = %d", who, C);
+    case CSC_TOO_SHORT: return fail(BSRNN_EARG, "%s: T = %d frames, the four layers need at least %d", who, T, CRITIC_MIN_T);
+    case CSC_BAD_ORDER: return fail(BSRNN_EARG, "%s: x_order = %d is neither 0 (planar) nor 1 (interleaved)", who, x_order);
+    case CSC_ODD_INTERLEAVED: return fail(BSRNN_EARG, "%s: an interleaved input has an even number of channels, in_channels = %d is odd", who, I);
+    default:
+        return fail(BSRNN_EARG, "%s: in_channels = %d, C = %d, T = %d: x, a layer's output or the workspace would pass 2^31 - 1 elements", who, I, C, T);
+    }
+}
+
+// The fp32 snapshot of a committed critic: [w0 | b0 | w1 | b1 | w2 | b2 | w3 | b3 | lin_w | lin_b], every block 16-byte aligned
+struct CriticParams {
+    int64_t off[2 * CRITIC_LAYERS + 2], n[2 * CRITIC_LAYERS + 2], total = 0;
+    explicit CriticParams(int I)
+    {
+        int in = I;
+        for (int l = 0; l < CRITIC_LAYERS; ++l) {
+            n[2 * l] = (int64_t)CRITIC_WIDTHS[l] * in * CRITIC_TAPS;
+            n[2 * l + 1] = CRITIC_WIDTHS[l];
+            in = CRITIC_WIDTHS[l];
+        }
+        n[2 * CRITIC_LAYERS] = CRITIC_WIDTHS[CRITIC_LAYERS - 1];
+        n[2 * CRITIC_LAYERS + 1] = 1;
+        for (int j = 0; j < 2 * CRITIC_LAYERS + 2; ++j) { off[j] = total; total += csc_round4(n[j]); }
+    }
+};
+
+// A frozen critic: its own fp32 copy of every parameter (the exact chain reads it) and the first layer's fp16x2 image (critic_score_host.h)
+struct bsrnn_critic {
+    bsrnn_ctx* ctx = nullptr;
+    int I = 0;
+    bool committed = false, usable = false;      // usable: max |W| of the first layer <= 65504, the image holds finite pieces
+    float wmax = 0.f;
+    float* d_par = nullptr;
+    void* d_img = nullptr;
+    unsigned* d_max = nullptr;
+};
 
 static int spectrum_args_ok(int64_t R, int64_t n, int64_t stride, float scale, const char* who)
 {
@@ -133,6 +178,146 @@ int bsrnn_critic_conv_backward(bsrnn_ctx* c, const float* x, const float* w, con
     launch_critic_backward(x, w, y, dy, dx, dw, db, ws, C, I, T, O, leaky != 0, s);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the committed critic
+int bsrnn_critic_score_layout(int32_t in_channels, int32_t C, int32_t T, int64_t out[10])
+{
+    if (!out) return fail(BSRNN_EARG, "bsrnn_critic_score_layout: nowhere to write the layout");
+    if (int rc = score_sizes_ok(in_channels, C, T, CSC_ORDER_PLANAR, "bsrnn_critic_score_layout")) return rc;
+    const CscPlan p = csc_plan(in_channels, C, T);
+    for (int l = 0; l < CRITIC_LAYERS; ++l) out[l] = p.len[l];
+    out[4] = p.slabs; out[5] = p.ch_per_slab; out[6] = p.ws_floats; out[7] = p.ws_exact_floats;
+    out[8] = csc_image_halves(in_channels) * 2;
+    out[9] = CriticParams(in_channels).total * (int64_t)sizeof(float);
+    return 0;
+}
+
+int bsrnn_critic_create(bsrnn_ctx* c, int32_t in_channels, bsrnn_critic** out)
+{
+    if (!c) return fail(BSRNN_EARG, "null context");
+    if (!out) return fail(BSRNN_EARG, "bsrnn_critic_create: nowhere to put the object");
+    switch (csc_check_channels(in_channels)) {
+    case CSC_OK: break;
+    case CSC_BAD_CHANNELS: return fail(BSRNN_EARG, "bsrnn_critic_create: need in_channels >= 1, got %d", in_channels);
+    default: return fail(BSRNN_EARG, "bsrnn_critic_create: in_channels = %d: the first layer's weights would pass 2^31 - 1 elements", in_channels);
+    }
+    if (c->zombie) return fail(BSRNN_ESTATE, "context was destroyed");
+    bsrnn_critic* k = new bsrnn_critic();
+    k->ctx = c; k->I = in_channels;
+    if (c->device >= 0) {          // (a host-only context gets an object that answers its argument checks and then BSRNN_ESTATE)
+        CallGuard guard_(c);
+        if (!guard_.ok) { delete k; return guard_.refuse(); }
+        const CriticParams q(in_channels);
+        hipError_t e = hipSetDevice(c->device);
+        if (e == hipSuccess) e = hipMalloc((void**)&k->d_par, (size_t)q.total * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc(&k->d_img, (size_t)csc_image_halves(in_channels) * 2);
+        if (e == hipSuccess) e = hipMalloc((void**)&k->d_max, sizeof(unsigned));
+        if (e != hipSuccess) {
+            (void)hipFree(k->d_par); (void)hipFree(k->d_img); (void)hipFree(k->d_max);
+            delete k;
+            (void)hipGetLastError();
+            return fail(BSRNN_EHIP, "bsrnn_critic_create: %s (the snapshot and the image take %lld MB)", hipGetErrorString(e),
+                        (long long)(((int64_t)q.total * 4 + csc_image_halves(in_channels) * 2) >> 20));
+        }
+        g_dbg[DBG_ALLOC] += 3;
+    }
+    ++c->live_streams;
+    *out = k;
+    return 0;
+}
+
+void bsrnn_critic_destroy(bsrnn_critic* k)
+{
+    if (!k) return;
+    bsrnn_ctx* c = k->ctx;
+    if (c->device >= 0) {
+        (void)hipSetDevice(c->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(k->d_par); (void)hipFree(k->d_img); (void)hipFree(k->d_max);
+    }
+    delete k;
+    if (--c->live_streams == 0 && c->zombie) destroy_now(c);     // as bsrnn_stream_destroy: the context goes with the last object that points at it
+}
+
+int bsrnn_critic_commit(bsrnn_critic* k, const float* const conv_w[4], const float* const conv_b[4], const float* lin_w, const float* lin_b,
+                        void* stream)
+{
+    if (!k) return fail(BSRNN_EARG, "null critic");
+    if (!conv_w || !conv_b || !lin_w || !lin_b) return fail(BSRNN_EARG, "bsrnn_critic_commit: null argument (need conv_w_dev, conv_b_dev, lin_w_dev and lin_b_dev)");
+    for (int l = 0; l < CRITIC_LAYERS; ++l)
+        if (!conv_w[l] || !conv_b[l]) return fail(BSRNN_EARG, "bsrnn_critic_commit: null weight or bias pointer of layer %d", l);
+    bsrnn_ctx* c = k->ctx;
+    if (int rc = check_device(c)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const CriticParams q(k->I);
+    const float* src[2 * CRITIC_LAYERS + 2];
+    for (int l = 0; l < CRITIC_LAYERS; ++l) { src[2 * l] = conv_w[l]; src[2 * l + 1] = conv_b[l]; }
+    src[2 * CRITIC_LAYERS] = lin_w; src[2 * CRITIC_LAYERS + 1] = lin_b;
+    k->committed = false;
+    for (int j = 0; j < 2 * CRITIC_LAYERS + 2; ++j)
+        HIP_TRY(hipMemcpyAsync(k->d_par + q.off[j], src[j], (size_t)q.n[j] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(k->d_max, 0, sizeof(unsigned), s));
+    launch_critic_commit(k->d_par + q.off[0], k->d_img, k->d_max, k->I, s);      // (from the snapshot: the caller's may change from here on)
+    HIP_TRY(hipGetLastError());
+    unsigned bits = 0;
+    HIP_TRY(hipMemcpyAsync(&bits, k->d_max, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float top; memcpy(&top, &bits, sizeof(float));
+    k->wmax = top;
+    k->usable = top <= CSC_F16_MAX;                                               // (false for NaN too)
+    k->committed = true;
+    return 0;
+}
+
+int bsrnn_critic_score(bsrnn_critic* k, const float* x, int32_t C, int32_t T, int32_t x_order, float* score, float* y1, void* stream)
+{
+    if (!k) return fail(BSRNN_EARG, "null critic");
+    if (!x || !score) return fail(BSRNN_EARG, "bsrnn_critic_score: null argument (need x_dev and score_dev; only y1_dev may be null)");
+    if (int rc = score_sizes_ok(k->I, C, T, x_order, "bsrnn_critic_score")) return rc;
+    const CscPlan p = csc_plan(k->I, C, T);
+    const size_t nx = (size_t)C * k->I * T * sizeof(float), ny1 = (size_t)C * CSC_O * p.len[0] * sizeof(float);
+    if (ranges_overlap(score, sizeof(float), x, nx) || ranges_overlap(y1, ny1, x, nx))
+        return fail(BSRNN_EARG, "bsrnn_critic_score: %s overlaps x_dev (a call that left the fp16 range is run again from x)",
+                    ranges_overlap(score, sizeof(float), x, nx) ? "score_dev" : "y1_dev");
+    if (ranges_overlap(score, sizeof(float), y1, ny1)) return fail(BSRNN_EARG, "bsrnn_critic_score: score_dev overlaps y1_dev");
+    bsrnn_ctx* c = k->ctx;
+    if (int rc = check_device(c)) return rc;
+    if (!k->committed) return fail(BSRNN_ESTATE, "bsrnn_critic_score: bsrnn_critic_commit() has not been called");
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const CriticParams q(k->I);
+    const float* const par = k->d_par;
+    auto run = [&]() -> int {
+        const bool exact = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+        const bool copy = exact && x_order == CSC_ORDER_INTERLEAVED;
+        const size_t n_ws = (size_t)(copy ? p.ws_exact_floats : p.ws_floats);
+        float* ws = train_scratch(c, n_ws);
+        if (!ws) return fail(BSRNN_EHIP, "bsrnn_critic_score: out of device memory (%zu MB of workspace)", n_ws * sizeof(float) >> 20);
+        float* yl[CRITIC_LAYERS];
+        for (int l = 0; l < CRITIC_LAYERS; ++l) yl[l] = ws + p.off_y[l];
+        if (y1) yl[0] = y1;
+        float* shared = ws + p.off_shared;
+        if (exact) {
+            const float* xp = x;
+            if (copy) { launch_critic_planar(x, ws + p.ws_floats, C, k->I, T, s); xp = ws + p.ws_floats; }
+            launch_critic_forward(xp, par + q.off[0], par + q.off[1], yl[0], shared, C, k->I, T, CSC_O, 1, s);
+        } else {
+            launch_critic_first_h2(x, k->d_img, par + q.off[1], yl[0], shared, c->d_range, p, x_order, s);
+        }
+        for (int l = 1; l < CRITIC_LAYERS; ++l)
+            launch_critic_forward(yl[l - 1], par + q.off[2 * l], par + q.off[2 * l + 1], yl[l], shared, C, CRITIC_WIDTHS[l - 1], p.len[l - 1],
+                                  CRITIC_WIDTHS[l], l + 1 < CRITIC_LAYERS, s);
+        launch_critic_tail(yl[CRITIC_LAYERS - 1], par + q.off[2 * CRITIC_LAYERS], par + q.off[2 * CRITIC_LAYERS + 1], score, C,
+                           p.len[CRITIC_LAYERS - 1], s);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    const bool exact_now = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+    if (int rc = run()) return rc;
+    if (exact_now) return 0;               // (the exact chain ran: no guard to wait for)
+    return finish_call(c, s, run);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include "metrics_host.h"       // MetricClip, METRIC_TIME_Q: what the metric kernels and their host tail agree on (HIP-free)
 #include "remix_host.h"         // RemixRow, RemixTerm: what the re-mix kernel knows of a row and of a term (HIP-free)
 #include "critic_host.h"        // CriticLayout: tiles, K slabs and reduction chunks of the critic's convolution (HIP-free)
+#include "critic_score_host.h"  // CscPlan: the committed critic's weight image, K slabs and workspace (HIP-free)
 #include "critic_spectrum_host.h"   // CsSlab: the rows x frames one launch pair of the critic's 4096-point analysis owns (HIP-free)
 
 namespace bsrnn {
@@ -434,6 +435,17 @@ void launch_critic_forward(const float* x, const float* w, const float* b, float
                            hipStream_t s);
 void launch_critic_backward(const float* x, const float* w, const float* y, const float* dy, float* dx, float* dw, float* db, float* scratch,
                             int C, int I, int T, int O, int leaky, hipStream_t s);
+
+// The committed critic (bsrnn_critic_commit / _score; critic_score.hip, the image, the plan and the workspace: critic_score_host.h).
+// commit: w [1024][I][16] -> image (csc_image_halves(I) fp16 values) and *wmax = max of the bit patterns of |w| (the caller zeroes it).
+// first_h2: layer 1 in fp16x2 from the image, x [C][I][T] in either channel order -> y1 [C][1024][len[0]] (bias and LeakyReLU applied),
+// part = the plan's shared block; raises *range_flag when a staged |x| passes 65504.  tail: y4 [C][32][T4] -> score[0].  planar: an
+// interleaved x copied into the reference's channel order.
+void launch_critic_commit(const float* w, void* image, unsigned* wmax, int I, hipStream_t s);
+void launch_critic_first_h2(const float* x, const void* image, const float* bias, float* y1, float* part, int* range_flag, const CscPlan& p,
+                            int x_order, hipStream_t s);
+void launch_critic_tail(const float* y4, const float* lin_w, const float* lin_b, float* score, int C, int T4, hipStream_t s);
+void launch_critic_planar(const float* x, float* out, int C, int I, int T, hipStream_t s);
 
 // The critic's input (bsrnn_critic_spectrum; stft4096.hip, the definition and the slab rule: critic_spectrum_host.h): the 4096-point
 // analysis of slab q of a call - rows [r0, r1) x frames [t0, t1) of wave (rows `stride` floats apart, n samples each, T frames) - as

@@ -6,6 +6,10 @@ time, the mean over the rows, `Linear(32, 1)` and a sigmoid: [C, in_channels, T]
 layer goes through `bsrnn_linear_train_*` (train.LinearFunction); the two means and the sigmoid are torch on the same device.  No CPU
 fallback: the library has to be there and the tensors on the GPU.
 
+`Discriminator.commit()` freezes the module into a `CommittedCritic`: the library's `bsrnn_critic` object, which scores in ONE call with
+the first layer on the fp16x2 matrix path (fp32 in and out, range guard, exact re-run) and keeps its own copy of the weights - the
+critic as a separator's training loop uses it, under no_grad.
+
 `critic_spectrum` forms the critic's input as the reference's train-discriminator.py:62-68 does - the 4096-point analysis, real parts
 then imaginary parts, 4098 channels - with the library's `bsrnn_critic_spectrum`.
 """
@@ -67,6 +71,86 @@ def reference_channel_order(y):
     """The library's interleaved spectrum [R, 2 F, T] (re, im, re, im, ...) in the order the reference feeds its critic:
     torch.cat((x.real, x.imag), dim=1) of m_dataset.py:205 - all real parts, then all imaginary parts."""
     return torch.cat((y[:, 0::2, :], y[:, 1::2, :]), dim=1)
+
+
+def score_layout(in_channels, C, T):
+    """bsrnn_critic_score_layout as a dict: the frames behind the four layers, the K slabs of the fp16x2 first layer, the workspace of
+    a score in floats (and with the planar copy of an interleaved input on the exact kernels), the bytes of the fp16x2 image and of the
+    fp32 snapshot a CommittedCritic holds."""
+    out = (ctypes.c_int64 * 10)()
+    _native.check(_lib.bsrnn_critic_score_layout(in_channels, C, T, out))
+    v = list(out)
+    return dict(frames=v[0:4], slabs=v[4], ch_per_slab=v[5], ws_floats=v[6], ws_exact_floats=v[7], image_bytes=v[8], snapshot_bytes=v[9])
+
+
+class CommittedCritic:
+    """A frozen Discriminator as an object of the library (bsrnn_critic_*): `Discriminator.commit()` makes one.  It holds a SNAPSHOT -
+    its own fp32 copy of every parameter and the first layer as two fp16 pieces, `score_layout(...)["snapshot_bytes"]` and
+    `["image_bytes"]`, about 2 x 134 MB at 2050 channels - so the module may train on; `recommit(D)` follows it.  `score` is one library
+    call, carries no graph and follows the context's compute mode and range policy like the model entry points."""
+
+    def __init__(self, module):
+        if not isinstance(module, Discriminator):
+            raise TypeError("CommittedCritic: expected a Discriminator, got %s" % type(module).__name__)
+        dev = next(module.parameters()).device
+        if dev.type != "cuda":
+            raise ValueError("CommittedCritic: the critic's kernels run on the GPU: move the Discriminator to a cuda device first (there is no CPU fallback)")
+        self.in_channels = module.in_channels
+        self.device = dev
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(dev):
+            _native.check(_lib.bsrnn_critic_create(_context(dev), self.in_channels, ctypes.byref(self._h)))
+        self.recommit(module)
+
+    def recommit(self, module):
+        """Take a new snapshot of `module` (same in_channels, same device)."""
+        if self._h is None:
+            raise ValueError("CommittedCritic: closed")
+        if not isinstance(module, Discriminator) or module.in_channels != self.in_channels:
+            raise ValueError("CommittedCritic.recommit: expected a Discriminator(%d)" % self.in_channels)
+        convs = [m for m in module.layers if isinstance(m, nn.Conv1d)]
+        lin = module.layers2[0]
+        keep = [_f32c(t) for m in convs for t in (m.weight, m.bias)] + [_f32c(lin.weight), _f32c(lin.bias)]
+        if any(t.device != self.device for t in keep):
+            raise ValueError("CommittedCritic.recommit: the module is not on %s" % (self.device,))
+        w = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in keep[0:8:2]])
+        b = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in keep[1:8:2]])
+        with torch.cuda.device(self.device):
+            _native.check(_lib.bsrnn_critic_commit(self._h, w, b, _p(keep[8]), _p(keep[9]), _s(self.device)))     # (synchronous: `keep` may go)
+        return self
+
+    def score(self, x, interleaved=False, return_y1=False):
+        """x [C, in_channels, T] on the device, T >= 601 -> the score [1] (no graph).  interleaved=True: x is the separator's spectrum
+        (re, im, re, im, ...) and is read through the channel map, without the `reference_channel_order` copy.  return_y1: also the
+        first layer's output [C, 1024, T1] (test and measurement support)."""
+        if self._h is None:
+            raise ValueError("CommittedCritic: closed")
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise ValueError("CommittedCritic: expected x [C, %d, T], got %s" % (self.in_channels, tuple(getattr(x, "shape", ()))))
+        if x.shape[2] < MIN_FRAMES:
+            raise ValueError("CommittedCritic: x has %d frames, the four layers need at least %d (%d samples at hop 1024)" % (
+                x.shape[2], MIN_FRAMES, (MIN_FRAMES - 1) * 1024))
+        if x.device != self.device:
+            raise ValueError("CommittedCritic: x must be on %s, the committed critic's device (there is no CPU fallback)" % (self.device,))
+        x = _f32c(x)
+        C, _, T = x.shape
+        with torch.cuda.device(self.device):
+            out = torch.empty((1,), device=self.device)
+            y1 = torch.empty((C, WIDTHS[0], frames_out(T)), device=self.device) if return_y1 else None
+            _native.check(_lib.bsrnn_critic_score(self._h, _p(x), C, T, int(bool(interleaved)), _p(out), _p(y1), _s(self.device)))
+        return (out, y1) if return_y1 else out
+
+    def close(self):
+        """Free the snapshot and the image (idempotent)."""
+        if getattr(self, "_h", None) is not None:
+            _lib.bsrnn_critic_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class CriticConvFunction(torch.autograd.Function):
@@ -135,6 +219,10 @@ class Discriminator(nn.Module):
         """forward with the critic's parameters held fixed: the gradient flows through the critic into x and nowhere else (the
         adversarial term of train.train_loss)."""
         return self._score(x, fixed=True)
+
+    def commit(self):
+        """The module as it stands, frozen into a CommittedCritic (a snapshot: later changes of the parameters do not reach it)."""
+        return CommittedCritic(self)
 
     def _score(self, x, fixed):
         if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != self.in_channels:

@@ -32,12 +32,12 @@ def evaluate_many_long(model, pairs, segment_frames=256, max_rows=64):
 def train_infer(model, discriminator, sample, lossfn=None, verbose=False):
     """m_dataset.py:202-226.  sample = (waveform, waveform_speech), each [1, R, n].  lossfn must be the reference's
     L1Loss(reduction='mean') (train.py:54) or None.  Returns 0-dim tensors like the reference (its validation loop calls
-    `.item()` on them, train.py:140-144); they carry no graph: inference only.  discriminator: None, or a Discriminator(2050) whose
+    `.item()` on them, train.py:140-144); they carry no graph: inference only.  discriminator: None, a Discriminator(2050) or its CommittedCritic (Discriminator.commit()) whose
     score of the model's output (under no_grad) is added to the loss; the clip then needs 601 frames (614 400 samples).  sdr, sdr2 and
     sdr3 do not depend on it.  (The reference's loss then has shape [1]; `.item()` serves both.)"""
     if discriminator is not None:
-        from .discriminator import Discriminator
-        if not isinstance(discriminator, Discriminator):
+        from .discriminator import CommittedCritic, Discriminator
+        if not isinstance(discriminator, (Discriminator, CommittedCritic)):
             raise NotImplementedError("the discriminator must be a speechseparation_amd Discriminator (or None), got %s" % type(discriminator).__name__)
     if lossfn is not None and not (isinstance(lossfn, torch.nn.L1Loss) and lossfn.reduction == "mean"):
         raise ValueError("only the reference's L1Loss(reduction='mean') is implemented on the device")
@@ -48,6 +48,11 @@ def train_infer(model, discriminator, sample, lossfn=None, verbose=False):
     if discriminator is None:
         return out
     mix = sample[0].squeeze(0) if sample[0].dim() == 3 and sample[0].shape[0] == 1 else sample[0]
+    if isinstance(discriminator, CommittedCritic):             # one library call on the interleaved spectrum, no reorder copy
+        dev = model._device_for(mix)
+        with torch.no_grad():
+            score = discriminator.score(model.forward(model.stft(mix.to(dev))), interleaved=True)
+        return (out[0] + score.to(torch.float64).cpu().reshape(()),) + out[1:]
     with torch.no_grad():                                      # m_dataset.py:205-208
         score = discriminator(critic_input(model, mix))
     return (out[0] + score.detach().to(torch.float64).cpu().reshape(()),) + out[1:]

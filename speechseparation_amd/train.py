@@ -314,7 +314,8 @@ def train_loss(model, mix, speech, discriminator=None, adversarial=False):
     discriminator: a Discriminator(2050) whose score of the model's output is added to the loss - under no_grad, as the reference adds
     it (m_dataset.py:205-213): a constant, the gradients are those of discriminator=None bit for bit.  adversarial=True lets the gradient
     flow through the critic into the model instead, the critic's parameters held fixed (Discriminator.score_fixed).  Either way the clip
-    needs 601 frames."""
+    needs 601 frames.  A CommittedCritic (Discriminator.commit()) serves the constant term in one library call, reading the model's
+    interleaved spectrum as it lies (no reorder copy); it has no dx, so adversarial=True with it raises."""
     x = stft(mix)
     y = forward_train(model, x)
     x_time = IstftFunction.apply(y)
@@ -323,7 +324,11 @@ def train_loss(model, mix, speech, discriminator=None, adversarial=False):
     l1 = lambda a, b: (a - b).abs().mean()                      # noqa: E731
     loss = l1(x_time, s_time) + l1(y[:, 0::2, :], s[:, 0::2, :]) + l1(y[:, 1::2, :], s[:, 1::2, :])
     if discriminator is not None:
-        from .discriminator import Discriminator, reference_channel_order
+        from .discriminator import CommittedCritic, Discriminator, reference_channel_order
+        if isinstance(discriminator, CommittedCritic):
+            if adversarial:
+                raise ValueError("train_loss: adversarial=True needs the critic's dx: pass the Discriminator (score_fixed), not a CommittedCritic")
+            return loss + discriminator.score(y, interleaved=True).reshape(()), x_time
         if not isinstance(discriminator, Discriminator):
             raise NotImplementedError("the discriminator must be a speechseparation_amd Discriminator (or None), got %s" % type(discriminator).__name__)
         if adversarial:

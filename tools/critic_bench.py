@@ -6,6 +6,14 @@ every figure the two floors it sits between: the kernel's FLOP count over the 15
 bytes over HBM bandwidth (about 6.3 TB/s).
 
     python tools/critic_bench.py > profiles/critic_bench.txt
+
+`--score` times the committed critic instead (Discriminator.commit(), bsrnn_critic_score) at the same four shapes, beside the exact
+first-layer forward alone (bsrnn_critic_conv_forward) and the module's no_grad __call__: `--rounds` medians of `--reps` runs each, the
+median of the medians and their spread (lowest .. highest).  The score is timed as the library call it is - all four layers, the tail and,
+under the default range policy, the wait for the guard word - and once more under the deferred policy (asynchronous).  Its rate counts
+the first layer's FLOPs over the whole call, against the 833 TF the f16 matrix pipe offers a three-term product.
+
+    python tools/critic_bench.py --score > profiles/critic_score_bench.txt
 """
 import argparse
 import ctypes
@@ -21,6 +29,7 @@ from speechseparation_amd import _native, train as hip_train                    
 from speechseparation_amd.discriminator import WIDTHS, Discriminator, conv_layout, frames_out     # noqa: E402
 
 F32_MATRIX_TF, HBM_TBS = 155.0, 6.3
+F16X3_TF = 833.0                          # 2.5 PF of dense f16 over three terms
 
 
 def timed(fn, warmup, reps):
@@ -38,8 +47,60 @@ def timed(fn, warmup, reps):
     return statistics.median(ms)
 
 
+def rounds_of(fn, warmup, reps, rounds):
+    """Median of `rounds` medians and their lowest and highest."""
+    m = sorted(timed(fn, warmup, reps) for _ in range(rounds))
+    return statistics.median(m), m[0], m[-1]
+
+
+def score_bench(args, dev, lib, ctx, p):
+    from speechseparation_amd.discriminator import score_layout
+    print("critic_bench --score: %s; %d medians of %d runs after %d warm-up runs each: median of the medians (lowest .. highest), ms" % (
+        torch.cuda.get_device_name(0), args.rounds, args.reps, args.warmup))
+    for ch in args.channels:
+        D = Discriminator(ch).to(dev)
+        cc = D.commit()
+        w, b = D.layers[0].weight.detach(), D.layers[0].bias.detach()
+        for sec in args.seconds:
+            T = max(601, 1 + int(sec * 44100) // 1024)
+            To = frames_out(T)
+            x = torch.randn(2, ch, T, device=dev)
+            y = torch.empty(2, WIDTHS[0], To, device=dev)
+            flop = 2.0 * 2 * To * WIDTHS[0] * ch * 16
+            lay = score_layout(ch, 2, T)
+            print("\nin_channels %d, T = %d frames, C = 2: first layer %.1f GFLOP, %d K slabs of %d channels; image %.0f MB + snapshot %.0f MB" % (
+                ch, T, flop * 1e-9, lay["slabs"], lay["ch_per_slab"], lay["image_bytes"] * 1e-6, lay["snapshot_bytes"] * 1e-6))
+
+            def module():
+                with torch.no_grad():
+                    D(x)
+            rows = [("bsrnn_critic_score (policy exact)", lambda: cc.score(x), native_policy(lib, ctx, _native.RANGE_EXACT)),
+                    ("bsrnn_critic_score (policy deferred)", lambda: cc.score(x), native_policy(lib, ctx, _native.RANGE_DEFERRED)),
+                    ("bsrnn_critic_score, interleaved x", lambda: cc.score(x, interleaved=True), native_policy(lib, ctx, _native.RANGE_DEFERRED)),
+                    ("exact first-layer forward alone", lambda: _native.check(lib.bsrnn_critic_conv_forward(ctx, p(x), p(w), p(b), p(y), 2, ch, T, WIDTHS[0], 1, None)), None),
+                    ("no_grad Discriminator.__call__", module, None)]
+            for name, fn, policy in rows:
+                if policy is not None:
+                    policy()
+                med, lo, hi = rounds_of(fn, args.warmup, args.reps, args.rounds)
+                native_policy(lib, ctx, _native.RANGE_EXACT)()
+                rate = flop / med * 1e-9
+                print("  %-38s %8.3f (%.3f .. %.3f)   first layer's FLOPs over it: %6.1f TF = %4.1f %% of %.0f, %5.1f %% of %.0f" % (
+                    name, med, lo, hi, rate, 100 * rate / F16X3_TF, F16X3_TF, 100 * rate / F32_MATRIX_TF, F32_MATRIX_TF))
+            del x, y
+        cc.close()
+        del D, w, b
+        torch.cuda.empty_cache()
+
+
+def native_policy(lib, ctx, policy):
+    return lambda: _native.check(lib.bsrnn_set_range_policy(ctx, policy))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--score", action="store_true", help="time the committed critic (bsrnn_critic_score) instead of the layers")
+    ap.add_argument("--rounds", type=int, default=5, help="--score: medians per figure")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--seconds", type=float, nargs="*", default=[8.0, 60.0])
@@ -48,6 +109,8 @@ def main():
     dev = torch.device("cuda:0")
     lib, ctx = _native.lib, hip_train._context(dev)
     p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p()       # noqa: E731
+    if args.score:
+        return score_bench(args, dev, lib, ctx, p)
     print("critic_bench: %s, medians of %d after %d warm-up runs; ms (TF of the product) | floor at %.0f TF" % (
         torch.cuda.get_device_name(0), args.reps, args.warmup, F32_MATRIX_TF))
     for ch in args.channels:
