@@ -324,6 +324,43 @@ int  bsrnn_critic_score(bsrnn_critic* critic, const float* x_dev, int32_t C, int
 int  bsrnn_critic_score_layout(int32_t in_channels, int32_t C, int32_t T, int64_t out[10]);
 void bsrnn_critic_destroy(bsrnn_critic* critic);
 
+/* The committed critic's gradient: the score and d score / d x in one call - the critic as the adversarial term of a separator's loss
+ * uses it.  Opt-in per object; an object without it behaves as above.
+ *   bsrnn_critic_enable_grad  allocates, once, the first layer's weights a second time as two fp16 pieces, in the operand order of the
+ *                         product over the OUTPUT channels (out[7] bytes of bsrnn_critic_grad_layout, the size of the first image up to
+ *                         padding: one more block, bsrnn_debug_counter(0)), and builds it from the snapshot if a commit exists; every later
+ *                         bsrnn_critic_commit rebuilds it.  Idempotent.  BSRNN_ESTATE on a host-only context.
+ *   bsrnn_critic_score_grad   score_dev[0] = the bits bsrnn_critic_score gives on the same input, and dx_dev [C][in_channels][T], in x's
+ *                         own order (x_order 1: the gradient of row r of the interleaved spectrum lies in row r), = gscale * d score / d x;
+ *                         gscale_dev points at one float on the device, NULL means 1.  Every position of dx is written (zeros where no
+ *                         window reaches).  Back through the sigmoid, Linear(32, 1), the two means and layers 4, 3, 2 on the exact fp32
+ *                         kernels of bsrnn_critic_conv_backward - with no dW or db - then the first layer's dx
+ *                             G[(i, k)][t] = sum_o W[o][i][k] dp1[c][o][t],   dx[c][i][s] = sum over k = s % 3, s % 3 + 3, ... of G[(i, k)][(s - k) / 3]
+ *                         as two fp16 pieces on the f16 matrix cores with fp32 accumulation (three terms).  dp1 is far below fp16's
+ *                         range: the pass that forms it records max |dp1| on the device, the product runs on dp1 * 2^e with the largest
+ *                         operand in [2^14, 2^15) and its result is multiplied by 2^-e, both exact; a zero maximum gives dx = 0.  The
+ *                         call follows the compute mode and the range policy like bsrnn_critic_score: an |x| beyond 65504 or a
+ *                         non-finite dp1 raises the guard, and under BSRNN_RANGE_EXACT forward and backward then run again on the exact
+ *                         kernels from the snapshot before the call returns; under BSRNN_RANGE_DEFERRED the call is asynchronous and
+ *                         bsrnn_sync reports BSRNN_ERANGE.  BSRNN_GEMM=f32 and a first-layer weight beyond +-65504 go to the exact
+ *                         kernels directly.  No fp32 atomics, one workgroup per (8 input channels, 369 positions, row) over all 1024
+ *                         output channels: no partial sums, bit-reproducible.  Workspace: the context's grow-only training buffer, out[5]
+ *                         floats (out[6] when an interleaved x goes through the exact kernels: a planar copy of x and a planar dx).
+ *   bsrnn_critic_layer1_dx    the first layer's dx alone, from a given dp_dev [C][1024][(T - 16) / 3 + 1], on the same path (test and
+ *                         measurement support).
+ * BSRNN_EARG, before anything touches the device and also on a host-only context: a null object or pointer (gscale_dev may be NULL),
+ * C < 1, T < 601, x_order outside {0, 1}, x_order 1 with an odd in_channels, a tensor, image, grid or workspace beyond 2^31 - 1 elements,
+ * dx_dev overlapping x_dev, score_dev (or dp_dev), score_dev overlapping x_dev.  Then BSRNN_ESTATE on a host-only context, before the
+ * first commit and when the gradient is not enabled.  Nothing is launched on a refusal. */
+int  bsrnn_critic_enable_grad(bsrnn_critic* critic, void* stream);
+int  bsrnn_critic_score_grad(bsrnn_critic* critic, const float* x_dev, int32_t C, int32_t T, int32_t x_order, const float* gscale_dev,
+                             float* score_dev, float* dx_dev, void* stream);
+int  bsrnn_critic_layer1_dx(bsrnn_critic* critic, const float* dp_dev, int32_t C, int32_t T, int32_t x_order, float* dx_dev, void* stream);
+/* Sizes of a gradient call (no context or device needed): out[0] = tiles of input channels, out[1] = tiles of input positions per row,
+ * out[2], out[3], out[4] = channels, positions and frames of a tile (8, 369, 128); out[5] = workspace in floats, out[6] = with the exact
+ * chain's planar copies; out[7] = bytes of the dx image.  BSRNN_EARG as above, or for a null out. */
+int  bsrnn_critic_grad_layout(int32_t in_channels, int32_t C, int32_t T, int64_t out[8]);
+
 /* torch.optim.AdamW(model.parameters(), lr, weight_decay) of train.py:50, one tensor per call: p, m (exp_avg), v (exp_avg_sq)
  * updated in place from the gradient g; `step` counts from 1 (bias correction).  n floats each, device pointers.  The betas are
  * double, as torch's: 1 - beta2 and the bias corrections are formed from them in double (from 0.999f, 1 - beta2 is 1.3e-5 off). */

@@ -6,6 +6,9 @@
 // And the committed critic (bsrnn_critic_create / _commit / _score): the whole module frozen into an object, its first layer on the fp16x2
 // matrix path under the context's range policy, the exact layers above as its re-run.  The image, the plan and every size:
 // critic_score_host.h; the kernels: critic_score.hip.
+// And its gradient (bsrnn_critic_enable_grad / _score_grad / _layer1_dx): the score and d score / d x in one call, the first layer's dx on
+// the fp16x2 matrix path from a second image, layers 4 .. 2 on the exact dx kernel with no dW beside it.  The image, the tiles and the
+// workspace: critic_grad_host.h; the kernels: critic_grad.hip.
 #include "api_internal.h"
 
 #include <cmath>
@@ -63,7 +66,39 @@ struct bsrnn_critic {
     float* d_par = nullptr;
     void* d_img = nullptr;
     unsigned* d_max = nullptr;
+    void* d_img_dx = nullptr;                    // the first layer's image in the dx product's order: bsrnn_critic_enable_grad allocates it
 };
+
+static int grad_sizes_ok(int32_t I, int32_t C, int32_t T, int32_t x_order, const char* who)
+{
+    switch (cgd_check(I, C, T, x_order)) {
+    case CGD_OK: return 0;
+    case CGD_BAD_CHANNELS: return fail(BSRNN_EARG, "%s: need in_channels >= 1, got %d", who, I);
+    case CGD_BAD_ROWS: return fail(BSRNN_EARG, "%s: need C >= 1 rows, got C = %d", who, C);
+    case CGD_TOO_SHORT: return fail(BSRNN_EARG, "%s: T = %d frames, the four layers need at least %d", who, T, CRITIC_MIN_T);
+    case CGD_BAD_ORDER: return fail(BSRNN_EARG, "%s: x_order = %d is neither 0 (planar) nor 1 (interleaved)", who, x_order);
+    case CGD_ODD_INTERLEAVED: return fail(BSRNN_EARG, "%s: an interleaved input has an even number of channels, in_channels = %d is odd", who, I);
+    default:
+        return fail(BSRNN_EARG, "%s: in_channels = %d, C = %d, T = %d: x, a layer's gradient, the image or the workspace would pass 2^31 - 1 elements",
+                    who, I, C, T);
+    }
+}
+
+// The first layer's dx from dp1 [C][1024][T1] at ws + g.off_dp[0], whose maximum stands in the max word: fp16x2 from the image, or the
+// exact kernel (through the planar dx and the scatter when dx is interleaved)
+static void first_layer_dx(const bsrnn_critic* k, const CriticParams& q, const CgdPlan& g, const float* dp1, float* ws, float* dx, int x_order,
+                           bool exact, hipStream_t s)
+{
+    const int C = g.f.C, T = g.f.T;
+    if (!exact) {
+        launch_critic_dx_h2(dp1, k->d_img_dx, dx, (const unsigned*)(ws + g.off_max), k->ctx->d_range, g, x_order, s);
+    } else if (x_order == CSC_ORDER_INTERLEAVED) {
+        launch_critic_dx(k->d_par + q.off[0], dp1, ws + g.off_dxp, C, k->I, T, CSC_O, s);
+        launch_critic_scatter(ws + g.off_dxp, dx, C, k->I, T, s);
+    } else {
+        launch_critic_dx(k->d_par + q.off[0], dp1, dx, C, k->I, T, CSC_O, s);
+    }
+}
 
 static int spectrum_args_ok(int64_t R, int64_t n, int64_t stride, float scale, const char* who)
 {
@@ -234,7 +269,7 @@ void bsrnn_critic_destroy(bsrnn_critic* k)
     if (c->device >= 0) {
         (void)hipSetDevice(c->device);
         (void)hipDeviceSynchronize();
-        (void)hipFree(k->d_par); (void)hipFree(k->d_img); (void)hipFree(k->d_max);
+        (void)hipFree(k->d_par); (void)hipFree(k->d_img); (void)hipFree(k->d_max); (void)hipFree(k->d_img_dx);
     }
     delete k;
     if (--c->live_streams == 0 && c->zombie) destroy_now(c);     // as bsrnn_stream_destroy: the context goes with the last object that points at it
@@ -260,6 +295,7 @@ int bsrnn_critic_commit(bsrnn_critic* k, const float* const conv_w[4], const flo
         HIP_TRY(hipMemcpyAsync(k->d_par + q.off[j], src[j], (size_t)q.n[j] * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(k->d_max, 0, sizeof(unsigned), s));
     launch_critic_commit(k->d_par + q.off[0], k->d_img, k->d_max, k->I, s);      // (from the snapshot: the caller's may change from here on)
+    if (k->d_img_dx) launch_critic_grad_commit(k->d_par + q.off[0], k->d_img_dx, k->I, s);
     HIP_TRY(hipGetLastError());
     unsigned bits = 0;
     HIP_TRY(hipMemcpyAsync(&bits, k->d_max, sizeof(unsigned), hipMemcpyDeviceToHost, s));
@@ -311,6 +347,141 @@ int bsrnn_critic_score(bsrnn_critic* k, const float* x, int32_t C, int32_t T, in
                                   CRITIC_WIDTHS[l], l + 1 < CRITIC_LAYERS, s);
         launch_critic_tail(yl[CRITIC_LAYERS - 1], par + q.off[2 * CRITIC_LAYERS], par + q.off[2 * CRITIC_LAYERS + 1], score, C,
                            p.len[CRITIC_LAYERS - 1], s);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    const bool exact_now = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+    if (int rc = run()) return rc;
+    if (exact_now) return 0;               // (the exact chain ran: no guard to wait for)
+    return finish_call(c, s, run);
+}
+
+// ------------------------------------------------------------------------------------------------ the committed critic's gradient
+int bsrnn_critic_grad_layout(int32_t in_channels, int32_t C, int32_t T, int64_t out[8])
+{
+    if (!out) return fail(BSRNN_EARG, "bsrnn_critic_grad_layout: nowhere to write the layout");
+    if (int rc = grad_sizes_ok(in_channels, C, T, CSC_ORDER_PLANAR, "bsrnn_critic_grad_layout")) return rc;
+    const CgdPlan g = cgd_plan(in_channels, C, T);
+    out[0] = g.i_tiles; out[1] = g.s_tiles; out[2] = CGD_CH; out[3] = CGD_TILE_S; out[4] = CGD_TILE_T;
+    out[5] = g.ws_floats; out[6] = g.ws_exact_floats; out[7] = cgd_image_halves(in_channels) * 2;
+    return 0;
+}
+
+int bsrnn_critic_enable_grad(bsrnn_critic* k, void* stream)
+{
+    if (!k) return fail(BSRNN_EARG, "null critic");
+    if (cgd_check_channels(k->I) != CGD_OK)
+        return fail(BSRNN_EARG, "bsrnn_critic_enable_grad: in_channels = %d: the dx image would pass 2^31 - 1 elements", k->I);
+    bsrnn_ctx* c = k->ctx;
+    if (int rc = check_device(c)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    if (k->d_img_dx) return 0;
+    void* img = nullptr;
+    const hipError_t e = hipMalloc(&img, (size_t)cgd_image_halves(k->I) * 2);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(BSRNN_EHIP, "bsrnn_critic_enable_grad: %s (the dx image takes %lld MB)", hipGetErrorString(e),
+                    (long long)((cgd_image_halves(k->I) * 2) >> 20));
+    }
+    ++g_dbg[DBG_ALLOC];
+    if (k->committed) {
+        launch_critic_grad_commit(k->d_par + CriticParams(k->I).off[0], img, k->I, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    k->d_img_dx = img;
+    return 0;
+}
+
+int bsrnn_critic_layer1_dx(bsrnn_critic* k, const float* dp, int32_t C, int32_t T, int32_t x_order, float* dx, void* stream)
+{
+    if (!k) return fail(BSRNN_EARG, "null critic");
+    if (!dp || !dx) return fail(BSRNN_EARG, "bsrnn_critic_layer1_dx: null argument (need dp_dev and dx_dev)");
+    if (int rc = grad_sizes_ok(k->I, C, T, x_order, "bsrnn_critic_layer1_dx")) return rc;
+    const CgdPlan g = cgd_plan(k->I, C, T);
+    const size_t nx = (size_t)C * k->I * T * sizeof(float), ndp = (size_t)C * CSC_O * g.f.len[0] * sizeof(float);
+    if (ranges_overlap(dx, nx, dp, ndp)) return fail(BSRNN_EARG, "bsrnn_critic_layer1_dx: dx_dev overlaps dp_dev (a call that left the fp16 range is run again from dp)");
+    bsrnn_ctx* c = k->ctx;
+    if (int rc = check_device(c)) return rc;
+    if (!k->committed) return fail(BSRNN_ESTATE, "bsrnn_critic_layer1_dx: bsrnn_critic_commit() has not been called");
+    if (!k->d_img_dx) return fail(BSRNN_ESTATE, "bsrnn_critic_layer1_dx: bsrnn_critic_enable_grad() has not been called");
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const CriticParams q(k->I);
+    auto run = [&]() -> int {
+        const bool exact = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+        const size_t n_ws = (size_t)(exact && x_order == CSC_ORDER_INTERLEAVED ? g.ws_exact_floats : g.ws_floats);
+        float* ws = train_scratch(c, n_ws);
+        if (!ws) return fail(BSRNN_EHIP, "bsrnn_critic_layer1_dx: out of device memory (%zu MB of workspace)", n_ws * sizeof(float) >> 20);
+        if (!exact) {
+            HIP_TRY(hipMemsetAsync(ws + g.off_max, 0, 4 * sizeof(float), s));
+            launch_critic_dp_max(dp, nullptr, nullptr, (unsigned*)(ws + g.off_max), ndp / sizeof(float), s);
+        }
+        first_layer_dx(k, q, g, dp, ws, dx, x_order, exact, s);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    const bool exact_now = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+    if (int rc = run()) return rc;
+    if (exact_now) return 0;
+    return finish_call(c, s, run);
+}
+
+int bsrnn_critic_score_grad(bsrnn_critic* k, const float* x, int32_t C, int32_t T, int32_t x_order, const float* gscale, float* score, float* dx,
+                            void* stream)
+{
+    if (!k) return fail(BSRNN_EARG, "null critic");
+    if (!x || !score || !dx) return fail(BSRNN_EARG, "bsrnn_critic_score_grad: null argument (need x_dev, score_dev and dx_dev; only gscale_dev may be null)");
+    if (int rc = grad_sizes_ok(k->I, C, T, x_order, "bsrnn_critic_score_grad")) return rc;
+    const CgdPlan g = cgd_plan(k->I, C, T);
+    const CscPlan& p = g.f;
+    const size_t nx = (size_t)C * k->I * T * sizeof(float);
+    if (ranges_overlap(dx, nx, x, nx)) return fail(BSRNN_EARG, "bsrnn_critic_score_grad: dx_dev overlaps x_dev (a call that left the fp16 range is run again from x)");
+    if (ranges_overlap(score, sizeof(float), x, nx)) return fail(BSRNN_EARG, "bsrnn_critic_score_grad: score_dev overlaps x_dev");
+    if (ranges_overlap(dx, nx, score, sizeof(float))) return fail(BSRNN_EARG, "bsrnn_critic_score_grad: dx_dev overlaps score_dev");
+    if (ranges_overlap(gscale, sizeof(float), dx, nx) || ranges_overlap(gscale, sizeof(float), score, sizeof(float)))
+        return fail(BSRNN_EARG, "bsrnn_critic_score_grad: gscale_dev overlaps an output (the re-run reads it again)");
+    bsrnn_ctx* c = k->ctx;
+    if (int rc = check_device(c)) return rc;
+    if (!k->committed) return fail(BSRNN_ESTATE, "bsrnn_critic_score_grad: bsrnn_critic_commit() has not been called");
+    if (!k->d_img_dx) return fail(BSRNN_ESTATE, "bsrnn_critic_score_grad: bsrnn_critic_enable_grad() has not been called");
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    const CriticParams q(k->I);
+    const float* const par = k->d_par;
+    auto run = [&]() -> int {
+        const bool exact = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+        const bool copy = exact && x_order == CSC_ORDER_INTERLEAVED;
+        const size_t n_ws = (size_t)(copy ? g.ws_exact_floats : g.ws_floats);
+        float* ws = train_scratch(c, n_ws);
+        if (!ws) return fail(BSRNN_EHIP, "bsrnn_critic_score_grad: out of device memory (%zu MB of workspace)", n_ws * sizeof(float) >> 20);
+        float *yl[CRITIC_LAYERS], *dpl[CRITIC_LAYERS];
+        for (int l = 0; l < CRITIC_LAYERS; ++l) { yl[l] = ws + p.off_y[l]; dpl[l] = ws + g.off_dp[l]; }
+        float* shared = ws + p.off_shared;
+        // the score, exactly as bsrnn_critic_score forms it
+        if (exact) {
+            const float* xp = x;
+            if (copy) { launch_critic_planar(x, ws + g.off_xp, C, k->I, T, s); xp = ws + g.off_xp; }
+            launch_critic_forward(xp, par + q.off[0], par + q.off[1], yl[0], shared, C, k->I, T, CSC_O, 1, s);
+        } else {
+            launch_critic_first_h2(x, k->d_img, par + q.off[1], yl[0], shared, c->d_range, p, x_order, s);
+        }
+        for (int l = 1; l < CRITIC_LAYERS; ++l)
+            launch_critic_forward(yl[l - 1], par + q.off[2 * l], par + q.off[2 * l + 1], yl[l], shared, C, CRITIC_WIDTHS[l - 1], p.len[l - 1],
+                                  CRITIC_WIDTHS[l], l + 1 < CRITIC_LAYERS, s);
+        launch_critic_tail(yl[CRITIC_LAYERS - 1], par + q.off[2 * CRITIC_LAYERS], par + q.off[2 * CRITIC_LAYERS + 1], score, C,
+                           p.len[CRITIC_LAYERS - 1], s);
+        // and back: the tail, then per layer dy (in the shared block) = dx of the layer above, dp = dy * act'(y); no dW anywhere
+        launch_critic_tail_grad(score, par + q.off[2 * CRITIC_LAYERS], gscale, ws + g.off_pool, dpl[CRITIC_LAYERS - 1], C, p.len[CRITIC_LAYERS - 1], s);
+        HIP_TRY(hipMemsetAsync(ws + g.off_max, 0, 4 * sizeof(float), s));
+        for (int l = CRITIC_LAYERS - 1; l >= 1; --l) {
+            const size_t n = (size_t)C * CRITIC_WIDTHS[l - 1] * p.len[l - 1];
+            launch_critic_dx(par + q.off[2 * l], dpl[l], shared, C, CRITIC_WIDTHS[l - 1], p.len[l - 1], CRITIC_WIDTHS[l], s);
+            if (l > 1) launch_critic_dp(shared, yl[l - 1], dpl[l - 1], n, s);
+            else launch_critic_dp_max(shared, yl[0], dpl[0], (unsigned*)(ws + g.off_max), n, s);
+        }
+        first_layer_dx(k, q, g, dpl[0], ws, dx, x_order, exact, s);
         HIP_TRY(hipGetLastError());
         return 0;
     };

@@ -238,4 +238,15 @@ void launch_critic_backward(const float* x, const float* w, const float* y, cons
         hipLaunchKernelGGL(critic_dx_kernel, dim3((unsigned)((size_t)g.s_tiles * g.i_tiles * C)), dim3(256), 0, s, w, dp, dx, C, I, T, O, g);
 }
 
+void launch_critic_dp(const float* dy, const float* y, float* dp, size_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(critic_dp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dy, y, dp, n);
+}
+
+void launch_critic_dx(const float* w, const float* dp, float* dx, int C, int I, int T, int O, hipStream_t s)
+{
+    const CriticLayout g = critic_layout(C, I, T, O);
+    hipLaunchKernelGGL(critic_dx_kernel, dim3((unsigned)((size_t)g.s_tiles * g.i_tiles * C)), dim3(256), 0, s, w, dp, dx, C, I, T, O, g);
+}
+
 }  // namespace bsrnn

@@ -14,6 +14,7 @@
 #include "remix_host.h"         // RemixRow, RemixTerm: what the re-mix kernel knows of a row and of a term (HIP-free)
 #include "critic_host.h"        // CriticLayout: tiles, K slabs and reduction chunks of the critic's convolution (HIP-free)
 #include "critic_score_host.h"  // CscPlan: the committed critic's weight image, K slabs and workspace (HIP-free)
+#include "critic_grad_host.h"   // CgdPlan: the committed critic's dx image, tiles and workspace (HIP-free)
 #include "critic_spectrum_host.h"   // CsSlab: the rows x frames one launch pair of the critic's 4096-point analysis owns (HIP-free)
 
 namespace bsrnn {
@@ -446,6 +447,21 @@ void launch_critic_first_h2(const float* x, const void* image, const float* bias
                             int x_order, hipStream_t s);
 void launch_critic_tail(const float* y4, const float* lin_w, const float* lin_b, float* score, int C, int T4, hipStream_t s);
 void launch_critic_planar(const float* x, float* out, int C, int I, int T, hipStream_t s);
+
+// The committed critic's gradient (bsrnn_critic_enable_grad / _score_grad / _layer1_dx; critic_grad.hip, the second image, the tiling and
+// the workspace: critic_grad_host.h).  dp / dx: the two backward kernels of critic.hip alone - dp = dy * act'(y) over n values, and
+// dx [C][I][T] from dp [C][O][T_out] - with no dW beside them.  grad_commit: w [1024][I][16] -> the dx image (cgd_image_halves(I) fp16
+// values).  tail_grad: score[0], lin_w, gscale (null: 1) -> gp [32] and dp4 [C][32][T4].  dp_max: as dp (y null: a plain read; dp null:
+// nothing written; dy == dp allowed) and *mx = max of the bit patterns of |dp| (the caller zeroes it).  dx_h2: layer 1's dx in fp16x2
+// from the image and *mx, written in x_order; raises *range_flag for a non-finite maximum.  scatter: a planar dx into interleaved order.
+void launch_critic_dp(const float* dy, const float* y, float* dp, size_t n, hipStream_t s);
+void launch_critic_dx(const float* w, const float* dp, float* dx, int C, int I, int T, int O, hipStream_t s);
+void launch_critic_grad_commit(const float* w, void* image, int I, hipStream_t s);
+void launch_critic_tail_grad(const float* score, const float* lin_w, const float* gscale, float* gp, float* dp4, int C, int T4, hipStream_t s);
+void launch_critic_dp_max(const float* dy, const float* y, float* dp, unsigned* mx, size_t n, hipStream_t s);
+void launch_critic_dx_h2(const float* dp, const void* image, float* dx, const unsigned* mx, int* range_flag, const CgdPlan& g, int x_order,
+                         hipStream_t s);
+void launch_critic_scatter(const float* in, float* out, int C, int I, int T, hipStream_t s);
 
 // The critic's input (bsrnn_critic_spectrum; stft4096.hip, the definition and the slab rule: critic_spectrum_host.h): the 4096-point
 // analysis of slab q of a call - rows [r0, r1) x frames [t0, t1) of wave (rows `stride` floats apart, n samples each, T frames) - as

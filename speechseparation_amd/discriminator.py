@@ -8,7 +8,9 @@ fallback: the library has to be there and the tensors on the GPU.
 
 `Discriminator.commit()` freezes the module into a `CommittedCritic`: the library's `bsrnn_critic` object, which scores in ONE call with
 the first layer on the fp16x2 matrix path (fp32 in and out, range guard, exact re-run) and keeps its own copy of the weights - the
-critic as a separator's training loop uses it, under no_grad.
+critic as a separator's training loop uses it, under no_grad.  `commit(grad=True)` gives that object its gradient as well:
+`score_grad` returns the score and d score / d x from one call (`bsrnn_critic_score_grad`, the first layer's dx on the fp16x2 matrix
+path, no dW anywhere), and `score_fixed` wraps it for autograd - the adversarial term of `train.train_loss`.
 
 `critic_spectrum` forms the critic's input as the reference's train-discriminator.py:62-68 does - the 4096-point analysis, real parts
 then imaginary parts, 4098 channels - with the library's `bsrnn_critic_spectrum`.
@@ -83,13 +85,56 @@ def score_layout(in_channels, C, T):
     return dict(frames=v[0:4], slabs=v[4], ch_per_slab=v[5], ws_floats=v[6], ws_exact_floats=v[7], image_bytes=v[8], snapshot_bytes=v[9])
 
 
+def grad_layout(in_channels, C, T):
+    """bsrnn_critic_grad_layout as a dict: the tiles of the fp16x2 dx (input channels, input positions per row) and a tile's extent,
+    the workspace of a score with its gradient in floats (and with the exact chain's planar copies), the bytes of the dx image."""
+    out = (ctypes.c_int64 * 8)()
+    _native.check(_lib.bsrnn_critic_grad_layout(in_channels, C, T, out))
+    v = list(out)
+    return dict(i_tiles=v[0], s_tiles=v[1], tile_channels=v[2], tile_positions=v[3], tile_frames=v[4], ws_floats=v[5], ws_exact_floats=v[6],
+                image_bytes=v[7])
+
+
+class _CommittedScoreFunction(torch.autograd.Function):
+    """score = cc(x) with the gradient kept from the same library call: backward returns dx * grad_output."""
+
+    @staticmethod
+    def forward(ctx, x, cc, interleaved):
+        score, dx = cc.score_grad(x, interleaved=interleaved)
+        ctx.save_for_backward(dx)
+        return score
+
+    @staticmethod
+    def backward(ctx, g):
+        (dx,) = ctx.saved_tensors
+        return dx * g.reshape(()), None, None
+
+
+def layer1_dx(cc, dp, T, interleaved=False):
+    """The first layer's dx alone (bsrnn_critic_layer1_dx; test and measurement support): dp [C, 1024, frames_out(T)] -> dx
+    [C, in_channels, T] on the path `score_grad` takes, rows in the interleaved order when asked."""
+    cc._open(grad=True)
+    if not isinstance(dp, torch.Tensor) or dp.dim() != 3 or tuple(dp.shape[1:]) != (WIDTHS[0], frames_out(T)):
+        raise ValueError("layer1_dx: expected dp [C, %d, %d], got %s" % (WIDTHS[0], frames_out(T), tuple(getattr(dp, "shape", ()))))
+    if dp.device != cc.device:
+        raise ValueError("layer1_dx: dp must be on %s" % (cc.device,))
+    dp = _f32c(dp)
+    C = dp.shape[0]
+    with torch.cuda.device(cc.device):
+        dx = torch.empty((C, cc.in_channels, T), device=cc.device)
+        _native.check(_lib.bsrnn_critic_layer1_dx(cc._h, _p(dp), C, T, int(bool(interleaved)), _p(dx), _s(cc.device)))
+    return dx
+
+
 class CommittedCritic:
     """A frozen Discriminator as an object of the library (bsrnn_critic_*): `Discriminator.commit()` makes one.  It holds a SNAPSHOT -
     its own fp32 copy of every parameter and the first layer as two fp16 pieces, `score_layout(...)["snapshot_bytes"]` and
     `["image_bytes"]`, about 2 x 134 MB at 2050 channels - so the module may train on; `recommit(D)` follows it.  `score` is one library
-    call, carries no graph and follows the context's compute mode and range policy like the model entry points."""
+    call, carries no graph and follows the context's compute mode and range policy like the model entry points.  grad=True
+    (`Discriminator.commit(grad=True)`) adds the gradient: a second image of the first layer (`grad_layout(...)["image_bytes"]`),
+    `score_grad` and `score_fixed`."""
 
-    def __init__(self, module):
+    def __init__(self, module, grad=False):
         if not isinstance(module, Discriminator):
             raise TypeError("CommittedCritic: expected a Discriminator, got %s" % type(module).__name__)
         dev = next(module.parameters()).device
@@ -100,6 +145,9 @@ class CommittedCritic:
         self._h = ctypes.c_void_p()
         with torch.cuda.device(dev):
             _native.check(_lib.bsrnn_critic_create(_context(dev), self.in_channels, ctypes.byref(self._h)))
+            self.has_grad = bool(grad)
+            if grad:
+                _native.check(_lib.bsrnn_critic_enable_grad(self._h, _s(dev)))
         self.recommit(module)
 
     def recommit(self, module):
@@ -119,12 +167,13 @@ class CommittedCritic:
             _native.check(_lib.bsrnn_critic_commit(self._h, w, b, _p(keep[8]), _p(keep[9]), _s(self.device)))     # (synchronous: `keep` may go)
         return self
 
-    def score(self, x, interleaved=False, return_y1=False):
-        """x [C, in_channels, T] on the device, T >= 601 -> the score [1] (no graph).  interleaved=True: x is the separator's spectrum
-        (re, im, re, im, ...) and is read through the channel map, without the `reference_channel_order` copy.  return_y1: also the
-        first layer's output [C, 1024, T1] (test and measurement support)."""
+    def _open(self, grad=False):
         if self._h is None:
             raise ValueError("CommittedCritic: closed")
+        if grad and not self.has_grad:
+            raise ValueError("CommittedCritic: this object has no gradient: commit(grad=True) makes one that has")
+
+    def _checked(self, x):
         if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != self.in_channels:
             raise ValueError("CommittedCritic: expected x [C, %d, T], got %s" % (self.in_channels, tuple(getattr(x, "shape", ()))))
         if x.shape[2] < MIN_FRAMES:
@@ -132,13 +181,44 @@ class CommittedCritic:
                 x.shape[2], MIN_FRAMES, (MIN_FRAMES - 1) * 1024))
         if x.device != self.device:
             raise ValueError("CommittedCritic: x must be on %s, the committed critic's device (there is no CPU fallback)" % (self.device,))
-        x = _f32c(x)
+        return _f32c(x)
+
+    def score(self, x, interleaved=False, return_y1=False):
+        """x [C, in_channels, T] on the device, T >= 601 -> the score [1] (no graph).  interleaved=True: x is the separator's spectrum
+        (re, im, re, im, ...) and is read through the channel map, without the `reference_channel_order` copy.  return_y1: also the
+        first layer's output [C, 1024, T1] (test and measurement support)."""
+        self._open()
+        x = self._checked(x)
         C, _, T = x.shape
         with torch.cuda.device(self.device):
             out = torch.empty((1,), device=self.device)
             y1 = torch.empty((C, WIDTHS[0], frames_out(T)), device=self.device) if return_y1 else None
             _native.check(_lib.bsrnn_critic_score(self._h, _p(x), C, T, int(bool(interleaved)), _p(out), _p(y1), _s(self.device)))
         return (out, y1) if return_y1 else out
+
+    def score_grad(self, x, interleaved=False, gscale=None):
+        """x as for `score` -> (score [1], dx [C, in_channels, T]) from ONE library call: the bits `score` gives, and
+        gscale * d score / d x in x's own channel order (interleaved=True: the gradient of the separator's spectrum as it lies).
+        gscale: None (1) or a one-element float tensor on the device.  Neither carries a graph.  Needs commit(grad=True)."""
+        self._open(grad=True)
+        x = self._checked(x)
+        C, _, T = x.shape
+        if gscale is not None:
+            if not isinstance(gscale, torch.Tensor) or gscale.numel() != 1 or gscale.device != self.device:
+                raise ValueError("CommittedCritic.score_grad: gscale must be a one-element tensor on %s" % (self.device,))
+            gscale = _f32c(gscale.detach())
+        with torch.cuda.device(self.device):
+            out = torch.empty((1,), device=self.device)
+            dx = torch.empty_like(x)
+            _native.check(_lib.bsrnn_critic_score_grad(self._h, _p(x.detach()), C, T, int(bool(interleaved)), _p(gscale), _p(out), _p(dx),
+                                                       _s(self.device)))
+        return out, dx
+
+    def score_fixed(self, x, interleaved=False):
+        """The score [1] with a graph into x and nowhere else (the critic is frozen): forward makes the one `score_grad` call and keeps
+        dx - it is formed while the activations stand in the shared workspace - and backward returns dx * grad_output."""
+        self._open(grad=True)
+        return _CommittedScoreFunction.apply(x, self, bool(interleaved))
 
     def close(self):
         """Free the snapshot and the image (idempotent)."""
@@ -220,9 +300,10 @@ class Discriminator(nn.Module):
         adversarial term of train.train_loss)."""
         return self._score(x, fixed=True)
 
-    def commit(self):
-        """The module as it stands, frozen into a CommittedCritic (a snapshot: later changes of the parameters do not reach it)."""
-        return CommittedCritic(self)
+    def commit(self, grad=False):
+        """The module as it stands, frozen into a CommittedCritic (a snapshot: later changes of the parameters do not reach it).
+        grad=True: the object also serves d score / d x (`score_grad`, `score_fixed`), at the price of a second first-layer image."""
+        return CommittedCritic(self, grad=grad)
 
     def _score(self, x, fixed):
         if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != self.in_channels:

@@ -315,7 +315,8 @@ def train_loss(model, mix, speech, discriminator=None, adversarial=False):
     it (m_dataset.py:205-213): a constant, the gradients are those of discriminator=None bit for bit.  adversarial=True lets the gradient
     flow through the critic into the model instead, the critic's parameters held fixed (Discriminator.score_fixed).  Either way the clip
     needs 601 frames.  A CommittedCritic (Discriminator.commit()) serves the constant term in one library call, reading the model's
-    interleaved spectrum as it lies (no reorder copy); it has no dx, so adversarial=True with it raises."""
+    interleaved spectrum as it lies (no reorder copy); adversarial=True with it needs commit(grad=True) - then the score and its dx come
+    from one library call (CommittedCritic.score_fixed), the gradient landing in the spectrum's own layout - and raises otherwise."""
     x = stft(mix)
     y = forward_train(model, x)
     x_time = IstftFunction.apply(y)
@@ -327,7 +328,10 @@ def train_loss(model, mix, speech, discriminator=None, adversarial=False):
         from .discriminator import CommittedCritic, Discriminator, reference_channel_order
         if isinstance(discriminator, CommittedCritic):
             if adversarial:
-                raise ValueError("train_loss: adversarial=True needs the critic's dx: pass the Discriminator (score_fixed), not a CommittedCritic")
+                if not discriminator.has_grad:
+                    raise ValueError("train_loss: adversarial=True needs the critic's dx: pass the Discriminator (score_fixed) or a "
+                                     "CommittedCritic made by commit(grad=True), not a plain CommittedCritic")
+                return loss + discriminator.score_fixed(y, interleaved=True).reshape(()), x_time
             return loss + discriminator.score(y, interleaved=True).reshape(()), x_time
         if not isinstance(discriminator, Discriminator):
             raise NotImplementedError("the discriminator must be a speechseparation_amd Discriminator (or None), got %s" % type(discriminator).__name__)

@@ -14,6 +14,14 @@ under the default range policy, the wait for the guard word - and once more unde
 the first layer's FLOPs over the whole call, against the 833 TF the f16 matrix pipe offers a three-term product.
 
     python tools/critic_bench.py --score > profiles/critic_score_bench.txt
+
+`--grad` times the committed critic's score with its gradient (Discriminator.commit(grad=True), bsrnn_critic_score_grad: one call) at the
+same four shapes, beside the adversarial path it replaces, run in the same session: reference_channel_order of the interleaved spectrum,
+Discriminator.score_fixed, backward to x (the exact kernels through autograd, the first layer's dW formed and dropped).  Also the first
+layer's dx alone on both paths (bsrnn_critic_layer1_dx; bsrnn_critic_conv_backward with and without dx, the difference).  Same method as
+`--score`.  The last line of every shape says whether score_grad is faster than the path it replaces by more than both spreads together.
+
+    python tools/critic_bench.py --grad > profiles/critic_grad_bench.txt
 """
 import argparse
 import ctypes
@@ -93,6 +101,61 @@ def score_bench(args, dev, lib, ctx, p):
         torch.cuda.empty_cache()
 
 
+def grad_bench(args, dev, lib, ctx, p):
+    from speechseparation_amd.discriminator import grad_layout, layer1_dx, reference_channel_order
+    print("critic_bench --grad: %s; %d medians of %d runs after %d warm-up runs each: median of the medians (lowest .. highest), ms" % (
+        torch.cuda.get_device_name(0), args.rounds, args.reps, args.warmup))
+    for ch in args.channels:
+        D = Discriminator(ch).to(dev)
+        cc = D.commit(grad=True)
+        w = D.layers[0].weight.detach()
+        for sec in args.seconds:
+            T = max(601, 1 + int(sec * 44100) // 1024)
+            To = frames_out(T)
+            y = torch.randn(2, ch, T, device=dev)                       # the separator's interleaved spectrum
+            dp = torch.randn(2, WIDTHS[0], To, device=dev) * 1e-6
+            dx, dw, db = torch.empty_like(y), torch.empty_like(w), torch.empty(WIDTHS[0], device=dev)
+            flop = 2.0 * 2 * To * WIDTHS[0] * ch * 16
+            lay = grad_layout(ch, 2, T)
+            print("\nin_channels %d, T = %d frames, C = 2: %.1f GFLOP per first-layer product; %d x %d x 2 workgroups; dx image %.0f MB" % (
+                ch, T, flop * 1e-9, lay["i_tiles"], lay["s_tiles"], lay["image_bytes"] * 1e-6))
+
+            def parent():
+                ya = y.detach().requires_grad_(True)
+                D.score_fixed(reference_channel_order(ya)).sum().backward()
+                return ya.grad
+
+            def exact_bwd(want_dx):
+                return lambda: _native.check(lib.bsrnn_critic_conv_backward(ctx, p(y), p(w), None, p(dp), p(dx) if want_dx else None, p(dw), p(db),
+                                                                            2, ch, T, WIDTHS[0], 0, None))
+            rows = [("score_grad, interleaved (policy exact)", lambda: cc.score_grad(y, interleaved=True), _native.RANGE_EXACT),
+                    ("score_grad, interleaved (deferred)", lambda: cc.score_grad(y, interleaved=True), _native.RANGE_DEFERRED),
+                    ("score_grad, planar (deferred)", lambda: cc.score_grad(y), _native.RANGE_DEFERRED),
+                    ("score alone (deferred)", lambda: cc.score(y, interleaved=True), _native.RANGE_DEFERRED),
+                    ("reorder + score_fixed + backward to x", parent, _native.RANGE_EXACT),
+                    ("layer1_dx, fp16x2 (deferred)", lambda: layer1_dx(cc, dp, T, interleaved=True), _native.RANGE_DEFERRED),
+                    ("exact first layer dW + db", exact_bwd(False), _native.RANGE_EXACT),
+                    ("exact first layer dW + db + dx", exact_bwd(True), _native.RANGE_EXACT)]
+            got = {}
+            for name, fn, policy in rows:
+                native_policy(lib, ctx, policy)()
+                got[name] = rounds_of(fn, args.warmup, args.reps, args.rounds)
+                native_policy(lib, ctx, _native.RANGE_EXACT)()
+                print("  %-40s %8.3f (%.3f .. %.3f)" % ((name,) + got[name]))
+            med = got["layer1_dx, fp16x2 (deferred)"][0]
+            print("  first-layer dx: fp16x2 %.3f ms = %.1f TF (%.1f %% of %.0f); exact %.3f ms (dW + db + dx minus dW + db)" % (
+                med, flop / med * 1e-9, 100 * flop / med * 1e-9 / F16X3_TF, F16X3_TF,
+                got["exact first layer dW + db + dx"][0] - got["exact first layer dW + db"][0]))
+            new, old = got["score_grad, interleaved (policy exact)"], got["reorder + score_fixed + backward to x"]
+            spreads = (new[2] - new[1]) + (old[2] - old[1])
+            print("  score_grad %.3f ms against %.3f ms: %.2fx; the difference %.3f ms %s both spreads together (%.3f ms)" % (
+                new[0], old[0], old[0] / new[0], old[0] - new[0], "exceeds" if old[0] - new[0] > spreads else "DOES NOT exceed", spreads))
+            del y, dp, dx, dw, db
+        cc.close()
+        del D, w
+        torch.cuda.empty_cache()
+
+
 def native_policy(lib, ctx, policy):
     return lambda: _native.check(lib.bsrnn_set_range_policy(ctx, policy))
 
@@ -100,7 +163,9 @@ def native_policy(lib, ctx, policy):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--score", action="store_true", help="time the committed critic (bsrnn_critic_score) instead of the layers")
-    ap.add_argument("--rounds", type=int, default=5, help="--score: medians per figure")
+    ap.add_argument("--grad", action="store_true", help="time the committed critic's score with its gradient (bsrnn_critic_score_grad) beside "
+                    "the adversarial path through Discriminator.score_fixed")
+    ap.add_argument("--rounds", type=int, default=5, help="--score, --grad: medians per figure")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--seconds", type=float, nargs="*", default=[8.0, 60.0])
@@ -111,6 +176,8 @@ def main():
     p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p()       # noqa: E731
     if args.score:
         return score_bench(args, dev, lib, ctx, p)
+    if args.grad:
+        return grad_bench(args, dev, lib, ctx, p)
     print("critic_bench: %s, medians of %d after %d warm-up runs; ms (TF of the product) | floor at %.0f TF" % (
         torch.cuda.get_device_name(0), args.reps, args.warmup, F32_MATRIX_TF))
     for ch in args.channels:

@@ -154,9 +154,17 @@ def build_parser():
                     "dialog and background WAV files under DIR are held on the device, and every --batch_size items are mixed there in one launch")
     ap.add_argument("--remix_seconds", type=float, default=50.0, metavar="S", help="length of a re-mixed item at 44.1 kHz (the reference's 50)")
     ap.add_argument("--remix_backgrounds", type=int, default=4, metavar="N", help="backgrounds per re-mixed item (the reference's 4)")
+    # (absent from the parsed arguments unless given: a run without them sees the arguments it always saw)
+    ap.add_argument("--critic", type=str, default=argparse.SUPPRESS, metavar="PATH", help="state dict of a Discriminator(2050) (train-discriminator.py at its "
+                    "default --n_fft 2048): committed once, its score of the model's output is added to every clip's loss as a constant "
+                    "(clips need 601 frames)")
+    ap.add_argument("--adversarial", action="store_true", default=argparse.SUPPRESS, help="with --critic: let the gradient flow through the frozen critic into the model "
+                    "(score and dx from one library call, CommittedCritic.score_fixed)")
     return ap
 
 
+CRITIC_REFUSAL = ("--critic does not go with --graph, --ragged or --remix: the critic's term is part of the per-clip step only "
+                  "(no graph capture of it, no ragged or packed step with a critic)")
 REMIX_REFUSAL = "--remix does not go with --rir or --graph: the reference's MixDataSet has no reverberation, and the items of a step are a ragged batch"
 
 
@@ -167,6 +175,11 @@ def parse_args(ap, argv=None):
         ap.error(REMIX_REFUSAL)
     if args.remix and (int(args.remix_seconds * 44100) <= 1024 or args.remix_backgrounds < 0):
         ap.error("--remix needs --remix_seconds of more than 1024 samples at 44.1 kHz and --remix_backgrounds >= 0")
+    critic, adversarial = getattr(args, "critic", None), getattr(args, "adversarial", False)
+    if critic and (args.graph or args.ragged or args.remix):
+        ap.error(CRITIC_REFUSAL)
+    if adversarial and not critic:
+        ap.error("--adversarial needs --critic PATH")
     return args
 
 
@@ -217,6 +230,14 @@ def main(argv=None):
     graphs = {}                                                  # clip shape -> GraphedTrainStep
     if args.resume and os.path.exists(os.path.join(args.outdir, "optimizer.pth")):
         optimizer.load_state_dict(torch.load(os.path.join(args.outdir, "optimizer.pth"), weights_only=True))
+
+    critic, adversarial = None, getattr(args, "adversarial", False)
+    if getattr(args, "critic", None):
+        from speechseparation_amd.discriminator import Discriminator
+        D = Discriminator(2050)
+        D.load_state_dict(torch.load(args.critic, weights_only=True), strict=True)
+        critic = D.to(device).commit(grad=adversarial)      # a snapshot: the module goes, the object stays for the run
+        del D
 
     reverb = None
     if args.rir:
@@ -271,7 +292,7 @@ def main(argv=None):
                 epoch_loss += float(loss)
                 epoch_sdr += float(step.last_sdr)
                 continue
-            loss, x_time = hip_train.train_loss(model, mix, speech)
+            loss, x_time = hip_train.train_loss(model, mix, speech, discriminator=critic, adversarial=adversarial)
             sdr = hip_train.sdr(x_time, speech[:, :x_time.shape[1]])
             (-sdr if args.loss_sdr else loss).backward()
             batch_i += 1
