@@ -361,6 +361,46 @@ int  bsrnn_critic_layer1_dx(bsrnn_critic* critic, const float* dp_dev, int32_t C
  * chain's planar copies; out[7] = bytes of the dx image.  BSRNN_EARG as above, or for a null out. */
 int  bsrnn_critic_grad_layout(int32_t in_channels, int32_t C, int32_t T, int64_t out[8]);
 
+/* The committed critic on a padded batch: one score per CLIP of a rectangle x_dev [R][in_channels][Tmax] (either channel order) whose rows
+ * belong to clips of different lengths - clip c owns clip_rows_host[c] consecutive rows of frames_host[c] frames each,
+ * 601 <= frames[c] <= Tmax, the rows of all clips summing to R.  What lies behind a row's frames is never read.
+ *   bsrnn_critic_score_ragged       scores_dev[c] = sigmoid(Linear(mean over the clip's rows of mean over its own frames of layers(x))): what
+ *                               bsrnn_critic_score gives for the clip alone up to the order of the first layer's sums, which is that of the
+ *                               rectangle (the K slabs of bsrnn_critic_score_layout(in_channels, R, Tmax)) - a function of (in_channels, R,
+ *                               Tmax) and the row's own length, never of the other clips; one clip owning all rows at frames = Tmax gives
+ *                               bsrnn_critic_score's bits.  The first layer's workgroups whose 128 frames all lie behind a row's
+ *                               (frames - 16) / 3 + 1 return at once.  y1_dev, when not NULL, receives the first layer's output
+ *                               [R][1024][(Tmax - 16) / 3 + 1], valid below each row's own length (test and measurement support).
+ *   bsrnn_critic_score_grad_ragged  the same scores, and dx_dev [R][in_channels][Tmax] = gscale_dev[c] * d score_c / d x for the rows of
+ *                               clip c (gscale_dev [n_clips] on the device, NULL means 1), in x's own order; every position is written,
+ *                               zeros behind a row's frames.  The scale of the first layer's dx (bsrnn_critic_score_grad) is formed per
+ *                               CLIP: a clip with a tiny gradient beside a large one keeps its own precision.
+ *   bsrnn_critic_layer1_dx_ragged   the first layer's dx alone from dp_dev [R][1024][(Tmax - 16) / 3 + 1], zeros behind each row's own
+ *                               length (test and measurement support).
+ * All follow the compute mode and the range policy as bsrnn_critic_score_grad does: an |x| beyond 65504 INSIDE a row's frames or a
+ * non-finite dp1 raises the guard, BSRNN_RANGE_EXACT runs the whole call again on the exact kernels, BSRNN_RANGE_DEFERRED stays
+ * asynchronous; BSRNN_GEMM=f32 and a hot weight go to the exact kernels directly.  The two tables travel through the context's upload ring,
+ * the workspace is the grow-only training buffer (out[10] / out[11] / out[12] floats of the layout): a second call of a shape allocates
+ * nothing.  Bit-reproducible; no fp32 atomics.
+ * BSRNN_EARG, before anything touches the device and also on a host-only context: a null object or pointer (y1_dev and gscale_dev may be
+ * NULL), n_clips < 1, a clip with fewer than 1 row, with fewer than 601 or more than Tmax frames, rows not summing to R, x_order outside
+ * {0, 1}, x_order 1 with an odd in_channels, a tensor, image, grid or workspace beyond 2^31 - 1 elements, overlapping buffers.  Then
+ * BSRNN_ESTATE on a host-only context, before the first commit and (the two gradient calls) when the gradient is not enabled. */
+int  bsrnn_critic_score_ragged(bsrnn_critic* critic, const float* x_dev, int32_t R, int32_t Tmax, const int32_t* frames_host,
+                               const int32_t* clip_rows_host, int32_t n_clips, int32_t x_order, float* scores_dev, float* y1_dev, void* stream);
+int  bsrnn_critic_score_grad_ragged(bsrnn_critic* critic, const float* x_dev, int32_t R, int32_t Tmax, const int32_t* frames_host,
+                                    const int32_t* clip_rows_host, int32_t n_clips, int32_t x_order, const float* gscale_dev,
+                                    float* scores_dev, float* dx_dev, void* stream);
+int  bsrnn_critic_layer1_dx_ragged(bsrnn_critic* critic, const float* dp_dev, int32_t R, int32_t Tmax, const int32_t* frames_host,
+                                   const int32_t* clip_rows_host, int32_t n_clips, int32_t x_order, float* dx_dev, void* stream);
+/* The plan of a ragged call (no context or device needed): out[0..3] = frames behind the four layers at Tmax; out[4], out[5] = K slabs of
+ * the first layer and input channels per slab; out[6] = frame tiles per row of the first layer's forward, out[7] = the live ones summed over
+ * the rows; out[8] = position tiles per row of its dx, out[9] = the live ones summed over the rows; out[10] = workspace of a score in
+ * floats, out[11] = of a score with its gradient, out[12] = with the exact chain's planar copies; out[13] = bytes of the two tables.
+ * BSRNN_EARG as above, or for a null out. */
+int  bsrnn_critic_ragged_layout(int32_t in_channels, int32_t R, int32_t Tmax, const int32_t* frames_host, const int32_t* clip_rows_host,
+                                int32_t n_clips, int64_t out[14]);
+
 /* torch.optim.AdamW(model.parameters(), lr, weight_decay) of train.py:50, one tensor per call: p, m (exp_avg), v (exp_avg_sq)
  * updated in place from the gradient g; `step` counts from 1 (bias correction).  n floats each, device pointers.  The betas are
  * double, as torch's: 1 - beta2 and the bias corrections are formed from them in double (from 0.999f, 1 - beta2 is 1.3e-5 off). */

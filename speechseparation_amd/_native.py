@@ -44,6 +44,7 @@ SYMBOLS = [
     "bsrnn_critic_spectrum", "bsrnn_critic_spectrum_layout",
     "bsrnn_critic_create", "bsrnn_critic_commit", "bsrnn_critic_score", "bsrnn_critic_score_layout", "bsrnn_critic_destroy",
     "bsrnn_critic_enable_grad", "bsrnn_critic_score_grad", "bsrnn_critic_layer1_dx", "bsrnn_critic_grad_layout",
+    "bsrnn_critic_score_ragged", "bsrnn_critic_score_grad_ragged", "bsrnn_critic_layer1_dx_ragged", "bsrnn_critic_ragged_layout",
 ]
 RANGE_DEFERRED, RANGE_EXACT = 0, 1          # BSRNN_RANGE_* of include/bsrnn_hip.h
 STREAM_ROWS_MAX = 2048                      # BSRNN_STREAM_ROWS_MAX
@@ -219,6 +220,10 @@ def _load():
         "bsrnn_critic_score_grad": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "bsrnn_critic_layer1_dx": (C.c_int, [vp, vp, i32, i32, i32, vp, vp]),
         "bsrnn_critic_grad_layout": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
+        "bsrnn_critic_score_ragged": (C.c_int, [vp, vp, i32, i32, C.POINTER(i32), C.POINTER(i32), i32, i32, vp, vp, vp]),
+        "bsrnn_critic_score_grad_ragged": (C.c_int, [vp, vp, i32, i32, C.POINTER(i32), C.POINTER(i32), i32, i32, vp, vp, vp, vp]),
+        "bsrnn_critic_layer1_dx_ragged": (C.c_int, [vp, vp, i32, i32, C.POINTER(i32), C.POINTER(i32), i32, i32, vp, vp]),
+        "bsrnn_critic_ragged_layout": (C.c_int, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(i64)]),
         "bsrnn_critic_destroy": (None, [vp]),
         "bsrnn_set_profiling": (C.c_int, [vp, i32]),
         "bsrnn_stage_count": (C.c_int, []),

@@ -9,6 +9,8 @@
 // And its gradient (bsrnn_critic_enable_grad / _score_grad / _layer1_dx): the score and d score / d x in one call, the first layer's dx on
 // the fp16x2 matrix path from a second image, layers 4 .. 2 on the exact dx kernel with no dW beside it.  The image, the tiles and the
 // workspace: critic_grad_host.h; the kernels: critic_grad.hip.
+// And both on a padded batch (bsrnn_critic_score_ragged / _score_grad_ragged / _layer1_dx_ragged): one score per clip of a rectangle of rows
+// of different lengths, the padding frames of the first layer skipped.  The tables, the live tiles and the workspace: critic_ragged_host.h.
 #include "api_internal.h"
 
 #include <cmath>
@@ -81,6 +83,28 @@ static int grad_sizes_ok(int32_t I, int32_t C, int32_t T, int32_t x_order, const
     default:
         return fail(BSRNN_EARG, "%s: in_channels = %d, C = %d, T = %d: x, a layer's gradient, the image or the workspace would pass 2^31 - 1 elements",
                     who, I, C, T);
+    }
+}
+
+// A ragged call's arguments (critic_ragged_host.h): frames and clip_rows are not null
+static int ragged_args_ok(int32_t I, int32_t R, int32_t Tmax, const int32_t* frames, const int32_t* clip_rows, int32_t n_clips, int32_t x_order,
+                          bool grad, const char* who)
+{
+    int bad = -1;
+    switch (crg_check(I, R, Tmax, frames, clip_rows, n_clips, x_order, grad, &bad)) {
+    case CRG_OK: return 0;
+    case CRG_BAD_CHANNELS: return fail(BSRNN_EARG, "%s: need in_channels >= 1, got %d", who, I);
+    case CRG_NO_CLIPS: return fail(BSRNN_EARG, "%s: need n_clips >= 1, got n_clips = %d", who, n_clips);
+    case CRG_BAD_CLIP_ROWS: return fail(BSRNN_EARG, "%s: clip %d has %d rows, need at least 1", who, bad, clip_rows[bad]);
+    case CRG_CLIP_TOO_SHORT:
+        return fail(BSRNN_EARG, "%s: clip %d has %d frames, the four layers need at least %d", who, bad, frames[bad], CRITIC_MIN_T);
+    case CRG_CLIP_TOO_LONG: return fail(BSRNN_EARG, "%s: clip %d has %d frames, more than Tmax = %d", who, bad, frames[bad], Tmax);
+    case CRG_ROWS_MISMATCH: return fail(BSRNN_EARG, "%s: the clips' rows do not sum to R = %d", who, R);
+    case CRG_BAD_ORDER: return fail(BSRNN_EARG, "%s: x_order = %d is neither 0 (planar) nor 1 (interleaved)", who, x_order);
+    case CRG_ODD_INTERLEAVED: return fail(BSRNN_EARG, "%s: an interleaved input has an even number of channels, in_channels = %d is odd", who, I);
+    default:
+        return fail(BSRNN_EARG, "%s: in_channels = %d, R = %d, Tmax = %d, n_clips = %d: x, a layer's gradient, an image or the workspace would pass "
+                    "2^31 - 1 elements", who, I, R, Tmax, n_clips);
     }
 }
 
@@ -482,6 +506,210 @@ int bsrnn_critic_score_grad(bsrnn_critic* k, const float* x, int32_t C, int32_t 
             else launch_critic_dp_max(shared, yl[0], dpl[0], (unsigned*)(ws + g.off_max), n, s);
         }
         first_layer_dx(k, q, g, dpl[0], ws, dx, x_order, exact, s);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    const bool exact_now = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+    if (int rc = run()) return rc;
+    if (exact_now) return 0;               // (the exact chain ran: no guard to wait for)
+    return finish_call(c, s, run);
+}
+
+// ------------------------------------------------------------------------------------------------ the committed critic on a padded batch
+int bsrnn_critic_ragged_layout(int32_t in_channels, int32_t R, int32_t Tmax, const int32_t* frames, const int32_t* clip_rows, int32_t n_clips,
+                               int64_t out[14])
+{
+    if (!out) return fail(BSRNN_EARG, "bsrnn_critic_ragged_layout: nowhere to write the layout");
+    if (!frames || !clip_rows) return fail(BSRNN_EARG, "bsrnn_critic_ragged_layout: null argument (need frames_host and clip_rows_host)");
+    if (int rc = ragged_args_ok(in_channels, R, Tmax, frames, clip_rows, n_clips, CSC_ORDER_PLANAR, true, "bsrnn_critic_ragged_layout")) return rc;
+    const CrgPlan p = crg_plan(in_channels, R, Tmax, n_clips);
+    for (int l = 0; l < CRITIC_LAYERS; ++l) out[l] = p.g.f.len[l];
+    out[4] = p.g.f.slabs; out[5] = p.g.f.ch_per_slab;
+    out[6] = p.g.f.t_tiles; out[8] = p.g.s_tiles;
+    crg_live_tiles(p, frames, clip_rows, &out[7], &out[9]);
+    out[10] = p.g.f.ws_floats; out[11] = p.ws_floats; out[12] = p.ws_exact_floats; out[13] = p.table_bytes;
+    return 0;
+}
+
+// What the three ragged calls share behind their argument checks: the tables go up through the context's ring, in front of the kernels
+struct RaggedTables { const CrgRow* rows; const CrgClip* clips; };
+static int ragged_upload(bsrnn_ctx* c, const CrgPlan& p, const int32_t* frames, const int32_t* clip_rows, hipStream_t s, RaggedTables* t)
+{
+    const int R = p.g.f.C;
+    const size_t row_bytes = (size_t)R * sizeof(CrgRow);
+    if (int rc = c->rg.upload((size_t)p.table_bytes, s, [&](char* h) {
+            crg_tables(frames, clip_rows, p.n_clips, reinterpret_cast<CrgRow*>(h), reinterpret_cast<CrgClip*>(h + row_bytes));
+        })) return rc;
+    t->rows = reinterpret_cast<const CrgRow*>(c->rg.d);
+    t->clips = reinterpret_cast<const CrgClip*>(c->rg.d + row_bytes);
+    return 0;
+}
+
+// The forward of a ragged call into yl[0 .. 3] and scores: the first layer on fp16x2 with its dead tiles skipped (or the exact kernel on the
+// rectangle, through a zero-padded planar copy at xp when x is interleaved), layers 2 - 4 on the rectangle, the tail per clip
+static void ragged_forward(const bsrnn_critic* k, const CriticParams& q, const CrgPlan& p, const RaggedTables& t, const float* x, float* xp,
+                           float* const yl[CRITIC_LAYERS], float* shared, float* scores, int x_order, bool exact, hipStream_t s)
+{
+    const CscPlan& f = p.g.f;
+    const float* const par = k->d_par;
+    const int R = f.C, Tmax = f.T;
+    if (exact) {
+        const float* src = x;
+        if (x_order == CSC_ORDER_INTERLEAVED) { launch_critic_planar_ragged(x, xp, R, k->I, Tmax, t.rows, s); src = xp; }
+        launch_critic_forward(src, par + q.off[0], par + q.off[1], yl[0], shared, R, k->I, Tmax, CSC_O, 1, s);
+    } else {
+        launch_critic_first_h2_ragged(x, k->d_img, par + q.off[1], yl[0], shared, k->ctx->d_range, f, x_order, t.rows, s);
+    }
+    for (int l = 1; l < CRITIC_LAYERS; ++l)
+        launch_critic_forward(yl[l - 1], par + q.off[2 * l], par + q.off[2 * l + 1], yl[l], shared, R, CRITIC_WIDTHS[l - 1], f.len[l - 1],
+                              CRITIC_WIDTHS[l], l + 1 < CRITIC_LAYERS, s);
+    launch_critic_tail_ragged(yl[CRITIC_LAYERS - 1], par + q.off[2 * CRITIC_LAYERS], par + q.off[2 * CRITIC_LAYERS + 1], scores, t.clips, p.n_clips,
+                              f.len[CRITIC_LAYERS - 1], s);
+}
+
+// The first layer's dx of a ragged call from dp1 [R][1024][T1max] (zeros behind a row's T1_r), whose maxima per clip stand in the max words
+static void ragged_first_layer_dx(const bsrnn_critic* k, const CriticParams& q, const CrgPlan& p, const RaggedTables& t, const float* dp1, float* ws,
+                                  float* dx, int x_order, bool exact, hipStream_t s)
+{
+    const int R = p.g.f.C, Tmax = p.g.f.T;
+    if (!exact) {
+        launch_critic_dx_h2_ragged(dp1, k->d_img_dx, dx, (const unsigned*)(ws + p.off_max), k->ctx->d_range, p.g, x_order, t.rows, s);
+    } else if (x_order == CSC_ORDER_INTERLEAVED) {
+        launch_critic_dx(k->d_par + q.off[0], dp1, ws + p.off_dxp, R, k->I, Tmax, CSC_O, s);
+        launch_critic_scatter(ws + p.off_dxp, dx, R, k->I, Tmax, s);
+    } else {
+        launch_critic_dx(k->d_par + q.off[0], dp1, dx, R, k->I, Tmax, CSC_O, s);
+    }
+}
+
+int bsrnn_critic_score_ragged(bsrnn_critic* k, const float* x, int32_t R, int32_t Tmax, const int32_t* frames, const int32_t* clip_rows,
+                              int32_t n_clips, int32_t x_order, float* scores, float* y1, void* stream)
+{
+    const char* who = "bsrnn_critic_score_ragged";
+    if (!k) return fail(BSRNN_EARG, "null critic");
+    if (!x || !frames || !clip_rows || !scores)
+        return fail(BSRNN_EARG, "%s: null argument (need x_dev, frames_host, clip_rows_host and scores_dev; only y1_dev may be null)", who);
+    if (int rc = ragged_args_ok(k->I, R, Tmax, frames, clip_rows, n_clips, x_order, false, who)) return rc;
+    const CrgPlan p = crg_plan(k->I, R, Tmax, n_clips);
+    const CscPlan& f = p.g.f;
+    const size_t nx = (size_t)R * k->I * Tmax * sizeof(float), ns = (size_t)n_clips * sizeof(float), ny1 = (size_t)R * CSC_O * f.len[0] * sizeof(float);
+    if (ranges_overlap(scores, ns, x, nx) || ranges_overlap(y1, ny1, x, nx))
+        return fail(BSRNN_EARG, "%s: %s overlaps x_dev (a call that left the fp16 range is run again from x)", who,
+                    ranges_overlap(scores, ns, x, nx) ? "scores_dev" : "y1_dev");
+    if (ranges_overlap(scores, ns, y1, ny1)) return fail(BSRNN_EARG, "%s: scores_dev overlaps y1_dev", who);
+    bsrnn_ctx* c = k->ctx;
+    if (int rc = check_device(c)) return rc;
+    if (!k->committed) return fail(BSRNN_ESTATE, "%s: bsrnn_critic_commit() has not been called", who);
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    RaggedTables t{};
+    if (int rc = ragged_upload(c, p, frames, clip_rows, s, &t)) return rc;
+    const CriticParams q(k->I);
+    auto run = [&]() -> int {
+        const bool exact = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+        const bool copy = exact && x_order == CSC_ORDER_INTERLEAVED;
+        const size_t n_ws = (size_t)(copy ? f.ws_exact_floats : f.ws_floats);
+        float* ws = train_scratch(c, n_ws);
+        if (!ws) return fail(BSRNN_EHIP, "%s: out of device memory (%zu MB of workspace)", who, n_ws * sizeof(float) >> 20);
+        float* yl[CRITIC_LAYERS];
+        for (int l = 0; l < CRITIC_LAYERS; ++l) yl[l] = ws + f.off_y[l];
+        if (y1) yl[0] = y1;
+        ragged_forward(k, q, p, t, x, ws + f.ws_floats, yl, ws + f.off_shared, scores, x_order, exact, s);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    const bool exact_now = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+    if (int rc = run()) return rc;
+    if (exact_now) return 0;               // (the exact chain ran: no guard to wait for)
+    return finish_call(c, s, run);
+}
+
+int bsrnn_critic_layer1_dx_ragged(bsrnn_critic* k, const float* dp, int32_t R, int32_t Tmax, const int32_t* frames, const int32_t* clip_rows,
+                                  int32_t n_clips, int32_t x_order, float* dx, void* stream)
+{
+    const char* who = "bsrnn_critic_layer1_dx_ragged";
+    if (!k) return fail(BSRNN_EARG, "null critic");
+    if (!dp || !frames || !clip_rows || !dx) return fail(BSRNN_EARG, "%s: null argument (need dp_dev, frames_host, clip_rows_host and dx_dev)", who);
+    if (int rc = ragged_args_ok(k->I, R, Tmax, frames, clip_rows, n_clips, x_order, true, who)) return rc;
+    const CrgPlan p = crg_plan(k->I, R, Tmax, n_clips);
+    const size_t n_row = (size_t)CSC_O * p.g.f.len[0], nx = (size_t)R * k->I * Tmax * sizeof(float), ndp = (size_t)R * n_row * sizeof(float);
+    if (ranges_overlap(dx, nx, dp, ndp)) return fail(BSRNN_EARG, "%s: dx_dev overlaps dp_dev (a call that left the fp16 range is run again from dp)", who);
+    bsrnn_ctx* c = k->ctx;
+    if (int rc = check_device(c)) return rc;
+    if (!k->committed) return fail(BSRNN_ESTATE, "%s: bsrnn_critic_commit() has not been called", who);
+    if (!k->d_img_dx) return fail(BSRNN_ESTATE, "%s: bsrnn_critic_enable_grad() has not been called", who);
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    RaggedTables t{};
+    if (int rc = ragged_upload(c, p, frames, clip_rows, s, &t)) return rc;
+    const CriticParams q(k->I);
+    auto run = [&]() -> int {
+        const bool exact = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+        const size_t n_ws = (size_t)(exact && x_order == CSC_ORDER_INTERLEAVED ? p.ws_exact_floats : p.ws_floats);
+        float* ws = train_scratch(c, n_ws);
+        if (!ws) return fail(BSRNN_EHIP, "%s: out of device memory (%zu MB of workspace)", who, n_ws * sizeof(float) >> 20);
+        if (!exact) {
+            HIP_TRY(hipMemsetAsync(ws + p.off_max, 0, (size_t)csc_round4(n_clips) * sizeof(float), s));
+            launch_critic_dp_max_rows(dp, nullptr, nullptr, (unsigned*)(ws + p.off_max), t.rows, R, n_row, s);
+        }
+        ragged_first_layer_dx(k, q, p, t, dp, ws, dx, x_order, exact, s);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    const bool exact_now = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+    if (int rc = run()) return rc;
+    if (exact_now) return 0;
+    return finish_call(c, s, run);
+}
+
+int bsrnn_critic_score_grad_ragged(bsrnn_critic* k, const float* x, int32_t R, int32_t Tmax, const int32_t* frames, const int32_t* clip_rows,
+                                   int32_t n_clips, int32_t x_order, const float* gscale, float* scores, float* dx, void* stream)
+{
+    const char* who = "bsrnn_critic_score_grad_ragged";
+    if (!k) return fail(BSRNN_EARG, "null critic");
+    if (!x || !frames || !clip_rows || !scores || !dx)
+        return fail(BSRNN_EARG, "%s: null argument (need x_dev, frames_host, clip_rows_host, scores_dev and dx_dev; only gscale_dev may be null)", who);
+    if (int rc = ragged_args_ok(k->I, R, Tmax, frames, clip_rows, n_clips, x_order, true, who)) return rc;
+    const CrgPlan p = crg_plan(k->I, R, Tmax, n_clips);
+    const CscPlan& f = p.g.f;
+    const size_t nx = (size_t)R * k->I * Tmax * sizeof(float), ns = (size_t)n_clips * sizeof(float);
+    if (ranges_overlap(dx, nx, x, nx)) return fail(BSRNN_EARG, "%s: dx_dev overlaps x_dev (a call that left the fp16 range is run again from x)", who);
+    if (ranges_overlap(scores, ns, x, nx)) return fail(BSRNN_EARG, "%s: scores_dev overlaps x_dev", who);
+    if (ranges_overlap(dx, nx, scores, ns)) return fail(BSRNN_EARG, "%s: dx_dev overlaps scores_dev", who);
+    if (ranges_overlap(gscale, ns, dx, nx) || ranges_overlap(gscale, ns, scores, ns))
+        return fail(BSRNN_EARG, "%s: gscale_dev overlaps an output (the re-run reads it again)", who);
+    bsrnn_ctx* c = k->ctx;
+    if (int rc = check_device(c)) return rc;
+    if (!k->committed) return fail(BSRNN_ESTATE, "%s: bsrnn_critic_commit() has not been called", who);
+    if (!k->d_img_dx) return fail(BSRNN_ESTATE, "%s: bsrnn_critic_enable_grad() has not been called", who);
+    hipStream_t s = (hipStream_t)stream;
+    ENTER_CALL(c, s);
+    RaggedTables t{};
+    if (int rc = ragged_upload(c, p, frames, clip_rows, s, &t)) return rc;
+    const CriticParams q(k->I);
+    const float* const par = k->d_par;
+    auto run = [&]() -> int {
+        const bool exact = force_f32() || gemm_mode() == GEMM_F32 || !k->usable;
+        const bool copy = exact && x_order == CSC_ORDER_INTERLEAVED;
+        const size_t n_ws = (size_t)(copy ? p.ws_exact_floats : p.ws_floats);
+        float* ws = train_scratch(c, n_ws);
+        if (!ws) return fail(BSRNN_EHIP, "%s: out of device memory (%zu MB of workspace)", who, n_ws * sizeof(float) >> 20);
+        float *yl[CRITIC_LAYERS], *dpl[CRITIC_LAYERS];
+        for (int l = 0; l < CRITIC_LAYERS; ++l) { yl[l] = ws + f.off_y[l]; dpl[l] = ws + p.g.off_dp[l]; }
+        float* shared = ws + f.off_shared;
+        // the scores, exactly as bsrnn_critic_score_ragged forms them
+        ragged_forward(k, q, p, t, x, ws + p.off_xp, yl, shared, scores, x_order, exact, s);
+        // and back: the tail per clip (zeros behind a row's T4_r), then layers 4 .. 2 on the rectangle, dp1 with the maximum per clip
+        launch_critic_tail_grad_ragged(scores, par + q.off[2 * CRITIC_LAYERS], gscale, ws + p.off_pool, dpl[CRITIC_LAYERS - 1], t.clips, n_clips,
+                                       f.len[CRITIC_LAYERS - 1], s);
+        HIP_TRY(hipMemsetAsync(ws + p.off_max, 0, (size_t)csc_round4(n_clips) * sizeof(float), s));
+        for (int l = CRITIC_LAYERS - 1; l >= 1; --l) {
+            const size_t n_row = (size_t)CRITIC_WIDTHS[l - 1] * f.len[l - 1];
+            launch_critic_dx(par + q.off[2 * l], dpl[l], shared, R, CRITIC_WIDTHS[l - 1], f.len[l - 1], CRITIC_WIDTHS[l], s);
+            if (l > 1) launch_critic_dp(shared, yl[l - 1], dpl[l - 1], (size_t)R * n_row, s);
+            else launch_critic_dp_max_rows(shared, yl[0], dpl[0], (unsigned*)(ws + p.off_max), t.rows, R, n_row, s);
+        }
+        ragged_first_layer_dx(k, q, p, t, dpl[0], ws, dx, x_order, exact, s);
         HIP_TRY(hipGetLastError());
         return 0;
     };

@@ -16,6 +16,9 @@
 //                              (the stages' 64 KB) and is folded into the 369 input positions the tile completes, taps in tap order, the
 //                              result multiplied by the inverse power of two and written at the row the channel map names.
 //   critic_scatter_kernel      a planar dx written into the separator's interleaved order (the exact chain's way back).
+//   critic_tail_grad_ragged_kernel, critic_dp_max_rows_kernel, critic_dx_h2_kernel<true>   the same three on a padded batch
+//                              (bsrnn_critic_score_grad_ragged; critic_ragged_host.h): the tail's gradient per clip with zeros behind a row's
+//                              T4_r, the maximum and with it the scale PER CLIP, dead position tiles written as zeros without staging.
 // No atomics except the order-free integer max; no kernel here uses scratch memory.
 #include "kernels.h"
 
@@ -108,8 +111,13 @@ __global__ __launch_bounds__(256) void critic_dp_max_kernel(const float* dy, con
     }
 }
 
+// RAGGED (bsrnn_critic_score_grad_ragged; critic_ragged_host.h): row c holds rows[c].frames <= T frames and reads the max word of ITS
+// clip, mx[rows[c].clip]; a position tile wholly at or behind the row's frames writes zeros before it stages anything, and a live one
+// writes zeros at the positions behind them, so every s < T of every row is written.
+template <bool RAGGED>
 __global__ __launch_bounds__(256, 2) void critic_dx_h2_kernel(const float* __restrict__ dp, const _Float16* __restrict__ img, float* __restrict__ dx,
-                                                              const unsigned* __restrict__ mx, int* range_flag, CgdPlan g, int x_order)
+                                                              const unsigned* __restrict__ mx, int* range_flag, CgdPlan g, int x_order,
+                                                              const CrgRow* __restrict__ rows)
 {
     __shared__ __attribute__((aligned(16))) _Float16 sm[2 * STAGE];
     // The tiles (c, position tile) of one channel tile read the same weight blocks: they sit on consecutive workgroups of one XCD (speed only)
@@ -122,14 +130,31 @@ __global__ __launch_bounds__(256, 2) void critic_dx_h2_kernel(const float* __res
     const int t_lo = cgd_tile_frame0(bs), s0 = cgd_tile_first(bs), i0 = bi * CGD_CH;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, half = lane >> 5, r32 = lane & 31;
 
-    const unsigned mbits = mx[0];
+    int Tr = T, T1r = T1;                                    // the row's own frames, in front of and behind the layer (T and T1 stay the strides)
+    unsigned mbits;
+    if constexpr (RAGGED) {
+        const CrgRow row = rows[c];
+        Tr = row.frames; T1r = crg_t_out(Tr);
+        mbits = mx[row.clip];
+    } else {
+        mbits = mx[0];
+    }
     const int e = cgd_scale_exponent(mbits);
     if (mbits >= 0x7f800000u && range_flag && tid == 0) *range_flag = 1;       // a non-finite dp1: the guard, as for an |x| beyond fp16
+    if constexpr (RAGGED) {
+        if (s0 >= Tr) {
+            for (int idx = tid; idx < CGD_CH * CGD_TILE_S; idx += 256) {
+                const int ch = idx / CGD_TILE_S, s = s0 + (idx - ch * CGD_TILE_S);
+                if (i0 + ch < I && s < T) dx[((size_t)c * I + csc_channel_row(I, i0 + ch, x_order)) * T + s] = 0.f;
+            }
+            return;
+        }
+    }
 
     // staging: four 16-byte units of the stage's 16 KB of the image, and the unit (t = tid & 127, octet = tid >> 7) of both K steps
     const _Float16* const a_src = img + (size_t)bi * (CSC_O / CGD_KB) * CSC_BLOCK + 8 * tid;
     const int st = tid & (CGD_TILE_T - 1), sh = tid >> 7;
-    const bool t_in = t_lo + st >= 0 && t_lo + st < T1;
+    const bool t_in = t_lo + st >= 0 && t_lo + st < T1r;
     // (a lane's offset is small and the same for every load; the row (c, o) in front of it is uniform)
     const unsigned d_off = (unsigned)(8 * sh * T1 + (t_in ? t_lo + st : 0));
     const float* const d_row = dp + (size_t)c * CSC_O * T1;
@@ -234,7 +259,57 @@ __global__ __launch_bounds__(256, 2) void critic_dx_h2_kernel(const float* __res
         if (i0 + ch >= I || s >= T) continue;
         float v = 0.f;
         for (int k = d % CRITIC_STRIDE; k < CRITIC_TAPS; k += CRITIC_STRIDE) v += sg[sg_at(ch * CRITIC_TAPS + k, cgd_fold_column(d, k))];
+        if (RAGGED && s >= Tr) v = 0.f;                          // (a sum of products with zeros already: written as a plain zero)
         dx[((size_t)c * I + csc_channel_row(I, i0 + ch, x_order)) * T + s] = __builtin_ldexpf(v, -e);
+    }
+}
+
+// critic_tail_grad_kernel per clip of a padded batch: workgroup c forms gp[c][o] = ((gscale[c] * s_c (1 - s_c)) * lw[o] / rows_c) / T4_c and
+// writes it into dp4 [R][32][T4max] of the clip's rows for t < T4_c, and ZEROS for T4_c <= t < T4max (critic_ragged_host.h: with zeros
+// there the exact dx / dp kernels of layers 4 .. 2 run on the rectangle unchanged).
+__global__ __launch_bounds__(256) void critic_tail_grad_ragged_kernel(const float* __restrict__ scores, const float* __restrict__ lw,
+                                                                      const float* __restrict__ gscale, float* __restrict__ gp, float* __restrict__ dp4,
+                                                                      const CrgClip* __restrict__ clips, int T4max)
+{
+    constexpr int O4 = CRITIC_WIDTHS[CRITIC_LAYERS - 1];
+    __shared__ float sp[O4];
+    const CrgClip cl = clips[blockIdx.x];
+    const int C = cl.rows, T4 = crg_t4(cl.frames);
+    if (threadIdx.x < O4) {
+        const float s = scores[blockIdx.x], g = gscale ? gscale[blockIdx.x] : 1.f;
+        const float dz = g * ((1.f - s) * s);
+        const float v = ((dz * lw[threadIdx.x]) / (float)C) / (float)T4;
+        sp[threadIdx.x] = v;
+        gp[(size_t)blockIdx.x * O4 + threadIdx.x] = v;
+    }
+    __syncthreads();
+    const int n = C * O4 * T4max;
+    float* const out = dp4 + (size_t)cl.row0 * O4 * T4max;
+    for (int idx = threadIdx.x; idx < n; idx += 256) out[idx] = idx % T4max < T4 ? sp[(idx / T4max) % O4] : 0.f;
+}
+
+// critic_dp_max_kernel with the maximum per CLIP: a workgroup covers 256 values of ONE row r (per_row workgroups each) and raises
+// mx[rows[r].clip]
+__global__ __launch_bounds__(256) void critic_dp_max_rows_kernel(const float* dy, const float* __restrict__ y, float* dp, unsigned* __restrict__ mx,
+                                                                 const CrgRow* __restrict__ rows, unsigned n_row, unsigned per_row)
+{
+    __shared__ unsigned smax[4];
+    const unsigned r = blockIdx.x / per_row, j = (blockIdx.x - r * per_row) * 256 + threadIdx.x;
+    const size_t i = (size_t)r * n_row + j;
+    unsigned m = 0;
+    if (j < n_row) {
+        float gr = dy[i];
+        if (y) gr = y[i] > 0.f ? gr : 0.01f * gr;
+        if (dp) dp[i] = gr;
+        m = __float_as_uint(gr) & 0x7fffffffu;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { const unsigned v = __shfl_xor(m, d); m = v > m ? v : m; }
+    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = max(max(smax[0], smax[1]), max(smax[2], smax[3]));
+        if (m) atomicMax(mx + rows[r].clip, m);
     }
 }
 
@@ -270,7 +345,28 @@ void launch_critic_dx_h2(const float* dp, const void* image, float* dx, const un
                          hipStream_t s)
 {
     const size_t grid = (size_t)8 * ((g.i_tiles + 7) / 8) * g.f.C * g.s_tiles;
-    hipLaunchKernelGGL(critic_dx_h2_kernel, dim3((unsigned)grid), dim3(256), 0, s, dp, (const _Float16*)image, dx, mx, range_flag, g, x_order);
+    hipLaunchKernelGGL(critic_dx_h2_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, dp, (const _Float16*)image, dx, mx, range_flag, g, x_order,
+                       (const CrgRow*)nullptr);
+}
+
+// On a padded batch: g is the rectangle's plan, mx the clips' max words
+void launch_critic_dx_h2_ragged(const float* dp, const void* image, float* dx, const unsigned* mx, int* range_flag, const CgdPlan& g, int x_order,
+                                const CrgRow* rows, hipStream_t s)
+{
+    const size_t grid = (size_t)8 * ((g.i_tiles + 7) / 8) * g.f.C * g.s_tiles;
+    hipLaunchKernelGGL(critic_dx_h2_kernel<true>, dim3((unsigned)grid), dim3(256), 0, s, dp, (const _Float16*)image, dx, mx, range_flag, g, x_order, rows);
+}
+
+void launch_critic_tail_grad_ragged(const float* scores, const float* lin_w, const float* gscale, float* gp, float* dp4, const CrgClip* clips,
+                                    int n_clips, int T4max, hipStream_t s)
+{
+    hipLaunchKernelGGL(critic_tail_grad_ragged_kernel, dim3((unsigned)n_clips), dim3(256), 0, s, scores, lin_w, gscale, gp, dp4, clips, T4max);
+}
+
+void launch_critic_dp_max_rows(const float* dy, const float* y, float* dp, unsigned* mx, const CrgRow* rows, int R, size_t n_row, hipStream_t s)
+{
+    const unsigned per_row = (unsigned)((n_row + 255) / 256);
+    hipLaunchKernelGGL(critic_dp_max_rows_kernel, dim3(per_row * (unsigned)R), dim3(256), 0, s, dy, y, dp, mx, rows, (unsigned)n_row, per_row);
 }
 
 void launch_critic_scatter(const float* in, float* out, int C, int I, int T, hipStream_t s)

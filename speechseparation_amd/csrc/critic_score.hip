@@ -11,6 +11,9 @@
 //   critic_h2_finish_kernel  y1 = leaky(((p_0 + p_1) + ...) + b[o]) over the slabs' partial sums hi + 2^-11 lo.
 //   critic_tail_kernel     [C][32][T4] -> mean over t, mean over c, Linear(32, 1), sigmoid: one float, in a fixed order.
 //   critic_planar_kernel   an interleaved x in the reference's channel order (the exact chain reads that).
+//   critic_fwd_h2_kernel<true>, critic_tail_ragged_kernel, critic_planar_ragged_kernel   the same three on a padded batch of clips of
+//                          different lengths (bsrnn_critic_score_ragged; critic_ragged_host.h): tiles against the row's own length, dead tiles
+//                          return before staging, one tail workgroup and one score per clip, zeros behind a row's frames in the planar copy.
 // No atomics except the commit's order-free integer max; no kernel here uses scratch memory.
 #include "kernels.h"
 
@@ -69,8 +72,11 @@ __global__ __launch_bounds__(256) void critic_commit_kernel(const float* __restr
     }
 }
 
+// RAGGED (bsrnn_critic_score_ragged; critic_ragged_host.h): row c holds rows[c].frames <= T frames; the tile is taken against the row's own
+// T1_r, a tile wholly at or behind it returns before it stages anything, and nothing at or behind x[c][.][rows[c].frames] is loaded.
+template <bool RAGGED>
 __global__ __launch_bounds__(256, 2) void critic_fwd_h2_kernel(const float* __restrict__ x, const _Float16* __restrict__ img, float* __restrict__ part,
-                                                               int* range_flag, CscPlan p, int x_order)
+                                                               int* range_flag, CscPlan p, int x_order, const CrgRow* __restrict__ rows)
 {
     __shared__ __attribute__((aligned(16))) _Float16 sm[2 * STAGE];
     // The tiles (c, t tile) of one (slab, o tile) read the same weight blocks: they sit on consecutive workgroups of one XCD (speed only)
@@ -82,13 +88,18 @@ __global__ __launch_bounds__(256, 2) void critic_fwd_h2_kernel(const float* __re
     const int bo = grp % p.o_tiles, slab = grp / p.o_tiles;
     const int I = p.I, T = p.T, T1 = p.len[0];
     const int t0 = bt * CSC_TILE_T, o0 = bo * CSC_TILE_O;
+    int T1r = T1;                                            // the row's own frames behind the layer (T and T1 stay the strides)
+    if constexpr (RAGGED) {
+        T1r = crg_t_out(rows[c].frames);
+        if (t0 >= T1r) return;
+    }
     const int i_lo = slab * p.ch_per_slab, i_hi = min(I, i_lo + p.ch_per_slab);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, half = lane >> 5, r32 = lane & 31;
 
     // staging: four 16-byte units of the stage's 16 KB of the image, and the unit (t = tid & 127, h = tid >> 7) of both channels
     const _Float16* const a_src = img + (size_t)bo * csc_i_pad(I) * CSC_BLOCK + 8 * tid;
     const int st = tid & (CSC_TILE_T - 1), sh = tid >> 7;
-    const bool t_in = t0 + st < T1;                          // (then 3 (t0 + st) + 15 < T: the 16 taps lie inside the row)
+    const bool t_in = t0 + st < T1r;                         // (then 3 (t0 + st) + 15 < T: the 16 taps lie inside the row)
     const float* const x_src = x + (size_t)c * I * T + CRITIC_STRIDE * (t0 + st) + 8 * sh;
     h8 ra[4];
     float rx[CSC_CH][8];
@@ -180,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void critic_fwd_h2_kernel(const float* __re
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int t = t0 + 64 * wn + 32 * j + r32;
-            if (t >= T1) continue;
+            if (t >= T1r) continue;
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int o = o0 + 64 * wm + 32 * s + (reg & 3) + 8 * (reg >> 2) + 4 * half;
@@ -243,6 +254,51 @@ __global__ __launch_bounds__(256) void critic_planar_kernel(const float* __restr
     out[idx] = x[((ci - i) + csc_channel_row(I, i, CSC_ORDER_INTERLEAVED)) * T + t];
 }
 
+// critic_tail_kernel per clip of a padded batch: workgroup c reads rows clips[c].row0 .. + rows of y4 [R][32][T4max], the frames below the
+// clip's own T4, in the same fixed order, and writes scores[c].
+__global__ __launch_bounds__(256) void critic_tail_ragged_kernel(const float* __restrict__ y4, const float* __restrict__ lw, const float* __restrict__ lb,
+                                                                 float* __restrict__ scores, const CrgClip* __restrict__ clips, int T4max)
+{
+    constexpr int O4 = CRITIC_WIDTHS[CRITIC_LAYERS - 1];
+    __shared__ float sp[8][O4];
+    const CrgClip cl = clips[blockIdx.x];
+    const int C = cl.rows, T4 = crg_t4(cl.frames);
+    const int o = threadIdx.x & (O4 - 1), g = threadIdx.x >> 5;
+    float acc = 0.f;
+    for (int c = 0; c < C; ++c) {
+        float v = 0.f;
+        for (int t = g; t < T4; t += 8) v += y4[((size_t)(cl.row0 + c) * O4 + o) * T4max + t];
+        sp[g][o] = v;
+        __syncthreads();
+        if (g == 0) {
+            float m = sp[0][o];
+            for (int k = 1; k < 8; ++k) m += sp[k][o];
+            acc += m / (float)T4;
+        }
+        __syncthreads();
+    }
+    if (g == 0) sp[0][o] = acc / (float)C;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float z = 0.f;
+        for (int k = 0; k < O4; ++k) z += sp[0][k] * lw[k];
+        z += lb[0];
+        scores[blockIdx.x] = 1.f / (1.f + __expf(-z));
+    }
+}
+
+// critic_planar_kernel on a padded batch: zeros behind a row's frames, whatever x holds there
+__global__ __launch_bounds__(256) void critic_planar_ragged_kernel(const float* __restrict__ x, float* __restrict__ out, int I, int T, size_t n,
+                                                                   const CrgRow* __restrict__ rows)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const int t = (int)(idx % T);
+    const size_t ci = idx / T;
+    const int i = (int)(ci % I);
+    out[idx] = t < rows[ci / I].frames ? x[((ci - i) + csc_channel_row(I, i, CSC_ORDER_INTERLEAVED)) * T + t] : 0.f;
+}
+
 }  // namespace
 
 void launch_critic_commit(const float* w, void* image, unsigned* wmax, int I, hipStream_t s)
@@ -256,7 +312,19 @@ void launch_critic_first_h2(const float* x, const void* image, const float* bias
 {
     const int inner_n = p.C * p.t_tiles, groups = p.slabs * p.o_tiles;
     const size_t grid = (size_t)8 * ((groups + 7) / 8) * inner_n, n = (size_t)p.C * CSC_O * p.len[0];
-    hipLaunchKernelGGL(critic_fwd_h2_kernel, dim3((unsigned)grid), dim3(256), 0, s, x, (const _Float16*)image, part, range_flag, p, x_order);
+    hipLaunchKernelGGL(critic_fwd_h2_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, x, (const _Float16*)image, part, range_flag, p, x_order,
+                       (const CrgRow*)nullptr);
+    hipLaunchKernelGGL(critic_h2_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, bias, y1, n, p.len[0], p.slabs);
+}
+
+// The same two launches on a padded batch: p is the rectangle's plan (C = R rows of T = Tmax frames).  The finish runs over the rectangle;
+// what it writes behind a row's T1_r is unspecified (critic_ragged_host.h).
+void launch_critic_first_h2_ragged(const float* x, const void* image, const float* bias, float* y1, float* part, int* range_flag, const CscPlan& p,
+                                   int x_order, const CrgRow* rows, hipStream_t s)
+{
+    const int inner_n = p.C * p.t_tiles, groups = p.slabs * p.o_tiles;
+    const size_t grid = (size_t)8 * ((groups + 7) / 8) * inner_n, n = (size_t)p.C * CSC_O * p.len[0];
+    hipLaunchKernelGGL(critic_fwd_h2_kernel<true>, dim3((unsigned)grid), dim3(256), 0, s, x, (const _Float16*)image, part, range_flag, p, x_order, rows);
     hipLaunchKernelGGL(critic_h2_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, bias, y1, n, p.len[0], p.slabs);
 }
 
@@ -269,6 +337,18 @@ void launch_critic_planar(const float* x, float* out, int C, int I, int T, hipSt
 {
     const size_t n = (size_t)C * I * T;
     hipLaunchKernelGGL(critic_planar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, out, I, T, n);
+}
+
+void launch_critic_tail_ragged(const float* y4, const float* lin_w, const float* lin_b, float* scores, const CrgClip* clips, int n_clips, int T4max,
+                               hipStream_t s)
+{
+    hipLaunchKernelGGL(critic_tail_ragged_kernel, dim3((unsigned)n_clips), dim3(256), 0, s, y4, lin_w, lin_b, scores, clips, T4max);
+}
+
+void launch_critic_planar_ragged(const float* x, float* out, int R, int I, int Tmax, const CrgRow* rows, hipStream_t s)
+{
+    const size_t n = (size_t)R * I * Tmax;
+    hipLaunchKernelGGL(critic_planar_ragged_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, out, I, Tmax, n, rows);
 }
 
 }  // namespace bsrnn

@@ -15,6 +15,7 @@
 #include "critic_host.h"        // CriticLayout: tiles, K slabs and reduction chunks of the critic's convolution (HIP-free)
 #include "critic_score_host.h"  // CscPlan: the committed critic's weight image, K slabs and workspace (HIP-free)
 #include "critic_grad_host.h"   // CgdPlan: the committed critic's dx image, tiles and workspace (HIP-free)
+#include "critic_ragged_host.h" // CrgPlan: the committed critic on a padded batch, its tables and workspace (HIP-free)
 #include "critic_spectrum_host.h"   // CsSlab: the rows x frames one launch pair of the critic's 4096-point analysis owns (HIP-free)
 
 namespace bsrnn {
@@ -462,6 +463,23 @@ void launch_critic_dp_max(const float* dy, const float* y, float* dp, unsigned* 
 void launch_critic_dx_h2(const float* dp, const void* image, float* dx, const unsigned* mx, int* range_flag, const CgdPlan& g, int x_order,
                          hipStream_t s);
 void launch_critic_scatter(const float* in, float* out, int C, int I, int T, hipStream_t s);
+
+// The committed critic on a padded batch (bsrnn_critic_score_ragged / _score_grad_ragged; the tables, the live tiles and the workspace:
+// critic_ragged_host.h): the ragged forms of the launches above.  p / g are the RECTANGLE's plans (R rows of Tmax frames), rows [R] and
+// clips [n_clips] the call's device tables.  first_h2_ragged: y1 [R][1024][len[0]], valid below each row's own T1_r.  tail_ragged: one
+// score per clip.  tail_grad_ragged: gscale [n_clips] or null -> gp [n_clips][32] and dp4 [R][32][T4max], zeros behind a row's T4_r.
+// dp_max_rows: as dp_max, n_row values per row, the maximum into mx[clip of the row] (the caller zeroes the n_clips words).  dx_h2_ragged:
+// every s < Tmax of every row is written, zeros behind a row's frames.  planar_ragged: zeros behind a row's frames.
+void launch_critic_first_h2_ragged(const float* x, const void* image, const float* bias, float* y1, float* part, int* range_flag, const CscPlan& p,
+                                   int x_order, const CrgRow* rows, hipStream_t s);
+void launch_critic_tail_ragged(const float* y4, const float* lin_w, const float* lin_b, float* scores, const CrgClip* clips, int n_clips, int T4max,
+                               hipStream_t s);
+void launch_critic_planar_ragged(const float* x, float* out, int R, int I, int Tmax, const CrgRow* rows, hipStream_t s);
+void launch_critic_tail_grad_ragged(const float* scores, const float* lin_w, const float* gscale, float* gp, float* dp4, const CrgClip* clips,
+                                    int n_clips, int T4max, hipStream_t s);
+void launch_critic_dp_max_rows(const float* dy, const float* y, float* dp, unsigned* mx, const CrgRow* rows, int R, size_t n_row, hipStream_t s);
+void launch_critic_dx_h2_ragged(const float* dp, const void* image, float* dx, const unsigned* mx, int* range_flag, const CgdPlan& g, int x_order,
+                                const CrgRow* rows, hipStream_t s);
 
 // The critic's input (bsrnn_critic_spectrum; stft4096.hip, the definition and the slab rule: critic_spectrum_host.h): the 4096-point
 // analysis of slab q of a call - rows [r0, r1) x frames [t0, t1) of wave (rows `stride` floats apart, n samples each, T frames) - as

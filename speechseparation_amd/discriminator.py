@@ -11,6 +11,8 @@ the first layer on the fp16x2 matrix path (fp32 in and out, range guard, exact r
 critic as a separator's training loop uses it, under no_grad.  `commit(grad=True)` gives that object its gradient as well:
 `score_grad` returns the score and d score / d x from one call (`bsrnn_critic_score_grad`, the first layer's dx on the fp16x2 matrix
 path, no dW anywhere), and `score_fixed` wraps it for autograd - the adversarial term of `train.train_loss`.
+`score_ragged`, `score_grad_ragged` and `score_fixed_ragged` do the same for every clip of a padded batch in one call
+(`bsrnn_critic_score_ragged` / `_score_grad_ragged`) - the critic term of `train.train_loss_ragged`.
 
 `critic_spectrum` forms the critic's input as the reference's train-discriminator.py:62-68 does - the 4096-point analysis, real parts
 then imaginary parts, 4098 channels - with the library's `bsrnn_critic_spectrum`.
@@ -108,6 +110,55 @@ class _CommittedScoreFunction(torch.autograd.Function):
     def backward(ctx, g):
         (dx,) = ctx.saved_tensors
         return dx * g.reshape(()), None, None
+
+
+class _CommittedScoreRaggedFunction(torch.autograd.Function):
+    """scores [n_clips] = cc on a padded batch with the gradient kept from the same library call: backward returns dx scaled per clip by
+    grad_output[c]."""
+
+    @staticmethod
+    def forward(ctx, x, cc, frames, clip_rows, interleaved):
+        scores, dx = cc.score_grad_ragged(x, frames, clip_rows, interleaved=interleaved)
+        ctx.save_for_backward(dx)
+        ctx.rows = [1] * len(frames) if clip_rows is None else [int(r) for r in clip_rows]
+        return scores
+
+    @staticmethod
+    def backward(ctx, g):
+        (dx,) = ctx.saved_tensors
+        per_row = torch.repeat_interleave(g.reshape(-1).to(torch.float32), torch.tensor(ctx.rows, device=g.device))
+        return dx * per_row.reshape(-1, 1, 1), None, None, None, None
+
+
+def ragged_layout(in_channels, R, Tmax, frames, clip_rows=None):
+    """bsrnn_critic_ragged_layout as a dict: the frames behind the four layers at Tmax, the K slabs of the first layer, its frame tiles
+    per row and the live ones over all rows, the dx kernel's position tiles likewise, the workspace in floats of a score, of a score
+    with its gradient and with the exact chain's planar copies, the bytes of the call's two tables."""
+    fr = [int(t) for t in frames]
+    rows = [1] * len(fr) if clip_rows is None else [int(r) for r in clip_rows]
+    out = (ctypes.c_int64 * 14)()
+    _native.check(_lib.bsrnn_critic_ragged_layout(in_channels, R, Tmax, (ctypes.c_int32 * len(fr))(*fr), (ctypes.c_int32 * len(rows))(*rows),
+                                                  len(fr), out))
+    v = list(out)
+    return dict(frames=v[0:4], slabs=v[4], ch_per_slab=v[5], t_tiles=v[6], live_t_tiles=v[7], s_tiles=v[8], live_s_tiles=v[9],
+                ws_score_floats=v[10], ws_floats=v[11], ws_exact_floats=v[12], table_bytes=v[13])
+
+
+def layer1_dx_ragged(cc, dp, Tmax, frames, clip_rows=None, interleaved=False):
+    """The first layer's dx alone on a padded batch (bsrnn_critic_layer1_dx_ragged; test and measurement support): dp
+    [R, 1024, frames_out(Tmax)], zeros behind each row's own length -> dx [R, in_channels, Tmax], the scale formed per clip."""
+    cc._open(grad=True)
+    if not isinstance(dp, torch.Tensor) or dp.dim() != 3 or tuple(dp.shape[1:]) != (WIDTHS[0], frames_out(Tmax)):
+        raise ValueError("layer1_dx_ragged: expected dp [R, %d, %d], got %s" % (WIDTHS[0], frames_out(Tmax), tuple(getattr(dp, "shape", ()))))
+    if dp.device != cc.device:
+        raise ValueError("layer1_dx_ragged: dp must be on %s" % (cc.device,))
+    dp = _f32c(dp)
+    R = dp.shape[0]
+    fr, rows = cc._clips("layer1_dx_ragged", frames, clip_rows, R, Tmax)
+    with torch.cuda.device(cc.device):
+        dx = torch.empty((R, cc.in_channels, Tmax), device=cc.device)
+        _native.check(_lib.bsrnn_critic_layer1_dx_ragged(cc._h, _p(dp), R, Tmax, fr, rows, len(fr), int(bool(interleaved)), _p(dx), _s(cc.device)))
+    return dx
 
 
 def layer1_dx(cc, dp, T, interleaved=False):
@@ -219,6 +270,76 @@ class CommittedCritic:
         dx - it is formed while the activations stand in the shared workspace - and backward returns dx * grad_output."""
         self._open(grad=True)
         return _CommittedScoreFunction.apply(x, self, bool(interleaved))
+
+    def _clips(self, who, frames, clip_rows, R, Tmax):
+        """(frames, rows per clip) as int32 arrays, or ValueError for what the library refuses by clip."""
+        try:
+            fr = [int(t) for t in frames]
+            rows = [1] * len(fr) if clip_rows is None else [int(r) for r in clip_rows]
+        except TypeError:
+            raise ValueError("CommittedCritic.%s: frames and clip_rows must be sequences of ints" % who) from None
+        if not fr or len(rows) != len(fr):
+            raise ValueError("CommittedCritic.%s: %d frame counts and %d row counts, need one of each per clip and at least one clip" % (
+                who, len(fr), len(rows)))
+        for c, (t, n) in enumerate(zip(fr, rows)):
+            if n < 1:
+                raise ValueError("CommittedCritic.%s: clip %d has %d rows, need at least 1" % (who, c, n))
+            if not MIN_FRAMES <= t <= Tmax:
+                raise ValueError("CommittedCritic.%s: clip %d has %d frames, need %d <= frames <= %d (the four layers need %d)" % (
+                    who, c, t, MIN_FRAMES, Tmax, MIN_FRAMES))
+        if sum(rows) != R:
+            raise ValueError("CommittedCritic.%s: the clips own %d rows, the batch has %d" % (who, sum(rows), R))
+        return (ctypes.c_int32 * len(fr))(*fr), (ctypes.c_int32 * len(rows))(*rows)
+
+    def _checked_ragged(self, who, x):
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise ValueError("CommittedCritic.%s: expected x [R, %d, Tmax], got %s" % (who, self.in_channels, tuple(getattr(x, "shape", ()))))
+        if x.device != self.device:
+            raise ValueError("CommittedCritic.%s: x must be on %s, the committed critic's device (there is no CPU fallback)" % (who, self.device))
+        return _f32c(x)
+
+    def score_ragged(self, x, frames, clip_rows=None, interleaved=False, return_y1=False):
+        """One score per clip of a padded batch, in ONE library call (bsrnn_critic_score_ragged): x [R, in_channels, Tmax] on the device;
+        clip c owns clip_rows[c] consecutive rows (None: one row per clip) of frames[c] frames each, 601 <= frames[c] <= Tmax; what lies
+        behind a row's frames is never read.  -> scores [n_clips] (no graph): for every clip what `score` gives for it alone, up to the
+        order of the first layer's sums.  return_y1: also the first layer's output [R, 1024, frames_out(Tmax)], valid below each row's
+        own length (test and measurement support)."""
+        self._open()
+        x = self._checked_ragged("score_ragged", x)
+        R, _, Tmax = x.shape
+        fr, rows = self._clips("score_ragged", frames, clip_rows, R, Tmax)
+        with torch.cuda.device(self.device):
+            out = torch.empty((len(fr),), device=self.device)
+            y1 = torch.empty((R, WIDTHS[0], frames_out(Tmax)), device=self.device) if return_y1 else None
+            _native.check(_lib.bsrnn_critic_score_ragged(self._h, _p(x), R, Tmax, fr, rows, len(fr), int(bool(interleaved)), _p(out), _p(y1),
+                                                         _s(self.device)))
+        return (out, y1) if return_y1 else out
+
+    def score_grad_ragged(self, x, frames, clip_rows=None, interleaved=False, gscale=None):
+        """x, frames, clip_rows as for `score_ragged` -> (scores [n_clips], dx [R, in_channels, Tmax]) from ONE library call: the bits
+        `score_ragged` gives, and gscale[c] * d score_c / d x in the rows of clip c, in x's own layout, zeros behind a row's frames.
+        gscale: None (1) or a float tensor [n_clips] on the device.  Neither carries a graph.  Needs commit(grad=True)."""
+        self._open(grad=True)
+        x = self._checked_ragged("score_grad_ragged", x)
+        R, _, Tmax = x.shape
+        fr, rows = self._clips("score_grad_ragged", frames, clip_rows, R, Tmax)
+        if gscale is not None:
+            if not isinstance(gscale, torch.Tensor) or gscale.numel() != len(fr) or gscale.device != self.device:
+                raise ValueError("CommittedCritic.score_grad_ragged: gscale must be a tensor of %d values on %s" % (len(fr), self.device))
+            gscale = _f32c(gscale.detach().reshape(-1))
+        with torch.cuda.device(self.device):
+            out = torch.empty((len(fr),), device=self.device)
+            dx = torch.empty_like(x)
+            _native.check(_lib.bsrnn_critic_score_grad_ragged(self._h, _p(x.detach()), R, Tmax, fr, rows, len(fr), int(bool(interleaved)),
+                                                              _p(gscale), _p(out), _p(dx), _s(self.device)))
+        return out, dx
+
+    def score_fixed_ragged(self, x, frames, clip_rows=None, interleaved=False):
+        """The scores [n_clips] with a graph into x and nowhere else: forward makes the one `score_grad_ragged` call and keeps dx,
+        backward returns dx scaled per clip by grad_output[c]."""
+        self._open(grad=True)
+        return _CommittedScoreRaggedFunction.apply(x, self, [int(t) for t in frames], None if clip_rows is None else [int(r) for r in clip_rows],
+                                                   bool(interleaved))
 
     def close(self):
         """Free the snapshot and the image (idempotent)."""

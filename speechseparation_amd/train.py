@@ -475,18 +475,50 @@ def train_loss_ragged(model, mix, speech, lengths, clip_rows=None):
     (None: one row per clip) of lengths[c] samples each, 1024 < lengths[c] <= n_max.  Returns (losses [n_clips], sdrs [n_clips], x_time
     [R, (Tmax-1)*1024]): per clip what `train_loss` and `sdr` give for it alone, float32 with the graph attached, so
     losses.sum().backward() leaves the sum of the per-clip gradients (the reference's accumulation, train.py:97-115) in one backward pass.
-    The model runs on all R * Tmax frame rows: batch clips of similar length (train_backward_many does)."""
+    The model runs on all R * Tmax frame rows: batch clips of similar length (train_backward_many does).
+    `train_loss_ragged_critic` is the same pass with a critic's score in every clip's loss."""
+    return train_loss_ragged_critic(model, mix, speech, lengths, clip_rows)
+
+
+def train_loss_ragged_critic(model, mix, speech, lengths, clip_rows=None, discriminator=None, adversarial=False):
+    """`train_loss_ragged` with the critic's term (its own function: the signatures of train_loss_ragged, train_backward_many and
+    train_step_packed are held fixed by tests/test_train_ragged_host.py and tests/test_remix_host.py; with discriminator=None this IS
+    train_loss_ragged, bit for bit).
+    discriminator: a CommittedCritic (Discriminator(2050).commit()) whose score of clip c's output is added to losses[c], all clips in ONE
+    library call on the model's interleaved spectrum as it lies (CommittedCritic.score_ragged) - a constant, the gradients are those of
+    discriminator=None bit for bit.  adversarial=True lets the gradient flow through the critic into the model instead
+    (CommittedCritic.score_fixed_ragged; needs commit(grad=True)).  Either way every clip needs 601 frames (614400 samples)."""
     if (not isinstance(mix, torch.Tensor) or not isinstance(speech, torch.Tensor) or mix.dim() != 2 or tuple(mix.shape) != tuple(speech.shape)):
         raise ValueError("train_loss_ragged: expected mix and speech [R, n_max] of the same shape")
     R, n_max = mix.shape
     lens, rows, row_lens = _row_lengths("train_loss_ragged", lengths, clip_rows, R, n_max)
     _need_cuda(mix, "train_loss_ragged")
     _need_cuda(speech, "train_loss_ragged")
+    if discriminator is not None:
+        from .discriminator import MIN_FRAMES, CommittedCritic
+        if not isinstance(discriminator, CommittedCritic):
+            raise ValueError("train_loss_ragged_critic: the discriminator of a ragged batch must be a CommittedCritic (Discriminator.commit()) or None, "
+                             "got %s" % type(discriminator).__name__)
+        if adversarial and not discriminator.has_grad:
+            raise ValueError("train_loss_ragged_critic: adversarial=True needs the critic's dx: pass a "
+                             "CommittedCritic made by commit(grad=True), not a plain CommittedCritic")
+        for c, n in enumerate(lens):
+            if 1 + n // 1024 < MIN_FRAMES:
+                raise ValueError("train_loss_ragged_critic: clip %d has %d frames (%d samples), the critic's four layers need at least %d (%d samples)" % (
+                    c, 1 + n // 1024, n, MIN_FRAMES, (MIN_FRAMES - 1) * 1024))
+    elif adversarial:
+        raise ValueError("train_loss_ragged_critic: adversarial=True needs a discriminator")
     x = stft_ragged(mix, row_lens)
     y = forward_train(model, x)
     x_time = IstftRaggedFunction.apply(y, row_lens)
     s = stft_ragged(speech, row_lens)
     losses, sdrs = TriLossRaggedFunction.apply(y, s, x_time, speech, lens, rows)
+    if discriminator is not None:
+        frames = [1 + n // 1024 for n in lens]
+        if adversarial:
+            losses = losses + discriminator.score_fixed_ragged(y, frames, rows, interleaved=True)
+        else:
+            losses = losses + discriminator.score_ragged(y.detach(), frames, rows, interleaved=True)
     return losses, sdrs, x_time
 
 
@@ -508,7 +540,14 @@ def train_backward_many(model, pairs, loss_sdr=False, max_rows=64, max_padding=0
     (or [n]), both of a pair cut to their common length.  `spec.ragged_buckets` groups the pairs as `evaluate_many` does; each bucket is
     packed into two [rows, n_max] buffers and runs ONE `train_loss_ragged` and ONE backward() of losses.sum() (of -sdrs.sum() with
     loss_sdr): the gradients accumulate in .grad across buckets, as the reference's clip-by-clip loop leaves them.  Returns the per-pair
-    (loss, sdr) floats in input order, read back once per bucket after its backward is queued."""
+    (loss, sdr) floats in input order, read back once per bucket after its backward is queued.  `train_backward_many_critic` is the
+    same with a critic's score in every clip's loss."""
+    return train_backward_many_critic(model, pairs, None, False, loss_sdr=loss_sdr, max_rows=max_rows, max_padding=max_padding)
+
+
+def train_backward_many_critic(model, pairs, discriminator, adversarial=False, loss_sdr=False, max_rows=64, max_padding=0.25):
+    """`train_backward_many` with discriminator and adversarial handed to `train_loss_ragged_critic` for every bucket (None: the plain
+    pass)."""
     from . import spec as _spec
     pairs = list(pairs)
     shapes = _pair_shapes(pairs, "train_backward_many")
@@ -526,7 +565,10 @@ def train_backward_many(model, pairs, loss_sdr=False, max_rows=64, max_padding=0
             for k in range(2):
                 bufs[k, r0:r0 + ch, :n] = pairs[i][k].detach().reshape(ch, -1)[:, :n].to(device=dev, dtype=torch.float32)
             r0 += ch
-        losses, sdrs, _ = train_loss_ragged(model, bufs[0], bufs[1], lens, rows)
+        if discriminator is None and not adversarial:
+            losses, sdrs, _ = train_loss_ragged(model, bufs[0], bufs[1], lens, rows)
+        else:
+            losses, sdrs, _ = train_loss_ragged_critic(model, bufs[0], bufs[1], lens, rows, discriminator=discriminator, adversarial=adversarial)
         (-sdrs.sum() if loss_sdr else losses.sum()).backward()
         vals = torch.stack([losses.detach(), sdrs.detach()], 1).cpu().tolist()
         for i, v in zip(bucket, vals):
@@ -534,11 +576,11 @@ def train_backward_many(model, pairs, loss_sdr=False, max_rows=64, max_padding=0
     return results
 
 
-def train_step_many(model, optimizer, pairs, group=None, loss_sdr=False, max_rows=64, max_padding=0.25):
+def train_step_many(model, optimizer, pairs, group=None, loss_sdr=False, max_rows=64, max_padding=0.25, discriminator=None, adversarial=False):
     """One optimizer step over the clips in `pairs` (the reference's --batch_size accumulation, train.py:97-115): train_backward_many,
     the gradients averaged over the ranks of `group` when one is given (dist.all_reduce_gradients), optimizer.step(), zero_grad().
-    Returns train_backward_many's per-pair (loss, sdr)."""
-    out = train_backward_many(model, pairs, loss_sdr=loss_sdr, max_rows=max_rows, max_padding=max_padding)
+    Returns train_backward_many's per-pair (loss, sdr).  discriminator, adversarial: as for `train_loss_ragged_critic`."""
+    out = train_backward_many_critic(model, pairs, discriminator, adversarial, loss_sdr=loss_sdr, max_rows=max_rows, max_padding=max_padding)
     if group is not None:
         from .dist import all_reduce_gradients
         all_reduce_gradients(model.parameters(), group=group)
@@ -551,8 +593,16 @@ def train_step_packed(model, optimizer, mix, speech, lengths, clip_rows, group=N
     """`train_step_many`'s tail on buffers that are packed already - what augment.remix_many returns: ONE `train_loss_ragged` on
     mix, speech [R, n_max] (clip c owns clip_rows[c] consecutive rows of lengths[c] samples), ONE backward() of losses.sum() (of
     -sdrs.sum() with loss_sdr), the gradients averaged over `group` when one is given, optimizer.step(), zero_grad().  Returns the
-    per-clip (loss, sdr) floats."""
-    losses, sdrs, _ = train_loss_ragged(model, mix, speech, lengths, clip_rows)
+    per-clip (loss, sdr) floats.  `train_step_packed_critic` is the same step with a critic's score in every clip's loss."""
+    return train_step_packed_critic(model, optimizer, mix, speech, lengths, clip_rows, None, False, group=group, loss_sdr=loss_sdr)
+
+
+def train_step_packed_critic(model, optimizer, mix, speech, lengths, clip_rows, discriminator, adversarial=False, group=None, loss_sdr=False):
+    """`train_step_packed` with discriminator and adversarial handed to `train_loss_ragged_critic` (None: the plain step)."""
+    if discriminator is None and not adversarial:
+        losses, sdrs, _ = train_loss_ragged(model, mix, speech, lengths, clip_rows)
+    else:
+        losses, sdrs, _ = train_loss_ragged_critic(model, mix, speech, lengths, clip_rows, discriminator=discriminator, adversarial=adversarial)
     (-sdrs.sum() if loss_sdr else losses.sum()).backward()
     vals = torch.stack([losses.detach(), sdrs.detach()], 1).cpu().tolist()
     if group is not None:

@@ -22,6 +22,15 @@ layer's dx alone on both paths (bsrnn_critic_layer1_dx; bsrnn_critic_conv_backwa
 `--score`.  The last line of every shape says whether score_grad is faster than the path it replaces by more than both spreads together.
 
     python tools/critic_bench.py --grad > profiles/critic_grad_bench.txt
+
+`--ragged` times the committed critic on a padded batch (bsrnn_critic_score_grad_ragged / _score_ragged: one call for all clips) at 2050
+channels, interleaved order, 32 stereo clips with lengths spread evenly over 601 .. 793 frames and the same batch at 2154 frames (50 s
+items, all equal), beside the only route without it, run in the same session: per clip a contiguous copy of the clip's rows and
+score_grad / score, looped.  Same method as `--score`.  The last line of every shape says whether the one-call form is slower than the
+loop by more than both spreads together.  Then the step time of train_step_packed on the first batch with and without the adversarial
+term.
+
+    python tools/critic_bench.py --ragged > profiles/critic_ragged_bench.txt
 """
 import argparse
 import ctypes
@@ -156,6 +165,66 @@ def grad_bench(args, dev, lib, ctx, p):
         torch.cuda.empty_cache()
 
 
+def ragged_bench(args, dev, lib, ctx, p):
+    from speechseparation_amd.bsrnn import BSRNN
+    from speechseparation_amd.discriminator import ragged_layout
+    print("critic_bench --ragged: %s; %d medians of %d runs after %d warm-up runs each: median of the medians (lowest .. highest), ms" % (
+        torch.cuda.get_device_name(0), args.rounds, args.reps, args.warmup))
+    ch, clips = 2050, 32
+    D = Discriminator(ch).to(dev)
+    cc = D.commit(grad=True)
+    spread = [601 + (793 - 601) * c // (clips - 1) for c in range(clips)]
+    for name, frames in (("32 stereo clips, 601 .. 793 frames", spread), ("32 stereo clips, 2154 frames each", [2154] * clips)):
+        rows, Tmax, R = [2] * clips, max(frames), 2 * clips
+        y = torch.randn(R, ch, Tmax, device=dev)                        # the separator's interleaved spectrum
+        for c, t in enumerate(frames):
+            y[2 * c:2 * c + 2, :, t:] = 0
+        lay = ragged_layout(ch, R, Tmax, frames, rows)
+        print("\n%s: R = %d, Tmax = %d; first layer %d K slabs, live frame tiles %d of %d, live position tiles %d of %d; workspace %.0f MB" % (
+            name, R, Tmax, lay["slabs"], lay["live_t_tiles"], R * lay["t_tiles"], lay["live_s_tiles"], R * lay["s_tiles"], lay["ws_floats"] * 4e-6))
+
+        def loop_grad():
+            for c, t in enumerate(frames):
+                cc.score_grad(y[2 * c:2 * c + 2, :, :t].contiguous(), interleaved=True)
+
+        def loop_score():
+            for c, t in enumerate(frames):
+                cc.score(y[2 * c:2 * c + 2, :, :t].contiguous(), interleaved=True)
+        table = [("score_grad_ragged (policy exact)", lambda: cc.score_grad_ragged(y, frames, rows, interleaved=True), _native.RANGE_EXACT),
+                 ("score_grad_ragged (deferred)", lambda: cc.score_grad_ragged(y, frames, rows, interleaved=True), _native.RANGE_DEFERRED),
+                 ("score_ragged (deferred)", lambda: cc.score_ragged(y, frames, rows, interleaved=True), _native.RANGE_DEFERRED),
+                 ("per clip: copy + score_grad (exact)", loop_grad, _native.RANGE_EXACT),
+                 ("per clip: copy + score_grad (deferred)", loop_grad, _native.RANGE_DEFERRED),
+                 ("per clip: copy + score (deferred)", loop_score, _native.RANGE_DEFERRED)]
+        got = {}
+        for label, fn, policy in table:
+            native_policy(lib, ctx, policy)()
+            got[label] = rounds_of(fn, args.warmup, args.reps, args.rounds)
+            native_policy(lib, ctx, _native.RANGE_EXACT)()
+            print("  %-40s %8.3f (%.3f .. %.3f)" % ((label,) + got[label]))
+        for new, old in (("score_grad_ragged (policy exact)", "per clip: copy + score_grad (exact)"),
+                         ("score_grad_ragged (deferred)", "per clip: copy + score_grad (deferred)"),
+                         ("score_ragged (deferred)", "per clip: copy + score (deferred)")):
+            a, b = got[new], got[old]
+            spreads = (a[2] - a[1]) + (b[2] - b[1])
+            print("  %s %.3f ms against the loop's %.3f ms: %.2fx; one call is %s than the loop by more than both spreads together (%.3f ms)" % (
+                new, a[0], b[0], b[0] / a[0], "SLOWER" if a[0] - b[0] > spreads else "not slower", spreads))
+        del y
+        torch.cuda.empty_cache()
+    # the packed training step on the first batch, with and without the adversarial term
+    model = BSRNN().to(dev).train()
+    opt = hip_train.AdamW(model.parameters(), lr=0.001, weight_decay=0.01)
+    lens = [(t - 1) * 1024 for t in spread]
+    mix, speech = torch.randn(2 * clips, max(lens), device=dev) * 0.1, torch.randn(2 * clips, max(lens), device=dev) * 0.1
+    print("\ntrain_step_packed, 32 stereo clips of 601 .. 793 frames (one optimizer step, the per-clip read-back included)")
+    for label, kw in (("without a critic", {}), ("with the critic's score as a constant", dict(discriminator=cc)),
+                      ("with the adversarial term", dict(discriminator=cc, adversarial=True))):
+        got = rounds_of(lambda: hip_train.train_step_packed_critic(model, opt, mix, speech, lens, [2] * clips, kw.get("discriminator"),
+                                                                 kw.get("adversarial", False)), args.warmup, args.reps, args.rounds)
+        print("  %-40s %8.3f (%.3f .. %.3f)" % ((label,) + got))
+    cc.close()
+
+
 def native_policy(lib, ctx, policy):
     return lambda: _native.check(lib.bsrnn_set_range_policy(ctx, policy))
 
@@ -165,7 +234,9 @@ def main():
     ap.add_argument("--score", action="store_true", help="time the committed critic (bsrnn_critic_score) instead of the layers")
     ap.add_argument("--grad", action="store_true", help="time the committed critic's score with its gradient (bsrnn_critic_score_grad) beside "
                     "the adversarial path through Discriminator.score_fixed")
-    ap.add_argument("--rounds", type=int, default=5, help="--score, --grad: medians per figure")
+    ap.add_argument("--ragged", action="store_true", help="time the committed critic on a padded batch (bsrnn_critic_score_grad_ragged) beside "
+                    "the per-clip loop it replaces, and train_step_packed with and without the adversarial term")
+    ap.add_argument("--rounds", type=int, default=5, help="--score, --grad, --ragged: medians per figure")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--seconds", type=float, nargs="*", default=[8.0, 60.0])
@@ -178,6 +249,8 @@ def main():
         return score_bench(args, dev, lib, ctx, p)
     if args.grad:
         return grad_bench(args, dev, lib, ctx, p)
+    if args.ragged:
+        return ragged_bench(args, dev, lib, ctx, p)
     print("critic_bench: %s, medians of %d after %d warm-up runs; ms (TF of the product) | floor at %.0f TF" % (
         torch.cuda.get_device_name(0), args.reps, args.warmup, F32_MATRIX_TF))
     for ch in args.channels:

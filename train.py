@@ -23,6 +23,10 @@ one augment.SourceShelf on the device at start; an epoch is len(dialogs) items; 
 them on the item's index (augment.remix_draw), mixed by ONE launch into the padded buffers of the ragged step (augment.remix_many) and
 trained on in one backward pass (train_step_packed).  --remix_seconds / --remix_backgrounds: the reference's 50 and 4.  Validation still
 reads --datapath's val split, when there is one.  Refused with --rir or --graph.  Without --remix nothing changes.
+--batch_critic PATH [--adversarial] (with --ragged or --remix) adds a frozen Discriminator(2050)'s score to every clip's loss of the
+ragged and packed steps - one library call scores all clips of the padded batch, each over its own frames
+(speechseparation_amd.train.train_loss_ragged_critic, CommittedCritic.score_ragged / score_fixed_ragged); every clip needs 601 frames.
+--critic PATH stays the per-clip step's option and is still refused with --ragged, --remix and --graph.
 Not carried over: wandb logging, the discriminator argument (the reference's loop passes None; `speechseparation_amd.train.train_loss`
 takes a `Discriminator`, and `train-discriminator.py` trains one), ReduceLROnPlateau (commented out in the reference loop; the rule is
 `speechseparation_amd.train.ReduceLROnPlateau`) and its batch-size growth heuristic.  Under `torchrun` (one process per GPU) the clips are split over the ranks
@@ -160,11 +164,16 @@ def build_parser():
                     "(clips need 601 frames)")
     ap.add_argument("--adversarial", action="store_true", default=argparse.SUPPRESS, help="with --critic: let the gradient flow through the frozen critic into the model "
                     "(score and dx from one library call, CommittedCritic.score_fixed)")
+    ap.add_argument("--batch_critic", type=str, default=argparse.SUPPRESS, metavar="PATH", help="with --ragged or --remix: state dict of a "
+                    "Discriminator(2050), committed once; every clip of a step gets its own score added to its loss, all clips in one library "
+                    "call (CommittedCritic.score_ragged; with --adversarial score_fixed_ragged).  Clips need 601 frames")
     return ap
 
 
 CRITIC_REFUSAL = ("--critic does not go with --graph, --ragged or --remix: the critic's term is part of the per-clip step only "
                   "(no graph capture of it, no ragged or packed step with a critic)")
+BATCH_CRITIC_REFUSAL = ("--batch_critic goes with --ragged or --remix only, and not with --graph or --critic: it is the critic's term of the "
+                        "ragged and packed steps (--critic is the per-clip step's)")
 REMIX_REFUSAL = "--remix does not go with --rir or --graph: the reference's MixDataSet has no reverberation, and the items of a step are a ragged batch"
 
 
@@ -178,8 +187,11 @@ def parse_args(ap, argv=None):
     critic, adversarial = getattr(args, "critic", None), getattr(args, "adversarial", False)
     if critic and (args.graph or args.ragged or args.remix):
         ap.error(CRITIC_REFUSAL)
-    if adversarial and not critic:
-        ap.error("--adversarial needs --critic PATH")
+    batch_critic = getattr(args, "batch_critic", None)
+    if batch_critic and (critic or args.graph or not (args.ragged or args.remix)):
+        ap.error(BATCH_CRITIC_REFUSAL)
+    if adversarial and not critic and not batch_critic:
+        ap.error("--adversarial needs --critic PATH (or --batch_critic PATH with --ragged or --remix)")
     return args
 
 
@@ -232,10 +244,11 @@ def main(argv=None):
         optimizer.load_state_dict(torch.load(os.path.join(args.outdir, "optimizer.pth"), weights_only=True))
 
     critic, adversarial = None, getattr(args, "adversarial", False)
-    if getattr(args, "critic", None):
+    critic_path = getattr(args, "critic", None) or getattr(args, "batch_critic", None)      # (never both: parse_args)
+    if critic_path:
         from speechseparation_amd.discriminator import Discriminator
         D = Discriminator(2050)
-        D.load_state_dict(torch.load(args.critic, weights_only=True), strict=True)
+        D.load_state_dict(torch.load(critic_path, weights_only=True), strict=True)
         critic = D.to(device).commit(grad=adversarial)      # a snapshot: the module goes, the object stays for the run
         del D
 
@@ -261,8 +274,8 @@ def main(argv=None):
             for b0 in range(0, len(order), args.batch_size):
                 specs = [augment.remix_draw(train_set[i], shelf, remix_length, args.remix_backgrounds) for i in order[b0:b0 + args.batch_size]]
                 mix, speech, lengths, clip_rows = augment.remix_many(shelf, specs, remix_length)
-                for loss, sdr in hip_train.train_step_packed(model, optimizer, mix, speech, lengths, clip_rows,
-                                                             group=dist.group.WORLD if world > 1 else None, loss_sdr=args.loss_sdr):
+                for loss, sdr in hip_train.train_step_packed_critic(model, optimizer, mix, speech, lengths, clip_rows, critic, adversarial,
+                                                                    group=dist.group.WORLD if world > 1 else None, loss_sdr=args.loss_sdr):
                     batch_i += 1
                     epoch_loss += loss
                     epoch_sdr += sdr
@@ -274,7 +287,7 @@ def main(argv=None):
                 if reverb:
                     reverb(order[b0:b0 + args.batch_size], [mix for mix, _ in pairs])
                 for loss, sdr in hip_train.train_step_many(model, optimizer, pairs, group=dist.group.WORLD if world > 1 else None,
-                                                           loss_sdr=args.loss_sdr):
+                                                           loss_sdr=args.loss_sdr, discriminator=critic, adversarial=adversarial):
                     batch_i += 1
                     epoch_loss += loss
                     epoch_sdr += sdr
